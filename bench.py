@@ -2,6 +2,7 @@
 """Headline benchmark: ICP iterations/sec of scan-to-map registration on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4|tiny] [--mode strong|weak|replicas]
+                  [--dump-outputs DIR]
 
 A "step" is ONE registration of the synthetic scan against the synthetic map with exactly ITERS (=20) Gauss-Newton
 iterations of the reference's chain (param/icp.yaml: knn 1, maxDist 0.5, TrimmedDist 0.9, SurfaceNormal 1.57,
@@ -77,6 +78,43 @@ def cpu_baseline(sc, threads, legs=("omp", "1t")):
         if name == "omp":
             T_omp = T
     return out, T_omp
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+# What reg_register / reg_dist_register hand back besides the pose: RegResult fields that are results of the computation.
+# Timings (loop_ms, target_build_ms, source_prep_ms, prof_*) and statistics of how the loop ran (band stalls, tail launches
+# and iterations) are left out: they differ from run to run or between builds that compute the same thing.  `error` is an fp64
+# sum whose reduction order is not fixed: its last bits can differ between two runs (measured: 4e-15 of 14.05 at C3).
+RESULT_FIELDS = ("iterations", "converged", "max_iter_reached", "rank_last", "n_inliers", "n_matched", "error", "fitness",
+                 "inlier_rmse", "H_last", "b_last", "T_iter_last", "T_iter_prev", "n_constraints", "localizable",
+                 "xicp_combined", "xicp_high", "rotation_corrected")
+COLUMN_MAJOR_4X4 = ("T_iter_last", "T_iter_prev")
+
+
+def step_outputs(T, res):
+    """The arrays a caller of the timed step receives: the pose and the result fields above, as float32 / float64.
+    4x4 transforms in math layout (the ABI stores them column-major), H_last as 6x6."""
+    out = {"pose": np.asarray(T, dtype=np.float32).reshape(4, 4)}
+    for name in RESULT_FIELDS:
+        v = getattr(res, name)
+        a = np.array(v[:] if hasattr(v, "__len__") else v, dtype=np.float64)   # exact for the int32 / int64 / float fields
+        if name in COLUMN_MAJOR_4X4:
+            a = a.reshape(4, 4).T.copy()
+        elif name == "H_last":
+            a = a.reshape(6, 6)
+        out[name] = a
+    return out
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 only, DUMP_LIMIT_BYTES in all)."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def cpu_model():
@@ -288,6 +326,10 @@ def run_replicas(args, torch, capi, synth, dist, dev, rank, local_rank, world):
             "note": "total work (the 64-registration batch) is fixed as N grows: per-GPU efficiency = value(N) / (N * value(1))",
         }
         print(json.dumps(line), flush=True)
+    if rank == 0 and args.dump_outputs:
+        # this rank's share of the batch, as its last timed pass left it (registration i of the batch = seed + 100 + i)
+        dump_outputs(args.dump_outputs, {"poses": np.stack(timed).astype(np.float32),
+                                         "registration_ids": np.array(mine, dtype=np.float64)})
     if not ok:
         raise SystemExit(f"replicas: a timed pose differs from its single-stream registration by {dmax}")
 
@@ -309,7 +351,12 @@ def main():
     ap.add_argument("--streams", type=int, default=8,
                     help="secondary measurement (config 5 analogue): S independent C2 registrations in flight, one handle "
                          "+ HIP stream + host thread each; reported under \"batched\", never as `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pose and result fields; "
+                         "--mode replicas: the poses of the batch) as DIR/<name>.npy; same arguments, same inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -417,6 +464,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     T_final, res_final = out[0], out[1]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, step_outputs(T_final, res_final))
 
     # ---- kernel-level numbers (outside the timed region) ----
     kern = {}
