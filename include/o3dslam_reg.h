@@ -56,7 +56,29 @@ typedef enum {
 
 typedef enum {
     REG_COST_P2PL = 0, /* PointToPlaneErrorMinimizer   ICP.cpp:1512-1566 + ErrorMinimizers/PointToPlane.cpp:274-400 */
-    REG_COST_GICP = 1  /* plane-to-plane GICP factor (north star; arithmetic not in the reference tree) */
+    REG_COST_GICP = 1, /* plane-to-plane GICP factor (north star; arithmetic not in the reference tree) */
+    /* The two other operators of o3d_slam::cloudRegistrationFactory (open3d_slam/src/CloudRegistration.cpp:54-119; config
+       strings PointToPlaneIcp / PointToPointIcp, parameter_structure_definitions.lua:77,112):
+       REG_COST_O3D_P2PL  open3d::pipelines::registration::RegistrationICP with TransformationEstimationPointToPlane and
+                          the L2 loss (RegistrationIcpPointToPlane): per pair r = (p - q).n, J = [p x n, n] with p the
+                          transformed reading point, q / n the matched reference point / normal; the update solves
+                          J^T J x = -J^T r (fp64) and is x -> Rz(x2) Ry(x1) Rx(x0), t = x3..5 (TransformVector6dToMatrix4d).
+       REG_COST_O3D_P2P   RegistrationICP with TransformationEstimationPointToPoint(with_scaling = false)
+                          (RegistrationIcpPointToPoint): the update is Umeyama's closed form without scaling,
+                          S = cov(q, p) = U D V^T, R = U diag(1, 1, sign(det U det V)) V^T, t = mean(q) - R mean(p).
+       Rules of both: the input frame (no centring, as GICP); the update is LEFT-multiplied, T <- U T, in fp64; the loop
+       always stops by Open3D's ICPConvergenceCriteria exactly as gicp_stop_rule = 1 does (evaluate, update, evaluate
+       again; the last evaluation is reported), with gicp_rel_fitness / gicp_rel_rmse -- gicp_stop_rule itself is
+       ignored; fixed_iters > 0 runs that many updates as for GICP.  A pair is a match when d^2 <= max_dist^2.
+       Inputs: O3D_P2PL needs reference normals (reg_set_target: REG_MISSING_FIELD without), O3D_P2P only xyz; neither
+       reads reading normals or covariances.  The outlier-filter flags are ignored; use_xicp is REG_BAD_ARGUMENT.
+       reg_result: error = sum r^2 (O3D_P2PL) / sum |T p - q|^2 (O3D_P2P); H_last / b_last = J^T J / J^T r (O3D_P2PL),
+       zero (O3D_P2P); rank_last = rank of the 6x6 system (O3D_P2PL) / of the 3x3 cross-covariance (O3D_P2P).
+       reg_linearize returns J^T J / J^T r for O3D_P2PL and REG_UNSUPPORTED for O3D_P2P (Umeyama has no normal
+       equations); the distributed entry points (reg_dist_*, reg_match_local, reg_reduce_local, reg_solve_update, ...)
+       return REG_UNSUPPORTED for both.  Open3D 0.15.1 is an un-vendored dependency: restated, PARITY UNPINNED. */
+    REG_COST_O3D_P2PL = 2,
+    REG_COST_O3D_P2P = 3
 } reg_cost;
 
 /* Configuration == the hot-path subset of param/icp.yaml (open3d_slam_ros/param/icp.yaml:11-27,86-92). */
@@ -118,7 +140,7 @@ typedef struct {
     int32_t rank_last;          /* numerical rank of the last 6x6 system (6 = invertible) */
     int64_t n_inliers;          /* pairs with non-zero weight in the last iteration */
     int64_t n_matched;          /* pairs with a neighbour inside max_dist in the last iteration */
-    double  error;              /* P2PL: sum w r^2;  GICP: sum 0.5 r^T M r  (last iteration) */
+    double  error;              /* P2PL: sum w r^2;  GICP: sum 0.5 r^T M r;  O3D_*: see reg_cost  (last iteration) */
     double  fitness;            /* n_inliers / N   (open3d RegistrationResult::fitness_ analogue) */
     double  inlier_rmse;        /* sqrt(sum_inliers d^2 / n_inliers) */
     float   H_last[36];         /* last normal matrix, row-major (symmetric) */
@@ -162,7 +184,7 @@ REG_API reg_status reg_set_stream(reg_handle* h, void* hip_stream);
 
 /* == ICP::initReference (ICP.cpp:847-898): copy, subtract centroid, build the search structure
    (voxel-bin table replaces KDTreeMatcher::init, MatchersImpl.cpp:78-83).
-   P2PL needs `nrm`; GICP needs `cov`. */
+   P2PL and O3D_P2PL need `nrm`; GICP needs `cov`; O3D_P2P only `xyz`. */
 REG_API reg_status reg_set_target(reg_handle* h, const float* xyz, int64_t xyz_stride, const float* nrm,
                                   int64_t nrm_stride, const float* cov, int64_t m, int on_device);
 
@@ -326,6 +348,13 @@ REG_API void reg_host_x_to_T(const float x[6], float T[16]);
    Returns the rank of the reduced system. */
 REG_API int  reg_host_solve6_xicp(const float A[36], const float b[6], const int32_t flags[6], float x[6]);
 REG_API void reg_host_centroid(const float* xyz, int64_t stride, int64_t n, float out[3]);
+/* Update of the two Open3D costs from the reduced 32-double record of one iteration (the same code the update kernel
+   runs): cost REG_COST_O3D_P2PL -- {0..20: J^T J packed upper triangle, 21..26: J^T r, 27: sum r^2, 28: pairs, 29: pairs,
+   30: sum d^2}; REG_COST_O3D_P2P -- {0..2: sum (p - o), 3..5: sum (q - o), 6..14: sum (q - o)(p - o)^T row-major (row =
+   q component), 15..17: sum o, 27: sum |p - q|^2, 28..30 as above} about an origin o near the data.  T_update: the
+   column-major 4x4 U of T <- U T; *rank (may be NULL) as reg_result.rank_last.  REG_BAD_ARGUMENT for any other cost,
+   REG_NO_CORRESPONDENCES when sums[28] == 0. */
+REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T_update[16], int32_t* rank);
 /* Launch plan of the persistent tail kernel (csrc/kernels_tail.hpp) for a reading of n points on a device with `cus`
    compute units: plan = {usable (0/1), workgroups, workgroups per XCD class, reading points per XCD class}.  Octet
    oc = (s >> 3) * plan[2] + (b >> 3) of XCD class x = b & 7 is, with tile == 0, octet oc of the class's contiguous share

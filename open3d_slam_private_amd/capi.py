@@ -16,6 +16,9 @@ _SO = os.environ.get("O3D_REG_LIB") or os.path.join(_HERE, "lib", "libo3dslam_re
 STATUS_NAMES = {0: "OK", 1: "EMPTY_TARGET", 2: "EMPTY_SOURCE", 3: "NO_CORRESPONDENCES", 4: "BAD_TRANSFORM",
                 5: "NOT_CONFIGURED", 6: "BAD_ARGUMENT", 7: "MISSING_FIELD", 8: "DEVICE_ERROR", 9: "UNSUPPORTED"}
 COST_P2PL, COST_GICP = 0, 1
+# Open3D RegistrationICP with TransformationEstimationPointToPlane / PointToPoint (RegistrationIcpPointToPlane /
+# RegistrationIcpPointToPoint, open3d_slam/src/CloudRegistration.cpp:54-101); see reg_cost in the header
+COST_O3D_P2PL, COST_O3D_P2P = 2, 3
 
 
 class RegError(RuntimeError):
@@ -116,7 +119,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure",
            "reg_dist_get_unique_id", "reg_dist_init", "reg_dist_init_custom", "reg_dist_register", "reg_dist_shutdown",
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
-           "reg_dist_steer_counts", "reg_host_tail_plan"]
+           "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update"]
 
 
 def lib_path() -> str:
@@ -193,6 +196,7 @@ def load_library():
     lib.reg_voxelize_within_volume.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.POINTER(RegCrop), C.c_double, vp, vp, vp,
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
+    lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
     lib.reg_profile_kernels.argtypes = [vp, f32p, C.c_int, f32p]
     lib.reg_source_centroid_sums.argtypes = [vp, vp]
@@ -706,6 +710,18 @@ def host_centroid(xyz):
     out = np.zeros(3, np.float32)
     load_library().reg_host_centroid(_ptr(xyz), xyz.shape[1], xyz.shape[0], _ptr(out))
     return out
+
+
+def host_o3d_update(cost, sums):
+    """Update matrix U (4x4 float64, math layout; T <- U T) and rank of one iteration of an Open3D cost from its reduced
+    32-double record -- the arithmetic of the update kernel, on the host (reg_host_o3d_update)."""
+    s = np.ascontiguousarray(sums, np.float64).reshape(32)
+    U = np.zeros(16, np.float64)
+    rank = C.c_int32()
+    st = load_library().reg_host_o3d_update(int(cost), _ptr(s), _ptr(U), C.byref(rank))
+    if st != 0:
+        raise RegError(st, "reg_host_o3d_update")
+    return U.reshape(4, 4).T.copy(), rank.value
 
 
 def host_tail_plan(n, cus=256, tile=0):

@@ -93,7 +93,7 @@ static reg_status prepare_rowmajor(reg_handle* h, const float* T_init_row, const
         p2pl ? 1 : 0, h->perm, h->s_xyz.as<float4>(), (p2pl && h->has_snrm) ? h->s_nrm.as<float4>() : nullptr,
         h->i_hint.as<uint8_t>(), h->i_hist.as<uint32_t>(), h->i_acc.as<double>(), kAccRows * kSums, si,
         h->i_cache.as<float4>());
-    if (!p2pl)
+    if (h->prm.cost == REG_COST_GICP)
         k_pack_cov<<<grid_for(n), 256, 0, h->stream>>>(h->s_cov_raw.as<float>(), n, h->perm, h->s_cov.as<float4>());
     pmark("prepare_source");
     HIPCHK(h, hipGetLastError());
@@ -264,6 +264,21 @@ static reg_status enqueue_linearize(reg_handle* h, bool want_w, bool limit_from_
             h->i_d2.as<float>(), h->t_pts.as<float4>(), h->t_nrm.as<float4>(), f, h->i_state.as<SelectState>(),
             h->i_hist.as<uint32_t>() + 4096, h->i_hist.as<uint32_t>() + 2048, h->shift0, w,
             h->i_partials.as<double>(), h->i_cache.as<float4>());
+    } else if (cost_is_o3d(h->prm.cost)) {
+        // select-free: no outlier filters, no X-ICP; the update kernel of the Open3D costs
+        const float3 o = make_float3(h->t_mid[0], h->t_mid[1], h->t_mid[2]);
+        if (h->prm.cost == REG_COST_O3D_P2PL)
+            k_linearize_o3d<REG_COST_O3D_P2PL><<<h->n_blocks, 256, 0, h->stream>>>(
+                h->s_xyz.as<float4>(), h->n, it, h->i_pos.as<int>(), h->i_d2.as<float>(), h->t_nrm.as<float4>(), o, w,
+                h->i_partials.as<double>());
+        else
+            k_linearize_o3d<REG_COST_O3D_P2P><<<h->n_blocks, 256, 0, h->stream>>>(
+                h->s_xyz.as<float4>(), h->n, it, h->i_pos.as<int>(), h->i_d2.as<float>(), h->t_pts.as<float4>(), o, w,
+                h->i_partials.as<double>());
+        ++h->seq;
+        k_reduce_update_o3d<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_iter.as<IterState>(),
+                                                       h->d_mirror, h->seq);
+        return REG_OK;
     } else {
         k_linearize_gicp<<<h->n_blocks, 256, 0, h->stream>>>(h->s_xyz.as<float4>(), h->s_cov.as<float4>(), h->n, it,
                                                              h->i_pos.as<int>(), h->i_d2.as<float>(),
@@ -423,7 +438,8 @@ static TailPlan tail_plan(const reg_handle* h) {
 }
 
 static bool tail_eligible(const reg_handle* h) {
-    if (h->prm.cost != REG_COST_P2PL && h->env.no_gicp_tail) return false;
+    if (cost_is_o3d(h->prm.cost)) return false;   // the Open3D costs have no persistent-tail form
+    if (h->prm.cost == REG_COST_GICP && h->env.no_gicp_tail) return false;
     return h->dbg.disable_fused != 1 && !(h->dbg.debug_flags & (16 | 64 | 128)) && h->dbg.lanes_per_point != 4 && !h->env.no_tail &&
            tail_plan(h).ok;
 }
@@ -476,7 +492,7 @@ static reg_status enqueue_tail(reg_handle* h, const TailPlan& pl, int max_iters,
     uint8_t* hint = h->dbg.match_variant == 2 ? nullptr : h->i_hint.as<uint8_t>();
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timed = h->profiling && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    const bool gicp = h->prm.cost != REG_COST_P2PL;
+    const bool gicp = h->prm.cost == REG_COST_GICP;
     auto args = [&](auto launch) {
         // GICP: the covariances of the reading / the reference travel in the two attribute arguments
         const float4* s_attr = gicp ? (const float4*)h->s_cov.as<float4>() : (const float4*)(h->has_snrm ? h->s_nrm.as<float4>() : nullptr);
@@ -550,7 +566,15 @@ static reg_status iterate_once(reg_handle* h, const float* T_row, bool want_w) {
     return REG_OK;
 }
 
-static void sums_to_system(const double* sums, bool p2pl, float* H, float* b) {
+// H_last / b_last: the reduced system as reported.  P2PL: A, b of A x = b (b = -sums); GICP and O3D_P2PL: H, the gradient
+// sums as accumulated (J^T M J / J^T M r, J^T J / J^T r); O3D_P2P has no normal equations: zero.
+static void sums_to_system(const double* sums, int cost, float* H, float* b) {
+    if (cost == REG_COST_O3D_P2P) {
+        std::memset(H, 0, 36 * sizeof(float));
+        std::memset(b, 0, 6 * sizeof(float));
+        return;
+    }
+    const bool p2pl = cost == REG_COST_P2PL;
     int k = 0;
     for (int a = 0; a < 6; ++a)
         for (int c = a; c < 6; ++c) {
@@ -593,7 +617,7 @@ static void fill_result(reg_handle* h, const double* sums, reg_result* res) {
     res->error = sums[27];
     res->fitness = h->n > 0 ? sums[28] / (double)h->n : 0.0;
     res->inlier_rmse = sums[28] > 0 ? std::sqrt(sums[30] / sums[28]) : 0.0;
-    sums_to_system(sums, h->prm.cost == REG_COST_P2PL, res->H_last, res->b_last);
+    sums_to_system(sums, h->prm.cost, res->H_last, res->b_last);
     res->target_build_ms = h->target_build_ms;
     if (h->src_prep_pending && hipEventQuery(h->ev_s1) == hipSuccess) {
         float ms = 0.f;
@@ -626,6 +650,10 @@ reg_status reg_linearize(reg_handle* h, const float T_iter[16], float H[36], flo
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     if (!T_iter) return REG_BAD_ARGUMENT;
+    if (h->prm.cost == REG_COST_O3D_P2P) {
+        h->err = "reg_linearize: point-to-point (Umeyama) has no normal equations";
+        return REG_UNSUPPORTED;
+    }
     float Tr[16];
     col_to_row(T_iter, Tr);
     if (!m4_is_finite(Tr)) return REG_BAD_TRANSFORM;
@@ -633,7 +661,7 @@ reg_status reg_linearize(reg_handle* h, const float T_iter[16], float H[36], flo
     s = iterate_once(h, Tr, true);
     if (s != REG_OK) return s;
     const double* sums = h->h_mirror->sums;
-    if (H && b) sums_to_system(sums, h->prm.cost == REG_COST_P2PL, H, b);
+    if (H && b) sums_to_system(sums, h->prm.cost, H, b);
     if (err) *err = sums[27];
     if (n_inliers) *n_inliers = (int64_t)llround(sums[28]);
     if (sums[28] == 0.0) {
@@ -684,14 +712,16 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
     rmark("ev0");
     const unsigned long long seq0 = h->seq;
     const int fixed = h->prm.fixed_iters;
-    // (GICP stop rule 1 re-evaluates the correspondences once more after the last update: one more sequence)
-    const int limit = fixed > 0 ? fixed : h->prm.max_iter + ((!p2pl && h->prm.gicp_stop_rule == 1) ? 1 : 0);
+    // (Open3D's stop rule -- GICP rule 1, the O3D costs always -- re-evaluates the correspondences once more after the last
+    //  update: one more sequence)
+    const bool o3d_rule = cost_is_o3d(h->prm.cost) || (h->prm.cost == REG_COST_GICP && h->prm.gicp_stop_rule == 1);
+    const int limit = fixed > 0 ? fixed : h->prm.max_iter + (o3d_rule ? 1 : 0);
     // Iterations 0..kGenericFirst-1 run on the generic (select-based) path: the trimmed limit still moves too
     // much to be predicted.  Afterwards the fused two-kernel iteration is used; if its band prediction fails the
     // device stalls the queue and the host repairs that iteration on the generic path.
     const bool can_fuse = p2pl && h->dbg.disable_fused != 1;
     const bool trimming = p2pl && h->prm.use_trimmed && h->prm.trim_ratio != 1.0f;
-    const int kGenericFirst = trimming ? 2 : (p2pl ? 1 : std::max(1, h->env.gicp_tail_after));
+    const int kGenericFirst = trimming ? 2 : (h->prm.cost == REG_COST_GICP ? std::max(1, h->env.gicp_tail_after) : 1);
     const int kAhead = h->env.lookahead;
     const HostMirror* mir = h->h_mirror;
     int generic_left = kGenericFirst;
@@ -704,7 +734,7 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
     // The persistent tail (kernels_tail.hpp) replaces the burst of three-launch fused iterations when this registration
     // holds the device's tail lock (one persistent kernel per device at a time: see g_tail_mutex).
     // (GICP has no three-launch fused form: without the tail lock its iterations stay select-based)
-    const TailPlan tail_pl = ((can_fuse || !p2pl) && tail_eligible(h)) ? tail_plan(h) : TailPlan();
+    const TailPlan tail_pl = ((can_fuse || h->prm.cost == REG_COST_GICP) && tail_eligible(h)) ? tail_plan(h) : TailPlan();
     const RegActiveGuard active(h->prm.device);
     std::unique_lock<std::mutex> tail_lock;
     if (tail_pl.ok && (active.alone() || h->env.tail_always)) {

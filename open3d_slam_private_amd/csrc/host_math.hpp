@@ -544,4 +544,127 @@ O3D_HD inline int solve6_p2pl_fast(const float* A, const float* b, float* x) {
     return rank;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Updates of Open3D's RegistrationICP (REG_COST_O3D_P2PL / REG_COST_O3D_P2P) from the reduced 32-double record of one
+// iteration; fp64, row-major 4x4 U of T <- U T.  Open3D 0.15.1 is not part of the reference tree: restated from its
+// published TransformationEstimationPointToPlane / PointToPoint, PARITY UNPINNED.  The update kernel and
+// reg_host_o3d_update both run exactly this code.
+// ---------------------------------------------------------------------------------------------
+
+// TransformVector6dToMatrix4d: R = Rz(x2) Ry(x1) Rx(x0), t = x3..5
+O3D_HD inline void o3d_x_to_T(const double* x, double* U) {
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    U[0] = cg * cb;
+    U[1] = cg * sb * sa - sg * ca;
+    U[2] = cg * sb * ca + sg * sa;
+    U[3] = x[3];
+    U[4] = sg * cb;
+    U[5] = sg * sb * sa + cg * ca;
+    U[6] = sg * sb * ca - cg * sa;
+    U[7] = x[4];
+    U[8] = -sb;
+    U[9] = cb * sa;
+    U[10] = cb * ca;
+    U[11] = x[5];
+    U[12] = U[13] = U[14] = 0.0;
+    U[15] = 1.0;
+}
+
+// Point-to-plane: J^T J x = -J^T r (slots 0-20 packed upper triangle, 21-26).  LDL^T; a rank-deficient system takes the
+// minimum-norm eigen-solve (Open3D's Eigen LDLT returns some solution there: a documented deviation).  Returns the rank.
+O3D_HD inline int o3d_update_p2pl(const double* s, double* U) {
+    double H[36], g[6], x[6];
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) H[6 * i + j] = H[6 * j + i] = s[k++];
+    for (int i = 0; i < 6; ++i) g[i] = -s[21 + i];
+    int rank = 6;
+    if (!solve_ldlt6(H, g, x, 1e-10)) rank = solve_sym6(H, g, x, 1e-12);
+    o3d_x_to_T(x, U);
+    return rank;
+}
+
+// Point-to-point: Umeyama without scaling from the sums about the origin o (slots 0-2 sum (p - o), 3-5 sum (q - o),
+// 6-14 sum (q - o)(p - o)^T, 15-17 sum o, 28 pairs).  S = cov(q, p) = U D V^T by the eigenvectors v_k of S^T S
+// (descending), made a proper rotation by flipping v_2; then u_k = S v_k / |S v_k| for k = 0, 1 (Gram-Schmidt against
+// rounding) and u_2 = u_0 x u_1, which is exactly d u_2 of U diag(1, 1, d) V^T with d = sign(det U det V): no
+// determinant is needed.  Rank 1 (all pairs on a line): u_1 is the unit vector perpendicular to u_0 closest to v_1 or
+// v_2; rank 0: R = I.  Returns the rank of S (singular values above 1e-10 of the largest).
+O3D_HD inline int o3d_update_p2p(const double* s, double* U) {
+    const double n = s[28];
+    double o[3], mp[3], mq[3], S[9];
+    for (int k = 0; k < 3; ++k) {
+        o[k] = s[15 + k] / n;
+        mp[k] = s[k] / n;
+        mq[k] = s[3 + k] / n;
+    }
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) S[3 * i + j] = s[6 + 3 * i + j] / n - mq[i] * mp[j];
+    double B[9], W[9], lam[3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) B[3 * i + j] = S[i] * S[j] + S[3 + i] * S[3 + j] + S[6 + i] * S[6 + j];
+    jacobi_eig_sym3(B, W, lam);
+    int o0 = 0, o1 = 1, o2 = 2;
+    if (lam[o1] > lam[o0]) { const int t = o0; o0 = o1; o1 = t; }
+    if (lam[o2] > lam[o0]) { const int t = o0; o0 = o2; o2 = t; }
+    if (lam[o2] > lam[o1]) { const int t = o1; o1 = o2; o2 = t; }
+    // (selects, not run-time indices: the arrays stay in registers on the device)
+    double v[3][3], a[3][3], sig[3];
+    for (int r = 0; r < 3; ++r) {
+        const double w0 = W[3 * r], w1 = W[3 * r + 1], w2 = W[3 * r + 2];
+        v[0][r] = o0 == 0 ? w0 : (o0 == 1 ? w1 : w2);
+        v[1][r] = o1 == 0 ? w0 : (o1 == 1 ? w1 : w2);
+        v[2][r] = o2 == 0 ? w0 : (o2 == 1 ? w1 : w2);
+    }
+    const double detv = v[0][0] * (v[1][1] * v[2][2] - v[1][2] * v[2][1]) - v[0][1] * (v[1][0] * v[2][2] - v[1][2] * v[2][0]) +
+                        v[0][2] * (v[1][0] * v[2][1] - v[1][1] * v[2][0]);
+    if (detv < 0)
+        for (int r = 0; r < 3; ++r) v[2][r] = -v[2][r];
+    for (int k = 0; k < 3; ++k) {
+        for (int r = 0; r < 3; ++r) a[k][r] = S[3 * r] * v[k][0] + S[3 * r + 1] * v[k][1] + S[3 * r + 2] * v[k][2];
+        sig[k] = sqrt(a[k][0] * a[k][0] + a[k][1] * a[k][1] + a[k][2] * a[k][2]);
+    }
+    int rank = 0;
+    if (sig[0] > 1e-300) {
+        rank = 1;
+        for (int k = 1; k < 3; ++k) rank += sig[k] > 1e-10 * sig[0] ? 1 : 0;
+    }
+    double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    if (rank >= 1) {
+        double u0[3], u1[3], u2[3];
+        for (int r = 0; r < 3; ++r) u0[r] = a[0][r] / sig[0];
+        double c[3];
+        if (rank >= 2) {
+            for (int r = 0; r < 3; ++r) c[r] = a[1][r];
+        } else {
+            const double d1 = u0[0] * v[1][0] + u0[1] * v[1][1] + u0[2] * v[1][2];
+            const double d2 = u0[0] * v[2][0] + u0[1] * v[2][1] + u0[2] * v[2][2];
+            const bool use1 = fabs(d1) <= fabs(d2);
+            for (int r = 0; r < 3; ++r) c[r] = use1 ? v[1][r] : v[2][r];
+        }
+        const double dc = u0[0] * c[0] + u0[1] * c[1] + u0[2] * c[2];
+        for (int r = 0; r < 3; ++r) c[r] -= dc * u0[r];
+        const double cn = sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+        for (int r = 0; r < 3; ++r) u1[r] = c[r] / cn;
+        u2[0] = u0[1] * u1[2] - u0[2] * u1[1];
+        u2[1] = u0[2] * u1[0] - u0[0] * u1[2];
+        u2[2] = u0[0] * u1[1] - u0[1] * u1[0];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) R[3 * i + j] = u0[i] * v[0][j] + u1[i] * v[1][j] + u2[i] * v[2][j];
+    }
+    // t = mean(q) - R mean(p) with the means about o: (mq + o) - R (mp + o)
+    for (int i = 0; i < 3; ++i) {
+        const double pi = R[3 * i] * (mp[0] + o[0]) + R[3 * i + 1] * (mp[1] + o[1]) + R[3 * i + 2] * (mp[2] + o[2]);
+        for (int j = 0; j < 3; ++j) U[4 * i + j] = R[3 * i + j];
+        U[4 * i + 3] = (mq[i] + o[i]) - pi;
+    }
+    U[12] = U[13] = U[14] = 0.0;
+    U[15] = 1.0;
+    return rank;
+}
+
+O3D_HD inline int o3d_update(bool point_to_point, const double* s, double* U) {
+    return point_to_point ? o3d_update_p2p(s, U) : o3d_update_p2pl(s, U);
+}
+
 }  // namespace o3dreg

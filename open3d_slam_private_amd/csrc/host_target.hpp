@@ -131,6 +131,7 @@ struct reg_handle {
     int64_t m = 0;
     bool has_tnrm = false, has_tcov = false;
     float c_ref[3] = {0, 0, 0};
+    float t_mid[3] = {0, 0, 0};    // centre of the reference's bounding box (input frame unless P2PL): origin of the O3D_P2P sums
     DevBuf t_raw, t_nrm_raw, t_cov_raw, t_centred, t_keys, t_keys2, t_vals, t_vals2, t_pts, t_nrm, t_cov, t_flags,
         t_scan, t_hash, t_cells, t_tmp, t_misc, t_dir, t_rows;
     Grid grid;
@@ -195,6 +196,9 @@ static inline void row_to_col(const float* r, float* c) { m4_transpose(r, c); }
 
 static inline int grid_for(int64_t n, int block = 256) { return (int)((n + block - 1) / block); }
 
+// The two Open3D RegistrationICP costs (select-free iterations, input frame, Open3D stop rule; include/o3dslam_reg.h)
+static inline bool cost_is_o3d(int cost) { return cost == REG_COST_O3D_P2PL || cost == REG_COST_O3D_P2P; }
+
 extern "C" {
 
 void reg_default_params(reg_params* p) {
@@ -251,10 +255,11 @@ reg_status reg_create(const reg_params* p, reg_handle** out) {
     if (p->struct_size != (int32_t)sizeof(reg_params)) return REG_BAD_ARGUMENT;
     if (p->knn != 1) return REG_BAD_ARGUMENT;
     if (!(p->max_dist > 0.f)) return REG_BAD_ARGUMENT;
-    if (p->cost != REG_COST_P2PL && p->cost != REG_COST_GICP) return REG_BAD_ARGUMENT;
+    if (p->cost != REG_COST_P2PL && p->cost != REG_COST_GICP && !cost_is_o3d(p->cost)) return REG_BAD_ARGUMENT;
     if (p->use_trimmed && !(p->trim_ratio >= 0.f && p->trim_ratio <= 1.f)) return REG_BAD_ARGUMENT;
     if (p->fixed_iters <= 0 && p->max_iter <= 0) return REG_BAD_ARGUMENT;
-    if (p->use_xicp && p->cost != REG_COST_P2PL) return REG_BAD_ARGUMENT;   // the analysis expects point-to-plane (ICP.cpp:1118)
+    // the analysis expects libpointmatcher's point-to-plane (ICP.cpp:1118): GICP and the Open3D costs reject it
+    if (p->use_xicp && p->cost != REG_COST_P2PL) return REG_BAD_ARGUMENT;
     if (p->gicp_stop_rule != 0 && p->gicp_stop_rule != 1) return REG_BAD_ARGUMENT;
     reg_handle* h = new reg_handle();
     h->prm = *p;
@@ -611,7 +616,7 @@ static reg_status set_target_impl(reg_handle* h, const float* xyz, int64_t xyz_s
         return REG_EMPTY_TARGET;
     }
     if (!xyz || xyz_stride < 3 || (nrm && nrm_stride < 3) || m > 0x7fffffffLL) return REG_BAD_ARGUMENT;
-    if (h->prm.cost == REG_COST_P2PL && !nrm && !h->structure_only) {
+    if ((h->prm.cost == REG_COST_P2PL || h->prm.cost == REG_COST_O3D_P2PL) && !nrm && !h->structure_only) {
         h->err = "InvalidField: point-to-plane needs the `normals` descriptor on the reference";
         return REG_MISSING_FIELD;
     }
@@ -674,6 +679,7 @@ static reg_status set_target_impl(reg_handle* h, const float* xyz, int64_t xyz_s
             return REG_BAD_ARGUMENT;
         }
         max_abs = std::max(max_abs, std::max(std::fabs(bmin[k]), std::fabs(bmax[k])));
+        h->t_mid[k] = 0.5f * (bmin[k] + bmax[k]);
     }
     // bin edge: user value, or adapt to ~8 points per occupied bin (surface-like clouds: count ~ c^2)
     float cs = h->prm.cell_size;

@@ -697,3 +697,80 @@ k_linearize_gicp(const float4* __restrict__ src, const float4* __restrict__ src_
     }
     block_reduce_store(v, partials);
 }
+
+// Open3D RegistrationICP per-pair terms (REG_COST_O3D_P2PL / REG_COST_O3D_P2P; Open3D 0.15.1 restated, PARITY UNPINNED).
+// One thread per reading point, fp32 transform (xf_point), fp64 per-pair algebra, the same 32-double partial records.
+//   O3D_P2PL: p = T s, r = (p - q).n, J = [p x n, n] -> 0-20 J^T J (packed upper triangle), 21-26 J^T r, 27 r^2
+//             (tgt_attr: the {point, normal} pairs of the reference in sorted order)
+//   O3D_P2P:  0-2 (p - o), 3-5 (q - o), 6-14 (q - o)(p - o)^T row-major, 15-17 o, 27 |p - q|^2   (tgt_attr: the points)
+//   both:     28 pairs, 29 pairs, 30 d^2 of the search (fitness / inlier_rmse).
+// o is the centre of the reference's bounding box.  Accumulated about it, the sums describe offsets of the size of the
+// cloud, not of its distance from the world origin, so forming cov(q, p) = sum (q - o)(p - o)^T / n - mean(q - o)
+// mean(p - o)^T in fp64 cancels at most the few digits that separate the cloud's extent from its spread -- far above the
+// fp32 resolution of the inputs either way.
+template <int kCost>
+__global__ void __launch_bounds__(256)
+k_linearize_o3d(const float4* __restrict__ src, int64_t n, const IterState* __restrict__ it, const int* __restrict__ pos,
+                const float* __restrict__ d2, const float4* __restrict__ tgt_attr, float3 origin, float* __restrict__ w_out,
+                double* __restrict__ partials) {
+    static_assert(kCost == REG_COST_O3D_P2PL || kCost == REG_COST_O3D_P2P, "Open3D costs only");
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    const int64_t ic = i < n ? i : n - 1;
+    const int ps_raw = pos[ic];
+    const float4 s = src[ic];
+    const int st_done = it->done;
+    const Xf T = load_xf(it);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) asm volatile("" ::"s"(T.m[k]));
+    asm volatile("" ::"v"(ps_raw), "v"(s.x));
+    if (st_done) return;
+    double v[kSums];
+#pragma unroll
+    for (int k = 0; k < kSums; ++k) v[k] = 0.0;
+    if (i < n) {
+        const int ps = ps_raw;
+        float w = 0.f;
+        if (ps >= 0) {
+            w = 1.f;
+            const float3 tp = xf_point(T, s.x, s.y, s.z);
+            const double px = tp.x, py = tp.y, pz = tp.z;
+            if constexpr (kCost == REG_COST_O3D_P2PL) {
+                const float4 q = tgt_attr[2 * (int64_t)ps];
+                const float4 nn = tgt_attr[2 * (int64_t)ps + 1];
+                const double nx = nn.x, ny = nn.y, nz = nn.z;
+                const double r = (px - (double)q.x) * nx + (py - (double)q.y) * ny + (pz - (double)q.z) * nz;
+                const double J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+                int k = 0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a)
+#pragma unroll
+                    for (int c = a; c < 6; ++c) v[k++] = J[a] * J[c];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
+                v[27] = r * r;
+            } else {
+                const float4 q = tgt_attr[ps];
+                const double ox = origin.x, oy = origin.y, oz = origin.z;
+                const double p[3] = {px - ox, py - oy, pz - oz};
+                const double qq[3] = {(double)q.x - ox, (double)q.y - oy, (double)q.z - oz};
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    v[a] = p[a];
+                    v[3 + a] = qq[a];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) v[6 + 3 * a + c] = qq[a] * p[c];
+                }
+                v[15] = ox;
+                v[16] = oy;
+                v[17] = oz;
+                const double ex = px - (double)q.x, ey = py - (double)q.y, ez = pz - (double)q.z;
+                v[27] = ex * ex + ey * ey + ez * ez;
+            }
+            v[28] = 1.0;
+            v[29] = 1.0;
+            v[30] = (double)d2[i];
+        }
+        if (w_out) w_out[i] = w;
+    }
+    block_reduce_store(v, partials);
+}

@@ -85,11 +85,27 @@ __device__ __noinline__ void upd_xicp_stage_a(const double* tot, const float* Tr
         }
 }
 
-__global__ void __launch_bounds__(1024)
-k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
-                unsigned long long seq, int fused, const float* __restrict__ band, float* __restrict__ w_out,
-                const SelectState* __restrict__ sel, const float* __restrict__ gathered, int n_ranks, int my_rank,
-                XicpState* __restrict__ xs) {
+// Open3D costs (REG_COST_O3D_P2PL / P2P): the update of o3d_update (host_math.hpp) on one lane; results through LDS.
+// One out-of-line function per cost: the point-to-plane eigen-solve fallback indexes its arrays at run time (scratch), and
+// sharing its frame put the Umeyama update's arrays into scratch too.
+template <bool kP2P>
+__device__ __noinline__ int upd_o3d(const double* tot, double* U_out) {
+    double s[kSums], U[16];
+    for (int i = 0; i < kSums; ++i) s[i] = tot[i];
+    const int rank = o3d_update(kP2P, s, U);
+    for (int i = 0; i < 16; ++i) U_out[i] = U[i];
+    return rank;
+}
+
+// The whole kernel, once per update family: kO3d = false is k_reduce_update (P2PL / GICP, every path), kO3d = true is
+// k_reduce_update_o3d (select-free iterations of the Open3D costs: left-multiplied fp64 update, Open3D stop rule).  The
+// Open3D branches exist only in their own instantiation, so they cannot cost k_reduce_update registers.
+template <bool kO3d>
+__device__ __forceinline__ void reduce_update_body(const double* __restrict__ partials, int n_blocks, IterState* it,
+                                                   HostMirror* host, unsigned long long seq, int fused,
+                                                   const float* __restrict__ band, float* __restrict__ w_out,
+                                                   const SelectState* __restrict__ sel, const float* __restrict__ gathered,
+                                                   int n_ranks, int my_rank, XicpState* __restrict__ xs) {
     const int contrib_cap = contrib_cap_for(n_ranks);              // gathered blocks: per-rank record capacity
     const size_t contrib_stride = contrib_floats(contrib_cap);     // floats per rank block
     // fused: 0 = select-based iteration, 1 = fused iteration (band verification), 2 = R8x finish: the sums are
@@ -449,7 +465,7 @@ k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it
     const int lane = threadIdx.x;
     const unsigned long long st1 = __builtin_amdgcn_s_memtime();
     unsigned long long st2 = st1, st3 = st1;
-    const bool p2pl = sit->cost == REG_COST_P2PL;
+    const bool p2pl = !kO3d && sit->cost == REG_COST_P2PL;   // (kO3d: Open3D costs only)
     // Everything lane 0 will read from the LDS-resident state is fetched here in one batch, behind the solve below: read
     // one by one inside the serial section, every access cost its own ~100-cycle LDS round trip (3.4 k cycles measured
     // before the pose update even started).
@@ -577,7 +593,7 @@ k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it
                 else
                     iterate = sit->chk.check(Tn);
                 if (!iterate) sit->done = 1;
-            } else if (sit->gicp_stop_rule == 1 && sit->fixed_iters <= 0 &&
+            } else if ((kO3d || sit->gicp_stop_rule == 1) && sit->fixed_iters <= 0 &&
                        ((sit->iterations >= 1 &&
                          fabs(r_tot28 / (double)sit->n_total - sit->fit_prev) < (double)sit->gicp_rel_fitness &&
                          fabs(sqrt(tot[30] / r_tot28) - sit->rmse_prev) < (double)sit->gicp_rel_rmse) ||
@@ -597,20 +613,35 @@ k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it
                 int rank = 6;
                 sit->fit_prev = r_tot28 / (double)sit->n_total;
                 sit->rmse_prev = sqrt(tot[30] / r_tot28);
-                if (well) {
-                    for (int i = 0; i < 6; ++i) dl[i] = xsol[i];
+                if constexpr (kO3d) {
+                    // Open3D: T <- U T (RegistrationICP: transformation = update * transformation)
+                    double* U = &sh[0][0];   // the reduction's staging rows are free by now
+                    rank = sit->cost == REG_COST_O3D_P2P ? upd_o3d<true>(tot, U) : upd_o3d<false>(tot, U);
+                    for (int i = 0; i < 4; ++i)
+                        for (int j = 0; j < 4; ++j) {
+                            double v = 0;
+                            for (int kk = 0; kk < 4; ++kk) v += U[4 * i + kk] * sit->Td[4 * kk + j];
+                            Tn[4 * i + j] = v;
+                        }
+                    sit->rank_last = rank;
+                    (void)dl;
+                    (void)E;
                 } else {
-                    rank = upd_solve_sym6(tot, s_dl);
-                    for (int i = 0; i < 6; ++i) dl[i] = s_dl[i];
-                }
-                sit->rank_last = rank;
-                se3_exp(dl, E);
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) {
-                        double v = 0;
-                        for (int kk = 0; kk < 4; ++kk) v += sit->Td[4 * i + kk] * E[4 * kk + j];
-                        Tn[4 * i + j] = v;
+                    if (well) {
+                        for (int i = 0; i < 6; ++i) dl[i] = xsol[i];
+                    } else {
+                        rank = upd_solve_sym6(tot, s_dl);
+                        for (int i = 0; i < 6; ++i) dl[i] = s_dl[i];
                     }
+                    sit->rank_last = rank;
+                    se3_exp(dl, E);
+                    for (int i = 0; i < 4; ++i)
+                        for (int j = 0; j < 4; ++j) {
+                            double v = 0;
+                            for (int kk = 0; kk < 4; ++kk) v += sit->Td[4 * i + kk] * E[4 * kk + j];
+                            Tn[4 * i + j] = v;
+                        }
+                }
                 for (int i = 0; i < 16; ++i) {
                     sit->T_prev[i] = r_T[i];
                     sit->Td[i] = Tn[i];
@@ -619,7 +650,7 @@ k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it
                 sit->iterations += 1;
                 if (sit->fixed_iters > 0) {
                     if (sit->iterations >= sit->fixed_iters) sit->done = 1;
-                } else if (sit->gicp_stop_rule == 1) {
+                } else if (kO3d || sit->gicp_stop_rule == 1) {
                     // decided by the next evaluation (above)
                 } else {
                     const double dr = sqrt(dl[0] * dl[0] + dl[1] * dl[1] + dl[2] * dl[2]);
@@ -694,6 +725,21 @@ k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it
         __hip_atomic_store(&srec->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(&host->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+}
+
+__global__ void __launch_bounds__(1024)
+k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
+                unsigned long long seq, int fused, const float* __restrict__ band, float* __restrict__ w_out,
+                const SelectState* __restrict__ sel, const float* __restrict__ gathered, int n_ranks, int my_rank,
+                XicpState* __restrict__ xs) {
+    reduce_update_body<false>(partials, n_blocks, it, host, seq, fused, band, w_out, sel, gathered, n_ranks, my_rank, xs);
+}
+
+// Select-free iteration of the Open3D costs: sums of k_linearize_o3d -> update, Open3D convergence criteria, mirror.
+__global__ void __launch_bounds__(1024)
+k_reduce_update_o3d(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
+                    unsigned long long seq) {
+    reduce_update_body<true>(partials, n_blocks, it, host, seq, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr);
 }
 
 // Stream-ordered distributed path: this rank's workgroup partials -> 32 doubles (summed over ranks by the caller's

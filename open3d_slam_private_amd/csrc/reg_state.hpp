@@ -2,13 +2,19 @@
 // Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
 #pragma once
 
+// The 32-double record every linearize kernel reduces (IterState::sums, HostMirror::sums, the distributed halves):
+//   P2PL / GICP / O3D_P2PL   0-20 H (packed upper triangle), 21-26 b, 27 error, 28 inliers, 29 matched, 30 sum d^2 (inliers),
+//                            31 below-band count (fused path)
+//   O3D_P2P                  0-2 sum (p - o), 3-5 sum (q - o), 6-14 sum (q - o)(p - o)^T (row-major, row = q component),
+//                            15-17 sum o, 27 sum |p - q|^2, 28 / 29 pairs, 30 sum d^2; o = centre of the reference's
+//                            bounding box (k_linearize_o3d)
 // Iteration state living in device memory: the pose the kernels read, the checker history and the
 // termination flags.  The update kernel (last kernel of an iteration) is its only writer, so a whole
 // registration can be enqueued without a host round trip per Gauss-Newton iteration.
 struct IterState {
     float T[16];          // T_iter, row-major (P2PL: centred frames; GICP: reading -> reference)
     float T_prev[16];     // the pose the last completed iteration RAN at (its matches, weights and sums belong to it)
-    double Td[16];        // GICP: the same in double
+    double Td[16];        // GICP / O3D costs: the same in double
     Checkers chk;         // DifferentialTransformationChecker / CounterTransformationChecker state
     int iterations;
     int done;             // 1: the remaining enqueued kernels return immediately

@@ -5,6 +5,9 @@
                                    ICP.cpp:100-210), as used by o3d_slam::Mapper (Mapper.cpp:343,372-373)
   RegistrationIcpGeneralized   <-> o3d_slam::RegistrationIcpGeneralized::registerClouds
                                    (open3d_slam/src/CloudRegistration.cpp:16-21, CloudRegistration.hpp:19-73)
+  RegistrationIcpPointToPlane  <-> o3d_slam::RegistrationIcpPointToPlane (CloudRegistration.cpp:54-83)
+  RegistrationIcpPointToPoint  <-> o3d_slam::RegistrationIcpPointToPoint (CloudRegistration.cpp:84-101)
+  cloudRegistrationFactory     <-> o3d_slam::cloudRegistrationFactory (CloudRegistration.cpp:104-119)
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -250,6 +253,7 @@ class SurfaceNormalDataPointsFilter:
         return DataPoints(cloud.features, out["normals"] if self.keepNormals else cloud.normals, cloud.covariances)
 
 
+@dataclass
 class RegistrationResult:
     """open3d::pipelines::registration::RegistrationResult fields consumed by the reference
     (Odometry.cpp:56,77, PlaceRecognition.cpp:118)."""
@@ -295,3 +299,106 @@ class RegistrationIcpGeneralized:
                                  np.stack([sel, ids[sel]], axis=1))
         reg.close()
         return out
+
+
+class _RegistrationIcpOpen3d:
+    """Common part of the two Open3D RegistrationICP operators: the select-free iteration of the C ABI's
+    REG_COST_O3D_P2PL / REG_COST_O3D_P2P, stopped by Open3D's ICPConvergenceCriteria (only max_iteration_ is configured,
+    CloudRegistration.cpp:77-101, so relative_fitness_ = relative_rmse_ = 1e-6 end the loop)."""
+    _cost = None
+    _needs_target_normals = False
+
+    def __init__(self, maxCorrespondenceDistance_=1.0, max_iteration_=30):
+        self.maxCorrespondenceDistance_ = maxCorrespondenceDistance_
+        self.max_iteration_ = max_iteration_
+        self.relative_fitness_ = 1e-6   # open3d::pipelines::registration::ICPConvergenceCriteria defaults
+        self.relative_rmse_ = 1e-6
+
+    def params(self) -> RegParams:
+        p = capi.default_params()
+        p.cost = self._cost
+        p.use_trimmed = 0
+        p.max_dist = self.maxCorrespondenceDistance_
+        p.max_iter = self.max_iteration_
+        p.gicp_rel_fitness = self.relative_fitness_
+        p.gicp_rel_rmse = self.relative_rmse_
+        return p
+
+    def registerClouds(self, source: DataPoints, target: DataPoints, init=None) -> RegistrationResult:
+        if self._needs_target_normals and target.normals is None:
+            # Open3D: "TransformationEstimationPointToPlane ... require pre-computed normal vectors for target PointCloud."
+            raise InvalidField("point-to-plane needs normals on the target cloud")
+        reg = capi.Registration(self.params())
+        try:
+            reg.set_target(target.features, target.normals if self._needs_target_normals else None, None)
+            reg.set_source(source.features, None, None)
+            T, res = reg.register(np.eye(4) if init is None else init)
+            ids, _, _ = reg.correspondences(want_w=False)
+        except RegError as e:
+            raise _translate(e) from None
+        finally:
+            reg.close()
+        sel = np.nonzero(ids >= 0)[0]
+        return RegistrationResult(T.astype(np.float64), float(res.fitness), float(res.inlier_rmse),
+                                  np.stack([sel, ids[sel]], axis=1))
+
+    def estimateNormalsOrCovariancesIfNeeded(self, cloud: DataPoints) -> None:
+        """Point-to-point needs neither normals nor covariances (CloudRegistration.hpp: the base class's no-op)."""
+
+
+class RegistrationIcpPointToPlane(_RegistrationIcpOpen3d):
+    """o3d_slam::RegistrationIcpPointToPlane (CloudRegistration.hpp:29-42, CloudRegistration.cpp:54-83): Open3D
+    RegistrationICP with TransformationEstimationPointToPlane (L2 loss) -> REG_COST_O3D_P2PL."""
+    _cost = capi.COST_O3D_P2PL
+    _needs_target_normals = True
+
+    def __init__(self, maxCorrespondenceDistance_=1.0, max_iteration_=30, knnNormalEstimation_=5,
+                 maxRadiusNormalEstimation_=10.0):
+        super().__init__(maxCorrespondenceDistance_, max_iteration_)
+        self.knnNormalEstimation_ = knnNormalEstimation_
+        self.maxRadiusNormalEstimation_ = maxRadiusNormalEstimation_
+
+    def estimateNormalsOrCovariancesIfNeeded(self, cloud: DataPoints) -> None:
+        """CloudRegistration.cpp:62-75: a cloud that has normals is left alone; otherwise k-NN normals within the radius,
+        normalised and oriented towards the camera location (the origin) -- on the device (reg_estimate_normals)."""
+        if cloud.normals is not None:
+            return
+        if not (self.maxRadiusNormalEstimation_ > 0.0):
+            raise InvalidParameter("maxRadiusNormalEstimation_ must be > 0")
+        if not (self.knnNormalEstimation_ > 0):
+            raise InvalidParameter("knnNormalEstimation_ must be > 0")
+        p = capi.default_params()
+        p.cost = capi.COST_O3D_P2P
+        reg = capi.Registration(p)
+        try:
+            out = reg.estimate_normals(cloud.features, k=self.knnNormalEstimation_, max_dist=self.maxRadiusNormalEstimation_,
+                                       viewpoint=np.zeros(3, np.float32))
+        except RegError as e:
+            raise _translate(e) from None
+        finally:
+            reg.close()
+        cloud.normals = out["normals"]
+
+
+class RegistrationIcpPointToPoint(_RegistrationIcpOpen3d):
+    """o3d_slam::RegistrationIcpPointToPoint (CloudRegistration.hpp:44-53, CloudRegistration.cpp:84-101): Open3D
+    RegistrationICP with TransformationEstimationPointToPoint(with_scaling = false) -> REG_COST_O3D_P2P."""
+    _cost = capi.COST_O3D_P2P
+
+
+# CloudRegistrationType / ScanToMapRegistrationType (Parameters.hpp:37-49): same order, same strings
+CLOUD_REGISTRATION_TYPES = {"PointToPlaneIcp": 0, "PointToPointIcp": 1, "GeneralizedIcp": 2}
+
+
+def cloudRegistrationFactory(name_or_enum, maxCorrespondenceDistance_=0.2, maxNumIter_=50, knn_=5, maxDistanceKnn_=10.0):
+    """o3d_slam::cloudRegistrationFactory (CloudRegistration.cpp:104-119) with the fields of IcpParameters
+    (Parameters.hpp:66-72, defaults included): `cloud_registration_type` / `scan_to_map_refinement_type` string or the
+    enum value."""
+    kind = CLOUD_REGISTRATION_TYPES.get(name_or_enum) if isinstance(name_or_enum, str) else name_or_enum
+    if kind == 0 and not isinstance(kind, bool):
+        return RegistrationIcpPointToPlane(maxCorrespondenceDistance_, maxNumIter_, knn_, maxDistanceKnn_)
+    if kind == 1 and not isinstance(kind, bool):
+        return RegistrationIcpPointToPoint(maxCorrespondenceDistance_, maxNumIter_)
+    if kind == 2 and not isinstance(kind, bool):
+        return RegistrationIcpGeneralized(maxCorrespondenceDistance_, maxNumIter_)
+    raise RuntimeError("cloud: unknown type of cloud registration")
