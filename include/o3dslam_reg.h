@@ -141,7 +141,9 @@ typedef struct {
     int64_t n_inliers;          /* pairs with non-zero weight in the last iteration */
     int64_t n_matched;          /* pairs with a neighbour inside max_dist in the last iteration */
     double  error;              /* P2PL: sum w r^2;  GICP: sum 0.5 r^T M r;  O3D_*: see reg_cost  (last iteration) */
-    double  fitness;            /* n_inliers / N   (open3d RegistrationResult::fitness_ analogue) */
+    double  fitness;            /* n_inliers / N   (open3d RegistrationResult::fitness_ analogue); N = points of the
+                                   WHOLE reading.  reg_dist_finish: N is known after reg_dist_register or
+                                   reg_dist_prepare; a handle prepared only through reg_prepare_centroid reports NaN */
     double  inlier_rmse;        /* sqrt(sum_inliers d^2 / n_inliers) */
     float   H_last[36];         /* last normal matrix, row-major (symmetric) */
     float   b_last[6];

@@ -84,8 +84,12 @@ reg_status reg_dist_centroid_sums(reg_handle* h, void** sums_dev) {
 reg_status reg_dist_prepare(reg_handle* h, const float T_init[16], int64_t n_global) {
     if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
     if (!h || !T_init || n_global < 1) return REG_BAD_ARGUMENT;
+    reg_status s = check_ready(h, false);
+    if (s != REG_OK) return s;
+    if (n_global < h->n) return REG_BAD_ARGUMENT;
     float Tr[16];
     col_to_row(T_init, Tr);
+    h->n_total_hint = n_global;   // fitness (reg_dist_finish) and the GICP stop rule count the whole reading
     return prepare_rowmajor(h, Tr, nullptr, n_global);
 }
 
@@ -362,16 +366,17 @@ reg_status reg_dist_phase(reg_handle* h, int phase) {
                                                           hist0 + 2048, hist0 + 4096, hist0, st, it);
             break;
         case 3: {
+            // (the weights are always written, as in reg_register's select-based iteration: reg_get_correspondences reports them)
             if (h->prm.cost == REG_COST_P2PL) {
                 const FilterCfg f = make_filter_cfg(h, h->prm.use_trimmed ? 2 : 0);
                 k_linearize_p2pl<<<h->n_blocks, 256, 0, h->stream>>>(
                     h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, it, h->i_pos.as<int>(),
                     h->i_d2.as<float>(), h->t_pts.as<float4>(), h->t_nrm.as<float4>(), f, st, hist0 + 4096, hist0 + 2048,
-                    h->shift0, h->prm.use_xicp ? h->i_w.as<float>() : nullptr, h->i_partials.as<double>(), h->i_cache.as<float4>());
+                    h->shift0, h->i_w.as<float>(), h->i_partials.as<double>(), h->i_cache.as<float4>());
             } else {
                 k_linearize_gicp<<<h->n_blocks, 256, 0, h->stream>>>(h->s_xyz.as<float4>(), h->s_cov.as<float4>(), h->n, it,
                                                                      h->i_pos.as<int>(), h->i_d2.as<float>(),
-                                                                     h->t_pts.as<float4>(), h->t_cov.as<float4>(), nullptr,
+                                                                     h->t_pts.as<float4>(), h->t_cov.as<float4>(), h->i_w.as<float>(),
                                                                      h->i_partials.as<double>());
             }
             k_partials_sum<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_sums.as<double>(), it);
@@ -442,7 +447,7 @@ reg_status reg_dist_phase(reg_handle* h, int phase) {
             k_linearize_p2pl<<<h->n_blocks, 256, 0, h->stream>>>(
                 h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, it, h->i_pos.as<int>(),
                 h->i_d2.as<float>(), h->t_pts.as<float4>(), h->t_nrm.as<float4>(), f, st, hist0 + 4096, hist0 + 2048,
-                h->shift0, h->prm.use_xicp ? h->i_w.as<float>() : nullptr, h->i_partials.as<double>(), h->i_cache.as<float4>());
+                h->shift0, h->i_w.as<float>(), h->i_partials.as<double>(), h->i_cache.as<float4>());
             k_partials_sum<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_sums.as<double>(), it);
             break;
         }
@@ -522,7 +527,9 @@ reg_status reg_dist_finish(reg_handle* h, float T_out[16], reg_result* res) {
         res->xicp_high[k] = mir->xicp_high[k];
     }
     res->n_constraints = h->prm.use_xicp ? mir->n_constraints : 0;
-    fill_result(h, mir->sums, res);
+    // the sums are the group's: fitness over the WHOLE reading where the handle knows its size (the group's count exchange,
+    // reg_dist_prepare), unknown (NaN) otherwise -- never over this rank's slice
+    fill_result(h, mir->sums, res, h->n_total_hint > 0 ? (double)h->n_total_hint : (double)NAN);
     if (mir->status != REG_OK) {
         h->err = "ErrorMinimizer: no point to minimize";
         return (reg_status)mir->status;

@@ -611,11 +611,12 @@ static void compose_rowmajor(reg_handle* h, const float* T_iter, float* Tout_row
     }
 }
 
-static void fill_result(reg_handle* h, const double* sums, reg_result* res) {
+// n_reading: points of the whole reading the sums describe (> 0), NaN where the handle does not know it (fitness NaN)
+static void fill_result(reg_handle* h, const double* sums, reg_result* res, double n_reading) {
     res->n_inliers = (int64_t)llround(sums[28]);
     res->n_matched = (int64_t)llround(sums[29]);
     res->error = sums[27];
-    res->fitness = h->n > 0 ? sums[28] / (double)h->n : 0.0;
+    res->fitness = sums[28] / n_reading;
     res->inlier_rmse = sums[28] > 0 ? std::sqrt(sums[30] / sums[28]) : 0.0;
     sums_to_system(sums, h->prm.cost, res->H_last, res->b_last);
     res->target_build_ms = h->target_build_ms;
@@ -626,6 +627,15 @@ static void fill_result(reg_handle* h, const double* sums, reg_result* res) {
     }
     res->source_prep_ms = h->source_prep_ms;
     res->rotation_corrected = h->rotation_corrected;
+}
+
+// Sequences one registration may enqueue: fixed_iters, else max_iter -- plus one under Open3D's stop rule (GICP rule 1,
+// the O3D costs), whose last sequence only re-evaluates the correspondences at the final pose.  reg_register and
+// reg_dist_register both take their limit from here.
+static int sequence_limit(const reg_params& p) {
+    if (p.fixed_iters > 0) return p.fixed_iters;
+    const bool o3d_rule = cost_is_o3d(p.cost) || (p.cost == REG_COST_GICP && p.gicp_stop_rule == 1);
+    return p.max_iter + (o3d_rule ? 1 : 0);
 }
 
 extern "C" {
@@ -712,10 +722,7 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
     rmark("ev0");
     const unsigned long long seq0 = h->seq;
     const int fixed = h->prm.fixed_iters;
-    // (Open3D's stop rule -- GICP rule 1, the O3D costs always -- re-evaluates the correspondences once more after the last
-    //  update: one more sequence)
-    const bool o3d_rule = cost_is_o3d(h->prm.cost) || (h->prm.cost == REG_COST_GICP && h->prm.gicp_stop_rule == 1);
-    const int limit = fixed > 0 ? fixed : h->prm.max_iter + (o3d_rule ? 1 : 0);
+    const int limit = sequence_limit(h->prm);
     // Iterations 0..kGenericFirst-1 run on the generic (select-based) path: the trimmed limit still moves too
     // much to be predicted.  Afterwards the fused two-kernel iteration is used; if its band prediction fails the
     // device stalls the queue and the host repairs that iteration on the generic path.
@@ -961,7 +968,7 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
     res->converged = mir->converged;
     res->max_iter_reached = mir->max_iter_reached;
     res->rank_last = mir->rank_last;
-    fill_result(h, mir->sums, res);
+    fill_result(h, mir->sums, res, (double)h->n);
     if (mir->status != REG_OK) {
         h->err = mir->sums[29] == 0.0 ? "No matches available for computing distance quantiles"
                                       : "ErrorMinimizer: no point to minimize";

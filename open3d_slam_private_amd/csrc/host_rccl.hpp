@@ -431,6 +431,7 @@ reg_status reg_dist_shutdown(reg_handle* h) {
     delete d;
     h->dist = nullptr;
     h->dist_ranks = 0;
+    h->n_total_hint = 0;   // a plain single-GPU handle again: its reading is all there is
     return REG_OK;
 }
 
@@ -501,7 +502,7 @@ reg_status reg_dist_register(reg_handle* h, const float T_init[16], float T_out[
     if ((s = reg_dist_begin(h, nullptr)) != REG_OK) return s;
     bool xicp_first = h->prm.use_xicp && p2pl;
     const bool trimming = p2pl && h->prm.use_trimmed && h->prm.trim_ratio != 1.0f;
-    reg_dist_steer* st = reg_dist_steer_create(trimming ? 1 : 0, h->prm.fixed_iters, h->prm.max_iter, d->settle_tol,
+    reg_dist_steer* st = reg_dist_steer_create(trimming ? 1 : 0, h->prm.fixed_iters, sequence_limit(h->prm), d->settle_tol,
                                                (p2pl && h->dbg.disable_fused != 1) ? 1 : 0);
     reg_dist_reply reply;
     std::memset(&reply, 0, sizeof(reply));
@@ -531,7 +532,6 @@ reg_status reg_dist_register(reg_handle* h, const float T_init[16], float T_out[
     s = reg_dist_finish(h, T_out, res);
     if (res) {
         res->loop_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_loop_begin).count();
-        res->fitness = d->n_global > 0 ? (double)res->n_inliers / (double)d->n_global : 0.0;
         res->n_band_stalls = d->last_steer.n_stalls;
     }
     return s;

@@ -423,6 +423,9 @@ def test_stream_ordered_distributed_path_two_slices_one_gpu():
         dt, dr = synth.pose_error(T, T_ref)
         assert dt <= 1e-6 and dr <= 1e-6, (dt, dr)
         assert res.iterations == 8 and res.n_inliers == res_ref.n_inliers
+        # prepared through reg_prepare_centroid only, a handle never learns the size of the whole reading: its fitness
+        # is unknown (NaN), never the group's inliers over its own slice
+        assert math.isnan(res.fitness), res.fitness
     assert np.array_equal(outs[0][0], outs[1][0])      # every rank holds the identical pose
 
 
@@ -832,6 +835,7 @@ def test_select_by_gather_iteration_two_uneven_slices_one_gpu():
         dt, dr = synth.pose_error(T, T_ref)
         assert dt <= 1e-6 and dr <= 1e-6, (dt, dr)
         assert res.iterations == 7 and res.n_inliers == res_ref.n_inliers
+        assert res.fitness == res_ref.fitness      # reg_dist_prepare was told the size of the whole reading
     assert np.array_equal(outs[0][0], outs[1][0])
     assert torch.isinf(bufs[0][0][cuts[0][1] - cuts[0][0]:]).all()       # the shorter slice is padded with +inf
 
