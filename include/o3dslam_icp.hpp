@@ -50,12 +50,21 @@ public:
     ICP(const ICP&) = delete;
     ICP& operator=(const ICP&) = delete;
 
-    // ICPChainBase::setDefault (ICP.cpp:100-113)
-    void setDefault() { reg_default_params(&params_); reset(); }
-    // the chain of open3d_slam_ros/param/icp.yaml (what Mapper loads through loadFromYaml)
-    void setShippedChain() { reg_shipped_params(&params_); reset(); }
+    // ICPChainBase::setDefault (ICP.cpp:100-113); drops a chain set by setPmChain (the default chain is knn 1, no robust filter)
+    void setDefault() { reg_default_params(&params_); has_chain_ = false; reset(); }
+    // the chain of open3d_slam_ros/param/icp.yaml (what Mapper loads through loadFromYaml); drops a setPmChain chain
+    void setShippedChain() { reg_shipped_params(&params_); has_chain_ = false; reset(); }
     // direct access to the string-free parameter block (call before the first initReference)
     reg_params& parameters() { reset(); return params_; }
+    // libpointmatcher chain extension (reg_set_pm_chain: k-NN matching, RobustOutlierFilter, PointToPoint).  The chain
+    // is kept and re-applied whenever parameters() re-creates the handle (the robust state then starts afresh, as with a
+    // new filter); setting it resets the robust state.
+    void setPmChain(const reg_pm_chain& c) {
+        chain_ = c;
+        has_chain_ = true;
+        if (h_) check(reg_set_pm_chain(h_, &chain_));
+        else ensure();
+    }
 
     bool hasMap() const { return matcherIsInitialized_; }
     bool getMaxNumIterationsReached() const { return last_.max_iter_reached != 0; }
@@ -143,6 +152,16 @@ private:
             if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
             throw InvalidParameter(msg);
         }
+        if (has_chain_) {
+            const reg_status cs = reg_set_pm_chain(h_, &chain_);
+            if (cs != REG_OK) {
+                const std::string msg = reg_last_error(h_);
+                reg_destroy(h_);
+                h_ = nullptr;
+                if (cs == REG_DEVICE_ERROR) throw DeviceError(msg);
+                throw InvalidParameter("reg_set_pm_chain: the chain does not fit the parameters (" + std::to_string((int)cs) + ") " + msg);
+            }
+        }
     }
     void check(reg_status s) {
         if (s == REG_OK) return;
@@ -156,6 +175,8 @@ private:
         }
     }
     reg_params params_;
+    reg_pm_chain chain_{};
+    bool has_chain_ = false;
     reg_handle* h_ = nullptr;
     reg_result last_{};
     bool matcherIsInitialized_ = false;

@@ -357,6 +357,70 @@ REG_API void reg_host_centroid(const float* xyz, int64_t stride, int64_t n, floa
    column-major 4x4 U of T <- U T; *rank (may be NULL) as reg_result.rank_last.  REG_BAD_ARGUMENT for any other cost,
    REG_NO_CORRESPONDENCES when sums[28] == 0. */
 REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T_update[16], int32_t* rank);
+/* ---- libpointmatcher chain extension: k-NN matching, RobustOutlierFilter, PointToPointErrorMinimizer -------------
+   An opt-in extension of the REG_COST_P2PL loop (reg_params keeps its layout; reg_params.knn stays 1).  Set on a handle
+   with reg_set_pm_chain; every registration of that handle then runs the generic iteration k-NN search -> exact selects
+   -> weights + reduction -> update on the device (never the fused, tail or distributed forms).
+     KDTreeMatcher.knn (MatchersImpl.cpp)          1..16 exact nearest reference points within reg_params.max_dist
+                                                    (+inf allowed), ascending (d2, index); missing slots: id -1, d2 +inf
+     filters (OutlierFiltersImpl.cpp)              product of the weights of TrimmedDist (quantile over ALL N*knn
+                                                    finite d2, Matches.cpp:60-87), SurfaceNormal, MaxDist (reg_params)
+                                                    and RobustOutlierFilter (:397-598) when use_robust != 0
+     minimizer                                     REG_PM_POINT_TO_PLANE: A = sum w F F^T, b = -sum w F r (ICP.cpp:1527-1565);
+                                                    REG_PM_POINT_TO_POINT: weighted Kabsch (ErrorMinimizers/PointToPoint.cpp:62-100)
+                                                    in fp64, composed T_iter <- dT T_iter in the centred frames
+   Rules: only cost REG_COST_P2PL (else REG_BAD_ARGUMENT); use_xicp with knn > 1, robust weights or point-to-point is
+   REG_UNSUPPORTED; the "std" scale estimator is REG_UNSUPPORTED (getStandardDeviation, Matches.cpp:124-129, is an fp32
+   Eigen sum in Eigen's order over every entry including the +inf ones: it cannot be restated to a stated tolerance).
+   Robust state: the filter's `iteration` and `scale` persist across registrations of the handle as in the reference
+   (ICP::compute never resets them, OutlierFiltersImpl.cpp:408-409,510-543); reg_set_pm_chain resets them.
+   reg_result with a chain: n_inliers = pairs with w != 0, n_matched = pairs with finite d2, fitness = n_inliers /
+   (N knn) (pointUsedRatio, ErrorMinimizer.cpp:139), inlier_rmse unweighted over the inliers, error = sum w r^2
+   (point-to-plane) / sum w |p - q|^2 (point-to-point); point-to-point: H_last = b_last = 0 and rank_last is the rank
+   of the 3x3 cross-covariance.  reg_get_correspondences returns REG_UNSUPPORTED with knn > 1, reg_linearize always
+   with a chain; the distributed entry points return REG_UNSUPPORTED while a chain is set. */
+enum { REG_PM_POINT_TO_PLANE = 0, REG_PM_POINT_TO_POINT = 1 };
+enum {   /* robustFct (OutlierFiltersImpl.cpp:385-394) */
+    REG_ROBUST_CAUCHY = 0, REG_ROBUST_WELSCH = 1, REG_ROBUST_SC = 2, REG_ROBUST_GM = 3, REG_ROBUST_TUKEY = 4,
+    REG_ROBUST_HUBER = 5, REG_ROBUST_L1 = 6, REG_ROBUST_STUDENT = 7
+};
+enum { REG_SCALE_NONE = 0, REG_SCALE_MAD = 1, REG_SCALE_BERG = 2, REG_SCALE_STD = 3 /* REG_UNSUPPORTED */ };
+enum { REG_DIST_POINT2POINT = 0, REG_DIST_POINT2PLANE = 1 /* needs reference normals */ };
+typedef struct {
+    int32_t struct_size;         /* = sizeof(reg_pm_chain); checked */
+    int32_t knn;                 /* KDTreeMatcher knn, 1..16 (reg_params.knn stays 1) */
+    int32_t minimizer;           /* REG_PM_POINT_TO_PLANE (the loop as today) | REG_PM_POINT_TO_POINT */
+    int32_t use_robust;          /* RobustOutlierFilter in the chain */
+    int32_t robust_fct;          /* REG_ROBUST_* */
+    float   tuning;              /* "tuning" (> 0); with berg: the target scale */
+    int32_t scale_estimator;     /* REG_SCALE_NONE | MAD | BERG */
+    int32_t nb_iter_for_scale;   /* "nbIterationForScale" (0 = every iteration), 0..100 */
+    int32_t distance_type;       /* REG_DIST_POINT2POINT | REG_DIST_POINT2PLANE */
+    float   approximation;       /* "approximation" (INFINITY = off); w = 0 where e^2 >= (float)(approximation^2 in double) */
+    int32_t reserved[2];
+} reg_pm_chain;
+
+/* knn 1, point-to-plane, robust off: the loop as without a chain (robust defaults as OutlierFiltersImpl.h:230-244). */
+REG_API void       reg_default_pm_chain(reg_pm_chain* c);
+/* Pure check of a chain against the parameters it would run with (no device). */
+REG_API reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c);
+/* c == NULL or the default chain: back to the plain loop.  Resets the robust state. */
+REG_API reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c);
+/* Robust filter state as the next registration starts with it: scale and the filter's iteration counter (1 = fresh). */
+REG_API reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32_t* iteration);
+/* Correspondences of the last iteration (taken at T_iter_prev), reading input order, N x knn entries each, ascending
+   (d2, id); ids -1 / d2 +inf where fewer than knn reference points lie within max_dist.  knn must equal the chain's
+   knn.  Any pointer may be NULL. */
+REG_API reg_status reg_get_correspondences_k(reg_handle* h, int32_t knn, int32_t* ids, float* d2, float* w);
+/* The robust weight of the chain's kernels on the host: w[i] for squared distances d2_or_e[i] (the filter's `dists`),
+   scale and tuning as the filter holds them.  The same code as the device. */
+REG_API reg_status reg_host_robust_weights(int32_t fct, float tuning, float scale, float approximation,
+                                           const float* d2_or_e, int64_t n, float* w);
+/* Point-to-point update of the chain from its 32 reduced doubles ({0..2: sum w p, 3..5: sum w q, 6..14: sum w q p^T
+   row-major, 15..17: 0 (origin), 28: sum w}; the frames' origin): the column-major 4x4 dT of T_iter <- dT T_iter;
+   *rank = rank of the cross-covariance.  REG_NO_CORRESPONDENCES when sums[28] == 0. */
+REG_API reg_status reg_host_pm_p2p_update(const double sums[32], double T_update[16], int32_t* rank);
+
 /* Launch plan of the persistent tail kernel (csrc/kernels_tail.hpp) for a reading of n points on a device with `cus`
    compute units: plan = {usable (0/1), workgroups, workgroups per XCD class, reading points per XCD class}.  Octet
    oc = (s >> 3) * plan[2] + (b >> 3) of XCD class x = b & 7 is, with tile == 0, octet oc of the class's contiguous share

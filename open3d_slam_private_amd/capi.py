@@ -108,6 +108,20 @@ class TargetInfo(C.Structure):
                 ("centroid", C.c_float * 3), ("dims", C.c_int32 * 3)]
 
 
+class PmChain(C.Structure):
+    """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint)."""
+    _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("minimizer", C.c_int32), ("use_robust", C.c_int32),
+                ("robust_fct", C.c_int32), ("tuning", C.c_float), ("scale_estimator", C.c_int32),
+                ("nb_iter_for_scale", C.c_int32), ("distance_type", C.c_int32), ("approximation", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+PM_POINT_TO_PLANE, PM_POINT_TO_POINT = 0, 1
+ROBUST_FCTS = {"cauchy": 0, "welsch": 1, "sc": 2, "gm": 3, "tukey": 4, "huber": 5, "L1": 6, "student": 7}
+SCALE_ESTIMATORS = {"none": 0, "mad": 1, "berg": 2, "std": 3}
+DISTANCE_TYPES = {"point2point": 0, "point2plane": 1}
+
+
 EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destroy", "reg_last_error",
            "reg_set_stream", "reg_set_target", "reg_set_source", "reg_register", "reg_compute", "reg_prepare",
            "reg_linearize", "reg_get_correspondences", "reg_match_local", "reg_trim_histogram", "reg_reduce_local",
@@ -119,7 +133,9 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure",
            "reg_dist_get_unique_id", "reg_dist_init", "reg_dist_init_custom", "reg_dist_register", "reg_dist_shutdown",
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
-           "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update"]
+           "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
+           "reg_default_pm_chain", "reg_check_pm_chain", "reg_set_pm_chain", "reg_get_robust_state",
+           "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update"]
 
 
 def lib_path() -> str:
@@ -217,6 +233,14 @@ def load_library():
     lib.reg_smooth_normals.argtypes = [vp, vp, vp, i64, C.c_int, C.c_int, vp]
     lib.reg_estimate_normals.argtypes = [vp, vp, i64, i64, C.c_int, C.c_int, C.c_float, vp, C.c_int,
                                          C.POINTER(NormalsOut), C.POINTER(C.c_int64)]
+    lib.reg_default_pm_chain.argtypes = [C.POINTER(PmChain)]
+    lib.reg_default_pm_chain.restype = None
+    lib.reg_check_pm_chain.argtypes = [C.POINTER(RegParams), C.POINTER(PmChain)]
+    lib.reg_set_pm_chain.argtypes = [vp, C.POINTER(PmChain)]
+    lib.reg_get_robust_state.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    lib.reg_get_correspondences_k.argtypes = [vp, C.c_int32, vp, vp, vp]
+    lib.reg_host_robust_weights.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, vp, i64, vp]
+    lib.reg_host_pm_p2p_update.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the library does not export what the header declares
     _lib = lib
@@ -233,6 +257,41 @@ def shipped_params() -> RegParams:
     p = RegParams()
     load_library().reg_shipped_params(C.byref(p))
     return p
+
+
+def default_pm_chain() -> PmChain:
+    """knn 1, point-to-plane, robust off (the plain loop); robust fields at the reference's defaults."""
+    c = PmChain()
+    load_library().reg_default_pm_chain(C.byref(c))
+    return c
+
+
+def check_pm_chain(params: RegParams, chain: PmChain) -> int:
+    """reg_check_pm_chain status (0 = accepted) -- pure, no device."""
+    return int(load_library().reg_check_pm_chain(C.byref(params), C.byref(chain)))
+
+
+def host_robust_weights(fct, tuning, scale, d2, approximation=math.inf):
+    """RobustOutlierFilter weights of squared distances d2 (fp32, the device's code): fct is a name or REG_ROBUST_*."""
+    fid = ROBUST_FCTS[fct] if isinstance(fct, str) else int(fct)
+    d = np.ascontiguousarray(d2, np.float32).reshape(-1)
+    w = np.empty_like(d)
+    st = load_library().reg_host_robust_weights(fid, float(tuning), float(scale), float(approximation), _ptr(d), d.size,
+                                                _ptr(w))
+    if st != 0:
+        raise RegError(st, "reg_host_robust_weights")
+    return w
+
+
+def host_pm_p2p_update(sums):
+    """Point-to-point update dT (4x4 float64, math layout; T_iter <- dT T_iter) and rank from the chain's 32 sums."""
+    s = np.ascontiguousarray(sums, np.float64).reshape(32)
+    U = np.zeros(16, np.float64)
+    rank = C.c_int32()
+    st = load_library().reg_host_pm_p2p_update(_ptr(s), _ptr(U), C.byref(rank))
+    if st != 0:
+        raise RegError(st, "reg_host_pm_p2p_update")
+    return U.reshape(4, 4).T.copy(), rank.value
 
 
 def _f32(a):
@@ -507,6 +566,31 @@ class Registration:
         w = np.empty(n, np.float32) if want_w else None
         self._check(self._lib.reg_get_correspondences(self._h, _ptr(ids), _ptr(d2), _ptr(w)))
         return ids, d2, w
+
+    def set_pm_chain(self, chain: "PmChain | None"):
+        """reg_set_pm_chain: None (or the default chain) returns to the plain loop; resets the robust state."""
+        if chain is not None:
+            chain.struct_size = C.sizeof(PmChain)
+        self.pm_chain = chain
+        self._check(self._lib.reg_set_pm_chain(self._h, C.byref(chain) if chain is not None else None))
+
+    def get_correspondences_k(self, knn=None, want_w=True):
+        """(ids, d2, w) of the last iteration, each n x knn, reading input order, ascending (d2, id)."""
+        if knn is None:
+            knn = self.pm_chain.knn if getattr(self, "pm_chain", None) is not None else 1
+        n = self.n_source
+        ids = np.empty((n, knn), np.int32)
+        d2 = np.empty((n, knn), np.float32)
+        w = np.empty((n, knn), np.float32) if want_w else None
+        self._check(self._lib.reg_get_correspondences_k(self._h, int(knn), _ptr(ids), _ptr(d2), _ptr(w)))
+        return ids, d2, w
+
+    def robust_state(self):
+        """(scale, iteration) of the chain's RobustOutlierFilter as the next registration starts with them."""
+        sc = C.c_float()
+        it = C.c_int32()
+        self._check(self._lib.reg_get_robust_state(self._h, C.byref(sc), C.byref(it)))
+        return float(sc.value), int(it.value)
 
     def target_info(self) -> TargetInfo:
         info = TargetInfo()

@@ -36,16 +36,19 @@ static reg_status dist_stream_wait(reg_handle* h, double timeout_s, const char* 
 
 // The Open3D costs have no distributed form (include/o3dslam_reg.h): every multi-rank entry point refuses them.
 static reg_status o3d_dist_unsupported(reg_handle* h) {
-    h->err = "the Open3D costs (REG_COST_O3D_P2PL / O3D_P2P) have no distributed path";
+    h->err = h->pm_on ? "a handle with a libpointmatcher chain (reg_set_pm_chain) has no distributed path"
+                      : "the Open3D costs (REG_COST_O3D_P2PL / O3D_P2P) have no distributed path";
     return REG_UNSUPPORTED;
 }
+// ... nor a handle with a non-default libpointmatcher chain
+static inline bool dist_unsupported(const reg_handle* h) { return cost_is_o3d(h->prm.cost) || h->pm_on; }
 
 extern "C" {
 
 // ---- distributed halves ----
 
 reg_status reg_source_centroid_sums(reg_handle* h, int64_t sums[3]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, false);
     if (s != REG_OK) return s;
     if (!sums) return REG_BAD_ARGUMENT;
@@ -58,7 +61,7 @@ reg_status reg_source_centroid_sums(reg_handle* h, int64_t sums[3]) {
 }
 
 reg_status reg_prepare_centroid(reg_handle* h, const float T_init[16], const float c_read[3]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !T_init || !c_read) return REG_BAD_ARGUMENT;
     float Tr[16];
     col_to_row(T_init, Tr);
@@ -68,7 +71,7 @@ reg_status reg_prepare_centroid(reg_handle* h, const float T_init[16], const flo
 // Stream-ordered reading preparation for the multi-GPU path (no host round trip): enqueue this rank's integer centroid
 // sums into a device buffer, let the caller all-reduce (sum) those 3 int64 on the same stream, then prepare from them.
 reg_status reg_dist_centroid_sums(reg_handle* h, void** sums_dev) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, false);
     if (s != REG_OK) return s;
     if (!sums_dev) return REG_BAD_ARGUMENT;
@@ -82,7 +85,7 @@ reg_status reg_dist_centroid_sums(reg_handle* h, void** sums_dev) {
 }
 
 reg_status reg_dist_prepare(reg_handle* h, const float T_init[16], int64_t n_global) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !T_init || n_global < 1) return REG_BAD_ARGUMENT;
     reg_status s = check_ready(h, false);
     if (s != REG_OK) return s;
@@ -105,7 +108,7 @@ reg_status reg_compose(reg_handle* h, const float T_iter[16], float T_out[16]) {
 }
 
 reg_status reg_match_local(reg_handle* h, const float T_iter[16]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     float Tr[16];
@@ -120,7 +123,7 @@ reg_status reg_match_local(reg_handle* h, const float T_iter[16]) {
 }
 
 reg_status reg_trim_histogram(reg_handle* h, int level, uint32_t prefix, uint32_t hist[2048]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     if (level < 0 || level > 2 || !hist || !h->have_match) return REG_BAD_ARGUMENT;
@@ -136,7 +139,7 @@ reg_status reg_trim_histogram(reg_handle* h, int level, uint32_t prefix, uint32_
 
 // R5-R7 on this rank's slice for the pose given to the preceding reg_match_local
 reg_status reg_reduce_local(reg_handle* h, const float T_iter[16], float trim_limit, double sums[32]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     if (!h->have_match || !sums || !T_iter) return REG_BAD_ARGUMENT;
@@ -202,7 +205,7 @@ reg_status reg_solve_update(const reg_params* p, const double sums[32], const fl
 //   phase 4: R8+R9 on the device from the global sums (identical on every rank)
 // Without TrimmedDist (or GICP) phases 1 and 2 are no-ops and no histogram needs reducing.
 reg_status reg_dist_begin(reg_handle* h, const float T_start[16]) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     float Tr[16];
@@ -223,7 +226,7 @@ reg_status reg_dist_begin(reg_handle* h, const float T_start[16]) {
 }
 
 reg_status reg_dist_buffers(reg_handle* h, void** hist, void** sums) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !hist || !sums) return REG_BAD_ARGUMENT;
     if (h->n == 0) return REG_NOT_CONFIGURED;
     *hist = h->i_hist.p;
@@ -235,7 +238,7 @@ reg_status reg_dist_buffers(reg_handle* h, void** hist, void** sums) {
 // receives the blocks of all `n_ranks` ranks in rank order (one all-gather between phase 5 and phase 6).
 reg_status reg_dist_fused_buffers(reg_handle* h, int n_ranks, int rank, void** contrib, void** gathered,
                                   int64_t* contrib_bytes) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !contrib || !gathered || !contrib_bytes || n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks)
         return REG_BAD_ARGUMENT;
     if (h->n == 0) return REG_NOT_CONFIGURED;
@@ -260,7 +263,7 @@ reg_status reg_dist_fused_buffers(reg_handle* h, int n_ranks, int rank, void** c
 //   phase 10: match            -> all-gather d2_local (n_max floats) into d2_all (n_ranks * n_max floats)
 //   phase 11: select on d2_all + linearize of the local slice + partial sums   -> all-reduce the 32 sums -> phase 4
 reg_status reg_dist_gather_buffers(reg_handle* h, int n_ranks, int64_t n_max, void** d2_local, void** d2_all) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !d2_local || !d2_all || n_ranks < 1 || n_ranks > 64) return REG_BAD_ARGUMENT;
     if (h->n == 0) return REG_NOT_CONFIGURED;
     if (n_max < h->n) {
@@ -288,7 +291,7 @@ reg_status reg_dist_gather_buffers(reg_handle* h, int n_ranks, int64_t n_max, vo
 
 // Non-blocking view of the mirror the update kernel writes (the stream-ordered drivers steer by it).
 reg_status reg_dist_poll(reg_handle* h, reg_dist_status* out) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !out) return REG_BAD_ARGUMENT;
     const HostMirror* mir = h->h_mirror;
     const unsigned long long s = mirror_seq(h);
@@ -313,7 +316,7 @@ reg_status reg_dist_poll(reg_handle* h, reg_dist_status* out) {
 // set to seq_rel when that update kernel has reported, to 0 when it has not (yet, or ever: update kernels that find the
 // loop done or stalled do not report -- out->stream_idle then tells "never").
 reg_status reg_dist_record(reg_handle* h, int64_t seq_rel, reg_dist_status* out) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !out || seq_rel < 1) return REG_BAD_ARGUMENT;
     const unsigned long long want = h->dist_seq0 + (unsigned long long)seq_rel;
     // idle must be sampled BEFORE the record: "idle and no record" then really means the kernel did not report
@@ -341,7 +344,7 @@ reg_status reg_dist_record(reg_handle* h, int64_t seq_rel, reg_dist_status* out)
 }
 
 reg_status reg_dist_phase(reg_handle* h, int phase) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     const bool trim = h->prm.cost == REG_COST_P2PL && h->prm.use_trimmed;
@@ -480,7 +483,7 @@ reg_status reg_dist_phase(reg_handle* h, int phase) {
 }
 
 reg_status reg_dist_xicp_buffers(reg_handle* h, void** center, void** sums) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !center || !sums) return REG_BAD_ARGUMENT;
     if (!h->device_ok) return REG_DEVICE_ERROR;
     if (!h->prm.use_xicp) {
@@ -497,7 +500,7 @@ reg_status reg_dist_xicp_buffers(reg_handle* h, void** center, void** sums) {
 
 // Waits for everything enqueued on the stream, then reports like reg_register (T_out composed with R10).
 reg_status reg_dist_finish(reg_handle* h, float T_out[16], reg_result* res) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     if (!T_out) return REG_BAD_ARGUMENT;

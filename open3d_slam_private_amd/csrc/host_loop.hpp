@@ -100,6 +100,7 @@ static reg_status prepare_rowmajor(reg_handle* h, const float* T_init_row, const
     h->prepared = true;
     h->match_launches = 0;
     h->have_match = false;
+    h->pm_have_match = false;
     return REG_OK;
 }
 
@@ -638,6 +639,208 @@ static int sequence_limit(const reg_params& p) {
     return p.max_iter + (o3d_rule ? 1 : 0);
 }
 
+
+// ---- libpointmatcher chain extension (reg_set_pm_chain; kernels_pmchain.hpp) --------------------------------------
+
+static bool pm_chain_is_default(const reg_pm_chain* c) {
+    return c->knn == 1 && c->minimizer == REG_PM_POINT_TO_PLANE && !c->use_robust;
+}
+
+static PmCfg make_pm_cfg(const reg_handle* h) {
+    const reg_pm_chain& c = h->pm;
+    PmCfg f;
+    f.knn = c.knn;
+    f.minimizer = c.minimizer;
+    f.use_robust = c.use_robust;
+    f.robust_fct = c.robust_fct;
+    f.scale_estimator = c.scale_estimator;
+    f.nb_iter_for_scale = c.nb_iter_for_scale;
+    f.distance_type = c.distance_type;
+    f.use_trim = h->prm.use_trimmed;
+    f.use_normal = h->prm.use_surface_normal;
+    f.use_maxdist = h->prm.use_max_dist_filter;
+    // berg: the configured tuning is the target scale; the function's own constant replaces it (Bergstrom 2014,
+    // OutlierFiltersImpl.cpp:430-445)
+    f.tuning = c.tuning;
+    f.berg_target = c.tuning;
+    if (c.scale_estimator == REG_SCALE_BERG) {
+        if (c.robust_fct == REG_ROBUST_CAUCHY) f.tuning = 4.3040f;
+        else if (c.robust_fct == REG_ROBUST_TUKEY) f.tuning = 7.0589f;
+        else if (c.robust_fct == REG_ROBUST_HUBER) f.tuning = 2.0138f;
+    }
+    f.sq_approx = std::isinf(c.approximation) ? INFINITY : (float)((double)c.approximation * (double)c.approximation);
+    f.cos_max_angle = std::cos(h->prm.max_normal_angle);
+    const float md = h->prm.outlier_max_dist;
+    f.outlier_max_d2 = md * md;
+    return f;
+}
+
+// One exact select over nk keys (+inf keys are not counted) -> sel[slot]: the value of rank trim_rank(finite, ratio)
+// (getDistsQuantile: index size * quantile in float), or with median != 0 of rank finite / 2 (getMedianAbsDeviation: the
+// integer index, which differs from the float form once more than 2^24 keys are finite)
+static void enqueue_pm_select(reg_handle* h, const float* keys, int64_t nk, float ratio, int slot, int median = 0) {
+    uint32_t* hist = h->pm_hist.as<uint32_t>();
+    SelectState* st = h->pm_sel.as<SelectState>();
+    const IterState* it = h->i_iter.as<IterState>();
+    const int hb = (int)std::min<int64_t>(128, grid_for(nk));
+    k_hist_level0<<<hb, 256, 0, h->stream>>>(keys, nk, h->shift0, hist, it);
+    k_pm_select_level1<<<hb, 256, 0, h->stream>>>(keys, nk, h->shift0, ratio, median, hist, hist + 2048, st, it);
+    k_select_level<<<hb, 256, 0, h->stream>>>(keys, nk, 2, h->shift0, ratio, hist + 2048, hist + 4096, hist, st, it);
+    k_pm_select_finish<<<1, 256, 0, h->stream>>>(hist, st, h->shift0, h->pm_state.as<PmState>(), slot, it);
+}
+
+// One generic iteration of the chain; nothing waits on the host
+static reg_status enqueue_pm_iteration(reg_handle* h) {
+    const IterState* it = h->i_iter.as<IterState>();
+    const reg_pm_chain& c = h->pm;
+    const int64_t n = h->n, nk = n * (int64_t)c.knn;
+    const PmCfg cfg = make_pm_cfg(h);
+    int* kpos = h->pm_pos.as<int>();
+    float* kd2 = h->pm_d2.as<float>();
+    const unsigned blocks = (unsigned)((n + 15) / 16);
+    const float4* src = h->s_xyz.as<float4>();
+    if (c.knn <= 2)
+        k_match_knn<2><<<blocks, 256, 0, h->stream>>>(h->grid, src, n, c.knn, it, kpos, kd2);
+    else if (c.knn <= 4)
+        k_match_knn<4><<<blocks, 256, 0, h->stream>>>(h->grid, src, n, c.knn, it, kpos, kd2);
+    else if (c.knn <= 8)
+        k_match_knn<8><<<blocks, 256, 0, h->stream>>>(h->grid, src, n, c.knn, it, kpos, kd2);
+    else
+        k_match_knn<16><<<blocks, 256, 0, h->stream>>>(h->grid, src, n, c.knn, it, kpos, kd2);
+    if (cfg.use_trim) enqueue_pm_select(h, kd2, nk, h->prm.trim_ratio, 2);
+    if (c.use_robust) {
+        // MAD: median(d2) at the integer index size / 2; berg: getDistsQuantile(0.5), the float index
+        if (c.scale_estimator == REG_SCALE_MAD || c.scale_estimator == REG_SCALE_BERG)
+            enqueue_pm_select(h, kd2, nk, 0.5f, 0, c.scale_estimator == REG_SCALE_MAD ? 1 : 0);
+        if (c.scale_estimator == REG_SCALE_MAD) {
+            k_pm_absdev<<<(unsigned)std::min<int64_t>(1024, grid_for(nk)), 256, 0, h->stream>>>(kd2, nk, h->pm_state.as<PmState>(),
+                                                                                               h->pm_keys.as<float>(), it);
+            enqueue_pm_select(h, h->pm_keys.as<float>(), nk, 0.5f, 1, 1);
+        }
+        k_pm_scale<<<1, 64, 0, h->stream>>>(h->pm_state.as<PmState>(), cfg, it);
+    }
+    const int lb = (int)std::min<int64_t>(kPmLinBlocks, grid_for(nk));
+    const float4* snrm = h->has_snrm ? h->s_nrm.as<float4>() : nullptr;
+    const float4* tnrm = h->has_tnrm ? h->t_nrm.as<float4>() : nullptr;
+    if (c.minimizer == REG_PM_POINT_TO_POINT)
+        k_pm_linearize<true><<<lb, 256, 0, h->stream>>>(src, snrm, n, it, kpos, kd2, h->t_pts.as<float4>(), tnrm, cfg,
+                                                        h->pm_state.as<PmState>(), h->pm_w.as<float>(), h->pm_partials.as<double>());
+    else
+        k_pm_linearize<false><<<lb, 256, 0, h->stream>>>(src, snrm, n, it, kpos, kd2, h->t_pts.as<float4>(), tnrm, cfg,
+                                                         h->pm_state.as<PmState>(), h->pm_w.as<float>(), h->pm_partials.as<double>());
+    ++h->seq;
+    k_pm_update<<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
+                                          h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
+                                          cfg.use_trim);
+    HIPCHK(h, hipGetLastError());
+    h->have_match = true;
+    h->pm_have_match = true;
+    return REG_OK;
+}
+
+// reg_register for a handle with a chain: prepare as the plain loop (centred frames), then generic iterations only,
+// at most lookahead sequences in flight, the same sequence limit as the plain loop
+static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], reg_result* res) {
+    if (pm_needs_tnrm(h) && !h->has_tnrm && h->m > 0) {
+        h->err = "InvalidField: this chain needs the `normals` descriptor on the reference";
+        return REG_MISSING_FIELD;
+    }
+    reg_status s = check_ready(h, false);
+    if (s != REG_OK) return s;
+    const int64_t nk = h->n * (int64_t)h->pm.knn;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->pm_pos.reserve((size_t)nk * 4));
+    HIPCHK(h, h->pm_d2.reserve((size_t)nk * 4));
+    HIPCHK(h, h->pm_w.reserve((size_t)nk * 4));
+    HIPCHK(h, h->pm_keys.reserve((size_t)nk * 4));
+    HIPCHK(h, h->pm_partials.reserve((size_t)kPmLinBlocks * kSums * 8));
+    HIPCHK(h, h->pm_sel.reserve(sizeof(SelectState)));
+    if (!h->pm_hist.p) {
+        HIPCHK(h, h->pm_hist.reserve(3 * 2048 * 4));
+        HIPCHK(h, hipMemsetAsync(h->pm_hist.p, 0, 3 * 2048 * 4, h->stream));
+    }
+    float T_start[16];
+    m4_identity(T_start);
+    std::memcpy(h->T_init, Ti, 64);
+    IterState st0;
+    s = build_iter_state(h, T_start, 1, &st0);
+    if (s != REG_OK) return s;
+    st0.use_trim = 0;   // the chain's own selects; no band prediction
+    s = prepare_rowmajor(h, Ti, nullptr, 0, &st0);
+    if (s != REG_OK) return s;
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    const unsigned long long seq0 = h->seq;
+    const int limit = sequence_limit(h->prm);
+    const int kAhead = std::max(1, h->env.lookahead);
+    const HostMirror* mir = h->h_mirror;
+    unsigned long long acked = seq0;
+    for (;;) {
+        const unsigned long long m_seq = std::max(mirror_seq(h), seq0);
+        const bool any = m_seq > seq0;
+        if (any && mir->done) break;
+        acked = std::max(acked, m_seq);
+        const int completed = any ? mir->iterations : 0;
+        const int inflight = (int)(h->seq - acked);
+        if (completed + inflight < limit && inflight < kAhead) {
+            s = enqueue_pm_iteration(h);
+            if (s != REG_OK) return s;
+            continue;
+        }
+        if (inflight == 0) break;
+        s = wait_seq(h, acked + 1);
+        if (s != REG_OK) return s;
+        if (mirror_seq(h) <= acked) {
+            if (hipStreamQuery(h->stream) == hipSuccess && mirror_seq(h) <= acked) acked = h->seq;
+        }
+    }
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipEventSynchronize(h->ev1));
+    (void)hipEventElapsedTime(&res->loop_ms, h->ev0, h->ev1);
+    HIPCHK(h, hipGetLastError());
+    const double* sums = mir->sums;
+    res->iterations = mir->iterations;
+    for (int k = 0; k < 6; ++k) res->localizable[k] = 1;
+    res->converged = mir->converged;
+    res->max_iter_reached = mir->max_iter_reached;
+    res->rank_last = mir->rank_last;
+    fill_result(h, sums, res, (double)h->n);
+    // chain counts (kernels_pmchain.hpp: 29 finite pairs, 30 sum d2 over the inliers, 31 inliers)
+    res->n_inliers = (int64_t)llround(sums[31]);
+    res->n_matched = (int64_t)llround(sums[29]);
+    res->fitness = sums[31] / ((double)h->n * (double)h->pm.knn);
+    res->inlier_rmse = sums[31] > 0 ? std::sqrt(sums[30] / sums[31]) : 0.0;
+    sums_to_system(sums, h->pm.minimizer == REG_PM_POINT_TO_POINT ? REG_COST_O3D_P2P : REG_COST_P2PL, res->H_last, res->b_last);
+    if (mir->status != REG_OK) {
+        h->err = "ErrorMinimizer: no point to minimize (or no finite distance for a statistic of the chain)";
+        return (reg_status)mir->status;
+    }
+    float T_iter[16], Tout_row[16];
+    std::memcpy(T_iter, mir->T, 64);
+    compose_rowmajor(h, T_iter, Tout_row, /*later_kernel_reported=*/true);
+    row_to_col(T_iter, res->T_iter_last);
+    row_to_col(mir->T_prev, res->T_iter_prev);
+    row_to_col(Tout_row, T_out);
+    res->n_band_stalls = 0;
+    res->n_tail_launches = 0;
+    res->n_tail_iterations = 0;
+    h->last_stalls = 0;
+    h->last_tail_launches = 0;
+    h->last_tail_iters = 0;
+    return REG_OK;
+}
+
+static reg_status write_pm_state(reg_handle* h) {
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->pm_state.reserve(sizeof(PmState)));
+    PmState ps;
+    std::memset(&ps, 0, sizeof(ps));
+    ps.scale = 0.f;        // RobustOutlierFilter's constructor: scale(0.0), iteration(1)
+    ps.iteration = 1;
+    HIPCHK(h, hipMemcpyAsync(h->pm_state.p, &ps, sizeof(ps), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return REG_OK;
+}
+
 extern "C" {
 
 void reg_host_tail_plan(int64_t n, int32_t cus, int32_t tile, int32_t plan[4]) {
@@ -662,6 +865,10 @@ reg_status reg_linearize(reg_handle* h, const float T_iter[16], float H[36], flo
     if (!T_iter) return REG_BAD_ARGUMENT;
     if (h->prm.cost == REG_COST_O3D_P2P) {
         h->err = "reg_linearize: point-to-point (Umeyama) has no normal equations";
+        return REG_UNSUPPORTED;
+    }
+    if (h->pm_on) {
+        h->err = "reg_linearize: not available with a libpointmatcher chain (reg_set_pm_chain)";
         return REG_UNSUPPORTED;
     }
     float Tr[16];
@@ -699,6 +906,7 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
             fprintf(stderr, "[o3dreg] register %-14s t=%.1fus\n", what,
                     std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_reg0).count());
     };
+    if (h->pm_on) return register_pm(h, Ti, T_out, res);
     const bool p2pl = h->prm.cost == REG_COST_P2PL;
     float T_start[16];
     if (p2pl)
@@ -1047,6 +1255,13 @@ reg_status reg_get_correspondences(reg_handle* h, int32_t* ids, float* d2, float
         h->err = "no iteration has run yet";
         return REG_NOT_CONFIGURED;
     }
+    if (h->pm_on) {
+        if (h->pm.knn != 1) {
+            h->err = "reg_get_correspondences: the chain matches knn > 1 neighbours; use reg_get_correspondences_k";
+            return REG_UNSUPPORTED;
+        }
+        return reg_get_correspondences_k(h, 1, ids, d2, w);
+    }
     HIPCHK(h, hipSetDevice(h->prm.device));
     const int64_t n = h->n;
     if (ids) {
@@ -1065,6 +1280,135 @@ reg_status reg_get_correspondences(reg_handle* h, int32_t* ids, float* d2, float
         HIPCHK(h, hipMemcpyAsync(w, h->i_tmpf.as<float>() + n, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return REG_OK;
+}
+
+void reg_default_pm_chain(reg_pm_chain* c) {
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->struct_size = (int32_t)sizeof(reg_pm_chain);
+    c->knn = 1;
+    c->minimizer = REG_PM_POINT_TO_PLANE;
+    c->use_robust = 0;
+    // RobustOutlierFilter defaults (OutlierFiltersImpl.h:230-244)
+    c->robust_fct = REG_ROBUST_CAUCHY;
+    c->tuning = 1.0f;
+    c->scale_estimator = REG_SCALE_MAD;
+    c->nb_iter_for_scale = 0;
+    c->distance_type = REG_DIST_POINT2POINT;
+    c->approximation = std::numeric_limits<float>::infinity();
+}
+
+reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c) {
+    if (!p || !c) return REG_BAD_ARGUMENT;
+    if (c->struct_size != (int32_t)sizeof(reg_pm_chain)) return REG_BAD_ARGUMENT;
+    if (p->cost != REG_COST_P2PL) return REG_BAD_ARGUMENT;
+    if (c->knn < 1 || c->knn > kPmMaxKnn) return REG_BAD_ARGUMENT;
+    if (c->minimizer != REG_PM_POINT_TO_PLANE && c->minimizer != REG_PM_POINT_TO_POINT) return REG_BAD_ARGUMENT;
+    if (c->use_robust) {
+        if (c->robust_fct < REG_ROBUST_CAUCHY || c->robust_fct > REG_ROBUST_STUDENT) return REG_BAD_ARGUMENT;
+        if (!(c->tuning >= 1e-7f)) return REG_BAD_ARGUMENT;                       // "tuning" range [1e-7, inf]
+        if (c->scale_estimator == REG_SCALE_STD) return REG_UNSUPPORTED;          // see include/o3dslam_reg.h
+        if (c->scale_estimator < REG_SCALE_NONE || c->scale_estimator > REG_SCALE_BERG) return REG_BAD_ARGUMENT;
+        if (c->nb_iter_for_scale < 0 || c->nb_iter_for_scale > 100) return REG_BAD_ARGUMENT;
+        if (c->distance_type != REG_DIST_POINT2POINT && c->distance_type != REG_DIST_POINT2PLANE) return REG_BAD_ARGUMENT;
+        if (!(c->approximation >= 0.f)) return REG_BAD_ARGUMENT;                  // [0, inf]
+    }
+    if (p->use_xicp && !pm_chain_is_default(c)) return REG_UNSUPPORTED;
+    return REG_OK;
+}
+
+reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    reg_pm_chain nc;
+    if (c) {
+        const reg_status s = reg_check_pm_chain(&h->prm, c);
+        if (s != REG_OK) return s;
+        nc = *c;
+    } else {
+        reg_default_pm_chain(&nc);
+    }
+    const bool on = !pm_chain_is_default(&nc);
+    const reg_pm_chain old = h->pm;
+    const bool old_on = h->pm_on;
+    h->pm = nc;
+    h->pm_on = on;
+    // a reference set without normals (allowed for a chain that reads none) cannot serve a chain that needs them
+    if (h->m > 0 && !h->has_tnrm && (!on || pm_needs_tnrm(h))) {
+        h->pm = old;
+        h->pm_on = old_on;
+        h->err = "InvalidField: the reference was set without normals; this chain needs them";
+        return REG_MISSING_FIELD;
+    }
+    h->have_match = false;   // the buffers of the last iteration belong to the previous chain
+    h->pm_have_match = false;
+    return write_pm_state(h);
+}
+
+reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32_t* iteration) {
+    if (!h) return REG_BAD_ARGUMENT;
+    PmState ps;
+    std::memset(&ps, 0, sizeof(ps));
+    ps.iteration = 1;
+    if (h->pm_state.p) {
+        if (!h->device_ok || hipSetDevice(h->prm.device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+            hipMemcpy(&ps, h->pm_state.p, sizeof(ps), hipMemcpyDeviceToHost) != hipSuccess)
+            return REG_DEVICE_ERROR;
+    }
+    if (scale) *scale = ps.scale;
+    if (iteration) *iteration = ps.iteration;
+    return REG_OK;
+}
+
+reg_status reg_get_correspondences_k(reg_handle* h, int32_t knn, int32_t* ids, float* d2, float* w) {
+    reg_status s = check_ready(h, true);
+    if (s != REG_OK) return s;
+    if (!h->pm_on) {
+        if (knn != 1) return REG_BAD_ARGUMENT;
+        return reg_get_correspondences(h, ids, d2, w);
+    }
+    if (knn != h->pm.knn) {
+        h->err = "reg_get_correspondences_k: knn differs from the chain's";
+        return REG_BAD_ARGUMENT;
+    }
+    const int64_t nk = h->n * (int64_t)knn;
+    if (!h->pm_have_match || h->pm_pos.cap < (size_t)nk * 4 || h->pm_d2.cap < (size_t)nk * 4 || h->pm_w.cap < (size_t)nk * 4) {
+        h->err = "no chain registration has run on this reading";
+        return REG_NOT_CONFIGURED;
+    }
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->i_ids.reserve((size_t)nk * 4));
+    HIPCHK(h, h->i_tmpf.reserve((size_t)nk * 8));
+    int32_t* d_ids = h->i_ids.as<int32_t>();
+    float* d_d2 = h->i_tmpf.as<float>();
+    float* d_w = h->i_tmpf.as<float>() + nk;
+    k_pm_unpermute<<<grid_for(nk), 256, 0, h->stream>>>(h->pm_pos.as<int>(), h->pm_d2.as<float>(), h->pm_w.as<float>(),
+                                                        h->t_pts.as<float4>(), h->n, knn, h->perm, ids ? d_ids : nullptr,
+                                                        d2 ? d_d2 : nullptr, w ? d_w : nullptr);
+    if (ids) HIPCHK(h, hipMemcpyAsync(ids, d_ids, (size_t)nk * 4, hipMemcpyDeviceToHost, h->stream));
+    if (d2) HIPCHK(h, hipMemcpyAsync(d2, d_d2, (size_t)nk * 4, hipMemcpyDeviceToHost, h->stream));
+    if (w) HIPCHK(h, hipMemcpyAsync(w, d_w, (size_t)nk * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return REG_OK;
+}
+
+reg_status reg_host_robust_weights(int32_t fct, float tuning, float scale, float approximation, const float* d2_or_e,
+                                   int64_t n, float* w) {
+    if (fct < REG_ROBUST_CAUCHY || fct > REG_ROBUST_STUDENT || n < 0 || (n > 0 && (!d2_or_e || !w))) return REG_BAD_ARGUMENT;
+    const float sq = std::isinf(approximation) ? INFINITY : (float)((double)approximation * (double)approximation);
+    for (int64_t i = 0; i < n; ++i) w[i] = pm_robust_weight(fct, tuning, scale, sq, d2_or_e[i]);
+    return REG_OK;
+}
+
+reg_status reg_host_pm_p2p_update(const double sums[32], double T_update[16], int32_t* rank) {
+    if (!sums || !T_update) return REG_BAD_ARGUMENT;
+    if (!(sums[28] > 0.0)) return REG_NO_CORRESPONDENCES;
+    double U[16];
+    const int r = o3d_update_p2p(sums, U);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) T_update[4 * j + i] = U[4 * i + j];   // row-major -> column-major
+    if (rank) *rank = r;
     return REG_OK;
 }
 

@@ -667,4 +667,68 @@ O3D_HD inline int o3d_update(bool point_to_point, const double* s, double* U) {
     return point_to_point ? o3d_update_p2p(s, U) : o3d_update_p2pl(s, U);
 }
 
+// ---------------------------------------------------------------------------------------------
+// RobustOutlierFilter::robustFiltering (OutlierFiltersImpl.cpp:545-598), one entry, fp32 in the reference's operation
+// order: e2 = d / (scale * scale); k2 = k * k; the ARBITRARY_SMALL_VALUE clamp compares in double and stores
+// (float)1e-50 == 0 (a no-op but for -0 / 0); sq_approx = (float)(approximation^2 in double), +inf = off.
+// The chain's weight kernel and reg_host_robust_weights run exactly this code.
+// ---------------------------------------------------------------------------------------------
+O3D_HD inline float pm_robust_weight(int fct, float k, float scale, float sq_approx, float d) {
+    const float s2 = scale * scale;
+    const float e2 = d / s2;
+    const float k2 = k * k;
+    float w = 0.f;
+    switch (fct) {
+        case 0: {   // cauchy: 1 / (1 + e2 / k2)
+            const float a = e2 / k2;
+            w = 1.f / (1.f + a);
+            break;
+        }
+        case 1: {   // welsch: exp(-e2 / k2)
+            const float a = -e2 / k2;
+            w = expf(a);
+            break;
+        }
+        case 2: {   // sc: e2 >= k ? 4 k2 / (k + e2)^2 : 1
+            const float a = k + e2;
+            const float inv = 1.f / (a * a);
+            const float c = 4.f * k2;   // (float)(4.0 * k2): a power of two, exact
+            w = e2 >= k ? c * inv : 1.f;
+            break;
+        }
+        case 3: {   // gm: k2 / (k + e2)^2
+            const float a = k + e2;
+            const float inv = 1.f / (a * a);
+            w = k2 * inv;
+            break;
+        }
+        case 4: {   // tukey: e2 >= k2 ? 0 : (1 - e2 / k2)^2
+            const float a = 1.f - e2 / k2;
+            w = e2 >= k2 ? 0.f : a * a;
+            break;
+        }
+        case 5: {   // huber: e2 >= k2 ? k / sqrt(e2) : 1
+            const float inv = 1.f / sqrtf(e2);
+            w = e2 >= k2 ? k * inv : 1.f;
+            break;
+        }
+        case 6:     // L1: 1 / sqrt(e2)
+            w = 1.f / sqrtf(e2);
+            break;
+        case 7: {   // student, d = 3: (1 + e2 / k)^(-(k + 3) / 2) (k + 3) / (k + e2)
+            const float dd = 3.f;
+            const float ex = -(k + dd) / 2.f;
+            const float p = powf(1.f + e2 / k, ex);
+            const float inv = 1.f / (k + e2);
+            w = p * (k + dd) * inv;
+            break;
+        }
+        default:
+            break;
+    }
+    if ((double)w <= 1e-50) w = (float)1e-50;
+    if (sq_approx != INFINITY && e2 >= sq_approx) w = 0.f;
+    return w;
+}
+
 }  // namespace o3dreg

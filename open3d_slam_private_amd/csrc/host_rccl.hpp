@@ -382,7 +382,7 @@ static reg_status dist_init_common(reg_handle* h, int rank, int n_ranks, DistCtx
 }
 
 reg_status reg_dist_init(reg_handle* h, const char id[REG_DIST_ID_BYTES], int rank, int n_ranks) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!id) return REG_BAD_ARGUMENT;
     DistCtx* d = nullptr;
     reg_status s = dist_init_common(h, rank, n_ranks, &d);
@@ -406,7 +406,7 @@ reg_status reg_dist_init(reg_handle* h, const char id[REG_DIST_ID_BYTES], int ra
 }
 
 reg_status reg_dist_init_custom(reg_handle* h, const reg_collectives* c, int rank, int n_ranks) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!c || (n_ranks > 1 && (!c->all_reduce_sum || !c->all_gather))) return REG_BAD_ARGUMENT;
     DistCtx* d = nullptr;
     reg_status s = dist_init_common(h, rank, n_ranks, &d);
@@ -476,7 +476,7 @@ static reg_status dist_enqueue_fused(reg_handle* h) {
 // == ICP::compute for a reading that is point-partitioned over the ranks of the group.  Collective: every rank calls it
 // with the same T_init; every rank returns the same T_out and the GLOBAL result figures.
 reg_status reg_dist_register(reg_handle* h, const float T_init[16], float T_out[16], reg_result* res) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !T_init || !T_out) return REG_BAD_ARGUMENT;
     if (!h->dist) {
         h->err = "reg_dist_register: reg_dist_init has not been called";
@@ -538,7 +538,7 @@ reg_status reg_dist_register(reg_handle* h, const float T_init[16], float T_out[
 }
 
 reg_status reg_dist_info(reg_handle* h, int64_t* n_global, int32_t* n_generic, int32_t* n_fused, int32_t* n_stalls) {
-    if (h && cost_is_o3d(h->prm.cost)) return o3d_dist_unsupported(h);
+    if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!h || !h->dist) return REG_NOT_CONFIGURED;
     if (n_global) *n_global = h->dist->n_global;
     reg_dist_steer_counts(&h->dist->last_steer, n_generic, n_fused, n_stalls);

@@ -180,6 +180,13 @@ struct reg_handle {
     int shift0 = 21;                  // low bit of the level-0 radix digit (19 when max_dist^2 < 2: bits 31,30 are 0)
     int n_blocks = 0;
     bool have_match = false;
+    // libpointmatcher chain extension (reg_set_pm_chain; kernels_pmchain.hpp): pm_on = a non-default chain is set
+    bool pm_on = false;
+    reg_pm_chain pm;
+    // the chain's N x knn buffers hold the last iteration of a chain registration on the current reading (the plain
+    // entry points -- reg_information_matrix, ... -- set have_match but never fill these)
+    bool pm_have_match = false;
+    DevBuf pm_pos, pm_d2, pm_w, pm_keys, pm_hist, pm_sel, pm_state, pm_partials;
 };
 
 #define HIPCHK(h, call)                                                                        \
@@ -198,6 +205,12 @@ static inline int grid_for(int64_t n, int block = 256) { return (int)((n + block
 
 // The two Open3D RegistrationICP costs (select-free iterations, input frame, Open3D stop rule; include/o3dslam_reg.h)
 static inline bool cost_is_o3d(int cost) { return cost == REG_COST_O3D_P2PL || cost == REG_COST_O3D_P2P; }
+
+// A chain that reads reference normals: point-to-plane, the surface-normal filter or the robust point-to-plane distance
+static inline bool pm_needs_tnrm(const reg_handle* h) {
+    return h->pm.minimizer == REG_PM_POINT_TO_PLANE || h->prm.use_surface_normal ||
+           (h->pm.use_robust && h->pm.distance_type == REG_DIST_POINT2PLANE);
+}
 
 extern "C" {
 
@@ -313,7 +326,8 @@ void reg_destroy(reg_handle* h) {
                       &h->t_vals2, &h->t_pts, &h->t_nrm, &h->t_cov, &h->t_flags, &h->t_scan, &h->t_hash, &h->t_cells,
                       &h->t_tmp, &h->t_misc, &h->t_dir, &h->t_rows, &h->s_raw, &h->s_nrm_raw, &h->s_cov_raw, &h->s_xyz, &h->s_nrm, &h->s_cov,
                       &h->s_misc, &h->i_pos, &h->i_d2, &h->i_w, &h->i_hist, &h->i_state, &h->i_partials, &h->i_sums,
-                      &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band};
+                      &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
+                      &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials};
     for (DevBuf* b : bufs) b->release();
     if (h->h_mirror) (void)hipHostFree(h->h_mirror);
     if (h->h_iter) (void)hipHostFree(h->h_iter);
@@ -611,12 +625,14 @@ static reg_status set_target_impl(reg_handle* h, const float* xyz, int64_t xyz_s
     h->m = 0;
     h->crop_kept = 0;
     h->have_match = false;
+    h->pm_have_match = false;
     if (m <= 0) {
         h->err = "The reference point cloud is empty";
         return REG_EMPTY_TARGET;
     }
     if (!xyz || xyz_stride < 3 || (nrm && nrm_stride < 3) || m > 0x7fffffffLL) return REG_BAD_ARGUMENT;
-    if ((h->prm.cost == REG_COST_P2PL || h->prm.cost == REG_COST_O3D_P2PL) && !nrm && !h->structure_only) {
+    if ((h->prm.cost == REG_COST_P2PL || h->prm.cost == REG_COST_O3D_P2PL) && !nrm && !h->structure_only &&
+        !(h->pm_on && !pm_needs_tnrm(h))) {
         h->err = "InvalidField: point-to-plane needs the `normals` descriptor on the reference";
         return REG_MISSING_FIELD;
     }
@@ -1285,6 +1301,7 @@ reg_status reg_set_source(reg_handle* h, const float* xyz, int64_t xyz_stride, c
     h->n = 0;
     h->prepared = false;
     h->have_match = false;
+    h->pm_have_match = false;
     if (n <= 0) {
         h->err = "The reading point cloud is empty.";
         return REG_EMPTY_SOURCE;
@@ -1378,6 +1395,7 @@ reg_status reg_set_source_f64(reg_handle* h, const double* xyz, const double* no
     h->n = 0;
     h->prepared = false;
     h->have_match = false;
+    h->pm_have_match = false;
     if (n <= 0) {
         h->err = "The reading point cloud is empty.";
         return REG_EMPTY_SOURCE;

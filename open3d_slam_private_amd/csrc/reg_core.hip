@@ -44,6 +44,7 @@ using namespace o3dreg;
 #include "kernels_update.hpp"
 #include "kernels_tail.hpp"
 #include "kernels_normals.hpp"
+#include "kernels_pmchain.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"

@@ -212,6 +212,82 @@ class ICP:
         return self.compute(readingIn, referenceIn, T_refIn_readIn, True)
 
 
+class PointMatcherICP(ICP):
+    """ICP with the libpointmatcher chain extension (include/o3dslam_reg.h, reg_set_pm_chain): loadFromYaml also takes
+    KDTreeMatcher.knn up to 16, RobustOutlierFilter (OutlierFiltersImpl.h:230-244 names and defaults) and
+    PointToPointErrorMinimizer; everything else binds exactly as for ICP.  The filter's scale / iteration persist
+    across compute() calls on the same object, as in the reference."""
+
+    _ROBUST_DEFAULTS = {"robustFct": "cauchy", "tuning": 1.0, "scaleEstimator": "mad", "nbIterationForScale": 0,
+                        "distanceType": "point2point", "approximation": math.inf}
+
+    def __init__(self):
+        super().__init__()
+        self.chain: capi.PmChain | None = None
+
+    def setDefault(self):
+        super().setDefault()
+        self.chain = None
+
+    def loadFromYaml(self, stream_or_text):
+        import yaml
+        text = stream_or_text.read() if hasattr(stream_or_text, "read") else stream_or_text
+        doc = yaml.safe_load(text) or {}
+        chain = capi.default_pm_chain()
+        m = doc.get("matcher")
+        if isinstance(m, dict) and isinstance(m.get("KDTreeMatcher"), dict) and "knn" in m["KDTreeMatcher"]:
+            chain.knn = int(m["KDTreeMatcher"]["knn"])
+            m["KDTreeMatcher"] = dict(m["KDTreeMatcher"], knn=1)
+        kept = []
+        for f in doc.get("outlierFilters") or []:
+            (fname, fargs), = (f.items() if isinstance(f, dict) else [(f, {})])
+            if fname != "RobustOutlierFilter":
+                kept.append(f)
+                continue
+            if chain.use_robust:
+                raise NotImplementedError("more than one RobustOutlierFilter")
+            a = dict(self._ROBUST_DEFAULTS, **(fargs or {}))
+            unknown = set(a) - set(self._ROBUST_DEFAULTS)
+            if unknown:
+                raise InvalidParameter(f"RobustOutlierFilter: unknown parameter(s) {sorted(unknown)}")
+            if a["robustFct"] not in capi.ROBUST_FCTS:
+                raise InvalidParameter("Invalid robust function name.")
+            if a["scaleEstimator"] not in capi.SCALE_ESTIMATORS:
+                raise InvalidParameter("Invalid scale estimator name.")
+            if a["distanceType"] not in capi.DISTANCE_TYPES:
+                raise InvalidParameter("Invalid distance type name.")
+            chain.use_robust = 1
+            chain.robust_fct = capi.ROBUST_FCTS[a["robustFct"]]
+            chain.tuning = float(a["tuning"])
+            chain.scale_estimator = capi.SCALE_ESTIMATORS[a["scaleEstimator"]]
+            chain.nb_iter_for_scale = int(a["nbIterationForScale"])
+            chain.distance_type = capi.DISTANCE_TYPES[a["distanceType"]]
+            chain.approximation = float(a["approximation"])
+        if "outlierFilters" in doc:
+            doc["outlierFilters"] = kept
+        em = doc.get("errorMinimizer", "PointToPlaneErrorMinimizer")
+        if (next(iter(em)) if isinstance(em, dict) else em) == "PointToPointErrorMinimizer":
+            chain.minimizer = capi.PM_POINT_TO_POINT
+            doc["errorMinimizer"] = "PointToPlaneErrorMinimizer"
+        super().loadFromYaml(yaml.safe_dump(doc))
+        st = capi.check_pm_chain(self.params, chain)
+        if st == 9:
+            raise NotImplementedError("this chain is outside the accelerated path (std scale estimator, or X-ICP with "
+                                      "k-NN / robust weights / point-to-point)")
+        if st != 0:
+            raise InvalidParameter("invalid chain (knn must lie in 1..16; robust parameters out of range)")
+        self.chain = chain
+
+    def _ensure(self):
+        fresh = self._reg is None
+        super()._ensure()
+        if fresh and self.chain is not None:
+            try:
+                self._reg.set_pm_chain(self.chain)
+            except RegError as e:
+                raise _translate(e) from None
+
+
 @dataclass
 class SurfaceNormalDataPointsFilter:
     """SurfaceNormalDataPointsFilter (DataPointsFilters/SurfaceNormal.h:68-78, SurfaceNormal.cpp:152-252) on the
