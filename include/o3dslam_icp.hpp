@@ -247,4 +247,66 @@ private:
     reg_handle* h_ = nullptr;
 };
 
+// Base of the two data-point filter wrappers below: owns one handle, maps statuses to the reference's exceptions.
+class DeviceFilterBase {
+public:
+    DeviceFilterBase() = default;
+    ~DeviceFilterBase() { if (h_) reg_destroy(h_); }
+    DeviceFilterBase(const DeviceFilterBase&) = delete;
+    DeviceFilterBase& operator=(const DeviceFilterBase&) = delete;
+
+protected:
+    reg_handle* handle() {
+        if (!h_) {
+            reg_params p;
+            reg_default_params(&p);
+            reg_status s = reg_create(&p, &h_);
+            if (s != REG_OK) {
+                std::string msg = h_ ? reg_last_error(h_) : "reg_create failed";
+                if (h_) { reg_destroy(h_); h_ = nullptr; }
+                throw DeviceError(msg);
+            }
+        }
+        return h_;
+    }
+    void check(reg_status s) const {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(reg_last_error(h_));
+        if (s == REG_DEVICE_ERROR) throw DeviceError(reg_last_error(h_));
+        if (s != REG_OK) throw std::runtime_error(reg_last_error(h_));
+    }
+    reg_handle* h_ = nullptr;
+};
+
+// SamplingSurfaceNormalDataPointsFilter (DataPointsFilters/SamplingSurfaceNormal.cpp) on the device
+// (reg_sampling_surface_normal; determinism contract in include/o3dslam_reg.h).  Every output holds n rows of capacity;
+// returns the number of rows written.
+class SamplingSurfaceNormalFilter : public DeviceFilterBase {
+public:
+    reg_ssn_params params;
+    SamplingSurfaceNormalFilter() { reg_default_ssn_params(&params); }
+
+    int64_t compute(const DataPointsView& cloud, const reg_ssn_out& out, int64_t* unfitPointsCount = nullptr) {
+        int64_t m = 0;
+        check(reg_sampling_surface_normal(handle(), cloud.features, cloud.feature_stride, cloud.n, cloud.on_device ? 1 : 0,
+                                          &params, &out, &m, unfitPointsCount));
+        return m;
+    }
+};
+
+// The reading-side chain of reg_filter_points (MaxDist, MinDist, BoundingBox, DistanceLimit, RemoveNaN,
+// MaxQuantileOnAxis, FixStepSampling, Identity), applied in order.  Returns the number of points kept.
+class PointFilterChain : public DeviceFilterBase {
+public:
+    std::vector<reg_point_filter> filters;
+
+    int64_t compute(const DataPointsView& cloud, float* out_xyz, int32_t* out_idx = nullptr, const float* normals = nullptr,
+                    float* out_normals = nullptr, const float* covs6 = nullptr, float* out_covs6 = nullptr) {
+        int64_t m = 0;
+        check(reg_filter_points(handle(), cloud.features, cloud.feature_stride, normals, covs6, cloud.n,
+                                cloud.on_device ? 1 : 0, filters.data(), (int)filters.size(), out_xyz, out_normals,
+                                out_covs6, out_idx, &m));
+        return m;
+    }
+};
+
 }  // namespace o3dreg

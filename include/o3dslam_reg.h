@@ -554,6 +554,89 @@ typedef struct {
 } reg_target_info;
 REG_API reg_status reg_get_target_info(const reg_handle* h, reg_target_info* info);
 
+/* ---- data-point filters on the device ----------------------------------------------------------
+   SamplingSurfaceNormalDataPointsFilter (libpointmatcher DataPointsFilters/SamplingSurfaceNormal.cpp buildNew /
+   fuseRange; parameter names and defaults of SamplingSurfaceNormal.h).  The cloud is split recursively: on the first
+   strict argmax of the PROPAGATED box extents (utils.h argMax), by count (the left child gets count - count/2 points),
+   the cut value (first point of the right half) bounding both children on that axis; a range of count <= knn is a leaf.
+   A leaf whose actual extent exceeds max_box_dim is dropped; with keep_normals / keep_eigen_values / keep_eigen_vectors
+   a leaf with rank(C) + 1 < 3 is dropped as well (rank rule of reg_estimate_normals).  Dropped points count in n_unfit.
+   Determinism contract (libstdc++'s nth_element leaves ties and in-leaf order implementation-defined; these are the
+   documented choices):
+     - within a segment points are ordered by (coordinate on the cut axis, original index); -0.0 == +0.0;
+       non-finite input is REG_BAD_ARGUMENT;
+     - a leaf keeps the order the last split left; mean = sequential fp32 sum in that order / float(count);
+       C = sum (q - mean)(q - mean)^T sequentially in fp32;
+     - the kept index of a leaf is its SMALLEST original index; output rows are ascending by kept index;
+     - eigenvalues ascending, normal = eigenvector of the smallest, sign as reg_estimate_normals with viewpoint NULL
+       (largest component positive); densities = utils.h computeDensity.
+   sampling_method 1: one row per fitted leaf holding the leaf mean.  sampling_method 0 with ratio >= 1: every point of
+   every fitted leaf (its own xyz, the leaf's attributes).  sampling_method 0 with ratio < 1 draws from std::rand in
+   the reference, a stream that cannot be reproduced: REG_UNSUPPORTED.  average_existing_descriptors is accepted and
+   has no effect (the input carries no descriptors).  knn in [3, 64] (above: REG_UNSUPPORTED); n == 0 is
+   REG_EMPTY_SOURCE. */
+typedef struct {
+    int32_t struct_size;                    /* sizeof(reg_ssn_params) */
+    int32_t knn;                            /* 7 */
+    int32_t sampling_method;                /* 0 */
+    float   ratio;                          /* 0.5 */
+    float   max_box_dim;                    /* +inf */
+    int32_t average_existing_descriptors;   /* 1 (no effect) */
+    int32_t keep_normals;                   /* 1 */
+    int32_t keep_densities;                 /* 0 */
+    int32_t keep_eigen_values;              /* 0 */
+    int32_t keep_eigen_vectors;             /* 0 */
+} reg_ssn_params;
+REG_API void reg_default_ssn_params(reg_ssn_params* p);
+/* Outputs (host pointers, or device pointers when on_device != 0), n rows of capacity each; only xyz is required.
+     xyz        n_out x 3      normals  n_out x 3     densities n_out     eigvals n_out x 3 ascending
+     eigvecs    n_out x 9      (eigenvector k at [9 i + 3 k + r], as reg_estimate_normals)
+     src_idx    n_out          the kept input index of each row
+     leaf_id    n (per INPUT point): index of its leaf in depth-first order, -1 for the points of dropped leaves */
+typedef struct {
+    float*   xyz;
+    float*   normals;
+    float*   densities;
+    float*   eigvals;
+    float*   eigvecs;
+    int32_t* src_idx;
+    int32_t* leaf_id;
+} reg_ssn_out;
+REG_API reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t xyz_stride, int64_t n,
+                                               int on_device, const reg_ssn_params* p, const reg_ssn_out* out,
+                                               int64_t* n_out, int64_t* n_unfit);
+
+/* Reading-side point filters, run as an ordered chain in one call (each filter's inPlaceFilter; defaults of its .h).
+   Every filter is a predicate over the current cloud followed by an order-preserving compaction.  The norm is
+   sqrtf((x*x + y*y) + z*z) in fp32 without contraction (Eigen's norm() may differ in the last ulp at a threshold).
+     MAX_DIST        dim -1: |p| < |value|, else p[dim] < value              (MaxDist.cpp)
+     MIN_DIST        dim -1: |p| > |value|, else p[dim] > value              (MinDist.cpp)
+     BOUNDING_BOX    strict on all six bounds; remove_inside                 (BoundingBox.cpp)
+     DISTANCE_LIMIT  remove_inside ? d > value : d < value, d as MAX_DIST    (DistanceLimit.cpp)
+     REMOVE_NAN      drops points with a NaN coordinate; inf is kept        (RemoveNaN.cpp)
+     MAX_QUANTILE_ON_AXIS  limit = exact order statistic int(float(m) * value) of p[dim] over the current m points;
+                     keeps p[dim] < limit.  A NaN on that axis is REG_BAD_ARGUMENT (run REMOVE_NAN first).
+     FIX_STEP_SAMPLING keeps positions phase, phase + step, ... of the current cloud; step = startStep (init() resets
+                     it on every compute); the reference draws phase = rand() % step, here it is an argument (0..step-1)
+     IDENTITY
+   Inputs: xyz (stride in floats), nrm n x 3 and cov n x 6 (may be NULL) are carried along.  Outputs (capacity n rows):
+   out_xyz m x 3, out_nrm / out_cov (when the input has them, may be NULL), out_idx m source indices (may be NULL). */
+enum { REG_DPF_IDENTITY = 0, REG_DPF_MAX_DIST = 1, REG_DPF_MIN_DIST = 2, REG_DPF_BOUNDING_BOX = 3,
+       REG_DPF_DISTANCE_LIMIT = 4, REG_DPF_REMOVE_NAN = 5, REG_DPF_MAX_QUANTILE_ON_AXIS = 6, REG_DPF_FIX_STEP_SAMPLING = 7 };
+typedef struct {
+    int32_t type;            /* REG_DPF_* */
+    int32_t dim;             /* -1 (norm) or 0..2; MAX_QUANTILE_ON_AXIS: 0..2 */
+    float   value;           /* maxDist / minDist / dist / ratio */
+    int32_t remove_inside;   /* BOUNDING_BOX, DISTANCE_LIMIT */
+    float   box[6];          /* xMin xMax yMin yMax zMin zMax */
+    int32_t step;            /* FIX_STEP_SAMPLING: startStep >= 1 */
+    int32_t phase;           /* FIX_STEP_SAMPLING: 0 <= phase < step */
+} reg_point_filter;
+REG_API reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xyz_stride, const float* nrm,
+                                     const float* cov, int64_t n, int on_device, const reg_point_filter* filters,
+                                     int n_filters, float* out_xyz, float* out_nrm, float* out_cov, int32_t* out_idx,
+                                     int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,6 +108,46 @@ class TargetInfo(C.Structure):
                 ("centroid", C.c_float * 3), ("dims", C.c_int32 * 3)]
 
 
+class SsnParams(C.Structure):
+    """reg_ssn_params (include/o3dslam_reg.h): SamplingSurfaceNormalDataPointsFilter's parameters."""
+    _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("sampling_method", C.c_int32), ("ratio", C.c_float),
+                ("max_box_dim", C.c_float), ("average_existing_descriptors", C.c_int32), ("keep_normals", C.c_int32),
+                ("keep_densities", C.c_int32), ("keep_eigen_values", C.c_int32), ("keep_eigen_vectors", C.c_int32)]
+
+
+class SsnOut(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("normals", C.c_void_p), ("densities", C.c_void_p), ("eigvals", C.c_void_p),
+                ("eigvecs", C.c_void_p), ("src_idx", C.c_void_p), ("leaf_id", C.c_void_p)]
+
+
+class PointFilter(C.Structure):
+    """reg_point_filter: one reading-side filter of a reg_filter_points chain."""
+    _fields_ = [("type", C.c_int32), ("dim", C.c_int32), ("value", C.c_float), ("remove_inside", C.c_int32),
+                ("box", C.c_float * 6), ("step", C.c_int32), ("phase", C.c_int32)]
+
+
+DPF_TYPES = {"Identity": 0, "MaxDist": 1, "MinDist": 2, "BoundingBox": 3, "DistanceLimit": 4, "RemoveNaN": 5,
+             "MaxQuantileOnAxis": 6, "FixStepSampling": 7}
+
+
+def point_filter(spec: dict) -> PointFilter:
+    """A reg_point_filter from {"type": <name without DataPointsFilter>, <reference parameter>: value, ...}; parameters
+    left out take the defaults of the filter's .h."""
+    t = spec["type"]
+    f = PointFilter()
+    f.type = DPF_TYPES[t]
+    f.dim = int(spec.get("dim", 0 if t == "MaxQuantileOnAxis" else -1))
+    key = {"MaxDist": "maxDist", "MinDist": "minDist", "DistanceLimit": "dist", "MaxQuantileOnAxis": "ratio"}.get(t)
+    f.value = float(spec.get(key, 0.5 if t == "MaxQuantileOnAxis" else 1.0)) if key else 0.0
+    f.remove_inside = int(spec.get("removeInside", 1))
+    for i, (k, d) in enumerate((("xMin", -1.0), ("xMax", 1.0), ("yMin", -1.0), ("yMax", 1.0), ("zMin", -1.0),
+                                ("zMax", 1.0))):
+        f.box[i] = float(spec.get(k, d))
+    f.step = int(spec.get("startStep", 10))
+    f.phase = int(spec.get("phase", 0))
+    return f
+
+
 class PmChain(C.Structure):
     """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint)."""
     _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("minimizer", C.c_int32), ("use_robust", C.c_int32),
@@ -135,7 +175,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
            "reg_default_pm_chain", "reg_check_pm_chain", "reg_set_pm_chain", "reg_get_robust_state",
-           "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update"]
+           "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update",
+           "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points"]
 
 
 def lib_path() -> str:
@@ -241,6 +282,12 @@ def load_library():
     lib.reg_get_correspondences_k.argtypes = [vp, C.c_int32, vp, vp, vp]
     lib.reg_host_robust_weights.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, vp, i64, vp]
     lib.reg_host_pm_p2p_update.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.reg_default_ssn_params.argtypes = [C.POINTER(SsnParams)]
+    lib.reg_default_ssn_params.restype = None
+    lib.reg_sampling_surface_normal.argtypes = [vp, vp, i64, i64, C.c_int, C.POINTER(SsnParams), C.POINTER(SsnOut),
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.reg_filter_points.argtypes = [vp, vp, i64, vp, vp, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp,
+                                      C.POINTER(C.c_int64)]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the library does not export what the header declares
     _lib = lib
@@ -256,6 +303,55 @@ def default_params() -> RegParams:
 def shipped_params() -> RegParams:
     p = RegParams()
     load_library().reg_shipped_params(C.byref(p))
+    return p
+
+
+class DeviceArray:
+    """Device memory of the HIP runtime the library itself runs on (hipMalloc / hipFree of the libamdhip64 it loaded):
+    lets the filters hand their results to reg_set_target / reg_set_source without a host round trip."""
+
+    def __init__(self, nbytes: int):
+        load_library()
+        self._hip = C.CDLL("libamdhip64.so.7")   # already loaded by the library: the same runtime instance
+        self._hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        self._hip.hipFree.argtypes = [C.c_void_p]
+        self._hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.ptr = C.c_void_p()
+        self.nbytes = max(int(nbytes), 16)
+        if self._hip.hipMalloc(C.byref(self.ptr), self.nbytes) != 0:
+            self.ptr = C.c_void_p()
+            raise RegError(8, f"hipMalloc({self.nbytes}) failed")
+
+    @property
+    def value(self) -> int:
+        return int(self.ptr.value or 0)
+
+    def upload(self, a: np.ndarray):
+        a = np.ascontiguousarray(a)
+        if a.nbytes > self.nbytes or self._hip.hipMemcpy(self.ptr, a.ctypes.data, a.nbytes, 1) != 0:
+            raise RegError(8, "hipMemcpy (host to device) failed")
+
+    def download(self, shape, dtype=np.float32) -> np.ndarray:
+        out = np.empty(shape, dtype)
+        if out.nbytes > self.nbytes or self._hip.hipMemcpy(out.ctypes.data, self.ptr, out.nbytes, 2) != 0:
+            raise RegError(8, "hipMemcpy (device to host) failed")
+        return out
+
+    def free(self):
+        if self.ptr.value:
+            self._hip.hipFree(self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def default_ssn_params() -> SsnParams:
+    p = SsnParams()
+    load_library().reg_default_ssn_params(C.byref(p))
     return p
 
 
@@ -494,6 +590,71 @@ class Registration:
             1 if regularise else 0, C.byref(o), C.byref(resc)))
         out["n_rescanned"] = int(resc.value)
         return out
+
+    def sampling_surface_normal(self, xyz, params: "SsnParams | None" = None, want_leaf_id=False, **kw):
+        """SamplingSurfaceNormalDataPointsFilter on the device (reg_sampling_surface_normal).  `kw` sets SsnParams fields.
+        Returns a dict: xyz (m,3), src_idx (m,), normals / densities / eigvals / eigvecs as the keep* switches ask,
+        leaf_id (n,) on request, n_out, n_unfit."""
+        p = params if params is not None else default_ssn_params()
+        for k, v in kw.items():
+            setattr(p, k, v)
+        xyz = _f32(xyz)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        out = {"xyz": np.zeros((n, 3), np.float32), "src_idx": np.zeros(n, np.int32)}
+        for key, want, shape in (("normals", p.keep_normals, (n, 3)), ("densities", p.keep_densities, (n,)),
+                                 ("eigvals", p.keep_eigen_values, (n, 3)), ("eigvecs", p.keep_eigen_vectors, (n, 9))):
+            if want:
+                out[key] = np.zeros(shape, np.float32)
+        if want_leaf_id:
+            out["leaf_id"] = np.zeros(n, np.int32)
+        o = SsnOut()
+        for key in ("xyz", "normals", "densities", "eigvals", "eigvecs", "src_idx", "leaf_id"):
+            setattr(o, key, out[key].ctypes.data if key in out else None)
+        m, unfit = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_sampling_surface_normal(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, n, 0,
+                                                          C.byref(p), C.byref(o), C.byref(m), C.byref(unfit)))
+        for key in ("xyz", "src_idx", "normals", "densities", "eigvals", "eigvecs"):
+            if key in out:
+                out[key] = out[key][:m.value].copy()
+        out["n_out"], out["n_unfit"] = int(m.value), int(unfit.value)
+        return out
+
+    def sampling_surface_normal_device(self, xyz_ptr, xyz_stride, n, params: "SsnParams", xyz_out_ptr, normals_ptr=None,
+                                       densities_ptr=None, eigvals_ptr=None, eigvecs_ptr=None, src_idx_ptr=None,
+                                       leaf_id_ptr=None):
+        """Device-pointer form: every output holds n rows of capacity.  Returns (n_out, n_unfit)."""
+        o = SsnOut(xyz_out_ptr, normals_ptr, densities_ptr, eigvals_ptr, eigvecs_ptr, src_idx_ptr, leaf_id_ptr)
+        m, unfit = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_sampling_surface_normal(self._h, C.c_void_p(xyz_ptr), xyz_stride, n, 1, C.byref(params),
+                                                          C.byref(o), C.byref(m), C.byref(unfit)))
+        return int(m.value), int(unfit.value)
+
+    def filter_points(self, xyz, filters, normals=None, covs=None):
+        """Reading-side filter chain on the device (reg_filter_points).  filters: dicts for point_filter() or
+        PointFilter structs.  Returns (xyz (m,3), src_idx (m,), normals or None, covs or None)."""
+        xyz = _f32(xyz)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        nr = _f32(normals) if normals is not None else None
+        cv = _f32(covs) if covs is not None else None
+        arr = (PointFilter * max(len(filters), 1))(*[f if isinstance(f, PointFilter) else point_filter(f) for f in filters])
+        ox, oi = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        on = np.zeros((n, 3), np.float32) if nr is not None else None
+        oc = np.zeros((n, 6), np.float32) if cv is not None else None
+        m = C.c_int64(0)
+        self._check(self._lib.reg_filter_points(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, _ptr(nr), _ptr(cv),
+                                                n, 0, C.cast(arr, C.c_void_p), len(filters), _ptr(ox), _ptr(on), _ptr(oc),
+                                                _ptr(oi), C.byref(m)))
+        k = int(m.value)
+        return ox[:k].copy(), oi[:k].copy(), (on[:k].copy() if on is not None else None), (oc[:k].copy() if oc is not None else None)
+
+    def filter_points_device(self, xyz_ptr, xyz_stride, n, filters, out_xyz_ptr, nrm_ptr=None, cov_ptr=None,
+                             out_nrm_ptr=None, out_cov_ptr=None, out_idx_ptr=None) -> int:
+        arr = (PointFilter * max(len(filters), 1))(*[f if isinstance(f, PointFilter) else point_filter(f) for f in filters])
+        m = C.c_int64(0)
+        self._check(self._lib.reg_filter_points(self._h, C.c_void_p(xyz_ptr), xyz_stride, nrm_ptr, cov_ptr, n, 1,
+                                                C.cast(arr, C.c_void_p), len(filters), out_xyz_ptr, out_nrm_ptr,
+                                                out_cov_ptr, out_idx_ptr, C.byref(m)))
+        return int(m.value)
 
     def smooth_normals(self, normals, ids):
         """SurfaceNormalDataPointsFilter's smoothNormals (SurfaceNormal.cpp:259-283) on the device, sequential semantics.

@@ -1,0 +1,339 @@
+// kernels_filters.hpp -- data-point filters: SamplingSurfaceNormal (reference side) and the reading-side point filters
+// Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
+#pragma once
+
+// =================================================================================================
+// SamplingSurfaceNormalDataPointsFilter (libpointmatcher DataPointsFilters/SamplingSurfaceNormal.cpp buildNew /
+// fuseRange) under the determinism contract of reg_sampling_surface_normal (include/o3dslam_reg.h).
+// The tree shape depends only on (n, knn): the host lists every level's open segments (count > knn) and every leaf.
+// Per level: k_ssn_keys (cut axis from the propagated box, 64-bit key (orderable coordinate << 32) | index),
+// a rocPRIM segmented radix sort over the open segments, k_ssn_extract (new order) and k_ssn_children (cut value ->
+// child boxes).  Leaves: one thread per leaf (k_ssn_leaf), then a scan over the input indices and k_ssn_scatter.
+// =================================================================================================
+constexpr int kSsnMaxKnn = 64;
+
+__device__ __forceinline__ uint32_t ssn_orderable(float v) {
+    uint32_t u = __float_as_uint(v);
+    if (u == 0x80000000u) u = 0u;   // -0 == +0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// utils.h argMax: first strict maximum, starting from 0 (an all-zero extent gives axis 0)
+__device__ __forceinline__ int ssn_axis(const float* box) {
+    float best = 0.f;
+    int arg = 0;
+    for (int a = 0; a < 3; ++a) {
+        const float e = box[3 + a] - box[a];
+        if (e > best) {
+            best = e;
+            arg = a;
+        }
+    }
+    return arg;
+}
+
+// last open segment whose begin <= i; -1 when i lies in no open segment (a leaf of an earlier level)
+__device__ __forceinline__ int ssn_segment_of(const int32_t* __restrict__ sb, const int32_t* __restrict__ se, int ns, int i) {
+    int lo = 0, hi = ns;   // first begin > i
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sb[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    const int j = lo - 1;
+    return (j >= 0 && i < se[j]) ? j : -1;
+}
+
+// Packs the (strided) input into n x 3 floats, flags non-finite values and reduces the bounding box (orderable keys).
+__global__ void __launch_bounds__(256)
+k_ssn_pack(const float* __restrict__ xyz, int64_t stride, int n, float* __restrict__ px, uint32_t* __restrict__ misc) {
+    __shared__ uint32_t s_lo[3][256], s_hi[3][256];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    if (i < n) {
+        bool bad = false;
+        for (int a = 0; a < 3; ++a) {
+            const float v = xyz[(size_t)i * stride + a];
+            px[3 * (size_t)i + a] = v;
+            if (!isfinite(v)) bad = true;
+            lo[a] = hi[a] = ssn_orderable(v);
+        }
+        if (bad) misc[6] = 1u;
+    }
+    for (int a = 0; a < 3; ++a) {
+        s_lo[a][threadIdx.x] = lo[a];
+        s_hi[a][threadIdx.x] = hi[a];
+    }
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int a = 0; a < 3; ++a) {
+                s_lo[a][threadIdx.x] = min(s_lo[a][threadIdx.x], s_lo[a][threadIdx.x + s]);
+                s_hi[a][threadIdx.x] = max(s_hi[a][threadIdx.x], s_hi[a][threadIdx.x + s]);
+            }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(&misc[a], s_lo[a][0]);
+            atomicMax(&misc[3 + a], s_hi[a][0]);
+        }
+}
+
+__device__ __forceinline__ float ssn_from_orderable(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// root box + identity permutation
+__global__ void __launch_bounds__(256)
+k_ssn_init(const uint32_t* __restrict__ misc, int n, float* __restrict__ box0, int32_t* __restrict__ perm) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 6) box0[i] = ssn_from_orderable(misc[i]);
+    if (i < n) perm[i] = i;
+}
+
+__global__ void __launch_bounds__(256)
+k_ssn_keys(const float* __restrict__ px, const int32_t* __restrict__ perm, int n, const int32_t* __restrict__ sb,
+           const int32_t* __restrict__ se, int ns, const float* __restrict__ boxes, uint64_t* __restrict__ keys) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int j = ssn_segment_of(sb, se, ns, i);
+    if (j < 0) return;
+    const int ax = ssn_axis(boxes + 6 * (size_t)j);
+    const uint32_t p = (uint32_t)perm[i];
+    keys[i] = ((uint64_t)ssn_orderable(px[3 * (size_t)p + ax]) << 32) | (uint64_t)p;
+}
+
+__global__ void __launch_bounds__(256)
+k_ssn_extract(const uint64_t* __restrict__ keys, int n, const int32_t* __restrict__ sb, const int32_t* __restrict__ se,
+              int ns, int32_t* __restrict__ perm) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (ssn_segment_of(sb, se, ns, i) < 0) return;
+    perm[i] = (int32_t)(uint32_t)keys[i];
+}
+
+// child boxes: cutVal = coordinate of the first point of the right half (buildNew)
+__global__ void __launch_bounds__(256)
+k_ssn_children(const float* __restrict__ px, const int32_t* __restrict__ perm, const int32_t* __restrict__ sb,
+               const int32_t* __restrict__ se, const int32_t* __restrict__ child, int ns, const float* __restrict__ boxes,
+               float* __restrict__ next_boxes) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= ns) return;
+    float box[6];
+    for (int a = 0; a < 6; ++a) box[a] = boxes[6 * (size_t)j + a];
+    const int ax = ssn_axis(box);
+    const int c = se[j] - sb[j];
+    const int left = c - c / 2;
+    const float cut = px[3 * (size_t)perm[sb[j] + left] + ax];
+    const int cl = child[2 * j], cr = child[2 * j + 1];
+    if (cl >= 0) {
+        for (int a = 0; a < 6; ++a) next_boxes[6 * (size_t)cl + a] = box[a];
+        next_boxes[6 * (size_t)cl + 3 + ax] = cut;
+    }
+    if (cr >= 0) {
+        for (int a = 0; a < 6; ++a) next_boxes[6 * (size_t)cr + a] = box[a];
+        next_boxes[6 * (size_t)cr + ax] = cut;
+    }
+}
+
+// Same rank rule as k_pca_finish: eigenvalues of C (fp64 Jacobi), rank = |lambda| > 3 eps_f32 |lambda|_max.
+__device__ __forceinline__ int ssn_rank(const float* C) {
+    double M[9] = {C[0], C[1], C[2], C[1], C[3], C[4], C[2], C[4], C[5]}, V[9], lam[3];
+    jacobi_eig_sym3(M, V, lam);
+    const double lmax = fabs(fmax(lam[0], fmax(lam[1], lam[2])));   // |largest eigenvalue|, as k_pca_finish
+    int rank = 0;
+    for (int a = 0; a < 3; ++a)
+        if (lmax > 0 && fabs(lam[a]) > lmax * 3.0 * 1.1920929e-07) ++rank;
+    return rank;
+}
+
+// utils.h computeDensity with the fp32 operation order of k_pca_finish
+__device__ __forceinline__ float ssn_density(int m, float mx) {
+    const float tq = (float)(4. / 3.), pi = (float)3.14159265358979323846;
+    const float c0 = tq * pi;
+    const float r3 = mx * sqrtf(mx);
+    const float volume = c0 * r3;
+    return volume > 0.f ? (float)m / volume : 0.f;
+}
+
+// One thread per leaf (fuseRange): actual extent vs maxBoxDim, fp32 sequential mean / scatter, rank test when an
+// eigen output is requested.  Writes the leaf's PcaMoments (idx = its smallest original index), the per-input leaf id
+// and the keep flag of the input indices that become output rows.
+__global__ void __launch_bounds__(256)
+k_ssn_leaf(const float* __restrict__ px, const int32_t* __restrict__ perm, const int32_t* __restrict__ leaf_begin,
+           int n_leaves, float max_box_dim, int need_eig, int method, PcaMoments* __restrict__ leaf_mom,
+           int32_t* __restrict__ leaf_id, uint32_t* __restrict__ keep, unsigned long long* __restrict__ n_unfit) {
+    const int L = blockIdx.x * 256 + threadIdx.x;
+    if (L >= n_leaves) return;
+    const int b = leaf_begin[L], e = leaf_begin[L + 1];
+    const int m = e - b;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    float mean[3] = {0.f, 0.f, 0.f};
+    int32_t min_idx = 0x7fffffff;
+    for (int r = b; r < e; ++r) {
+        const int32_t p = perm[r];
+        min_idx = min(min_idx, p);
+        for (int a = 0; a < 3; ++a) {
+            const float v = px[3 * (size_t)p + a];
+            lo[a] = fminf(lo[a], v);
+            hi[a] = fmaxf(hi[a], v);
+            mean[a] = mean[a] + v;
+        }
+    }
+    float dim = hi[0] - lo[0];
+    for (int a = 1; a < 3; ++a) dim = fmaxf(dim, hi[a] - lo[a]);
+    bool fit = !(dim > max_box_dim);
+    const float fm = (float)m;
+    for (int a = 0; a < 3; ++a) mean[a] = mean[a] / fm;
+    float C[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float mx = 0.f;
+    for (int r = b; r < e; ++r) {
+        const size_t p = (size_t)perm[r];
+        const float dx = px[3 * p] - mean[0], dy = px[3 * p + 1] - mean[1], dz = px[3 * p + 2] - mean[2];
+        float u;
+        u = dx * dx; C[0] = C[0] + u;
+        u = dx * dy; C[1] = C[1] + u;
+        u = dx * dz; C[2] = C[2] + u;
+        u = dy * dy; C[3] = C[3] + u;
+        u = dy * dz; C[4] = C[4] + u;
+        u = dz * dz; C[5] = C[5] + u;
+        float s = dx * dx;
+        float t = dy * dy;
+        float s2 = s + t;
+        s = dz * dz;
+        s2 = s2 + s;
+        mx = fmaxf(mx, s2);
+    }
+    if (fit && need_eig && ssn_rank(C) + 1 < 3) fit = false;
+    PcaMoments rec;
+    for (int a = 0; a < 3; ++a) {
+        rec.mean[a] = mean[a];
+        rec.p[a] = mean[a];
+    }
+    for (int a = 0; a < 6; ++a) rec.C[a] = C[a];
+    rec.m = fm;
+    rec.max_d2 = mx;
+    rec.idx = (uint32_t)min_idx;
+    rec.pad = fit ? 1u : 0u;
+    leaf_mom[L] = rec;
+    for (int r = b; r < e; ++r) {
+        const int32_t p = perm[r];
+        leaf_id[p] = fit ? L : -1;
+        if (method == 0) keep[p] = fit ? 1u : 0u;
+        else keep[p] = (fit && p == min_idx) ? 1u : 0u;
+    }
+    if (!fit) atomicAdd(n_unfit, (unsigned long long)m);
+}
+
+// One thread per input index: kept rows go to slot pos[i] (ascending kept index).  Output moments carry idx = slot so
+// k_pca_finish writes the compacted normals / eigen outputs directly.
+__global__ void __launch_bounds__(256)
+k_ssn_scatter(const float* __restrict__ px, int n, int method, const uint32_t* __restrict__ keep,
+              const uint32_t* __restrict__ pos, const int32_t* __restrict__ leaf_id, const PcaMoments* __restrict__ leaf_mom,
+              float* __restrict__ out_xyz, int32_t* __restrict__ src_idx, float* __restrict__ densities,
+              PcaMoments* __restrict__ out_mom) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !keep[i]) return;
+    const uint32_t s = pos[i];
+    PcaMoments rec = leaf_mom[leaf_id[i]];
+    if (method == 0)
+        for (int a = 0; a < 3; ++a) rec.p[a] = px[3 * (size_t)i + a];
+    for (int a = 0; a < 3; ++a) out_xyz[3 * (size_t)s + a] = rec.p[a];
+    src_idx[s] = i;
+    if (densities) densities[s] = ssn_density((int)rec.m, rec.max_d2);
+    rec.idx = s;
+    out_mom[s] = rec;
+}
+
+// =================================================================================================
+// Reading-side point filters (reg_filter_points): a predicate per point of the current index list + order-preserving
+// compaction (rocPRIM exclusive scan).  Norm: sqrtf((x*x + y*y) + z*z), no contraction.
+// =================================================================================================
+struct PointFilterDev {
+    int type, dim, remove_inside, step, phase;
+    float value, limit;
+    float box[6];
+};
+
+__global__ void __launch_bounds__(256)
+k_pf_pack(const float* __restrict__ xyz, int64_t stride, const float* __restrict__ nrm, const float* __restrict__ cov,
+          int n, float* __restrict__ px, float* __restrict__ pn, float* __restrict__ pc, int32_t* __restrict__ idx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    for (int a = 0; a < 3; ++a) px[3 * (size_t)i + a] = xyz[(size_t)i * stride + a];
+    if (nrm)
+        for (int a = 0; a < 3; ++a) pn[3 * (size_t)i + a] = nrm[3 * (size_t)i + a];
+    if (cov)
+        for (int a = 0; a < 6; ++a) pc[6 * (size_t)i + a] = cov[6 * (size_t)i + a];
+    idx[i] = i;
+}
+
+__global__ void __launch_bounds__(256)
+k_pf_axis(const float* __restrict__ px, const int32_t* __restrict__ idx, int m, int dim, float* __restrict__ vals,
+          uint32_t* __restrict__ has_nan) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const float v = px[3 * (size_t)idx[j] + dim];
+    if (isnan(v)) has_nan[0] = 1u;
+    vals[j] = v;
+}
+
+__global__ void __launch_bounds__(256)
+k_pf_pred(const float* __restrict__ px, const int32_t* __restrict__ idx, int m, PointFilterDev f,
+          uint32_t* __restrict__ flag) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const float* p = px + 3 * (size_t)idx[j];
+    const float x = p[0], y = p[1], z = p[2];
+    float d;
+    if (f.dim < 0) {
+        float a = x * x;
+        float b = y * y;
+        float s = a + b;
+        a = z * z;
+        s = s + a;
+        d = sqrtf(s);
+    } else {
+        d = p[f.dim];
+    }
+    bool keep = true;
+    switch (f.type) {
+        case REG_DPF_MAX_DIST: keep = d < f.value; break;
+        case REG_DPF_MIN_DIST: keep = d > f.value; break;
+        case REG_DPF_DISTANCE_LIMIT: keep = f.remove_inside ? (d > f.value) : (d < f.value); break;
+        case REG_DPF_BOUNDING_BOX: {
+            const bool in = x > f.box[0] && x < f.box[1] && y > f.box[2] && y < f.box[3] && z > f.box[4] && z < f.box[5];
+            keep = f.remove_inside ? !in : in;
+            break;
+        }
+        case REG_DPF_REMOVE_NAN: keep = !(isnan(x) || isnan(y) || isnan(z)); break;
+        case REG_DPF_MAX_QUANTILE_ON_AXIS: keep = d < f.limit; break;
+        case REG_DPF_FIX_STEP_SAMPLING: keep = j >= f.phase && (j - f.phase) % f.step == 0; break;
+        default: keep = true; break;
+    }
+    flag[j] = keep ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(256)
+k_pf_compact(const int32_t* __restrict__ idx, int m, const uint32_t* __restrict__ flag, const uint32_t* __restrict__ pos,
+             int32_t* __restrict__ idx_out) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m || !flag[j]) return;
+    idx_out[pos[j]] = idx[j];
+}
+
+__global__ void __launch_bounds__(256)
+k_pf_gather(const float* __restrict__ px, const float* __restrict__ pn, const float* __restrict__ pc,
+            const int32_t* __restrict__ idx, int m, float* __restrict__ ox, float* __restrict__ on, float* __restrict__ oc,
+            int32_t* __restrict__ oidx) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const size_t i = (size_t)idx[j];
+    for (int a = 0; a < 3; ++a) ox[3 * (size_t)j + a] = px[3 * i + a];
+    if (on)
+        for (int a = 0; a < 3; ++a) on[3 * (size_t)j + a] = pn[3 * i + a];
+    if (oc)
+        for (int a = 0; a < 6; ++a) oc[6 * (size_t)j + a] = pc[6 * i + a];
+    if (oidx) oidx[j] = (int32_t)i;
+}

@@ -45,12 +45,14 @@ using namespace o3dreg;
 #include "kernels_tail.hpp"
 #include "kernels_normals.hpp"
 #include "kernels_pmchain.hpp"
+#include "kernels_filters.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
 #include "host_loop.hpp"
 #include "host_dist.hpp"
 #include "host_rccl.hpp"
+#include "host_filters.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -181,7 +181,7 @@ class ICP:
             self.matcherIsInitialized = False
             return False
         try:
-            self._reg.set_target(referenceIn.features, referenceIn.normals, referenceIn.covariances)
+            self._set_reference(referenceIn)
         except RegError as e:
             raise _translate(e) from None
         self.matcherIsInitialized = True
@@ -200,7 +200,7 @@ class ICP:
         if readingIn.getNbPoints() == 0:
             raise RuntimeError("The reading point cloud is empty.")  # ICP.cpp:958-960
         try:
-            self._reg.set_source(readingIn.features, readingIn.normals, readingIn.covariances)
+            self._set_reading(readingIn)
             T_out, res = self._reg.register(T)
         except RegError as e:
             raise _translate(e) from None
@@ -210,6 +210,12 @@ class ICP:
 
     def __call__(self, readingIn, referenceIn, T_refIn_readIn=None):
         return self.compute(readingIn, referenceIn, T_refIn_readIn, True)
+
+    def _set_reference(self, referenceIn: DataPoints):
+        self._reg.set_target(referenceIn.features, referenceIn.normals, referenceIn.covariances)
+
+    def _set_reading(self, readingIn: DataPoints):
+        self._reg.set_source(readingIn.features, readingIn.normals, readingIn.covariances)
 
 
 class PointMatcherICP(ICP):
@@ -224,15 +230,23 @@ class PointMatcherICP(ICP):
     def __init__(self):
         super().__init__()
         self.chain: capi.PmChain | None = None
+        self.referenceDataPointsFilters: list = []
+        self.readingDataPointsFilters: list[dict] = []
+        self._dev: dict = {}
 
     def setDefault(self):
         super().setDefault()
         self.chain = None
+        self.referenceDataPointsFilters, self.readingDataPointsFilters = [], []
 
     def loadFromYaml(self, stream_or_text):
+        """Also binds referenceDataPointsFilters (SamplingSurfaceNormal, SurfaceNormal) and readingDataPointsFilters
+        (READING_FILTERS) to the device filters (reg_sampling_surface_normal, reg_estimate_normals, reg_filter_points)."""
         import yaml
         text = stream_or_text.read() if hasattr(stream_or_text, "read") else stream_or_text
         doc = yaml.safe_load(text) or {}
+        ref_filters = [_reference_filter(f) for f in (doc.pop("referenceDataPointsFilters", None) or [])]
+        read_filters = [_reading_filter(f) for f in (doc.pop("readingDataPointsFilters", None) or [])]
         chain = capi.default_pm_chain()
         m = doc.get("matcher")
         if isinstance(m, dict) and isinstance(m.get("KDTreeMatcher"), dict) and "knn" in m["KDTreeMatcher"]:
@@ -277,6 +291,71 @@ class PointMatcherICP(ICP):
         if st != 0:
             raise InvalidParameter("invalid chain (knn must lie in 1..16; robust parameters out of range)")
         self.chain = chain
+        self.referenceDataPointsFilters, self.readingDataPointsFilters = ref_filters, read_filters
+
+    def _buf(self, key, nbytes):
+        b = self._dev.get(key)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._dev[key] = capi.DeviceArray(nbytes)
+        return b
+
+    def _set_reference(self, referenceIn: DataPoints):
+        """ICP::initReference: the reference filters run on the device and their output goes to reg_set_target as
+        device pointers (ICP.cpp:864-866: before the centroid)."""
+        if not self.referenceDataPointsFilters:
+            return super()._set_reference(referenceIn)
+        x = np.ascontiguousarray(referenceIn.features, np.float32)
+        n, stride = x.shape[0], x.shape[1]
+        src = self._buf("ref_in", x.nbytes)
+        src.upload(x)
+        cur, cur_stride, nrm = src.value, stride, None
+        for i, f in enumerate(self.referenceDataPointsFilters):
+            if isinstance(f, SamplingSurfaceNormalDataPointsFilter):
+                ox, on = self._buf(f"ref_xyz{i}", n * 12), self._buf(f"ref_nrm{i}", n * 12)
+                n, _ = self._reg.sampling_surface_normal_device(cur, cur_stride, n, f.params(), ox.value,
+                                                                on.value if f.keepNormals else None)
+                cur, cur_stride, nrm = ox.value, 3, (on.value if f.keepNormals else None)
+            else:   # SurfaceNormalDataPointsFilter: normals of the current points, xyz unchanged
+                on = self._buf(f"ref_nrm{i}", n * 12)
+                self._reg.estimate_normals_device(cur, cur_stride, n, on.value, k=f.knn, max_dist=f.maxDist,
+                                                  viewpoint=f.viewpoint)
+                if f.keepNormals:
+                    nrm = on.value
+        self._reg.set_target_device(cur, cur_stride, n, nrm, 3, None)
+        self.referenceFilteredCount = n
+
+    def _set_reading(self, readingIn: DataPoints):
+        """ICP::computeWithTransformedReference (ICP.cpp:950-955): the reading filters run on the device before the
+        reading's centroid; reg_set_source reads their output in place.  Correspondence ids index the filtered cloud."""
+        if not self.readingDataPointsFilters:
+            return super()._set_reading(readingIn)
+        x = np.ascontiguousarray(readingIn.features, np.float32)
+        n, stride = x.shape[0], x.shape[1]
+        src = self._buf("read_in", x.nbytes)
+        src.upload(x)
+        nin = cin = None
+        if readingIn.normals is not None:
+            nin = self._buf("read_nrm_in", n * 12)
+            nin.upload(np.ascontiguousarray(readingIn.normals, np.float32))
+        if readingIn.covariances is not None:
+            cin = self._buf("read_cov_in", n * 24)
+            cin.upload(np.ascontiguousarray(readingIn.covariances, np.float32))
+        ox, oi = self._buf("read_xyz", n * 12), self._buf("read_idx", n * 4)
+        on = self._buf("read_nrm", n * 12) if nin is not None else None
+        oc = self._buf("read_cov", n * 24) if cin is not None else None
+        m = self._reg.filter_points_device(src.value, stride, n, self.readingDataPointsFilters, ox.value,
+                                           nin.value if nin else None, cin.value if cin else None,
+                                           on.value if on else None, oc.value if oc else None, oi.value)
+        if m == 0:
+            raise RuntimeError("The reading point cloud is empty.")   # ICP.cpp:958-960
+        self._reg.set_source_device(ox.value, 3, m, on.value if on else None, 3, oc.value if oc else None)
+        self.readingFilteredCount = m
+
+    def readingFilteredIndices(self) -> np.ndarray:
+        """Source index (into the last compute()'s reading) of every filtered reading point."""
+        return self._dev["read_idx"].download(self.readingFilteredCount, np.int32)
 
     def _ensure(self):
         fresh = self._reg is None
@@ -327,6 +406,116 @@ class SurfaceNormalDataPointsFilter:
         self.eigValues, self.matchedIds = out.get("eigvals"), (out.get("ids") if self.keepMatchedIds else None)
         self.densities, self.eigVectors, self.meanDists = out.get("densities"), out.get("eigvecs"), out.get("mean_dists")
         return DataPoints(cloud.features, out["normals"] if self.keepNormals else cloud.normals, cloud.covariances)
+
+
+class SamplingSurfaceNormalDataPointsFilter:
+    """SamplingSurfaceNormalDataPointsFilter (DataPointsFilters/SamplingSurfaceNormal.{h,cpp}) on the device
+    (reg_sampling_surface_normal), parameters by the reference's names and defaults.  samplingMethod 0 with ratio < 1
+    draws from std::rand and is refused (NotImplementedError); averageExistingDescriptors has no effect (no descriptors
+    are carried).  `filter` returns the sampled DataPoints; densities / eigen outputs stay on the filter."""
+
+    PARAMS = {"ratio": 0.5, "knn": 7, "samplingMethod": 0, "maxBoxDim": math.inf, "averageExistingDescriptors": 1,
+              "keepNormals": 1, "keepDensities": 0, "keepEigenValues": 0, "keepEigenVectors": 0}
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.PARAMS)
+        if unknown:
+            raise InvalidParameter(f"SamplingSurfaceNormalDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
+        a = dict(self.PARAMS, **kw)
+        self.ratio, self.knn, self.samplingMethod = float(a["ratio"]), int(a["knn"]), int(a["samplingMethod"])
+        self.maxBoxDim, self.averageExistingDescriptors = float(a["maxBoxDim"]), bool(int(a["averageExistingDescriptors"]))
+        self.keepNormals, self.keepDensities = bool(int(a["keepNormals"])), bool(int(a["keepDensities"]))
+        self.keepEigenValues, self.keepEigenVectors = bool(int(a["keepEigenValues"])), bool(int(a["keepEigenVectors"]))
+        if self.knn < 3:
+            raise InvalidParameter("knn: minimum 3 (SamplingSurfaceNormal.h)")
+        if self.samplingMethod not in (0, 1):
+            raise InvalidParameter("samplingMethod: 0 or 1")
+        if self.knn > 64:
+            raise NotImplementedError("SamplingSurfaceNormalDataPointsFilter: knn above 64 is not supported on the device")
+        if self.samplingMethod == 0 and self.ratio < 1:
+            raise NotImplementedError("SamplingSurfaceNormalDataPointsFilter: samplingMethod 0 with ratio < 1 draws from "
+                                      "std::rand, which cannot be reproduced")
+        self.densities = self.eigValues = self.eigVectors = None
+        self._reg = None
+
+    def params(self) -> capi.SsnParams:
+        p = capi.default_ssn_params()
+        p.knn, p.sampling_method, p.ratio, p.max_box_dim = self.knn, self.samplingMethod, self.ratio, self.maxBoxDim
+        p.average_existing_descriptors = int(self.averageExistingDescriptors)
+        p.keep_normals, p.keep_densities = int(self.keepNormals), int(self.keepDensities)
+        p.keep_eigen_values, p.keep_eigen_vectors = int(self.keepEigenValues), int(self.keepEigenVectors)
+        return p
+
+    def filter(self, cloud: DataPoints) -> DataPoints:
+        if self._reg is None:
+            self._reg = capi.Registration(capi.default_params())
+        try:
+            out = self._reg.sampling_surface_normal(cloud.features, self.params())
+        except RegError as e:
+            raise _translate(e) from None
+        self.densities, self.eigValues, self.eigVectors = out.get("densities"), out.get("eigvals"), out.get("eigvecs")
+        return DataPoints(out["xyz"], out.get("normals"), None)
+
+
+# readingDataPointsFilters bound to reg_filter_points: name -> {parameter: default} (each filter's .h)
+READING_FILTERS = {
+    "IdentityDataPointsFilter": {},
+    "MaxDistDataPointsFilter": {"dim": -1, "maxDist": 1.0},
+    "MinDistDataPointsFilter": {"dim": -1, "minDist": 1.0},
+    "BoundingBoxDataPointsFilter": {"xMin": -1.0, "xMax": 1.0, "yMin": -1.0, "yMax": 1.0, "zMin": -1.0, "zMax": 1.0,
+                                    "removeInside": 1},
+    "DistanceLimitDataPointsFilter": {"dim": -1, "dist": 1.0, "removeInside": 1},
+    "RemoveNaNDataPointsFilter": {},
+    "MaxQuantileOnAxisDataPointsFilter": {"dim": 0, "ratio": 0.5},
+    # phase: the reference draws rand() % step on every compute; here it is explicit (default 0)
+    "FixStepSamplingDataPointsFilter": {"startStep": 10, "endStep": 10, "stepMult": 1.0, "phase": 0},
+}
+_REFUSED_FILTERS = {
+    "RandomSamplingDataPointsFilter": "draws from std::rand, which cannot be reproduced",
+    "MaxPointCountDataPointsFilter": "subsamples with std::rand above maxCount",
+}
+
+
+def _split(f):
+    (name, args), = (f.items() if isinstance(f, dict) else [(f, {})])
+    return name, dict(args or {})
+
+
+def _reading_filter(f) -> dict:
+    name, args = _split(f)
+    if name in _REFUSED_FILTERS:
+        raise NotImplementedError(f"{name}: {_REFUSED_FILTERS[name]}")
+    if name not in READING_FILTERS:
+        raise NotImplementedError(f"reading filter {name} is outside the accelerated path")
+    unknown = set(args) - set(READING_FILTERS[name])
+    if unknown:
+        raise InvalidParameter(f"{name}: unknown parameter(s) {sorted(unknown)}")
+    spec = dict(READING_FILTERS[name], **args)
+    spec["type"] = name[:-len("DataPointsFilter")]
+    if spec["type"] == "MaxQuantileOnAxis" and not (0 < float(spec["ratio"]) < 1):
+        raise InvalidParameter("MaxQuantileOnAxisDataPointsFilter: ratio must lie in (0, 1)")
+    if spec["type"] == "FixStepSampling" and int(spec["startStep"]) < 1:
+        raise InvalidParameter("FixStepSamplingDataPointsFilter: startStep >= 1")
+    return spec
+
+
+def _reference_filter(f):
+    name, args = _split(f)
+    if name == "SamplingSurfaceNormalDataPointsFilter":
+        return SamplingSurfaceNormalDataPointsFilter(**args)
+    if name == "SurfaceNormalDataPointsFilter":
+        known = {"knn", "maxDist", "epsilon", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
+                 "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"}
+        unknown = set(args) - known
+        if unknown:
+            raise InvalidParameter(f"SurfaceNormalDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
+        if int(args.pop("smoothNormals", 0)):
+            raise NotImplementedError("SurfaceNormalDataPointsFilter: smoothNormals in a reference chain")
+        args.pop("sortEigen", None)
+        return SurfaceNormalDataPointsFilter(**{k: (bool(int(v)) if k.startswith("keep") else v) for k, v in args.items()})
+    if name in _REFUSED_FILTERS:
+        raise NotImplementedError(f"{name}: {_REFUSED_FILTERS[name]}")
+    raise NotImplementedError(f"reference filter {name} is outside the accelerated path")
 
 
 @dataclass
