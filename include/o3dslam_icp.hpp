@@ -293,6 +293,23 @@ public:
     }
 };
 
+// OctreeGridDataPointsFilter (DataPointsFilters/OctreeGrid.cpp) on the device (reg_octree_grid; determinism contract
+// and the documented sampler deviation in include/o3dslam_reg.h).  normals (n x 3) and covs6 (n x 6) may be NULL and are
+// carried to out.normals / out.covs.  Every output holds n rows of capacity; returns the number of rows written.
+class OctreeGridFilter : public DeviceFilterBase {
+public:
+    reg_octree_params params;
+    OctreeGridFilter() { reg_default_octree_params(&params); }
+
+    int64_t compute(const DataPointsView& cloud, const reg_octree_out& out, const float* normals = nullptr,
+                    const float* covs6 = nullptr) {
+        int64_t m = 0;
+        check(reg_octree_grid(handle(), cloud.features, cloud.feature_stride, normals, covs6, cloud.n,
+                              cloud.on_device ? 1 : 0, &params, &out, &m));
+        return m;
+    }
+};
+
 // The reading-side chain of reg_filter_points (MaxDist, MinDist, BoundingBox, DistanceLimit, RemoveNaN,
 // MaxQuantileOnAxis, FixStepSampling, Identity), applied in order.  Returns the number of points kept.
 class PointFilterChain : public DeviceFilterBase {

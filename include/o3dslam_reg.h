@@ -637,6 +637,65 @@ REG_API reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xy
                                      int n_filters, float* out_xyz, float* out_nrm, float* out_cov, int32_t* out_idx,
                                      int64_t* n_out);
 
+/* OctreeGridDataPointsFilter (libpointmatcher DataPointsFilters/OctreeGrid.cpp, utils/octree/Octree.tpp build / idx /
+   visit, OctreeSamplers.tpp; parameter names and defaults of OctreeGrid.h).  Everything in fp32 without
+   FMA contraction:
+     - root box: min / max per axis; radii = max - min; centre 0 when center_at_origin, else min + radii * 0.5f;
+       radius = float(pow(2, ceil(log(x) / log(2)))) with x = double(max(radii)) * 0.5 in double with libm (x == 0
+       gives radius 0, a single leaf).  With center_at_origin points may lie outside the root box.
+     - a node is a leaf when double(radius) * 2.0 <= max_size_by_node or count <= max_point_by_node; otherwise a point
+       goes to child (x > cx) | (y > cy) << 1 | (z > cz) << 2 (strict: a point on a centre goes low), the child centre
+       is c + (+-0.5f * r) and the child radius r * 0.5f.  Members keep their input order; empty children are skipped.
+       Coincident points with max_size_by_node 0 split until the radius underflows to 0 (about 280 levels at most).
+     - non-empty leaves are visited depth-first, children 0..7; leaf k emits output row k:
+         FIRST    (0) its first member;
+         RAND     (1) member size_t(float(size - 1) * (float(rand()) / float(RAND_MAX))), one glibc rand() per
+                      non-empty leaf after srand(1) (RandomPtsSampler seeds 1 on every call), clamped to size - 1;
+         CENTROID (2) sequential fp32 sum in member order starting from the first member, / float(count); normals and
+                      covariances are averaged the same way (not renormalised); src_idx is the first member;
+         MEDOID   (3) the first member (member order) with the smallest sqrtf(dx*dx + (dy*dy + dz*dz)) (Eigen's norm of
+                      a 3-vector) to the leaf mean (sequential fp32 sum from 0.0f, / float(count)), strict < from
+                      FLT_MAX; when no distance is below FLT_MAX the first member.
+   Deviation: the reference samplers move rows with swapCols(idx, j) and look a displaced row up one level deep only
+   (indexVector[d]), so a row displaced twice before its leaf is visited emits the wrong point and drops the leaf's own
+   one.  Here row k is the sample of the k-th non-empty leaf, which is the evident intent; the tree (leaf membership
+   and depth-first order) matches exactly.
+   Non-finite input, or an extent whose radius is not finite, is REG_BAD_ARGUMENT; n == 0 is REG_EMPTY_SOURCE.
+   max_point_by_node >= 1, max_size_by_node >= 0 (not NaN), sampling_method 0..3, else REG_BAD_ARGUMENT.
+   build_parallel is accepted and has no effect (the reference's tree does not depend on it). */
+enum { REG_OCTREE_FIRST = 0, REG_OCTREE_RAND = 1, REG_OCTREE_CENTROID = 2, REG_OCTREE_MEDOID = 3 };
+typedef struct {
+    int32_t struct_size;          /* sizeof(reg_octree_params) */
+    int32_t build_parallel;       /* 1 (no effect) */
+    int64_t max_point_by_node;    /* 1 */
+    float   max_size_by_node;     /* 0 */
+    int32_t sampling_method;      /* 0 (REG_OCTREE_*) */
+    int32_t center_at_origin;     /* 1 */
+    int32_t reserved[5];
+} reg_octree_params;
+REG_API void reg_default_octree_params(reg_octree_params* p);
+/* Outputs (host pointers, or device pointers when on_device != 0); only xyz is required.
+     xyz        n_out x 3 (capacity n rows)   normals n_out x 3 and covs n_out x 6 when the input carries them
+     src_idx    n_out: the chosen input index of each row (CENTROID: the leaf's first member)
+     leaf_id    n (per INPUT point): the depth-first index of its non-empty leaf (== its output row)
+     leaf_depth n (per INPUT point): the depth of its leaf (root 0) */
+typedef struct {
+    float*   xyz;
+    float*   normals;
+    float*   covs;
+    int32_t* src_idx;
+    int32_t* leaf_id;
+    int32_t* leaf_depth;
+} reg_octree_out;
+REG_API reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, const float* nrm,
+                                   const float* cov, int64_t n, int on_device, const reg_octree_params* p,
+                                   const reg_octree_out* out, int64_t* n_out);
+/* Host helpers of the contract: the root box from per-axis min / max, and RandomPtsSampler's member position of each of
+   n_leaves leaves of the given sizes (glibc TYPE_3 rand() stream after srand(1)). */
+REG_API void reg_host_octree_root(const float min[3], const float max[3], int center_at_origin, float center[3],
+                                  float* radius);
+REG_API reg_status reg_host_octree_random_picks(const int64_t* sizes, int64_t n_leaves, int64_t* picks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -148,6 +148,18 @@ def point_filter(spec: dict) -> PointFilter:
     return f
 
 
+class OctreeParams(C.Structure):
+    """reg_octree_params (include/o3dslam_reg.h): OctreeGridDataPointsFilter's parameters."""
+    _fields_ = [("struct_size", C.c_int32), ("build_parallel", C.c_int32), ("max_point_by_node", C.c_int64),
+                ("max_size_by_node", C.c_float), ("sampling_method", C.c_int32), ("center_at_origin", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+class OctreeOut(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("normals", C.c_void_p), ("covs", C.c_void_p), ("src_idx", C.c_void_p),
+                ("leaf_id", C.c_void_p), ("leaf_depth", C.c_void_p)]
+
+
 class PmChain(C.Structure):
     """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint)."""
     _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("minimizer", C.c_int32), ("use_robust", C.c_int32),
@@ -176,7 +188,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
            "reg_default_pm_chain", "reg_check_pm_chain", "reg_set_pm_chain", "reg_get_robust_state",
            "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update",
-           "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points"]
+           "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
+           "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks"]
 
 
 def lib_path() -> str:
@@ -288,6 +301,13 @@ def load_library():
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_filter_points.argtypes = [vp, vp, i64, vp, vp, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp,
                                       C.POINTER(C.c_int64)]
+    lib.reg_default_octree_params.argtypes = [C.POINTER(OctreeParams)]
+    lib.reg_default_octree_params.restype = None
+    lib.reg_octree_grid.argtypes = [vp, vp, i64, vp, vp, i64, C.c_int, C.POINTER(OctreeParams), C.POINTER(OctreeOut),
+                                    C.POINTER(C.c_int64)]
+    lib.reg_host_octree_root.argtypes = [vp, vp, C.c_int, vp, C.POINTER(C.c_float)]
+    lib.reg_host_octree_root.restype = None
+    lib.reg_host_octree_random_picks.argtypes = [vp, i64, vp]
     for name in EXPORTS:
         getattr(lib, name)  # AttributeError if the library does not export what the header declares
     _lib = lib
@@ -353,6 +373,33 @@ def default_ssn_params() -> SsnParams:
     p = SsnParams()
     load_library().reg_default_ssn_params(C.byref(p))
     return p
+
+
+def default_octree_params(**kw) -> OctreeParams:
+    """reg_octree_params at OctreeGrid.h's defaults; `kw` sets fields."""
+    p = OctreeParams()
+    load_library().reg_default_octree_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def host_octree_root(lo, hi, center_at_origin=True):
+    """reg_host_octree_root: (centre float32[3], radius float32) of the octree's root box from per-axis min / max."""
+    lo, hi = _f32(np.reshape(lo, 3)), _f32(np.reshape(hi, 3))
+    c, r = np.zeros(3, np.float32), C.c_float(0)
+    load_library().reg_host_octree_root(_ptr(lo), _ptr(hi), int(bool(center_at_origin)), _ptr(c), C.byref(r))
+    return c, np.float32(r.value)
+
+
+def host_octree_random_picks(sizes) -> np.ndarray:
+    """reg_host_octree_random_picks: RandomPtsSampler's member position per leaf (glibc rand() after srand(1))."""
+    sz = np.ascontiguousarray(sizes, np.int64)
+    picks = np.zeros(sz.size, np.int64)
+    st = load_library().reg_host_octree_random_picks(_ptr(sz), sz.size, _ptr(picks))
+    if st != 0:
+        raise RegError(st, "reg_host_octree_random_picks: leaf sizes must be >= 1")
+    return picks
 
 
 def default_pm_chain() -> PmChain:
@@ -654,6 +701,44 @@ class Registration:
         self._check(self._lib.reg_filter_points(self._h, C.c_void_p(xyz_ptr), xyz_stride, nrm_ptr, cov_ptr, n, 1,
                                                 C.cast(arr, C.c_void_p), len(filters), out_xyz_ptr, out_nrm_ptr,
                                                 out_cov_ptr, out_idx_ptr, C.byref(m)))
+        return int(m.value)
+
+    def octree_grid(self, xyz, params: "OctreeParams | None" = None, normals=None, covs=None, **kw):
+        """OctreeGridDataPointsFilter on the device (reg_octree_grid).  `kw` sets OctreeParams fields.  Returns a dict:
+        xyz (m,3), src_idx (m,), normals / covs when given, leaf_id (n,), leaf_depth (n,), n_out."""
+        p = params if params is not None else default_octree_params()
+        for k, v in kw.items():
+            setattr(p, k, v)
+        xyz = _f32(xyz)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        nr = _f32(normals) if normals is not None else None
+        cv = _f32(covs) if covs is not None else None
+        out = {"xyz": np.zeros((n, 3), np.float32), "src_idx": np.zeros(n, np.int32),
+               "leaf_id": np.zeros(n, np.int32), "leaf_depth": np.zeros(n, np.int32)}
+        if nr is not None:
+            out["normals"] = np.zeros((n, 3), np.float32)
+        if cv is not None:
+            out["covs"] = np.zeros((n, 6), np.float32)
+        o = OctreeOut()
+        for key in ("xyz", "normals", "covs", "src_idx", "leaf_id", "leaf_depth"):
+            setattr(o, key, out[key].ctypes.data if key in out else None)
+        m = C.c_int64(0)
+        self._check(self._lib.reg_octree_grid(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, _ptr(nr), _ptr(cv),
+                                              n, 0, C.byref(p), C.byref(o), C.byref(m)))
+        for key in ("xyz", "src_idx", "normals", "covs"):
+            if key in out:
+                out[key] = out[key][:m.value].copy()
+        out["n_out"] = int(m.value)
+        return out
+
+    def octree_grid_device(self, xyz_ptr, xyz_stride, n, params: "OctreeParams", xyz_out_ptr, nrm_ptr=None, cov_ptr=None,
+                           normals_out_ptr=None, covs_out_ptr=None, src_idx_ptr=None, leaf_id_ptr=None,
+                           leaf_depth_ptr=None) -> int:
+        """Device-pointer form: outputs hold n rows of capacity.  Returns n_out."""
+        o = OctreeOut(xyz_out_ptr, normals_out_ptr, covs_out_ptr, src_idx_ptr, leaf_id_ptr, leaf_depth_ptr)
+        m = C.c_int64(0)
+        self._check(self._lib.reg_octree_grid(self._h, C.c_void_p(xyz_ptr), xyz_stride, nrm_ptr, cov_ptr, n, 1,
+                                              C.byref(params), C.byref(o), C.byref(m)))
         return int(m.value)
 
     def smooth_normals(self, normals, ids):

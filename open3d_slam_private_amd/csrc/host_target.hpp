@@ -190,6 +190,9 @@ struct reg_handle {
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
     DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;
+    // OctreeGridDataPointsFilter (host_octree.hpp): keys, sort orders, ranks, centres, per-round flags, leaf starts
+    DevBuf o_keys, o_keys_s, o_iota, o_idx, o_idx2, o_rank, o_rank_a, o_rank_s, o_c, o_kk, o_heads, o_pos, o_open, o_depth,
+        o_start, o_rand, o_radii;
 };
 
 #define HIPCHK(h, call)                                                                        \
@@ -333,7 +336,10 @@ void reg_destroy(reg_handle* h) {
                       &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
                       &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
-                      &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out};
+                      &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out,
+                      &h->o_keys, &h->o_keys_s, &h->o_iota, &h->o_idx, &h->o_idx2, &h->o_rank, &h->o_rank_a, &h->o_rank_s,
+                      &h->o_c, &h->o_kk, &h->o_heads, &h->o_pos, &h->o_open, &h->o_depth, &h->o_start, &h->o_rand,
+                      &h->o_radii};
     for (DevBuf* b : bufs) b->release();
     if (h->h_mirror) (void)hipHostFree(h->h_mirror);
     if (h->h_iter) (void)hipHostFree(h->h_iter);

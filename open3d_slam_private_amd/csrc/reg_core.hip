@@ -46,6 +46,7 @@ using namespace o3dreg;
 #include "kernels_normals.hpp"
 #include "kernels_pmchain.hpp"
 #include "kernels_filters.hpp"
+#include "kernels_octree.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
@@ -53,6 +54,7 @@ using namespace o3dreg;
 #include "host_dist.hpp"
 #include "host_rccl.hpp"
 #include "host_filters.hpp"
+#include "host_octree.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -231,8 +231,9 @@ class PointMatcherICP(ICP):
         super().__init__()
         self.chain: capi.PmChain | None = None
         self.referenceDataPointsFilters: list = []
-        self.readingDataPointsFilters: list[dict] = []
+        self.readingDataPointsFilters: list = []   # reg_filter_points specs and OctreeGridDataPointsFilter steps
         self._dev: dict = {}
+        self._read_stages: list = []
 
     def setDefault(self):
         super().setDefault()
@@ -240,8 +241,9 @@ class PointMatcherICP(ICP):
         self.referenceDataPointsFilters, self.readingDataPointsFilters = [], []
 
     def loadFromYaml(self, stream_or_text):
-        """Also binds referenceDataPointsFilters (SamplingSurfaceNormal, SurfaceNormal) and readingDataPointsFilters
-        (READING_FILTERS) to the device filters (reg_sampling_surface_normal, reg_estimate_normals, reg_filter_points)."""
+        """Also binds referenceDataPointsFilters (SamplingSurfaceNormal, SurfaceNormal, OctreeGrid) and
+        readingDataPointsFilters (READING_FILTERS, OctreeGrid) to the device filters (reg_sampling_surface_normal,
+        reg_estimate_normals, reg_filter_points, reg_octree_grid)."""
         import yaml
         text = stream_or_text.read() if hasattr(stream_or_text, "read") else stream_or_text
         doc = yaml.safe_load(text) or {}
@@ -311,8 +313,19 @@ class PointMatcherICP(ICP):
         src = self._buf("ref_in", x.nbytes)
         src.upload(x)
         cur, cur_stride, nrm = src.value, stride, None
+        if referenceIn.normals is not None and any(isinstance(f, OctreeGridDataPointsFilter)
+                                                   for f in self.referenceDataPointsFilters):
+            nb = self._buf("ref_nrm_in", n * 12)   # an octree step carries the descriptors it is given
+            nb.upload(np.ascontiguousarray(referenceIn.normals, np.float32))
+            nrm = nb.value
         for i, f in enumerate(self.referenceDataPointsFilters):
-            if isinstance(f, SamplingSurfaceNormalDataPointsFilter):
+            if isinstance(f, OctreeGridDataPointsFilter):
+                ox = self._buf(f"ref_xyz{i}", n * 12)
+                on = self._buf(f"ref_nrm{i}", n * 12) if nrm is not None else None
+                n = self._reg.octree_grid_device(cur, cur_stride, n, f.params(), ox.value, nrm, None,
+                                                 on.value if on is not None else None)
+                cur, cur_stride, nrm = ox.value, 3, (on.value if on is not None else None)
+            elif isinstance(f, SamplingSurfaceNormalDataPointsFilter):
                 ox, on = self._buf(f"ref_xyz{i}", n * 12), self._buf(f"ref_nrm{i}", n * 12)
                 n, _ = self._reg.sampling_surface_normal_device(cur, cur_stride, n, f.params(), ox.value,
                                                                 on.value if f.keepNormals else None)
@@ -342,20 +355,48 @@ class PointMatcherICP(ICP):
         if readingIn.covariances is not None:
             cin = self._buf("read_cov_in", n * 24)
             cin.upload(np.ascontiguousarray(readingIn.covariances, np.float32))
-        ox, oi = self._buf("read_xyz", n * 12), self._buf("read_idx", n * 4)
-        on = self._buf("read_nrm", n * 12) if nin is not None else None
-        oc = self._buf("read_cov", n * 24) if cin is not None else None
-        m = self._reg.filter_points_device(src.value, stride, n, self.readingDataPointsFilters, ox.value,
-                                           nin.value if nin else None, cin.value if cin else None,
-                                           on.value if on else None, oc.value if oc else None, oi.value)
-        if m == 0:
-            raise RuntimeError("The reading point cloud is empty.")   # ICP.cpp:958-960
-        self._reg.set_source_device(ox.value, 3, m, on.value if on else None, 3, oc.value if oc else None)
-        self.readingFilteredCount = m
+        cur, cur_stride = src.value, stride
+        cur_nrm, cur_cov = (nin.value if nin else None), (cin.value if cin else None)
+        self._read_stages = []
+        # runs of point filters go to reg_filter_points in one call; every octree step is a reg_octree_grid call
+        stages, run = [], []
+        for f in self.readingDataPointsFilters:
+            if isinstance(f, OctreeGridDataPointsFilter):
+                if run:
+                    stages.append(run)
+                stages.append(f)
+                run = []
+            else:
+                run.append(f)
+        if run or not stages:
+            stages.append(run)
+        for k, st in enumerate(stages):
+            sfx = "" if k == 0 else str(k)
+            ox, oi = self._buf("read_xyz" + sfx, n * 12), self._buf("read_idx" + sfx, n * 4)
+            on = self._buf("read_nrm" + sfx, n * 12) if cur_nrm is not None else None
+            oc = self._buf("read_cov" + sfx, n * 24) if cur_cov is not None else None
+            if isinstance(st, OctreeGridDataPointsFilter):
+                m = self._reg.octree_grid_device(cur, cur_stride, n, st.params(), ox.value, cur_nrm, cur_cov,
+                                                 on.value if on else None, oc.value if oc else None, oi.value)
+            else:
+                m = self._reg.filter_points_device(cur, cur_stride, n, st, ox.value, cur_nrm, cur_cov,
+                                                   on.value if on else None, oc.value if oc else None, oi.value)
+            if m == 0:
+                raise RuntimeError("The reading point cloud is empty.")   # ICP.cpp:958-960
+            self._read_stages.append(("read_idx" + sfx, m))
+            cur, cur_stride, n = ox.value, 3, m
+            cur_nrm, cur_cov = (on.value if on else None), (oc.value if oc else None)
+        self._reg.set_source_device(cur, 3, n, cur_nrm, 3, cur_cov)
+        self.readingFilteredCount = n
 
     def readingFilteredIndices(self) -> np.ndarray:
-        """Source index (into the last compute()'s reading) of every filtered reading point."""
-        return self._dev["read_idx"].download(self.readingFilteredCount, np.int32)
+        """Source index (into the last compute()'s reading) of every filtered reading point, composed through every
+        step of the chain."""
+        idx = None
+        for key, m in self._read_stages:
+            step = self._dev[key].download(m, np.int32)
+            idx = step if idx is None else idx[step]
+        return idx
 
     def _ensure(self):
         fresh = self._reg is None
@@ -457,6 +498,54 @@ class SamplingSurfaceNormalDataPointsFilter:
         return DataPoints(out["xyz"], out.get("normals"), None)
 
 
+class OctreeGridDataPointsFilter:
+    """OctreeGridDataPointsFilter (DataPointsFilters/OctreeGrid.{h,cpp}, utils/octree) on the device (reg_octree_grid),
+    parameters by the reference's names and defaults.  Row k of the output is the sample of the k-th non-empty leaf in
+    depth-first order (the documented deviation from the samplers' swapCols bookkeeping); samplingMethod 1
+    replays glibc's rand() after srand(1), as RandomPtsSampler does on every call.  Normals and covariances are carried
+    (CENTROID averages them).  After `filter`, srcIdx / leafId / leafDepth hold the last call's indices."""
+
+    PARAMS = {"buildParallel": 1, "maxPointByNode": 1, "maxSizeByNode": 0.0, "samplingMethod": 0, "centerAtOrigin": 1}
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.PARAMS)
+        if unknown:
+            raise InvalidParameter(f"OctreeGridDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
+        a = dict(self.PARAMS, **kw)
+        try:
+            self.maxPointByNode, self.maxSizeByNode = int(a["maxPointByNode"]), float(a["maxSizeByNode"])
+            self.samplingMethod = int(a["samplingMethod"])
+            flags = {k: int(a[k]) for k in ("buildParallel", "centerAtOrigin")}
+        except (TypeError, ValueError):
+            raise InvalidParameter("OctreeGridDataPointsFilter: parameters must be numbers") from None
+        if not 1 <= self.maxPointByNode <= 4294967295:
+            raise InvalidParameter("maxPointByNode: must lie in 1..4294967295 (OctreeGrid.h)")
+        if not self.maxSizeByNode >= 0:
+            raise InvalidParameter("maxSizeByNode: must be >= 0 (OctreeGrid.h)")
+        if self.samplingMethod not in (0, 1, 2, 3):
+            raise InvalidParameter("samplingMethod: 0 (first), 1 (random), 2 (centroid) or 3 (medoid)")
+        if any(v not in (0, 1) for v in flags.values()):
+            raise InvalidParameter("buildParallel / centerAtOrigin: 0 or 1")
+        self.buildParallel, self.centerAtOrigin = bool(flags["buildParallel"]), bool(flags["centerAtOrigin"])
+        self.srcIdx = self.leafId = self.leafDepth = None
+        self._reg = None
+
+    def params(self) -> capi.OctreeParams:
+        return capi.default_octree_params(max_point_by_node=self.maxPointByNode, max_size_by_node=self.maxSizeByNode,
+                                          sampling_method=self.samplingMethod, center_at_origin=int(self.centerAtOrigin),
+                                          build_parallel=int(self.buildParallel))
+
+    def filter(self, cloud: DataPoints) -> DataPoints:
+        if self._reg is None:
+            self._reg = capi.Registration(capi.default_params())
+        try:
+            out = self._reg.octree_grid(cloud.features, self.params(), cloud.normals, cloud.covariances)
+        except RegError as e:
+            raise _translate(e) from None
+        self.srcIdx, self.leafId, self.leafDepth = out["src_idx"], out["leaf_id"], out["leaf_depth"]
+        return DataPoints(out["xyz"], out.get("normals"), out.get("covs"))
+
+
 # readingDataPointsFilters bound to reg_filter_points: name -> {parameter: default} (each filter's .h)
 READING_FILTERS = {
     "IdentityDataPointsFilter": {},
@@ -481,8 +570,10 @@ def _split(f):
     return name, dict(args or {})
 
 
-def _reading_filter(f) -> dict:
+def _reading_filter(f):
     name, args = _split(f)
+    if name == "OctreeGridDataPointsFilter":
+        return OctreeGridDataPointsFilter(**args)
     if name in _REFUSED_FILTERS:
         raise NotImplementedError(f"{name}: {_REFUSED_FILTERS[name]}")
     if name not in READING_FILTERS:
@@ -503,6 +594,8 @@ def _reference_filter(f):
     name, args = _split(f)
     if name == "SamplingSurfaceNormalDataPointsFilter":
         return SamplingSurfaceNormalDataPointsFilter(**args)
+    if name == "OctreeGridDataPointsFilter":
+        return OctreeGridDataPointsFilter(**args)
     if name == "SurfaceNormalDataPointsFilter":
         known = {"knn", "maxDist", "epsilon", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
                  "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"}
