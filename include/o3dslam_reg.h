@@ -100,7 +100,8 @@ typedef struct {
     int32_t max_iter;           /* CounterTransformationChecker.maxIterationCount */
     float   min_diff_rot;       /* DifferentialTransformationChecker */
     float   min_diff_trans;
-    int32_t smooth_len;
+    int32_t smooth_len;         /* smoothLength, at most 15: reg_create returns REG_BAD_ARGUMENT above (the device
+                                   checkers keep the last 16 poses); <= 0 turns the differential checker off */
     int32_t fixed_iters;        /* >0: run exactly this many iterations, checkers ignored (throughput runs) */
     /* GICP termination, rule 0 (Gauss-Newton, rotation-first tangent); rule 1: gicp_stop_rule below */
     float   gicp_rot_eps;       /* rad */

@@ -19,6 +19,7 @@ COST_P2PL, COST_GICP = 0, 1
 # Open3D RegistrationICP with TransformationEstimationPointToPlane / PointToPoint (RegistrationIcpPointToPlane /
 # RegistrationIcpPointToPoint, open3d_slam/src/CloudRegistration.cpp:54-101); see reg_cost in the header
 COST_O3D_P2PL, COST_O3D_P2P = 2, 3
+SMOOTH_LEN_MAX = 15   # reg_params.smooth_len: reg_create returns BAD_ARGUMENT above (the device checkers keep 16 poses)
 
 
 class RegError(RuntimeError):

@@ -440,7 +440,7 @@ O3D_HD inline float quat_angular_distance(const float* a, const float* b) {
     return 2.0f * atan2f(sqrt(x * x + y * y + z * z), fabs(w));
 }
 
-constexpr int kCheckerHist = 16;   // smooth_len is clamped to kCheckerHist - 1
+constexpr int kCheckerHist = 16;   // reg_create refuses smooth_len > kCheckerHist - 1 (init's clamp only guards the ring)
 
 // DifferentialTransformationChecker + CounterTransformationChecker state (fixed-size ring so the same
 // code runs inside the device-side update kernel).

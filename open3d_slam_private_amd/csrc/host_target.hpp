@@ -277,6 +277,9 @@ reg_status reg_create(const reg_params* p, reg_handle** out) {
     if (p->cost != REG_COST_P2PL && p->cost != REG_COST_GICP && !cost_is_o3d(p->cost)) return REG_BAD_ARGUMENT;
     if (p->use_trimmed && !(p->trim_ratio >= 0.f && p->trim_ratio <= 1.f)) return REG_BAD_ARGUMENT;
     if (p->fixed_iters <= 0 && p->max_iter <= 0) return REG_BAD_ARGUMENT;
+    // the device checkers keep the last kCheckerHist poses (k_tail stages them in LDS): a longer smoothing window would
+    // average other steps than the reference's DifferentialTransformationChecker, so it is refused, not clamped
+    if (p->smooth_len > kCheckerHist - 1) return REG_BAD_ARGUMENT;
     // the analysis expects libpointmatcher's point-to-plane (ICP.cpp:1118): GICP and the Open3D costs reject it
     if (p->use_xicp && p->cost != REG_COST_P2PL) return REG_BAD_ARGUMENT;
     if (p->gicp_stop_rule != 0 && p->gicp_stop_rule != 1) return REG_BAD_ARGUMENT;

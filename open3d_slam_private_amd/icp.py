@@ -136,6 +136,8 @@ class ICP:
                 p.min_diff_rot = float(cargs.get("minDiffRotErr", 0.001))
                 p.min_diff_trans = float(cargs.get("minDiffTransErr", 0.001))
                 p.smooth_len = int(cargs.get("smoothLength", 3))
+                if p.smooth_len > capi.SMOOTH_LEN_MAX:     # reg_create refuses it as well
+                    raise InvalidParameter(f"smoothLength: at most {capi.SMOOTH_LEN_MAX} on the accelerated path")
             else:
                 raise NotImplementedError(f"transformation checker {cname}")
         da = doc.get("degeneracyAwareness")

@@ -1,9 +1,13 @@
 """The exact reference for the shipped point-to-plane chain, shared by the GPU tests (a plain helper module, not a test):
 global centroid, kd-tree, TrimmedDist plus the normal-angle filter, fp64 normal equations -- the oracle's R1 / R2 replayed
-once (numeric contract NC1-NC4), the kd-tree kept for several poses."""
+once (numeric contract NC1-NC4), the kd-tree kept for several poses -- and the field-by-field comparison of a finished
+registration with the oracle's."""
+import math
+
 import numpy as np
 
 from oracle import oracle as orc
+from open3d_slam_private_amd import synth
 
 NT = max(1, min(orc.max_threads(), 64))
 
@@ -48,7 +52,7 @@ class OracleSide:
     leaves TrimmedDist out (use_trimmed = 0); `T_init` is the prior R2 pre-transforms with (a rigid one: R3's
     re-orthogonalisation is not replayed)."""
 
-    def __init__(self, sc, n_src=None, c_read=None, src_xyz=None, src_nrm=None, trim_ratio=0.9, T_init=None):
+    def __init__(self, sc, n_src=None, c_read=None, src_xyz=None, src_nrm=None, trim_ratio=0.9, T_init=None, tree=None):
         src = sc.src_xyz[:n_src] if src_xyz is None else src_xyz
         snrm = sc.src_nrm[:n_src] if src_nrm is None else src_nrm
         self.c_ref = orc.centroid(sc.tgt_xyz)
@@ -62,7 +66,7 @@ class OracleSide:
         self.rd = _xf(T0, src - self.c_read)
         self.rdn = _rot(T0, snrm)
         self.tgt_nrm = sc.tgt_nrm
-        self.tree = orc.KdTree(self.tgt_c)
+        self.tree = orc.KdTree(self.tgt_c) if tree is None else tree   # `tree`: another side's, of the same target
         self.filt = orc.make_filters(trim_ratio=trim_ratio, max_normal_angle=1.57)
 
     def linearize(self, T_iter):
@@ -71,3 +75,49 @@ class OracleSide:
         w, limit = orc.weights(self.filt, self.rdn, self.tgt_nrm, T_iter, ids, d2, n_threads=NT)
         A6, b6, err, kept = orc.p2pl_normal_eq(self.rd, self.tgt_c, self.tgt_nrm, T_iter, ids, d2, w, n_threads=NT)
         return ids, d2, w, A6, b6, err, kept
+
+
+def oracle_registration(sc, p, T0):
+    """The oracle's registration of the scene with a handle's reg_params `p` (X-ICP as configured) from the prior T0."""
+    To, ores = orc.icp_p2pl(sc.tgt_xyz, sc.tgt_nrm, sc.src_xyz, sc.src_nrm, T0, max_dist=p.max_dist,
+                            trim_ratio=p.trim_ratio if p.use_trimmed else None,
+                            max_normal_angle=p.max_normal_angle if p.use_surface_normal else None, max_iter=p.max_iter,
+                            min_diff_rot=p.min_diff_rot, min_diff_trans=p.min_diff_trans, smooth_len=p.smooth_len,
+                            fixed_iters=p.fixed_iters, n_threads=NT,
+                            xicp=(p.xicp_enough, p.xicp_insufficient, p.xicp_min_angle_deg, p.xicp_strong_angle_deg)
+                            if p.use_xicp else None)
+    assert ores.status == 0
+    return To, ores
+
+
+def _T(buf):
+    return np.array(buf, np.float32).reshape(4, 4).T.copy()
+
+
+def check_against_oracle(what, T, res, corr, To, ores, side, n):
+    """One finished registration, field by field, against the oracle's."""
+    assert (res.iterations, bool(res.converged), bool(res.max_iter_reached)) == \
+        (ores.iterations, bool(ores.converged), bool(ores.max_iter_reached)), what
+    dt, dr = synth.pose_error(T, To)
+    assert dt <= 1e-4 and dr <= 1e-4, (what, dt, dr)
+    dt, dr = synth.pose_error(_T(res.T_iter_last), np.array(ores.T_iter, np.float32).reshape(4, 4))
+    assert dt <= 1e-4 and dr <= 1e-4, (what, "T_iter_last", dt, dr)
+    ids, d2, w, A6, b6, err, kept = side.linearize(_T(res.T_iter_prev))
+    gids, gd2, gw = corr
+    assert np.array_equal(gids, ids), f"{what}: {(gids != ids).sum()} of {ids.size} ids differ"
+    assert np.array_equal(gd2.view(np.uint32), d2.view(np.uint32)), f"{what}: d2 not bit-exact"
+    assert np.array_equal(gw, w), f"{what}: {(gw != w).sum()} weights differ"
+    assert res.n_inliers == kept and res.n_matched == int((ids >= 0).sum()), (what, res.n_inliers, kept)
+    assert abs(res.error - err) <= 1e-9 * max(err, 1e-30), (what, res.error, err)
+    assert res.fitness == kept / n, (what, res.fitness, kept / n)
+    rmse = math.sqrt(float(np.sum(d2[w != 0].astype(np.float64))) / kept)
+    assert abs(res.inlier_rmse - rmse) <= 1e-9 * rmse, (what, res.inlier_rmse, rmse)
+    scale = np.abs(A6).max()
+    H = np.array(res.H_last, np.float32).reshape(6, 6)
+    b = np.array(res.b_last, np.float32)
+    assert np.abs(H - A6).max() <= 1e-6 * scale, (what, np.abs(H - A6).max(), scale)
+    assert np.abs(b - b6).max() <= 1e-6 * np.abs(b6).max() + 1e-9 * scale, (what, np.abs(b - b6).max())
+    assert list(res.localizable) == list(ores.localizable) and res.n_constraints == ores.n_constraints, what
+    for k in range(6):
+        assert abs(res.xicp_combined[k] - ores.xicp_combined[k]) <= 1e-9 * max(1.0, ores.xicp_combined[k]), what
+        assert abs(res.xicp_high[k] - ores.xicp_high[k]) <= 1e-9 * max(1.0, ores.xicp_high[k]), what

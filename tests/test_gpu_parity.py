@@ -167,7 +167,9 @@ def test_synth_shipped_chain(n_src, n_tgt):
     T, res = reg.register(np.eye(4))
     To, ores = orc.icp_p2pl(sc.tgt_xyz, sc.tgt_nrm, sc.src_xyz, sc.src_nrm, max_dist=0.5, trim_ratio=0.9,
                             max_normal_angle=1.57, max_iter=30, min_diff_rot=0.001, min_diff_trans=0.008,
-                            smooth_len=3, n_threads=8)
+                            smooth_len=3, n_threads=8, xicp=(250.0, 180.0, 80.0, 45.0))   # the shipped chain has X-ICP on
+    assert p.use_xicp == 1
+    assert (res.iterations, res.converged, res.max_iter_reached) == (ores.iterations, ores.converged, ores.max_iter_reached)
     dt, dr = synth.pose_error(T, To)
     assert dt <= 1e-4 and dr <= 1e-4, (dt, dr)
     # and the registration actually recovers the synthetic motion
@@ -439,6 +441,31 @@ def _register(sc, **over):
     T, res = reg.register(np.eye(4))
     ids, d2, w = reg.correspondences()
     return T, res, ids, d2, w
+
+
+def _oracle_pose(sc, **over):
+    from oracle_side import oracle_registration
+    p = capi.shipped_params()
+    for k, v in over.items():
+        setattr(p, k, v)
+    return oracle_registration(sc, p, np.eye(4, dtype=np.float32))[0]
+
+
+def _vs_oracle(sc, T, res, corr, T0=None, **over):
+    """tests/oracle_side.check_against_oracle for a registration with the shipped chain plus `over` from T0."""
+    from oracle_side import OracleSide, check_against_oracle, oracle_registration
+    p = capi.shipped_params()
+    for k, v in over.items():
+        setattr(p, k, v)
+    T0 = np.eye(4, dtype=np.float32) if T0 is None else T0
+    key = (id(sc), T0.tobytes(), tuple(sorted(over.items())))
+    if key not in _ORACLE_RUNS:         # the same registration is checked on several loop paths
+        _ORACLE_RUNS[key] = (*oracle_registration(sc, p, T0), OracleSide(sc, T_init=T0))
+    To, ores, side = _ORACLE_RUNS[key]
+    check_against_oracle(over, T, res, corr, To, ores, side, sc.src_xyz.shape[0])
+
+
+_ORACLE_RUNS = {}
 
 
 @pytest.mark.parametrize("seed", [101, 102, 103])
@@ -1158,17 +1185,21 @@ def test_tail_entry_policy_in_checker_mode():
     more than it saves, tools/tools_checker_priors.py), a long one does; with a fixed count it takes over as soon as the trimmed
     limit allows.  Poses equal the select-based path's either way."""
     sc = synth.make_scene(24000, 240000, seed=90)
-    Ts, rs, *_ = _register(sc)                                   # checker mode, converges quickly
+    Ts, rs, *cs = _register(sc)                                  # checker mode, converges quickly
     Tg, rg, *_ = _register(sc, disable_fused=1)
     assert rs.iterations == rg.iterations and rs.iterations <= 6 and rs.n_tail_launches == 0
     assert np.abs(Ts - Tg).max() <= 2e-6
-    Tf, rf, *_ = _register(sc, fixed_iters=12)
+    _vs_oracle(sc, Ts, rs, cs)
+    Tf, rf, *cf = _register(sc, fixed_iters=12)
     assert rf.n_tail_launches >= 1 and rf.n_tail_iterations >= 5
+    dt, dr = synth.pose_error(Tf, _oracle_pose(sc, fixed_iters=12))
+    assert dt <= 1e-4 and dr <= 1e-4, (dt, dr)
     # a registration the checkers let run long (tight limits): the tail takes over after the eighth iteration
-    Tl, rl, *_ = _register(sc, min_diff_rot=1e-9, min_diff_trans=1e-9, max_iter=25)
+    Tl, rl, *cl = _register(sc, min_diff_rot=1e-9, min_diff_trans=1e-9, max_iter=25)
     Tlg, rlg, *_ = _register(sc, min_diff_rot=1e-9, min_diff_trans=1e-9, max_iter=25, disable_fused=1)
     assert rl.iterations == rlg.iterations and rl.iterations >= 10 and rl.n_tail_launches >= 1
     assert np.abs(Tl - Tlg).max() <= 2e-6
+    _vs_oracle(sc, Tl, rl, cl, min_diff_rot=1e-9, min_diff_trans=1e-9, max_iter=25)
 
 
 def test_persistent_tail_stall_and_repair_and_iteration_budget():
@@ -1255,7 +1286,9 @@ def test_far_priors_in_checker_mode_wait_for_the_pose_to_calm_down(monkeypatch):
             dT = np.eye(4)
             dT[:3, :3] = synth.rpy_to_R(*rng.normal(scale=0.05, size=3))
             dT[:3, 3] = rng.normal(scale=0.25, size=3)
-            T, res = reg.register((dT @ Tt).astype(np.float32))
+            T0 = (dT @ Tt).astype(np.float32)
+            T, res = reg.register(T0)
+            _vs_oracle(sc, T, res, reg.correspondences(), T0)
             out.append((T, res.iterations))
             stalls += res.n_band_stalls
         reg.close()

@@ -111,6 +111,22 @@ def test_reg_create_rejects_bad_parameters():
     p = capi.default_params()
     p.trim_ratio = 1.5
     assert lib.reg_create(C.byref(p), C.byref(h)) == 6
+    # the device checkers keep the last 16 poses: a longer smoothing window is refused, not clamped to 15
+    for sl in (capi.SMOOTH_LEN_MAX + 1, 24):
+        p = capi.default_params()
+        p.smooth_len = sl
+        assert lib.reg_create(C.byref(p), C.byref(h)) == 6, sl
+        assert not h.value
+    with pytest.raises(capi.RegError) as e:
+        capi.Registration(capi.shipped_params(), smooth_len=16)
+    assert e.value.status == 6
+    m = icp.ICP()
+    with pytest.raises(icp.InvalidParameter):
+        m.loadFromYaml(SHIPPED_YAML.replace("smoothLength: 3", "smoothLength: 16"))
+    with pytest.raises(icp.InvalidParameter):
+        icp.PointMatcherICP().loadFromYaml(SHIPPED_YAML.replace("smoothLength: 3", "smoothLength: 24"))
+    m.loadFromYaml(SHIPPED_YAML.replace("smoothLength: 3", "smoothLength: 15"))
+    assert m.params.smooth_len == 15
 
 
 SHIPPED_YAML = """
