@@ -28,6 +28,11 @@ typedef struct {
 /* Call right after reg_create, before reg_set_target (disable_halo and debug_flags & 32 act on the table build). */
 REG_API reg_status reg_debug_configure(reg_handle* h, const reg_debug_params* d);
 
+/* Empty-space bound of the halo directory (tests): out[i] = the lower bound on the distance from position i (n x 3 floats,
+ * frame of reg_set_target's input) to any reference point that the search reads for the halo bin of that position; 0 for a
+ * bin that lists points; -1 where the search does not consult the directory (outside the halo grid, no halo level). */
+REG_API reg_status reg_debug_halo_bound(reg_handle* h, const float* xyz, int64_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,7 +183,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dist_fused_buffers", "reg_dist_poll", "reg_estimate_normals", "reg_smooth_normals", "reg_host_solve6_xicp",
            "reg_set_target_f64", "reg_get_target_source_indices", "reg_voxelize_within_volume", "reg_carve_indices", "reg_dist_xicp_buffers", "reg_dist_gather_buffers",
            "reg_dist_record", "reg_dist_centroid_sums", "reg_dist_prepare",
-           "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure",
+           "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure", "reg_debug_halo_bound",
            "reg_dist_get_unique_id", "reg_dist_init", "reg_dist_init_custom", "reg_dist_register", "reg_dist_shutdown",
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
@@ -229,6 +229,7 @@ def load_library():
     lib.reg_last_error.restype = C.c_char_p
     lib.reg_set_stream.argtypes = [vp, vp]
     lib.reg_debug_configure.argtypes = [vp, C.POINTER(RegDebugParams)]
+    lib.reg_debug_halo_bound.argtypes = [vp, f32p, i64, f32p]
     lib.reg_dist_get_unique_id.argtypes = [C.c_char_p]
     lib.reg_dist_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
     lib.reg_dist_init_custom.argtypes = [vp, C.POINTER(Collectives), C.c_int, C.c_int]
@@ -792,6 +793,14 @@ class Registration:
         n = C.c_int64(0)
         self._check(self._lib.reg_information_matrix(self._h, _ptr(Ti), float(max_dist), info, C.byref(n)))
         return np.array(info[:], np.float64).reshape(6, 6), int(n.value)
+
+    def halo_bound(self, xyz):
+        """reg_debug_halo_bound: per position (frame of set_target's input) the empty-space bound the search reads for its
+        halo bin [m]; 0 for a bin that lists points, -1 where the search does not consult the directory."""
+        x = _f32(xyz)
+        out = np.empty(x.shape[0], np.float32)
+        self._check(self._lib.reg_debug_halo_bound(self._h, _ptr(x), x.shape[0], _ptr(out)))
+        return out
 
     def prepare(self, T_init=None):
         Ti = _T_in(np.eye(4) if T_init is None else T_init)

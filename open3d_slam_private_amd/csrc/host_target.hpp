@@ -37,6 +37,7 @@ struct EnvSwitches {
     bool event_timing = false;  // O3D_EVENT_TIMING: loop_ms from HIP events even when not profiling
     bool halo_occ = true;       // O3D_NO_HALO_OCC: halo-bin edge from the floored bin edge instead of the density-derived one (A/B)
     bool no_dynprune = false;   // O3D_NO_DYNPRUNE: level scans keep the ball they started with (A/B)
+    bool no_empty_bound = false;   // O3D_NO_EMPTY_BOUND: the halo directory carries no empty-space bound (A/B)
     bool no_burst = false;      // O3D_NO_BURST: trickle-feed the fused iterations (A/B of the burst submission)
     bool hints = false;         // O3D_HINTS: histogram of the terminating search level of the last iteration
     bool stamps = false;        // O3D_STAMPS: in-kernel cycle stamps of the update kernel
@@ -70,6 +71,7 @@ struct EnvSwitches {
         event_timing = getenv("O3D_EVENT_TIMING") != nullptr;
         no_burst = getenv("O3D_NO_BURST") != nullptr;
         no_dynprune = getenv("O3D_NO_DYNPRUNE") != nullptr;
+        no_empty_bound = getenv("O3D_NO_EMPTY_BOUND") != nullptr;
         halo_occ = getenv("O3D_NO_HALO_OCC") == nullptr;
         hints = getenv("O3D_HINTS") != nullptr;
         stamps = getenv("O3D_STAMPS") != nullptr;
@@ -153,7 +155,7 @@ struct reg_handle {
     IterState* h_iter = nullptr;      // pinned staging copy of the iteration state
     DevBuf i_iter;                    // IterState on the device
     unsigned long long seq = 0;
-    DevBuf t_halo_start, t_halo_cursor, t_halo_pts, i_band, i_acc, i_cache, i_stats, i_queue, i_qcount;
+    DevBuf t_halo_start, t_halo_cursor, t_halo_pts, t_halo_dir, i_band, i_acc, i_cache, i_stats, i_queue, i_qcount;
     DevBuf s_prep;
     PrepState* h_prep = nullptr;      // mapped pinned host copy of the device-side preparation state
     PrepState* d_prep_host = nullptr; // device view of h_prep
@@ -335,7 +337,7 @@ void reg_destroy(reg_handle* h) {
                       &h->t_vals2, &h->t_pts, &h->t_nrm, &h->t_cov, &h->t_flags, &h->t_scan, &h->t_hash, &h->t_cells,
                       &h->t_tmp, &h->t_misc, &h->t_dir, &h->t_rows, &h->s_raw, &h->s_nrm_raw, &h->s_cov_raw, &h->s_xyz, &h->s_nrm, &h->s_cov,
                       &h->s_misc, &h->i_pos, &h->i_d2, &h->i_w, &h->i_hist, &h->i_state, &h->i_partials, &h->i_sums,
-                      &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
+                      &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->t_halo_dir, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
                       &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
                       &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
@@ -361,6 +363,41 @@ const char* reg_last_error(const reg_handle* h) { return h ? h->err.c_str() : "n
 reg_status reg_debug_configure(reg_handle* h, const reg_debug_params* d) {
     if (!h || !d || d->struct_size != (int32_t)sizeof(reg_debug_params)) return REG_BAD_ARGUMENT;
     h->dbg = *d;
+    return REG_OK;
+}
+
+// Diagnostic copy of the halo directory's empty-space bound, looked up on the host exactly as nearest_halo() looks it up:
+// positions in the frame of reg_set_target's input; out[i] = lb of the bin of position i (0 for a bin with a run),
+// -1 where the search would not consult the directory (outside the halo grid, or no halo level).
+reg_status reg_debug_halo_bound(reg_handle* h, const float* xyz, int64_t n, float* out) {
+    if (!h || !xyz || !out || n < 0) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    const Grid& g = h->grid;
+    for (int64_t i = 0; i < n; ++i) out[i] = -1.f;
+    if (h->m <= 0 || !g.use_halo) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const size_t nbins = (size_t)g.hdimx * g.hdimy * g.hdimz;
+    std::vector<uint2> dir(nbins);
+    HIPCHK(h, hipMemcpyAsync(dir.data(), g.halo_dir, nbins * sizeof(uint2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    auto bin = [](float v, float c, float o, float inv) {   // k_center_bbox, then bin_coord_f: one rounding per operation
+        volatile float q = v - c;
+        volatile float d = q - o;
+        volatile float s = d * inv;
+        return std::floor((float)s);
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        const float fx = bin(xyz[3 * i], h->c_ref[0], g.hox, g.hinv_c), fy = bin(xyz[3 * i + 1], h->c_ref[1], g.hoy, g.hinv_c),
+                    fz = bin(xyz[3 * i + 2], h->c_ref[2], g.hoz, g.hinv_c);
+        if (!(fx >= 0.f && fy >= 0.f && fz >= 0.f && fx < (float)g.hdimx && fy < (float)g.hdimy && fz < (float)g.hdimz)) continue;
+        const uint2 hd = dir[((size_t)(int)fz * g.hdimy + (int)fy) * g.hdimx + (int)fx];
+        float lb = 0.f;
+        if ((int)hd.y < 0) {
+            const uint32_t u = hd.y & 0x7fffffffu;
+            std::memcpy(&lb, &u, 4);
+        }
+        out[i] = lb;
+    }
     return REG_OK;
 }
 
@@ -578,11 +615,32 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     hc.dimx = (int)dims[0];
     hc.dimy = (int)dims[1];
     hc.dimz = (int)dims[2];
+    // t_halo_start: counts, then bin starts, then -- once the directory is written -- the fill pass's cursors.
+    // t_halo_dir: the directory {start, count | bound} the search reads; before that, scratch of the bound's passes
+    // (bytes [0, 2 nbins): pass-x gaps, [4 nbins, 5 nbins): occupancy bytes).  t_halo_cursor: pass-y scratch (4 bytes per bin).
     HIPCHK(h, h->t_halo_start.reserve((nbins + 1) * 4));
-    HIPCHK(h, h->t_halo_cursor.reserve((nbins + 1) * 4));
+    HIPCHK(h, h->t_halo_dir.reserve(nbins * 8));
     HIPCHK(h, hipMemsetAsync(h->t_halo_start.p, 0, (nbins + 1) * 4, h->stream));
+    // Empty-space bound: for the bins whose run is empty, a lower bound on the distance to any reference point,
+    // carried in the directory record.  Only a finite max_dist has levels to skip and queries to reject.
+    HaloBoundCfg bc;
+    bc.dimx = hc.dimx;
+    bc.dimy = hc.dimy;
+    bc.dimz = hc.dimz;
+    bc.R = 0;
+    bc.ch = ch;
+    bc.rho_h = rho_h;
+    bc.eps_bins = (float)std::max(dims[0], std::max(dims[1], dims[2])) * (1.0f / 2097152.0f);
+    bc.sub = 2.f * abs_margin;
+    const bool bound = !h->env.no_empty_bound && std::isfinite(h->prm.max_dist) && h->prm.max_dist > 0.f;
+    uint8_t* const occ = (uint8_t*)h->t_halo_dir.p + 4 * nbins;
+    if (bound) {
+        bc.R = (int)std::min(64.0f, std::floor(h->prm.max_dist * inv) + 2.0f);   // (beyond 64 bins: a weaker, still valid bound)
+        HIPCHK(h, h->t_halo_cursor.reserve(nbins * 4));
+        HIPCHK(h, hipMemsetAsync(occ, 0, nbins, h->stream));
+    }
     k_halo_insert<<<grid_for(h->m), 256, 0, h->stream>>>(h->t_pts.as<float4>(), h->m, hc, 0,
-                                                         h->t_halo_start.as<uint32_t>(), nullptr);
+                                                         h->t_halo_start.as<uint32_t>(), nullptr, bound ? occ : nullptr);
     size_t ex_bytes = 0;
     HIPCHK(h, rocprim::exclusive_scan(nullptr, ex_bytes, h->t_halo_start.as<uint32_t>(), h->t_halo_start.as<uint32_t>(),
                                       0u, nbins + 1, rocprim::plus<uint32_t>(), h->stream));
@@ -592,11 +650,17 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
                                       h->stream));
     uint32_t total = 0;
     HIPCHK(h, hipMemcpyAsync(&total, h->t_halo_start.as<uint32_t>() + nbins, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->t_halo_cursor.p, h->t_halo_start.p, nbins * 4, hipMemcpyDeviceToDevice, h->stream));
+    if (bound) {
+        k_halo_gap_x<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(occ, h->t_halo_start.as<uint32_t>(), bc, h->t_halo_dir.as<uchar2>());
+        k_halo_gap_y<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_dir.as<uchar2>(), bc, h->t_halo_cursor.as<ushort2>());
+    }
+    k_halo_dir<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_start.as<uint32_t>(),
+                                                                 bound ? h->t_halo_cursor.as<ushort2>() : nullptr, bc,
+                                                                 h->t_halo_dir.as<uint2>());
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, h->t_halo_pts.reserve((size_t)std::max<uint32_t>(total, 1) * 16));
     k_halo_insert<<<grid_for(h->m), 256, 0, h->stream>>>(h->t_pts.as<float4>(), h->m, hc, 1,
-                                                         h->t_halo_cursor.as<uint32_t>(), h->t_halo_pts.as<float4>());
+                                                         h->t_halo_start.as<uint32_t>(), h->t_halo_pts.as<float4>(), nullptr);
     g.use_halo = 1;
     g.hox = hc.ox;
     g.hoy = hc.oy;
@@ -605,7 +669,12 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     g.hdimx = hc.dimx;
     g.hdimy = hc.dimy;
     g.hdimz = hc.dimz;
-    g.halo_start = h->t_halo_start.as<uint32_t>();
+    g.halo_dir = h->t_halo_dir.as<uint2>();
+    g.hmaxx = bmax[0];
+    g.hmaxy = bmax[1];
+    g.hmaxz = bmax[2];
+    g.lb_sub = 2.f * abs_margin;
+    g.out_bound = bound ? 1 : 0;
     g.halo_pts = h->t_halo_pts.as<float4>();
     g.rho_h = rho_h;
     g.level_after_halo = g.n_levels - 1;
@@ -614,7 +683,7 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
             g.level_after_halo = l;
             break;
         }
-    h->info.table_bytes += (int64_t)((nbins + 1) * 4 + (size_t)total * 16);
+    h->info.table_bytes += (int64_t)(nbins * 8 + (size_t)total * 16);
     return REG_OK;
 }
 

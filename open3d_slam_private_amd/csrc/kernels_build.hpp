@@ -183,9 +183,12 @@ __device__ __forceinline__ void halo_range(float v, float o, float inv_c, float 
     lo = (int)fminf(fmaxf(bin_coord_f(v - r, o, inv_c), 0.f), (float)(dim - 1));
     hi = (int)fminf(fmaxf(bin_coord_f(v + r, o, inv_c), 0.f), (float)(dim - 1));
 }
-// pass 0: count, pass 1: fill (cursor = running insert position per bin)
+// pass 0: count (and mark the bin the point itself lies in: `occ`, one byte per bin, may be null -- plain stores of the
+// same value: bit masks would need atomics, and same-address atomics serialise),
+// pass 1: fill (cursor = running insert position per bin)
 __global__ void k_halo_insert(const float4* __restrict__ pts_sorted, int64_t n, HaloCfg c, int pass,
-                              uint32_t* __restrict__ counts_or_cursor, float4* __restrict__ halo_pts) {
+                              uint32_t* __restrict__ counts_or_cursor, float4* __restrict__ halo_pts,
+                              uint8_t* __restrict__ occ) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 p = pts_sorted[i];
@@ -193,6 +196,13 @@ __global__ void k_halo_insert(const float4* __restrict__ pts_sorted, int64_t n, 
     halo_range(p.x, c.ox, c.inv_c, c.r_ins, c.dimx, x0, x1);
     halo_range(p.y, c.oy, c.inv_c, c.r_ins, c.dimy, y0, y1);
     halo_range(p.z, c.oz, c.inv_c, c.r_ins, c.dimz, z0, z1);
+    if (pass == 0 && occ) {
+        int bx, by, bz, unused;
+        halo_range(p.x, c.ox, c.inv_c, 0.f, c.dimx, bx, unused);
+        halo_range(p.y, c.oy, c.inv_c, 0.f, c.dimy, by, unused);
+        halo_range(p.z, c.oz, c.inv_c, 0.f, c.dimz, bz, unused);
+        occ[((size_t)bz * c.dimy + by) * c.dimx + bx] = 1;
+    }
     for (int z = z0; z <= z1; ++z)
         for (int y = y0; y <= y1; ++y)
             for (int x = x0; x <= x1; ++x) {
@@ -200,4 +210,94 @@ __global__ void k_halo_insert(const float4* __restrict__ pts_sorted, int64_t n, 
                 const uint32_t slot = atomicAdd(&counts_or_cursor[B], 1u);
                 if (pass == 1) halo_pts[slot] = make_float4(p.x, p.y, p.z, __uint_as_float((uint32_t)i));
             }
+}
+
+// Empty-space bound of the halo bins.  lb(B) bounds from below the distance between ANY position that bin_coord_f maps to
+// bin B and ANY reference point.  Two facts, both per bin B' = B + (dx, dy, dz) with g = max(|d| - 1, 0) whole bins between
+// the two per axis:
+//  (a) a reference point INSIDE B' is at least c_h * |g| away;
+//  (b) every reference point p lies only in and near bins whose run is non-empty (a run lists the points within rho_h of
+//      its bin's box).  Let S be the smallest |g|^2 over the bins with a run.  Walking from p towards B by s < rho_h ends in
+//      a bin that lists p, hence one with |g|^2 >= S, and has shortened the distance by exactly s: p is at least
+//      c_h * sqrt(S) + rho_h away.
+// lb is the larger of the two.  The minimum of |g|^2 over a set of bins separates per axis: three passes over the dense
+// grid, each looking R bins either way (R bins cover max_dist; "nothing within R" counts as a gap of R bins, still a lower
+// bound).  .x of the intermediate pairs belongs to (a), .y to (b).
+struct HaloBoundCfg {
+    int dimx, dimy, dimz, R;
+    float ch;        // bin edge
+    float rho_h;     // exactness radius of the halo level
+    float eps_bins;  // rounding of a bin coordinate fl(fl(v - o) * 1/c_h), in bins (2^-21 * largest dimension)
+    float sub;       // absolute margin taken off (2 * abs_margin, as the halo radius carries)
+};
+// pass x: whole bins between bin (x, y, z) and the nearest bin of its x-row that holds a point (.x: `occ` bytes) / that has a
+// run (.y: `start`, after its scan); 0: that bin itself or its neighbour; R: none within R + 1
+__global__ void k_halo_gap_x(const uint8_t* __restrict__ occ, const uint32_t* __restrict__ start, HaloBoundCfg c,
+                             uchar2* __restrict__ gx) {
+    const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
+    if (B >= nb) return;
+    const int x = (int)(B % (size_t)c.dimx);
+    int own = c.R + 1, run = c.R + 1;
+    const int lo = max(-c.R - 1, -x), hi = min(c.R + 1, c.dimx - 1 - x);
+    uint32_t prev = start[(ptrdiff_t)B + lo];
+    for (int d = lo; d <= hi; ++d) {
+        const uint32_t next = start[(ptrdiff_t)B + d + 1];
+        if (next != prev) run = min(run, abs(d));
+        if (occ[(ptrdiff_t)B + d]) own = min(own, abs(d));
+        prev = next;
+    }
+    gx[B] = make_uchar2((unsigned char)min(max(own - 1, 0), c.R), (unsigned char)min(max(run - 1, 0), c.R));
+}
+// pass y: min over the bins of the same (x, z) column of gx^2 + gy^2
+__global__ void k_halo_gap_y(const uchar2* __restrict__ gx, HaloBoundCfg c, ushort2* __restrict__ sxy) {
+    const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
+    if (B >= nb) return;
+    const int y = (int)((B / (size_t)c.dimx) % (size_t)c.dimy);
+    int S0 = c.R * c.R, S1 = S0;
+    const int lo = max(-c.R, -y), hi = min(c.R, c.dimy - 1 - y);
+    for (int d = lo; d <= hi; ++d) {
+        const uchar2 v = gx[(ptrdiff_t)B + (ptrdiff_t)d * c.dimx];
+        const int g = max(abs(d) - 1, 0);
+        S0 = min(S0, g * g + (int)v.x * (int)v.x);
+        S1 = min(S1, g * g + (int)v.y * (int)v.y);
+    }
+    sxy[B] = make_ushort2((unsigned short)S0, (unsigned short)S1);
+}
+// pass z + directory: one aligned record per bin, {first halo record, count} -- or, for a bin whose run is empty,
+// {first, 0x80000000 | bits(lb)} (lb >= 0, rounded down by the margins below): the search reads it with the ONE load
+// that used to fetch the run's start.  sxy == null: no bound (lb = 0).
+__global__ void k_halo_dir(const uint32_t* __restrict__ start, const ushort2* __restrict__ sxy, HaloBoundCfg c,
+                           uint2* __restrict__ dir) {
+    const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
+    if (B >= nb) return;
+    const uint32_t s = start[B], cnt = start[B + 1] - s;
+    uint32_t second = cnt;
+    if (cnt == 0) {
+        float lb = 0.f;
+        if (sxy) {
+            const size_t plane = (size_t)c.dimx * c.dimy;
+            const int z = (int)(B / plane);
+            int S0 = c.R * c.R, S1 = S0;
+            const int lo = max(-c.R, -z), hi = min(c.R, c.dimz - 1 - z);
+            for (int d = lo; d <= hi; ++d) {
+                const ushort2 v = sxy[(ptrdiff_t)B + (ptrdiff_t)d * (ptrdiff_t)plane];
+                const int g = max(abs(d) - 1, 0);
+                S0 = min(S0, g * g + (int)v.x);
+                S1 = min(S1, g * g + (int)v.y);
+            }
+            // bins -> metres, downward: 1e-3 relative (rounding of 1/c_h, of the distance the search computes and of its
+            // comparison with rho), the rounding of the two bin coordinates per axis, the absolute margin of the radii
+            const float down = 1.0f - 1e-3f;
+            const float g0 = sqrtf((float)S0) * down - 3.5f * c.eps_bins;
+            const float g1 = sqrtf((float)S1) * down - 3.5f * c.eps_bins;
+            const float lb0 = g0 * c.ch - c.sub;
+            const float lb1 = S1 > 0 ? g1 * c.ch + c.rho_h * down - c.sub : 0.f;
+            lb = fmaxf(fmaxf(lb0, lb1), 0.f);
+        }
+        second = 0x80000000u | __float_as_uint(lb);
+    }
+    dir[B] = make_uint2(s, second);
 }

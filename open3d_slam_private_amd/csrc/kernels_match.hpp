@@ -420,7 +420,7 @@ __device__ __forceinline__ void wave_reduce_step(double (&v)[kSums], int lane) {
     for (int k = 0; k < HALF; ++k) {
         const double keep = up ? v[k + HALF] : v[k];
         const double send = up ? v[k] : v[k + HALF];
-        v[k] = keep + __shfl_xor(send, BIT);
+        v[k] = keep + wave_xor_f64<BIT>(send);
     }
 }
 // (every index is a compile-time constant after unrolling: the array must stay in registers -- an earlier
@@ -432,7 +432,7 @@ __device__ __forceinline__ void wave_reduce32(double (&v)[kSums]) {
     wave_reduce_step<4, 8>(v, lane);
     wave_reduce_step<2, 4>(v, lane);
     wave_reduce_step<1, 2>(v, lane);
-    v[0] = v[0] + __shfl_xor(v[0], 1);
+    v[0] = v[0] + wave_xor_f64<1>(v[0]);
 }
 
 // block partial -> global: partials[blockIdx.x][kSums]  (256 threads = 4 waves)

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "group_dpp.hpp"
+
 namespace o3dreg {
 
 constexpr int kBrickLog2 = 3;                 // 8x8x8 voxel bins per brick
@@ -48,7 +50,14 @@ struct Grid {
     int use_halo;
     float hox, hoy, hoz, hinv_c;
     int hdimx, hdimy, hdimz;
-    const uint32_t* halo_start;  // [hdimx*hdimy*hdimz + 1]
+    // One aligned record per bin: {first halo record, count}; a bin whose run is EMPTY carries, in place of the count,
+    // 0x80000000 | bits(lb): a lower bound (>= 0, rounded down) on the distance from any position bin_coord_f maps to
+    // that bin to any reference point -- the search skips the levels whose radius cannot reach that far.
+    const uint2* halo_dir;       // [hdimx*hdimy*hdimz]
+    // The same bound for a query OUTSIDE the halo grid: its distance to the reference's bounding box [hox.., hmax..] (every
+    // reference point lies inside), less lb_sub; out_bound = 0 switches it off (unbounded max_dist, O3D_NO_EMPTY_BOUND).
+    float hmaxx, hmaxy, hmaxz, lb_sub;
+    int out_bound;
     const float4* halo_pts;
     float rho_h;                 // exactness radius of the halo level
     int level_after_halo;        // first regular level with rho > rho_h
@@ -211,7 +220,8 @@ constexpr int kGroup = 8;   // default group width (lanes per reading point); ke
 #if O3D_SEARCH_STATS
 // [0] level scans [1] bricks of their boxes [2] non-empty rows inside the boxes [3] rows kept by the ball [4] candidates
 // looked at [5] batches (phase 1 + compaction + flattened scan) [6] halo candidates [7] searches
-__device__ unsigned long long g_search_stats[64];   // [8..23] level scans by log2(candidates + 1), [24..39] by log2(rows kept + 1), [40..55] by log2(bricks + 1)
+__device__ unsigned long long g_search_stats[96];   // [8..23] level scans by log2(candidates + 1), [24..39] by log2(rows kept + 1), [40..55] by log2(bricks + 1)
+                                                    // [64..79] searches by the regular level they start at, [80] rejected by the empty-space bound
 #define SEARCH_STAT(i, v) atomicAdd(&g_search_stats[i], (unsigned long long)(v))
 // wave time by section of the search ([56 + i], s_memtime ticks of 10 ns; whoever is executing stamps: divergent groups of a wave
 // take their turns, each turn is charged to the section it runs): 0 halo run, 1 level box + brick directory, 2 row slots
@@ -278,10 +288,8 @@ __device__ __forceinline__ void scan_run(const Grid& g, float3 p, uint32_t s, ui
 // Runner-up of the group: every lane offers the smallest d2 it has seen at a position other than the winner's.
 template <int G>
 __device__ __forceinline__ float group_second(const Best& mine, int winner_pos) {
-    float c = (mine.pos == winner_pos) ? mine.second : fminf(mine.d2, mine.second);
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) c = fminf(c, __shfl_xor(c, m));
-    return c;
+    const float c = (mine.pos == winner_pos) ? mine.second : fminf(mine.d2, mine.second);
+    return group_min_f32<G>(c);
 }
 
 // kTop2: runner-up (distance AND position) and the best of the rest, from the lanes' own {winner, runner-up, third}.
@@ -292,17 +300,14 @@ __device__ __forceinline__ void group_top2(const Best& mine, Best& r, int gbase)
     const bool own = mine.pos == r.pos;
     const float cd = own ? mine.second : mine.d2;
     const int cp = own ? mine.pos2 : mine.pos;
-    float m2 = cd;
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) m2 = fminf(m2, __shfl_xor(m2, m));
+    const float m2 = group_min_f32<G>(cd);
     const unsigned who = (unsigned)((__ballot(cd == m2 && cp >= 0) >> gbase) & ((1ull << G) - 1ull));
     const int p2 = who ? __shfl(cp, gbase + __ffs((int)who) - 1) : -1;
     // ... and its best point that is neither the winner nor the group's runner-up
     float t = mine.third;
     if (mine.pos >= 0 && mine.pos != r.pos && mine.pos != p2) t = fminf(t, mine.d2);
     if (mine.pos2 >= 0 && mine.pos2 != r.pos && mine.pos2 != p2) t = fminf(t, mine.second);
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) t = fminf(t, __shfl_xor(t, m));
+    t = group_min_f32<G>(t);
     r.second = p2 >= 0 ? m2 : INFINITY;
     r.pos2 = p2;
     r.third = t;
@@ -311,17 +316,7 @@ __device__ __forceinline__ void group_top2(const Best& mine, Best& r, int gbase)
 template <int G, bool kTop2 = false>
 __device__ __forceinline__ Best group_min(Best b) {
     const Best mine = b;
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) {
-        const float od2 = __shfl_xor(b.d2, m);
-        const uint32_t oidx = __shfl_xor(b.idx, m);
-        const int opos = __shfl_xor(b.pos, m);
-        if (od2 < b.d2 || (od2 == b.d2 && oidx < b.idx)) {
-            b.d2 = od2;
-            b.idx = oidx;
-            b.pos = opos;
-        }
-    }
+    group_min3<G>(b.d2, b.idx, b.pos);
     if (kTop2)
         group_top2<G>(mine, b, (int)(threadIdx.x & 63) & ~(G - 1));
     else
@@ -380,9 +375,7 @@ __device__ __forceinline__ void consider_pos(const Grid& g, float3 p, const floa
 // Group minimum of (d2, original index) where idx may not have been fetched yet (0xffffffff).
 template <int G, bool kTop2 = false>
 __device__ __forceinline__ Best group_min_lazy(const Grid& g, Best b, int gbase) {
-    float m = b.d2;
-#pragma unroll
-    for (int k = 1; k < G; k <<= 1) m = fminf(m, __shfl_xor(m, k));
+    const float m = group_min_f32<G>(b.d2);
     const bool cand = b.pos >= 0 && b.d2 == m;
     const unsigned mask = (unsigned)((__ballot(cand) >> gbase) & ((1ull << G) - 1ull));
     Best r;
@@ -406,9 +399,7 @@ __device__ __forceinline__ Best group_min_lazy(const Grid& g, Best b, int gbase)
     // tie between lanes: lowest original index wins
     uint32_t idx = 0xffffffffu;
     if (cand) idx = b.idx != 0xffffffffu ? b.idx : __float_as_uint(g.pts[b.pos].w);
-    uint32_t mi = idx;
-#pragma unroll
-    for (int k = 1; k < G; k <<= 1) mi = min(mi, (uint32_t)__shfl_xor((int)mi, k));
+    const uint32_t mi = group_min_u32<G>(idx);
     const unsigned win = (unsigned)((__ballot(cand && idx == mi) >> gbase) & ((1ull << G) - 1ull));
     r.d2 = m;
     r.idx = mi;
@@ -563,13 +554,8 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
         }
         // exclusive prefix of the row counts over the lanes of the group
         const uint32_t cnt = (uint32_t)(__popc(m_lo) + __popc(m_hi));
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int o = 1; o < G; o <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
-            if (sub >= o) incl += v;
-        }
-        const int total = (int)(uint32_t)__shfl((int)incl, gbase + G - 1);
+        const uint32_t incl = group_scan_incl<G>(cnt, sub);
+        const int total = (int)group_bcast_last<G>(incl, sub, gbase);
 #if O3D_SEARCH_STATS
         if (sub == 0) {
             SEARCH_STAT(1, min(G, n_bricks - cb));
@@ -585,9 +571,7 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
                 // started; rows come in brick order, not by distance): same rule as the candidate-bounded box above -- no
                 // point farther than a known candidate can win, ties stay inside -- so the rows still to come are cut to
                 // the ball of the current best.  The covered radius shrinks with it.
-                float gb = best.d2;
-#pragma unroll
-                for (int o = G / 2; o >= 1; o >>= 1) gb = fminf(gb, __shfl_xor(gb, o));
+                const float gb = group_min_f32<G>(best.d2);
                 if (gb < INFINITY) {
                     const float dc = __builtin_amdgcn_sqrtf(gb) + slack;
                     const float rs = dc * 1.001f + (g.rho_box[l] - g.rho[l]);
@@ -663,13 +647,8 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
             for (int u = 0; u < S; ++u) {
                 const uint32_t c2 = e[u] - s[u];
                 if (u > 0 && __ballot(c2 != 0u) == 0ull) continue;
-                uint32_t in2 = c2;
-#pragma unroll
-                for (int o = 1; o < G; o <<= 1) {
-                    const uint32_t v = (uint32_t)__shfl_up((int)in2, o);
-                    if (sub >= o) in2 += v;
-                }
-                const uint32_t tot_u = (uint32_t)__shfl((int)in2, gbase + G - 1);
+                const uint32_t in2 = group_scan_incl<G>(c2, sub);
+                const uint32_t tot_u = group_bcast_last<G>(in2, sub, gbase);
                 const unsigned m = (unsigned)(__ballot(c2 != 0) >> gbase) & gmask;
                 if (c2 != 0) {
                     const uint32_t my = run_seg + (uint32_t)__popc(m & ((1u << sub) - 1u));
@@ -770,9 +749,22 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
         const bool inside = fx >= 0.f && fy >= 0.f && fz >= 0.f && fx < (float)g.hdimx && fy < (float)g.hdimy &&
                             fz < (float)g.hdimz;
         l = 0;
+        float lbd = 0.f;   // no reference point lies within lbd of the query (empty-space bound; group-uniform)
+        if (!inside && g.out_bound) {
+            const float ox = fmaxf(fmaxf(g.hox - p.x, p.x - g.hmaxx), 0.f), oy = fmaxf(fmaxf(g.hoy - p.y, p.y - g.hmaxy), 0.f),
+                        oz = fmaxf(fmaxf(g.hoz - p.z, p.z - g.hmaxz), 0.f);
+            float a = ox * ox;
+            float b = oy * oy;
+            float s2 = a + b;
+            a = oz * oz;
+            s2 = s2 + a;
+            lbd = __builtin_amdgcn_sqrtf(s2) * (1.0f - 1e-3f) - g.lb_sub;
+        }
         if (inside) {
             const size_t B = ((size_t)(int)fz * g.hdimy + (int)fy) * g.hdimx + (int)fx;
-            const uint32_t s = g.halo_start[B], e = g.halo_start[B + 1];
+            const uint2 hd = g.halo_dir[B];
+            const bool empty = (int)hd.y < 0;   // no run: hd.y carries the empty-space bound
+            const uint32_t s = hd.x, e = empty ? hd.x : hd.x + hd.y;
 #if O3D_SEARCH_STATS
             if (sub == 0) SEARCH_STAT(6, e - s);
 #endif
@@ -803,7 +795,22 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
                 while (l + 1 < g.n_levels && g.rho[l] * g.rho[l] < best.d2) ++l;
             } else {
                 l = max(g.level_after_halo, after_halo);
+                if (empty) lbd = __uint_as_float(hd.y & 0x7fffffffu);   // the directory's bound for this bin
             }
+        }
+        if (lbd > 0.f) {
+            // A level with rho < lbd finds nothing it could terminate on, so the climb starts at the first radius that
+            // reaches (any starting level is exact); a bound beyond max_dist leaves the point unmatched, with what the full
+            // climb would have written (no candidate, every radius up to max_dist covered, the last level).
+            if (lbd > g.rho[g.n_levels - 1]) {
+#if O3D_SEARCH_STATS
+                if (sub == 0) SEARCH_STAT(80, 1);
+#endif
+                *level_out = g.n_levels - 1;
+                if (cov2_out) *cov2_out = g.max_d2;
+                return true;
+            }
+            while (l + 1 < g.n_levels && g.rho[l] < lbd) ++l;
         }
     }
     l = max(max(l, after_halo), 0);   // no halo level (or the query lies outside its grid): the hinted level
@@ -814,6 +821,9 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
 template <int G, bool kPrune, bool kTop2>
 __device__ __forceinline__ Best nearest_levels(const Grid& g, float3 p, int sub, int gbase, int l, Best best, float cov, uint32_t* seg,
                                                float slack, int* level_out, float* cov2_out) {
+#if O3D_SEARCH_STATS
+    if (sub == 0) SEARCH_STAT(64 + min(l, 15), 1);
+#endif
     for (; l < g.n_levels; ++l) {
         cov = fmaxf(cov, scan_level_rows<G, kPrune, kTop2>(g, p, sub, gbase, l, seg, best, slack));
         best = group_min<G, kTop2>(best);

@@ -13,7 +13,7 @@ NAMES = ["level scans", "bricks in boxes", "non-empty rows in boxes", "rows kept
 
 
 def stats(lib, reset=True):
-    out = (ctypes.c_ulonglong * 64)()
+    out = (ctypes.c_ulonglong * 96)()   # (builds before the empty-space bound fill 64)
     assert lib.o3d_debug_search_stats(out, 1 if reset else 0) == 0
     return np.array(list(out), dtype=np.float64)
 
@@ -26,7 +26,7 @@ if __name__ == "__main__":
     sc = synth.make_scene(n_src, n_tgt, seed=seed)
     p = capi.shipped_params()
     p.disable_fused = 1
-    prev = np.zeros(64)
+    prev = np.zeros(96)
     for k in range(1, 4):
         p.fixed_iters = k
         reg = capi.Registration(p)
@@ -41,6 +41,8 @@ if __name__ == "__main__":
         prev = cur
         n = max(d[7], 1.0)
         print(f"iteration {k - 1}: " + ", ".join(f"{NAMES[i]} {d[i] / n:.1f}" for i in range(7)) + f" per search ({int(d[7])} searches)", flush=True)
+        print(f"    failing level scans (no candidate) {d[8] / n:.2f} per search; rejected by the empty-space bound {int(d[80])}; "
+              "searches by the regular level they start at: " + " ".join(f"{int(v)}" for v in d[64:80][:int(np.max(np.nonzero(d[64:80])[0], initial=0)) + 1]))
         for nm, o in (("candidates", 8), ("rows kept", 24), ("bricks", 40)):
             hh = d[o:o + 16]
             print(f"    level scans by {nm} (0, 1, 2-3, 4-7, ...): " + " ".join(f"{int(v)}" for v in hh[:int(np.max(np.nonzero(hh)[0], initial=0)) + 1]))
