@@ -56,14 +56,25 @@ public:
     void setShippedChain() { reg_shipped_params(&params_); has_chain_ = false; reset(); }
     // direct access to the string-free parameter block (call before the first initReference)
     reg_params& parameters() { reset(); return params_; }
-    // libpointmatcher chain extension (reg_set_pm_chain: k-NN matching, RobustOutlierFilter, PointToPoint).  The chain
-    // is kept and re-applied whenever parameters() re-creates the handle (the robust state then starts afresh, as with a
-    // new filter); setting it resets the robust state.
+    // libpointmatcher chain extension (reg_set_pm_chain: k-NN matching, RobustOutlierFilter, PointToPoint, and the
+    // MinDist / MedianDist / VarTrimmedDist outlier filters: use_min_dist_filter, use_median_dist, use_var_trimmed and
+    // their parameters; start from reg_default_pm_chain).  The chain is kept and re-applied whenever parameters()
+    // re-creates the handle (the robust state then starts afresh, as with a new filter); setting it resets the robust
+    // state.
     void setPmChain(const reg_pm_chain& c) {
         chain_ = c;
         has_chain_ = true;
         if (h_) check(reg_set_pm_chain(h_, &chain_));
         else ensure();
+    }
+
+    // VarTrimmedDistOutlierFilter's "Optimized ratio" of the last iteration, the rank it came from and n = N knn
+    struct VarTrim { float ratio; int64_t index; int64_t n_total; };
+    VarTrim varTrim() {
+        ensure();
+        VarTrim v{};
+        check(reg_get_var_trim(h_, &v.ratio, &v.index, &v.n_total));
+        return v;
     }
 
     bool hasMap() const { return matcherIsInitialized_; }

@@ -365,8 +365,9 @@ REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T
      KDTreeMatcher.knn (MatchersImpl.cpp)          1..16 exact nearest reference points within reg_params.max_dist
                                                     (+inf allowed), ascending (d2, index); missing slots: id -1, d2 +inf
      filters (OutlierFiltersImpl.cpp)              product of the weights of TrimmedDist (quantile over ALL N*knn
-                                                    finite d2, Matches.cpp:60-87), SurfaceNormal, MaxDist (reg_params)
-                                                    and RobustOutlierFilter (:397-598) when use_robust != 0
+                                                    finite d2, Matches.cpp:60-87), SurfaceNormal, MaxDist (reg_params),
+                                                    RobustOutlierFilter (:397-598) when use_robust != 0, and MinDist /
+                                                    MedianDist / VarTrimmedDist (below)
      minimizer                                     REG_PM_POINT_TO_PLANE: A = sum w F F^T, b = -sum w F r (ICP.cpp:1527-1565);
                                                     REG_PM_POINT_TO_POINT: weighted Kabsch (ErrorMinimizers/PointToPoint.cpp:62-100)
                                                     in fp64, composed T_iter <- dT T_iter in the centred frames
@@ -379,7 +380,30 @@ REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T
    (N knn) (pointUsedRatio, ErrorMinimizer.cpp:139), inlier_rmse unweighted over the inliers, error = sum w r^2
    (point-to-plane) / sum w |p - q|^2 (point-to-point); point-to-point: H_last = b_last = 0 and rank_last is the rank
    of the 3x3 cross-covariance.  reg_get_correspondences returns REG_UNSUPPORTED with knn > 1, reg_linearize always
-   with a chain; the distributed entry points return REG_UNSUPPORTED while a chain is set. */
+   with a chain; the distributed entry points return REG_UNSUPPORTED while a chain is set.
+
+   MinDist, MedianDist and VarTrimmedDist outlier filters (OutlierFiltersImpl.cpp:86-220).  All three act on
+   Matches.dists, the N x knn squared distances (+inf = no match), and multiply into the chain's weight like the others;
+   a chain that sets one of them is not the default chain and runs the generic chain iteration.
+     MinDist        w = [d2 >= minDist^2], minDist^2 an fp32 product; minDist in [1e-7, inf).  +inf passes, as in the
+                    reference (the pair has no id and its weight is zero anyway).
+     MedianDist     limit = factor * getDistsQuantile(0.5) in fp32, the quantile over the finite distances at index
+                    (size_t)(n_finite * 0.5f) (the float-index form, as berg); w = [d2 <= limit]; factor in [1e-7, inf);
+                    no finite distance: REG_NO_CORRESPONDENCES.
+     VarTrimmedDist (Phillips 2007) n = N knn counts EVERY entry; v = ascending sort of the entries that are finite and
+                    > 0, m = |v|; minEl = floor(minRatio n), maxEl = floor(maxRatio n) as fp32 products;
+                    FRMS(j) = S(j) / (j + 1) / ((j + 1) / n)^(2 lambda) with S(j) = v[0] + ... + v[j]; k = the first j that
+                    minimises FRMS; optRatio = (float)k / (float)n; limit = getDistsQuantile(optRatio) over the finite
+                    distances, zeros included; w = [d2 <= limit].  Ratios in [1e-7, 1], minRatio >= maxRatio is
+                    REG_BAD_ARGUMENT; m = 0 is REG_NO_CORRESPONDENCES.
+                    Two documented deviations from the reference: (1) S and FRMS are fp64 with a fixed summation order
+                    (deterministic from run to run), where the reference keeps an fp32 sequential running sum and
+                    evaluates FRMS in fp32; near a flat minimum the two may pick ranks a few places apart.  (2) When
+                    m < maxEl (entries that are +inf or 0) the reference maps n elements over a buffer that holds m and
+                    reads uninitialised memory; here the candidates are j in [minEl, min(maxEl, m)), and k = m - 1
+                    when that range is empty.
+   Any of the three with use_xicp is REG_UNSUPPORTED.  struct_size: sizeof(reg_pm_chain), or REG_PM_CHAIN_SIZE_V1 (the
+   struct up to reserved[2], as callers built before these fields pass it: the three filters are then off). */
 enum { REG_PM_POINT_TO_PLANE = 0, REG_PM_POINT_TO_POINT = 1 };
 enum {   /* robustFct (OutlierFiltersImpl.cpp:385-394) */
     REG_ROBUST_CAUCHY = 0, REG_ROBUST_WELSCH = 1, REG_ROBUST_SC = 2, REG_ROBUST_GM = 3, REG_ROBUST_TUKEY = 4,
@@ -399,9 +423,20 @@ typedef struct {
     int32_t distance_type;       /* REG_DIST_POINT2POINT | REG_DIST_POINT2PLANE */
     float   approximation;       /* "approximation" (INFINITY = off); w = 0 where e^2 >= (float)(approximation^2 in double) */
     int32_t reserved[2];
+    /* -- fields after REG_PM_CHAIN_SIZE_V1 -- */
+    int32_t use_min_dist_filter; /* MinDistOutlierFilter */
+    float   outlier_min_dist;    /* "minDist" (1) */
+    int32_t use_median_dist;     /* MedianDistOutlierFilter */
+    float   median_factor;       /* "factor" (3) */
+    int32_t use_var_trimmed;     /* VarTrimmedDistOutlierFilter */
+    float   var_min_ratio;       /* "minRatio" (0.05) */
+    float   var_max_ratio;       /* "maxRatio" (0.99) */
+    float   var_lambda;          /* "lambda" (2.35) */
 } reg_pm_chain;
+#define REG_PM_CHAIN_SIZE_V1 48
 
-/* knn 1, point-to-plane, robust off: the loop as without a chain (robust defaults as OutlierFiltersImpl.h:230-244). */
+/* knn 1, point-to-plane, robust / MinDist / MedianDist / VarTrimmedDist off: the loop as without a chain (parameter
+   defaults as OutlierFiltersImpl.h). */
 REG_API void       reg_default_pm_chain(reg_pm_chain* c);
 /* Pure check of a chain against the parameters it would run with (no device). */
 REG_API reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c);
@@ -409,6 +444,16 @@ REG_API reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c
 REG_API reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c);
 /* Robust filter state as the next registration starts with it: scale and the filter's iteration counter (1 = fresh). */
 REG_API reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32_t* iteration);
+/* VarTrimmedDist of the last iteration (taken at T_iter_prev, like the correspondences): the optimised ratio (the
+   reference logs it as "Optimized ratio"), the rank k it came from and n = N knn.  REG_NOT_CONFIGURED without a chain
+   registration with use_var_trimmed on the current reading.  Any pointer may be NULL. */
+REG_API reg_status reg_get_var_trim(const reg_handle* h, float* ratio, int64_t* index, int64_t* n_total);
+/* The VarTrimmedDist contract above on the host (no device): d2[n] may hold +inf and zeros.  *index = k, *ratio =
+   optRatio, *limit = the quantile the weights compare against.  The device evaluates the same objective (fp64) with
+   another, fixed, summation order.  REG_BAD_ARGUMENT for ratios outside [1e-7, 1] or minRatio >= maxRatio,
+   REG_NO_CORRESPONDENCES when no entry is finite and > 0.  Any output pointer may be NULL. */
+REG_API reg_status reg_host_var_trim(const float* d2, int64_t n, float minRatio, float maxRatio, float lambda,
+                                     int64_t* index, float* ratio, float* limit);
 /* Correspondences of the last iteration (taken at T_iter_prev), reading input order, N x knn entries each, ascending
    (d2, id); ids -1 / d2 +inf where fewer than knn reference points lie within max_dist.  knn must equal the chain's
    knn.  Any pointer may be NULL. */

@@ -162,13 +162,19 @@ class OctreeOut(C.Structure):
 
 
 class PmChain(C.Structure):
-    """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint)."""
+    """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint, and the
+    MinDist / MedianDist / VarTrimmedDist outlier filters appended after `reserved`)."""
     _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("minimizer", C.c_int32), ("use_robust", C.c_int32),
                 ("robust_fct", C.c_int32), ("tuning", C.c_float), ("scale_estimator", C.c_int32),
                 ("nb_iter_for_scale", C.c_int32), ("distance_type", C.c_int32), ("approximation", C.c_float),
-                ("reserved", C.c_int32 * 2)]
+                ("reserved", C.c_int32 * 2),
+                ("use_min_dist_filter", C.c_int32), ("outlier_min_dist", C.c_float),
+                ("use_median_dist", C.c_int32), ("median_factor", C.c_float),
+                ("use_var_trimmed", C.c_int32), ("var_min_ratio", C.c_float), ("var_max_ratio", C.c_float),
+                ("var_lambda", C.c_float)]
 
 
+PM_CHAIN_SIZE_V1 = 48   # REG_PM_CHAIN_SIZE_V1: the struct up to `reserved`, still accepted (the three new filters off)
 PM_POINT_TO_PLANE, PM_POINT_TO_POINT = 0, 1
 ROBUST_FCTS = {"cauchy": 0, "welsch": 1, "sc": 2, "gm": 3, "tukey": 4, "huber": 5, "L1": 6, "student": 7}
 SCALE_ESTIMATORS = {"none": 0, "mad": 1, "berg": 2, "std": 3}
@@ -189,6 +195,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
            "reg_default_pm_chain", "reg_check_pm_chain", "reg_set_pm_chain", "reg_get_robust_state",
            "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update",
+           "reg_get_var_trim", "reg_host_var_trim",
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks"]
 
@@ -297,6 +304,9 @@ def load_library():
     lib.reg_get_correspondences_k.argtypes = [vp, C.c_int32, vp, vp, vp]
     lib.reg_host_robust_weights.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, vp, i64, vp]
     lib.reg_host_pm_p2p_update.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.reg_get_var_trim.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.reg_host_var_trim.argtypes = [vp, i64, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float)]
     lib.reg_default_ssn_params.argtypes = [C.POINTER(SsnParams)]
     lib.reg_default_ssn_params.restype = None
     lib.reg_sampling_surface_normal.argtypes = [vp, vp, i64, i64, C.c_int, C.POINTER(SsnParams), C.POINTER(SsnOut),
@@ -405,7 +415,8 @@ def host_octree_random_picks(sizes) -> np.ndarray:
 
 
 def default_pm_chain() -> PmChain:
-    """knn 1, point-to-plane, robust off (the plain loop); robust fields at the reference's defaults."""
+    """knn 1, point-to-plane, robust / MinDist / MedianDist / VarTrimmedDist off (the plain loop); their parameters at
+    the reference's defaults."""
     c = PmChain()
     load_library().reg_default_pm_chain(C.byref(c))
     return c
@@ -426,6 +437,18 @@ def host_robust_weights(fct, tuning, scale, d2, approximation=math.inf):
     if st != 0:
         raise RegError(st, "reg_host_robust_weights")
     return w
+
+
+def host_var_trim(d2, min_ratio=0.05, max_ratio=0.99, lam=2.35):
+    """reg_host_var_trim: (k, optRatio, limit) of VarTrimmedDistOutlierFilter for the squared distances d2 (any shape;
+    +inf = no match), the contract of include/o3dslam_reg.h evaluated on the host."""
+    d = np.ascontiguousarray(d2, np.float32).reshape(-1)
+    k, ratio, limit = C.c_int64(), C.c_float(), C.c_float()
+    st = load_library().reg_host_var_trim(_ptr(d), d.size, float(min_ratio), float(max_ratio), float(lam), C.byref(k),
+                                          C.byref(ratio), C.byref(limit))
+    if st != 0:
+        raise RegError(st, "reg_host_var_trim")
+    return int(k.value), float(ratio.value), float(limit.value)
 
 
 def host_pm_p2p_update(sums):
@@ -847,6 +870,12 @@ class Registration:
         it = C.c_int32()
         self._check(self._lib.reg_get_robust_state(self._h, C.byref(sc), C.byref(it)))
         return float(sc.value), int(it.value)
+
+    def get_var_trim(self):
+        """(optRatio, k, n) of the chain's VarTrimmedDistOutlierFilter in the last iteration (at T_iter_prev)."""
+        ratio, k, n = C.c_float(), C.c_int64(), C.c_int64()
+        self._check(self._lib.reg_get_var_trim(self._h, C.byref(ratio), C.byref(k), C.byref(n)))
+        return float(ratio.value), int(k.value), int(n.value)
 
     def target_info(self) -> TargetInfo:
         info = TargetInfo()

@@ -643,7 +643,22 @@ static int sequence_limit(const reg_params& p) {
 // ---- libpointmatcher chain extension (reg_set_pm_chain; kernels_pmchain.hpp) --------------------------------------
 
 static bool pm_chain_is_default(const reg_pm_chain* c) {
-    return c->knn == 1 && c->minimizer == REG_PM_POINT_TO_PLANE && !c->use_robust;
+    return c->knn == 1 && c->minimizer == REG_PM_POINT_TO_PLANE && !c->use_robust && !c->use_min_dist_filter &&
+           !c->use_median_dist && !c->use_var_trimmed;
+}
+
+// The caller's chain in today's layout: a struct of REG_PM_CHAIN_SIZE_V1 bytes (built before MinDist / MedianDist /
+// VarTrimmedDist) is completed with those filters off
+static bool pm_chain_read(const reg_pm_chain* c, reg_pm_chain* out) {
+    if (c->struct_size == (int32_t)sizeof(reg_pm_chain)) {
+        *out = *c;
+        return true;
+    }
+    if (c->struct_size != REG_PM_CHAIN_SIZE_V1) return false;
+    reg_default_pm_chain(out);
+    std::memcpy(out, c, REG_PM_CHAIN_SIZE_V1);
+    out->struct_size = (int32_t)sizeof(reg_pm_chain);
+    return true;
 }
 
 static PmCfg make_pm_cfg(const reg_handle* h) {
@@ -672,6 +687,14 @@ static PmCfg make_pm_cfg(const reg_handle* h) {
     f.cos_max_angle = std::cos(h->prm.max_normal_angle);
     const float md = h->prm.outlier_max_dist;
     f.outlier_max_d2 = md * md;
+    f.use_mindist = c.use_min_dist_filter;
+    f.use_median = c.use_median_dist;
+    f.use_var = c.use_var_trimmed;
+    f.outlier_min_d2 = c.outlier_min_dist * c.outlier_min_dist;
+    f.median_factor = c.median_factor;
+    f.var_min_ratio = c.var_min_ratio;
+    f.var_max_ratio = c.var_max_ratio;
+    f.var_lambda = c.var_lambda;
     return f;
 }
 
@@ -687,6 +710,32 @@ static void enqueue_pm_select(reg_handle* h, const float* keys, int64_t nk, floa
     k_pm_select_level1<<<hb, 256, 0, h->stream>>>(keys, nk, h->shift0, ratio, median, hist, hist + 2048, st, it);
     k_select_level<<<hb, 256, 0, h->stream>>>(keys, nk, 2, h->shift0, ratio, hist + 2048, hist + 4096, hist, st, it);
     k_pm_select_finish<<<1, 256, 0, h->stream>>>(hist, st, h->shift0, h->pm_state.as<PmState>(), slot, it);
+}
+
+// Tiles of the VarTrimmedDist kernels over nk keys, and the layout of pm_var: five 8-byte records per tile, VarState
+static inline int pm_var_tiles(int64_t nk) { return (int)((nk + kVarTile - 1) / kVarTile); }
+static inline size_t pm_var_bytes(int64_t nk) { return (size_t)pm_var_tiles(nk) * 40 + sizeof(VarState); }
+
+// VarTrimmedDist limit of this iteration -> PmState (kernels_pmoutliers.hpp).  The sort runs whatever the loop state is
+// and only writes scratch; the kernels after it return at once when the loop is done.
+static reg_status enqueue_pm_var_trim(reg_handle* h, const PmCfg& cfg, const float* kd2, int64_t nk) {
+    const IterState* it = h->i_iter.as<IterState>();
+    const int nb = pm_var_tiles(nk);
+    uint32_t* sorted = h->pm_sorted.as<uint32_t>();
+    double* bsum = h->pm_var.as<double>();
+    double* boff = bsum + nb;
+    double* bval = boff + nb;
+    long long* bidx = reinterpret_cast<long long*>(bval + nb);
+    uint2* bcnt = reinterpret_cast<uint2*>(bidx + nb);
+    VarState* vs = reinterpret_cast<VarState*>(bcnt + nb);
+    size_t bytes = h->pm_sort_bytes;
+    HIPCHK(h, rocprim::radix_sort_keys(h->pm_sort_tmp.p, bytes, reinterpret_cast<const uint32_t*>(kd2), sorted, (size_t)nk, 0, 32,
+                                       h->stream));
+    k_pm_var_block_sums<<<nb, 256, 0, h->stream>>>(sorted, nk, bsum, bcnt, it);
+    k_pm_var_scan_blocks<<<1, 256, 0, h->stream>>>(bsum, bcnt, nb, boff, vs, nk, cfg.var_min_ratio, cfg.var_max_ratio, it);
+    k_pm_var_objective<<<nb, 256, 0, h->stream>>>(sorted, nk, boff, vs, nk, 2.0 * (double)cfg.var_lambda, bval, bidx, it);
+    k_pm_var_finish<<<1, 256, 0, h->stream>>>(sorted, bval, bidx, nb, vs, nk, h->pm_state.as<PmState>(), it);
+    return REG_OK;
 }
 
 // One generic iteration of the chain; nothing waits on the host
@@ -708,6 +757,11 @@ static reg_status enqueue_pm_iteration(reg_handle* h) {
     else
         k_match_knn<16><<<blocks, 256, 0, h->stream>>>(h->grid, src, n, c.knn, it, kpos, kd2);
     if (cfg.use_trim) enqueue_pm_select(h, kd2, nk, h->prm.trim_ratio, 2);
+    if (cfg.use_median) enqueue_pm_select(h, kd2, nk, 0.5f, 3);   // getDistsQuantile(0.5): the float index
+    if (cfg.use_var) {
+        const reg_status vs = enqueue_pm_var_trim(h, cfg, kd2, nk);
+        if (vs != REG_OK) return vs;
+    }
     if (c.use_robust) {
         // MAD: median(d2) at the integer index size / 2; berg: getDistsQuantile(0.5), the float index
         if (c.scale_estimator == REG_SCALE_MAD || c.scale_estimator == REG_SCALE_BERG)
@@ -731,7 +785,7 @@ static reg_status enqueue_pm_iteration(reg_handle* h) {
     ++h->seq;
     k_pm_update<<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
                                           h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
-                                          cfg.use_trim);
+                                          cfg.use_trim, cfg.use_median);
     HIPCHK(h, hipGetLastError());
     h->have_match = true;
     h->pm_have_match = true;
@@ -758,6 +812,15 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     if (!h->pm_hist.p) {
         HIPCHK(h, h->pm_hist.reserve(3 * 2048 * 4));
         HIPCHK(h, hipMemsetAsync(h->pm_hist.p, 0, 3 * 2048 * 4, h->stream));
+    }
+    if (h->pm.use_var_trimmed) {
+        HIPCHK(h, h->pm_sorted.reserve((size_t)nk * 4));
+        HIPCHK(h, h->pm_var.reserve(pm_var_bytes(nk)));
+        size_t need = 0;
+        HIPCHK(h, rocprim::radix_sort_keys(nullptr, need, h->pm_d2.as<uint32_t>(), h->pm_sorted.as<uint32_t>(), (size_t)nk, 0, 32,
+                                           h->stream));
+        HIPCHK(h, h->pm_sort_tmp.reserve(std::max<size_t>(need, 16)));
+        h->pm_sort_bytes = need;
     }
     float T_start[16];
     m4_identity(T_start);
@@ -1297,11 +1360,24 @@ void reg_default_pm_chain(reg_pm_chain* c) {
     c->nb_iter_for_scale = 0;
     c->distance_type = REG_DIST_POINT2POINT;
     c->approximation = std::numeric_limits<float>::infinity();
+    // MinDist / MedianDist / VarTrimmedDist defaults (OutlierFiltersImpl.h:96-101,115-120,153-160)
+    c->use_min_dist_filter = 0;
+    c->outlier_min_dist = 1.0f;
+    c->use_median_dist = 0;
+    c->median_factor = 3.0f;
+    c->use_var_trimmed = 0;
+    c->var_min_ratio = 0.05f;
+    c->var_max_ratio = 0.99f;
+    c->var_lambda = 2.35f;
 }
 
-reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c) {
-    if (!p || !c) return REG_BAD_ARGUMENT;
-    if (c->struct_size != (int32_t)sizeof(reg_pm_chain)) return REG_BAD_ARGUMENT;
+static bool pm_ratio_ok(float r) { return r >= 1e-7f && r <= 1.f; }
+
+reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c_in) {
+    if (!p || !c_in) return REG_BAD_ARGUMENT;
+    reg_pm_chain full;
+    if (!pm_chain_read(c_in, &full)) return REG_BAD_ARGUMENT;
+    const reg_pm_chain* c = &full;
     if (p->cost != REG_COST_P2PL) return REG_BAD_ARGUMENT;
     if (c->knn < 1 || c->knn > kPmMaxKnn) return REG_BAD_ARGUMENT;
     if (c->minimizer != REG_PM_POINT_TO_PLANE && c->minimizer != REG_PM_POINT_TO_POINT) return REG_BAD_ARGUMENT;
@@ -1314,6 +1390,14 @@ reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c) {
         if (c->distance_type != REG_DIST_POINT2POINT && c->distance_type != REG_DIST_POINT2PLANE) return REG_BAD_ARGUMENT;
         if (!(c->approximation >= 0.f)) return REG_BAD_ARGUMENT;                  // [0, inf]
     }
+    // parameter ranges of the reference ("minDist" / "factor" [1e-7, inf), ratios [1e-7, 1]); NaN fails every test
+    if (c->use_min_dist_filter && !(c->outlier_min_dist >= 1e-7f && c->outlier_min_dist < INFINITY)) return REG_BAD_ARGUMENT;
+    if (c->use_median_dist && !(c->median_factor >= 1e-7f && c->median_factor < INFINITY)) return REG_BAD_ARGUMENT;
+    if (c->use_var_trimmed) {
+        if (!pm_ratio_ok(c->var_min_ratio) || !pm_ratio_ok(c->var_max_ratio) || !std::isfinite(c->var_lambda))
+            return REG_BAD_ARGUMENT;
+        if (c->var_min_ratio >= c->var_max_ratio) return REG_BAD_ARGUMENT;   // the filter's constructor throws
+    }
     if (p->use_xicp && !pm_chain_is_default(c)) return REG_UNSUPPORTED;
     return REG_OK;
 }
@@ -1325,7 +1409,7 @@ reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c) {
     if (c) {
         const reg_status s = reg_check_pm_chain(&h->prm, c);
         if (s != REG_OK) return s;
-        nc = *c;
+        (void)pm_chain_read(c, &nc);
     } else {
         reg_default_pm_chain(&nc);
     }
@@ -1358,6 +1442,57 @@ reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32_t* iter
     }
     if (scale) *scale = ps.scale;
     if (iteration) *iteration = ps.iteration;
+    return REG_OK;
+}
+
+reg_status reg_get_var_trim(const reg_handle* h, float* ratio, int64_t* index, int64_t* n_total) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->pm_on || !h->pm.use_var_trimmed || !h->pm_have_match || !h->pm_state.p) return REG_NOT_CONFIGURED;
+    PmState ps;
+    if (hipSetDevice(h->prm.device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess ||
+        hipMemcpy(&ps, h->pm_state.p, sizeof(ps), hipMemcpyDeviceToHost) != hipSuccess)
+        return REG_DEVICE_ERROR;
+    if (!ps.var_valid) return REG_NOT_CONFIGURED;
+    if (ratio) *ratio = ps.var_ratio;
+    if (index) *index = (int64_t)ps.var_k;
+    if (n_total) *n_total = (int64_t)ps.var_n;
+    return REG_OK;
+}
+
+reg_status reg_host_var_trim(const float* d2, int64_t n, float minRatio, float maxRatio, float lambda, int64_t* index,
+                             float* ratio, float* limit) {
+    if (n < 0 || (n > 0 && !d2)) return REG_BAD_ARGUMENT;
+    if (!pm_ratio_ok(minRatio) || !pm_ratio_ok(maxRatio) || minRatio >= maxRatio || !std::isfinite(lambda)) return REG_BAD_ARGUMENT;
+    std::vector<float> fin;   // the finite distances, zeros included (getDistsQuantile)
+    fin.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        if (d2[i] != INFINITY) fin.push_back(d2[i]);
+    std::sort(fin.begin(), fin.end());
+    const int64_t nz = std::upper_bound(fin.begin(), fin.end(), 0.f) - fin.begin();
+    const int64_t m = (int64_t)fin.size() - nz;   // v = fin[nz ...]
+    if (m <= 0) return REG_NO_CORRESPONDENCES;
+    int64_t lo, hi;
+    pm_var_range(n, m, minRatio, maxRatio, &lo, &hi);
+    const double two_lambda = 2.0 * (double)lambda;
+    int64_t k = m - 1;
+    if (lo < hi) {
+        double S = 0.0, best = 0.0;
+        k = -1;
+        for (int64_t j = 0; j < hi; ++j) {
+            S += (double)fin[(size_t)(nz + j)];
+            if (j < lo) continue;
+            const double f = pm_var_frms(S, j, n, two_lambda);
+            if (k < 0 || f < best) {
+                best = f;
+                k = j;
+            }
+        }
+    }
+    const float r = (float)k / (float)n;
+    if (index) *index = k;
+    if (ratio) *ratio = r;
+    if (limit) *limit = fin[pm_quantile_rank((uint32_t)fin.size(), r)];
     return REG_OK;
 }
 

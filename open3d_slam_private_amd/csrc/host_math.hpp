@@ -731,4 +731,33 @@ O3D_HD inline float pm_robust_weight(int fct, float k, float scale, float sq_app
     return w;
 }
 
+// ---------------------------------------------------------------------------------------------
+// VarTrimmedDistOutlierFilter (include/o3dslam_reg.h): the objective and the candidate range, shared by
+// the device kernels (kernels_pmoutliers.hpp) and reg_host_var_trim.
+//   FRMS(j) = S(j) / (j + 1) / ((j + 1) / n)^(2 lambda) in fp64, n = every entry of the distance matrix
+//   candidates j in [minEl, min(maxEl, m)), minEl = floor(minRatio * n), maxEl = floor(maxRatio * n) as fp32 products
+// ---------------------------------------------------------------------------------------------
+O3D_HD inline double pm_var_frms(double S, int64_t j, int64_t n, double two_lambda) {
+    const double id = (double)(j + 1);
+    const double ratio = id / (double)n;
+    return S / id / pow(ratio, two_lambda);
+}
+
+O3D_HD inline void pm_var_range(int64_t n, int64_t m, float min_ratio, float max_ratio, int64_t* lo, int64_t* hi) {
+    const float a = min_ratio * (float)n, b = max_ratio * (float)n;
+    const int64_t min_el = (int64_t)floorf(a), max_el = (int64_t)floorf(b);
+    *lo = min_el;
+    *hi = max_el < m ? max_el : m;
+}
+
+// Matches::getDistsQuantile's index (Matches.cpp:82-86): size * quantile evaluated in float, truncated; 1 -> the maximum
+// (the host-and-device form of trim_rank, kernels_match.hpp)
+O3D_HD inline uint32_t pm_quantile_rank(uint32_t total, float ratio) {
+    if (total == 0) return 0;
+    if (ratio == 1.0f) return total - 1;
+    const float posf = (float)total * ratio;
+    const uint32_t r = (uint32_t)posf;
+    return r >= total ? total - 1 : r;
+}
+
 }  // namespace o3dreg

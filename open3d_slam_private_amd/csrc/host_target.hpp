@@ -189,6 +189,10 @@ struct reg_handle {
     // entry points -- reg_information_matrix, ... -- set have_match but never fill these)
     bool pm_have_match = false;
     DevBuf pm_pos, pm_d2, pm_w, pm_keys, pm_hist, pm_sel, pm_state, pm_partials;
+    // VarTrimmedDist (kernels_pmoutliers.hpp): the sorted distances, rocPRIM's temporary storage, the per-tile records
+    // {sum, offset, best value, best index, counts} + VarState; sized by register_pm, never inside the loop
+    DevBuf pm_sorted, pm_sort_tmp, pm_var;
+    size_t pm_sort_bytes = 0;
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
     DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;
@@ -339,6 +343,7 @@ void reg_destroy(reg_handle* h) {
                       &h->s_misc, &h->i_pos, &h->i_d2, &h->i_w, &h->i_hist, &h->i_state, &h->i_partials, &h->i_sums,
                       &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->t_halo_dir, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
                       &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials,
+                      &h->pm_sorted, &h->pm_sort_tmp, &h->pm_var,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
                       &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
                       &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out,

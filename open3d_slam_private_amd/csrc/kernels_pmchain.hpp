@@ -7,6 +7,7 @@
 //   [k_hist_level0, k_pm_select_level1, k_select_level (level 2), k_pm_select_finish]  per exact select: TrimmedDist quantile, median(d2),
 //                                               median(|d2 - median|) (k_pm_absdev in between) -- no host round trip
 //   k_pm_scale                                  RobustOutlierFilter scale / iteration (state persists across registrations)
+//   [sort + k_pm_var_*]                         VarTrimmedDist limit (kernels_pmoutliers.hpp); one more select for MedianDist
 //   k_pm_linearize<kP2P>                        weights of the whole chain + per-workgroup fp64 partial sums
 //   k_pm_update                                 reduce, solve / Kabsch, T_iter <- dT T_iter, checkers, host mirror
 // Every kernel returns at once when the loop is done (enqueued iterations past convergence are no-ops).
@@ -24,6 +25,11 @@ struct PmCfg {
     float berg_target;      // berg: the configured tuning (target scale)
     float sq_approx;        // (float)(approximation^2), +inf = off
     float cos_max_angle, outlier_max_d2;
+    // MinDist / MedianDist / VarTrimmedDist (kernels_pmoutliers.hpp)
+    int use_mindist, use_median, use_var;
+    float outlier_min_d2;   // minDist^2 (fp32 product)
+    float median_factor;
+    float var_min_ratio, var_max_ratio, var_lambda;
 };
 
 // Device-resident state of the chain, one per handle.  scale / iteration are the filter's members and persist across
@@ -31,9 +37,13 @@ struct PmCfg {
 struct PmState {
     float scale;
     int iteration;     // the filter's counter: 1 before its first call
-    float sel[3];      // 0: median of d2, 1: median of |d2 - sel[0]|, 2: TrimmedDist limit (+inf: no finite distance)
+    float sel[4];      // 0: median of d2, 1: median of |d2 - sel[0]|, 2: TrimmedDist limit (+inf: no finite distance),
+                       // 3: MedianDist's getDistsQuantile(0.5)
     int fail;          // a statistic this iteration needed had no finite distance (ConvergenceError)
-    int pad[2];
+    int var_valid;     // var_* below belong to an iteration that ran
+    // VarTrimmedDist of the last iteration that ran (k_pm_var_finish)
+    float var_limit, var_ratio;
+    long long var_k, var_n;
 };
 
 // Exact k nearest reference points of every transformed reading point, within max_dist.  16 lanes per point, level
@@ -245,6 +255,7 @@ k_pm_linearize(const float4* __restrict__ src, const float4* __restrict__ src_nr
     if (it->done) return;
     const Xf T = load_xf(it);
     const float trim_limit = ps->sel[2], scale = ps->scale;
+    const float median_limit = c.median_factor * ps->sel[3], var_limit = ps->var_limit;
     const int64_t nk = n * (int64_t)c.knn;
     double v[kSums];
 #pragma unroll
@@ -274,6 +285,9 @@ k_pm_linearize(const float4* __restrict__ src, const float4* __restrict__ src_nr
                 if (val < c.cos_max_angle) w = 0.f;
             }
             if (c.use_maxdist && !(dd <= c.outlier_max_d2)) w = 0.f;
+            if (c.use_mindist && !(dd >= c.outlier_min_d2)) w = 0.f;
+            if (c.use_median && !(dd <= median_limit)) w = 0.f;
+            if (c.use_var && !(dd <= var_limit)) w = 0.f;
             const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
             if (c.use_robust) {
                 float dist = dd;
@@ -372,7 +386,7 @@ __device__ __noinline__ int pm_solve(const double* tot, bool p2p, float* dT) {
 
 __global__ void __launch_bounds__(256)
 k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host, unsigned long long seq,
-            PmState* __restrict__ ps, int p2p, int use_trim) {
+            PmState* __restrict__ ps, int p2p, int use_trim, int use_median) {
     __shared__ double sh[8][kSums];
     __shared__ double tot[kSums];
     if (it->done) return;
@@ -401,7 +415,7 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     if (threadIdx.x != 0) return;
     float Tc[16];
     for (int i = 0; i < 16; ++i) Tc[i] = it->T[i];
-    const bool fail = ps->fail != 0 || (use_trim && !(ps->sel[2] < INFINITY));
+    const bool fail = ps->fail != 0 || (use_trim && !(ps->sel[2] < INFINITY)) || (use_median && !(ps->sel[3] < INFINITY));
     ps->fail = 0;
     for (int i = 0; i < 16; ++i) it->T_prev[i] = Tc[i];
     if (fail || tot[31] == 0.0 || !(tot[28] > 0.0)) {

@@ -222,12 +222,20 @@ class ICP:
 
 class PointMatcherICP(ICP):
     """ICP with the libpointmatcher chain extension (include/o3dslam_reg.h, reg_set_pm_chain): loadFromYaml also takes
-    KDTreeMatcher.knn up to 16, RobustOutlierFilter (OutlierFiltersImpl.h:230-244 names and defaults) and
-    PointToPointErrorMinimizer; everything else binds exactly as for ICP.  The filter's scale / iteration persist
+    KDTreeMatcher.knn up to 16, RobustOutlierFilter (OutlierFiltersImpl.h:230-244 names and defaults),
+    MinDistOutlierFilter, MedianDistOutlierFilter, VarTrimmedDistOutlierFilter (OutlierFiltersImpl.h:96-160) and
+    PointToPointErrorMinimizer; everything else binds exactly as for ICP.  The robust filter's scale / iteration persist
     across compute() calls on the same object, as in the reference."""
 
     _ROBUST_DEFAULTS = {"robustFct": "cauchy", "tuning": 1.0, "scaleEstimator": "mad", "nbIterationForScale": 0,
                         "distanceType": "point2point", "approximation": math.inf}
+    # filter -> ({parameter: default}, chain switch, {parameter: chain field})
+    _DIST_FILTERS = {
+        "MinDistOutlierFilter": ({"minDist": 1.0}, "use_min_dist_filter", {"minDist": "outlier_min_dist"}),
+        "MedianDistOutlierFilter": ({"factor": 3.0}, "use_median_dist", {"factor": "median_factor"}),
+        "VarTrimmedDistOutlierFilter": ({"minRatio": 0.05, "maxRatio": 0.99, "lambda": 2.35}, "use_var_trimmed",
+                                        {"minRatio": "var_min_ratio", "maxRatio": "var_max_ratio", "lambda": "var_lambda"}),
+    }
 
     def __init__(self):
         super().__init__()
@@ -259,6 +267,9 @@ class PointMatcherICP(ICP):
         kept = []
         for f in doc.get("outlierFilters") or []:
             (fname, fargs), = (f.items() if isinstance(f, dict) else [(f, {})])
+            if fname in self._DIST_FILTERS:
+                self._bind_dist_filter(chain, fname, fargs or {})
+                continue
             if fname != "RobustOutlierFilter":
                 kept.append(f)
                 continue
@@ -291,11 +302,28 @@ class PointMatcherICP(ICP):
         st = capi.check_pm_chain(self.params, chain)
         if st == 9:
             raise NotImplementedError("this chain is outside the accelerated path (std scale estimator, or X-ICP with "
-                                      "k-NN / robust weights / point-to-point)")
+                                      "k-NN / robust weights / point-to-point / MinDist / MedianDist / VarTrimmedDist)")
         if st != 0:
-            raise InvalidParameter("invalid chain (knn must lie in 1..16; robust parameters out of range)")
+            raise InvalidParameter("invalid chain (knn must lie in 1..16; a filter parameter out of range; "
+                                   "VarTrimmedDistOutlierFilter: minRatio should be smaller than maxRatio)")
         self.chain = chain
         self.referenceDataPointsFilters, self.readingDataPointsFilters = ref_filters, read_filters
+
+    @classmethod
+    def _bind_dist_filter(cls, chain, fname, fargs):
+        """MinDist / MedianDist / VarTrimmedDist -> the chain's fields; the ranges are checked by reg_check_pm_chain."""
+        defaults, switch, fields = cls._DIST_FILTERS[fname]
+        if getattr(chain, switch):
+            raise NotImplementedError(f"more than one {fname}")
+        unknown = set(fargs) - set(defaults)
+        if unknown:
+            raise InvalidParameter(f"{fname}: unknown parameter(s) {sorted(unknown)}")
+        setattr(chain, switch, 1)
+        for name, value in dict(defaults, **fargs).items():
+            try:
+                setattr(chain, fields[name], float(value))
+            except (TypeError, ValueError):
+                raise InvalidParameter(f"{fname}: {name} must be a number") from None
 
     def _buf(self, key, nbytes):
         b = self._dev.get(key)
