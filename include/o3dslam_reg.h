@@ -51,7 +51,9 @@ typedef enum {
     REG_BAD_ARGUMENT = 6,        /* InvalidParameter                         Registrar.h:103-109 */
     REG_MISSING_FIELD = 7,       /* InvalidField: no `normals` descriptor    DataPoints.cpp:1112 */
     REG_DEVICE_ERROR = 8,        /* HIP runtime failure (no reference analogue); the product never falls back to CPU */
-    REG_UNSUPPORTED = 9
+    REG_UNSUPPORTED = 9,
+    REG_OUT_OF_BOUNDS = 10       /* ConvergenceError "limit out of bounds" of BoundTransformationChecker
+                                    TransformationCheckersImpl.cpp:217-224; nothing in ICP::compute catches it */
 } reg_status;
 
 typedef enum {
@@ -153,7 +155,8 @@ typedef struct {
     float   T_iter_last[16];    /* final T_iter (column-major): P2PL in the centred frames, GICP == T_out */
     int32_t n_band_stalls;      /* fused path: iterations whose trimmed-band prediction failed and were re-run on the generic path */
     int32_t n_constraints;      /* use_xicp: number of non-localizable directions (0 = plain solve) */
-    float   prof_ms[4];         /* loop profiling (o3dslam_reg_debug.h: profile_loop): summed device time of [0] k_match, [1] k_iter_fused launches */
+    float   prof_ms[4];         /* loop profiling (o3dslam_reg_debug.h: profile_loop): summed device time of [0] k_match, [1] k_iter_fused launches;
+                                   [2] a chain with with_cov: device time of the covariance evaluation after the loop (not in loop_ms) */
     int32_t prof_launches[4];   /* ... and how many launches that was */
     /* use_xicp: [0..2] rotation eigen-directions (descending eigenvalue), [3..5] translation; 1 = localizable
        (LocalizabilityCategory, PointMatcher.h:603-607); all 1 when the analysis is off */
@@ -372,7 +375,7 @@ REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T
                                                     REG_PM_POINT_TO_POINT: weighted Kabsch (ErrorMinimizers/PointToPoint.cpp:62-100)
                                                     in fp64, composed T_iter <- dT T_iter in the centred frames
    Rules: only cost REG_COST_P2PL (else REG_BAD_ARGUMENT); use_xicp with knn > 1, robust weights or point-to-point is
-   REG_UNSUPPORTED; the "std" scale estimator is REG_UNSUPPORTED (getStandardDeviation, Matches.cpp:124-129, is an fp32
+   REG_UNSUPPORTED (see the Bound checker / covariance below for the one chain that runs with it); the "std" scale estimator is REG_UNSUPPORTED (getStandardDeviation, Matches.cpp:124-129, is an fp32
    Eigen sum in Eigen's order over every entry including the +inf ones: it cannot be restated to a stated tolerance).
    Robust state: the filter's `iteration` and `scale` persist across registrations of the handle as in the reference
    (ICP::compute never resets them, OutlierFiltersImpl.cpp:408-409,510-543); reg_set_pm_chain resets them.
@@ -402,8 +405,58 @@ REG_API reg_status reg_host_o3d_update(int cost, const double sums[32], double T
                     m < maxEl (entries that are +inf or 0) the reference maps n elements over a buffer that holds m and
                     reads uninitialised memory; here the candidates are j in [minEl, min(maxEl, m)), and k = m - 1
                     when that range is empty.
-   Any of the three with use_xicp is REG_UNSUPPORTED.  struct_size: sizeof(reg_pm_chain), or REG_PM_CHAIN_SIZE_V1 (the
-   struct up to reserved[2], as callers built before these fields pass it: the three filters are then off). */
+   Any of the three with use_xicp is REG_UNSUPPORTED.  struct_size: sizeof(reg_pm_chain), REG_PM_CHAIN_SIZE_V2 (the struct
+   up to var_lambda) or REG_PM_CHAIN_SIZE_V1 (the struct up to reserved[2]), as callers built before the later fields pass
+   it: the fields they do not hold are then off.
+
+   Pose covariance, minimizer statistics, BoundTransformationChecker and SolutionRemapping.  A chain that
+   sets with_cov, use_bound or degeneracy_method is not the default chain and runs the generic chain iteration: never the
+   fused, tail or distributed forms.  use_xicp: a chain that is the plain loop plus with_cov and / or use_bound (knn 1,
+   point-to-plane, none of the chain's filters) runs the first-iteration localizability analysis and the constrained
+   solve inside the chain iteration, with the plain loop's kernels and arithmetic; together with any other chain field it
+   stays REG_UNSUPPORTED, and SolutionRemapping with use_xicp is REG_BAD_ARGUMENT (two degeneracy methods at once).
+     with_cov       PointToPlaneWithCovErrorMinimizer (ErrorMinimizers/PointToPlaneWithCov.cpp:61-162): Censi's closed form
+                    cov = sensorStdDev^2 H^-1 M H^-1, read with reg_get_covariance.  The reference evaluates the estimate in
+                    every iteration and keeps the last; here it is evaluated once, after the loop, on the state of the last
+                    iteration (unobservable).  Point-to-plane only (with REG_PM_POINT_TO_POINT: REG_UNSUPPORTED --
+                    PointToPointWithCov.cpp:77 sets normal = (1,1,1), so the first three components of every v are equal, H is
+                    singular by construction and the reference's result is whatever PartialPivLU returns for it).
+                    Pairs: every (i, k) of the last iteration with w != 0 and a finite d2, at T_iter_prev; the weight VALUES
+                    are not used (the reference's `if (outlierWeights > 0)` is commented out).  p = the reading point moved by
+                    T_iter_prev in the centred frames (the loop's fp32 arithmetic), q / n = the matched reference point /
+                    normal; both clouds are then centred on their own mean over the kept pairs (compute_in_place,
+                    PointToPlane.cpp:281-284).  Deviation: the mean is an fp64 sum in a fixed order rounded to fp32 (Eigen's
+                    fp32 rowwise().mean() order is unspecified).  The last update dT gives beta = -asin(dT(2,0)), alpha =
+                    atan2(dT(2,1), dT(2,2)), gamma = atan2(dT(1,0) / cos beta, dT(0,0) / cos beta), t = dT(0..2,3).  Per pair,
+                    in fp32 and the reference's expression order (lines 116-146): ranges and directions of the centred
+                    points, n_alpha / n_beta / n_gamma, E, N_reading, N_reference and the 6-vectors v, a, b;
+                    H = sum v v^T, M = sum (a a^T + b b^T): 21 + 21 fp64 sums, per-workgroup partial rows and one fixed-order
+                    final sum (no float atomics: two calls return identical bits).  cov = sigma^2 H^-1 M H^-1 in fp64,
+                    stored as fp32, row-major in the reference's order [x y z alpha beta gamma].  rank = rank of H by the rank
+                    rule of the solver (eigenvalues above 6 eps_fp32 of the largest); with rank < 6 the reference inverts a
+                    singular matrix and returns whatever comes out: here cov is all NaN and the status REG_OK.  A kept pair
+                    whose centred point has zero norm makes the result NaN, as in the reference.  Without reference normals:
+                    REG_MISSING_FIELD (the reference returns FLT_MAX * I, PointToPlaneWithCov.cpp:91-92).
+     use_bound      BoundTransformationChecker (TransformationCheckersImpl.cpp:166-225), evaluated in the update step on the
+                    device after every update, in fp32: rotation = quaternion angular distance between T_iter and the identity
+                    the checkers were initialised with (ICP.cpp:993-997), translation = |t_iter| in the centred frames;
+                    strict `>` against max_rotation_norm / max_translation_norm.  A violation ends the registration with
+                    REG_OUT_OF_BOUNDS: T_out = T_init, reg_result is filled and T_iter_last holds the offending pose.
+                    Checkers run in YAML order and an exception ends the pass: with bound_after_counter != 0 a Counter that
+                    fires in the same iteration hides the violation (the registration ends with max_iter_reached).
+                    fixed_iters > 0 ignores this checker like the others.
+     degeneracy_method  REG_DEGENERACY_SOLUTION_REMAPPING (ICP.cpp:2446-2501, 1621-1666; PointToPlane.cpp:301-309).
+                    Point-to-plane only (REG_UNSUPPORTED with point-to-point: the reference warns and skips the detection).
+                    Per iteration, on the fp32 normal matrix A: eigenvalues (descending) / eigenvectors u_j; direction j is
+                    degenerate when lambda_j < sr_threshold -- with sr_use2019 the threshold is the condition number
+                    lambda_max / lambda_min, as the code passes it (ICP.cpp:2473-2481).  If any direction is degenerate
+                    P = sum over the kept j of u_j u_j^T (for orthonormal U the reference's eigenvectors^-T * copy^T);
+                    otherwise P KEEPS ITS VALUE OF THE PREVIOUS ITERATION (the reference's behaviour: a stale projector
+                    stays in force).  P is the identity at the start of every registration (PointMatcher.h:645).
+                    x = P solve(A, b).  A all zero or P all zero: the loop stops before the update, T_out = T_init bit for
+                    bit, status REG_OK, reg_minimizer_stats.returned_prior = 1 (ICP.cpp:1175-1179, 1335-1341).
+                    Deviation: the fp64 Jacobi eigen-solver stands in for Eigen's fp32 JacobiSVD; decisions can differ only
+                    when an eigenvalue lies within fp32 round-off of the threshold. */
 enum { REG_PM_POINT_TO_PLANE = 0, REG_PM_POINT_TO_POINT = 1 };
 enum {   /* robustFct (OutlierFiltersImpl.cpp:385-394) */
     REG_ROBUST_CAUCHY = 0, REG_ROBUST_WELSCH = 1, REG_ROBUST_SC = 2, REG_ROBUST_GM = 3, REG_ROBUST_TUKEY = 4,
@@ -432,11 +485,25 @@ typedef struct {
     float   var_min_ratio;       /* "minRatio" (0.05) */
     float   var_max_ratio;       /* "maxRatio" (0.99) */
     float   var_lambda;          /* "lambda" (2.35) */
+    /* -- fields after REG_PM_CHAIN_SIZE_V2 (pose covariance, BoundTransformationChecker, SolutionRemapping; below) -- */
+    int32_t with_cov;            /* PointToPlaneWithCovErrorMinimizer: reg_get_covariance after the registration */
+    float   sensor_std_dev;      /* "sensorStdDev" (0.01), [0, inf) */
+    int32_t use_bound;           /* BoundTransformationChecker */
+    float   max_rotation_norm;   /* "maxRotationNorm" (1), >= 0, rad */
+    float   max_translation_norm;/* "maxTranslationNorm" (1), >= 0 */
+    int32_t bound_after_counter; /* 1: the Counter checker is listed before the Bound checker (YAML order) */
+    int32_t degeneracy_method;   /* REG_DEGENERACY_NONE | REG_DEGENERACY_SOLUTION_REMAPPING */
+    float   sr_threshold;        /* SolutionRemapping "threshold" */
+    int32_t sr_use2019;          /* SolutionRemapping "use2019" */
+    int32_t reserved2;
 } reg_pm_chain;
 #define REG_PM_CHAIN_SIZE_V1 48
+#define REG_PM_CHAIN_SIZE_V2 80
+enum { REG_DEGENERACY_NONE = 0, REG_DEGENERACY_SOLUTION_REMAPPING = 1 };
 
-/* knn 1, point-to-plane, robust / MinDist / MedianDist / VarTrimmedDist off: the loop as without a chain (parameter
-   defaults as OutlierFiltersImpl.h). */
+/* knn 1, point-to-plane, robust / MinDist / MedianDist / VarTrimmedDist / covariance / Bound / SolutionRemapping off: the
+   loop as without a chain (parameter defaults as OutlierFiltersImpl.h, PointToPlaneWithCov.h:75,
+   TransformationCheckersImpl.h). */
 REG_API void       reg_default_pm_chain(reg_pm_chain* c);
 /* Pure check of a chain against the parameters it would run with (no device). */
 REG_API reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c);
@@ -448,6 +515,44 @@ REG_API reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32
    reference logs it as "Optimized ratio"), the rank k it came from and n = N knn.  REG_NOT_CONFIGURED without a chain
    registration with use_var_trimmed on the current reading.  Any pointer may be NULL. */
 REG_API reg_status reg_get_var_trim(const reg_handle* h, float* ratio, int64_t* index, int64_t* n_total);
+/* Pose covariance of the last registration (with_cov; contract above): cov row-major 6x6 [x y z alpha beta gamma], *rank
+   the rank of H (cov is all NaN when rank < 6).  REG_NOT_CONFIGURED unless the last registration on the current reading
+   ran with with_cov.  Two calls return identical bits.  Any output pointer may be NULL. */
+REG_API reg_status reg_get_covariance(const reg_handle* h, float cov[36], int32_t* rank);
+/* The 42 fp64 sums the covariance came from: the packed upper triangles (row by row) of H and M.  Same validity. */
+REG_API reg_status reg_get_covariance_sums(const reg_handle* h, double H[21], double M[21]);
+/* cov = sigma^2 H^-1 M H^-1 from the packed sums, the same code as the device, without a device. */
+REG_API reg_status reg_host_censi_covariance(const double H[21], const double M[21], float sigma, float cov[36],
+                                             int32_t* rank);
+/* ErrorMinimizer quality getters (ErrorMinimizer.cpp:249-277, PointToPlane.cpp:780-930) of the last chain registration,
+   valid whenever reg_get_correspondences[_k] is (REG_NOT_CONFIGURED otherwise); taken at T_iter_prev.
+   The reference adds the weights in an fp32 running sum; here the sum is fp64 in a fixed order, rounded once. */
+typedef struct {
+    int32_t struct_size;               /* = sizeof(reg_minimizer_stats); checked */
+    int32_t returned_prior;            /* SolutionRemapping left the loop and T_out = T_init */
+    double  point_used_ratio;          /* pairs with w != 0 / (N knn)                    getPointUsedRatio */
+    double  weighted_point_used_ratio; /* sum w / (N knn)                                 getWeightedPointUsedRatio */
+    double  overlap;                   /* = weighted_point_used_ratio: what getOverlap returns for clouds without
+                                          simpleSensorNoise / densities descriptors (PointToPlane.cpp:886-890) */
+    double  residual_error;            /* sum w ((p - q) . n)^2 (PointToPlane.cpp:780-816) / sum w |p - q|^2
+                                          (PointToPoint.cpp:103-116) = reg_result.error */
+    int64_t n_rejected_matches;        /* pairs with w == 0 */
+    int64_t n_rejected_points;         /* reading points all of whose knn pairs have w == 0 */
+} reg_minimizer_stats;
+REG_API reg_status reg_get_minimizer_stats(reg_handle* h, reg_minimizer_stats* out);
+/* SolutionRemapping of the last iteration: categories (1 = kept, 0 = degenerate; solRemapCategories), the eigenvalues
+   descending (optimizationEigenvalues) and lambda_max / lambda_min (optimizationConditionNumber_).  REG_NOT_CONFIGURED
+   without a SolutionRemapping registration on the current reading.  Any pointer may be NULL. */
+REG_API reg_status reg_get_degeneracy(const reg_handle* h, int32_t categories[6], float eigenvalues[6],
+                                      float* condition_number);
+/* BoundTransformationChecker's condition variables after the last update (rotation [rad], translation).
+   REG_NOT_CONFIGURED without a use_bound registration on the current reading. */
+REG_API reg_status reg_get_bound(const reg_handle* h, float* rotation, float* translation);
+/* One SolutionRemapping step on the host, the same code as the device: A row-major fp32, P_in the projector in force
+   (the identity for the first iteration), P_out the projector after this step (== P_in when nothing is degenerate).
+   Returns REG_OK, or REG_NO_CORRESPONDENCES when the reference would return the prior (A or P_out all zero). */
+REG_API reg_status reg_host_solution_remap(const float A[36], float threshold, int use2019, const double P_in[36],
+                                           double P_out[36], int32_t categories[6], float eigenvalues[6]);
 /* The VarTrimmedDist contract above on the host (no device): d2[n] may hold +inf and zeros.  *index = k, *ratio =
    optRatio, *limit = the quantile the weights compare against.  The device evaluates the same objective (fp64) with
    another, fixed, summation order.  REG_BAD_ARGUMENT for ratios outside [1e-7, 1] or minRatio >= maxRatio,

@@ -14,7 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("O3D_REG_LIB") or os.path.join(_HERE, "lib", "libo3dslam_reg.so")   # O3D_REG_LIB: A/B builds (tools/)
 
 STATUS_NAMES = {0: "OK", 1: "EMPTY_TARGET", 2: "EMPTY_SOURCE", 3: "NO_CORRESPONDENCES", 4: "BAD_TRANSFORM",
-                5: "NOT_CONFIGURED", 6: "BAD_ARGUMENT", 7: "MISSING_FIELD", 8: "DEVICE_ERROR", 9: "UNSUPPORTED"}
+                5: "NOT_CONFIGURED", 6: "BAD_ARGUMENT", 7: "MISSING_FIELD", 8: "DEVICE_ERROR", 9: "UNSUPPORTED",
+                10: "OUT_OF_BOUNDS"}
+OUT_OF_BOUNDS = 10   # REG_OUT_OF_BOUNDS: BoundTransformationChecker's ConvergenceError
 COST_P2PL, COST_GICP = 0, 1
 # Open3D RegistrationICP with TransformationEstimationPointToPlane / PointToPoint (RegistrationIcpPointToPlane /
 # RegistrationIcpPointToPoint, open3d_slam/src/CloudRegistration.cpp:54-101); see reg_cost in the header
@@ -162,8 +164,9 @@ class OctreeOut(C.Structure):
 
 
 class PmChain(C.Structure):
-    """reg_pm_chain: the libpointmatcher chain extension (k-NN matching, RobustOutlierFilter, PointToPoint, and the
-    MinDist / MedianDist / VarTrimmedDist outlier filters appended after `reserved`)."""
+    """reg_pm_chain up to `var_lambda` (REG_PM_CHAIN_SIZE_V2 bytes): the libpointmatcher chain extension (k-NN matching,
+    RobustOutlierFilter, PointToPoint, and the MinDist / MedianDist / VarTrimmedDist outlier filters appended after
+    `reserved`).  The C ABI accepts this size; the fields after it are then off.  PmChainV3 is the whole struct."""
     _fields_ = [("struct_size", C.c_int32), ("knn", C.c_int32), ("minimizer", C.c_int32), ("use_robust", C.c_int32),
                 ("robust_fct", C.c_int32), ("tuning", C.c_float), ("scale_estimator", C.c_int32),
                 ("nb_iter_for_scale", C.c_int32), ("distance_type", C.c_int32), ("approximation", C.c_float),
@@ -174,7 +177,26 @@ class PmChain(C.Structure):
                 ("var_lambda", C.c_float)]
 
 
-PM_CHAIN_SIZE_V1 = 48   # REG_PM_CHAIN_SIZE_V1: the struct up to `reserved`, still accepted (the three new filters off)
+class PmChainV3(PmChain):
+    """The whole reg_pm_chain: PmChain plus the pose covariance, BoundTransformationChecker and SolutionRemapping fields
+    appended after `var_lambda` (a ctypes subclass appends its fields to its base's)."""
+    _fields_ = [("with_cov", C.c_int32), ("sensor_std_dev", C.c_float),
+                ("use_bound", C.c_int32), ("max_rotation_norm", C.c_float), ("max_translation_norm", C.c_float),
+                ("bound_after_counter", C.c_int32),
+                ("degeneracy_method", C.c_int32), ("sr_threshold", C.c_float), ("sr_use2019", C.c_int32),
+                ("reserved2", C.c_int32)]
+
+
+class MinimizerStats(C.Structure):
+    """reg_minimizer_stats: the ErrorMinimizer quality getters of the last registration."""
+    _fields_ = [("struct_size", C.c_int32), ("returned_prior", C.c_int32), ("point_used_ratio", C.c_double),
+                ("weighted_point_used_ratio", C.c_double), ("overlap", C.c_double), ("residual_error", C.c_double),
+                ("n_rejected_matches", C.c_int64), ("n_rejected_points", C.c_int64)]
+
+
+PM_CHAIN_SIZE_V1 = 48   # REG_PM_CHAIN_SIZE_V1: the struct up to `reserved`, still accepted (the later fields off)
+PM_CHAIN_SIZE_V2 = 80   # REG_PM_CHAIN_SIZE_V2: the struct up to `var_lambda`, still accepted (covariance / Bound / SR off)
+DEGENERACY_NONE, DEGENERACY_SOLUTION_REMAPPING = 0, 1
 PM_POINT_TO_PLANE, PM_POINT_TO_POINT = 0, 1
 ROBUST_FCTS = {"cauchy": 0, "welsch": 1, "sc": 2, "gm": 3, "tukey": 4, "huber": 5, "L1": 6, "student": 7}
 SCALE_ESTIMATORS = {"none": 0, "mad": 1, "berg": 2, "std": 3}
@@ -196,6 +218,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_pm_chain", "reg_check_pm_chain", "reg_set_pm_chain", "reg_get_robust_state",
            "reg_get_correspondences_k", "reg_host_robust_weights", "reg_host_pm_p2p_update",
            "reg_get_var_trim", "reg_host_var_trim",
+           "reg_get_covariance", "reg_get_covariance_sums", "reg_host_censi_covariance", "reg_get_minimizer_stats",
+           "reg_get_degeneracy", "reg_get_bound", "reg_host_solution_remap",
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks"]
 
@@ -296,7 +320,7 @@ def load_library():
     lib.reg_smooth_normals.argtypes = [vp, vp, vp, i64, C.c_int, C.c_int, vp]
     lib.reg_estimate_normals.argtypes = [vp, vp, i64, i64, C.c_int, C.c_int, C.c_float, vp, C.c_int,
                                          C.POINTER(NormalsOut), C.POINTER(C.c_int64)]
-    lib.reg_default_pm_chain.argtypes = [C.POINTER(PmChain)]
+    lib.reg_default_pm_chain.argtypes = [C.POINTER(PmChainV3)]   # writes sizeof(reg_pm_chain) bytes
     lib.reg_default_pm_chain.restype = None
     lib.reg_check_pm_chain.argtypes = [C.POINTER(RegParams), C.POINTER(PmChain)]
     lib.reg_set_pm_chain.argtypes = [vp, C.POINTER(PmChain)]
@@ -304,6 +328,14 @@ def load_library():
     lib.reg_get_correspondences_k.argtypes = [vp, C.c_int32, vp, vp, vp]
     lib.reg_host_robust_weights.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, vp, i64, vp]
     lib.reg_host_pm_p2p_update.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    pf, pd, pi32 = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    lib.reg_get_covariance.argtypes = [vp, vp, pi32]
+    lib.reg_get_covariance_sums.argtypes = [vp, vp, vp]
+    lib.reg_host_censi_covariance.argtypes = [vp, vp, C.c_float, vp, pi32]
+    lib.reg_get_minimizer_stats.argtypes = [vp, C.POINTER(MinimizerStats)]
+    lib.reg_get_degeneracy.argtypes = [vp, vp, vp, pf]
+    lib.reg_get_bound.argtypes = [vp, pf, pf]
+    lib.reg_host_solution_remap.argtypes = [vp, C.c_float, C.c_int, vp, vp, vp, vp]
     lib.reg_get_var_trim.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_host_var_trim.argtypes = [vp, i64, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float)]
@@ -414,11 +446,21 @@ def host_octree_random_picks(sizes) -> np.ndarray:
     return picks
 
 
-def default_pm_chain() -> PmChain:
-    """knn 1, point-to-plane, robust / MinDist / MedianDist / VarTrimmedDist off (the plain loop); their parameters at
+def default_pm_chain_v3() -> PmChainV3:
+    """reg_default_pm_chain: knn 1, point-to-plane, every module of the chain off (the plain loop); their parameters at
     the reference's defaults."""
-    c = PmChain()
+    c = PmChainV3()
     load_library().reg_default_pm_chain(C.byref(c))
+    return c
+
+
+def default_pm_chain() -> PmChain:
+    """The same defaults in the struct up to `var_lambda` (struct_size = REG_PM_CHAIN_SIZE_V2): knn 1, point-to-plane,
+    robust / MinDist / MedianDist / VarTrimmedDist off.  A chain of this size cannot switch the later modules on."""
+    full = default_pm_chain_v3()
+    c = PmChain()
+    C.memmove(C.byref(c), C.byref(full), C.sizeof(PmChain))
+    c.struct_size = C.sizeof(PmChain)
     return c
 
 
@@ -449,6 +491,47 @@ def host_var_trim(d2, min_ratio=0.05, max_ratio=0.99, lam=2.35):
     if st != 0:
         raise RegError(st, "reg_host_var_trim")
     return int(k.value), float(ratio.value), float(limit.value)
+
+
+def _pack_sym6(A) -> np.ndarray:
+    """Upper triangle of a 6x6 matrix, row by row (the layout of the covariance sums)."""
+    A = np.asarray(A, np.float64).reshape(6, 6)
+    return np.ascontiguousarray(A[np.triu_indices(6)])
+
+
+def unpack_sym6(v) -> np.ndarray:
+    """The symmetric 6x6 matrix of 21 packed upper-triangle values."""
+    A = np.zeros((6, 6), np.float64)
+    A[np.triu_indices(6)] = np.asarray(v, np.float64).reshape(21)
+    return A + np.triu(A, 1).T
+
+
+def host_censi_covariance(H, M, sigma=0.01):
+    """reg_host_censi_covariance: (cov float32 6x6 [x y z alpha beta gamma], rank of H) from the sums H = sum v v^T and
+    M = sum (a a^T + b b^T), given as 6x6 matrices or as 21 packed values -- the device's code on the host."""
+    Hp = _pack_sym6(H) if np.size(H) == 36 else np.ascontiguousarray(H, np.float64).reshape(21)
+    Mp = _pack_sym6(M) if np.size(M) == 36 else np.ascontiguousarray(M, np.float64).reshape(21)
+    cov = np.zeros(36, np.float32)
+    rank = C.c_int32()
+    st = load_library().reg_host_censi_covariance(_ptr(Hp), _ptr(Mp), float(sigma), _ptr(cov), C.byref(rank))
+    if st != 0:
+        raise RegError(st, "reg_host_censi_covariance")
+    return cov.reshape(6, 6), int(rank.value)
+
+
+def host_solution_remap(A, threshold, use2019=False, P_in=None):
+    """reg_host_solution_remap: one SolutionRemapping step on the fp32 normal matrix A with the projector P_in in force
+    (None: the identity).  Returns (P_out float64 6x6, categories int32[6], eigenvalues float32[6] descending,
+    return_prior bool)."""
+    a = np.ascontiguousarray(A, np.float32).reshape(36)
+    pin = np.ascontiguousarray(np.eye(6) if P_in is None else P_in, np.float64).reshape(36)
+    pout = np.zeros(36, np.float64)
+    cat, eig = np.zeros(6, np.int32), np.zeros(6, np.float32)
+    st = load_library().reg_host_solution_remap(_ptr(a), float(threshold), int(bool(use2019)), _ptr(pin), _ptr(pout),
+                                                _ptr(cat), _ptr(eig))
+    if st not in (0, 3):
+        raise RegError(st, "reg_host_solution_remap")
+    return pout.reshape(6, 6), cat, eig, st == 3
 
 
 def host_pm_p2p_update(sums):
@@ -524,6 +607,10 @@ class Registration:
     def _check(self, st):
         if st != 0:
             raise RegError(st, self._lib.reg_last_error(self._h).decode())
+
+    def last_error(self) -> str:
+        """reg_last_error: the message of the last failing call on this handle."""
+        return self._lib.reg_last_error(self._h).decode()
 
     def set_stream(self, hip_stream: int):
         self._check(self._lib.reg_set_stream(self._h, C.c_void_p(hip_stream)))
@@ -849,7 +936,7 @@ class Registration:
     def set_pm_chain(self, chain: "PmChain | None"):
         """reg_set_pm_chain: None (or the default chain) returns to the plain loop; resets the robust state."""
         if chain is not None:
-            chain.struct_size = C.sizeof(PmChain)
+            chain.struct_size = C.sizeof(type(chain))   # PmChain (REG_PM_CHAIN_SIZE_V2) or PmChainV3
         self.pm_chain = chain
         self._check(self._lib.reg_set_pm_chain(self._h, C.byref(chain) if chain is not None else None))
 
@@ -876,6 +963,37 @@ class Registration:
         ratio, k, n = C.c_float(), C.c_int64(), C.c_int64()
         self._check(self._lib.reg_get_var_trim(self._h, C.byref(ratio), C.byref(k), C.byref(n)))
         return float(ratio.value), int(k.value), int(n.value)
+
+    def get_covariance(self):
+        """(cov float32 6x6 in the order [x y z alpha beta gamma], rank of H) of the last with_cov registration."""
+        cov = np.zeros(36, np.float32)
+        rank = C.c_int32()
+        self._check(self._lib.reg_get_covariance(self._h, _ptr(cov), C.byref(rank)))
+        return cov.reshape(6, 6), int(rank.value)
+
+    def get_covariance_sums(self):
+        """(H, M) float64 6x6: the sums the covariance of the last with_cov registration came from."""
+        Hp, Mp = np.zeros(21, np.float64), np.zeros(21, np.float64)
+        self._check(self._lib.reg_get_covariance_sums(self._h, _ptr(Hp), _ptr(Mp)))
+        return unpack_sym6(Hp), unpack_sym6(Mp)
+
+    def get_minimizer_stats(self) -> MinimizerStats:
+        st = MinimizerStats()
+        st.struct_size = C.sizeof(MinimizerStats)
+        self._check(self._lib.reg_get_minimizer_stats(self._h, C.byref(st)))
+        return st
+
+    def get_degeneracy(self):
+        """(categories int32[6], eigenvalues float32[6] descending, condition number) of SolutionRemapping's last step."""
+        cat, eig, cond = np.zeros(6, np.int32), np.zeros(6, np.float32), C.c_float()
+        self._check(self._lib.reg_get_degeneracy(self._h, _ptr(cat), _ptr(eig), C.byref(cond)))
+        return cat, eig, float(cond.value)
+
+    def get_bound(self):
+        """(rotation [rad], translation) BoundTransformationChecker compared against its limits after the last update."""
+        r, t = C.c_float(), C.c_float()
+        self._check(self._lib.reg_get_bound(self._h, C.byref(r), C.byref(t)))
+        return float(r.value), float(t.value)
 
     def target_info(self) -> TargetInfo:
         info = TargetInfo()

@@ -644,19 +644,21 @@ static int sequence_limit(const reg_params& p) {
 
 static bool pm_chain_is_default(const reg_pm_chain* c) {
     return c->knn == 1 && c->minimizer == REG_PM_POINT_TO_PLANE && !c->use_robust && !c->use_min_dist_filter &&
-           !c->use_median_dist && !c->use_var_trimmed;
+           !c->use_median_dist && !c->use_var_trimmed && !c->with_cov && !c->use_bound && c->degeneracy_method == 0;
 }
+static bool pm_chain_has_extras(const reg_pm_chain* c) { return c->with_cov || c->use_bound || c->degeneracy_method != 0; }
 
 // The caller's chain in today's layout: a struct of REG_PM_CHAIN_SIZE_V1 bytes (built before MinDist / MedianDist /
-// VarTrimmedDist) is completed with those filters off
+// VarTrimmedDist) or REG_PM_CHAIN_SIZE_V2 bytes (before covariance / Bound / SolutionRemapping) is completed with the
+// fields it does not hold off
 static bool pm_chain_read(const reg_pm_chain* c, reg_pm_chain* out) {
     if (c->struct_size == (int32_t)sizeof(reg_pm_chain)) {
         *out = *c;
         return true;
     }
-    if (c->struct_size != REG_PM_CHAIN_SIZE_V1) return false;
+    if (c->struct_size != REG_PM_CHAIN_SIZE_V1 && c->struct_size != REG_PM_CHAIN_SIZE_V2) return false;
     reg_default_pm_chain(out);
-    std::memcpy(out, c, REG_PM_CHAIN_SIZE_V1);
+    std::memcpy(out, c, (size_t)c->struct_size);
     out->struct_size = (int32_t)sizeof(reg_pm_chain);
     return true;
 }
@@ -696,6 +698,20 @@ static PmCfg make_pm_cfg(const reg_handle* h) {
     f.var_max_ratio = c.var_max_ratio;
     f.var_lambda = c.var_lambda;
     return f;
+}
+
+static PmExtraCfg make_pm_extra_cfg(const reg_handle* h) {
+    const reg_pm_chain& c = h->pm;
+    PmExtraCfg x;
+    x.use_bound = c.use_bound;
+    x.bound_after_counter = c.bound_after_counter;
+    x.max_rot = c.max_rotation_norm;
+    x.max_trans = c.max_translation_norm;
+    x.degeneracy = c.degeneracy_method;
+    x.sr_use2019 = c.sr_use2019;
+    x.sr_threshold = c.sr_threshold;
+    x.with_cov = c.with_cov;
+    return x;
 }
 
 // One exact select over nk keys (+inf keys are not counted) -> sel[slot]: the value of rank trim_rank(finite, ratio)
@@ -783,12 +799,62 @@ static reg_status enqueue_pm_iteration(reg_handle* h) {
         k_pm_linearize<false><<<lb, 256, 0, h->stream>>>(src, snrm, n, it, kpos, kd2, h->t_pts.as<float4>(), tnrm, cfg,
                                                          h->pm_state.as<PmState>(), h->pm_w.as<float>(), h->pm_partials.as<double>());
     ++h->seq;
-    k_pm_update<<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
-                                          h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
-                                          cfg.use_trim, cfg.use_median);
+    const PmExtraCfg xc = make_pm_extra_cfg(h);
+    if (pm_chain_has_extras(&c))
+        k_pm_update<true><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
+                                                    h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
+                                                    cfg.use_trim, cfg.use_median, xc, h->pm_xstate.as<PmExtraState>(), 0,
+                                                    h->prm.use_xicp ? h->i_xicp.as<XicpState>() : nullptr);
+    else
+        k_pm_update<false><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
+                                                     h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
+                                                     cfg.use_trim, cfg.use_median, xc, nullptr, 0, nullptr);
+    if (h->xicp_pending) {
+        // R8x, first iteration (only a chain of Bound / covariance over the plain filters runs with use_xicp: knn 1, so
+        // the chain's N x 1 buffers are the plain loop's): the information sums, then decide + solve + update
+        h->xicp_pending = false;
+        const int blocks = (int)std::min<int64_t>(512, (h->n + 255) / 256);
+        k_xicp_center<<<blocks, 256, 0, h->stream>>>(src, h->n, it, kpos, h->pm_w.as<float>(), h->i_xicp.as<XicpState>());
+        k_xicp_detect<<<blocks, 256, 0, h->stream>>>(src, h->n, it, kpos, h->pm_w.as<float>(), h->t_nrm.as<float4>(),
+                                                     h->i_xicp.as<XicpState>());
+        k_pm_update<true><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
+                                                    h->pm_state.as<PmState>(), 0, cfg.use_trim, cfg.use_median, xc,
+                                                    h->pm_xstate.as<PmExtraState>(), 1, h->i_xicp.as<XicpState>());
+    }
     HIPCHK(h, hipGetLastError());
     h->have_match = true;
     h->pm_have_match = true;
+    return REG_OK;
+}
+
+// Workgroups of the post-loop reductions over nk pairs
+static inline int pmx_blocks(int64_t nk) { return (int)std::max<int64_t>(1, std::min<int64_t>(kPmxBlocks, grid_for(nk))); }
+
+// PointToPlaneWithCovErrorMinimizer::estimateCovariance on the buffers of the last iteration (kernels_pmextras.hpp): two
+// passes over the pairs and two single-workgroup reductions; the result block is copied to the host.
+static reg_status evaluate_pm_covariance(reg_handle* h) {
+    const int64_t n = h->n, nk = n * (int64_t)h->pm.knn;
+    const int nb = pmx_blocks(nk);
+    HIPCHK(h, h->pm_xrows.reserve((size_t)kPmxBlocks * kPmxCovSums * 8));
+    HIPCHK(h, h->pm_xmeans.reserve(kPmxRow * 8));
+    HIPCHK(h, h->pm_xcov.reserve(sizeof(PmCovOut)));
+    const IterState* it = h->i_iter.as<IterState>();
+    const float4* src = h->s_xyz.as<float4>();
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    k_pmx_pair_means<<<nb, 256, 0, h->stream>>>(src, n, h->pm.knn, it, h->pm_pos.as<int>(), h->pm_w.as<float>(),
+                                                h->t_pts.as<float4>(), h->pm_xrows.as<double>());
+    k_pmx_reduce_rows<<<1, 256, 0, h->stream>>>(h->pm_xrows.as<double>(), nb, h->pm_xmeans.as<double>());
+    k_pmx_cov_terms<<<nb, 256, 0, h->stream>>>(src, n, h->pm.knn, it, h->pm_pos.as<int>(), h->pm_w.as<float>(),
+                                               h->t_pts.as<float4>(), h->t_nrm.as<float4>(), h->pm_xmeans.as<double>(),
+                                               h->pm_xstate.as<PmExtraState>(), h->pm_xrows.as<double>());
+    k_pmx_cov_finish<<<1, 256, 0, h->stream>>>(h->pm_xrows.as<double>(), nb, h->pm_xmeans.as<double>(), h->pm.sensor_std_dev,
+                                               h->pm_xcov.as<PmCovOut>());
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&h->pm_cov_host, h->pm_xcov.p, sizeof(PmCovOut), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    (void)hipEventElapsedTime(&h->pm_cov_ms, h->ev0, h->ev1);
+    HIPCHK(h, hipGetLastError());
+    h->pm_cov_valid = true;
     return REG_OK;
 }
 
@@ -821,6 +887,17 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
                                            h->stream));
         HIPCHK(h, h->pm_sort_tmp.reserve(std::max<size_t>(need, 16)));
         h->pm_sort_bytes = need;
+    }
+    const bool extras = pm_chain_has_extras(&h->pm);
+    h->pm_x_valid = false;
+    h->pm_cov_valid = false;
+    if (extras) {
+        // P = identity and clear flags, as the reference's per-registration local (PointMatcher.h:645)
+        HIPCHK(h, h->pm_xstate.reserve(sizeof(PmExtraState)));
+        std::memset(&h->pm_xhost, 0, sizeof(PmExtraState));
+        for (int k = 0; k < 6; ++k) h->pm_xhost.P[7 * k] = 1.0;
+        HIPCHK(h, hipMemcpyAsync(h->pm_xstate.p, &h->pm_xhost, sizeof(PmExtraState), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     float T_start[16];
     m4_identity(T_start);
@@ -862,7 +939,12 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     HIPCHK(h, hipGetLastError());
     const double* sums = mir->sums;
     res->iterations = mir->iterations;
-    for (int k = 0; k < 6; ++k) res->localizable[k] = 1;
+    for (int k = 0; k < 6; ++k) {
+        res->localizable[k] = h->prm.use_xicp ? mir->localizable[k] : 1;
+        res->xicp_combined[k] = h->prm.use_xicp ? mir->xicp_comb[k] : 0.0;
+        res->xicp_high[k] = h->prm.use_xicp ? mir->xicp_high[k] : 0.0;
+    }
+    res->n_constraints = h->prm.use_xicp ? mir->n_constraints : 0;
     res->converged = mir->converged;
     res->max_iter_reached = mir->max_iter_reached;
     res->rank_last = mir->rank_last;
@@ -873,16 +955,41 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     res->fitness = sums[31] / ((double)h->n * (double)h->pm.knn);
     res->inlier_rmse = sums[31] > 0 ? std::sqrt(sums[30] / sums[31]) : 0.0;
     sums_to_system(sums, h->pm.minimizer == REG_PM_POINT_TO_POINT ? REG_COST_O3D_P2P : REG_COST_P2PL, res->H_last, res->b_last);
+    h->pm_last_error = res->error;
+    if (extras) {
+        HIPCHK(h, hipMemcpy(&h->pm_xhost, h->pm_xstate.p, sizeof(PmExtraState), hipMemcpyDeviceToHost));
+        h->pm_x_valid = true;
+    }
+    if (mir->status == REG_OUT_OF_BOUNDS) {
+        // BoundTransformationChecker threw: T_out stays T_init (set by reg_register), the offending pose is reported
+        row_to_col(mir->T, res->T_iter_last);
+        row_to_col(mir->T_prev, res->T_iter_prev);
+        char msg[160];
+        snprintf(msg, sizeof(msg), "limit out of bounds: rot: %g/%g tr: %g/%g", (double)h->pm_xhost.bound_rot,
+                 (double)h->pm.max_rotation_norm, (double)h->pm_xhost.bound_trans, (double)h->pm.max_translation_norm);
+        h->err = msg;
+        return REG_OUT_OF_BOUNDS;
+    }
     if (mir->status != REG_OK) {
         h->err = "ErrorMinimizer: no point to minimize (or no finite distance for a statistic of the chain)";
         return (reg_status)mir->status;
     }
     float T_iter[16], Tout_row[16];
     std::memcpy(T_iter, mir->T, 64);
-    compose_rowmajor(h, T_iter, Tout_row, /*later_kernel_reported=*/true);
     row_to_col(T_iter, res->T_iter_last);
     row_to_col(mir->T_prev, res->T_iter_prev);
-    row_to_col(Tout_row, T_out);
+    if (extras && h->pm_xhost.returned_prior) {
+        // SolutionRemapping could not detect: the prior is returned as it came in (reg_register copied it to T_out)
+    } else {
+        compose_rowmajor(h, T_iter, Tout_row, /*later_kernel_reported=*/true);
+        row_to_col(Tout_row, T_out);
+        if (h->pm.with_cov && h->pm_xhost.have_dT) {
+            s = evaluate_pm_covariance(h);
+            if (s != REG_OK) return s;
+            res->prof_ms[2] = h->pm_cov_ms;   // device time of the covariance evaluation, outside loop_ms
+            res->prof_launches[2] = 4;
+        }
+    }
     res->n_band_stalls = 0;
     res->n_tail_launches = 0;
     res->n_tail_iterations = 0;
@@ -1369,6 +1476,16 @@ void reg_default_pm_chain(reg_pm_chain* c) {
     c->var_min_ratio = 0.05f;
     c->var_max_ratio = 0.99f;
     c->var_lambda = 2.35f;
+    // PointToPlaneWithCov.h:75, TransformationCheckersImpl.h (BoundTransformationChecker), SolutionRemapping off
+    c->with_cov = 0;
+    c->sensor_std_dev = 0.01f;
+    c->use_bound = 0;
+    c->max_rotation_norm = 1.0f;
+    c->max_translation_norm = 1.0f;
+    c->bound_after_counter = 0;
+    c->degeneracy_method = REG_DEGENERACY_NONE;
+    c->sr_threshold = 0.f;
+    c->sr_use2019 = 0;
 }
 
 static bool pm_ratio_ok(float r) { return r >= 1e-7f && r <= 1.f; }
@@ -1398,7 +1515,27 @@ reg_status reg_check_pm_chain(const reg_params* p, const reg_pm_chain* c_in) {
             return REG_BAD_ARGUMENT;
         if (c->var_min_ratio >= c->var_max_ratio) return REG_BAD_ARGUMENT;   // the filter's constructor throws
     }
-    if (p->use_xicp && !pm_chain_is_default(c)) return REG_UNSUPPORTED;
+    // covariance / Bound / SolutionRemapping: NaN fails every range test
+    if (c->with_cov) {
+        if (!(c->sensor_std_dev >= 0.f && c->sensor_std_dev < INFINITY)) return REG_BAD_ARGUMENT;   // [0, inf)
+        if (c->minimizer == REG_PM_POINT_TO_POINT) return REG_UNSUPPORTED;   // PointToPointWithCov: see include/o3dslam_reg.h
+    }
+    if (c->use_bound) {
+        if (!(c->max_rotation_norm >= 0.f) || !(c->max_translation_norm >= 0.f)) return REG_BAD_ARGUMENT;   // [0, inf]
+    }
+    if (c->degeneracy_method != REG_DEGENERACY_NONE) {
+        if (c->degeneracy_method != REG_DEGENERACY_SOLUTION_REMAPPING) return REG_BAD_ARGUMENT;
+        if (c->sr_threshold != c->sr_threshold) return REG_BAD_ARGUMENT;
+        if (p->use_xicp) return REG_BAD_ARGUMENT;                            // two degeneracy methods at once
+        if (c->minimizer == REG_PM_POINT_TO_POINT) return REG_UNSUPPORTED;   // the reference warns and skips the detection
+    }
+    // X-ICP runs with a chain only when the chain is the plain loop plus the Bound checker and / or the covariance
+    if (p->use_xicp && !pm_chain_is_default(c)) {
+        reg_pm_chain plain = *c;
+        plain.with_cov = 0;
+        plain.use_bound = 0;
+        if (!pm_chain_is_default(&plain)) return REG_UNSUPPORTED;
+    }
     return REG_OK;
 }
 
@@ -1458,6 +1595,101 @@ reg_status reg_get_var_trim(const reg_handle* h, float* ratio, int64_t* index, i
     if (index) *index = (int64_t)ps.var_k;
     if (n_total) *n_total = (int64_t)ps.var_n;
     return REG_OK;
+}
+
+reg_status reg_get_covariance(const reg_handle* h, float cov[36], int32_t* rank) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->pm_on || !h->pm.with_cov || !h->pm_have_match || !h->pm_cov_valid) return REG_NOT_CONFIGURED;
+    if (cov) std::memcpy(cov, h->pm_cov_host.cov, sizeof(float) * 36);
+    if (rank) *rank = h->pm_cov_host.rank;
+    return REG_OK;
+}
+
+reg_status reg_get_covariance_sums(const reg_handle* h, double H[21], double M[21]) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->pm_on || !h->pm.with_cov || !h->pm_have_match || !h->pm_cov_valid) return REG_NOT_CONFIGURED;
+    if (H) std::memcpy(H, h->pm_cov_host.sums, sizeof(double) * 21);
+    if (M) std::memcpy(M, h->pm_cov_host.sums + 21, sizeof(double) * 21);
+    return REG_OK;
+}
+
+reg_status reg_host_censi_covariance(const double H[21], const double M[21], float sigma, float cov[36], int32_t* rank) {
+    if (!H || !M || !cov) return REG_BAD_ARGUMENT;
+    const int r = pmx_censi_covariance(H, M, (double)sigma, cov);
+    if (rank) *rank = r;
+    return REG_OK;
+}
+
+reg_status reg_get_minimizer_stats(reg_handle* h, reg_minimizer_stats* out) {
+    if (!h || !out || out->struct_size != (int32_t)sizeof(reg_minimizer_stats)) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    // a chain registration reads the chain's N x knn weights; the plain point-to-plane loop its N weights
+    const int knn = h->pm_on ? h->pm.knn : 1;
+    const int64_t n = h->n, nk = n * (int64_t)knn;
+    const bool chain_ok = h->pm_on && h->pm_have_match && h->pm_w.cap >= (size_t)nk * 4;
+    const bool plain_ok = !h->pm_on && h->prm.cost == REG_COST_P2PL && h->have_match && h->i_w.cap >= (size_t)n * 4;
+    if (nk <= 0 || (!chain_ok && !plain_ok)) {
+        h->err = "no point-to-plane registration has run on this reading";
+        return REG_NOT_CONFIGURED;
+    }
+    const float* kw = h->pm_on ? h->pm_w.as<float>() : h->i_w.as<float>();
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->pm_xrows.reserve((size_t)kPmxBlocks * kPmxCovSums * 8));
+    HIPCHK(h, h->pm_xmeans.reserve(kPmxRow * 8));
+    const int nb = pmx_blocks(n);
+    k_pmx_stats<<<nb, 256, 0, h->stream>>>(kw, n, knn, h->pm_xrows.as<double>());
+    k_pmx_reduce_rows<<<1, 256, 0, h->stream>>>(h->pm_xrows.as<double>(), nb, h->pm_xmeans.as<double>());
+    double t[kPmxRow];
+    HIPCHK(h, hipMemcpyAsync(t, h->pm_xmeans.p, sizeof(t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    out->returned_prior = (h->pm_x_valid && h->pm_xhost.returned_prior) ? 1 : 0;
+    out->point_used_ratio = t[1] / (double)nk;
+    out->weighted_point_used_ratio = t[0] / (double)nk;
+    out->overlap = out->weighted_point_used_ratio;
+    out->residual_error = h->pm_on ? h->pm_last_error : h->h_mirror->sums[27];
+    out->n_rejected_matches = (int64_t)llround(t[2]);
+    out->n_rejected_points = (int64_t)llround(t[3]);
+    return REG_OK;
+}
+
+reg_status reg_get_degeneracy(const reg_handle* h, int32_t categories[6], float eigenvalues[6], float* condition_number) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->pm_on || h->pm.degeneracy_method == REG_DEGENERACY_NONE || !h->pm_have_match || !h->pm_x_valid ||
+        !h->pm_xhost.sr_valid)
+        return REG_NOT_CONFIGURED;
+    for (int k = 0; k < 6; ++k) {
+        if (categories) categories[k] = h->pm_xhost.cat[k];
+        if (eigenvalues) eigenvalues[k] = h->pm_xhost.eig[k];
+    }
+    if (condition_number) *condition_number = h->pm_xhost.cond;
+    return REG_OK;
+}
+
+reg_status reg_get_bound(const reg_handle* h, float* rotation, float* translation) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->pm_on || !h->pm.use_bound || !h->pm_have_match || !h->pm_x_valid || !h->pm_xhost.bound_valid)
+        return REG_NOT_CONFIGURED;
+    if (rotation) *rotation = h->pm_xhost.bound_rot;
+    if (translation) *translation = h->pm_xhost.bound_trans;
+    return REG_OK;
+}
+
+reg_status reg_host_solution_remap(const float A[36], float threshold, int use2019, const double P_in[36], double P_out[36],
+                                   int32_t categories[6], float eigenvalues[6]) {
+    if (!A || !P_in || !P_out) return REG_BAD_ARGUMENT;
+    int cat[6];
+    float eig[6], cond;
+    const int prior = pmx_solution_remap(A, threshold, use2019, P_in, P_out, cat, eig, &cond);
+    for (int k = 0; k < 6; ++k) {
+        if (categories) categories[k] = cat[k];
+        if (eigenvalues) eigenvalues[k] = eig[k];
+    }
+    return prior ? REG_NO_CORRESPONDENCES : REG_OK;
 }
 
 reg_status reg_host_var_trim(const float* d2, int64_t n, float minRatio, float maxRatio, float lambda, int64_t* index,

@@ -193,6 +193,15 @@ struct reg_handle {
     // {sum, offset, best value, best index, counts} + VarState; sized by register_pm, never inside the loop
     DevBuf pm_sorted, pm_sort_tmp, pm_var;
     size_t pm_sort_bytes = 0;
+    // covariance / statistics / Bound / SolutionRemapping (kernels_pmextras.hpp): the device state of the modules, the rows
+    // of the post-loop reductions, their totals and the covariance result block; host copies of the last registration
+    DevBuf pm_xstate, pm_xrows, pm_xmeans, pm_xcov;
+    PmExtraState pm_xhost;
+    PmCovOut pm_cov_host;
+    bool pm_x_valid = false;      // pm_xhost belongs to the last chain registration on the current reading
+    bool pm_cov_valid = false;    // ... and pm_cov_host (a with_cov registration that ended with an update)
+    float pm_cov_ms = 0.f;        // device time of the covariance evaluation (HIP events)
+    double pm_last_error = 0.0;   // reg_result.error of the last chain registration
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
     DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;

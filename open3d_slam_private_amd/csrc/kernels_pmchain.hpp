@@ -9,7 +9,8 @@
 //   k_pm_scale                                  RobustOutlierFilter scale / iteration (state persists across registrations)
 //   [sort + k_pm_var_*]                         VarTrimmedDist limit (kernels_pmoutliers.hpp); one more select for MedianDist
 //   k_pm_linearize<kP2P>                        weights of the whole chain + per-workgroup fp64 partial sums
-//   k_pm_update                                 reduce, solve / Kabsch, T_iter <- dT T_iter, checkers, host mirror
+//   k_pm_update<kX>                             reduce, solve / Kabsch, T_iter <- dT T_iter, checkers, host mirror; kX: with
+//                                               SolutionRemapping / BoundTransformationChecker (kernels_pmextras.hpp)
 // Every kernel returns at once when the loop is done (enqueued iterations past convergence are no-ops).
 #pragma once
 
@@ -384,12 +385,24 @@ __device__ __noinline__ int pm_solve(const double* tot, bool p2p, float* dT) {
     return rank;
 }
 
+template <bool kX>
 __global__ void __launch_bounds__(256)
 k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host, unsigned long long seq,
-            PmState* __restrict__ ps, int p2p, int use_trim, int use_median) {
+            PmState* __restrict__ ps, int p2p, int use_trim, int use_median, PmExtraCfg xc, PmExtraState* __restrict__ xs,
+            int finish, XicpState* __restrict__ xq) {
     __shared__ double sh[8][kSums];
     __shared__ double tot[kSums];
     if (it->done) return;
+    if constexpr (kX) {
+        // R8x with a chain, second launch of the first iteration (after k_xicp_center / k_xicp_detect): the sums are the
+        // ones this kernel reduced before the analysis
+        if (finish) {
+            if (it->xicp_stage != 2) return;
+            if (threadIdx.x < kSums) tot[threadIdx.x] = it->sums[threadIdx.x];
+            __syncthreads();
+            n_blocks = 0;
+        }
+    }
     const int comp = threadIdx.x & (kSums - 1), part = threadIdx.x / kSums;   // 8 parts x 32 comps
     double t = 0;
     for (int b0 = part; b0 < n_blocks; b0 += 8 * 8) {
@@ -404,7 +417,7 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     }
     sh[part][comp] = t;
     __syncthreads();
-    if (threadIdx.x < kSums) {
+    if (threadIdx.x < kSums && !(kX && finish)) {
         double s = 0;
 #pragma unroll
         for (int p = 0; p < 8; ++p) s += sh[p][threadIdx.x];
@@ -415,6 +428,34 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     if (threadIdx.x != 0) return;
     float Tc[16];
     for (int i = 0; i < 16; ++i) Tc[i] = it->T[i];
+    if constexpr (kX) {
+        if (!finish && it->xicp_stage == 1 && xq != nullptr && ps->fail == 0 && tot[31] != 0.0 && tot[28] > 0.0 &&
+            !(use_trim && !(ps->sel[2] < INFINITY))) {
+            // R8x stage A as the plain loop's update kernel: eigen-directions of the two blocks of A in the frame the data
+            // came from; the analysis kernels collect the sums, then this kernel runs again (finish).  Nothing is reported.
+            upd_xicp_stage_a(tot, it->xicp_Trd, xq->vr, 0);
+            upd_xicp_stage_a(tot, it->xicp_Trd, xq->vt, 3);
+            for (int i = 0; i < 4; ++i) xq->center[i] = 0.0;
+            for (int i = 0; i < 6; ++i) {
+                xq->comb[i] = 0.0;
+                xq->high[i] = 0.0;
+            }
+            it->xicp_stage = 2;
+            return;
+        }
+        if (finish) {
+            int nc = 0;
+            for (int i = 0; i < 6; ++i) {
+                const int ok = (xq->comb[i] >= (double)it->xicp_enough || xq->high[i] >= (double)it->xicp_insufficient) ? 1 : 0;
+                it->xicp_flags[i] = ok;
+                it->xicp_comb[i] = xq->comb[i];
+                it->xicp_high[i] = xq->high[i];
+                nc += ok ? 0 : 1;
+            }
+            it->xicp_nc = nc;
+            it->xicp_stage = 0;
+        }
+    }
     const bool fail = ps->fail != 0 || (use_trim && !(ps->sel[2] < INFINITY)) || (use_median && !(ps->sel[3] < INFINITY));
     ps->fail = 0;
     for (int i = 0; i < 16; ++i) it->T_prev[i] = Tc[i];
@@ -423,13 +464,46 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
         it->done = 1;
     } else {
         float dT[16], Tn[16];
-        it->rank_last = pm_solve(tot, p2p != 0, dT);
-        m4_mul(dT, Tc, Tn);   // T_iter = real * T_iter (ICP.cpp:1213-1215)
-        for (int i = 0; i < 16; ++i) it->T[i] = Tn[i];
-        const int iters = it->iterations + 1;
-        it->iterations = iters;
-        const bool iterate = it->fixed_iters > 0 ? iters < it->fixed_iters : it->chk.check(Tn);
-        if (!iterate) it->done = 1;
+        bool prior = false;
+        if constexpr (kX) {
+            if (xc.degeneracy != 0) {
+                int rank = it->rank_last;
+                prior = pmx_solve_remap(tot, xc, xs, dT, &rank) != 0;
+                it->rank_last = rank;
+            } else if (it->xicp_nc > 0) {
+                // R8x: no update along the non-localizable eigen-directions of the CURRENT A (PointToPlane.cpp:459-505)
+                float x[6];
+                it->rank_last = upd_solve6_xicp(tot, it->xicp_flags, x);
+                x_to_T(x, dT);
+            } else {
+                it->rank_last = pm_solve(tot, p2p != 0, dT);
+            }
+        } else {
+            it->rank_last = pm_solve(tot, p2p != 0, dT);
+        }
+        if (prior) {
+            // the detection failed: the reference leaves the loop before the update and returns the prior
+            xs->returned_prior = 1;
+            it->done = 1;
+        } else {
+            m4_mul(dT, Tc, Tn);   // T_iter = real * T_iter (ICP.cpp:1213-1215)
+            for (int i = 0; i < 16; ++i) it->T[i] = Tn[i];
+            const int iters = it->iterations + 1;
+            it->iterations = iters;
+            const bool iterate = it->fixed_iters > 0 ? iters < it->fixed_iters : it->chk.check(Tn);
+            if (!iterate) it->done = 1;
+            if constexpr (kX) {
+                for (int i = 0; i < 16; ++i) xs->dT[i] = dT[i];
+                xs->have_dT = 1;
+                // checkers run in YAML order and an exception ends the pass: a Counter listed first that fires hides the bound
+                if (xc.use_bound && it->fixed_iters <= 0 && !(xc.bound_after_counter && it->chk.max_iter_reached)) {
+                    if (pmx_bound_check(Tn, xc, xs)) {
+                        it->status = REG_OUT_OF_BOUNDS;
+                        it->done = 1;
+                    }
+                }
+            }
+        }
     }
     for (int i = 0; i < kSums; ++i) host->sums[i] = tot[i];
     for (int i = 0; i < 16; ++i) {
@@ -444,6 +518,14 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     host->max_iter_reached = it->chk.max_iter_reached ? 1 : 0;
     host->stall = 0;
     host->band_count = 0;
+    if constexpr (kX) {
+        for (int i = 0; i < 6; ++i) {
+            host->localizable[i] = it->xicp_flags[i];
+            host->xicp_comb[i] = it->xicp_comb[i];
+            host->xicp_high[i] = it->xicp_high[i];
+        }
+        host->n_constraints = it->xicp_nc;
+    }
     HostMirror::SeqRecord* rec = &host->ring[seq % kSeqRing];
     rec->iterations = it->iterations;
     rec->done = it->done;

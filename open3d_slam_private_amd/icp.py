@@ -59,6 +59,8 @@ def _translate(e: RegError):
         return InvalidField(str(e))
     if e.status == 6:
         return InvalidParameter(str(e))
+    if e.status == capi.OUT_OF_BOUNDS:   # BoundTransformationChecker (TransformationCheckersImpl.cpp:217-224)
+        return ConvergenceError(str(e).split(": ", 1)[-1])
     return RuntimeError(str(e))
 
 
@@ -205,6 +207,7 @@ class ICP:
             self._set_reading(readingIn)
             T_out, res = self._reg.register(T)
         except RegError as e:
+            self.last_result = getattr(self._reg, "last_result", None)   # filled on REG_OUT_OF_BOUNDS as well
             raise _translate(e) from None
         self.last_result = res
         self.maxNumIterationsReached = bool(res.max_iter_reached)
@@ -220,12 +223,61 @@ class ICP:
         self._reg.set_source(readingIn.features, readingIn.normals, readingIn.covariances)
 
 
+class ErrorMinimizerView:
+    """The getters of PointMatcher<T>::ErrorMinimizer a caller reads after ICP::compute (ErrorMinimizer.cpp:249-285,
+    PointToPlane.cpp:780-930, PointToPlaneWithCov.cpp:165-169), for the last compute() of a PointMatcherICP."""
+
+    def __init__(self, icp: "PointMatcherICP"):
+        self._icp = icp
+
+    def _stats(self):
+        if self._icp._reg is None:
+            raise RuntimeError("no registration has run")
+        try:
+            return self._icp._reg.get_minimizer_stats()
+        except RegError as e:
+            raise _translate(e) from None
+
+    def getCovariance(self) -> np.ndarray:
+        """6x6, order [x y z alpha beta gamma]; the zero matrix unless the minimizer is PointToPlaneWithCovErrorMinimizer
+        (the base class, ErrorMinimizer.cpp:281-285)."""
+        chain = self._icp.chain
+        if chain is None or not chain.with_cov:
+            return np.zeros((6, 6), np.float32)
+        if self._icp._reg is None:
+            raise RuntimeError("no registration has run")
+        try:
+            return self._icp._reg.get_covariance()[0]
+        except RegError as e:
+            raise _translate(e) from None
+
+    def getOverlap(self) -> float:
+        return float(self._stats().overlap)
+
+    def getPointUsedRatio(self) -> float:
+        return float(self._stats().point_used_ratio)
+
+    def getWeightedPointUsedRatio(self) -> float:
+        return float(self._stats().weighted_point_used_ratio)
+
+    def getResidualError(self) -> float:
+        return float(self._stats().residual_error)
+
+
 class PointMatcherICP(ICP):
     """ICP with the libpointmatcher chain extension (include/o3dslam_reg.h, reg_set_pm_chain): loadFromYaml also takes
     KDTreeMatcher.knn up to 16, RobustOutlierFilter (OutlierFiltersImpl.h:230-244 names and defaults),
-    MinDistOutlierFilter, MedianDistOutlierFilter, VarTrimmedDistOutlierFilter (OutlierFiltersImpl.h:96-160) and
-    PointToPointErrorMinimizer; everything else binds exactly as for ICP.  The robust filter's scale / iteration persist
-    across compute() calls on the same object, as in the reference."""
+    MinDistOutlierFilter, MedianDistOutlierFilter, VarTrimmedDistOutlierFilter (OutlierFiltersImpl.h:96-160),
+    PointToPointErrorMinimizer, PointToPlaneWithCovErrorMinimizer (sensorStdDev), BoundTransformationChecker
+    (maxRotationNorm, maxTranslationNorm; its place relative to the Counter checker is kept) and degeneracyAwareness
+    SolutionRemapping (threshold, use2019); everything else binds exactly as for ICP.  The robust filter's scale /
+    iteration persist across compute() calls on the same object, as in the reference.  `errorMinimizer` holds the
+    minimizer's getters (covariance, overlap, ratios, residual) of the last compute().
+
+    PointToPlaneWithCovErrorMinimizer together with OptimizedEqualityConstraints: the reference runs the localizability
+    detection only when the minimizer's name is exactly PointToPlaneErrorMinimizer (ICP.cpp:1114,1138) and the flags
+    start as localizable (PointMatcher.h:638-639), so the constrained solve is the plain one; the parameters are
+    checked and the analysis is switched off (params.use_xicp = 0)."""
 
     _ROBUST_DEFAULTS = {"robustFct": "cauchy", "tuning": 1.0, "scaleEstimator": "mad", "nbIterationForScale": 0,
                         "distanceType": "point2point", "approximation": math.inf}
@@ -239,11 +291,12 @@ class PointMatcherICP(ICP):
 
     def __init__(self):
         super().__init__()
-        self.chain: capi.PmChain | None = None
+        self.chain: capi.PmChainV3 | None = None
         self.referenceDataPointsFilters: list = []
         self.readingDataPointsFilters: list = []   # reg_filter_points specs and OctreeGridDataPointsFilter steps
         self._dev: dict = {}
         self._read_stages: list = []
+        self.errorMinimizer = ErrorMinimizerView(self)
 
     def setDefault(self):
         super().setDefault()
@@ -259,7 +312,7 @@ class PointMatcherICP(ICP):
         doc = yaml.safe_load(text) or {}
         ref_filters = [_reference_filter(f) for f in (doc.pop("referenceDataPointsFilters", None) or [])]
         read_filters = [_reading_filter(f) for f in (doc.pop("readingDataPointsFilters", None) or [])]
-        chain = capi.default_pm_chain()
+        chain = capi.default_pm_chain_v3()
         m = doc.get("matcher")
         if isinstance(m, dict) and isinstance(m.get("KDTreeMatcher"), dict) and "knn" in m["KDTreeMatcher"]:
             chain.knn = int(m["KDTreeMatcher"]["knn"])
@@ -295,14 +348,81 @@ class PointMatcherICP(ICP):
         if "outlierFilters" in doc:
             doc["outlierFilters"] = kept
         em = doc.get("errorMinimizer", "PointToPlaneErrorMinimizer")
-        if (next(iter(em)) if isinstance(em, dict) else em) == "PointToPointErrorMinimizer":
+        (emname, emargs), = (em.items() if isinstance(em, dict) else [(em, {})])
+        emargs = emargs or {}
+        if emname == "PointToPointErrorMinimizer":
             chain.minimizer = capi.PM_POINT_TO_POINT
             doc["errorMinimizer"] = "PointToPlaneErrorMinimizer"
+        elif emname == "PointToPointWithCovErrorMinimizer":
+            raise NotImplementedError("PointToPointWithCovErrorMinimizer: its estimate sets normal = (1,1,1) "
+                                      "(PointToPointWithCov.cpp:77), so H is singular by construction and the result is "
+                                      "the output of an LU on a rank-deficient matrix")
+        elif emname == "PointToPlaneWithCovErrorMinimizer":
+            unknown = set(emargs) - {"sensorStdDev", "force2D", "force4DOF"}
+            if unknown:
+                raise InvalidParameter(f"PointToPlaneWithCovErrorMinimizer: unknown parameter(s) {sorted(unknown)}")
+            try:
+                chain.sensor_std_dev = float(emargs.get("sensorStdDev", 0.01))
+                forced = float(emargs.get("force2D", 0)) != 0 or float(emargs.get("force4DOF", 0)) != 0
+            except (TypeError, ValueError):
+                raise InvalidParameter("PointToPlaneWithCovErrorMinimizer: parameters must be numbers") from None
+            if forced:
+                raise NotImplementedError("PointToPlaneWithCovErrorMinimizer: force2D / force4DOF are outside the "
+                                          "accelerated path")
+            chain.with_cov = 1
+            doc["errorMinimizer"] = "PointToPlaneErrorMinimizer"
+        checkers, counter_seen = [], False
+        for c in doc.get("transformationCheckers") or []:
+            (cname, cargs), = (c.items() if isinstance(c, dict) else [(c, {})])
+            if cname == "CounterTransformationChecker":
+                counter_seen = True
+            if cname != "BoundTransformationChecker":
+                checkers.append(c)
+                continue
+            if chain.use_bound:
+                raise NotImplementedError("more than one BoundTransformationChecker")
+            cargs = cargs or {}
+            unknown = set(cargs) - {"maxRotationNorm", "maxTranslationNorm"}
+            if unknown:
+                raise InvalidParameter(f"BoundTransformationChecker: unknown parameter(s) {sorted(unknown)}")
+            try:
+                chain.max_rotation_norm = float(cargs.get("maxRotationNorm", 1.0))
+                chain.max_translation_norm = float(cargs.get("maxTranslationNorm", 1.0))
+            except (TypeError, ValueError):
+                raise InvalidParameter("BoundTransformationChecker: parameters must be numbers") from None
+            if not (chain.max_rotation_norm >= 0 and chain.max_translation_norm >= 0):
+                raise InvalidParameter("BoundTransformationChecker: maxRotationNorm / maxTranslationNorm must be >= 0")
+            chain.use_bound = 1
+            chain.bound_after_counter = 1 if counter_seen else 0
+        if "transformationCheckers" in doc:
+            doc["transformationCheckers"] = checkers
+        da = doc.get("degeneracyAwareness")
+        if da == "SolutionRemapping":
+            da = {"SolutionRemapping": None}
+        if isinstance(da, dict) and "SolutionRemapping" in da:
+            if len(da) != 1:
+                raise InvalidParameter("degeneracyAwareness: one method at a time")
+            dargs = da["SolutionRemapping"] or {}
+            if "threshold" not in dargs or "use2019" not in dargs:     # ICP.cpp:603-627
+                raise InvalidParameter("SolutionRemapping needs threshold, use2019")
+            unknown = set(dargs) - {"threshold", "use2019"}
+            if unknown:
+                raise InvalidParameter(f"SolutionRemapping: unknown parameter(s) {sorted(unknown)}")
+            try:
+                chain.sr_threshold = float(dargs["threshold"])
+                chain.sr_use2019 = 1 if float(dargs["use2019"]) == 1.0 else 0
+            except (TypeError, ValueError):
+                raise InvalidParameter("SolutionRemapping: parameters must be numbers") from None
+            chain.degeneracy_method = capi.DEGENERACY_SOLUTION_REMAPPING
+            doc.pop("degeneracyAwareness")
         super().loadFromYaml(yaml.safe_dump(doc))
+        if chain.with_cov and self.params.use_xicp:
+            self.params.use_xicp = 0   # the reference skips the detection for this minimizer (class docstring)
         st = capi.check_pm_chain(self.params, chain)
         if st == 9:
-            raise NotImplementedError("this chain is outside the accelerated path (std scale estimator, or X-ICP with "
-                                      "k-NN / robust weights / point-to-point / MinDist / MedianDist / VarTrimmedDist)")
+            raise NotImplementedError("this chain is outside the accelerated path (std scale estimator; X-ICP with "
+                                      "k-NN / robust weights / point-to-point / MinDist / MedianDist / VarTrimmedDist / "
+                                      "BoundTransformationChecker; SolutionRemapping or a covariance with point-to-point)")
         if st != 0:
             raise InvalidParameter("invalid chain (knn must lie in 1..16; a filter parameter out of range; "
                                    "VarTrimmedDistOutlierFilter: minRatio should be smaller than maxRatio)")
