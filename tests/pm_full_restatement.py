@@ -1,0 +1,244 @@
+"""The two restatement families of the libpointmatcher chain in one class, the factor table of the chain's modules with
+its pairwise covering set, and the last-iteration check shared by the GPU tests (a plain helper module, not a test).
+
+  FullChain / PmFullRestatement   tests/pm_extras_restatement.py (covariance, statistics, Bound, SolutionRemapping) over
+                                  tests/pm_outliers_restatement.py (MinDist, MedianDist, VarTrimmedDist) by cooperative
+                                  inheritance: PmExtrasRestatement.step calls self.weights, PmOutliersRestatement.weights
+                                  calls super().weights
+  FACTORS / covering_rows         the ten factors of DESIGN.md 5k and a deterministic greedy pairwise covering array
+  device_config / restated_chain  one row as (reg_pm_chain fields, reg_params fields) and as FullChain arguments
+  check_last_iteration            ids / d2 / weights / counts / getters of a registration's last iteration"""
+import functools
+import itertools
+import math
+
+import numpy as np
+
+from oracle import oracle as orc
+from open3d_slam_private_amd import capi
+from tests.oracle_side import _xf
+from tests.pm_chain_restatement import NT
+from tests.pm_extras_restatement import ExtrasChain, PmExtrasRestatement
+from tests.pm_outliers_restatement import (OutlierChain, PmOutliersRestatement, fork_rank, var_rank,
+                                           var_rank_is_near_optimal)
+
+f32 = np.float32
+EYE = np.eye(4, dtype=f32)
+
+
+class FullChain(ExtrasChain, OutlierChain):
+    """Every argument of Chain, ExtrasChain and OutlierChain."""
+
+
+class PmFullRestatement(PmExtrasRestatement, PmOutliersRestatement):
+    """register / step / covariance / stats of PmExtrasRestatement with the weights of PmOutliersRestatement."""
+
+
+# ---- the factor table ------------------------------------------------------------------------------------------------
+
+ROBUST_LEVELS = {
+    "off": None,
+    "cauchy/mad": dict(robust="cauchy", scale="mad", distance="point2point"),
+    "huber/berg": dict(robust="huber", scale="berg", distance="point2point"),
+    "tukey/none/p2plane": dict(robust="tukey", scale="none", distance="point2plane"),
+}
+FACTORS = {
+    "knn": [1, 3, 16],
+    "minimizer": ["point2plane", "point2point"],
+    "max_dist": [0.5, math.inf],
+    "trimmed": [None, 0.9],
+    "surface_normal": [None, 1.0],
+    "max_dist_filter": [None, 0.3],
+    "robust": list(ROBUST_LEVELS),
+    "min_dist": [None, 0.02],
+    "median": [None, 1.5],
+    "var": [None, (0.05, 0.99, 2.35)],
+}
+ALL_ON = dict(knn=16, minimizer="point2plane", max_dist=0.5, trimmed=0.9, surface_normal=1.0, max_dist_filter=0.3,
+              robust="cauchy/mad", min_dist=0.02, median=1.5, var=(0.05, 0.99, 2.35))
+TUNING = 1.0
+
+
+def device_config(row, **extra_chain):
+    """(fields of reg_pm_chain, fields of reg_params) of a row; extra_chain adds fields of the chain as they are."""
+    kw = dict(knn=row["knn"], minimizer=capi.PM_POINT_TO_POINT if row["minimizer"] == "point2point" else capi.PM_POINT_TO_PLANE)
+    pk = dict(max_dist=row["max_dist"], use_trimmed=0)
+    if row.get("trimmed") is not None:
+        pk.update(use_trimmed=1, trim_ratio=row["trimmed"])
+    if row.get("surface_normal") is not None:
+        pk.update(use_surface_normal=1, max_normal_angle=row["surface_normal"])
+    if row.get("max_dist_filter") is not None:
+        pk.update(use_max_dist_filter=1, outlier_max_dist=row["max_dist_filter"])
+    rb = ROBUST_LEVELS[row.get("robust", "off")]
+    if rb is not None:
+        kw.update(use_robust=1, robust_fct=capi.ROBUST_FCTS[rb["robust"]], tuning=TUNING,
+                  scale_estimator=capi.SCALE_ESTIMATORS[rb["scale"]], distance_type=capi.DISTANCE_TYPES[rb["distance"]],
+                  nb_iter_for_scale=row.get("nb_iter", 0))
+    if row.get("min_dist") is not None:
+        kw.update(use_min_dist_filter=1, outlier_min_dist=row["min_dist"])
+    if row.get("median") is not None:
+        kw.update(use_median_dist=1, median_factor=row["median"])
+    if row.get("var") is not None:
+        kw.update(use_var_trimmed=1, var_min_ratio=row["var"][0], var_max_ratio=row["var"][1], var_lambda=row["var"][2])
+    kw.update(extra_chain)
+    return kw, pk
+
+
+def restated_chain(row, **extra):
+    """The FullChain of a row; extra adds arguments of FullChain as they are."""
+    kw = dict(knn=row["knn"], minimizer=row["minimizer"], max_dist=row["max_dist"], trim_ratio=row.get("trimmed"),
+              max_normal_angle=row.get("surface_normal"), outlier_max_dist=row.get("max_dist_filter"),
+              min_dist=row.get("min_dist"), median_factor=row.get("median"), var_trim=row.get("var"))
+    rb = ROBUST_LEVELS[row.get("robust", "off")]
+    if rb is not None:
+        kw.update(rb, tuning=TUNING, nb_iter=row.get("nb_iter", 0))
+    kw.update(extra)
+    return FullChain(**kw)
+
+
+def device_structs(row, **extra_chain):
+    """(reg_params, reg_pm_chain) of a row, as reg_check_pm_chain and reg_create / reg_set_pm_chain take them."""
+    kw, pk = device_config(row, **extra_chain)
+    p = capi.default_params()
+    for k, v in pk.items():
+        setattr(p, k, v)
+    c = capi.default_pm_chain_v3()
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return p, c
+
+
+def row_name(row):
+    on = [f"knn{row['knn']}", "p2p" if row["minimizer"] == "point2point" else "p2pl",
+          "md" + ("inf" if math.isinf(row["max_dist"]) else str(row["max_dist"]))]
+    on += [n for n, k in (("trim", "trimmed"), ("sn", "surface_normal"), ("maxd", "max_dist_filter"), ("min", "min_dist"),
+                          ("med", "median"), ("var", "var")) if row.get(k) is not None]
+    if row.get("robust", "off") != "off":
+        on.append(row["robust"].replace("/", "_"))
+    return "-".join(on)
+
+
+def is_plain_loop(row):
+    """The row switches nothing of reg_pm_chain on (pm_chain_is_default, host_loop.hpp): the handle runs the plain loop."""
+    return (row["knn"] == 1 and row["minimizer"] == "point2plane" and row.get("robust", "off") == "off" and
+            row.get("min_dist") is None and row.get("median") is None and row.get("var") is None)
+
+
+def pairs_of(row):
+    """Every (factor, level, factor, level) of two different factors in a row, levels by their index in FACTORS."""
+    names = list(FACTORS)
+    idx = [FACTORS[n].index(row[n]) for n in names]
+    return {(a, idx[a], b, idx[b]) for a in range(len(names)) for b in range(a + 1, len(names))}
+
+
+def covering_rows():
+    """The all-on row, then rows picked greedily from the full factorial (in itertools.product order, the first of the
+    best): each covers the most level pairs not covered yet.  Plain construction: the same rows on every run.  A
+    combination that leaves reg_pm_chain at its defaults is the plain loop, not a chain, and is no candidate."""
+    names = list(FACTORS)
+    rows = [dict(ALL_ON)]
+    covered = set(pairs_of(rows[0]))
+    cand = [dict(zip(names, lv)) for lv in itertools.product(*FACTORS.values())]
+    cand = [r for r in cand if not is_plain_loop(r)]
+    cand_pairs = [pairs_of(r) for r in cand]
+    todo = set().union(*cand_pairs) - covered
+    while todo:
+        gain = [len(p & todo) for p in cand_pairs]
+        best = int(np.argmax(gain))
+        rows.append(cand[best])
+        todo -= cand_pairs[best]
+    return rows
+
+
+# ---- the last iteration of a device registration ---------------------------------------------------------------------
+
+def _T(a):
+    return np.array(a, f32).reshape(4, 4).T
+
+
+def check_last_iteration(reg, res, r, knn, max_dist, replay_first=False, trajectory=None):
+    """ids / d2 of the last iteration bit-exact against the oracle at T_iter_prev; the weights bit-exact against the
+    restatement (for VarTrimmedDist: evaluated at the device's own rank, which must be near-optimal).  Returns the
+    oracle's d2 and the device's (ratio, k, n) when the chain has a VarTrimmedDist.
+
+    The state RobustOutlierFilter carries from earlier iterations is replayed along `trajectory`: the device's own T_iter
+    of every iteration before the last, in order; None stands for a pose that was not recorded and is accepted only for a
+    filter whose scale does not depend on earlier iterations (replay_first = True: the identity alone, the pose of the first
+    iteration of a fixed_iters = 2 run).  After the last iteration the device's robust state must be the restatement's."""
+    ids, d2, w = reg.get_correspondences_k(knn)
+    Tp = _T(res.T_iter_prev)
+    if trajectory is None:
+        trajectory = [EYE] if replay_first else []
+    for Tk in trajectory:
+        if Tk is None:   # a pose the device did not record: the filter may carry nothing but its count across it
+            assert r.c.robust is not None and r.c.scale in ("mad", "none") and r.c.nb_iter == 0
+            r.iteration += 1
+            continue
+        ik, ek = orc.knn_k(r.tree, _xf(np.asarray(Tk, f32), r.rd), knn, max_dist=max_dist, n_threads=NT)
+        r.var_k = None
+        r.weights(np.asarray(Tk, f32), ik, ek)
+        assert not r.fail
+    oid, od2 = orc.knn_k(r.tree, _xf(Tp, r.rd), knn, max_dist=max_dist, n_threads=NT)
+    assert np.array_equal(ids, oid)
+    assert np.array_equal(d2.view(np.uint32), od2.view(np.uint32))
+    var = None
+    if r.c.var_trim is not None:
+        ratio, k, n = var = reg.get_var_trim()
+        assert n == od2.size
+        ok, excess = var_rank_is_near_optimal(od2, k, *r.c.var_trim)
+        print(f"  var: device k = {k}, restatement k = {var_rank(od2, *r.c.var_trim)}, fork (fp32 sequential) k = "
+              f"{fork_rank(od2, *r.c.var_trim)}, n = {n}, FRMS64(k) / min - 1 = {excess:.3e}")
+        assert ok, (k, var_rank(od2, *r.c.var_trim), excess)
+        r.var_k = k
+    ow = r.weights(Tp, oid, od2)
+    assert not r.fail
+    if var is not None:
+        assert f32(var[0]).view(np.uint32) == f32(r.last_var[1]).view(np.uint32)
+    assert np.array_equal(w.view(np.uint32), ow.view(np.uint32)), int((w != ow).sum())
+    assert res.n_inliers == int((ow != 0).sum())
+    if r.c.robust is not None and (trajectory or res.iterations == 1):
+        assert reg.robust_state() == (float(r.scale), r.iteration)
+    r.last = dict(ids=oid, d2=od2, w=ow, T_prev=Tp)
+    return od2, var
+
+
+# ---- the scale cases of DESIGN.md 5k ---------------------------------------------------------------------------------
+
+# more than 2^24 keys: N x knn with the float median index int(f32(n) * f32(0.5)) one above the integer index n // 2.
+# Above 2^24 fp32 holds even integers only, so the two part ways for n = 3 (mod 4), which no multiple of 16 is; knn 15
+# still runs the 16-wide matcher, and 1 118 485 x 15 = 16 777 275 is the first such count above 2^24 for it.
+BIG_N, BIG_KNN, BIG_M = 1_118_485, 15, 50_000
+BIG_KEYS = BIG_N * BIG_KNN
+# lambda 0.7 / 0.5: the minimum of the objective lies inside the candidate range on these inputs (with the default 2.35
+# it sits on the last candidate, which a scan that loses its offsets could still find)
+SCALE_ROW = dict(knn=16, minimizer="point2point", max_dist=0.5, trimmed=0.9, robust="cauchy/mad", min_dist=0.02, median=1.5,
+                 var=(0.05, 0.99, 0.7))
+ZERO_M, ZERO_KNN, ZERO_VAR = 300_000, 3, (0.05, 0.99, 0.5)
+
+
+@functools.lru_cache(maxsize=1)
+def scale_scene():
+    """200 k x knn 16 = 3.2 M keys: 1563 tiles of 2048, seven per thread of the single-workgroup scan."""
+    from open3d_slam_private_amd import synth
+    return synth.make_scene(200_000, 400_000, seed=3)
+
+
+@functools.lru_cache(maxsize=1)
+def zero_run_cloud():
+    """A reference that is also the reading: (xyz, normals)."""
+    from open3d_slam_private_amd import synth
+    sc = synth.make_scene(1000, ZERO_M, seed=6)
+    return sc.tgt_xyz, sc.tgt_nrm
+
+
+@functools.lru_cache(maxsize=1)
+def big_scene():
+    from open3d_slam_private_amd import synth
+    return synth.make_scene(BIG_N, BIG_M, seed=12)
+
+
+def first_iteration_d2(tgt, src, knn, max_dist):
+    """The oracle's (ids, d2) of the first iteration (T_iter = identity, centred frames, identity prior)."""
+    r = PmFullRestatement(tgt, None, FullChain(knn=knn, max_dist=max_dist))
+    r.set_reading(src)
+    return orc.knn_k(r.tree, _xf(EYE, r.rd), knn, max_dist=max_dist, n_threads=NT)
