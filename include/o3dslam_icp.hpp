@@ -51,9 +51,9 @@ public:
     ICP& operator=(const ICP&) = delete;
 
     // ICPChainBase::setDefault (ICP.cpp:100-113); drops a chain set by setPmChain (the default chain is knn 1, no robust filter)
-    void setDefault() { reg_default_params(&params_); has_chain_ = false; reset(); }
+    void setDefault() { reg_default_params(&params_); has_chain_ = false; has_ternary_ = false; reset(); }
     // the chain of open3d_slam_ros/param/icp.yaml (what Mapper loads through loadFromYaml); drops a setPmChain chain
-    void setShippedChain() { reg_shipped_params(&params_); has_chain_ = false; reset(); }
+    void setShippedChain() { reg_shipped_params(&params_); has_chain_ = false; has_ternary_ = false; reset(); }
     // direct access to the string-free parameter block (call before the first initReference)
     reg_params& parameters() { reset(); return params_; }
     // libpointmatcher chain extension (reg_set_pm_chain: k-NN matching, RobustOutlierFilter, PointToPoint, and the
@@ -66,6 +66,25 @@ public:
         has_chain_ = true;
         if (h_) check(reg_set_pm_chain(h_, &chain_));
         else ensure();
+    }
+
+    // degeneracyAwareness EqualityConstraints (X-ICP, ternary; reg_set_ternary_xicp): start from
+    // reg_default_ternary_xicp, set enabled = 1.  Kept and re-applied like the chain; not together with
+    // parameters().use_xicp or a SolutionRemapping chain (InvalidParameter).
+    void setTernaryXicp(const reg_ternary_xicp& t) {
+        ternary_ = t;
+        ternary_.struct_size = (int32_t)sizeof(reg_ternary_xicp);
+        has_ternary_ = true;
+        if (h_) check(reg_set_ternary_xicp(h_, &ternary_));
+        else ensure();
+    }
+    // its analysis of the last iteration of the last compute()
+    reg_ternary_xicp_result localizability() {
+        ensure();
+        reg_ternary_xicp_result r{};
+        r.struct_size = (int32_t)sizeof(reg_ternary_xicp_result);
+        check(reg_get_ternary_xicp(h_, &r));
+        return r;
     }
 
     // VarTrimmedDistOutlierFilter's "Optimized ratio" of the last iteration, the rank it came from and n = N knn
@@ -173,6 +192,16 @@ private:
                 throw InvalidParameter("reg_set_pm_chain: the chain does not fit the parameters (" + std::to_string((int)cs) + ") " + msg);
             }
         }
+        if (has_ternary_) {
+            const reg_status ts = reg_set_ternary_xicp(h_, &ternary_);
+            if (ts != REG_OK) {
+                const std::string msg = reg_last_error(h_);
+                reg_destroy(h_);
+                h_ = nullptr;
+                if (ts == REG_DEVICE_ERROR) throw DeviceError(msg);
+                throw InvalidParameter("reg_set_ternary_xicp: (" + std::to_string((int)ts) + ") " + msg);
+            }
+        }
     }
     void check(reg_status s) {
         if (s == REG_OK) return;
@@ -188,6 +217,8 @@ private:
     reg_params params_;
     reg_pm_chain chain_{};
     bool has_chain_ = false;
+    reg_ternary_xicp ternary_{};
+    bool has_ternary_ = false;
     reg_handle* h_ = nullptr;
     reg_result last_{};
     bool matcherIsInitialized_ = false;

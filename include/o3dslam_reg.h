@@ -572,6 +572,88 @@ REG_API reg_status reg_host_robust_weights(int32_t fct, float tuning, float scal
    *rank = rank of the cross-covariance.  REG_NO_CORRESPONDENCES when sums[28] == 0. */
 REG_API reg_status reg_host_pm_p2p_update(const double sums[32], double T_update[16], int32_t* rank);
 
+/* ---- degeneracyAwareness: EqualityConstraints (X-ICP, ternary; icp.yaml:56-67) -----------------------------------
+   A companion of the chain (the layout of reg_pm_chain and the meaning of degeneracy_method do not change).  With it on
+   the handle registers on the chain's generic iteration, also under the default chain, and EVERY iteration, after A, b
+   and the deltas are known and before the solve:
+     1. eigenvectors of the two 3x3 blocks of A, the data frame, the centre of the matched pairs and both alignment
+        vectors exactly as the first-iteration analysis of use_xicp (translation: the matched normal; rotation:
+        (p - centre) x n, normalised unless its norm is < 1), fp32 with one rounding per operation;
+     2. per eigen-direction k (rotation 0-2, translation 3-5) with a = |alignment . v_k|:  high = sum a over a >
+        cos(strong) (n_high pairs), combined = sum a over a >= cos(minimal) (n_combined pairs), fp64 sums over ALL pairs
+        (the reference stops adding once a direction is localizable: the terms are non-negative, so no decision changes,
+        only the reported sums of localizable directions are larger);
+     3. category, tested in this order:  combined >= high_information || high >= enough_information -> LOCALIZABLE;
+        combined >= enough_information -> PARTIAL_MIXED (sample: the n_combined pairs);  high >= insufficient_information
+        -> PARTIAL_HIGH (sample: the n_high pairs);  otherwise NONE (constraint value 0).  Every category but LOCALIZABLE
+        clears reg_result.localizable[k];
+     4. a partial direction's constraint value is v_k . x3, x3 the solution of the 3x3 problem over its sample in the
+        optimisation frame (translation: A3 = sum n n^T, b3 = -sum n r; rotation: A3 = sum c c^T, b3 = -sum c r with
+        c = p x n, r = n . (p - q); no weights; nine fp64 sums of fp32 products rounded once to fp32), solved by the
+        reference's sequence (partial-pivot LU in fp32, L^T L y = L^T P b3 in fp64, x3 = U^-1 y in fp32);
+     5. the solve is the KKT system of PointToPlane.cpp:484-503 with the constraint values as right-hand side (plain
+        solve when every direction is localizable).
+   The prior is returned (REG_OK, T_out = T_init, reg_minimizer_stats.returned_prior = 1) when a sample holds fewer pairs
+   than insufficient_information or more than there are pairs (ICP.cpp:1956-1967; with unit reference normals a <= 1 and
+   the ordered thresholds rule this out, normals longer than 1 -- nothing normalises them -- do not), and -- a deviation -- when a constraint
+   value is not finite (a singular U, e.g. exactly axis-aligned sample normals).  Further deviations: DESIGN.md 5l.
+   PARITY UNPINNED against the reference itself (its localizability unit tests are empty); pinned: device == restatement.
+   Runs with: point-to-plane, knn 1, the 0/1-weight outlier filters, the Bound checker, fixed_iters.  REG_UNSUPPORTED:
+   knn > 1, RobustOutlierFilter, point-to-point, with_cov, a cost other than REG_COST_P2PL; reg_dist_* refuse a handle
+   with it on.  REG_BAD_ARGUMENT: together with use_xicp or SolutionRemapping (two methods at once), thresholds that are
+   not finite or not ordered insufficient <= enough <= high, angles outside (0, 90], a wrong struct_size. */
+typedef enum {
+    REG_TERNARY_LOCALIZABLE = 0,
+    REG_TERNARY_PARTIAL_MIXED = 1,
+    REG_TERNARY_PARTIAL_HIGH = 2,
+    REG_TERNARY_NONE = 3
+} reg_ternary_category;
+typedef struct {
+    int32_t struct_size;               /* sizeof(reg_ternary_xicp) */
+    int32_t enabled;
+    float high_information;            /* highInformationThreshold (250 shipped) */
+    float enough_information;          /* enoughInformationThreshold (180) */
+    float insufficient_information;    /* insufficientInformationThreshold (35) */
+    float min_alignment_angle_deg;     /* point2NormalMinimalAlignmentAngleThreshold (80) */
+    float strong_alignment_angle_deg;  /* point2NormalStrongAlignmentAngleThreshold (45) */
+    int32_t reserved;
+} reg_ternary_xicp;
+typedef struct {
+    int32_t struct_size;               /* sizeof(reg_ternary_xicp_result), set by the caller */
+    int32_t iteration;                 /* 1-based number of the iteration the values belong to (taken at T_iter_prev) */
+    int32_t category[6];               /* reg_ternary_category */
+    int32_t sane;                      /* 0: the sanity rule failed (the prior was returned) */
+    int32_t reserved;
+    double combined[6], high[6];
+    int64_t n_combined[6], n_high[6];
+    int64_t n_pairs;
+    float constraint[6];               /* 0 unless partial */
+    double partial_sums[6][9];         /* 0-5 upper triangle of A3 row by row, 6-8 = -b3; zero unless partial */
+    float eigenvectors[2][9];          /* optimisation frame, [0] rotation, [1] translation; [3 * k + r] = component r of k */
+} reg_ternary_xicp_result;
+/* enabled = 0 and the shipped yaml's commented values (250, 180, 35, 80, 45) */
+REG_API void       reg_default_ternary_xicp(reg_ternary_xicp* t);
+/* A pure check (no device) of the method against the parameters and a chain (NULL: the default chain). */
+REG_API reg_status reg_check_ternary_xicp(const reg_params* p, const reg_pm_chain* c, const reg_ternary_xicp* t);
+/* Turn the method on (or off: NULL or enabled = 0).  A call that would leave an invalid pair (method, chain) fails and
+   leaves the handle unchanged; so does a later reg_set_pm_chain. */
+REG_API reg_status reg_set_ternary_xicp(reg_handle* h, const reg_ternary_xicp* t);
+/* The analysis of the last iteration.  REG_NOT_CONFIGURED unless the last registration on the current reading ran with
+   the method on and analysed at least one iteration. */
+REG_API reg_status reg_get_ternary_xicp(reg_handle* h, reg_ternary_xicp_result* out);
+/* Step 3 on the host, the same code as the device; *sane = 0 when the sanity rule fails.  Returns REG_BAD_ARGUMENT for a
+   params struct reg_check_ternary_xicp would refuse for its ranges. */
+REG_API reg_status reg_host_ternary_decide(const double combined[6], const double high[6], const int64_t n_combined[6],
+                                           const int64_t n_high[6], int64_t n_pairs, const reg_ternary_xicp* params,
+                                           int32_t category[6], int32_t* sane);
+/* Step 4 on the host, the same code as the device: sums9 as partial_sums above, v the eigenvector in the optimisation
+   frame.  Returns REG_NO_CORRESPONDENCES (and stores the value all the same) when the value is not finite. */
+REG_API reg_status reg_host_partial_constraint(const double sums9[9], const float v[3], float* value);
+/* reg_host_solve6_xicp with right-hand sides rhs[k] on the constraint rows of the directions with flags[k] == 0; all of
+   them zero gives reg_host_solve6_xicp's bits.  Returns the rank of the reduced system. */
+REG_API int  reg_host_solve6_xicp_rhs(const float A[36], const float b[6], const int32_t flags[6], const float rhs[6],
+                                      float x[6]);
+
 /* Launch plan of the persistent tail kernel (csrc/kernels_tail.hpp) for a reading of n points on a device with `cus`
    compute units: plan = {usable (0/1), workgroups, workgroups per XCD class, reading points per XCD class}.  Octet
    oc = (s >> 3) * plan[2] + (b >> 3) of XCD class x = b & 7 is, with tile == 0, octet oc of the class's contiguous share

@@ -194,6 +194,22 @@ class MinimizerStats(C.Structure):
                 ("n_rejected_matches", C.c_int64), ("n_rejected_points", C.c_int64)]
 
 
+class TernaryXicp(C.Structure):
+    """reg_ternary_xicp: degeneracyAwareness EqualityConstraints (X-ICP, ternary), a companion of the chain."""
+    _fields_ = [("struct_size", C.c_int32), ("enabled", C.c_int32), ("high_information", C.c_float),
+                ("enough_information", C.c_float), ("insufficient_information", C.c_float),
+                ("min_alignment_angle_deg", C.c_float), ("strong_alignment_angle_deg", C.c_float), ("reserved", C.c_int32)]
+
+
+class TernaryXicpResult(C.Structure):
+    """reg_ternary_xicp_result: the analysis of the last iteration (taken at T_iter_prev)."""
+    _fields_ = [("struct_size", C.c_int32), ("iteration", C.c_int32), ("category", C.c_int32 * 6), ("sane", C.c_int32),
+                ("reserved", C.c_int32), ("combined", C.c_double * 6), ("high", C.c_double * 6),
+                ("n_combined", C.c_int64 * 6), ("n_high", C.c_int64 * 6), ("n_pairs", C.c_int64),
+                ("constraint", C.c_float * 6), ("partial_sums", (C.c_double * 9) * 6), ("eigenvectors", (C.c_float * 9) * 2)]
+
+
+TERNARY_LOCALIZABLE, TERNARY_PARTIAL_MIXED, TERNARY_PARTIAL_HIGH, TERNARY_NONE = 0, 1, 2, 3
 PM_CHAIN_SIZE_V1 = 48   # REG_PM_CHAIN_SIZE_V1: the struct up to `reserved`, still accepted (the later fields off)
 PM_CHAIN_SIZE_V2 = 80   # REG_PM_CHAIN_SIZE_V2: the struct up to `var_lambda`, still accepted (covariance / Bound / SR off)
 DEGENERACY_NONE, DEGENERACY_SOLUTION_REMAPPING = 0, 1
@@ -220,6 +236,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_get_var_trim", "reg_host_var_trim",
            "reg_get_covariance", "reg_get_covariance_sums", "reg_host_censi_covariance", "reg_get_minimizer_stats",
            "reg_get_degeneracy", "reg_get_bound", "reg_host_solution_remap",
+           "reg_default_ternary_xicp", "reg_check_ternary_xicp", "reg_set_ternary_xicp", "reg_get_ternary_xicp",
+           "reg_host_ternary_decide", "reg_host_partial_constraint", "reg_host_solve6_xicp_rhs",
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks"]
 
@@ -336,6 +354,15 @@ def load_library():
     lib.reg_get_degeneracy.argtypes = [vp, vp, vp, pf]
     lib.reg_get_bound.argtypes = [vp, pf, pf]
     lib.reg_host_solution_remap.argtypes = [vp, C.c_float, C.c_int, vp, vp, vp, vp]
+    lib.reg_default_ternary_xicp.argtypes = [C.POINTER(TernaryXicp)]
+    lib.reg_default_ternary_xicp.restype = None
+    lib.reg_check_ternary_xicp.argtypes = [C.POINTER(RegParams), vp, C.POINTER(TernaryXicp)]
+    lib.reg_set_ternary_xicp.argtypes = [vp, C.POINTER(TernaryXicp)]
+    lib.reg_get_ternary_xicp.argtypes = [vp, C.POINTER(TernaryXicpResult)]
+    lib.reg_host_ternary_decide.argtypes = [vp, vp, vp, vp, i64, C.POINTER(TernaryXicp), vp, pi32]
+    lib.reg_host_partial_constraint.argtypes = [vp, vp, pf]
+    lib.reg_host_solve6_xicp_rhs.argtypes = [f32p, f32p, vp, f32p, f32p]
+    lib.reg_host_solve6_xicp_rhs.restype = C.c_int
     lib.reg_get_var_trim.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_host_var_trim.argtypes = [vp, i64, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int64), C.POINTER(C.c_float),
                                       C.POINTER(C.c_float)]
@@ -467,6 +494,54 @@ def default_pm_chain() -> PmChain:
 def check_pm_chain(params: RegParams, chain: PmChain) -> int:
     """reg_check_pm_chain status (0 = accepted) -- pure, no device."""
     return int(load_library().reg_check_pm_chain(C.byref(params), C.byref(chain)))
+
+
+def default_ternary_xicp(enabled=False) -> TernaryXicp:
+    """reg_default_ternary_xicp: the shipped yaml's commented EqualityConstraints values (250, 180, 35; 80, 45 degrees)."""
+    t = TernaryXicp()
+    load_library().reg_default_ternary_xicp(C.byref(t))
+    t.enabled = 1 if enabled else 0
+    return t
+
+
+def check_ternary_xicp(params: RegParams, chain, ternary: TernaryXicp) -> int:
+    """reg_check_ternary_xicp status (0 = accepted) -- pure, no device.  chain None: the default chain."""
+    return int(load_library().reg_check_ternary_xicp(C.byref(params), C.byref(chain) if chain is not None else None,
+                                                     C.byref(ternary)))
+
+
+def host_ternary_decide(combined, high, n_combined, n_high, n_pairs, params: TernaryXicp):
+    """reg_host_ternary_decide: (categories int32[6], sane bool) -- the device's decision on the host."""
+    c, h = np.ascontiguousarray(combined, np.float64).reshape(6), np.ascontiguousarray(high, np.float64).reshape(6)
+    nc, nh = np.ascontiguousarray(n_combined, np.int64).reshape(6), np.ascontiguousarray(n_high, np.int64).reshape(6)
+    cat, sane = np.zeros(6, np.int32), C.c_int32()
+    st = load_library().reg_host_ternary_decide(_ptr(c), _ptr(h), _ptr(nc), _ptr(nh), int(n_pairs), C.byref(params), _ptr(cat),
+                                                C.byref(sane))
+    if st != 0:
+        raise RegError(st, "reg_host_ternary_decide")
+    return cat, bool(sane.value)
+
+
+def host_partial_constraint(sums9, v):
+    """reg_host_partial_constraint: (value float32, finite bool) of one partial direction from its nine sums and its
+    eigenvector in the optimisation frame -- the device's code on the host."""
+    s = np.ascontiguousarray(sums9, np.float64).reshape(9)
+    vv = np.ascontiguousarray(v, np.float32).reshape(3)
+    val = C.c_float()
+    st = load_library().reg_host_partial_constraint(_ptr(s), _ptr(vv), C.byref(val))
+    if st not in (0, 3):
+        raise RegError(st, "reg_host_partial_constraint")
+    return np.float32(val.value), st == 0
+
+
+def host_solve6_xicp_rhs(A, b, flags, rhs):
+    """reg_host_solve6_xicp_rhs: (x float32[6], rank) with right-hand sides on the constraint rows."""
+    f = np.ascontiguousarray(flags, np.int32).reshape(6)
+    r = np.ascontiguousarray(rhs, np.float32).reshape(6)
+    x = np.zeros(6, np.float32)
+    rank = load_library().reg_host_solve6_xicp_rhs(_ptr(np.ascontiguousarray(A, np.float32).reshape(36)),
+                                                   _ptr(np.ascontiguousarray(b, np.float32).reshape(6)), _ptr(f), _ptr(r), _ptr(x))
+    return x, int(rank)
 
 
 def host_robust_weights(fct, tuning, scale, d2, approximation=math.inf):
@@ -939,6 +1014,20 @@ class Registration:
             chain.struct_size = C.sizeof(type(chain))   # PmChain (REG_PM_CHAIN_SIZE_V2) or PmChainV3
         self.pm_chain = chain
         self._check(self._lib.reg_set_pm_chain(self._h, C.byref(chain) if chain is not None else None))
+
+    def set_ternary_xicp(self, ternary: "TernaryXicp | None"):
+        """reg_set_ternary_xicp: None (or enabled = 0) turns EqualityConstraints off."""
+        if ternary is not None:
+            ternary.struct_size = C.sizeof(TernaryXicp)
+        self._check(self._lib.reg_set_ternary_xicp(self._h, C.byref(ternary) if ternary is not None else None))
+        self.ternary_xicp = ternary
+
+    def get_ternary_xicp(self) -> TernaryXicpResult:
+        """reg_get_ternary_xicp: the EqualityConstraints analysis of the last iteration."""
+        out = TernaryXicpResult()
+        out.struct_size = C.sizeof(TernaryXicpResult)
+        self._check(self._lib.reg_get_ternary_xicp(self._h, C.byref(out)))
+        return out
 
     def get_correspondences_k(self, knn=None, want_w=True):
         """(ids, d2, w) of the last iteration, each n x knn, reading input order, ascending (d2, id)."""

@@ -800,7 +800,25 @@ static reg_status enqueue_pm_iteration(reg_handle* h) {
                                                          h->pm_state.as<PmState>(), h->pm_w.as<float>(), h->pm_partials.as<double>());
     ++h->seq;
     const PmExtraCfg xc = make_pm_extra_cfg(h);
-    if (pm_chain_has_extras(&c))
+    if (h->xt_on) {
+        // EqualityConstraints: the analysis of THIS iteration between two launches of the update kernel; the partial-sums
+        // kernel is always enqueued and gated on the device (kernels_xicp_ternary.hpp)
+        XtState* xt = h->xt_state.as<XtState>();
+        double* rows = h->xt_rows.as<double>();
+        const float* kw = h->pm_w.as<float>();
+        const int nb = (int)std::max<int64_t>(1, std::min<int64_t>(kXtBlocks, grid_for(n)));
+        IterState* itw = h->i_iter.as<IterState>();
+        k_pm_update<true, true><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, itw, h->d_mirror, h->seq,
+                                                          h->pm_state.as<PmState>(), 0, cfg.use_trim, cfg.use_median, xc,
+                                                          h->pm_xstate.as<PmExtraState>(), 0, nullptr, xt, rows, nb);
+        k_xt_center<<<nb, 256, 0, h->stream>>>(src, n, it, kpos, kw, xt, rows);
+        k_xt_detect<<<nb, 256, 0, h->stream>>>(src, n, it, kpos, kw, tnrm, xt, rows);
+        k_xt_decide<<<1, 256, 0, h->stream>>>(it, xt, rows, nb);
+        k_xt_partial<<<nb, 256, 0, h->stream>>>(src, n, it, kpos, kw, h->t_pts.as<float4>(), tnrm, xt, rows);
+        k_pm_update<true, true><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, itw, h->d_mirror, h->seq,
+                                                          h->pm_state.as<PmState>(), 0, cfg.use_trim, cfg.use_median, xc,
+                                                          h->pm_xstate.as<PmExtraState>(), 1, nullptr, xt, rows, nb);
+    } else if (pm_chain_has_extras(&c))
         k_pm_update<true><<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
                                                     h->pm_state.as<PmState>(), c.minimizer == REG_PM_POINT_TO_POINT ? 1 : 0,
                                                     cfg.use_trim, cfg.use_median, xc, h->pm_xstate.as<PmExtraState>(), 0,
@@ -888,9 +906,10 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
         HIPCHK(h, h->pm_sort_tmp.reserve(std::max<size_t>(need, 16)));
         h->pm_sort_bytes = need;
     }
-    const bool extras = pm_chain_has_extras(&h->pm);
+    const bool extras = pm_chain_has_extras(&h->pm) || h->xt_on;
     h->pm_x_valid = false;
     h->pm_cov_valid = false;
+    h->xt_valid = false;
     if (extras) {
         // P = identity and clear flags, as the reference's per-registration local (PointMatcher.h:645)
         HIPCHK(h, h->pm_xstate.reserve(sizeof(PmExtraState)));
@@ -906,6 +925,26 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     s = build_iter_state(h, T_start, 1, &st0);
     if (s != REG_OK) return s;
     st0.use_trim = 0;   // the chain's own selects; no band prediction
+    if (h->xt_on) {
+        HIPCHK(h, h->xt_state.reserve(sizeof(XtState)));
+        HIPCHK(h, h->xt_rows.reserve(kXtRowsTotal * 8));
+        XtState& x = h->xt_host;
+        std::memset(&x, 0, sizeof(XtState));
+        x.high_thr = h->xt.high_information;
+        x.enough_thr = h->xt.enough_information;
+        x.insufficient_thr = h->xt.insufficient_information;
+        x.cos_min = (float)std::cos((double)h->xt.min_alignment_angle_deg * 3.14159265358979323846 / 180.0);
+        x.cos_strong = (float)std::cos((double)h->xt.strong_alignment_angle_deg * 3.14159265358979323846 / 180.0);
+        // T_refMean_dataIn = T_refIn_refMean^-1 * T_init, as build_iter_state forms it for the first-iteration analysis
+        float A[16], Trd[16];
+        m4_identity(A);
+        for (int k = 0; k < 3; ++k) A[4 * k + 3] = -h->c_ref[k];
+        m4_mul(A, h->T_init, Trd);
+        for (int k = 0; k < 12; ++k) x.Trd[k] = Trd[k];
+        x.sane = 1;
+        HIPCHK(h, hipMemcpyAsync(h->xt_state.p, &x, sizeof(XtState), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
     s = prepare_rowmajor(h, Ti, nullptr, 0, &st0);
     if (s != REG_OK) return s;
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
@@ -940,11 +979,11 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     const double* sums = mir->sums;
     res->iterations = mir->iterations;
     for (int k = 0; k < 6; ++k) {
-        res->localizable[k] = h->prm.use_xicp ? mir->localizable[k] : 1;
-        res->xicp_combined[k] = h->prm.use_xicp ? mir->xicp_comb[k] : 0.0;
-        res->xicp_high[k] = h->prm.use_xicp ? mir->xicp_high[k] : 0.0;
+        res->localizable[k] = (h->prm.use_xicp || h->xt_on) ? mir->localizable[k] : 1;
+        res->xicp_combined[k] = (h->prm.use_xicp || h->xt_on) ? mir->xicp_comb[k] : 0.0;
+        res->xicp_high[k] = (h->prm.use_xicp || h->xt_on) ? mir->xicp_high[k] : 0.0;
     }
-    res->n_constraints = h->prm.use_xicp ? mir->n_constraints : 0;
+    res->n_constraints = (h->prm.use_xicp || h->xt_on) ? mir->n_constraints : 0;
     res->converged = mir->converged;
     res->max_iter_reached = mir->max_iter_reached;
     res->rank_last = mir->rank_last;
@@ -959,6 +998,10 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     if (extras) {
         HIPCHK(h, hipMemcpy(&h->pm_xhost, h->pm_xstate.p, sizeof(PmExtraState), hipMemcpyDeviceToHost));
         h->pm_x_valid = true;
+    }
+    if (h->xt_on) {
+        HIPCHK(h, hipMemcpy(&h->xt_host, h->xt_state.p, sizeof(XtState), hipMemcpyDeviceToHost));
+        h->xt_valid = true;
     }
     if (mir->status == REG_OUT_OF_BOUNDS) {
         // BoundTransformationChecker threw: T_out stays T_init (set by reg_register), the offending pose is reported
@@ -979,7 +1022,8 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     row_to_col(T_iter, res->T_iter_last);
     row_to_col(mir->T_prev, res->T_iter_prev);
     if (extras && h->pm_xhost.returned_prior) {
-        // SolutionRemapping could not detect: the prior is returned as it came in (reg_register copied it to T_out)
+        // the detection failed (SolutionRemapping / EqualityConstraints): the prior is returned as it came in
+        // (reg_register copied it to T_out)
     } else {
         compose_rowmajor(h, T_iter, Tout_row, /*later_kernel_reported=*/true);
         row_to_col(Tout_row, T_out);
@@ -1550,7 +1594,15 @@ reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c) {
     } else {
         reg_default_pm_chain(&nc);
     }
-    const bool on = !pm_chain_is_default(&nc);
+    if (h->xt_on) {
+        // the pair (EqualityConstraints, chain) must stay valid: otherwise nothing changes
+        const reg_status s = reg_check_ternary_xicp(&h->prm, &nc, &h->xt);
+        if (s != REG_OK) {
+            h->err = "reg_set_pm_chain: this chain does not run with EqualityConstraints (reg_set_ternary_xicp)";
+            return s;
+        }
+    }
+    const bool on = !pm_chain_is_default(&nc) || h->xt_on;
     const reg_pm_chain old = h->pm;
     const bool old_on = h->pm_on;
     h->pm = nc;
@@ -1565,6 +1617,132 @@ reg_status reg_set_pm_chain(reg_handle* h, const reg_pm_chain* c) {
     h->have_match = false;   // the buffers of the last iteration belong to the previous chain
     h->pm_have_match = false;
     return write_pm_state(h);
+}
+
+void reg_default_ternary_xicp(reg_ternary_xicp* t) {
+    std::memset(t, 0, sizeof(*t));
+    t->struct_size = (int32_t)sizeof(reg_ternary_xicp);
+    t->enabled = 0;
+    t->high_information = 250.f;           // icp.yaml:56-67
+    t->enough_information = 180.f;
+    t->insufficient_information = 35.f;
+    t->min_alignment_angle_deg = 80.f;
+    t->strong_alignment_angle_deg = 45.f;
+}
+
+static bool ternary_ranges_ok(const reg_ternary_xicp* t) {
+    if (t->struct_size != (int32_t)sizeof(reg_ternary_xicp)) return false;
+    const float hi = t->high_information, en = t->enough_information, in = t->insufficient_information;
+    if (!std::isfinite(hi) || !std::isfinite(en) || !std::isfinite(in)) return false;
+    if (!(in <= en && en <= hi)) return false;
+    const float a = t->min_alignment_angle_deg, b = t->strong_alignment_angle_deg;
+    return a > 0.f && a <= 90.f && b > 0.f && b <= 90.f;   // NaN fails
+}
+
+reg_status reg_check_ternary_xicp(const reg_params* p, const reg_pm_chain* c_in, const reg_ternary_xicp* t) {
+    if (!p || !t) return REG_BAD_ARGUMENT;
+    if (!ternary_ranges_ok(t)) return REG_BAD_ARGUMENT;
+    reg_pm_chain full;
+    if (c_in) {
+        if (!pm_chain_read(c_in, &full)) return REG_BAD_ARGUMENT;
+    } else {
+        reg_default_pm_chain(&full);
+    }
+    if (!t->enabled) return REG_OK;
+    if (p->use_xicp || full.degeneracy_method != REG_DEGENERACY_NONE) return REG_BAD_ARGUMENT;   // two methods at once
+    if (p->cost != REG_COST_P2PL) return REG_UNSUPPORTED;
+    if (full.knn != 1 || full.use_robust || full.minimizer != REG_PM_POINT_TO_PLANE || full.with_cov) return REG_UNSUPPORTED;
+    return REG_OK;
+}
+
+reg_status reg_set_ternary_xicp(reg_handle* h, const reg_ternary_xicp* t) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    reg_ternary_xicp nt;
+    reg_default_ternary_xicp(&nt);
+    reg_pm_chain chain = h->pm;
+    if (!h->pm_on) reg_default_pm_chain(&chain);   // no chain set: the default chain (the chain loop reads it)
+    if (t) {
+        const reg_status s = reg_check_ternary_xicp(&h->prm, &chain, t);
+        if (s != REG_OK) {
+            h->err = "reg_set_ternary_xicp: the method does not run with these parameters / this chain (include/o3dslam_reg.h)";
+            return s;
+        }
+        nt = *t;
+    }
+    const bool on = nt.enabled != 0;
+    if (on && h->m > 0 && !h->has_tnrm) {
+        h->err = "InvalidField: the reference was set without normals; EqualityConstraints needs them";
+        return REG_MISSING_FIELD;
+    }
+    // the robust state first: a device failure there leaves the handle as it was
+    const reg_status ws = write_pm_state(h);
+    if (ws != REG_OK) return ws;
+    h->pm = chain;
+    h->xt = nt;
+    h->xt_on = on;
+    h->xt_valid = false;
+    h->pm_on = on || !pm_chain_is_default(&chain);
+    h->have_match = false;   // the buffers of the last iteration belong to the previous configuration
+    h->pm_have_match = false;
+    return REG_OK;
+}
+
+reg_status reg_get_ternary_xicp(reg_handle* h, reg_ternary_xicp_result* out) {
+    if (!h || !out || out->struct_size != (int32_t)sizeof(reg_ternary_xicp_result)) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (!h->xt_on || !h->pm_have_match || !h->xt_valid || !h->xt_host.valid) return REG_NOT_CONFIGURED;
+    const XtState& x = h->xt_host;
+    std::memset(out, 0, sizeof(*out));
+    out->struct_size = (int32_t)sizeof(reg_ternary_xicp_result);
+    out->iteration = x.iteration;
+    out->sane = x.sane;
+    out->n_pairs = (int64_t)x.n_pairs;
+    for (int k = 0; k < 6; ++k) {
+        out->category[k] = x.cat[k];
+        out->combined[k] = x.comb[k];
+        out->high[k] = x.high[k];
+        out->n_combined[k] = (int64_t)x.n_comb[k];
+        out->n_high[k] = (int64_t)x.n_high[k];
+        out->constraint[k] = x.constraint[k];
+        for (int c = 0; c < 9; ++c) out->partial_sums[k][c] = x.psums[9 * k + c];
+    }
+    for (int k = 0; k < 9; ++k) {
+        out->eigenvectors[0][k] = x.vo[k];
+        out->eigenvectors[1][k] = x.vo[9 + k];
+    }
+    return REG_OK;
+}
+
+reg_status reg_host_ternary_decide(const double combined[6], const double high[6], const int64_t n_combined[6],
+                                   const int64_t n_high[6], int64_t n_pairs, const reg_ternary_xicp* params,
+                                   int32_t category[6], int32_t* sane) {
+    if (!combined || !high || !n_combined || !n_high || !params || !category) return REG_BAD_ARGUMENT;
+    if (!ternary_ranges_ok(params)) return REG_BAD_ARGUMENT;
+    long long nc[6], nh[6];
+    int cat[6];
+    for (int k = 0; k < 6; ++k) {
+        nc[k] = (long long)n_combined[k];
+        nh[k] = (long long)n_high[k];
+    }
+    const int ok = xicp_ternary_decide(combined, high, nc, nh, (long long)n_pairs, params->high_information,
+                                       params->enough_information, params->insufficient_information, cat);
+    for (int k = 0; k < 6; ++k) category[k] = cat[k];
+    if (sane) *sane = ok;
+    return REG_OK;
+}
+
+reg_status reg_host_partial_constraint(const double sums9[9], const float v[3], float* value) {
+    if (!sums9 || !v || !value) return REG_BAD_ARGUMENT;
+    const float val = xicp_partial_constraint(sums9, v);
+    *value = val;
+    return std::isfinite(val) ? REG_OK : REG_NO_CORRESPONDENCES;
+}
+
+int reg_host_solve6_xicp_rhs(const float A[36], const float b[6], const int32_t flags[6], const float rhs[6], float x[6]) {
+    int f[6];
+    for (int k = 0; k < 6; ++k) f[k] = flags[k];
+    return solve6_xicp_rhs(A, b, f, rhs, x);
 }
 
 reg_status reg_get_robust_state(const reg_handle* h, float* scale, int32_t* iteration) {

@@ -249,25 +249,41 @@ O3D_HD inline void xicp_eigvecs(const float* A, double* Vr, double* Vt) {
     eig3_desc(St, Vt);
 }
 
-// Equality-constrained solve: no update along the non-localizable eigen-directions (flags[k] == 0).  Null-space form
-// of the reference's (6+c)x(6+c) KKT system: x = Z (Z^T A Z)^-1 Z^T b with Z = the localizable eigenvectors.
-O3D_HD inline int solve6_xicp(const float* A, const float* b, const int* flags, float* x) {
-    double Vr[9], Vt[9], Z[36];
+// Equality-constrained solve: v_k . x = rhs[k] along the non-localizable eigen-directions (flags[k] == 0).  Null-space form
+// of the reference's (6+c)x(6+c) KKT system: x = N d + Z y with N the constrained eigenvectors, d their right-hand sides,
+// Z the localizable ones and Z^T A Z y = Z^T (b - A N d).  kRhs = false is the constraint value 0 of the optimised method
+// (x = Z (Z^T A Z)^-1 Z^T b; rhs is not read); with kRhs = true an all-zero rhs returns the same bits: N d and A N d are
+// then +0, and adding +0 changes no term (tests/test_xicp_ternary_host.py).
+template <bool kRhs>
+O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* flags, const float* rhs, float* x) {
+    double Vr[9], Vt[9], Z[36], xn[6] = {0, 0, 0, 0, 0, 0};
     xicp_eigvecs(A, Vr, Vt);
     int m = 0;
     for (int k = 0; k < 3; ++k)
         if (flags[k]) {
             for (int r = 0; r < 6; ++r) Z[6 * r + m] = r < 3 ? Vr[3 * r + k] : 0.0;
             ++m;
+        } else if (kRhs) {
+            for (int r = 0; r < 3; ++r) xn[r] += Vr[3 * r + k] * (double)rhs[k];
         }
     for (int k = 0; k < 3; ++k)
         if (flags[3 + k]) {
             for (int r = 0; r < 6; ++r) Z[6 * r + m] = r >= 3 ? Vt[3 * (r - 3) + k] : 0.0;
             ++m;
+        } else if (kRhs) {
+            for (int r = 0; r < 3; ++r) xn[3 + r] += Vt[3 * r + k] * (double)rhs[3 + k];
         }
-    for (int i = 0; i < 6; ++i) x[i] = 0.f;
+    for (int i = 0; i < 6; ++i) x[i] = kRhs ? (float)xn[i] : 0.f;
     if (m == 0) return 0;
-    double AZ[36], M[36], V[36], lam[6], g[6];
+    double AZ[36], M[36], V[36], lam[6], g[6], bb[6];
+    for (int i = 0; i < 6; ++i) {
+        bb[i] = (double)b[i];
+        if (kRhs) {
+            double t = 0;
+            for (int j = 0; j < 6; ++j) t += 0.5 * ((double)A[6 * i + j] + (double)A[6 * j + i]) * xn[j];
+            bb[i] = (double)b[i] - t;
+        }
+    }
     for (int i = 0; i < 6; ++i)
         for (int c = 0; c < m; ++c) {
             double t = 0;
@@ -281,7 +297,7 @@ O3D_HD inline int solve6_xicp(const float* A, const float* b, const int* flags, 
             M[m * a + c] = t;
         }
         double t = 0;
-        for (int i = 0; i < 6; ++i) t += Z[6 * i + a] * (double)b[i];
+        for (int i = 0; i < 6; ++i) t += Z[6 * i + a] * bb[i];
         g[a] = t;
     }
     for (int a = 0; a < m; ++a)
@@ -305,11 +321,153 @@ O3D_HD inline int solve6_xicp(const float* A, const float* b, const int* flags, 
         for (int a = 0; a < m; ++a) y[a] += V[m * a + k] * vb;
     }
     for (int i = 0; i < 6; ++i) {
-        double t = 0;
+        double t = kRhs ? xn[i] : 0.0;
         for (int c = 0; c < m; ++c) t += Z[6 * i + c] * y[c];
         x[i] = (float)t;
     }
     return rank;
+}
+O3D_HD inline int solve6_xicp(const float* A, const float* b, const int* flags, float* x) {
+    return solve6_xicp_impl<false>(A, b, flags, nullptr, x);
+}
+// ... with right-hand sides on the constraint rows (EqualityConstraints: the constraint values of partial directions)
+O3D_HD inline int solve6_xicp_rhs(const float* A, const float* b, const int* flags, const float* rhs, float* x) {
+    return solve6_xicp_impl<true>(A, b, flags, rhs, x);
+}
+
+// ---- X-ICP ternary EqualityConstraints (ICP.cpp:1698-2125, 2504-2795; PointToPlane.cpp:459-505, 570-626) ----------
+// Shared by the device (kernels_xicp_ternary.hpp, k_pm_update) and the reg_host_* entry points: the same code.
+// Deviations from the reference, all documented in DESIGN.md 5l:
+//   * the 3x3 partial problem is built from fp64 sums of fp32 products rounded once to fp32, where the reference runs
+//     Eigen's fp32 GEMM over the sampled cloud;
+//   * the fp64 least-squares step uses the project's Jacobi eigen-solver in place of Eigen's JacobiSVD;
+//   * the eigenvector of the constraint value is taken in the optimisation frame directly, before the round trip through
+//     the data frame the reference makes (two fp32 rotations that cancel up to rounding);
+//   * a constraint value that is not finite (a singular U) ends the registration as a failed detection (prior returned)
+//     where the reference would carry the NaN into the solve.
+constexpr int kXtLocalizable = 0, kXtPartialMixed = 1, kXtPartialHigh = 2, kXtNone = 3;
+
+// Category of the six eigen-directions from both alignment sums and their pair counts.  The order of the tests is the
+// reference's (decideLocalizabilityLevel).  Returns 0 when the sanity rule (ICP.cpp:1956-1967) fails for the sample of a
+// partial direction: fewer pairs than the insufficient threshold, or more than there are pairs.
+O3D_HD inline int xicp_ternary_decide(const double* comb, const double* high, const long long* n_comb, const long long* n_high,
+                                      long long n_pairs, float high_thr, float enough_thr, float insufficient_thr, int* cat) {
+    int sane = 1;
+    for (int k = 0; k < 6; ++k) {
+        long long sample = -1;
+        if (comb[k] >= (double)high_thr || high[k] >= (double)enough_thr) {
+            cat[k] = kXtLocalizable;
+        } else if (comb[k] >= (double)enough_thr) {
+            cat[k] = kXtPartialMixed;
+            sample = n_comb[k];
+        } else if (high[k] >= (double)insufficient_thr) {
+            cat[k] = kXtPartialHigh;
+            sample = n_high[k];
+        } else {
+            cat[k] = kXtNone;
+        }
+        if (sample >= 0 && ((double)sample < (double)insufficient_thr || sample > n_pairs)) sane = 0;
+    }
+    return sane;
+}
+
+// cofactor_3x3<i, j> of Eigen's Inverse_impl.h on a row-major 3x3
+O3D_HD inline float xicp_cof3(const float* m, int i, int j) {
+    const int i1 = (i + 1) % 3, i2 = (i + 2) % 3, j1 = (j + 1) % 3, j2 = (j + 2) % 3;
+    const float p = m[3 * i1 + j1] * m[3 * i2 + j2], q = m[3 * i1 + j2] * m[3 * i2 + j1];
+    return p - q;
+}
+
+// Constraint value of one partial direction from the nine sums of its sample (0-5: upper triangle of A3 row by row,
+// 6-8: sum of f r with f the normal (translation) or p x n (rotation); b3 = -that) and its eigenvector v in the
+// optimisation frame.  solveSimpleOptimizationProblemForPartialConstraints: partial-pivot LU of A3 in fp32 (Eigen's
+// unblocked order), new_A = L^T L, new_b = L^T (P b3) in fp32, y = least squares of new_A y = new_b in fp64 rounded to
+// fp32, x3 = U^-1 y with the 3x3 cofactor inverse in fp32, value = v . x3.  A singular U gives a value that is not finite.
+O3D_HD inline float xicp_partial_constraint(const double* s, const float* v) {
+    float a00 = (float)s[0], a01 = (float)s[1], a02 = (float)s[2], a11 = (float)s[3], a12 = (float)s[4], a22 = (float)s[5];
+    float m0[3] = {a00, a01, a02}, m1[3] = {a01, a11, a12}, m2[3] = {a02, a12, a22};
+    float b0 = -(float)s[6], b1 = -(float)s[7], b2 = -(float)s[8];
+    // column 0
+    {
+        int piv = 0;
+        float big = fabsf(m0[0]);
+        if (fabsf(m1[0]) > big) { big = fabsf(m1[0]); piv = 1; }
+        if (fabsf(m2[0]) > big) { big = fabsf(m2[0]); piv = 2; }
+        if (piv == 1) {
+            for (int c = 0; c < 3; ++c) { const float t = m0[c]; m0[c] = m1[c]; m1[c] = t; }
+            const float t = b0; b0 = b1; b1 = t;
+        } else if (piv == 2) {
+            for (int c = 0; c < 3; ++c) { const float t = m0[c]; m0[c] = m2[c]; m2[c] = t; }
+            const float t = b0; b0 = b2; b2 = t;
+        }
+        if (big != 0.f) {
+            m1[0] = m1[0] / m0[0];
+            m2[0] = m2[0] / m0[0];
+        }
+        float t;
+        t = m1[0] * m0[1]; m1[1] = m1[1] - t;
+        t = m1[0] * m0[2]; m1[2] = m1[2] - t;
+        t = m2[0] * m0[1]; m2[1] = m2[1] - t;
+        t = m2[0] * m0[2]; m2[2] = m2[2] - t;
+    }
+    // column 1
+    {
+        const float big = fabsf(m2[1]) > fabsf(m1[1]) ? fabsf(m2[1]) : fabsf(m1[1]);
+        if (fabsf(m2[1]) > fabsf(m1[1])) {
+            for (int c = 0; c < 3; ++c) { const float t = m1[c]; m1[c] = m2[c]; m2[c] = t; }
+            const float t = b1; b1 = b2; b2 = t;
+        }
+        if (big != 0.f) m2[1] = m2[1] / m1[1];
+        const float t = m2[1] * m1[2];
+        m2[2] = m2[2] - t;
+    }
+    const float l10 = m1[0], l20 = m2[0], l21 = m2[1];
+    // new_A = L^T L (k = 0, 1, 2 in order; the products with the structural zeros and ones of L are exact)
+    float n00, n01, n02, n11, n12, t;
+    t = l10 * l10; n00 = 1.f + t; t = l20 * l20; n00 = n00 + t;
+    t = l20 * l21; n01 = l10 + t;
+    n02 = l20;
+    t = l21 * l21; n11 = 1.f + t;
+    n12 = l21;
+    // new_b = L^T (P b3)
+    float nb0, nb1;
+    t = l10 * b1; nb0 = b0 + t; t = l20 * b2; nb0 = nb0 + t;
+    t = l21 * b2; nb1 = b1 + t;
+    const float nb2 = b2;
+    // y: fp64 least squares (eigenvalues above 3 eps_fp64 of the largest, the rank rule of JacobiSVD::solve)
+    double M[9] = {(double)n00, (double)n01, (double)n02, (double)n01, (double)n11, (double)n12, (double)n02, (double)n12, 1.0};
+    double W[9], lam[3];
+    jacobi_eig_sym3(M, W, lam);
+    const double g[3] = {(double)nb0, (double)nb1, (double)nb2};
+    const double lmax = fmax(fabs(lam[0]), fmax(fabs(lam[1]), fabs(lam[2])));
+    double yd[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (!(fabs(lam[k]) > lmax * (3.0 * 2.220446049250313e-16))) continue;
+        const double vb = (W[k] * g[0] + W[3 + k] * g[1] + W[6 + k] * g[2]) / lam[k];
+        yd[0] += W[k] * vb;
+        yd[1] += W[3 + k] * vb;
+        yd[2] += W[6 + k] * vb;
+    }
+    const float y0 = (float)yd[0], y1 = (float)yd[1], y2 = (float)yd[2];
+    // x3 = U^-1 y: Eigen's 3x3 inverse (cofactors; the determinant along column 0; inverse(r, c) = cofactor<c, r> / det)
+    const float u[9] = {m0[0], m0[1], m0[2], 0.f, m1[1], m1[2], 0.f, 0.f, m2[2]};
+    const float c00 = xicp_cof3(u, 0, 0), c10 = xicp_cof3(u, 1, 0), c20 = xicp_cof3(u, 2, 0);
+    float det = c00 * u[0];
+    t = c10 * u[3]; det = det + t;
+    t = c20 * u[6]; det = det + t;
+    const float invdet = 1.f / det;
+    const float i00 = c00 * invdet, i01 = c10 * invdet, i02 = c20 * invdet;
+    const float i10 = xicp_cof3(u, 0, 1) * invdet, i11 = xicp_cof3(u, 1, 1) * invdet, i12 = xicp_cof3(u, 2, 1) * invdet;
+    const float i20 = xicp_cof3(u, 0, 2) * invdet, i21 = xicp_cof3(u, 1, 2) * invdet, i22 = xicp_cof3(u, 2, 2) * invdet;
+    float x0, x1, x2;
+    t = i00 * y0; x0 = t; t = i01 * y1; x0 = x0 + t; t = i02 * y2; x0 = x0 + t;
+    t = i10 * y0; x1 = t; t = i11 * y1; x1 = x1 + t; t = i12 * y2; x1 = x1 + t;
+    t = i20 * y0; x2 = t; t = i21 * y1; x2 = x2 + t; t = i22 * y2; x2 = x2 + t;
+    float val = v[0] * x0;
+    t = v[1] * x1; val = val + t;
+    t = v[2] * x2; val = val + t;
+    return val;
 }
 
 // x = [rx ry rz tx ty tz] -> row-major 4x4, fp32, one rounding per op (NC10).

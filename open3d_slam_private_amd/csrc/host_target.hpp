@@ -182,7 +182,8 @@ struct reg_handle {
     int shift0 = 21;                  // low bit of the level-0 radix digit (19 when max_dist^2 < 2: bits 31,30 are 0)
     int n_blocks = 0;
     bool have_match = false;
-    // libpointmatcher chain extension (reg_set_pm_chain; kernels_pmchain.hpp): pm_on = a non-default chain is set
+    // libpointmatcher chain extension (reg_set_pm_chain; kernels_pmchain.hpp): pm_on = a non-default chain is set, or
+    // EqualityConstraints is on (xt_on below): the handle registers on the chain loop
     bool pm_on = false;
     reg_pm_chain pm;
     // the chain's N x knn buffers hold the last iteration of a chain registration on the current reading (the plain
@@ -202,6 +203,13 @@ struct reg_handle {
     bool pm_cov_valid = false;    // ... and pm_cov_host (a with_cov registration that ended with an update)
     float pm_cov_ms = 0.f;        // device time of the covariance evaluation (HIP events)
     double pm_last_error = 0.0;   // reg_result.error of the last chain registration
+    // degeneracyAwareness EqualityConstraints (reg_set_ternary_xicp; kernels_xicp_ternary.hpp): with xt_on the handle
+    // registers on the chain loop (pm_on) also under the default chain
+    bool xt_on = false;
+    reg_ternary_xicp xt;
+    DevBuf xt_state, xt_rows;     // XtState; the per-workgroup rows of the three passes
+    XtState xt_host;              // the state after the last registration with the method on
+    bool xt_valid = false;        // ... which belongs to the current reading
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
     DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;
@@ -353,6 +361,7 @@ void reg_destroy(reg_handle* h) {
                       &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->t_halo_dir, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
                       &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials,
                       &h->pm_sorted, &h->pm_sort_tmp, &h->pm_var,
+                      &h->xt_state, &h->xt_rows,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
                       &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
                       &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out,

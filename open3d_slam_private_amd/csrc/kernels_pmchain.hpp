@@ -11,6 +11,8 @@
 //   k_pm_linearize<kP2P>                        weights of the whole chain + per-workgroup fp64 partial sums
 //   k_pm_update<kX>                             reduce, solve / Kabsch, T_iter <- dT T_iter, checkers, host mirror; kX: with
 //                                               SolutionRemapping / BoundTransformationChecker (kernels_pmextras.hpp)
+//   [k_pm_update<true, true>, k_xt_*, k_pm_update<true, true>]  instead, with EqualityConstraints on: the ternary X-ICP
+//                                               analysis of every iteration between two launches (kernels_xicp_ternary.hpp)
 // Every kernel returns at once when the loop is done (enqueued iterations past convergence are no-ops).
 #pragma once
 
@@ -385,18 +387,31 @@ __device__ __noinline__ int pm_solve(const double* tot, bool p2p, float* dT) {
     return rank;
 }
 
-template <bool kX>
+// kT (with kX): the ternary X-ICP analysis runs EVERY iteration between a first launch (finish = 0: reduce, eigenvectors)
+// and a second one (finish = 1: constraint values, KKT solve with its right-hand side, update); kernels_xicp_ternary.hpp
+template <bool kX, bool kT = false>
 __global__ void __launch_bounds__(256)
 k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host, unsigned long long seq,
             PmState* __restrict__ ps, int p2p, int use_trim, int use_median, PmExtraCfg xc, PmExtraState* __restrict__ xs,
-            int finish, XicpState* __restrict__ xq) {
+            int finish, XicpState* __restrict__ xq, XtState* __restrict__ xt = nullptr, const double* __restrict__ xt_rows = nullptr,
+            int xt_n_rows = 0) {
     __shared__ double sh[8][kSums];
     __shared__ double tot[kSums];
+    __shared__ double xt_tot[kT ? kXtPart : 1];
     if (it->done) return;
+    if constexpr (kT) {
+        if (finish) {
+            if (xt->stage != 1) return;
+            if (threadIdx.x < kSums) tot[threadIdx.x] = it->sums[threadIdx.x];
+            __syncthreads();
+            if (xt->mask != 0) pmx_sum_rows<kXtPart>(xt_rows + kXtRowsPart, xt_n_rows, xt_tot);
+            n_blocks = 0;
+        }
+    }
     if constexpr (kX) {
         // R8x with a chain, second launch of the first iteration (after k_xicp_center / k_xicp_detect): the sums are the
         // ones this kernel reduced before the analysis
-        if (finish) {
+        if (finish && !kT) {
             if (it->xicp_stage != 2) return;
             if (threadIdx.x < kSums) tot[threadIdx.x] = it->sums[threadIdx.x];
             __syncthreads();
@@ -417,7 +432,7 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     }
     sh[part][comp] = t;
     __syncthreads();
-    if (threadIdx.x < kSums && !(kX && finish)) {
+    if (threadIdx.x < kSums && !(kX && finish)) {   // (finish: tot holds the sums of the first launch)
         double s = 0;
 #pragma unroll
         for (int p = 0; p < 8; ++p) s += sh[p][threadIdx.x];
@@ -428,6 +443,20 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
     if (threadIdx.x != 0) return;
     float Tc[16];
     for (int i = 0; i < 16; ++i) Tc[i] = it->T[i];
+    bool xt_prior = false;
+    float xt_rhs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (kT) {
+        if (!finish && ps->fail == 0 && tot[31] != 0.0 && tot[28] > 0.0 && !(use_trim && !(ps->sel[2] < INFINITY)) &&
+            !(use_median && !(ps->sel[3] < INFINITY))) {
+            // the system of this iteration is known: its eigen-directions, then the analysis kernels, then this kernel again
+            xt_stage_a(tot, xt->Trd, xt->vr, xt->vo, 0);
+            xt_stage_a(tot, xt->Trd, xt->vt, xt->vo + 9, 3);
+            xt->mask = 0;
+            xt->stage = 1;
+            return;
+        }
+        if (finish) xt_prior = xt_finish(xt, xt_tot, it, xt_rhs) != 0;
+    }
     if constexpr (kX) {
         if (!finish && it->xicp_stage == 1 && xq != nullptr && ps->fail == 0 && tot[31] != 0.0 && tot[28] > 0.0 &&
             !(use_trim && !(ps->sel[2] < INFINITY))) {
@@ -443,7 +472,7 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
             it->xicp_stage = 2;
             return;
         }
-        if (finish) {
+        if (finish && !kT) {
             int nc = 0;
             for (int i = 0; i < 6; ++i) {
                 const int ok = (xq->comb[i] >= (double)it->xicp_enough || xq->high[i] >= (double)it->xicp_insufficient) ? 1 : 0;
@@ -466,7 +495,13 @@ k_pm_update(const double* __restrict__ partials, int n_blocks, IterState* it, Ho
         float dT[16], Tn[16];
         bool prior = false;
         if constexpr (kX) {
-            if (xc.degeneracy != 0) {
+            if (kT && xt_prior) {
+                prior = true;
+            } else if (kT && it->xicp_nc > 0) {
+                float x[6];
+                it->rank_last = upd_solve6_xicp_rhs(tot, it->xicp_flags, xt_rhs, x);
+                x_to_T(x, dT);
+            } else if (xc.degeneracy != 0) {
                 int rank = it->rank_last;
                 prior = pmx_solve_remap(tot, xc, xs, dT, &rank) != 0;
                 it->rank_last = rank;

@@ -45,6 +45,7 @@ using namespace o3dreg;
 #include "kernels_tail.hpp"
 #include "kernels_normals.hpp"
 #include "kernels_pmextras.hpp"
+#include "kernels_xicp_ternary.hpp"
 #include "kernels_pmchain.hpp"
 #include "kernels_pmoutliers.hpp"
 #include "kernels_filters.hpp"

@@ -270,7 +270,8 @@ class PointMatcherICP(ICP):
     MinDistOutlierFilter, MedianDistOutlierFilter, VarTrimmedDistOutlierFilter (OutlierFiltersImpl.h:96-160),
     PointToPointErrorMinimizer, PointToPlaneWithCovErrorMinimizer (sensorStdDev), BoundTransformationChecker
     (maxRotationNorm, maxTranslationNorm; its place relative to the Counter checker is kept) and degeneracyAwareness
-    SolutionRemapping (threshold, use2019); everything else binds exactly as for ICP.  The robust filter's scale /
+    SolutionRemapping (threshold, use2019) or EqualityConstraints (all five keys; `localizability` holds its last
+    analysis); everything else binds exactly as for ICP.  The robust filter's scale /
     iteration persist across compute() calls on the same object, as in the reference.  `errorMinimizer` holds the
     minimizer's getters (covariance, overlap, ratios, residual) of the last compute().
 
@@ -289,9 +290,16 @@ class PointMatcherICP(ICP):
                                         {"minRatio": "var_min_ratio", "maxRatio": "var_max_ratio", "lambda": "var_lambda"}),
     }
 
+    # degeneracyAwareness EqualityConstraints (X-ICP, ternary): yaml key -> reg_ternary_xicp field (ICP.cpp:671-721)
+    _TERNARY_KEYS = {"highInformationThreshold": "high_information", "enoughInformationThreshold": "enough_information",
+                     "insufficientInformationThreshold": "insufficient_information",
+                     "point2NormalMinimalAlignmentAngleThreshold": "min_alignment_angle_deg",
+                     "point2NormalStrongAlignmentAngleThreshold": "strong_alignment_angle_deg"}
+
     def __init__(self):
         super().__init__()
         self.chain: capi.PmChainV3 | None = None
+        self.ternary: capi.TernaryXicp | None = None
         self.referenceDataPointsFilters: list = []
         self.readingDataPointsFilters: list = []   # reg_filter_points specs and OctreeGridDataPointsFilter steps
         self._dev: dict = {}
@@ -301,6 +309,7 @@ class PointMatcherICP(ICP):
     def setDefault(self):
         super().setDefault()
         self.chain = None
+        self.ternary = None
         self.referenceDataPointsFilters, self.readingDataPointsFilters = [], []
 
     def loadFromYaml(self, stream_or_text):
@@ -415,9 +424,39 @@ class PointMatcherICP(ICP):
                 raise InvalidParameter("SolutionRemapping: parameters must be numbers") from None
             chain.degeneracy_method = capi.DEGENERACY_SOLUTION_REMAPPING
             doc.pop("degeneracyAwareness")
+        ternary = None
+        if isinstance(da, dict) and "EqualityConstraints" in da and isinstance(da["EqualityConstraints"], dict):
+            if len(da) != 1:
+                raise InvalidParameter("degeneracyAwareness: one method at a time")
+            dargs = da["EqualityConstraints"]
+            unknown = set(dargs) - set(self._TERNARY_KEYS)
+            if unknown:
+                raise InvalidParameter(f"EqualityConstraints: unknown parameter(s) {sorted(unknown)}")
+            # a block without all five keys is one the reference itself rejects (ICP.cpp:674-720 returns false): it stays
+            # with the base class, which refuses the method
+            if all(k in dargs for k in self._TERNARY_KEYS):
+                ternary = capi.default_ternary_xicp(True)
+                try:
+                    for key, field in self._TERNARY_KEYS.items():
+                        if isinstance(dargs[key], (bool, str)) or dargs[key] is None:
+                            raise TypeError(key)
+                        setattr(ternary, field, float(dargs[key]))
+                except (TypeError, ValueError):
+                    raise InvalidParameter("EqualityConstraints: parameters must be numbers") from None
+                doc.pop("degeneracyAwareness")
         super().loadFromYaml(yaml.safe_dump(doc))
         if chain.with_cov and self.params.use_xicp:
             self.params.use_xicp = 0   # the reference skips the detection for this minimizer (class docstring)
+        if chain.with_cov:
+            ternary = None             # ... and likewise for EqualityConstraints
+        if ternary is not None:
+            st = capi.check_ternary_xicp(self.params, chain, ternary)
+            if st == 9:
+                raise NotImplementedError("EqualityConstraints runs with point-to-plane, knn 1 and the 0/1-weight outlier "
+                                          "filters only (no RobustOutlierFilter, no point-to-point)")
+            if st != 0:
+                raise InvalidParameter("EqualityConstraints: thresholds must be finite and ordered insufficient <= enough "
+                                       "<= high, angles must lie in (0, 90]")
         st = capi.check_pm_chain(self.params, chain)
         if st == 9:
             raise NotImplementedError("this chain is outside the accelerated path (std scale estimator; X-ICP with "
@@ -427,6 +466,7 @@ class PointMatcherICP(ICP):
             raise InvalidParameter("invalid chain (knn must lie in 1..16; a filter parameter out of range; "
                                    "VarTrimmedDistOutlierFilter: minRatio should be smaller than maxRatio)")
         self.chain = chain
+        self.ternary = ternary
         self.referenceDataPointsFilters, self.readingDataPointsFilters = ref_filters, read_filters
 
     @classmethod
@@ -556,6 +596,21 @@ class PointMatcherICP(ICP):
                 self._reg.set_pm_chain(self.chain)
             except RegError as e:
                 raise _translate(e) from None
+        if fresh and self.ternary is not None:
+            try:
+                self._reg.set_ternary_xicp(self.ternary)
+            except RegError as e:
+                raise _translate(e) from None
+
+    @property
+    def localizability(self) -> "capi.TernaryXicpResult":
+        """The EqualityConstraints analysis of the last compute()'s last iteration (reg_get_ternary_xicp)."""
+        if self._reg is None:
+            raise RuntimeError("no registration has run")
+        try:
+            return self._reg.get_ternary_xicp()
+        except RegError as e:
+            raise _translate(e) from None
 
 
 @dataclass
