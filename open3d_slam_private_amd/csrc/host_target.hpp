@@ -59,7 +59,11 @@ struct EnvSwitches {
     int lookahead = 2;          // O3D_KAHEAD
     float settle_tol = 0.05f;   // O3D_SETTLE: relative change of the trimmed limit below which the fused iterations start (round 2 sweep:
                                 // 0.05 beats 0.25 by 5 % on C3 -- an early fused iteration has a wide band and moves every point by millimetres)
-    float halo_ratio = 1.5f;    // O3D_HALO_RATIO: halo-bin edge in units of the brick-table bin edge (tuning sweeps)
+    float halo_ratio = 1.25f;   // O3D_HALO_RATIO: halo-bin edge in units of the brick-table bin edge.  Was 1.5 until the sweep of
+                                // profiles/r05_fine_halo_geometry.txt: a run covers the bin's box grown by rho_h, so a smaller box is a
+                                // shorter run (C3: 62 -> 42 records per settled query) and rho_h = 0.5 c still answers them; C3 +3 %,
+                                // C4 +3 %, the table build no slower.  Finer bins go on paying in the search but cost the build
+                                // 
     float halo_rho = 0.4f;      // O3D_HALO_RHO: exactness radius of the halo level in units of the halo-bin edge (round 2 sweep,
                                 // profiles/r02_table_sweep.txt: 0.4 beats 0.25 by 2-6 % on C2 / C3 / C4 -- fewer queries fall through
                                 // to the level scans, whose latency chain bounds the search kernels)
@@ -611,8 +615,8 @@ static void set_levels(reg_handle* h, float c, float max_abs) {
     g.n_levels = n;
 }
 
-// Level-0 accelerator: dense halo bins of edge c_h = 1.5 c with rho_h = 0.4 c_h (O3D_HALO_RHO; each point is listed in
-// 1-2 bins per axis: ~4.5 copies).  Skipped when the dense grid would be too large or on request.
+// Level-0 accelerator: dense halo bins of edge c_h = 1.25 c (O3D_HALO_RATIO) with rho_h = 0.4 c_h (O3D_HALO_RHO; each point is
+// listed in 1-2 bins per axis: ~4.5 copies).  Skipped when the dense grid would be too large or on request.
 static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const float bmax[3], float max_abs) {
     Grid& g = h->grid;
     g.use_halo = 0;

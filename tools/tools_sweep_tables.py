@@ -1,6 +1,6 @@
 """Sweep of the search-structure knobs (env switches read at reg_create) on one workload:
   O3D_BIN_OCC    points per occupied bin the automatic bin edge aims at (default 8)
-  O3D_HALO_RATIO halo-bin edge / bin edge (default 1.5)
+  O3D_HALO_RATIO halo-bin edge / bin edge (default 1.25; 1.5 when this sweep was run)
   O3D_HALO_RHO   exactness radius of the halo level / halo-bin edge (default 0.25)
 Prints, per combination: registration time (min / median of 6), search-kernel times from the per-dispatch HIP events,
 table size, build time; the final pose must be identical for every combination (the search is exact for any table).
