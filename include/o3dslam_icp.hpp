@@ -276,6 +276,7 @@ public:
                                                   orientTowardsViewpoint ? viewpoint.data() : nullptr,
                                                   regularisedCovariances ? 1 : 0, &out, nullptr);
         if (s == REG_BAD_ARGUMENT) throw InvalidParameter(reg_last_error(h_));
+        if (s == REG_MISSING_FIELD) throw InvalidField(reg_last_error(h_));
         if (s == REG_DEVICE_ERROR) throw DeviceError(reg_last_error(h_));
         if (s != REG_OK) throw std::runtime_error(reg_last_error(h_));
         if (smoothNormals) {
@@ -364,6 +365,58 @@ public:
         check(reg_filter_points(handle(), cloud.features, cloud.feature_stride, normals, covs6, cloud.n,
                                 cloud.on_device ? 1 : 0, filters.data(), (int)filters.size(), out_xyz, out_normals,
                                 out_covs6, out_idx, &m));
+        return m;
+    }
+};
+
+// The descriptor-carrying chain of reg_filter_cloud: the filters of PointFilterChain plus ObservationDirection,
+// OrientNormals, Shadow, SimpleSensorNoise, IncidenceAngle, CutAtDescriptorThreshold and MaxDensity, over xyz and up to
+// REG_MAX_FIELDS descriptor fields (include/o3dslam_reg.h gives each filter's contract and which fields it names).
+// add() returns the index of a field: `in` NULL for one the chain creates, `out` with n rows of capacity or NULL.
+// A filter that reads a field which does not exist at its place throws InvalidField, as the reference does.
+class CloudFilterChain : public DeviceFilterBase {
+public:
+    std::vector<reg_field> fields;
+    std::vector<reg_cloud_filter> filters;
+
+    int add(const float* in, float* out, int span) {
+        reg_field f{};
+        f.in = in;
+        f.out = out;
+        f.span = span;
+        fields.push_back(f);
+        return (int)fields.size() - 1;
+    }
+    // a record with struct_size set and no field named; fill base.type and what the type reads
+    static reg_cloud_filter filter(int type) {
+        reg_cloud_filter c{};
+        c.struct_size = (int32_t)sizeof(reg_cloud_filter);
+        c.base.type = type;
+        c.field_a = c.field_b = c.field_out = -1;
+        c.seed = 1;
+        return c;
+    }
+    int64_t compute(const DataPointsView& cloud, float* out_xyz, int32_t* out_idx = nullptr) {
+        int64_t m = 0;
+        check(reg_filter_cloud(handle(), cloud.features, cloud.feature_stride, cloud.n, cloud.on_device ? 1 : 0,
+                               fields.data(), (int)fields.size(), filters.data(), (int)filters.size(), out_xyz, out_idx,
+                               &m));
+        return m;
+    }
+};
+
+// VoxelGridDataPointsFilter with useCentroid 1 (reg_voxel_grid; contract in include/o3dslam_reg.h): one output row per
+// occupied voxel, ascending by its first member's index; `fields` as for CloudFilterChain (every field with `in` set).
+class VoxelGridFilter : public DeviceFilterBase {
+public:
+    reg_voxel_grid_params params;
+    std::vector<reg_field> fields;
+    VoxelGridFilter() { reg_default_voxel_grid_params(&params); }
+
+    int64_t compute(const DataPointsView& cloud, float* out_xyz, int32_t* out_idx = nullptr) {
+        int64_t m = 0;
+        check(reg_voxel_grid(handle(), cloud.features, cloud.feature_stride, cloud.n, cloud.on_device ? 1 : 0,
+                             fields.data(), (int)fields.size(), &params, out_xyz, out_idx, &m));
         return m;
     }
 };

@@ -870,6 +870,93 @@ REG_API reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xy
                                      int n_filters, float* out_xyz, float* out_nrm, float* out_cov, int32_t* out_idx,
                                      int64_t* n_out);
 
+/* Descriptor-carrying filter chain (reg_filter_cloud): the cloud is xyz plus up to REG_MAX_FIELDS named descriptor
+   fields, one n x span fp32 array each (the caller keeps the names; `normals` is a field of span 3, `covariances` of
+   span 6, and so on).  A field with in == NULL does not exist until a filter of the chain creates it; a field with
+   out == NULL is carried but not returned.  Every compaction carries every field; a field that never came to exist
+   leaves its `out` untouched.  filters[] embeds reg_point_filter (`base`), so the eight filters above run unchanged in
+   the same call; base.type also takes the descriptor filters below.  field_a / field_b / field_out index fields[]
+   (-1: none).  A filter that reads a field which does not exist at its place in the chain returns REG_MISSING_FIELD
+   (the reference throws InvalidField); an index outside [-1, n_fields) or a span that does not fit is REG_BAD_ARGUMENT.
+   All arithmetic in fp32 without contraction: norm(v) = sqrtf((x*x + y*y) + z*z), dot(a, b) = (a0*b0 + a1*b1) + a2*b2,
+   normalized(v) = v / norm(v) per component when norm(v) > 0, else v (Eigen's normalized()).
+     OBSERVATION_DIRECTION  field_out (span 3) = v - p, v = the sensor centre {x, y, z}     (ObservationDirection.cpp:61-88)
+     ORIENT_NORMALS         field_a (normals, span 3) is negated where dot(field_b, field_a) < 0 (flag = towardCenter 1)
+                            or > 0 (flag 0); field_b = observationDirections (span 3)       (OrientNormals.cpp:60-96)
+     SHADOW                 keeps |dot(normalized(field_a), normalized(p))| > v[0]; v[0] is sin(eps), computed by the
+                            caller; field_a = normals (span 3)                              (Shadow.cpp:62-94)
+     SIMPLE_SENSOR_NOISE    field_out (span 1); flag = sensorType: 0, 1, 2, 4: max(minRadius, beamAngle * norm(p) +
+                            beamConst) with the fp32 constants of SimpleSensorNoise.cpp:87-113; 3: (norm(p) * norm(p)) *
+                            float(0.5 * 0.00285).  v[0] = gain is accepted and unused, as in the reference.  flag outside
+                            0..4 is REG_BAD_ARGUMENT                                        (SimpleSensorNoise.cpp:80-136)
+     INCIDENCE_ANGLE        field_out (span 1) = acosf(dot(normalized(field_b), field_a)); field_a = normals, field_b =
+                            observationDirections (both span 3)                             (IncidenceAngle.cpp:50-74)
+     CUT_AT_DESCRIPTOR_THRESHOLD  keeps column 0 of field_a <= v[0] (flag = useLargerThan 1) or >= v[0] (flag 0)
+                                                                                            (CutAtDescriptorThreshold.cpp:62-101)
+     MAX_DENSITY            field_a = densities (column 0 of a field of any span), v[0] = maxDensity > 0.  last = the largest density of the
+                            current cloud, nSat = how many points equal it.  A point with density <= maxDensity is kept.
+                            Any other point consumes one draw r = float(rand()) / float(RAND_MAX), in cloud order, and is
+                            kept when r < a, a = maxDensity / density, multiplied by float(1 - nSat / nPoints) (integer
+                            division, as written there) when density == last.  Deviation: the reference continues the
+                            process-wide std::rand stream; here every call replays glibc's rand() after srand(seed)
+                            (seed 1 by default in the bindings)                              (MaxDensity.cpp:59-105) */
+enum { REG_MAX_FIELDS = 16 };
+enum { REG_DPF_OBSERVATION_DIRECTION = 8, REG_DPF_ORIENT_NORMALS = 9, REG_DPF_SHADOW = 10,
+       REG_DPF_SIMPLE_SENSOR_NOISE = 11, REG_DPF_INCIDENCE_ANGLE = 12, REG_DPF_CUT_AT_DESCRIPTOR_THRESHOLD = 13,
+       REG_DPF_MAX_DENSITY = 14 };
+typedef struct {
+    const float* in;         /* n x span, NULL: created by a filter of the chain */
+    float*       out;        /* capacity n x span, NULL: not returned */
+    int32_t      span;       /* 1..16 */
+    int32_t      reserved;   /* must be 0 */
+} reg_field;
+typedef struct {
+    int32_t  struct_size;    /* sizeof(reg_cloud_filter) */
+    reg_point_filter base;   /* base.type: any REG_DPF_*; the other members only for the types 0..7 */
+    int32_t  field_a;        /* see the table above; -1: none */
+    int32_t  field_b;
+    int32_t  field_out;
+    float    v[3];           /* centre / sin(eps) / gain / threshold / maxDensity */
+    int32_t  flag;           /* towardCenter / sensorType / useLargerThan */
+    uint32_t seed;           /* MAX_DENSITY */
+    int32_t  reserved[3];    /* must be 0 */
+} reg_cloud_filter;
+/* xyz, fields[].in / .out, out_xyz (m x 3, capacity n rows) and out_idx (m source indices, may be NULL) are host pointers,
+   or device pointers when on_device != 0.  MAX_DENSITY reads two counters back per call, the other new filters none. */
+REG_API reg_status reg_filter_cloud(reg_handle* h, const float* xyz, int64_t xyz_stride, int64_t n, int on_device,
+                                    const reg_field* fields, int n_fields, const reg_cloud_filter* filters,
+                                    int n_filters, float* out_xyz, int32_t* out_idx, int64_t* n_out);
+/* The first `count` values of glibc's rand() after srand(seed) (TYPE_3 random_r), the stream MAX_DENSITY and the
+   octree's random sampler replay. */
+REG_API reg_status reg_host_glibc_rand(uint32_t seed, int64_t count, int32_t* out);
+
+/* VoxelGridDataPointsFilter, useCentroid 1 (libpointmatcher DataPointsFilters/VoxelGrid.cpp:71-344; parameter names and
+   defaults of VoxelGrid.h).  All fp32 without contraction, per axis a with v = v_size[a]:
+     minBound = min / v;  numDiv = unsigned((1.0f + max / v) - minBound);  cell = unsigned(floorf(x / v - minBound));
+     linear id = i + j * nx + k * nx * ny (64-bit).
+   By rounding a cell index can reach numDiv on its axis; the linear id then aliases the neighbouring row's first cell
+   (i = 0, j + 1), exactly as the reference's linear index does, and the two cells are one voxel.
+   A voxel's output point is the sequential fp32 sum of its members in input order, starting from its first member,
+   divided by float(count).  With average_existing_descriptors every field is averaged the same way (normals are not
+   renormalised), otherwise the first member's descriptors are kept.  Output rows are ascending by first-member index;
+   out_idx is that index.  The dense voxel array of the reference is never allocated (64-bit keys, a stable radix sort,
+   one thread per voxel and column for the ordered sums: a crowded voxel is summed by one thread).
+   use_centroid 0 is REG_UNSUPPORTED: that branch of this fork writes the cell centre into feature rows 1..3 -- y, z and
+   the homogeneous pad (VoxelGrid.cpp:289-304) -- and the reference's own test never runs it (DataFilters.cpp:638-672).
+   nx * ny * nz >= 2^32 (the reference wraps or fails to allocate), non-finite input, v_size not finite or <= 0, or a
+   field with in == NULL is REG_BAD_ARGUMENT.  fields[] as for reg_filter_cloud (every field must exist). */
+typedef struct {
+    int32_t struct_size;                    /* sizeof(reg_voxel_grid_params) */
+    float   v_size[3];                      /* vSizeX vSizeY vSizeZ: 1 1 1 */
+    int32_t use_centroid;                   /* 1 */
+    int32_t average_existing_descriptors;   /* 1 */
+    int32_t reserved[2];                    /* must be 0 */
+} reg_voxel_grid_params;
+REG_API void reg_default_voxel_grid_params(reg_voxel_grid_params* p);
+REG_API reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, int64_t n, int on_device,
+                                  const reg_field* fields, int n_fields, const reg_voxel_grid_params* p, float* out_xyz,
+                                  int32_t* out_idx, int64_t* n_out);
+
 /* OctreeGridDataPointsFilter (libpointmatcher DataPointsFilters/OctreeGrid.cpp, utils/octree/Octree.tpp build / idx /
    visit, OctreeSamplers.tpp; parameter names and defaults of OctreeGrid.h).  Everything in fp32 without
    FMA contraction:

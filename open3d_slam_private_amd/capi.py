@@ -151,6 +151,100 @@ def point_filter(spec: dict) -> PointFilter:
     return f
 
 
+class Field(C.Structure):
+    """reg_field: one descriptor field of a reg_filter_cloud call (`in_` is the C member `in`)."""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("span", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CloudFilter(C.Structure):
+    """reg_cloud_filter: one filter of a reg_filter_cloud chain (a reg_point_filter plus the descriptor filters)."""
+    _fields_ = [("struct_size", C.c_int32), ("base", PointFilter), ("field_a", C.c_int32), ("field_b", C.c_int32),
+                ("field_out", C.c_int32), ("v", C.c_float * 3), ("flag", C.c_int32), ("seed", C.c_uint32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class VoxelGridParams(C.Structure):
+    """reg_voxel_grid_params (include/o3dslam_reg.h): VoxelGridDataPointsFilter's parameters."""
+    _fields_ = [("struct_size", C.c_int32), ("v_size", C.c_float * 3), ("use_centroid", C.c_int32),
+                ("average_existing_descriptors", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def default_voxel_grid_params(v_size=(1.0, 1.0, 1.0), use_centroid=1, average_existing_descriptors=1) -> VoxelGridParams:
+    p = VoxelGridParams()
+    load_library().reg_default_voxel_grid_params(C.byref(p))
+    for a in range(3):
+        p.v_size[a] = float(v_size[a])
+    p.use_centroid, p.average_existing_descriptors = int(use_centroid), int(average_existing_descriptors)
+    return p
+
+
+MAX_FIELDS = 16
+MISSING_FIELD = 7    # REG_MISSING_FIELD
+# descriptor filter -> (REG_DPF_*, name of field_a, name of field_b, (name, span) of field_out); "@descName": the
+# filter's own parameter names the field
+CLOUD_FILTERS = {
+    "ObservationDirection": (8, None, None, ("observationDirections", 3)),
+    "OrientNormals": (9, "normals", "observationDirections", None),
+    "Shadow": (10, "normals", None, None),
+    "SimpleSensorNoise": (11, None, None, ("simpleSensorNoise", 1)),
+    "IncidenceAngle": (12, "normals", "observationDirections", ("incidenceAngles", 1)),
+    "CutAtDescriptorThreshold": (13, "@descName", None, None),
+    "MaxDensity": (14, "densities", None, None),
+}
+
+
+def cloud_filter_created_fields(filters) -> list:
+    """(name, span) of every descriptor the chain creates, in chain order, without repeats."""
+    out = []
+    for spec in filters:
+        made = CLOUD_FILTERS.get(spec["type"], (0, None, None, None))[3]
+        if made and made not in out:
+            out.append(made)
+    return out
+
+
+def cloud_filter(spec: dict, names: list) -> CloudFilter:
+    """A reg_cloud_filter from {"type": <name without DataPointsFilter>, <reference parameter>: value, ...}; `names` lists
+    the call's fields in order.  A field the filter reads that is not in `names` becomes index -1 (REG_MISSING_FIELD)."""
+    c = CloudFilter()
+    c.struct_size = C.sizeof(CloudFilter)
+    c.field_a = c.field_b = c.field_out = -1
+    t = spec["type"]
+    if t not in CLOUD_FILTERS:
+        c.base = point_filter(spec)
+        return c
+    code, a, b, made = CLOUD_FILTERS[t]
+    c.base.type = code
+    if a == "@descName":
+        a = str(spec.get("descName", "none"))
+    find = lambda name: names.index(name) if name in names else -1
+    c.field_a = find(a) if a else -1
+    c.field_b = find(b) if b else -1
+    c.field_out = find(made[0]) if made else -1
+    if t == "ObservationDirection":
+        c.v[0], c.v[1], c.v[2] = float(spec.get("x", 0)), float(spec.get("y", 0)), float(spec.get("z", 0))
+    elif t == "OrientNormals":
+        c.flag = int(spec.get("towardCenter", 1))
+    elif t == "Shadow":
+        c.v[0] = np.float32(np.sin(np.float32(spec.get("eps", 0.1))))   # sin() in fp32, as the reference's T = float
+    elif t == "SimpleSensorNoise":
+        c.flag, c.v[0] = int(spec.get("sensorType", 0)), float(spec.get("gain", 1))
+    elif t == "CutAtDescriptorThreshold":
+        c.flag, c.v[0] = int(spec.get("useLargerThan", 1)), float(spec.get("threshold", 0))
+    elif t == "MaxDensity":
+        c.v[0], c.seed = float(spec.get("maxDensity", 10)), int(spec.get("seed", 1))
+    return c
+
+
+def host_glibc_rand(seed: int, count: int) -> np.ndarray:
+    """reg_host_glibc_rand: the first `count` values of glibc's rand() after srand(seed)."""
+    out = np.zeros(count, np.int32)
+    st = load_library().reg_host_glibc_rand(int(seed), count, _ptr(out))
+    if st != 0:
+        raise RegError(st, "reg_host_glibc_rand")
+    return out
+
+
 class OctreeParams(C.Structure):
     """reg_octree_params (include/o3dslam_reg.h): OctreeGridDataPointsFilter's parameters."""
     _fields_ = [("struct_size", C.c_int32), ("build_parallel", C.c_int32), ("max_point_by_node", C.c_int64),
@@ -239,7 +333,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_ternary_xicp", "reg_check_ternary_xicp", "reg_set_ternary_xicp", "reg_get_ternary_xicp",
            "reg_host_ternary_decide", "reg_host_partial_constraint", "reg_host_solve6_xicp_rhs",
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
-           "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks"]
+           "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks",
+           "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid"]
 
 
 def lib_path() -> str:
@@ -372,6 +467,12 @@ def load_library():
                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_filter_points.argtypes = [vp, vp, i64, vp, vp, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp,
                                       C.POINTER(C.c_int64)]
+    lib.reg_filter_cloud.argtypes = [vp, vp, i64, i64, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_int64)]
+    lib.reg_host_glibc_rand.argtypes = [C.c_uint32, i64, vp]
+    lib.reg_default_voxel_grid_params.argtypes = [C.POINTER(VoxelGridParams)]
+    lib.reg_default_voxel_grid_params.restype = None
+    lib.reg_voxel_grid.argtypes = [vp, vp, i64, i64, C.c_int, vp, C.c_int, C.POINTER(VoxelGridParams), vp, vp,
+                                   C.POINTER(C.c_int64)]
     lib.reg_default_octree_params.argtypes = [C.POINTER(OctreeParams)]
     lib.reg_default_octree_params.restype = None
     lib.reg_octree_grid.argtypes = [vp, vp, i64, vp, vp, i64, C.c_int, C.POINTER(OctreeParams), C.POINTER(OctreeOut),
@@ -438,6 +539,17 @@ class DeviceArray:
             self.free()
         except Exception:
             pass
+
+
+def download(ptr: int, shape, dtype=np.float32) -> np.ndarray:
+    """Copies a device array that starts at the raw pointer `ptr` to the host."""
+    out = np.empty(shape, dtype)
+    if out.nbytes:
+        hip = C.CDLL("libamdhip64.so.7")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        if hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), out.nbytes, 2) != 0:
+            raise RegError(8, "hipMemcpy (device to host) failed")
+    return out
 
 
 def default_ssn_params() -> SsnParams:
@@ -888,6 +1000,73 @@ class Registration:
         self._check(self._lib.reg_filter_points(self._h, C.c_void_p(xyz_ptr), xyz_stride, nrm_ptr, cov_ptr, n, 1,
                                                 C.cast(arr, C.c_void_p), len(filters), out_xyz_ptr, out_nrm_ptr,
                                                 out_cov_ptr, out_idx_ptr, C.byref(m)))
+        return int(m.value)
+
+    def filter_cloud(self, xyz, filters, descriptors=None):
+        """Descriptor-carrying filter chain on the device (reg_filter_cloud).  filters: dicts as for point_filter() /
+        cloud_filter(); descriptors: {name: (n, span) array} carried through every compaction.  Returns
+        (xyz (m,3), src_idx (m,), {name: (m, span)}) with the descriptors the chain created added."""
+        xyz = _f32(xyz)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        given = {k: _f32(v).reshape(n, -1) for k, v in (descriptors or {}).items()}
+        spans = [(k, v.shape[1]) for k, v in given.items()]
+        spans += [f for f in cloud_filter_created_fields(filters) if f[0] not in given]
+        names = [k for k, _ in spans]
+        outs = {k: np.zeros((n, w), np.float32) for k, w in spans}
+        farr = (Field * max(len(spans), 1))()
+        for i, (k, w) in enumerate(spans):
+            farr[i].in_, farr[i].out, farr[i].span = (given[k].ctypes.data if k in given else None), outs[k].ctypes.data, w
+        carr = (CloudFilter * max(len(filters), 1))(*[cloud_filter(f, names) for f in filters])
+        ox, oi = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        m = C.c_int64(0)
+        self._check(self._lib.reg_filter_cloud(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, n, 0,
+                                               C.cast(farr, C.c_void_p), len(spans), C.cast(carr, C.c_void_p), len(filters),
+                                               _ptr(ox), _ptr(oi), C.byref(m)))
+        k = int(m.value)
+        return ox[:k].copy(), oi[:k].copy(), {name: a[:k].copy() for name, a in outs.items()}
+
+    def filter_cloud_device(self, xyz_ptr, xyz_stride, n, filters, fields, out_xyz_ptr, out_idx_ptr=None) -> int:
+        """Device-pointer form.  fields: [(name, in_ptr or None, out_ptr or None, span)], every output with n rows of
+        capacity.  Returns n_out."""
+        names = [f[0] for f in fields]
+        farr = (Field * max(len(fields), 1))()
+        for i, (_, pin, pout, w) in enumerate(fields):
+            farr[i].in_, farr[i].out, farr[i].span = pin or None, pout or None, w
+        carr = (CloudFilter * max(len(filters), 1))(*[cloud_filter(f, names) for f in filters])
+        m = C.c_int64(0)
+        self._check(self._lib.reg_filter_cloud(self._h, C.c_void_p(xyz_ptr), xyz_stride, n, 1, C.cast(farr, C.c_void_p),
+                                               len(fields), C.cast(carr, C.c_void_p), len(filters), out_xyz_ptr,
+                                               out_idx_ptr, C.byref(m)))
+        return int(m.value)
+
+    def voxel_grid(self, xyz, params: "VoxelGridParams | None" = None, descriptors=None):
+        """VoxelGridDataPointsFilter (useCentroid 1) on the device (reg_voxel_grid).  Returns (xyz (m,3), src_idx (m,),
+        {name: (m, span)}): one row per occupied voxel, ascending by its first member's index."""
+        p = params if params is not None else default_voxel_grid_params()
+        xyz = _f32(xyz)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        given = {k: _f32(v).reshape(n, -1) for k, v in (descriptors or {}).items()}
+        outs = {k: np.zeros(v.shape, np.float32) for k, v in given.items()}
+        farr = (Field * max(len(given), 1))()
+        for i, (k, v) in enumerate(given.items()):
+            farr[i].in_, farr[i].out, farr[i].span = v.ctypes.data, outs[k].ctypes.data, v.shape[1]
+        ox, oi = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+        m = C.c_int64(0)
+        self._check(self._lib.reg_voxel_grid(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, n, 0,
+                                             C.cast(farr, C.c_void_p), len(given), C.byref(p), _ptr(ox), _ptr(oi),
+                                             C.byref(m)))
+        k = int(m.value)
+        return ox[:k].copy(), oi[:k].copy(), {name: a[:k].copy() for name, a in outs.items()}
+
+    def voxel_grid_device(self, xyz_ptr, xyz_stride, n, params: "VoxelGridParams", fields, out_xyz_ptr,
+                          out_idx_ptr=None) -> int:
+        """Device-pointer form; fields as for filter_cloud_device (every in_ptr set).  Returns n_out."""
+        farr = (Field * max(len(fields), 1))()
+        for i, (_, pin, pout, w) in enumerate(fields):
+            farr[i].in_, farr[i].out, farr[i].span = pin or None, pout or None, w
+        m = C.c_int64(0)
+        self._check(self._lib.reg_voxel_grid(self._h, C.c_void_p(xyz_ptr), xyz_stride, n, 1, C.cast(farr, C.c_void_p),
+                                             len(fields), C.byref(params), out_xyz_ptr, out_idx_ptr, C.byref(m)))
         return int(m.value)
 
     def octree_grid(self, xyz, params: "OctreeParams | None" = None, normals=None, covs=None, **kw):

@@ -58,6 +58,74 @@ void ssn_plan(int n, int knn, SsnPlan& P) {
     P.leaf_begin.push_back(n);
 }
 
+// The checks reg_filter_points makes on one reg_point_filter (types REG_DPF_IDENTITY .. REG_DPF_FIX_STEP_SAMPLING).
+bool pf_valid(const reg_point_filter& f) {
+    const bool quant = f.type == REG_DPF_MAX_QUANTILE_ON_AXIS;
+    bool ok = f.type >= REG_DPF_IDENTITY && f.type <= REG_DPF_FIX_STEP_SAMPLING &&
+              (quant ? (f.dim >= 0 && f.dim <= 2) : (f.dim >= -1 && f.dim <= 2));
+    if (quant) ok = ok && f.value > 0.f && f.value < 1.f;
+    if (f.type == REG_DPF_FIX_STEP_SAMPLING) ok = ok && f.step >= 1 && f.phase >= 0 && f.phase < f.step;
+    return ok;
+}
+
+// flag[j] = the filter keeps the j-th point of the index list (f_keys / f_misc / f_tmp are scratch; `who` prefixes errors)
+reg_status pf_flags(reg_handle* h, const reg_point_filter& f, const float* px, const int32_t* idx, int m, uint32_t* flag,
+                    const char* who) {
+    hipStream_t s = h->stream;
+    PointFilterDev d{};
+    d.type = f.type;
+    const bool uses_dim = f.type == REG_DPF_MAX_DIST || f.type == REG_DPF_MIN_DIST || f.type == REG_DPF_DISTANCE_LIMIT ||
+                          f.type == REG_DPF_MAX_QUANTILE_ON_AXIS;
+    d.dim = uses_dim ? f.dim : 0;
+    d.remove_inside = f.remove_inside;
+    d.step = f.step;
+    d.phase = f.phase;
+    d.value = (uses_dim && f.dim < 0) ? std::fabs(f.value) : f.value;   // anyabs() for the norm
+    for (int a = 0; a < 6; ++a) d.box[a] = f.box[a];
+    if (f.type == REG_DPF_MAX_QUANTILE_ON_AXIS) {
+        const int q = (int)((float)m * f.value);   // int(float(n) * ratio), MaxQuantileOnAxis.cpp
+        if (q >= m) {
+            h->err = std::string(who) + ": MaxQuantileOnAxis quantile index beyond the cloud";
+            return REG_BAD_ARGUMENT;
+        }
+        float* vals = h->f_keys.as<float>();
+        float* sorted = vals + m;
+        HIPCHK(h, hipMemsetAsync(h->f_misc.p, 0, 4, s));
+        k_pf_axis<<<grid_for(m), 256, 0, s>>>(px, idx, m, f.dim, vals, h->f_misc.as<uint32_t>());
+        size_t need = 0;
+        HIPCHK(h, rocprim::radix_sort_keys(nullptr, need, vals, sorted, (unsigned)m, 0, 32, s));
+        HIPCHK(h, h->f_tmp.reserve(need));
+        HIPCHK(h, rocprim::radix_sort_keys(h->f_tmp.p, need, vals, sorted, (unsigned)m, 0, 32, s));
+        uint32_t has_nan = 0;
+        HIPCHK(h, hipMemcpyAsync(&d.limit, sorted + q, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(&has_nan, h->f_misc.p, 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipStreamSynchronize(s));
+        if (has_nan) {
+            h->err = std::string(who) + ": MaxQuantileOnAxis on an axis holding NaN (run RemoveNaN first)";
+            return REG_BAD_ARGUMENT;
+        }
+    }
+    k_pf_pred<<<grid_for(m), 256, 0, s>>>(px, idx, m, d, flag);
+    return REG_OK;
+}
+
+// Order-preserving compaction of the index list by flag: idx <- the kept entries (idx2 is the spare list), m <- their count.
+reg_status pf_compact(reg_handle* h, int32_t*& idx, int32_t*& idx2, const uint32_t* flag, uint32_t* pos, int& m) {
+    hipStream_t s = h->stream;
+    size_t need = 0;
+    HIPCHK(h, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
+    HIPCHK(h, h->f_tmp.reserve(need));
+    HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
+    k_pf_compact<<<grid_for(m), 256, 0, s>>>(idx, m, flag, pos, idx2);
+    uint32_t tail[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&tail[0], pos + m - 1, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(&tail[1], flag + m - 1, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    m = (int)(tail[0] + tail[1]);
+    std::swap(idx, idx2);
+    return REG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,18 +298,11 @@ reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xyz_stride
         h->err = "reg_filter_points: bad argument";
         return REG_BAD_ARGUMENT;
     }
-    for (int k = 0; k < n_filters; ++k) {
-        const reg_point_filter& f = filters[k];
-        const bool quant = f.type == REG_DPF_MAX_QUANTILE_ON_AXIS;
-        bool ok = f.type >= REG_DPF_IDENTITY && f.type <= REG_DPF_FIX_STEP_SAMPLING &&
-                  (quant ? (f.dim >= 0 && f.dim <= 2) : (f.dim >= -1 && f.dim <= 2));
-        if (quant) ok = ok && f.value > 0.f && f.value < 1.f;
-        if (f.type == REG_DPF_FIX_STEP_SAMPLING) ok = ok && f.step >= 1 && f.phase >= 0 && f.phase < f.step;
-        if (!ok) {
+    for (int k = 0; k < n_filters; ++k)
+        if (!pf_valid(filters[k])) {
             h->err = "reg_filter_points: bad filter " + std::to_string(k);
             return REG_BAD_ARGUMENT;
         }
-    }
     *n_out = 0;
     if (n == 0) return REG_OK;
     const int N = (int)n;
@@ -270,51 +331,10 @@ reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xyz_stride
     for (int k = 0; k < n_filters && m > 0; ++k) {
         const reg_point_filter& f = filters[k];
         if (f.type == REG_DPF_IDENTITY) continue;
-        PointFilterDev d{};
-        d.type = f.type;
-        const bool uses_dim = f.type == REG_DPF_MAX_DIST || f.type == REG_DPF_MIN_DIST || f.type == REG_DPF_DISTANCE_LIMIT ||
-                              f.type == REG_DPF_MAX_QUANTILE_ON_AXIS;
-        d.dim = uses_dim ? f.dim : 0;
-        d.remove_inside = f.remove_inside;
-        d.step = f.step;
-        d.phase = f.phase;
-        d.value = (uses_dim && f.dim < 0) ? std::fabs(f.value) : f.value;   // anyabs() for the norm
-        for (int a = 0; a < 6; ++a) d.box[a] = f.box[a];
-        if (f.type == REG_DPF_MAX_QUANTILE_ON_AXIS) {
-            const int q = (int)((float)m * f.value);   // int(float(n) * ratio), MaxQuantileOnAxis.cpp
-            if (q >= m) {
-                h->err = "reg_filter_points: MaxQuantileOnAxis quantile index beyond the cloud";
-                return REG_BAD_ARGUMENT;
-            }
-            float* vals = h->f_keys.as<float>();
-            float* sorted = vals + m;
-            HIPCHK(h, hipMemsetAsync(h->f_misc.p, 0, 4, s));
-            k_pf_axis<<<grid_for(m), 256, 0, s>>>(px, idx, m, f.dim, vals, h->f_misc.as<uint32_t>());
-            size_t need = 0;
-            HIPCHK(h, rocprim::radix_sort_keys(nullptr, need, vals, sorted, (unsigned)m, 0, 32, s));
-            HIPCHK(h, h->f_tmp.reserve(need));
-            HIPCHK(h, rocprim::radix_sort_keys(h->f_tmp.p, need, vals, sorted, (unsigned)m, 0, 32, s));
-            uint32_t has_nan = 0;
-            HIPCHK(h, hipMemcpyAsync(&d.limit, sorted + q, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(&has_nan, h->f_misc.p, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipStreamSynchronize(s));
-            if (has_nan) {
-                h->err = "reg_filter_points: MaxQuantileOnAxis on an axis holding NaN (run RemoveNaN first)";
-                return REG_BAD_ARGUMENT;
-            }
-        }
-        k_pf_pred<<<grid_for(m), 256, 0, s>>>(px, idx, m, d, flag);
-        size_t need = 0;
-        HIPCHK(h, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
-        HIPCHK(h, h->f_tmp.reserve(need));
-        HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
-        k_pf_compact<<<grid_for(m), 256, 0, s>>>(idx, m, flag, pos, idx2);
-        uint32_t tail[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(&tail[0], pos + m - 1, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(&tail[1], flag + m - 1, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        m = (int)(tail[0] + tail[1]);
-        std::swap(idx, idx2);
+        reg_status st = pf_flags(h, f, px, idx, m, flag, "reg_filter_points");
+        if (st != REG_OK) return st;
+        st = pf_compact(h, idx, idx2, flag, pos, m);
+        if (st != REG_OK) return st;
     }
     float *ox = out_xyz, *on = nrm ? out_nrm : nullptr, *oc = cov ? out_cov : nullptr;
     int32_t* oi = out_idx;

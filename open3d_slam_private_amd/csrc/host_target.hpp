@@ -217,6 +217,7 @@ struct reg_handle {
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
     DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;
+    DevBuf f_fields, f_draws;     // reg_filter_cloud (host_cloud_filters.hpp): descriptor-field workspace, MaxDensity's draws
     // OctreeGridDataPointsFilter (host_octree.hpp): keys, sort orders, ranks, centres, per-round flags, leaf starts
     DevBuf o_keys, o_keys_s, o_iota, o_idx, o_idx2, o_rank, o_rank_a, o_rank_s, o_c, o_kk, o_heads, o_pos, o_open, o_depth,
         o_start, o_rand, o_radii;
@@ -368,7 +369,7 @@ void reg_destroy(reg_handle* h) {
                       &h->xt_state, &h->xt_rows,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
                       &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
-                      &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out,
+                      &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out, &h->f_fields, &h->f_draws,
                       &h->o_keys, &h->o_keys_s, &h->o_iota, &h->o_idx, &h->o_idx2, &h->o_rank, &h->o_rank_a, &h->o_rank_s,
                       &h->o_c, &h->o_kk, &h->o_heads, &h->o_pos, &h->o_open, &h->o_depth, &h->o_start, &h->o_rand,
                       &h->o_radii};

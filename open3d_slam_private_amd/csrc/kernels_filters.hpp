@@ -337,3 +337,220 @@ k_pf_gather(const float* __restrict__ px, const float* __restrict__ pn, const fl
         for (int a = 0; a < 6; ++a) oc[6 * (size_t)j + a] = pc[6 * i + a];
     if (oidx) oidx[j] = (int32_t)i;
 }
+
+// =================================================================================================
+// Descriptor-carrying filters (reg_filter_cloud): the same index list + predicate + scan + compaction, with every
+// descriptor field held in a workspace of n x span floats addressed by SOURCE index.  Map filters (k_fc_map) create or
+// rewrite a field for the points of the current index list; predicates (k_fc_pred) read fields the same way.
+// norm = sqrtf((x*x + y*y) + z*z), dot = (a0*b0 + a1*b1) + a2*b2, no contraction (include/o3dslam_reg.h).
+// =================================================================================================
+struct CloudFilterDev {
+    int type, flag;
+    float v[3];
+    float last;         // MAX_DENSITY: the largest density of the current cloud
+    float sat_factor;   // MAX_DENSITY: float(1 - nSat / nPoints)
+};
+
+__device__ __forceinline__ float fc_dot(const float* a, const float* b) {
+    float s = a[0] * b[0];
+    float t = a[1] * b[1];
+    s = s + t;
+    t = a[2] * b[2];
+    return s + t;
+}
+
+__device__ __forceinline__ float fc_norm(const float* a) { return sqrtf(fc_dot(a, a)); }
+
+// Eigen's normalized(): v / norm when norm > 0, else v
+__device__ __forceinline__ void fc_normalized(const float* a, float* out) {
+    const float nn = fc_norm(a);
+    for (int c = 0; c < 3; ++c) out[c] = nn > 0.f ? a[c] / nn : a[c];
+}
+
+__device__ __forceinline__ float fc_laser_noise(float min_radius, float beam_angle, float beam_const, float r) {
+    float e = beam_angle * r;
+    e = e + beam_const;
+    return fmaxf(min_radius, e);
+}
+
+__global__ void __launch_bounds__(256)
+k_fc_map(const float* __restrict__ px, const int32_t* __restrict__ idx, int m, CloudFilterDev f, float* fa,
+         const float* fb, float* fout) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const size_t i = (size_t)idx[j];
+    const float p[3] = {px[3 * i], px[3 * i + 1], px[3 * i + 2]};
+    switch (f.type) {
+        case REG_DPF_OBSERVATION_DIRECTION:
+            for (int c = 0; c < 3; ++c) fout[3 * i + c] = f.v[c] - p[c];
+            break;
+        case REG_DPF_ORIENT_NORMALS: {
+            const float nr[3] = {fa[3 * i], fa[3 * i + 1], fa[3 * i + 2]};
+            const float ob[3] = {fb[3 * i], fb[3 * i + 1], fb[3 * i + 2]};
+            const float s = fc_dot(ob, nr);
+            if (f.flag ? (s < 0.f) : (s > 0.f))
+                for (int c = 0; c < 3; ++c) fa[3 * i + c] = -nr[c];
+            break;
+        }
+        case REG_DPF_SIMPLE_SENSOR_NOISE: {
+            const float r = fc_norm(p);
+            float v;
+            switch (f.flag) {
+                case 0: v = fc_laser_noise(0.012f, 0.0068f, 0.0008f, r); break;
+                case 1: v = fc_laser_noise(0.028f, 0.0013f, 0.0001f, r); break;
+                case 2: v = fc_laser_noise(0.018f, 0.0006f, 0.0015f, r); break;
+                case 3: v = (r * r) * (float)(0.5 * 0.00285); break;
+                default: v = fc_laser_noise(0.004f, 0.0053f, -0.0092f, r); break;
+            }
+            fout[i] = v;
+            break;
+        }
+        case REG_DPF_INCIDENCE_ANGLE: {
+            const float nr[3] = {fa[3 * i], fa[3 * i + 1], fa[3 * i + 2]};
+            const float ob[3] = {fb[3 * i], fb[3 * i + 1], fb[3 * i + 2]};
+            float u[3];
+            fc_normalized(ob, u);
+            fout[i] = acosf(fc_dot(u, nr));
+            break;
+        }
+        default: break;
+    }
+}
+
+// MAX_DENSITY, pass 1: the largest density of the current cloud as an orderable key (NaN never wins: it is skipped)
+__global__ void __launch_bounds__(256)
+k_fc_density_max(const float* __restrict__ den, int span, const int32_t* __restrict__ idx, int m,
+                 uint32_t* __restrict__ misc) {
+    __shared__ uint32_t s_hi[256];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    uint32_t k = 0u;
+    if (j < m) {
+        const float d = den[(size_t)idx[j] * span];
+        if (!isnan(d)) k = ssn_orderable(d);
+    }
+    s_hi[threadIdx.x] = k;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) s_hi[threadIdx.x] = max(s_hi[threadIdx.x], s_hi[threadIdx.x + s]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) atomicMax(&misc[0], s_hi[0]);
+}
+
+// MAX_DENSITY, pass 2: flag = needs a draw (density > maxDensity); misc[1] += points equal to the largest density
+__global__ void __launch_bounds__(256)
+k_fc_density_mask(const float* __restrict__ den, int span, const int32_t* __restrict__ idx, int m, float max_density,
+                  uint32_t* __restrict__ misc, uint32_t* __restrict__ need) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    bool sat = false;
+    if (j < m) {
+        const float d = den[(size_t)idx[j] * span];
+        need[j] = d > max_density ? 1u : 0u;
+        sat = !isnan(d) && ssn_orderable(d) == misc[0];
+    }
+    const int c = __syncthreads_count(sat ? 1 : 0);
+    if (threadIdx.x == 0 && c) atomicAdd(&misc[1], (uint32_t)c);
+}
+
+__global__ void __launch_bounds__(256)
+k_fc_pred(const float* __restrict__ px, const int32_t* __restrict__ idx, int m, CloudFilterDev f,
+          const float* __restrict__ fa, int span_a, const uint32_t* __restrict__ need,
+          const uint32_t* __restrict__ draw_pos, const float* __restrict__ draws, uint32_t* __restrict__ flag) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const size_t i = (size_t)idx[j];
+    bool keep = true;
+    switch (f.type) {
+        case REG_DPF_SHADOW: {
+            const float p[3] = {px[3 * i], px[3 * i + 1], px[3 * i + 2]};
+            const float nr[3] = {fa[3 * i], fa[3 * i + 1], fa[3 * i + 2]};
+            float un[3], up[3];
+            fc_normalized(nr, un);
+            fc_normalized(p, up);
+            keep = fabsf(fc_dot(un, up)) > f.v[0];
+            break;
+        }
+        case REG_DPF_CUT_AT_DESCRIPTOR_THRESHOLD: {
+            const float v = fa[i * span_a];
+            keep = f.flag ? (v <= f.v[0]) : (v >= f.v[0]);
+            break;
+        }
+        case REG_DPF_MAX_DENSITY: {
+            if (need[j]) {
+                const float d = fa[i * span_a];
+                float a = f.v[0] / d;
+                if (d == f.last) a = a * f.sat_factor;
+                keep = draws[draw_pos[j]] < a;
+            }
+            break;
+        }
+        default: break;
+    }
+    flag[j] = keep ? 1u : 0u;
+}
+
+// one thread per output element of a field: out[j, c] = ws[idx[j], c]
+__global__ void __launch_bounds__(256)
+k_fc_gather(const float* __restrict__ ws, int span, const int32_t* __restrict__ idx, int m, float* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)m * span) return;
+    const size_t j = t / span, c = t % span;
+    out[t] = ws[(size_t)idx[j] * span + c];
+}
+
+// =================================================================================================
+// VoxelGridDataPointsFilter, useCentroid 1 (reg_voxel_grid): 64-bit linear voxel ids, a stable rocPRIM radix sort of
+// (id, input index), then ordered sums -- one thread per voxel and column walks the voxel's members in input order.
+// =================================================================================================
+struct VoxelGridDev {
+    float v[3], min_bound[3];
+    uint64_t nx, nxy;
+};
+
+__global__ void __launch_bounds__(256)
+k_vg_keys(const float* __restrict__ px, int n, VoxelGridDev g, uint64_t* __restrict__ keys, int32_t* __restrict__ iota) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    uint64_t c[3];
+    for (int a = 0; a < 3; ++a) {
+        float q = px[3 * (size_t)i + a] / g.v[a];
+        q = q - g.min_bound[a];
+        c[a] = (uint64_t)(unsigned)floorf(q);
+    }
+    keys[i] = c[0] + c[1] * g.nx + c[2] * g.nxy;
+    iota[i] = i;
+}
+
+// is_first[i] = input point i is the first member of its voxel (sorted position r is a segment head)
+__global__ void __launch_bounds__(256)
+k_vg_first(const uint64_t* __restrict__ keys_s, const int32_t* __restrict__ idx, int n, uint32_t* __restrict__ is_first) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    is_first[idx[r]] = (r == 0 || keys_s[r] != keys_s[r - 1]) ? 1u : 0u;
+}
+
+// One thread per (sorted position, column); only segment heads work.  in: n x span addressed by input index (row
+// stride `stride`); out row = pos[first member].  average 0 copies the first member.
+__global__ void __launch_bounds__(256)
+k_vg_reduce(const float* __restrict__ in, int64_t stride, int span, const uint64_t* __restrict__ keys_s,
+            const int32_t* __restrict__ idx, const uint32_t* __restrict__ pos, int n, int average,
+            float* __restrict__ out, int32_t* __restrict__ src_idx) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)n * span) return;
+    const int r = (int)(t / span), c = (int)(t % span);
+    const uint64_t key = keys_s[r];
+    if (r > 0 && keys_s[r - 1] == key) return;
+    const int32_t first = idx[r];
+    float acc = in[(size_t)first * stride + c];
+    if (average) {
+        int count = 1;
+        for (int q = r + 1; q < n && keys_s[q] == key; ++q) {
+            acc = acc + in[(size_t)idx[q] * stride + c];
+            ++count;
+        }
+        acc = acc / (float)count;
+    }
+    const size_t row = pos[first];
+    out[row * span + c] = acc;
+    if (src_idx && c == 0) src_idx[row] = first;
+}

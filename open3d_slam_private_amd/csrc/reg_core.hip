@@ -58,6 +58,7 @@ using namespace o3dreg;
 #include "host_rccl.hpp"
 #include "host_filters.hpp"
 #include "host_octree.hpp"
+#include "host_cloud_filters.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -43,10 +43,12 @@ class InvalidParameter(RuntimeError):
 class DataPoints:
     """The fields of PointMatcher<float>::DataPoints the path touches (PointMatcher.h:222-403):
     `features` N x 4 ({x,y,z,1} per point == the column-major 4 x N Eigen matrix in memory) or N x 3,
-    descriptor `normals` N x 3."""
+    descriptor `normals` N x 3, `covariances` N x 6, and any other named descriptor in `descriptors` (name -> N x span
+    fp32, e.g. `densities`, `observationDirections`); the filter chains see all of them as named descriptors."""
     features: np.ndarray
     normals: np.ndarray | None = None
     covariances: np.ndarray | None = None
+    descriptors: dict = field(default_factory=dict)
 
     def getNbPoints(self) -> int:
         return 0 if self.features is None else int(np.asarray(self.features).shape[0])
@@ -304,6 +306,7 @@ class PointMatcherICP(ICP):
         self.readingDataPointsFilters: list = []   # reg_filter_points specs and OctreeGridDataPointsFilter steps
         self._dev: dict = {}
         self._read_stages: list = []
+        self._read_fields: dict = {}
         self.errorMinimizer = ErrorMinimizerView(self)
 
     def setDefault(self):
@@ -314,8 +317,8 @@ class PointMatcherICP(ICP):
 
     def loadFromYaml(self, stream_or_text):
         """Also binds referenceDataPointsFilters (SamplingSurfaceNormal, SurfaceNormal, OctreeGrid) and
-        readingDataPointsFilters (READING_FILTERS, OctreeGrid) to the device filters (reg_sampling_surface_normal,
-        reg_estimate_normals, reg_filter_points, reg_octree_grid)."""
+        readingDataPointsFilters (READING_FILTERS, DESCRIPTOR_FILTERS, SurfaceNormal, OctreeGrid) to the device filters
+        (reg_sampling_surface_normal, reg_estimate_normals, reg_filter_points, reg_filter_cloud, reg_octree_grid)."""
         import yaml
         text = stream_or_text.read() if hasattr(stream_or_text, "read") else stream_or_text
         doc = yaml.safe_load(text) or {}
@@ -532,8 +535,12 @@ class PointMatcherICP(ICP):
     def _set_reading(self, readingIn: DataPoints):
         """ICP::computeWithTransformedReference (ICP.cpp:950-955): the reading filters run on the device before the
         reading's centroid; reg_set_source reads their output in place.  Correspondence ids index the filtered cloud."""
+        self._read_fields = {}
         if not self.readingDataPointsFilters:
+            self._read_stages = []
             return super()._set_reading(readingIn)
+        if readingIn.descriptors or _needs_fields(self.readingDataPointsFilters):
+            return self._set_reading_fields(readingIn)
         x = np.ascontiguousarray(readingIn.features, np.float32)
         n, stride = x.shape[0], x.shape[1]
         src = self._buf("read_in", x.nbytes)
@@ -579,6 +586,19 @@ class PointMatcherICP(ICP):
         self._reg.set_source_device(cur, 3, n, cur_nrm, 3, cur_cov)
         self.readingFilteredCount = n
 
+    def _set_reading_fields(self, readingIn: DataPoints):
+        """The reading chain with named descriptors (run_filter_chain): every field stays on the device; the final
+        `normals` / `covariances` fields go to reg_set_source."""
+        _check_fields(self.readingDataPointsFilters, _cloud_fields(readingIn))
+        cur, stride, n, fields, stages = run_filter_chain(self._reg, self._buf, "read", self.readingDataPointsFilters,
+                                                          readingIn)
+        if n == 0:
+            raise RuntimeError("The reading point cloud is empty.")   # ICP.cpp:958-960
+        self._read_stages, self._read_fields = stages, dict(fields, _n=n)
+        nrm, cov = fields.get("normals"), fields.get("covariances")
+        self._reg.set_source_device(cur, stride, n, nrm[0] if nrm else None, 3, cov[0] if cov else None)
+        self.readingFilteredCount = n
+
     def readingFilteredIndices(self) -> np.ndarray:
         """Source index (into the last compute()'s reading) of every filtered reading point, composed through every
         step of the chain."""
@@ -586,7 +606,16 @@ class PointMatcherICP(ICP):
         for key, m in self._read_stages:
             step = self._dev[key].download(m, np.int32)
             idx = step if idx is None else idx[step]
+        if idx is None and self._read_fields:
+            idx = np.arange(self._read_fields["_n"], dtype=np.int32)   # a chain without a compaction
         return idx
+
+    def readingFilteredDescriptor(self, name: str) -> np.ndarray:
+        """The descriptor `name` (n x span) of the last compute()'s filtered reading, downloaded from the device."""
+        if name == "_n" or name not in self._read_fields:
+            raise InvalidField(f"Cannot find descriptor {name}")
+        ptr, span = self._read_fields[name]
+        return capi.download(ptr, (self._read_fields["_n"], span))
 
     def _ensure(self):
         fresh = self._reg is None
@@ -751,6 +780,45 @@ class OctreeGridDataPointsFilter:
         return DataPoints(out["xyz"], out.get("normals"), out.get("covs"))
 
 
+class VoxelGridDataPointsFilter:
+    """VoxelGridDataPointsFilter (DataPointsFilters/VoxelGrid.{h,cpp}) on the device (reg_voxel_grid), parameters by the
+    reference's names and defaults.  useCentroid 0 is refused: that branch of this fork writes the cell centre into
+    feature rows 1..3 -- y, z and the homogeneous pad (VoxelGrid.cpp:289-304) -- and the reference's own test never runs
+    it (DataFilters.cpp:638-672).  Every descriptor is carried (averaged with averageExistingDescriptors, else the
+    voxel's first member's).  A stage of parse_filters / filter_cloud chains and of an assigned
+    `readingDataPointsFilters`; loadFromYaml keeps refusing the name (see _reading_filter)."""
+
+    PARAMS = {"vSizeX": 1.0, "vSizeY": 1.0, "vSizeZ": 1.0, "useCentroid": 1, "averageExistingDescriptors": 1}
+
+    def __init__(self, **kw):
+        unknown = set(kw) - set(self.PARAMS)
+        if unknown:
+            raise InvalidParameter(f"VoxelGridDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
+        a = dict(self.PARAMS, **kw)
+        try:
+            self.vSize = tuple(float(a[k]) for k in ("vSizeX", "vSizeY", "vSizeZ"))
+            flags = {k: int(a[k]) for k in ("useCentroid", "averageExistingDescriptors")}
+        except (TypeError, ValueError):
+            raise InvalidParameter("VoxelGridDataPointsFilter: parameters must be numbers") from None
+        if not all(0.001 <= v < math.inf for v in self.vSize):
+            raise InvalidParameter("vSizeX / vSizeY / vSizeZ: must lie in [0.001, inf) (VoxelGrid.h)")
+        if any(v not in (0, 1) for v in flags.values()):
+            raise InvalidParameter("useCentroid / averageExistingDescriptors: 0 or 1")
+        if not flags["useCentroid"]:
+            raise NotImplementedError("VoxelGridDataPointsFilter: useCentroid 0 writes the cell centre into feature rows "
+                                      "1..3 in the reference (VoxelGrid.cpp:289-304); only useCentroid 1 is built")
+        self.useCentroid, self.averageExistingDescriptors = True, bool(flags["averageExistingDescriptors"])
+        self.srcIdx = None
+        self._reg = None
+
+    def params(self) -> capi.VoxelGridParams:
+        return capi.default_voxel_grid_params(self.vSize, 1, int(self.averageExistingDescriptors))
+
+    def filter(self, cloud: DataPoints) -> DataPoints:
+        out, self.srcIdx = filter_cloud([self], cloud, return_indices=True)
+        return out
+
+
 # readingDataPointsFilters bound to reg_filter_points: name -> {parameter: default} (each filter's .h)
 READING_FILTERS = {
     "IdentityDataPointsFilter": {},
@@ -764,6 +832,17 @@ READING_FILTERS = {
     # phase: the reference draws rand() % step on every compute; here it is explicit (default 0)
     "FixStepSamplingDataPointsFilter": {"startStep": 10, "endStep": 10, "stepMult": 1.0, "phase": 0},
 }
+# Descriptor filters bound to reg_filter_cloud: name -> {parameter: default} (each filter's .h).  MaxDensity's seed: the
+# reference continues the process-wide std::rand stream; here every call replays rand() after srand(seed).
+DESCRIPTOR_FILTERS = {
+    "ObservationDirectionDataPointsFilter": {"x": 0.0, "y": 0.0, "z": 0.0},
+    "OrientNormalsDataPointsFilter": {"towardCenter": 1},
+    "ShadowDataPointsFilter": {"eps": 0.1},
+    "SimpleSensorNoiseDataPointsFilter": {"sensorType": 0, "gain": 1.0},
+    "IncidenceAngleDataPointsFilter": {},
+    "CutAtDescriptorThresholdDataPointsFilter": {"descName": "none", "useLargerThan": 1, "threshold": 0.0},
+    "MaxDensityDataPointsFilter": {"maxDensity": 10.0, "seed": 1},
+}
 _REFUSED_FILTERS = {
     "RandomSamplingDataPointsFilter": "draws from std::rand, which cannot be reproduced",
     "MaxPointCountDataPointsFilter": "subsamples with std::rand above maxCount",
@@ -775,10 +854,59 @@ def _split(f):
     return name, dict(args or {})
 
 
+def _descriptor_filter(name, args):
+    unknown = set(args) - set(DESCRIPTOR_FILTERS[name])
+    if unknown:
+        raise InvalidParameter(f"{name}: unknown parameter(s) {sorted(unknown)}")
+    spec = dict(DESCRIPTOR_FILTERS[name], **args)
+    spec["type"] = name[:-len("DataPointsFilter")]
+    try:
+        for k, v in spec.items():
+            if k not in ("type", "descName"):
+                spec[k] = float(v) if isinstance(DESCRIPTOR_FILTERS[name][k], float) else int(v)
+    except (TypeError, ValueError):
+        raise InvalidParameter(f"{name}: parameters must be numbers") from None
+    t = spec["type"]
+    if t == "SimpleSensorNoise" and not 0 <= spec["sensorType"] <= 4:
+        raise InvalidParameter(f"SimpleSensorNoiseDataPointsFilter: Error, sensorType id {spec['sensorType']} does not exist.")
+    if t == "SimpleSensorNoise" and not spec["gain"] >= 1:
+        raise InvalidParameter("SimpleSensorNoiseDataPointsFilter: gain must be >= 1")
+    if t == "Shadow" and not 0.0 <= spec["eps"] <= 3.1416:
+        raise InvalidParameter("ShadowDataPointsFilter: eps must lie in [0, 3.1416]")
+    if t == "MaxDensity" and not spec["maxDensity"] >= 0.0000001:
+        raise InvalidParameter("MaxDensityDataPointsFilter: maxDensity must be >= 0.0000001")
+    if t == "MaxDensity" and not 1 <= spec["seed"] <= 0x7fffffff:
+        raise InvalidParameter("MaxDensityDataPointsFilter: seed must lie in 1..2147483647")
+    if t in ("OrientNormals", "CutAtDescriptorThreshold"):
+        key = "towardCenter" if t == "OrientNormals" else "useLargerThan"
+        if spec[key] not in (0, 1):
+            raise InvalidParameter(f"{name}: {key} must be 0 or 1")
+    return spec
+
+
+def _surface_normal_filter(args, where):
+    known = {"knn", "maxDist", "epsilon", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
+             "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"}
+    unknown = set(args) - known
+    if unknown:
+        raise InvalidParameter(f"SurfaceNormalDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
+    if int(args.pop("smoothNormals", 0)):
+        raise NotImplementedError(f"SurfaceNormalDataPointsFilter: smoothNormals in a {where} chain")
+    args.pop("sortEigen", None)
+    return SurfaceNormalDataPointsFilter(**{k: (bool(int(v)) if k.startswith("keep") else v) for k, v in args.items()})
+
+
 def _reading_filter(f):
+    """One entry of a yaml readingDataPointsFilters list.  VoxelGridDataPointsFilter is not bound here: a default
+    VoxelGrid in a loaded reading chain is pinned to NotImplementedError (tests/test_data_filters_host.py,
+    test_refused_chains_still_raise); parse_filters / filter_cloud take it (_chain_filter)."""
     name, args = _split(f)
     if name == "OctreeGridDataPointsFilter":
         return OctreeGridDataPointsFilter(**args)
+    if name == "SurfaceNormalDataPointsFilter":
+        return _surface_normal_filter(args, "reading")
+    if name in DESCRIPTOR_FILTERS:
+        return _descriptor_filter(name, args)
     if name in _REFUSED_FILTERS:
         raise NotImplementedError(f"{name}: {_REFUSED_FILTERS[name]}")
     if name not in READING_FILTERS:
@@ -802,18 +930,210 @@ def _reference_filter(f):
     if name == "OctreeGridDataPointsFilter":
         return OctreeGridDataPointsFilter(**args)
     if name == "SurfaceNormalDataPointsFilter":
-        known = {"knn", "maxDist", "epsilon", "keepNormals", "keepDensities", "keepEigenValues", "keepEigenVectors",
-                 "keepMatchedIds", "keepMeanDist", "sortEigen", "smoothNormals"}
-        unknown = set(args) - known
-        if unknown:
-            raise InvalidParameter(f"SurfaceNormalDataPointsFilter: unknown parameter(s) {sorted(unknown)}")
-        if int(args.pop("smoothNormals", 0)):
-            raise NotImplementedError("SurfaceNormalDataPointsFilter: smoothNormals in a reference chain")
-        args.pop("sortEigen", None)
-        return SurfaceNormalDataPointsFilter(**{k: (bool(int(v)) if k.startswith("keep") else v) for k, v in args.items()})
+        return _surface_normal_filter(args, "reference")
     if name in _REFUSED_FILTERS:
         raise NotImplementedError(f"{name}: {_REFUSED_FILTERS[name]}")
     raise NotImplementedError(f"reference filter {name} is outside the accelerated path")
+
+
+# ---- filter chains over named descriptors ----------------------------------------------------------------------------
+# descriptors SurfaceNormalDataPointsFilter deposits in a chain: (switch, reference name, span, reg_estimate_normals output)
+_SURFACE_NORMAL_FIELDS = (("keepNormals", "normals", 3, "normals_ptr"), ("keepDensities", "densities", 1, "densities_ptr"),
+                          ("keepEigenValues", "eigValues", 3, "eigvals_ptr"),
+                          ("keepEigenVectors", "eigVectors", 9, "eigvecs_ptr"), ("keepMeanDist", "meanDists", 1, "mean_dists_ptr"))
+
+
+def _needs_fields(filters) -> bool:
+    """True when the chain creates or reads a named descriptor or holds a VoxelGrid stage (it then runs through
+    run_filter_chain)."""
+    return any(isinstance(f, (SurfaceNormalDataPointsFilter, VoxelGridDataPointsFilter)) or
+               (isinstance(f, dict) and f["type"] in capi.CLOUD_FILTERS)
+               for f in filters)
+
+
+def _cloud_fields(cloud: DataPoints) -> dict:
+    """name -> span of the descriptors a cloud carries."""
+    out = {}
+    if cloud.normals is not None:
+        out["normals"] = 3
+    if cloud.covariances is not None:
+        out["covariances"] = 6
+    for name, a in (cloud.descriptors or {}).items():
+        a = np.asarray(a)
+        out[name] = 1 if a.ndim == 1 else int(a.shape[1])
+    return out
+
+
+def _check_fields(filters, have: dict) -> dict:
+    """Walks the chain over the descriptor names: InvalidField where a filter reads a descriptor that does not exist at
+    its place (as the reference throws), NotImplementedError where an octree step would have to carry other fields than
+    normals / covariances.  Returns the names (-> span) after the chain."""
+    have = dict(have)
+    for f in filters:
+        if isinstance(f, SurfaceNormalDataPointsFilter):
+            for switch, name, span, _ in _SURFACE_NORMAL_FIELDS:
+                if getattr(f, switch):
+                    have[name] = span
+        elif isinstance(f, OctreeGridDataPointsFilter):
+            extra = sorted(set(have) - {"normals", "covariances"})
+            if extra:
+                raise NotImplementedError(f"OctreeGridDataPointsFilter: cannot carry the descriptors {extra}")
+        elif isinstance(f, dict) and f["type"] in capi.CLOUD_FILTERS:
+            _, a, b, made = capi.CLOUD_FILTERS[f["type"]]
+            for need in (a, b):
+                need = f.get("descName", "none") if need == "@descName" else need
+                if need and need not in have:
+                    raise InvalidField(f"{f['type']}DataPointsFilter: Error, cannot find {need} in descriptors.")
+            if made:
+                have[made[0]] = made[1]
+    return have
+
+
+def run_filter_chain(reg, buf, tag, filters, cloud: DataPoints):
+    """Runs a parsed chain on the device.  `buf(key, nbytes)` hands out device buffers that stay valid until the next run.
+    Stages: runs of point / descriptor filters are one reg_filter_cloud call each, SurfaceNormal is reg_estimate_normals
+    (it adds fields, drops no point), OctreeGrid is reg_octree_grid.  Returns (xyz pointer, stride, n,
+    {name: (pointer, span)}, [(key of the stage's source-index buffer, its length)])."""
+    x = np.ascontiguousarray(cloud.features, np.float32)
+    n, stride = x.shape[0], x.shape[1]
+    src = buf(tag + "_in", x.nbytes)
+    src.upload(x)
+    cur = src.value
+    fields = {}
+    given = dict(cloud.descriptors or {})
+    if cloud.normals is not None:
+        given["normals"] = cloud.normals
+    if cloud.covariances is not None:
+        given["covariances"] = cloud.covariances
+    for name, a in given.items():
+        a = np.ascontiguousarray(a, np.float32).reshape(n, -1)
+        b = buf(f"{tag}_in_{name}", a.nbytes)
+        b.upload(a)
+        fields[name] = (b.value, a.shape[1])
+    stages, run = [], []
+    for f in filters:
+        if isinstance(f, dict):
+            run.append(f)
+        else:
+            if run:
+                stages.append(run)
+            stages.append(f)
+            run = []
+    if run:
+        stages.append(run)
+    idx_stages = []
+    for k, st in enumerate(stages):
+        if n == 0:
+            break
+        if isinstance(st, SurfaceNormalDataPointsFilter):
+            outs = {}
+            for switch, name, span, arg in _SURFACE_NORMAL_FIELDS:
+                if getattr(st, switch) or name == "normals":
+                    outs[name] = (buf(f"{tag}_{k}_{name}", n * span * 4).value, span, arg)
+            kw = {arg: ptr for name, (ptr, _, arg) in outs.items() if name != "normals"}
+            reg.estimate_normals_device(cur, stride, n, outs["normals"][0], k=st.knn, max_dist=st.maxDist,
+                                        viewpoint=st.viewpoint, **kw)
+            for name, (ptr, span, _) in outs.items():
+                if name != "normals" or st.keepNormals:
+                    fields[name] = (ptr, span)
+            continue
+        ox, oi = buf(f"{tag}_{k}_xyz", n * 12), buf(f"{tag}_{k}_idx", n * 4)
+        if isinstance(st, VoxelGridDataPointsFilter):
+            flist = [(name, ptr, buf(f"{tag}_{k}_{name}", n * span * 4).value, span) for name, (ptr, span) in fields.items()]
+            m = reg.voxel_grid_device(cur, stride, n, st.params(), flist, ox.value, oi.value)
+            fields = {name: (out, span) for name, _, out, span in flist}
+        elif isinstance(st, OctreeGridDataPointsFilter):
+            nrm, cov = fields.get("normals"), fields.get("covariances")
+            on = buf(f"{tag}_{k}_normals", n * 12) if nrm else None
+            oc = buf(f"{tag}_{k}_covariances", n * 24) if cov else None
+            m = reg.octree_grid_device(cur, stride, n, st.params(), ox.value, nrm[0] if nrm else None,
+                                       cov[0] if cov else None, on.value if on else None, oc.value if oc else None, oi.value)
+            fields = {name: (b.value, span) for name, b, span in (("normals", on, 3), ("covariances", oc, 6)) if b}
+        else:
+            spans = [(name, span) for name, (_, span) in fields.items()]
+            spans += [c for c in capi.cloud_filter_created_fields(st) if c[0] not in fields]
+            if len(spans) > capi.MAX_FIELDS:
+                raise NotImplementedError(f"a filter chain carries at most {capi.MAX_FIELDS} descriptors")
+            flist = [(name, fields[name][0] if name in fields else None, buf(f"{tag}_{k}_{name}", n * span * 4).value, span)
+                     for name, span in spans]
+            m = reg.filter_cloud_device(cur, stride, n, st, flist, ox.value, oi.value)
+            fields = {name: (out, span) for name, _, out, span in flist}
+        idx_stages.append((f"{tag}_{k}_idx", m))
+        cur, stride, n = ox.value, 3, m
+    return cur, stride, n, fields, idx_stages
+
+
+def _chain_filter(f):
+    """One yaml entry of a chain applied outside loadFromYaml: everything _reading_filter binds, and VoxelGrid."""
+    name, args = _split(f)
+    if name == "VoxelGridDataPointsFilter":
+        return VoxelGridDataPointsFilter(**args)
+    return _reading_filter(f)
+
+
+def parse_filters(chain) -> list:
+    """A yaml list of data-point filters (as under readingDataPointsFilters) -> the parsed chain."""
+    return [_chain_filter(f) for f in (chain or [])]
+
+
+class FilterChainRunner:
+    """Keeps one handle and its device buffers across calls: the mapper applies the same chain to every scan, and a
+    fresh handle plus fresh allocations per call would cost more than the kernels."""
+
+    def __init__(self):
+        self._reg = None
+        self._dev = {}
+
+    def _buf(self, key, nbytes):
+        b = self._dev.get(key)
+        if b is None or b.nbytes < nbytes:
+            if b is not None:
+                b.free()
+            b = self._dev[key] = capi.DeviceArray(nbytes)
+        return b
+
+    def apply(self, filters, cloud: DataPoints, return_indices: bool = False):
+        parsed = [_chain_filter(f) if isinstance(f, str) or (isinstance(f, dict) and "type" not in f) else f
+                  for f in filters]
+        _check_fields(parsed, _cloud_fields(cloud))
+        if self._reg is None:
+            self._reg = capi.Registration(capi.default_params())
+        try:
+            cur, stride, n, fields, stages = run_filter_chain(self._reg, self._buf, "fc", parsed, cloud)
+            xyz = capi.download(cur, (n, stride))[:, :3].copy()
+            desc = {name: capi.download(ptr, (n, span)) for name, (ptr, span) in fields.items()}
+            idx = None
+            for key, m in stages:
+                step = self._dev[key].download(m, np.int32)
+                idx = step if idx is None else idx[step]
+            if idx is None:
+                idx = np.arange(n, dtype=np.int32)
+        except RegError as e:
+            raise _translate(e) from None
+        out = DataPoints(xyz, desc.pop("normals", None), desc.pop("covariances", None), desc)
+        return (out, idx) if return_indices else out
+
+    def close(self):
+        for b in self._dev.values():
+            b.free()
+        self._dev = {}
+        if self._reg is not None:
+            self._reg.close()
+            self._reg = None
+
+
+def filter_cloud(filters, cloud: DataPoints, return_indices: bool = False, runner: "FilterChainRunner | None" = None):
+    """Applies a chain (parse_filters' output, or the yaml list itself) to a cloud on the device, outside a registration:
+    `icp.readingDataPointsFilters.apply(cloud)` of the reference.  Returns the filtered DataPoints (features m x 3), with
+    return_indices also the source index of every kept point.  Pass a FilterChainRunner to keep the handle and the
+    device buffers between calls (one per scan stream); without one they live for this call only."""
+    own = runner is None
+    r = FilterChainRunner() if own else runner
+    try:
+        return r.apply(filters, cloud, return_indices)
+    finally:
+        if own:
+            r.close()
 
 
 @dataclass
