@@ -142,6 +142,58 @@ public:
         return out;
     }
 
+    // ---- submap-pair constraints (constraint_builders.cpp:43-90, PlaceRecognition.cpp:97-149) -----------------------------
+    // The front of buildConstraint in one call (reg_set_pair_overlap_f64): computeIndicesOfOverlappingPoints at
+    // sourceToTarget (column-major double[16] == Eigen::Matrix4d::data(), nullptr: identity), SelectByIndex + fp32 cast on
+    // the device, the selected target as the reference and the selected source as the reading.  Open3D's fp64 arrays:
+    // points / normals n x 3, covariances n x 9 doubles (nullptr where the cost does not need them).  Then registerPair()
+    // and informationMatrix(); an empty overlap throws std::runtime_error (REG_EMPTY_TARGET).
+    struct PairOverlap { int64_t n_source; int64_t n_target; };
+    PairOverlap setPairOverlap(const double* srcPoints, const double* srcNormals, const double* srcCovs, int64_t n,
+                               const double* tgtPoints, const double* tgtNormals, const double* tgtCovs, int64_t m,
+                               bool on_device, const double* sourceToTarget, double voxelSize,
+                               int32_t minNumPointsPerVoxel = 1) {
+        ensure();
+        matcherIsInitialized_ = false;
+        pair_ = PairOverlap{0, 0};
+        check(reg_set_pair_overlap_f64(h_, srcPoints, srcNormals, srcCovs, n, tgtPoints, tgtNormals, tgtCovs, m,
+                                       on_device ? 1 : 0, sourceToTarget, voxelSize, minNumPointsPerVoxel, &pair_.n_source,
+                                       &pair_.n_target));
+        matcherIsInitialized_ = true;
+        return pair_;
+    }
+    // registration of the pair set by setPairOverlap, from T_init
+    TransformationParameters registerPair(const TransformationParameters& T_init) {
+        ensure();
+        TransformationParameters out = T_init;
+        check(reg_register(h_, T_init.data(), out.data(), &last_));
+        return out;
+    }
+    // GetInformationMatrixFromPointClouds on the clouds currently set (row-major 6 x 6, rotation first); *nPairs: the
+    // number of correspondences within the distance that the sum ran over
+    std::array<double, 36> informationMatrix(const TransformationParameters& T, float maxCorrespondenceDistance,
+                                             int64_t* nPairs = nullptr) {
+        ensure();
+        std::array<double, 36> info{};
+        int64_t n_pairs = 0;
+        check(reg_information_matrix(h_, T.data(), maxCorrespondenceDistance, info.data(), &n_pairs));
+        if (nPairs) *nPairs = n_pairs;
+        return info;
+    }
+    // positions of the selected points in the clouds given to setPairOverlap (SelectByIndex's index lists, ascending)
+    std::vector<int32_t> pairSourceIndices() {
+        ensure();
+        std::vector<int32_t> idx((size_t)pair_.n_source);
+        if (!idx.empty()) check(reg_get_source_source_indices(h_, idx.data()));
+        return idx;
+    }
+    std::vector<int32_t> pairTargetIndices() {
+        ensure();
+        std::vector<int32_t> idx((size_t)pair_.n_target);
+        if (!idx.empty()) check(reg_get_target_source_indices(h_, idx.data()));
+        return idx;
+    }
+
     // ---- one process per GPU, reading partitioned over the group (BASELINE config C4) --------------------------------
     // Rank 0 creates the 128-byte id (ICP::makeGroupId) and hands it to the other ranks; every rank joins with its rank.
     static std::array<char, REG_DIST_ID_BYTES> makeGroupId() {
@@ -221,8 +273,42 @@ private:
     bool has_ternary_ = false;
     reg_handle* h_ = nullptr;
     reg_result last_{};
+    PairOverlap pair_{0, 0};
     bool matcherIsInitialized_ = false;
 };
+
+// o3d_slam::computeIndicesOfOverlappingPoints (helpers.cpp:320-345) on the device (reg_overlap_indices): the ascending
+// indices of the points of either fp64 cloud (n x 3 / m x 3 doubles, host memory) whose voxel holds at least
+// minNumPointsPerVoxel points of the target and of the source moved by sourceToTarget (column-major double[16], nullptr:
+// identity).  The reference emits the lists in std::unordered_map order.
+struct OverlapIndices { std::vector<int32_t> source, target; };
+inline OverlapIndices overlapIndices(const double* source, int64_t n, const double* target, int64_t m,
+                                     const double* sourceToTarget, double voxelSize, int32_t minNumPointsPerVoxel = 1,
+                                     int device = 0) {
+    reg_params p;
+    reg_default_params(&p);
+    p.cost = REG_COST_O3D_P2P;   // no field requirements: the handle only lends its stream and workspace
+    p.device = device;
+    reg_handle* h = nullptr;
+    reg_status s = reg_create(&p, &h);
+    OverlapIndices out;
+    std::string msg;
+    if (s == REG_OK) {
+        out.source.resize((size_t)(n > 0 ? n : 0));
+        out.target.resize((size_t)(m > 0 ? m : 0));
+        int64_t ns = 0, nt = 0;
+        s = reg_overlap_indices(h, source, n, target, m, 0, sourceToTarget, voxelSize, minNumPointsPerVoxel, out.source.data(),
+                                &ns, out.target.data(), &nt);
+        out.source.resize((size_t)ns);
+        out.target.resize((size_t)nt);
+    }
+    if (s != REG_OK) msg = h ? reg_last_error(h) : "reg_create rejected the parameters";
+    if (h) reg_destroy(h);
+    if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+    if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+    if (s != REG_OK) throw std::runtime_error(msg);
+    return out;
+}
 
 // SurfaceNormalDataPointsFilter (DataPointsFilters/SurfaceNormal.cpp:152-252) on the device: exact k-NN (the point
 // itself included) + PCA.  Outputs are written to caller-owned arrays laid out like the `normals` (3 x N),

@@ -774,6 +774,51 @@ REG_API reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const
 REG_API reg_status reg_information_matrix(reg_handle* h, const float T[16], float max_dist, double info[36],
                                          int64_t* n_pairs);
 
+/* ---- voxel-overlap selection and the submap-pair front of the constraint builders -----
+   Every pose-graph constraint between two submaps starts with the same chain (open3d_slam/src/constraint_builders.cpp:43-90,
+   PlaceRecognition.cpp:97-149): computeIndicesOfOverlappingPoints (helpers.cpp:320-345), SelectByIndex on both clouds,
+   one registration, GetInformationMatrixFromPointClouds on the reduced clouds.  These entry points are the first two
+   steps; reg_register and reg_information_matrix are the other two.
+
+   Numeric contract: fp64, one rounding per operation (the build forbids contraction).
+     transformed source point, T with rows r0..r3 (helpers.cpp:302-303: T * (x, y, z, 1), head<3>() / w):
+         w  = ((T30*x + T31*y) + T32*z) + T33
+         x' = (((T00*x + T01*y) + T02*z) + T03) / w          (y', z' alike)
+       The reference transforms with Open3D's own PointCloud::Transform, which is not in the reference tree: PARITY of this
+       line is UNPINNED; the formula above is that of the tree's own transform helper.  T_src_to_tgt == NULL is identity
+       and runs no transform pass; identity through the formula reproduces finite inputs exactly, so the two agree.
+       T_src_to_tgt: const double[16], column-major (Eigen::Matrix4d::data()).
+     voxel key, per axis: floor(p * (1.0 / voxel_size)) (VoxelHashMap.hpp:43-51), the key of reg_voxelize_within_volume and
+       reg_carve_indices; 21 bits per axis, offset binary.
+     invalid keys: a non-finite coordinate or a voxel index outside +-2^20, in the target or in the transformed source,
+       returns REG_BAD_ARGUMENT (the reference casts to int there: undefined behaviour).
+     selected voxels: at least min_points_per_voxel points of the target AND of the transformed source;
+       min_points_per_voxel >= 1 or REG_BAD_ARGUMENT (assert_ge, helpers.cpp:323).
+     result: every point of either cloud that lies in a selected voxel.  Source indices refer to the untransformed source.
+       Both lists ascend (the reference emits them in std::unordered_map order, which is unspecified; as reg_carve_indices).
+   Common rules: on_device covers all cloud arrays of a call (and the index outputs of reg_overlap_indices);
+   n, m <= 2^31 - 1; voxel_size <= 0 or non-finite returns REG_BAD_ARGUMENT.
+
+   reg_overlap_indices: the index query.  n == 0 or m == 0, or clouds that share no voxel, return REG_OK with both counts 0. */
+REG_API reg_status reg_overlap_indices(reg_handle* h, const double* src_xyz, int64_t n, const double* tgt_xyz, int64_t m,
+                                       int on_device, const double T_src_to_tgt[16] /* NULL: identity */, double voxel_size,
+                                       int32_t min_points_per_voxel, int32_t* src_idx /* capacity n */, int64_t* n_src,
+                                       int32_t* tgt_idx /* capacity m */, int64_t* n_tgt);
+/* reg_set_pair_overlap_f64: the whole front of buildConstraint in one call, both clouds on the device throughout: overlap
+   flags, order-preserving compaction with the fp64 -> fp32 cast of reg_set_target_f64 (normals m x 3, covs m x 9 doubles,
+   may be NULL), the search table on the selected target (as reg_set_target), the selected source as the reading (as
+   reg_set_source).  Field requirements are those of reg_set_target / reg_set_source for the handle's cost
+   (REG_MISSING_FIELD).  An empty overlap -- an empty cloud included -- returns REG_EMPTY_TARGET, as an empty crop does, and
+   leaves the handle without reference and reading.  reg_get_target_source_indices maps reference ids back to tgt_xyz,
+   reg_get_source_source_indices reading indices to src_xyz (idx[n_src_kept]); after a plain reg_set_source* the latter
+   fails with REG_NOT_CONFIGURED, as the former does after a plain reg_set_target. */
+REG_API reg_status reg_set_pair_overlap_f64(reg_handle* h, const double* src_xyz, const double* src_normals,
+                                            const double* src_covs, int64_t n, const double* tgt_xyz, const double* tgt_normals,
+                                            const double* tgt_covs, int64_t m, int on_device, const double T_src_to_tgt[16],
+                                            double voxel_size, int32_t min_points_per_voxel, int64_t* n_src_kept,
+                                            int64_t* n_tgt_kept);
+REG_API reg_status reg_get_source_source_indices(reg_handle* h, int32_t* idx);
+
 /* Introspection of the search structure (tests, DESIGN.md numbers). */
 typedef struct {
     int64_t n_points;

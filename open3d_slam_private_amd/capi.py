@@ -334,7 +334,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_host_ternary_decide", "reg_host_partial_constraint", "reg_host_solve6_xicp_rhs",
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks",
-           "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid"]
+           "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid",
+           "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices"]
 
 
 def lib_path() -> str:
@@ -411,6 +412,11 @@ def load_library():
                                       C.c_double, C.c_double, C.c_double, C.c_double, vp, C.POINTER(C.c_int64)]
     lib.reg_voxelize_within_volume.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.POINTER(RegCrop), C.c_double, vp, vp, vp,
                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.reg_overlap_indices.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int32, vp,
+                                        C.POINTER(C.c_int64), vp, C.POINTER(C.c_int64)]
+    lib.reg_set_pair_overlap_f64.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, C.c_int, C.POINTER(C.c_double), C.c_double,
+                                             C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.reg_get_source_source_indices.argtypes = [vp, vp]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -747,6 +753,14 @@ def _T_in(T):
     return np.ascontiguousarray(T.T).reshape(16)
 
 
+def _T_in_f64(T):
+    """numpy 4x4 (math layout) -> column-major double[16] (== Eigen::Matrix4d::data()); None stays NULL (identity)."""
+    if T is None:
+        return None
+    T = np.asarray(T, dtype=np.float64).reshape(4, 4)
+    return (C.c_double * 16)(*T.T.reshape(16))
+
+
 def _T_out(buf):
     return np.array(buf, dtype=np.float32).reshape(4, 4).T.copy()
 
@@ -887,6 +901,63 @@ class Registration:
         idx = np.empty(self.n_target_kept, np.int32)
         self._check(self._lib.reg_get_target_source_indices(self._h, _ptr(idx)))
         return idx
+
+    # ---- voxel overlap of two clouds / the submap-pair front of the constraint builders ----
+    def overlap_indices(self, src_xyz, tgt_xyz, voxel_size, T=None, min_points=1):
+        """computeIndicesOfOverlappingPoints (helpers.cpp:320-345) on the device: ascending indices (src_idx, tgt_idx) of
+        the points of either fp64 cloud whose voxel holds >= min_points points of the target and of the source moved by
+        `T` (4x4 sourceToTarget; None: identity)."""
+        s = np.ascontiguousarray(src_xyz, np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(tgt_xyz, np.float64).reshape(-1, 3)
+        si, ti = np.empty(max(s.shape[0], 1), np.int32), np.empty(max(t.shape[0], 1), np.int32)
+        ns, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_overlap_indices(self._h, _ptr(s), s.shape[0], _ptr(t), t.shape[0], 0, _T_in_f64(T),
+                                                  float(voxel_size), int(min_points), _ptr(si), C.byref(ns), _ptr(ti),
+                                                  C.byref(nt)))
+        return si[:int(ns.value)].copy(), ti[:int(nt.value)].copy()
+
+    def overlap_indices_device(self, src_ptr, n, tgt_ptr, m, voxel_size, src_idx_ptr, tgt_idx_ptr, T=None, min_points=1):
+        """As overlap_indices with both fp64 clouds and both int32 index outputs (capacity n / m) resident in HBM.
+        Returns (n_src, n_tgt)."""
+        ns, nt = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_overlap_indices(self._h, C.c_void_p(src_ptr), n, C.c_void_p(tgt_ptr), m, 1, _T_in_f64(T),
+                                                  float(voxel_size), int(min_points), C.c_void_p(src_idx_ptr), C.byref(ns),
+                                                  C.c_void_p(tgt_idx_ptr), C.byref(nt)))
+        return int(ns.value), int(nt.value)
+
+    def set_pair_overlap_f64(self, src_xyz, tgt_xyz, voxel_size, T=None, min_points=1, src_normals=None, src_covs=None,
+                             tgt_normals=None, tgt_covs=None):
+        """The front of buildConstraint (constraint_builders.cpp:51-58) in one call: overlap selection of the two fp64
+        clouds, SelectByIndex + fp32 cast on the device, the selected target as the reference and the selected source as
+        the reading.  Returns (n_src_kept, n_tgt_kept)."""
+        f64 = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w) if a is not None else None
+        s, sn, sc = f64(src_xyz, 3), f64(src_normals, 3), f64(src_covs, 9)
+        t, tn, tc = f64(tgt_xyz, 3), f64(tgt_normals, 3), f64(tgt_covs, 9)
+        return self._set_pair(_ptr(s), _ptr(sn), _ptr(sc), s.shape[0], _ptr(t), _ptr(tn), _ptr(tc), t.shape[0], 0,
+                              voxel_size, T, min_points)
+
+    def set_pair_overlap_f64_device(self, src_ptr, n, tgt_ptr, m, voxel_size, T=None, min_points=1, src_nrm_ptr=None,
+                                    src_cov_ptr=None, tgt_nrm_ptr=None, tgt_cov_ptr=None):
+        """As set_pair_overlap_f64 with the fp64 arrays already resident in HBM (xyz / normals x 3, covs x 9 doubles)."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._set_pair(vp(src_ptr), vp(src_nrm_ptr), vp(src_cov_ptr), n, vp(tgt_ptr), vp(tgt_nrm_ptr),
+                              vp(tgt_cov_ptr), m, 1, voxel_size, T, min_points)
+
+    def _set_pair(self, s, sn, sc, n, t, tn, tc, m, on_device, voxel_size, T, min_points):
+        ks, kt = C.c_int64(0), C.c_int64(0)
+        st = self._lib.reg_set_pair_overlap_f64(self._h, s, sn, sc, n, t, tn, tc, m, on_device, _T_in_f64(T),
+                                                float(voxel_size), int(min_points), C.byref(ks), C.byref(kt))
+        # n_target_kept sizes target_source_indices() (as after set_target_f64), n_source_kept source_source_indices()
+        self.n_source_kept, self.n_target_kept = int(ks.value), int(kt.value)
+        self.n_source = self.n_source_kept if st == 0 else 0
+        self._check(st)
+        return self.n_source_kept, self.n_target_kept
+
+    def source_source_indices(self):
+        """Position of every reading point in the source cloud given to set_pair_overlap_f64."""
+        idx = np.empty(max(getattr(self, "n_source_kept", 0), 1), np.int32)
+        self._check(self._lib.reg_get_source_source_indices(self._h, _ptr(idx)))
+        return idx[:self.n_source_kept]
 
     def set_source(self, xyz, normals=None, covs=None):
         xyz = _f32(xyz)

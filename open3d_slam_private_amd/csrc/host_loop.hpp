@@ -1431,16 +1431,21 @@ reg_status reg_information_matrix(reg_handle* h, const float T[16], float max_di
     s = enqueue_match(h, /*zero_hist=*/false);
     if (s != REG_OK) return s;
     h->have_match = true;
-    HIPCHK(h, h->i_sums.reserve(kSums * 8));
-    HIPCHK(h, hipMemsetAsync(h->i_sums.p, 0, 10 * sizeof(double), h->stream));
+    // one row of sums per workgroup, added up here in block order: the same clouds give the same 36 doubles on every call
+    // and on every handle (a device-side atomic sum would depend on the order in which the workgroups retire)
     const int blocks = (int)std::min<int64_t>(512, (h->n + 255) / 256);
+    HIPCHK(h, h->i_info.reserve((size_t)512 * 10 * sizeof(double)));
+    HIPCHK(h, hipMemsetAsync(h->i_info.p, 0, (size_t)blocks * 10 * sizeof(double), h->stream));
     k_info_sums<<<blocks, 256, 0, h->stream>>>(h->i_pos.as<int>(), h->i_d2.as<float>(), h->n, h->t_pts.as<float4>(),
                                                h->c_ref[0], h->c_ref[1], h->c_ref[2], max_dist * max_dist,
-                                               h->i_sums.as<double>());
-    double m[10];
-    HIPCHK(h, hipMemcpyAsync(m, h->i_sums.p, sizeof(m), hipMemcpyDeviceToHost, h->stream));
+                                               h->i_info.as<double>());
+    std::vector<double> rows((size_t)blocks * 10);
+    HIPCHK(h, hipMemcpyAsync(rows.data(), h->i_info.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
+    double m[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int b = 0; b < blocks; ++b)
+        for (int k = 0; k < 10; ++k) m[k] += rows[(size_t)b * 10 + k];
     // sum over pairs of G^T G with rows [0 z -y 1 0 0], [-z 0 x 0 1 0], [y -x 0 0 0 1]
     const double c = m[0], sx = m[1], sy = m[2], sz = m[3], xx = m[4], yy = m[5], zz = m[6], xy = m[7], xz = m[8], yz = m[9];
     const double I[36] = {yy + zz, -xy, -xz, 0, -sz, sy,

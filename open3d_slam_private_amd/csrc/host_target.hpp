@@ -123,6 +123,11 @@ struct reg_handle {
     int64_t crop_kept = 0;
     DevBuf v_fout, v_oout, v_oxyz, v_onrm, v_ocov;   // reg_voxelize_within_volume
     DevBuf v_ukeys, v_ustart;                        // reg_carve_indices
+    // reg_overlap_indices / reg_set_pair_overlap_f64 (host_overlap.hpp): per layer (0: source, 1: target) keys, sorted keys,
+    // unique keys + counts, flags + offsets; run counts and the invalid-key word; rocPRIM's storage; the reading's index map
+    DevBuf ov_keys[2], ov_sorted, ov_ukeys[2], ov_ucnt[2], ov_flags[2], ov_offs[2], ov_misc, ov_tmp, ov_sidx;
+    DevBuf i_info;                                   // reg_information_matrix: one row of sums per workgroup
+    int64_t src_kept = 0;                            // > 0: ov_sidx maps the current reading back (reg_set_pair_overlap_f64)
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;
@@ -246,6 +251,31 @@ static inline bool pm_needs_tnrm(const reg_handle* h) {
            (h->pm.use_robust && h->pm.distance_type == REG_DIST_POINT2PLANE);
 }
 
+// The fields the handle's cost needs on the reference / on the reading (reg_set_target, reg_set_source, reg_set_pair_overlap_f64)
+static reg_status check_target_fields(reg_handle* h, bool has_nrm, bool has_cov) {
+    if ((h->prm.cost == REG_COST_P2PL || h->prm.cost == REG_COST_O3D_P2PL) && !has_nrm && !h->structure_only &&
+        !(h->pm_on && !pm_needs_tnrm(h))) {
+        h->err = "InvalidField: point-to-plane needs the `normals` descriptor on the reference";
+        return REG_MISSING_FIELD;
+    }
+    if (h->prm.cost == REG_COST_GICP && !has_cov && !h->structure_only) {
+        h->err = "InvalidField: GICP needs covariances on the reference";
+        return REG_MISSING_FIELD;
+    }
+    return REG_OK;
+}
+static reg_status check_source_fields(reg_handle* h, bool has_nrm, bool has_cov) {
+    if (h->prm.cost == REG_COST_P2PL && h->prm.use_surface_normal && !has_nrm) {
+        h->err = "InvalidField: SurfaceNormalOutlierFilter needs the `normals` descriptor on the reading";
+        return REG_MISSING_FIELD;
+    }
+    if (h->prm.cost == REG_COST_GICP && !has_cov) {
+        h->err = "InvalidField: GICP needs covariances on the reading";
+        return REG_MISSING_FIELD;
+    }
+    return REG_OK;
+}
+
 extern "C" {
 
 void reg_default_params(reg_params* p) {
@@ -354,6 +384,7 @@ void reg_destroy(reg_handle* h) {
     h->n_out.release();
     h->i_xicp.release();
     for (DevBuf* b : {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov, &h->c_flags, &h->c_offs, &h->c_xyz, &h->c_nrm, &h->c_cov, &h->c_idx, &h->v_fout, &h->v_oout, &h->v_oxyz, &h->v_onrm, &h->v_ocov, &h->v_ukeys, &h->v_ustart, &h->d_d2all, &h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov, &h->r_xyz, &h->r_nrm, &h->r_cov}) b->release();
+    for (DevBuf* b : {&h->ov_keys[0], &h->ov_keys[1], &h->ov_sorted, &h->ov_ukeys[0], &h->ov_ukeys[1], &h->ov_ucnt[0], &h->ov_ucnt[1], &h->ov_flags[0], &h->ov_flags[1], &h->ov_offs[0], &h->ov_offs[1], &h->ov_misc, &h->ov_tmp, &h->ov_sidx, &h->i_info}) b->release();
     h->n_eig.release();
     h->n_cov.release();
     h->n_ids.release();
@@ -743,15 +774,7 @@ static reg_status set_target_impl(reg_handle* h, const float* xyz, int64_t xyz_s
         return REG_EMPTY_TARGET;
     }
     if (!xyz || xyz_stride < 3 || (nrm && nrm_stride < 3) || m > 0x7fffffffLL) return REG_BAD_ARGUMENT;
-    if ((h->prm.cost == REG_COST_P2PL || h->prm.cost == REG_COST_O3D_P2PL) && !nrm && !h->structure_only &&
-        !(h->pm_on && !pm_needs_tnrm(h))) {
-        h->err = "InvalidField: point-to-plane needs the `normals` descriptor on the reference";
-        return REG_MISSING_FIELD;
-    }
-    if (h->prm.cost == REG_COST_GICP && !cov && !h->structure_only) {
-        h->err = "InvalidField: GICP needs covariances on the reference";
-        return REG_MISSING_FIELD;
-    }
+    if (const reg_status fs = check_target_fields(h, nrm != nullptr, cov != nullptr)) return fs;
     HIPCHK(h, hipSetDevice(h->prm.device));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     const float* d_xyz = xyz;
@@ -1411,6 +1434,7 @@ reg_status reg_set_source(reg_handle* h, const float* xyz, int64_t xyz_stride, c
     if (!h) return REG_BAD_ARGUMENT;
     if (!h->device_ok) return REG_DEVICE_ERROR;
     h->n = 0;
+    h->src_kept = 0;
     h->prepared = false;
     h->have_match = false;
     h->pm_have_match = false;
@@ -1419,14 +1443,7 @@ reg_status reg_set_source(reg_handle* h, const float* xyz, int64_t xyz_stride, c
         return REG_EMPTY_SOURCE;
     }
     if (!xyz || xyz_stride < 3 || (nrm && nrm_stride < 3) || n > 0x7fffffffLL) return REG_BAD_ARGUMENT;
-    if (h->prm.cost == REG_COST_P2PL && h->prm.use_surface_normal && !nrm) {
-        h->err = "InvalidField: SurfaceNormalOutlierFilter needs the `normals` descriptor on the reading";
-        return REG_MISSING_FIELD;
-    }
-    if (h->prm.cost == REG_COST_GICP && !cov) {
-        h->err = "InvalidField: GICP needs covariances on the reading";
-        return REG_MISSING_FIELD;
-    }
+    if (const reg_status fs = check_source_fields(h, nrm != nullptr, cov != nullptr)) return fs;
     HIPCHK(h, hipSetDevice(h->prm.device));
     HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
     // packed private copies (the reference deep-copies the reading, ICP.cpp:952)

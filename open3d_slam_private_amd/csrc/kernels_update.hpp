@@ -782,7 +782,7 @@ __global__ void k_unpermute_f32(const float* __restrict__ in, int64_t n, const u
 // point in the reference's own frame (sorted point + centroid): count, x, y, z, xx, yy, zz, xy, xz, yz.
 __global__ void __launch_bounds__(256)
 k_info_sums(const int* __restrict__ pos, const float* __restrict__ d2, int64_t n, const float4* __restrict__ tgt,
-            float cx, float cy, float cz, float max_d2, double* __restrict__ out /* [10], zeroed */) {
+            float cx, float cy, float cz, float max_d2, double* __restrict__ out /* [gridDim.x][10], zeroed */) {
     double v[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) v[k] = 0.0;
@@ -802,5 +802,5 @@ k_info_sums(const int* __restrict__ pos, const float* __restrict__ d2, int64_t n
         v[8] += x * z;
         v[9] += y * z;
     }
-    xicp_block_add<10>(v, out);
+    xicp_block_add<10>(v, out + 10 * blockIdx.x);   // one adder per row: the host sums the rows in block order
 }

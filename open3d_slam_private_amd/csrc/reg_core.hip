@@ -50,6 +50,7 @@ using namespace o3dreg;
 #include "kernels_pmoutliers.hpp"
 #include "kernels_filters.hpp"
 #include "kernels_octree.hpp"
+#include "kernels_overlap.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
@@ -59,6 +60,7 @@ using namespace o3dreg;
 #include "host_filters.hpp"
 #include "host_octree.hpp"
 #include "host_cloud_filters.hpp"
+#include "host_overlap.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

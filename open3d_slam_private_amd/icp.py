@@ -8,6 +8,9 @@
   RegistrationIcpPointToPlane  <-> o3d_slam::RegistrationIcpPointToPlane (CloudRegistration.cpp:54-83)
   RegistrationIcpPointToPoint  <-> o3d_slam::RegistrationIcpPointToPoint (CloudRegistration.cpp:84-101)
   cloudRegistrationFactory     <-> o3d_slam::cloudRegistrationFactory (CloudRegistration.cpp:104-119)
+  computeIndicesOfOverlappingPoints <-> o3d_slam::computeIndicesOfOverlappingPoints (helpers.cpp:320-345)
+  buildConstraint              <-> o3d_slam::buildConstraint (constraint_builders.cpp:43-90)
+  refineLoopClosure            <-> the refinement of a loop-closure candidate (PlaceRecognition.cpp:97-149)
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -1156,7 +1159,7 @@ class RegistrationIcpGeneralized:
         self.relative_rmse_ = 1e-6
         self._reg = None
 
-    def registerClouds(self, source: DataPoints, target: DataPoints, init=None) -> RegistrationResult:
+    def params(self) -> RegParams:
         p = capi.default_params()
         p.cost = capi.COST_GICP
         p.use_trimmed = 0
@@ -1167,7 +1170,10 @@ class RegistrationIcpGeneralized:
         p.gicp_stop_rule = 1
         p.gicp_rel_fitness = self.relative_fitness_
         p.gicp_rel_rmse = self.relative_rmse_
-        reg = capi.Registration(p)
+        return p
+
+    def registerClouds(self, source: DataPoints, target: DataPoints, init=None) -> RegistrationResult:
+        reg = capi.Registration(self.params())
         try:
             reg.set_target(target.features, None, target.covariances)
             reg.set_source(source.features, None, source.covariances)
@@ -1285,3 +1291,163 @@ def cloudRegistrationFactory(name_or_enum, maxCorrespondenceDistance_=0.2, maxNu
     if kind == 2 and not isinstance(kind, bool):
         return RegistrationIcpGeneralized(maxCorrespondenceDistance_, maxNumIter_)
     raise RuntimeError("cloud: unknown type of cloud registration")
+
+
+# ---- submap-pair constraints (constraint_builders.cpp:43-90, PlaceRecognition.cpp:97-149) ----------------------
+ICP_RUN_UNTIL_CONVERGENCE_ITERATIONS = 100   # magic::icpRunUntilConvergenceNumberOfIterations (constraint_builders.cpp:63)
+
+
+@dataclass
+class Constraint:
+    """o3d_slam::Constraint, the fields the two builders fill (constraint_builders.cpp:75-82, PlaceRecognition.cpp:140-150)."""
+    sourceSubmapIdx_: int = 0
+    targetSubmapIdx_: int = 0
+    sourceToTarget_: np.ndarray = field(default_factory=lambda: np.eye(4))
+    informationMatrix_: np.ndarray = field(default_factory=lambda: np.eye(6))
+    isInformationMatrixValid_: bool = False
+    isOdometryConstraint_: bool = False
+
+
+def _xyz64(cloud, what):
+    a = np.asarray(cloud.features if isinstance(cloud, DataPoints) else cloud)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise InvalidParameter(f"{what}: points must be N x 3 (or N x 4 homogeneous), got shape {a.shape}")
+    return np.ascontiguousarray(a[:, :3], np.float64)
+
+
+def _field64(a, n, width, what):
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape != (n, width):
+        raise InvalidParameter(f"{what} must be {n} x {width}, got shape {a.shape}")
+    return np.ascontiguousarray(a, np.float64)
+
+
+def _covs9(c6):
+    """DataPoints.covariances (xx xy xz yy yz zz) -> Open3D's row-major Matrix3d."""
+    return None if c6 is None else np.ascontiguousarray(c6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]])
+
+
+def _check_overlap_args(sourceToTarget, voxelSize, minNumPointsPerVoxel):
+    if not (isinstance(voxelSize, (int, float, np.floating, np.integer)) and math.isfinite(voxelSize) and voxelSize > 0):
+        raise InvalidParameter(f"voxelSize must be finite and > 0, got {voxelSize!r}")
+    if not (isinstance(minNumPointsPerVoxel, (int, np.integer)) and not isinstance(minNumPointsPerVoxel, bool)
+            and minNumPointsPerVoxel >= 1):
+        raise InvalidParameter(f"minNumPointsPerVoxel must be an integer >= 1, got {minNumPointsPerVoxel!r}")   # assert_ge
+    if sourceToTarget is None:
+        return None
+    T = np.asarray(sourceToTarget, np.float64)
+    if T.shape != (4, 4):
+        raise InvalidParameter(f"sourceToTarget must be 4 x 4, got shape {T.shape}")
+    return T
+
+
+def computeIndicesOfOverlappingPoints(source, target, sourceToTarget, voxelSize, minNumPointsPerVoxel=1):
+    """o3d_slam::computeIndicesOfOverlappingPoints (helpers.cpp:320-345) on the device: (idxsSource, idxsTarget), ascending
+    (the reference emits std::unordered_map order).  `source` / `target`: DataPoints or N x 3 arrays; sourceToTarget 4 x 4 or
+    None (identity)."""
+    T = _check_overlap_args(sourceToTarget, voxelSize, minNumPointsPerVoxel)
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")
+    p = capi.default_params()
+    p.cost = capi.COST_O3D_P2P
+    reg = capi.Registration(p)
+    try:
+        return reg.overlap_indices(s, t, voxelSize, T, minNumPointsPerVoxel)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+
+
+def _pair_on_handle(reg, source, target, T, voxelSize, needs_target_normals, needs_covs):
+    """One upload per cloud: the overlap front (voxelSize not None) or the plain fp64 entry points."""
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")
+    tn = _field64(target.normals, t.shape[0], 3, "target normals") if needs_target_normals else None
+    sc = _covs9(_field64(source.covariances, s.shape[0], 6, "source covariances")) if needs_covs else None
+    tc = _covs9(_field64(target.covariances, t.shape[0], 6, "target covariances")) if needs_covs else None
+    if voxelSize is not None:
+        reg.set_pair_overlap_f64(s, t, voxelSize, T, 1, None, sc, tn, tc)
+    else:
+        reg.set_target_f64(t, tn, tc)
+        reg.set_source_f64(s, None, sc)
+
+
+def _result_of(reg, T, res) -> RegistrationResult:
+    ids, _, _ = reg.correspondences(want_w=False)
+    sel = np.nonzero(ids >= 0)[0]
+    return RegistrationResult(T.astype(np.float64), float(res.fitness), float(res.inlier_rmse),
+                              np.stack([sel, ids[sel]], axis=1))
+
+
+def buildConstraint(source: DataPoints, target: DataPoints, *, isComputeOverlap, icpMaxCorrespondenceDistance,
+                    voxelSizeOverlapCompute, isEstimateInformationMatrix, isSkipIcpRefinement, sourceIdx=0, targetIdx=0,
+                    withResult=False):
+    """o3d_slam::buildConstraint (constraint_builders.cpp:43-90) for two submap clouds: overlap selection at identity
+    (minNumPointsPerVoxel = 1), Open3D point-to-plane RegistrationICP from identity with max_iteration_ = 100, the
+    information matrix at the result with the same distance -- one handle, one upload per cloud.  With `withResult` the
+    RegistrationResult (indices into the selected clouds, as in the reference) is returned next to the Constraint."""
+    if isComputeOverlap:
+        _check_overlap_args(None, voxelSizeOverlapCompute, 1)
+    if not (math.isfinite(icpMaxCorrespondenceDistance) and icpMaxCorrespondenceDistance > 0):
+        raise InvalidParameter(f"icpMaxCorrespondenceDistance must be finite and > 0, got {icpMaxCorrespondenceDistance!r}")
+    if target.normals is None and not isSkipIcpRefinement:
+        raise InvalidField("point-to-plane needs normals on the target cloud")
+    op = RegistrationIcpPointToPlane(icpMaxCorrespondenceDistance, ICP_RUN_UNTIL_CONVERGENCE_ITERATIONS)
+    has_nrm = target.normals is not None
+    p = op.params()
+    if not has_nrm:
+        p.cost = capi.COST_O3D_P2P   # no refinement asked for: only the search structure and the information matrix are used
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")   # shape errors before the device is touched
+    _field64(target.normals, t.shape[0], 3, "target normals")
+    reg = capi.Registration(p)
+    result = RegistrationResult()
+    info = np.eye(6)
+    try:
+        _pair_on_handle(reg, source, target, None, voxelSizeOverlapCompute if isComputeOverlap else None, has_nrm, False)
+        if not isSkipIcpRefinement:
+            T, res = reg.register(np.eye(4))
+            result = _result_of(reg, T, res)
+        if isEstimateInformationMatrix:
+            info, _ = reg.information_matrix(result.transformation_, icpMaxCorrespondenceDistance)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    c = Constraint(sourceIdx, targetIdx, result.transformation_.copy(), info, bool(isEstimateInformationMatrix), True)
+    return (c, result) if withResult else c
+
+
+def refineLoopClosure(source: DataPoints, target: DataPoints, T_ransac, registration, voxelSizeForOverlap,
+                      maxIcpCorrespondenceDistance, sourceIdx=0, targetIdx=0):
+    """The refinement of a loop-closure candidate (PlaceRecognition.cpp:97-149): overlap selection at T_ransac
+    (minNumPointsPerVoxel = 1), the given B1 operator from T_ransac on the overlap clouds, the information matrix on the same
+    clouds at the refined pose.  Returns (Constraint, RegistrationResult): the caller applies minRefinementFitness_ and the
+    consistency check.  maxIcpCorrespondenceDistance must not exceed the operator's maxCorrespondenceDistance_ (the reach of
+    the search structure both run on)."""
+    T0 = _check_overlap_args(T_ransac, voxelSizeForOverlap, 1)
+    if T0 is None:
+        T0 = np.eye(4)
+    if not (0 < maxIcpCorrespondenceDistance <= registration.maxCorrespondenceDistance_):
+        raise InvalidParameter("maxIcpCorrespondenceDistance must be > 0 and <= the operator's maxCorrespondenceDistance_")
+    p = registration.params()
+    needs_nrm = p.cost == capi.COST_O3D_P2PL
+    needs_cov = p.cost == capi.COST_GICP
+    if needs_nrm and target.normals is None:
+        raise InvalidField("point-to-plane needs normals on the target cloud")
+    if needs_cov and (source.covariances is None or target.covariances is None):
+        raise InvalidField("GICP needs covariances on both clouds")
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")
+    if needs_nrm:
+        _field64(target.normals, t.shape[0], 3, "target normals")
+    reg = capi.Registration(p)
+    try:
+        _pair_on_handle(reg, source, target, T0, voxelSizeForOverlap, needs_nrm, needs_cov)
+        T, res = reg.register(T0)
+        result = _result_of(reg, T, res)
+        info, _ = reg.information_matrix(result.transformation_, maxIcpCorrespondenceDistance)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    return Constraint(sourceIdx, targetIdx, result.transformation_.copy(), info, True, False), result
