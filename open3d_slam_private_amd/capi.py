@@ -897,6 +897,32 @@ class Registration:
                                                 float(truncation), float(min_dot), _ptr(out), C.byref(n)))
         return out[:int(n.value)].copy()
 
+    def voxelize_within_volume_device(self, xyz_ptr, m, voxel_size, out_xyz_ptr, volume=None, nrm_ptr=None, cov_ptr=None,
+                                      out_nrm_ptr=None, out_cov_ptr=None):
+        """As voxelize_within_volume with the fp64 cloud and the fp64 outputs (capacity m rows each: x 3, normals x 3,
+        covs x 9) resident in HBM; the kernels write the outputs in place.  Returns (n_out, n_outside)."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        c = self._crop_struct(volume)
+        n_out, n_outside = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_voxelize_within_volume(self._h, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), m, 1,
+                                                         C.byref(c) if c is not None else None, float(voxel_size),
+                                                         vp(out_xyz_ptr), vp(out_nrm_ptr), vp(out_cov_ptr), C.byref(n_out),
+                                                         C.byref(n_outside)))
+        return int(n_out.value), int(n_outside.value)
+
+    def carve_indices_device(self, map_ptr, m, scan_ptr, n_scan, sensor, removed_ptr, voxel_size=0.1, max_ray=20.0,
+                             truncation=0.1, min_dot=0.5, map_nrm_ptr=None, subset=None):
+        """As carve_indices with the fp64 map (m x 3; normals m x 3), the fp64 scan (n_scan x 3) and the int32 output
+        (capacity m) resident in HBM.  Returns n_removed."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        sen = (C.c_double * 3)(*[float(v) for v in sensor])
+        c = self._crop_struct(subset)
+        n = C.c_int64(0)
+        self._check(self._lib.reg_carve_indices(self._h, vp(map_ptr), vp(map_nrm_ptr), m, vp(scan_ptr), n_scan, 1, sen,
+                                                C.byref(c) if c is not None else None, float(voxel_size), float(max_ray),
+                                                float(truncation), float(min_dot), vp(removed_ptr), C.byref(n)))
+        return int(n.value)
+
     def target_source_indices(self):
         idx = np.empty(self.n_target_kept, np.int32)
         self._check(self._lib.reg_get_target_source_indices(self._h, _ptr(idx)))
