@@ -108,7 +108,7 @@ reg_status reg_filter_cloud(reg_handle* h, const float* xyz, int64_t xyz_stride,
     HIPCHK(h, hipSetDevice(h->prm.device));
     hipStream_t s = h->stream;
     const float* d_in = nullptr;
-    HIPCHK(h, dpf_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
+    HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_fields.reserve(std::max<size_t>(off[n_fields], 1) * (size_t)N * 4));
     HIPCHK(h, h->f_perm.reserve((size_t)N * 4));
@@ -166,19 +166,14 @@ reg_status reg_filter_cloud(reg_handle* h, const float* xyz, int64_t xyz_stride,
             HIPCHK(h, hipMemsetAsync(misc, 0, 8, s));
             k_fc_density_max<<<grid_for(m), 256, 0, s>>>(fa, span_a, idx, m, misc);
             k_fc_density_mask<<<grid_for(m), 256, 0, s>>>(fa, span_a, idx, m, c.v[0], misc, need_w);
-            size_t bytes = 0;
-            HIPCHK(h, rocprim::exclusive_scan(nullptr, bytes, need_w, dpos_w, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
-            HIPCHK(h, h->f_tmp.reserve(bytes));
-            HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, bytes, need_w, dpos_w, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
-            uint32_t rb[2] = {0u, 0u}, tail[2] = {0u, 0u};
+            REGCHK(scan_excl(h, h->rp_tmp, need_w, dpos_w, (size_t)m));
+            uint32_t rb[2] = {0u, 0u}, tail[2];
             HIPCHK(h, hipMemcpyAsync(rb, misc, 8, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(&tail[0], dpos_w + m - 1, 4, hipMemcpyDeviceToHost, s));
-            HIPCHK(h, hipMemcpyAsync(&tail[1], need_w + m - 1, 4, hipMemcpyDeviceToHost, s));
+            REGCHK(flag_total_async(h, need_w, dpos_w, m, tail));
             HIPCHK(h, hipStreamSynchronize(s));
-            const uint32_t u = (rb[0] & 0x80000000u) ? (rb[0] & 0x7fffffffu) : ~rb[0];
-            std::memcpy(&d.last, &u, 4);
+            d.last = float_from_orderable(rb[0]);
             d.sat_factor = (float)(1 - (int)rb[1] / m);   // integer division, MaxDensity.cpp:88
-            const int64_t n_draws = (int64_t)tail[0] + tail[1];
+            const int64_t n_draws = flag_total(tail);
             std::vector<int32_t> rv;
             oct_glibc_rand(c.seed ? c.seed : 1u, n_draws, rv);   // srand(0) seeds 1 (glibc srandom_r)
             draws.resize((size_t)std::max<int64_t>(n_draws, 1));
@@ -265,7 +260,7 @@ reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, i
     HIPCHK(h, hipSetDevice(h->prm.device));
     hipStream_t s = h->stream;
     const float* d_in = nullptr;
-    HIPCHK(h, dpf_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
+    HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
     const uint32_t misc0[10] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
@@ -284,11 +279,7 @@ reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, i
     unsigned __int128 total = 1;
     uint64_t nd[3];
     for (int a = 0; a < 3; ++a) {
-        const uint32_t kl = box[a], kh = box[3 + a];
-        const uint32_t ul = (kl & 0x80000000u) ? (kl & 0x7fffffffu) : ~kl, uh = (kh & 0x80000000u) ? (kh & 0x7fffffffu) : ~kh;
-        float lo, hi;
-        std::memcpy(&lo, &ul, 4);
-        std::memcpy(&hi, &uh, 4);
+        const float lo = float_from_orderable(box[a]), hi = float_from_orderable(box[3 + a]);
         const float v = p->v_size[a];
         const float min_bound = lo / v;
         float d = hi / v;
@@ -322,20 +313,13 @@ reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, i
     k_vg_keys<<<grid_for(N), 256, 0, s>>>(px, N, g, keys, iota);
     // a cell index may reach numDiv by rounding, so the ids stay below 4 * total (< 2^34)
     const int bits = std::min(64, oct_bits((uint64_t)total * 4u));
-    size_t need = 0;
-    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, need, keys, keys_s, iota, idx, (unsigned)N, 0, bits, s));
-    HIPCHK(h, h->f_tmp.reserve(need));
-    HIPCHK(h, rocprim::radix_sort_pairs(h->f_tmp.p, need, keys, keys_s, iota, idx, (unsigned)N, 0, bits, s));
+    REGCHK(sort_pairs(h, h->rp_tmp, keys, keys_s, iota, idx, (unsigned)N, 0, bits));
     k_vg_first<<<grid_for(N), 256, 0, s>>>(keys_s, idx, N, is_first);
-    need = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, need, is_first, pos, 0u, (size_t)N, rocprim::plus<uint32_t>(), s));
-    HIPCHK(h, h->f_tmp.reserve(need));
-    HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, need, is_first, pos, 0u, (size_t)N, rocprim::plus<uint32_t>(), s));
-    uint32_t tail[2] = {0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(&tail[1], is_first + N - 1, 4, hipMemcpyDeviceToHost, s));
+    REGCHK(scan_excl(h, h->rp_tmp, is_first, pos, (size_t)N));
+    uint32_t tail[2];
+    REGCHK(flag_total_async(h, is_first, pos, N, tail));
     HIPCHK(h, hipStreamSynchronize(s));
-    const int m = (int)(tail[0] + tail[1]);
+    const int m = (int)flag_total(tail);
     // fields: device inputs are read in place, host inputs go through the workspace
     const float* fin[REG_MAX_FIELDS] = {nullptr};
     if (!on_device && n_fields > 0) HIPCHK(h, h->f_fields.reserve(off[n_fields] * (size_t)N * 4));

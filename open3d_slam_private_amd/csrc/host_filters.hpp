@@ -4,19 +4,6 @@
 
 namespace {
 
-// Uploads (host input) or reads in place (device input) `count` elements; returns the device pointer.
-template <class T>
-hipError_t dpf_input(reg_handle* h, DevBuf& buf, const T* src, size_t count, int on_device, const T** out) {
-    if (!src || on_device) {
-        *out = src;
-        return hipSuccess;
-    }
-    hipError_t e = buf.reserve(count * sizeof(T));
-    if (e != hipSuccess) return e;
-    *out = buf.as<T>();
-    return hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
-}
-
 // Tree shape of SamplingSurfaceNormal: depends only on (n, knn).  Per level the open segments [begin, end) and the
 // slots of their children in the next level (-1: a leaf); the leaves' begins in depth-first order (+ sentinel n).
 struct SsnPlan {
@@ -68,7 +55,7 @@ bool pf_valid(const reg_point_filter& f) {
     return ok;
 }
 
-// flag[j] = the filter keeps the j-th point of the index list (f_keys / f_misc / f_tmp are scratch; `who` prefixes errors)
+// flag[j] = the filter keeps the j-th point of the index list (f_keys / f_misc are scratch; `who` prefixes errors)
 reg_status pf_flags(reg_handle* h, const reg_point_filter& f, const float* px, const int32_t* idx, int m, uint32_t* flag,
                     const char* who) {
     hipStream_t s = h->stream;
@@ -92,10 +79,7 @@ reg_status pf_flags(reg_handle* h, const reg_point_filter& f, const float* px, c
         float* sorted = vals + m;
         HIPCHK(h, hipMemsetAsync(h->f_misc.p, 0, 4, s));
         k_pf_axis<<<grid_for(m), 256, 0, s>>>(px, idx, m, f.dim, vals, h->f_misc.as<uint32_t>());
-        size_t need = 0;
-        HIPCHK(h, rocprim::radix_sort_keys(nullptr, need, vals, sorted, (unsigned)m, 0, 32, s));
-        HIPCHK(h, h->f_tmp.reserve(need));
-        HIPCHK(h, rocprim::radix_sort_keys(h->f_tmp.p, need, vals, sorted, (unsigned)m, 0, 32, s));
+        REGCHK(sort_keys(h, h->rp_tmp, vals, sorted, (unsigned)m, 0, 32));
         uint32_t has_nan = 0;
         HIPCHK(h, hipMemcpyAsync(&d.limit, sorted + q, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(h, hipMemcpyAsync(&has_nan, h->f_misc.p, 4, hipMemcpyDeviceToHost, s));
@@ -112,16 +96,12 @@ reg_status pf_flags(reg_handle* h, const reg_point_filter& f, const float* px, c
 // Order-preserving compaction of the index list by flag: idx <- the kept entries (idx2 is the spare list), m <- their count.
 reg_status pf_compact(reg_handle* h, int32_t*& idx, int32_t*& idx2, const uint32_t* flag, uint32_t* pos, int& m) {
     hipStream_t s = h->stream;
-    size_t need = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
-    HIPCHK(h, h->f_tmp.reserve(need));
-    HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, need, flag, pos, 0u, (size_t)m, rocprim::plus<uint32_t>(), s));
+    REGCHK(scan_excl(h, h->rp_tmp, flag, pos, (size_t)m));
     k_pf_compact<<<grid_for(m), 256, 0, s>>>(idx, m, flag, pos, idx2);
-    uint32_t tail[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tail[0], pos + m - 1, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(&tail[1], flag + m - 1, 4, hipMemcpyDeviceToHost, s));
+    uint32_t tail[2];
+    REGCHK(flag_total_async(h, flag, pos, m, tail));
     HIPCHK(h, hipStreamSynchronize(s));
-    m = (int)(tail[0] + tail[1]);
+    m = (int)flag_total(tail);
     std::swap(idx, idx2);
     return REG_OK;
 }
@@ -173,7 +153,7 @@ reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t 
     HIPCHK(h, hipSetDevice(h->prm.device));
     hipStream_t s = h->stream;
     const float* d_in = nullptr;
-    HIPCHK(h, dpf_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
+    HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
     // misc: [0..2] min, [3..5] max (orderable keys), [6] non-finite flag, [8..9] n_unfit (64-bit)
@@ -217,11 +197,9 @@ reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t 
         const int32_t* se = sb + ns;
         const int32_t* ch = se + ns;
         k_ssn_keys<<<grid_for(N), 256, 0, s>>>(px, perm, N, sb, se, ns, boxes, keys);
-        size_t need = 0;
-        HIPCHK(h, rocprim::segmented_radix_sort_keys(nullptr, need, keys, keys2, (unsigned)N, (unsigned)ns, sb, se, 0, 64, s));
-        HIPCHK(h, h->f_tmp.reserve(need));
-        HIPCHK(h, rocprim::segmented_radix_sort_keys(h->f_tmp.p, need, keys, keys2, (unsigned)N, (unsigned)ns, sb, se, 0,
-                                                     64, s));
+        REGCHK(with_tmp(h, h->rp_tmp, [&](void* t, size_t& b) {
+            return rocprim::segmented_radix_sort_keys(t, b, keys, keys2, (unsigned)N, (unsigned)ns, sb, se, 0, 64, s);
+        }));
         k_ssn_extract<<<grid_for(N), 256, 0, s>>>(keys2, N, sb, se, ns, perm);
         k_ssn_children<<<grid_for(ns), 256, 0, s>>>(px, perm, sb, se, ch, ns, boxes, boxes2);
         std::swap(boxes, boxes2);
@@ -237,17 +215,13 @@ reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t 
     k_ssn_leaf<<<grid_for(n_leaves), 256, 0, s>>>(px, perm, d_leaf_begin, n_leaves, p->max_box_dim, need_eig ? 1 : 0,
                                                   method, h->f_mom.as<PcaMoments>(), d_lid, keep,
                                                   (unsigned long long*)(misc + 8));
-    size_t scan_bytes = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, scan_bytes, keep, pos, 0u, (size_t)N, rocprim::plus<uint32_t>(), s));
-    HIPCHK(h, h->f_tmp.reserve(scan_bytes));
-    HIPCHK(h, rocprim::exclusive_scan(h->f_tmp.p, scan_bytes, keep, pos, 0u, (size_t)N, rocprim::plus<uint32_t>(), s));
-    uint32_t tail[2] = {0, 0};
+    REGCHK(scan_excl(h, h->rp_tmp, keep, pos, (size_t)N));
+    uint32_t tail[2];
     unsigned long long unfit = 0;
-    HIPCHK(h, hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(&tail[1], keep + N - 1, 4, hipMemcpyDeviceToHost, s));
+    REGCHK(flag_total_async(h, keep, pos, N, tail));
     HIPCHK(h, hipMemcpyAsync(&unfit, misc + 8, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
-    const int M = (int)(tail[0] + tail[1]);
+    const int M = (int)flag_total(tail);
     // outputs: the caller's device pointers, else one staging buffer (rows of every array)
     const size_t rows = (size_t)std::max(M, 1);
     float *o_xyz = out->xyz, *o_nrm = out->normals, *o_den = out->densities, *o_eva = out->eigvals, *o_eve = out->eigvecs;
@@ -309,9 +283,9 @@ reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xyz_stride
     HIPCHK(h, hipSetDevice(h->prm.device));
     hipStream_t s = h->stream;
     const float *d_in = nullptr, *d_nrm = nullptr, *d_cov = nullptr;
-    HIPCHK(h, dpf_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
-    HIPCHK(h, dpf_input(h, h->f_in_nrm, nrm, (size_t)N * 3, on_device, &d_nrm));
-    HIPCHK(h, dpf_input(h, h->f_in_cov, cov, (size_t)N * 6, on_device, &d_cov));
+    HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
+    HIPCHK(h, staged_input(h, h->f_in_nrm, nrm, (size_t)N * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->f_in_cov, cov, (size_t)N * 6, on_device, &d_cov));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     if (nrm) HIPCHK(h, h->f_pn.reserve((size_t)N * 12));
     if (cov) HIPCHK(h, h->f_pc.reserve((size_t)N * 24));

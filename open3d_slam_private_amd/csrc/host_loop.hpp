@@ -900,11 +900,10 @@ static reg_status register_pm(reg_handle* h, const float* Ti, float T_out[16], r
     if (h->pm.use_var_trimmed) {
         HIPCHK(h, h->pm_sorted.reserve((size_t)nk * 4));
         HIPCHK(h, h->pm_var.reserve(pm_var_bytes(nk)));
-        size_t need = 0;
-        HIPCHK(h, rocprim::radix_sort_keys(nullptr, need, h->pm_d2.as<uint32_t>(), h->pm_sorted.as<uint32_t>(), (size_t)nk, 0, 32,
-                                           h->stream));
-        HIPCHK(h, h->pm_sort_tmp.reserve(std::max<size_t>(need, 16)));
-        h->pm_sort_bytes = need;
+        // storage for the sort of enqueue_pm_var_trim, which runs inside the loop on these arguments
+        REGCHK(tmp_reserve(h, h->pm_sort_tmp, h->pm_sort_bytes, [&](void* t, size_t& b) {
+            return rocprim::radix_sort_keys(t, b, h->pm_d2.as<uint32_t>(), h->pm_sorted.as<uint32_t>(), (size_t)nk, 0, 32, h->stream);
+        }));
     }
     const bool extras = pm_chain_has_extras(&h->pm) || h->xt_on;
     h->pm_x_valid = false;

@@ -44,6 +44,14 @@ O3D_HD inline void m4_mul(const float* A, const float* B, float* C) {
     memcpy(C, R, sizeof(R));
 }
 
+// The float behind an orderable key (k_ssn_pack: the key order is the float order; minima / maxima are taken on keys)
+O3D_HD inline float float_from_orderable(uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+
 O3D_HD inline void m4_transpose(const float* A, float* B) {
     float R[16];
     for (int i = 0; i < 4; ++i)

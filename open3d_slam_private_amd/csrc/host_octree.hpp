@@ -100,9 +100,9 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
     HIPCHK(h, hipSetDevice(h->prm.device));
     hipStream_t s = h->stream;
     const float *d_in = nullptr, *d_nrm = nullptr, *d_cov = nullptr;
-    HIPCHK(h, dpf_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
-    HIPCHK(h, dpf_input(h, h->f_in_nrm, nrm, (size_t)N * 3, on_device, &d_nrm));
-    HIPCHK(h, dpf_input(h, h->f_in_cov, cov, (size_t)N * 6, on_device, &d_cov));
+    HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
+    HIPCHK(h, staged_input(h, h->f_in_nrm, nrm, (size_t)N * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->f_in_cov, cov, (size_t)N * 6, on_device, &d_cov));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
     // misc: [0..2] min, [3..5] max (orderable keys), [6] non-finite flag, [8] any node still open
@@ -118,16 +118,10 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
         h->err = "reg_octree_grid: non-finite input";
         return REG_BAD_ARGUMENT;
     }
-    auto from_orderable = [](uint32_t k) {
-        const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-        float v;
-        std::memcpy(&v, &u, 4);
-        return v;
-    };
     float lo[3], hi[3], c0[4] = {0.f, 0.f, 0.f, 0.f}, r0 = 0.f;
     for (int a = 0; a < 3; ++a) {
-        lo[a] = from_orderable(box[a]);
-        hi[a] = from_orderable(box[3 + a]);
+        lo[a] = float_from_orderable(box[a]);
+        hi[a] = float_from_orderable(box[3 + a]);
     }
     oct_root(lo, hi, p->center_at_origin, c0, &r0);
     if (!std::isfinite(r0) || !std::isfinite(c0[0]) || !std::isfinite(c0[1]) || !std::isfinite(c0[2])) {
@@ -175,19 +169,11 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
             const bool first = d0 == 0;
             k_oct_keys<<<grid_for(N), 256, 0, s>>>(px, N, d_root_c, d_radii + d0, levels, first ? nullptr : open, pc, keys,
                                                    iota);
-            size_t need = 0;
-            const int begin_bit = 63 - 3 * levels;
-            HIPCHK(h, rocprim::radix_sort_pairs(nullptr, need, keys, keys_s, iota, idx, (unsigned)N, begin_bit, 63, s));
-            HIPCHK(h, h->f_tmp.reserve(need));
-            HIPCHK(h, rocprim::radix_sort_pairs(h->f_tmp.p, need, keys, keys_s, iota, idx, (unsigned)N, begin_bit, 63, s));
+            REGCHK(sort_pairs(h, h->rp_tmp, keys, keys_s, iota, idx, (unsigned)N, 63 - 3 * levels, 63));
             const uint32_t* rk = nullptr;
             if (!first) {   // (rank, key) order: the key order above, then a stable sort by rank
                 k_oct_gather_rank<<<grid_for(N), 256, 0, s>>>(idx, rank, N, rank_a);
-                const int rbits = oct_bits(n_groups - 1);
-                need = 0;
-                HIPCHK(h, rocprim::radix_sort_pairs(nullptr, need, rank_a, rank_s, idx, idx2, (unsigned)N, 0, rbits, s));
-                HIPCHK(h, h->f_tmp.reserve(need));
-                HIPCHK(h, rocprim::radix_sort_pairs(h->f_tmp.p, need, rank_a, rank_s, idx, idx2, (unsigned)N, 0, rbits, s));
+                REGCHK(sort_pairs(h, h->rp_tmp, rank_a, rank_s, idx, idx2, (unsigned)N, 0, oct_bits(n_groups - 1)));
                 std::swap(idx, idx2);
                 k_oct_gather_keys<<<grid_for(N), 256, 0, s>>>(idx, keys, N, keys_s);
                 rk = rank_s;
@@ -196,10 +182,7 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
             k_oct_depth<<<grid_for(N), 256, 0, s>>>(keys_s, rk, idx, first ? nullptr : open, N, max_pts, d0, d_size, kk,
                                                     depth, misc + 8);
             k_oct_heads<<<grid_for(N), 256, 0, s>>>(keys_s, rk, kk, N, heads);
-            need = 0;
-            HIPCHK(h, rocprim::inclusive_scan(nullptr, need, heads, pos, (size_t)N, rocprim::plus<uint32_t>(), s));
-            HIPCHK(h, h->f_tmp.reserve(need));
-            HIPCHK(h, rocprim::inclusive_scan(h->f_tmp.p, need, heads, pos, (size_t)N, rocprim::plus<uint32_t>(), s));
+            REGCHK(scan_incl(h, h->rp_tmp, heads, pos, (size_t)N));
             k_oct_scatter<<<grid_for(N), 256, 0, s>>>(idx, pos, kk, N, rank, open);
             uint32_t tail[2] = {0u, 0u};
             HIPCHK(h, hipMemcpyAsync(&tail[0], pos + N - 1, 4, hipMemcpyDeviceToHost, s));
@@ -217,14 +200,8 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
     // members by (leaf, input index): a stable sort of the leaf ids in input order (iota from the last k_oct_keys)
     HIPCHK(h, h->o_start.reserve(((size_t)n_leaves + 1) * 4));
     int32_t* start = h->o_start.as<int32_t>();
-    {
-        const int lbits = oct_bits(n_leaves - 1);
-        size_t need = 0;
-        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, need, rank, rank_s, iota, idx, (unsigned)N, 0, lbits, s));
-        HIPCHK(h, h->f_tmp.reserve(need));
-        HIPCHK(h, rocprim::radix_sort_pairs(h->f_tmp.p, need, rank, rank_s, iota, idx, (unsigned)N, 0, lbits, s));
-        k_oct_starts<<<grid_for(N), 256, 0, s>>>(rank_s, N, (int)n_leaves, start);
-    }
+    REGCHK(sort_pairs(h, h->rp_tmp, rank, rank_s, iota, idx, (unsigned)N, 0, oct_bits(n_leaves - 1)));
+    k_oct_starts<<<grid_for(N), 256, 0, s>>>(rank_s, N, (int)n_leaves, start);
     const int32_t* d_rand = nullptr;
     if (method == REG_OCTREE_RAND) {
         std::vector<int32_t> rv;

@@ -6,14 +6,6 @@
 // Words of ov_misc: [0] invalid-key flag, [1] / [2] unique voxels of the source / target layer
 enum { kOvlBad = 0, kOvlRuns = 1 };
 
-static reg_status ovl_scan(reg_handle* h, const uint32_t* in, uint32_t* out, size_t count) {
-    size_t tb = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, in, out, 0u, count, rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->ov_tmp.reserve(tb));
-    HIPCHK(h, rocprim::exclusive_scan(h->ov_tmp.p, tb, in, out, 0u, count, rocprim::plus<uint32_t>(), h->stream));
-    return REG_OK;
-}
-
 // Flags (input order, n + 1 / m + 1 words, the last one 0) and their exclusive scans for both layers, in ov_flags / ov_offs;
 // the selected counts.  d_src / d_tgt: device pointers, n, m >= 1.  One synchronisation: the invalid-key word and the counts.
 static reg_status ovl_select(reg_handle* h, const double* d_src, int64_t n, const double* d_tgt, int64_t m, const double* T_col,
@@ -42,20 +34,11 @@ static reg_status ovl_select(reg_handle* h, const double* d_src, int64_t n, cons
         HIPCHK(h, h->ov_flags[l].reserve((size_t)(c + 1) * 4));
         HIPCHK(h, h->ov_offs[l].reserve((size_t)(c + 1) * 4));
         k_ovl_keys<<<grid_for(c), 256, 0, h->stream>>>(pts[l], c, l == 0 ? Ts : Tt, inv, h->ov_keys[l].as<uint64_t>(), misc + kOvlBad);
-        size_t sb = 0;
-        HIPCHK(h, rocprim::radix_sort_keys(nullptr, sb, h->ov_keys[l].as<uint64_t>(), h->ov_sorted.as<uint64_t>(), (size_t)c, 0,
-                                           64, h->stream));
-        HIPCHK(h, h->ov_tmp.reserve(sb));
-        HIPCHK(h, rocprim::radix_sort_keys(h->ov_tmp.p, sb, h->ov_keys[l].as<uint64_t>(), h->ov_sorted.as<uint64_t>(), (size_t)c,
-                                           0, 64, h->stream));
-        size_t rb = 0;
-        HIPCHK(h, rocprim::run_length_encode(nullptr, rb, h->ov_sorted.as<uint64_t>(), (unsigned int)c,
-                                             h->ov_ukeys[l].as<uint64_t>(), h->ov_ucnt[l].as<uint32_t>(), misc + kOvlRuns + l,
-                                             h->stream));
-        HIPCHK(h, h->ov_tmp.reserve(rb));
-        HIPCHK(h, rocprim::run_length_encode(h->ov_tmp.p, rb, h->ov_sorted.as<uint64_t>(), (unsigned int)c,
-                                             h->ov_ukeys[l].as<uint64_t>(), h->ov_ucnt[l].as<uint32_t>(), misc + kOvlRuns + l,
-                                             h->stream));
+        REGCHK(sort_keys(h, h->rp_tmp, h->ov_keys[l].as<uint64_t>(), h->ov_sorted.as<uint64_t>(), (size_t)c, 0, 64));
+        REGCHK(with_tmp(h, h->rp_tmp, [&](void* t, size_t& b) {
+            return rocprim::run_length_encode(t, b, h->ov_sorted.as<uint64_t>(), (unsigned int)c, h->ov_ukeys[l].as<uint64_t>(),
+                                              h->ov_ucnt[l].as<uint32_t>(), misc + kOvlRuns + l, h->stream);
+        }));
     }
     for (int l = 0; l < 2; ++l) {
         const int o = 1 - l;
@@ -63,8 +46,7 @@ static reg_status ovl_select(reg_handle* h, const double* d_src, int64_t n, cons
             h->ov_keys[l].as<uint64_t>(), cnt[l], h->ov_ukeys[l].as<uint64_t>(), h->ov_ucnt[l].as<uint32_t>(), misc + kOvlRuns + l,
             h->ov_ukeys[o].as<uint64_t>(), h->ov_ucnt[o].as<uint32_t>(), misc + kOvlRuns + o, (uint32_t)min_points,
             h->ov_flags[l].as<uint32_t>());
-        const reg_status s = ovl_scan(h, h->ov_flags[l].as<uint32_t>(), h->ov_offs[l].as<uint32_t>(), (size_t)cnt[l] + 1);
-        if (s != REG_OK) return s;
+        REGCHK(scan_excl(h, h->rp_tmp, h->ov_flags[l].as<uint32_t>(), h->ov_offs[l].as<uint32_t>(), (size_t)cnt[l] + 1));
     }
     uint32_t back[3] = {0, 0, 0};
     HIPCHK(h, hipMemcpyAsync(&back[0], misc + kOvlBad, 4, hipMemcpyDeviceToHost, h->stream));
@@ -106,18 +88,12 @@ reg_status reg_overlap_indices(reg_handle* h, const double* src_xyz, int64_t n, 
         return REG_BAD_ARGUMENT;
     }
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const double *d_src = src_xyz, *d_tgt = tgt_xyz;
-    if (!on_device) {
-        // host clouds are staged in the fp64 staging buffers of reg_set_source_f64 / reg_set_target_f64: those are dead once
-        // their cast kernel has run (the handle keeps the fp32 copies), so the query does not disturb a reference or
-        // reading that is set, and a handle used for both pays for one staging area
-        HIPCHK(h, h->r_in_xyz.reserve((size_t)n * 24));
-        HIPCHK(h, hipMemcpyAsync(h->r_in_xyz.p, src_xyz, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
-        d_src = h->r_in_xyz.as<double>();
-        HIPCHK(h, h->c_in_xyz.reserve((size_t)m * 24));
-        HIPCHK(h, hipMemcpyAsync(h->c_in_xyz.p, tgt_xyz, (size_t)m * 24, hipMemcpyHostToDevice, h->stream));
-        d_tgt = h->c_in_xyz.as<double>();
-    }
+    // host clouds are staged in the fp64 staging buffers of reg_set_source_f64 / reg_set_target_f64: those are dead once
+    // their cast kernel has run (the handle keeps the fp32 copies), so the query does not disturb a reference or
+    // reading that is set, and a handle used for both pays for one staging area
+    const double *d_src = nullptr, *d_tgt = nullptr;
+    HIPCHK(h, staged_input(h, h->r_in_xyz, src_xyz, (size_t)n * 3, on_device, &d_src));
+    HIPCHK(h, staged_input(h, h->c_in_xyz, tgt_xyz, (size_t)m * 3, on_device, &d_tgt));
     int64_t ks = 0, kt = 0;
     const reg_status s = ovl_select(h, d_src, n, d_tgt, m, T_src_to_tgt, voxel_size, min_points_per_voxel, &ks, &kt);
     if (s != REG_OK) return s;
@@ -170,22 +146,12 @@ reg_status reg_set_pair_overlap_f64(reg_handle* h, const double* src_xyz, const 
     if (const reg_status fs = check_source_fields(h, src_normals != nullptr, src_covs != nullptr)) return fs;
     HIPCHK(h, hipSetDevice(h->prm.device));
     const double *d_s[3] = {src_xyz, src_normals, src_covs}, *d_t[3] = {tgt_xyz, tgt_normals, tgt_covs};
-    if (!on_device) {
-        DevBuf* sb[3] = {&h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov};
-        DevBuf* tb[3] = {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov};
-        const size_t width[3] = {24, 24, 72};
-        for (int k = 0; k < 3; ++k) {
-            if (d_s[k]) {
-                HIPCHK(h, sb[k]->reserve((size_t)n * width[k]));
-                HIPCHK(h, hipMemcpyAsync(sb[k]->p, d_s[k], (size_t)n * width[k], hipMemcpyHostToDevice, h->stream));
-                d_s[k] = sb[k]->as<double>();
-            }
-            if (d_t[k]) {
-                HIPCHK(h, tb[k]->reserve((size_t)m * width[k]));
-                HIPCHK(h, hipMemcpyAsync(tb[k]->p, d_t[k], (size_t)m * width[k], hipMemcpyHostToDevice, h->stream));
-                d_t[k] = tb[k]->as<double>();
-            }
-        }
+    DevBuf* sb[3] = {&h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov};
+    DevBuf* tb[3] = {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov};
+    const size_t width[3] = {3, 3, 9};
+    for (int k = 0; k < 3; ++k) {
+        HIPCHK(h, staged_input(h, *sb[k], d_s[k], (size_t)n * width[k], on_device, &d_s[k]));
+        HIPCHK(h, staged_input(h, *tb[k], d_t[k], (size_t)m * width[k], on_device, &d_t[k]));
     }
     int64_t ks = 0, kt = 0;
     reg_status s = ovl_select(h, d_s[0], n, d_t[0], m, T_src_to_tgt, voxel_size, min_points_per_voxel, &ks, &kt);

@@ -1,0 +1,95 @@
+// host_prims.hpp -- host primitives the entry points share: rocPRIM's temporary-storage protocol, scans and sorts on it,
+// the total of a flag array, the crop configuration, staged inputs
+// Part of the single translation unit reg_core.hip (included by host_target.hpp once reg_handle, DevBuf and HIPCHK are
+// complete; not a standalone header).
+#pragma once
+
+#define REGCHK(call)                                                                           \
+    do {                                                                                       \
+        const reg_status s_ = (call);                                                          \
+        if (s_ != REG_OK) return s_;                                                           \
+    } while (0)
+
+// rocPRIM's two-phase protocol.  call(tmp, bytes) is ONE spelling of the rocPRIM call: with tmp == nullptr it reports the
+// bytes it needs, with storage it runs.  tmp_reserve is the first phase alone, for a call that runs later on the same
+// arguments; with_tmp is both.  The working call never sees a null pointer (to rocPRIM that is another size query: nothing
+// would run and no error would be raised), whatever size was reported.
+template <class F>   // F: hipError_t(void* tmp, size_t& bytes)
+static reg_status tmp_reserve(reg_handle* h, DevBuf& tmp, size_t& bytes, F call) {
+    bytes = 0;
+    HIPCHK(h, call((void*)nullptr, bytes));
+    HIPCHK(h, tmp.reserve(bytes ? bytes : 1));
+    return REG_OK;
+}
+template <class F>
+static reg_status with_tmp(reg_handle* h, DevBuf& tmp, F call) {
+    size_t bytes = 0;
+    REGCHK(tmp_reserve(h, tmp, bytes, call));
+    HIPCHK(h, call(tmp.p, bytes));
+    return REG_OK;
+}
+
+// out[i] = in[0] + ... + in[i - 1] (exclusive) / ... + in[i] (inclusive); in == out is allowed
+static reg_status scan_excl(reg_handle* h, DevBuf& tmp, const uint32_t* in, uint32_t* out, size_t n) {
+    return with_tmp(h, tmp, [&](void* t, size_t& b) {
+        return rocprim::exclusive_scan(t, b, in, out, 0u, n, rocprim::plus<uint32_t>(), h->stream);
+    });
+}
+static reg_status scan_incl(reg_handle* h, DevBuf& tmp, const uint32_t* in, uint32_t* out, size_t n) {
+    return with_tmp(h, tmp, [&](void* t, size_t& b) {
+        return rocprim::inclusive_scan(t, b, in, out, n, rocprim::plus<uint32_t>(), h->stream);
+    });
+}
+
+// Stable ascending radix sorts on the key bits [begin_bit, end_bit)
+template <class K, class V, class Size>
+static reg_status sort_pairs(reg_handle* h, DevBuf& tmp, K* keys, K* keys_out, V* vals, V* vals_out, Size n, int begin_bit,
+                             int end_bit) {
+    return with_tmp(h, tmp, [&](void* t, size_t& b) {
+        return rocprim::radix_sort_pairs(t, b, keys, keys_out, vals, vals_out, n, begin_bit, end_bit, h->stream);
+    });
+}
+template <class K, class Size>
+static reg_status sort_keys(reg_handle* h, DevBuf& tmp, K* keys, K* keys_out, Size n, int begin_bit, int end_bit) {
+    return with_tmp(h, tmp, [&](void* t, size_t& b) {
+        return rocprim::radix_sort_keys(t, b, keys, keys_out, n, begin_bit, end_bit, h->stream);
+    });
+}
+
+// Total of n 0 / 1 flags from their exclusive scan: enqueues the read-backs of the last offset and the last flag into
+// tail[2] (n == 0: nothing).  The caller synchronises -- usually with further words in flight -- and then reads flag_total.
+static reg_status flag_total_async(reg_handle* h, const uint32_t* flags, const uint32_t* offs, int64_t n, uint32_t tail[2]) {
+    tail[0] = tail[1] = 0;
+    if (n <= 0) return REG_OK;
+    HIPCHK(h, hipMemcpyAsync(&tail[0], offs + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&tail[1], flags + (n - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    return REG_OK;
+}
+static inline int64_t flag_total(const uint32_t tail[2]) { return (int64_t)tail[0] + (int64_t)tail[1]; }
+
+// reg_crop (null: no cropping) -> the kernels' CropCfg; false: unknown type
+static bool crop_cfg(const reg_crop* crop, CropCfg* c) {
+    std::memset(c, 0, sizeof(*c));
+    if (!crop) return true;
+    if (crop->type < REG_CROP_NONE || crop->type > REG_CROP_CYLINDER) return false;
+    c->type = crop->type;
+    c->cx = crop->center[0];
+    c->cy = crop->center[1];
+    c->cz = crop->center[2];
+    c->rmin = crop->radius_min;
+    c->rmax = crop->radius_max;
+    c->zmin = crop->min_z;
+    c->zmax = crop->max_z;
+    return true;
+}
+
+// Uploads (host input) or reads in place (device input, or none) `count` elements; *out is the device pointer.
+template <class T>
+static hipError_t staged_input(reg_handle* h, DevBuf& buf, const T* src, size_t count, int on_device, const T** out) {
+    *out = src;
+    if (!src || on_device) return hipSuccess;
+    const hipError_t e = buf.reserve(count * sizeof(T));
+    if (e != hipSuccess) return e;
+    *out = buf.as<T>();
+    return hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
+}

@@ -124,8 +124,8 @@ struct reg_handle {
     DevBuf v_fout, v_oout, v_oxyz, v_onrm, v_ocov;   // reg_voxelize_within_volume
     DevBuf v_ukeys, v_ustart;                        // reg_carve_indices
     // reg_overlap_indices / reg_set_pair_overlap_f64 (host_overlap.hpp): per layer (0: source, 1: target) keys, sorted keys,
-    // unique keys + counts, flags + offsets; run counts and the invalid-key word; rocPRIM's storage; the reading's index map
-    DevBuf ov_keys[2], ov_sorted, ov_ukeys[2], ov_ucnt[2], ov_flags[2], ov_offs[2], ov_misc, ov_tmp, ov_sidx;
+    // unique keys + counts, flags + offsets; run counts and the invalid-key word; the reading's index map
+    DevBuf ov_keys[2], ov_sorted, ov_ukeys[2], ov_ucnt[2], ov_flags[2], ov_offs[2], ov_misc, ov_sidx;
     DevBuf i_info;                                   // reg_information_matrix: one row of sums per workgroup
     int64_t src_kept = 0;                            // > 0: ov_sidx maps the current reading back (reg_set_pair_overlap_f64)
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
@@ -144,7 +144,8 @@ struct reg_handle {
     float c_ref[3] = {0, 0, 0};
     float t_mid[3] = {0, 0, 0};    // centre of the reference's bounding box (input frame unless P2PL): origin of the O3D_P2P sums
     DevBuf t_raw, t_nrm_raw, t_cov_raw, t_centred, t_keys, t_keys2, t_vals, t_vals2, t_pts, t_nrm, t_cov, t_flags,
-        t_scan, t_hash, t_cells, t_tmp, t_misc, t_dir, t_rows;
+        t_scan, t_hash, t_cells, t_misc, t_dir, t_rows;
+    DevBuf rp_tmp;   // rocPRIM's temporary storage, live within one call (host_prims.hpp); every entry point but reg_set_source
     Grid grid;
     reg_target_info info;
     float target_build_ms = 0.f;
@@ -220,7 +221,7 @@ struct reg_handle {
     XtState xt_host;              // the state after the last registration with the method on
     bool xt_valid = false;        // ... which belongs to the current reading
     // data-point filters (host_filters.hpp): inputs, tree / index lists, leaf records, scans, host-pointer outputs
-    DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_tmp, f_segs, f_boxes, f_boxes2, f_leaf,
+    DevBuf f_in, f_in_nrm, f_in_cov, f_px, f_pn, f_pc, f_perm, f_keys, f_keys2, f_segs, f_boxes, f_boxes2, f_leaf,
         f_mom, f_mom2, f_lid, f_keep, f_pos, f_misc, f_out;
     DevBuf f_fields, f_draws;     // reg_filter_cloud (host_cloud_filters.hpp): descriptor-field workspace, MaxDensity's draws
     // OctreeGridDataPointsFilter (host_octree.hpp): keys, sort orders, ranks, centres, per-round flags, leaf starts
@@ -241,6 +242,8 @@ static inline void col_to_row(const float* c, float* r) { m4_transpose(c, r); }
 static inline void row_to_col(const float* r, float* c) { m4_transpose(r, c); }
 
 static inline int grid_for(int64_t n, int block = 256) { return (int)((n + block - 1) / block); }
+
+#include "host_prims.hpp"
 
 // The two Open3D RegistrationICP costs (select-free iterations, input frame, Open3D stop rule; include/o3dslam_reg.h)
 static inline bool cost_is_o3d(int cost) { return cost == REG_COST_O3D_P2PL || cost == REG_COST_O3D_P2P; }
@@ -384,7 +387,7 @@ void reg_destroy(reg_handle* h) {
     h->n_out.release();
     h->i_xicp.release();
     for (DevBuf* b : {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov, &h->c_flags, &h->c_offs, &h->c_xyz, &h->c_nrm, &h->c_cov, &h->c_idx, &h->v_fout, &h->v_oout, &h->v_oxyz, &h->v_onrm, &h->v_ocov, &h->v_ukeys, &h->v_ustart, &h->d_d2all, &h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov, &h->r_xyz, &h->r_nrm, &h->r_cov}) b->release();
-    for (DevBuf* b : {&h->ov_keys[0], &h->ov_keys[1], &h->ov_sorted, &h->ov_ukeys[0], &h->ov_ukeys[1], &h->ov_ucnt[0], &h->ov_ucnt[1], &h->ov_flags[0], &h->ov_flags[1], &h->ov_offs[0], &h->ov_offs[1], &h->ov_misc, &h->ov_tmp, &h->ov_sidx, &h->i_info}) b->release();
+    for (DevBuf* b : {&h->ov_keys[0], &h->ov_keys[1], &h->ov_sorted, &h->ov_ukeys[0], &h->ov_ukeys[1], &h->ov_ucnt[0], &h->ov_ucnt[1], &h->ov_flags[0], &h->ov_flags[1], &h->ov_offs[0], &h->ov_offs[1], &h->ov_misc, &h->ov_sidx, &h->i_info}) b->release();
     h->n_eig.release();
     h->n_cov.release();
     h->n_ids.release();
@@ -392,14 +395,14 @@ void reg_destroy(reg_handle* h) {
     h->n_mom.release();
     DevBuf* bufs[] = {&h->t_raw, &h->t_nrm_raw, &h->t_cov_raw, &h->t_centred, &h->t_keys, &h->t_keys2, &h->t_vals,
                       &h->t_vals2, &h->t_pts, &h->t_nrm, &h->t_cov, &h->t_flags, &h->t_scan, &h->t_hash, &h->t_cells,
-                      &h->t_tmp, &h->t_misc, &h->t_dir, &h->t_rows, &h->s_raw, &h->s_nrm_raw, &h->s_cov_raw, &h->s_xyz, &h->s_nrm, &h->s_cov,
+                      &h->rp_tmp, &h->t_misc, &h->t_dir, &h->t_rows, &h->s_raw, &h->s_nrm_raw, &h->s_cov_raw, &h->s_xyz, &h->s_nrm, &h->s_cov,
                       &h->s_misc, &h->i_pos, &h->i_d2, &h->i_w, &h->i_hist, &h->i_state, &h->i_partials, &h->i_sums,
                       &h->i_ids, &h->d_contrib, &h->d_gathered, &h->s_prep, &h->i_iter, &h->t_halo_start, &h->t_halo_cursor, &h->t_halo_pts, &h->t_halo_dir, &h->i_band, &h->i_acc, &h->i_cache, &h->i_stats, &h->i_queue, &h->i_qcount, &h->i_hint, &h->s_keys, &h->s_keys2, &h->s_perm, &h->s_perm2, &h->s_tmp, &h->i_tmpf, &h->i_tail_sync, &h->i_tail_rows, &h->i_tail_band,
                       &h->pm_pos, &h->pm_d2, &h->pm_w, &h->pm_keys, &h->pm_hist, &h->pm_sel, &h->pm_state, &h->pm_partials,
                       &h->pm_sorted, &h->pm_sort_tmp, &h->pm_var,
                       &h->xt_state, &h->xt_rows,
                       &h->f_in, &h->f_in_nrm, &h->f_in_cov, &h->f_px, &h->f_pn, &h->f_pc, &h->f_perm, &h->f_keys, &h->f_keys2,
-                      &h->f_tmp, &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
+                      &h->f_segs, &h->f_boxes, &h->f_boxes2, &h->f_leaf, &h->f_mom, &h->f_mom2, &h->f_lid,
                       &h->f_keep, &h->f_pos, &h->f_misc, &h->f_out, &h->f_fields, &h->f_draws,
                       &h->o_keys, &h->o_keys_s, &h->o_iota, &h->o_idx, &h->o_idx2, &h->o_rank, &h->o_rank_a, &h->o_rank_s,
                       &h->o_c, &h->o_kk, &h->o_heads, &h->o_pos, &h->o_open, &h->o_depth, &h->o_start, &h->o_rand,
@@ -545,24 +548,13 @@ static reg_status build_grid(reg_handle* h, float c, const float bmin[3], const 
     auto bits_for = [](double v) { int b = 1; while ((double)(1ull << b) < v) ++b; return b; };
     const int bz_bits = bits_for(std::ceil(dims[2] / kBrickDim) + 1);
     const int end_bit = std::min(64, 3 * kBrickLog2 + 2 * kBrickBits + bz_bits);
-    size_t tmp_bytes = 0;
-    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tmp_bytes, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                        h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)m, 0, end_bit,
-                                        h->stream));
-    HIPCHK(h, h->t_tmp.reserve(tmp_bytes));
-    HIPCHK(h, rocprim::radix_sort_pairs(h->t_tmp.p, tmp_bytes, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                        h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)m, 0, end_bit,
-                                        h->stream));
+    REGCHK(sort_pairs(h, h->rp_tmp, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
+                      h->t_vals2.as<uint32_t>(), (size_t)m, 0, end_bit));
     // brick heads -> brick ids
     HIPCHK(h, h->t_flags.reserve(m * 4));
     HIPCHK(h, h->t_scan.reserve(m * 4));
     k_brick_heads<<<grid_for(m), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), m, h->t_flags.as<uint32_t>());
-    size_t scan_bytes = 0;
-    HIPCHK(h, rocprim::inclusive_scan(nullptr, scan_bytes, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(),
-                                      (size_t)m, rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(scan_bytes));
-    HIPCHK(h, rocprim::inclusive_scan(h->t_tmp.p, scan_bytes, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(),
-                                      (size_t)m, rocprim::plus<uint32_t>(), h->stream));
+    REGCHK(scan_incl(h, h->rp_tmp, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), (size_t)m));
     uint32_t nb = 0;
     HIPCHK(h, hipMemcpyAsync(&nb, h->t_scan.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -608,12 +600,7 @@ static reg_status build_grid(reg_handle* h, float c, const float bmin[3], const 
     g.bdx = bdx;
     g.bdy = bdy;
     g.bdz = bdz;
-    size_t ex_bytes = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, ex_bytes, h->t_cells.as<uint32_t>(), h->t_cells.as<uint32_t>(), 0u,
-                                      n_cells, rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(ex_bytes));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, ex_bytes, h->t_cells.as<uint32_t>(), h->t_cells.as<uint32_t>(), 0u,
-                                      n_cells, rocprim::plus<uint32_t>(), h->stream));
+    REGCHK(scan_excl(h, h->rp_tmp, h->t_cells.as<uint32_t>(), h->t_cells.as<uint32_t>(), n_cells));
     HIPCHK(h, hipMemcpyAsync(occupied, h->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     g.hash_mask = cap - 1;
@@ -700,13 +687,7 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     }
     k_halo_insert<<<grid_for(h->m), 256, 0, h->stream>>>(h->t_pts.as<float4>(), h->m, hc, 0,
                                                          h->t_halo_start.as<uint32_t>(), nullptr, bound ? occ : nullptr);
-    size_t ex_bytes = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, ex_bytes, h->t_halo_start.as<uint32_t>(), h->t_halo_start.as<uint32_t>(),
-                                      0u, nbins + 1, rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(ex_bytes));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, ex_bytes, h->t_halo_start.as<uint32_t>(),
-                                      h->t_halo_start.as<uint32_t>(), 0u, nbins + 1, rocprim::plus<uint32_t>(),
-                                      h->stream));
+    REGCHK(scan_excl(h, h->rp_tmp, h->t_halo_start.as<uint32_t>(), h->t_halo_start.as<uint32_t>(), nbins + 1));
     uint32_t total = 0;
     HIPCHK(h, hipMemcpyAsync(&total, h->t_halo_start.as<uint32_t>() + nbins, 4, hipMemcpyDeviceToHost, h->stream));
     if (bound) {
@@ -916,49 +897,21 @@ reg_status reg_set_target_f64(reg_handle* h, const double* xyz, const double* no
     }
     if (!xyz || m > 0x7fffffffLL) return REG_BAD_ARGUMENT;
     CropCfg c;
-    std::memset(&c, 0, sizeof(c));
-    if (crop) {
-        if (crop->type < REG_CROP_NONE || crop->type > REG_CROP_CYLINDER) return REG_BAD_ARGUMENT;
-        c.type = crop->type;
-        c.cx = crop->center[0];
-        c.cy = crop->center[1];
-        c.cz = crop->center[2];
-        c.rmin = crop->radius_min;
-        c.rmax = crop->radius_max;
-        c.zmin = crop->min_z;
-        c.zmax = crop->max_z;
-    }
+    if (!crop_cfg(crop, &c)) return REG_BAD_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const double *d_xyz = xyz, *d_nrm = normals, *d_cov = covs;
-    if (!on_device) {
-        HIPCHK(h, h->c_in_xyz.reserve((size_t)m * 24));
-        HIPCHK(h, hipMemcpyAsync(h->c_in_xyz.p, xyz, (size_t)m * 24, hipMemcpyHostToDevice, h->stream));
-        d_xyz = h->c_in_xyz.as<double>();
-        if (normals) {
-            HIPCHK(h, h->c_in_nrm.reserve((size_t)m * 24));
-            HIPCHK(h, hipMemcpyAsync(h->c_in_nrm.p, normals, (size_t)m * 24, hipMemcpyHostToDevice, h->stream));
-            d_nrm = h->c_in_nrm.as<double>();
-        }
-        if (covs) {
-            HIPCHK(h, h->c_in_cov.reserve((size_t)m * 72));
-            HIPCHK(h, hipMemcpyAsync(h->c_in_cov.p, covs, (size_t)m * 72, hipMemcpyHostToDevice, h->stream));
-            d_cov = h->c_in_cov.as<double>();
-        }
-    }
+    const double *d_xyz = nullptr, *d_nrm = nullptr, *d_cov = nullptr;
+    HIPCHK(h, staged_input(h, h->c_in_xyz, xyz, (size_t)m * 3, on_device, &d_xyz));
+    HIPCHK(h, staged_input(h, h->c_in_nrm, normals, (size_t)m * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->c_in_cov, covs, (size_t)m * 9, on_device, &d_cov));
     HIPCHK(h, h->c_flags.reserve((size_t)m * 4));
     HIPCHK(h, h->c_offs.reserve((size_t)m * 4));
-    k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, m, c, h->c_flags.as<uint32_t>());
-    size_t tb = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(tb));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    uint32_t last[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&last[0], h->c_offs.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&last[1], h->c_flags.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    uint32_t *flags = h->c_flags.as<uint32_t>(), *offs = h->c_offs.as<uint32_t>();
+    k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, m, c, flags);
+    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)m));
+    uint32_t last[2];
+    REGCHK(flag_total_async(h, flags, offs, m, last));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t kept = (int64_t)last[0] + (int64_t)last[1];
+    const int64_t kept = flag_total(last);
     if (n_kept) *n_kept = kept;
     if (kept == 0) {
         h->m = 0;
@@ -969,8 +922,7 @@ reg_status reg_set_target_f64(reg_handle* h, const double* xyz, const double* no
     if (d_nrm) HIPCHK(h, h->c_nrm.reserve((size_t)kept * 12));
     if (d_cov) HIPCHK(h, h->c_cov.reserve((size_t)kept * 24));
     HIPCHK(h, h->c_idx.reserve((size_t)kept * 4));
-    k_crop_gather<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, d_nrm, d_cov, m, h->c_flags.as<uint32_t>(),
-                                                      h->c_offs.as<uint32_t>(), h->c_xyz.as<float>(),
+    k_crop_gather<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, d_nrm, d_cov, m, flags, offs, h->c_xyz.as<float>(),
                                                       d_nrm ? h->c_nrm.as<float>() : nullptr,
                                                       d_cov ? h->c_cov.as<float>() : nullptr, h->c_idx.as<int32_t>());
     const reg_status s = reg_set_target(h, h->c_xyz.as<float>(), 3, d_nrm ? h->c_nrm.as<float>() : nullptr, 3,
@@ -1003,20 +955,8 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
         return REG_BAD_ARGUMENT;
     if (m == 0) return REG_OK;
     CropCfg c;
-    std::memset(&c, 0, sizeof(c));
-    if (volume) {
-        if (volume->type < REG_CROP_NONE || volume->type > REG_CROP_CYLINDER) return REG_BAD_ARGUMENT;
-        c.type = volume->type;
-        c.cx = volume->center[0];
-        c.cy = volume->center[1];
-        c.cz = volume->center[2];
-        c.rmin = volume->radius_min;
-        c.rmax = volume->radius_max;
-        c.zmin = volume->min_z;
-        c.zmax = volume->max_z;
-    }
+    if (!crop_cfg(volume, &c)) return REG_BAD_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const hipMemcpyKind in_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const hipMemcpyKind out_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (!(voxel_size > 0.0)) {   // helpers.cpp:121-124: nothing to do
         HIPCHK(h, hipMemcpyAsync(out_xyz, xyz, (size_t)m * 24, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost, h->stream));
@@ -1027,25 +967,19 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
         if (n_outside) *n_outside = m;
         return REG_OK;
     }
-    const double *d_xyz = xyz, *d_nrm = normals, *d_cov = covs;
+    const double *d_xyz = nullptr, *d_nrm = nullptr, *d_cov = nullptr;
+    HIPCHK(h, staged_input(h, h->c_in_xyz, xyz, (size_t)m * 3, on_device, &d_xyz));
+    HIPCHK(h, staged_input(h, h->c_in_nrm, normals, (size_t)m * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->c_in_cov, covs, (size_t)m * 9, on_device, &d_cov));
     double *d_oxyz = out_xyz, *d_onrm = out_normals, *d_ocov = out_covs;
     if (!on_device) {
-        HIPCHK(h, h->c_in_xyz.reserve((size_t)m * 24));
-        HIPCHK(h, hipMemcpyAsync(h->c_in_xyz.p, xyz, (size_t)m * 24, in_kind, h->stream));
-        d_xyz = h->c_in_xyz.as<double>();
         HIPCHK(h, h->v_oxyz.reserve((size_t)m * 24));
         d_oxyz = h->v_oxyz.as<double>();
         if (normals) {
-            HIPCHK(h, h->c_in_nrm.reserve((size_t)m * 24));
-            HIPCHK(h, hipMemcpyAsync(h->c_in_nrm.p, normals, (size_t)m * 24, in_kind, h->stream));
-            d_nrm = h->c_in_nrm.as<double>();
             HIPCHK(h, h->v_onrm.reserve((size_t)m * 24));
             d_onrm = h->v_onrm.as<double>();
         }
         if (covs) {
-            HIPCHK(h, h->c_in_cov.reserve((size_t)m * 72));
-            HIPCHK(h, hipMemcpyAsync(h->c_in_cov.p, covs, (size_t)m * 72, in_kind, h->stream));
-            d_cov = h->c_in_cov.as<double>();
             HIPCHK(h, h->v_ocov.reserve((size_t)m * 72));
             d_ocov = h->v_ocov.as<double>();
         }
@@ -1057,61 +991,41 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
     HIPCHK(h, h->v_oout.reserve((size_t)m * 4));
     HIPCHK(h, h->t_misc.reserve(256));
     HIPCHK(h, hipMemsetAsync(h->t_misc.p, 0, 4, h->stream));
-    k_vox_classify<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, m, c, inv, h->c_flags.as<uint32_t>(), h->v_fout.as<uint32_t>(),
-                                                       h->t_misc.as<uint32_t>());
-    size_t tb = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(tb));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, tb, h->v_fout.as<uint32_t>(), h->v_oout.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    uint32_t tail[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tail[0], h->c_offs.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tail[1], h->c_flags.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tail[2], h->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
+    uint32_t *f_in = h->c_flags.as<uint32_t>(), *o_in = h->c_offs.as<uint32_t>();     // inside the volume: flags, offsets
+    uint32_t *f_out = h->v_fout.as<uint32_t>(), *o_out = h->v_oout.as<uint32_t>();    // outside
+    k_vox_classify<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, m, c, inv, f_in, f_out, h->t_misc.as<uint32_t>());
+    REGCHK(scan_excl(h, h->rp_tmp, f_in, o_in, (size_t)m));
+    REGCHK(scan_excl(h, h->rp_tmp, f_out, o_out, (size_t)m));
+    uint32_t tail[2], bad = 0;
+    REGCHK(flag_total_async(h, f_in, o_in, m, tail));
+    HIPCHK(h, hipMemcpyAsync(&bad, h->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (tail[2]) {
+    if (bad) {
         h->err = "voxel_size too small for the extent of the cloud (voxel index exceeds 2^20)";
         return REG_BAD_ARGUMENT;
     }
-    const int64_t n_in = (int64_t)tail[0] + tail[1], n_outs = m - n_in;
+    const int64_t n_in = flag_total(tail), n_outs = m - n_in;
     int64_t n_vox = 0;
     HIPCHK(h, h->t_keys.reserve((size_t)std::max<int64_t>(n_in, 1) * 8));
     HIPCHK(h, h->t_keys2.reserve((size_t)std::max<int64_t>(n_in, 1) * 8));
     HIPCHK(h, h->t_vals.reserve((size_t)std::max<int64_t>(n_in, 1) * 4));
     HIPCHK(h, h->t_vals2.reserve((size_t)std::max<int64_t>(n_in, 1) * 4));
-    k_vox_scatter<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, d_nrm, d_cov, m, inv, h->c_flags.as<uint32_t>(),
-                                                      h->c_offs.as<uint32_t>(), h->v_oout.as<uint32_t>(),
-                                                      h->t_keys.as<uint64_t>(), h->t_vals.as<uint32_t>(), d_oxyz, d_onrm,
-                                                      d_ocov);
+    k_vox_scatter<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, d_nrm, d_cov, m, inv, f_in, o_in, o_out, h->t_keys.as<uint64_t>(),
+                                                      h->t_vals.as<uint32_t>(), d_oxyz, d_onrm, d_ocov);
     if (n_in > 0) {
-        size_t sb = 0;
-        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, sb, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                            h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)n_in, 0,
-                                            3 * kVoxBits, h->stream));
-        HIPCHK(h, h->t_tmp.reserve(sb));
-        HIPCHK(h, rocprim::radix_sort_pairs(h->t_tmp.p, sb, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                            h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)n_in, 0,
-                                            3 * kVoxBits, h->stream));
+        REGCHK(sort_pairs(h, h->rp_tmp, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
+                          h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits));
         HIPCHK(h, h->t_flags.reserve((size_t)n_in * 4));
         HIPCHK(h, h->t_scan.reserve((size_t)n_in * 4));
-        k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, h->t_flags.as<uint32_t>());
-        size_t eb = 0;
-        HIPCHK(h, rocprim::exclusive_scan(nullptr, eb, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), 0u, (size_t)n_in,
-                                          rocprim::plus<uint32_t>(), h->stream));
-        HIPCHK(h, h->t_tmp.reserve(eb));
-        HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, eb, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), 0u, (size_t)n_in,
-                                          rocprim::plus<uint32_t>(), h->stream));
-        uint32_t lv[2] = {0, 0};
-        HIPCHK(h, hipMemcpyAsync(&lv[0], h->t_scan.as<uint32_t>() + (n_in - 1), 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipMemcpyAsync(&lv[1], h->t_flags.as<uint32_t>() + (n_in - 1), 4, hipMemcpyDeviceToHost, h->stream));
-        k_vox_reduce<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), h->t_vals2.as<uint32_t>(), n_in,
-                                                            h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), d_xyz, d_nrm,
-                                                            d_cov, n_outs, d_oxyz, d_onrm, d_ocov);
+        uint32_t *heads = h->t_flags.as<uint32_t>(), *vox = h->t_scan.as<uint32_t>();
+        k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads);
+        REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n_in));
+        uint32_t lv[2];
+        REGCHK(flag_total_async(h, heads, vox, n_in, lv));
+        k_vox_reduce<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), h->t_vals2.as<uint32_t>(), n_in, heads, vox,
+                                                            d_xyz, d_nrm, d_cov, n_outs, d_oxyz, d_onrm, d_ocov);
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        n_vox = (int64_t)lv[0] + lv[1];
+        n_vox = flag_total(lv);
     }
     const int64_t total = n_outs + n_vox;
     if (!on_device) {
@@ -1140,33 +1054,12 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
     }
     if (m == 0 || n_scan == 0) return REG_OK;
     CropCfg c;
-    std::memset(&c, 0, sizeof(c));
-    if (subset) {
-        if (subset->type < REG_CROP_NONE || subset->type > REG_CROP_CYLINDER) return REG_BAD_ARGUMENT;
-        c.type = subset->type;
-        c.cx = subset->center[0];
-        c.cy = subset->center[1];
-        c.cz = subset->center[2];
-        c.rmin = subset->radius_min;
-        c.rmax = subset->radius_max;
-        c.zmin = subset->min_z;
-        c.zmax = subset->max_z;
-    }
+    if (!crop_cfg(subset, &c)) return REG_BAD_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const double *d_map = map_xyz, *d_nrm = map_normals, *d_scan = scan_xyz;
-    if (!on_device) {
-        HIPCHK(h, h->c_in_xyz.reserve((size_t)m * 24));
-        HIPCHK(h, hipMemcpyAsync(h->c_in_xyz.p, map_xyz, (size_t)m * 24, hipMemcpyHostToDevice, h->stream));
-        d_map = h->c_in_xyz.as<double>();
-        if (map_normals) {
-            HIPCHK(h, h->c_in_nrm.reserve((size_t)m * 24));
-            HIPCHK(h, hipMemcpyAsync(h->c_in_nrm.p, map_normals, (size_t)m * 24, hipMemcpyHostToDevice, h->stream));
-            d_nrm = h->c_in_nrm.as<double>();
-        }
-        HIPCHK(h, h->c_in_cov.reserve((size_t)n_scan * 24));
-        HIPCHK(h, hipMemcpyAsync(h->c_in_cov.p, scan_xyz, (size_t)n_scan * 24, hipMemcpyHostToDevice, h->stream));
-        d_scan = h->c_in_cov.as<double>();
-    }
+    const double *d_map = nullptr, *d_nrm = nullptr, *d_scan = nullptr;
+    HIPCHK(h, staged_input(h, h->c_in_xyz, map_xyz, (size_t)m * 3, on_device, &d_map));
+    HIPCHK(h, staged_input(h, h->c_in_nrm, map_normals, (size_t)m * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->c_in_cov, scan_xyz, (size_t)n_scan * 3, on_device, &d_scan));   // (the third staging buffer)
     const double inv = 1.0 / voxel_size;
     // 1. candidate map points (inside the subset volume), keyed by voxel, stably sorted
     HIPCHK(h, h->c_flags.reserve((size_t)m * 4));
@@ -1175,78 +1068,54 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
     HIPCHK(h, h->v_oout.reserve((size_t)m * 4));
     HIPCHK(h, h->t_misc.reserve(256));
     HIPCHK(h, hipMemsetAsync(h->t_misc.p, 0, 4, h->stream));
-    k_vox_classify<<<grid_for(m), 256, 0, h->stream>>>(d_map, m, c, inv, h->c_flags.as<uint32_t>(), h->v_fout.as<uint32_t>(),
-                                                       h->t_misc.as<uint32_t>());
-    size_t tb = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(tb));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, tb, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    uint32_t tail[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(&tail[0], h->c_offs.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tail[1], h->c_flags.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&tail[2], h->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
+    uint32_t *f_in = h->c_flags.as<uint32_t>(), *o_in = h->c_offs.as<uint32_t>();    // inside the subset volume: flags, offsets
+    uint32_t *mark = h->v_fout.as<uint32_t>(), *o_mark = h->v_oout.as<uint32_t>();   // step 3's marks over the map
+    k_vox_classify<<<grid_for(m), 256, 0, h->stream>>>(d_map, m, c, inv, f_in, mark, h->t_misc.as<uint32_t>());
+    REGCHK(scan_excl(h, h->rp_tmp, f_in, o_in, (size_t)m));
+    uint32_t tail[2], bad = 0;
+    REGCHK(flag_total_async(h, f_in, o_in, m, tail));
+    HIPCHK(h, hipMemcpyAsync(&bad, h->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (tail[2]) {
+    if (bad) {
         h->err = "voxel_size too small for the extent of the map (voxel index exceeds 2^20)";
         return REG_BAD_ARGUMENT;
     }
-    const int64_t n_in = (int64_t)tail[0] + tail[1];
+    const int64_t n_in = flag_total(tail);
     if (n_in == 0) return REG_OK;
     HIPCHK(h, h->t_keys.reserve((size_t)n_in * 8));
     HIPCHK(h, h->t_keys2.reserve((size_t)n_in * 8));
     HIPCHK(h, h->t_vals.reserve((size_t)n_in * 4));
     HIPCHK(h, h->t_vals2.reserve((size_t)n_in * 4));
-    k_carve_keys<<<grid_for(m), 256, 0, h->stream>>>(d_map, m, inv, h->c_flags.as<uint32_t>(), h->c_offs.as<uint32_t>(),
-                                                     h->t_keys.as<uint64_t>(), h->t_vals.as<uint32_t>());
-    size_t sb = 0;
-    HIPCHK(h, rocprim::radix_sort_pairs(nullptr, sb, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                        h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits,
-                                        h->stream));
-    HIPCHK(h, h->t_tmp.reserve(sb));
-    HIPCHK(h, rocprim::radix_sort_pairs(h->t_tmp.p, sb, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(),
-                                        h->t_vals.as<uint32_t>(), h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits,
-                                        h->stream));
+    k_carve_keys<<<grid_for(m), 256, 0, h->stream>>>(d_map, m, inv, f_in, o_in, h->t_keys.as<uint64_t>(), h->t_vals.as<uint32_t>());
+    REGCHK(sort_pairs(h, h->rp_tmp, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
+                      h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits));
     // 2. unique voxels
     HIPCHK(h, h->t_flags.reserve((size_t)n_in * 4));
     HIPCHK(h, h->t_scan.reserve((size_t)n_in * 4));
-    k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, h->t_flags.as<uint32_t>());
-    size_t eb = 0;
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, eb, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), 0u, (size_t)n_in,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(eb));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, eb, h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>(), 0u, (size_t)n_in,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    uint32_t lv[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&lv[0], h->t_scan.as<uint32_t>() + (n_in - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&lv[1], h->t_flags.as<uint32_t>() + (n_in - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    uint32_t *heads = h->t_flags.as<uint32_t>(), *vox = h->t_scan.as<uint32_t>();
+    k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads);
+    REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n_in));
+    uint32_t lv[2];
+    REGCHK(flag_total_async(h, heads, vox, n_in, lv));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t nu = (int64_t)lv[0] + lv[1];
+    const int64_t nu = flag_total(lv);
     HIPCHK(h, h->v_ukeys.reserve((size_t)nu * 8));
     HIPCHK(h, h->v_ustart.reserve((size_t)(nu + 1) * 4));
-    k_carve_unique<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, h->t_flags.as<uint32_t>(),
-                                                          h->t_scan.as<uint32_t>(), h->v_ukeys.as<uint64_t>(),
+    k_carve_unique<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads, vox, h->v_ukeys.as<uint64_t>(),
                                                           h->v_ustart.as<uint32_t>());
     const uint32_t n_in32 = (uint32_t)n_in;
     HIPCHK(h, hipMemcpyAsync(h->v_ustart.as<uint32_t>() + nu, &n_in32, 4, hipMemcpyHostToDevice, h->stream));
-    // 3. rays -> marks (v_fout / v_oout are reused as mark / offsets over the map)
-    HIPCHK(h, hipMemsetAsync(h->v_fout.p, 0, (size_t)m * 4, h->stream));
+    // 3. rays -> marks
+    HIPCHK(h, hipMemsetAsync(mark, 0, (size_t)m * 4, h->stream));
     k_carve_rays<<<grid_for(n_scan), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], voxel_size, max_ray,
                                                           truncation, min_dot, inv, h->v_ukeys.as<uint64_t>(),
-                                                          h->v_ustart.as<uint32_t>(), nu, h->t_vals2.as<uint32_t>(), d_nrm,
-                                                          h->v_fout.as<uint32_t>());
+                                                          h->v_ustart.as<uint32_t>(), nu, h->t_vals2.as<uint32_t>(), d_nrm, mark);
     // 4. ascending list of marked map indices
-    HIPCHK(h, rocprim::exclusive_scan(nullptr, tb, h->v_fout.as<uint32_t>(), h->v_oout.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    HIPCHK(h, h->t_tmp.reserve(tb));
-    HIPCHK(h, rocprim::exclusive_scan(h->t_tmp.p, tb, h->v_fout.as<uint32_t>(), h->v_oout.as<uint32_t>(), 0u, (size_t)m,
-                                      rocprim::plus<uint32_t>(), h->stream));
-    uint32_t rt[2] = {0, 0};
-    HIPCHK(h, hipMemcpyAsync(&rt[0], h->v_oout.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(&rt[1], h->v_fout.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, h->stream));
+    REGCHK(scan_excl(h, h->rp_tmp, mark, o_mark, (size_t)m));
+    uint32_t rt[2];
+    REGCHK(flag_total_async(h, mark, o_mark, m, rt));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t nr = (int64_t)rt[0] + rt[1];
+    const int64_t nr = flag_total(rt);
     int32_t* d_out = removed;
     if (!on_device) {
         HIPCHK(h, h->c_idx.reserve((size_t)std::max<int64_t>(nr, 1) * 4));
@@ -1254,7 +1123,7 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
         h->crop_kept = 0;   // c_idx no longer holds the crop map of reg_set_target_f64
     }
     if (nr > 0) {
-        k_carve_collect<<<grid_for(m), 256, 0, h->stream>>>(h->v_fout.as<uint32_t>(), h->v_oout.as<uint32_t>(), m, d_out);
+        k_carve_collect<<<grid_for(m), 256, 0, h->stream>>>(mark, o_mark, m, d_out);
         if (!on_device) HIPCHK(h, hipMemcpyAsync(removed, d_out, (size_t)nr * 4, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1499,14 +1368,8 @@ reg_status reg_set_source(reg_handle* h, const float* xyz, int64_t xyz_stride, c
         const float cell = h->m > 0 ? h->info.cell_size * (float)kBrickDim : 1.0f;
         k_source_keys<<<grid_for(n), 256, 0, h->stream>>>(h->s_raw.as<float>(), xyz_stride, n, 1.0f / cell,
                                                           h->s_keys.as<uint32_t>(), h->s_perm.as<uint32_t>());
-        size_t tb = 0;
-        HIPCHK(h, rocprim::radix_sort_pairs(nullptr, tb, h->s_keys.as<uint32_t>(), h->s_keys2.as<uint32_t>(),
-                                            h->s_perm.as<uint32_t>(), h->s_perm2.as<uint32_t>(), (size_t)n, 0, 30,
-                                            h->stream));
-        HIPCHK(h, h->s_tmp.reserve(tb));
-        HIPCHK(h, rocprim::radix_sort_pairs(h->s_tmp.p, tb, h->s_keys.as<uint32_t>(), h->s_keys2.as<uint32_t>(),
-                                            h->s_perm.as<uint32_t>(), h->s_perm2.as<uint32_t>(), (size_t)n, 0, 30,
-                                            h->stream));
+        REGCHK(sort_pairs(h, h->s_tmp, h->s_keys.as<uint32_t>(), h->s_keys2.as<uint32_t>(), h->s_perm.as<uint32_t>(),
+                          h->s_perm2.as<uint32_t>(), (size_t)n, 0, 30));
         h->perm = h->s_perm2.as<uint32_t>();
     }
     HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
@@ -1531,22 +1394,10 @@ reg_status reg_set_source_f64(reg_handle* h, const double* xyz, const double* no
     }
     if (!xyz || n > 0x7fffffffLL) return REG_BAD_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const double *d_xyz = xyz, *d_nrm = normals, *d_cov = covs;
-    if (!on_device) {
-        HIPCHK(h, h->r_in_xyz.reserve((size_t)n * 24));
-        HIPCHK(h, hipMemcpyAsync(h->r_in_xyz.p, xyz, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
-        d_xyz = h->r_in_xyz.as<double>();
-        if (normals) {
-            HIPCHK(h, h->r_in_nrm.reserve((size_t)n * 24));
-            HIPCHK(h, hipMemcpyAsync(h->r_in_nrm.p, normals, (size_t)n * 24, hipMemcpyHostToDevice, h->stream));
-            d_nrm = h->r_in_nrm.as<double>();
-        }
-        if (covs) {
-            HIPCHK(h, h->r_in_cov.reserve((size_t)n * 72));
-            HIPCHK(h, hipMemcpyAsync(h->r_in_cov.p, covs, (size_t)n * 72, hipMemcpyHostToDevice, h->stream));
-            d_cov = h->r_in_cov.as<double>();
-        }
-    }
+    const double *d_xyz = nullptr, *d_nrm = nullptr, *d_cov = nullptr;
+    HIPCHK(h, staged_input(h, h->r_in_xyz, xyz, (size_t)n * 3, on_device, &d_xyz));
+    HIPCHK(h, staged_input(h, h->r_in_nrm, normals, (size_t)n * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->r_in_cov, covs, (size_t)n * 9, on_device, &d_cov));
     HIPCHK(h, h->r_xyz.reserve((size_t)n * 12));
     if (d_nrm) HIPCHK(h, h->r_nrm.reserve((size_t)n * 12));
     if (d_cov) HIPCHK(h, h->r_cov.reserve((size_t)n * 24));

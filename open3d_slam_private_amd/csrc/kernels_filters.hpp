@@ -80,15 +80,11 @@ k_ssn_pack(const float* __restrict__ xyz, int64_t stride, int n, float* __restri
         }
 }
 
-__device__ __forceinline__ float ssn_from_orderable(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
 // root box + identity permutation
 __global__ void __launch_bounds__(256)
 k_ssn_init(const uint32_t* __restrict__ misc, int n, float* __restrict__ box0, int32_t* __restrict__ perm) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < 6) box0[i] = ssn_from_orderable(misc[i]);
+    if (i < 6) box0[i] = float_from_orderable(misc[i]);
     if (i < n) perm[i] = i;
 }
 
