@@ -34,6 +34,17 @@ static reg_status dist_stream_wait(reg_handle* h, double timeout_s, const char* 
     }
 }
 
+// Is the stream idle?  A device fault is an error: it must end the caller's polling loop.
+static reg_status dist_stream_idle(reg_handle* h, int32_t* idle) {
+    const hipError_t qe = hipStreamQuery(h->stream);
+    if (qe != hipSuccess && qe != hipErrorNotReady) {
+        h->err = std::string("device fault while waiting for an iteration: ") + hipGetErrorString(qe);
+        return REG_DEVICE_ERROR;
+    }
+    *idle = qe == hipSuccess ? 1 : 0;
+    return REG_OK;
+}
+
 // The Open3D costs have no distributed form (include/o3dslam_reg.h): every multi-rank entry point refuses them.
 static reg_status o3d_dist_unsupported(reg_handle* h) {
     h->err = h->pm_on ? "a handle with a libpointmatcher chain (reg_set_pm_chain) has no distributed path"
@@ -303,13 +314,7 @@ reg_status reg_dist_poll(reg_handle* h, reg_dist_status* out) {
     out->stall = any ? mir->stall : 0;
     out->limit_last = any ? mir->limit_last : INFINITY;
     out->limit_prev = any ? mir->limit_prev : INFINITY;
-    const hipError_t qe = hipStreamQuery(h->stream);
-    if (qe != hipSuccess && qe != hipErrorNotReady) {
-        h->err = std::string("device fault while waiting for an iteration: ") + hipGetErrorString(qe);
-        return REG_DEVICE_ERROR;
-    }
-    out->stream_idle = qe == hipSuccess ? 1 : 0;
-    return REG_OK;
+    return dist_stream_idle(h, &out->stream_idle);
 }
 
 // The record of ONE specific sequence (1 = the first iteration enqueued after reg_dist_begin).  out->sequences_done is
@@ -320,12 +325,8 @@ reg_status reg_dist_record(reg_handle* h, int64_t seq_rel, reg_dist_status* out)
     if (!h || !out || seq_rel < 1) return REG_BAD_ARGUMENT;
     const unsigned long long want = h->dist_seq0 + (unsigned long long)seq_rel;
     // idle must be sampled BEFORE the record: "idle and no record" then really means the kernel did not report
-    const hipError_t qe = hipStreamQuery(h->stream);
-    if (qe != hipSuccess && qe != hipErrorNotReady) {   // a device fault must end the caller's polling loop
-        h->err = std::string("device fault while waiting for an iteration: ") + hipGetErrorString(qe);
-        return REG_DEVICE_ERROR;
-    }
-    const int idle = qe == hipSuccess ? 1 : 0;
+    int32_t idle = 0;
+    REGCHK(dist_stream_idle(h, &idle));
     const HostMirror::SeqRecord* rec = &h->h_mirror->ring[want % kSeqRing];
     const unsigned long long got = __atomic_load_n(&rec->seq, __ATOMIC_ACQUIRE);
     std::memset(out, 0, sizeof(*out));
@@ -348,133 +349,73 @@ reg_status reg_dist_phase(reg_handle* h, int phase) {
     reg_status s = check_ready(h, true);
     if (s != REG_OK) return s;
     const bool trim = h->prm.cost == REG_COST_P2PL && h->prm.use_trimmed;
-    uint32_t* hist0 = h->i_hist.as<uint32_t>();
+    const float* d2 = h->i_d2.as<float>();
+    uint32_t* hist = h->i_hist.as<uint32_t>();
     SelectState* st = h->i_state.as<SelectState>();
-    const IterState* it = h->i_iter.as<IterState>();
     const int hb = std::min(h->n_blocks, 128);
     switch (phase) {
         case 0:
+        case 10:
             s = enqueue_match(h);
             if (s != REG_OK) return s;
-            if (trim) k_hist_level0<<<hb, 256, 0, h->stream>>>(h->i_d2.as<float>(), h->n, h->shift0, hist0, it);
+            if (phase == 0 && trim) launch_hist_level0(h, d2, h->n, hb, hist);   // always built here, whatever the match variant
             break;
         case 1:
-            if (trim)
-                k_select_level<<<hb, 256, 0, h->stream>>>(h->i_d2.as<float>(), h->n, 1, h->shift0, h->prm.trim_ratio,
-                                                          hist0, hist0 + 2048, nullptr, st, it);
-            break;
         case 2:
-            if (trim)
-                k_select_level<<<hb, 256, 0, h->stream>>>(h->i_d2.as<float>(), h->n, 2, h->shift0, h->prm.trim_ratio,
-                                                          hist0 + 2048, hist0 + 4096, hist0, st, it);
+            if (trim) launch_select_level(h, phase, d2, h->n, hb, hist, st, h->prm.trim_ratio);
             break;
-        case 3: {
-            // (the weights are always written, as in reg_register's select-based iteration: reg_get_correspondences reports them)
-            if (h->prm.cost == REG_COST_P2PL) {
-                const FilterCfg f = make_filter_cfg(h, h->prm.use_trimmed ? 2 : 0);
-                k_linearize_p2pl<<<h->n_blocks, 256, 0, h->stream>>>(
-                    h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, it, h->i_pos.as<int>(),
-                    h->i_d2.as<float>(), h->t_pts.as<float4>(), h->t_nrm.as<float4>(), f, st, hist0 + 4096, hist0 + 2048,
-                    h->shift0, h->i_w.as<float>(), h->i_partials.as<double>(), h->i_cache.as<float4>());
-            } else {
-                k_linearize_gicp<<<h->n_blocks, 256, 0, h->stream>>>(h->s_xyz.as<float4>(), h->s_cov.as<float4>(), h->n, it,
-                                                                     h->i_pos.as<int>(), h->i_d2.as<float>(),
-                                                                     h->t_pts.as<float4>(), h->t_cov.as<float4>(), h->i_w.as<float>(),
-                                                                     h->i_partials.as<double>());
+        case 11:
+            if (h->prm.cost != REG_COST_P2PL || h->dist_nmax <= 0) return REG_BAD_ARGUMENT;
+            if (trim) {
+                const int64_t n_all = (int64_t)h->dist_gather_ranks * h->dist_nmax;
+                const float* d2_all = h->d_d2all.as<float>();
+                const int gb = (int)std::min<int64_t>(128, (n_all + 255) / 256);
+                launch_hist_level0(h, d2_all, n_all, gb, hist);
+                launch_select_level(h, 1, d2_all, n_all, gb, hist, st, h->prm.trim_ratio);
+                launch_select_level(h, 2, d2_all, n_all, gb, hist, st, h->prm.trim_ratio);
             }
-            k_partials_sum<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_sums.as<double>(), it);
+            [[fallthrough]];   // the rest is phase 3 (point-to-plane here)
+        case 3:
+            // (the weights are always written, as in reg_register's select-based iteration: reg_get_correspondences reports them)
+            if (h->prm.cost == REG_COST_P2PL)
+                launch_linearize_p2pl(h, h->prm.use_trimmed ? 2 : 0, h->i_w.as<float>());
+            else
+                launch_linearize_gicp(h, h->i_w.as<float>());
+            // this rank's rows -> the 32 sums the caller all-reduces
+            k_partials_sum<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_sums.as<double>(),
+                                                      h->i_iter.as<IterState>());
             break;
-        }
         case 4:
-            ++h->seq;
-            k_reduce_update<<<1, 1024, 0, h->stream>>>(h->i_sums.as<double>(), 1, h->i_iter.as<IterState>(), h->d_mirror,
-                                                       h->seq, 0, nullptr, nullptr,
-                                                       h->prm.cost == REG_COST_P2PL ? st : nullptr, nullptr, 0, 0,
-                                                       h->prm.use_xicp ? h->i_xicp.as<XicpState>() : nullptr);
+            update_from_allreduced_sums(h);
             break;
         case 5: {
             // fused iteration, local half: search + weights + normal equations + band records (into this rank's
             // contribution block), then the block header.  Followed by the caller's ONE all-gather.
+            // (8 lanes per point whatever lanes_per_point says, launches not timed, no search statistics)
             if (h->prm.cost != REG_COST_P2PL || h->dist_ranks <= 0) return REG_BAD_ARGUMENT;
-            const FilterCfg f = make_filter_cfg(h, 0);
-            uint8_t* hint = h->dbg.match_variant == 2 ? nullptr : h->i_hint.as<uint8_t>();
             float* contrib = h->d_contrib.as<float>();
-            if (h->dbg.debug_flags & 16) {
-                const int blocks = grid_for(h->n * 8);
-                k_iter_fused<8><<<8 * ((blocks + 7) / 8), 256, 0, h->stream>>>(
-                    h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, h->i_iter.as<IterState>(),
-                    h->grid, h->t_nrm.as<float4>(), f, h->i_pos.as<int>(), h->i_d2.as<float>(), h->i_w.as<float>(), hint,
-                    contrib + kContribHdr, contrib_cap_for(h->dist_ranks), h->i_acc.as<double>(), blocks);
-            } else {
-                const int blocks = grid_for(h->n);
-                k_coh_check<<<8 * ((blocks + 7) / 8), 256, 0, h->stream>>>(
-                    h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, h->i_iter.as<IterState>(),
-                    h->grid, h->t_nrm.as<float4>(), f, h->i_pos.as<int>(), h->i_d2.as<float>(), h->i_w.as<float>(),
-                    h->i_cache.as<float4>(), h->i_queue.as<uint32_t>(), coherent_queue_cap(h->n), contrib + kContribHdr,
-                    contrib_cap_for(h->dist_ranks), h->i_acc.as<double>(), blocks);
-                k_coh_search<8><<<coherent_search_grid(h), 256, 0, h->stream>>>(
-                    h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, h->i_iter.as<IterState>(),
-                    h->grid, h->t_nrm.as<float4>(), f, h->i_pos.as<int>(), h->i_d2.as<float>(), h->i_w.as<float>(), hint,
-                    h->i_cache.as<float4>(), h->i_queue.as<uint32_t>(), coherent_queue_cap(h->n), contrib + kContribHdr,
-                    contrib_cap_for(h->dist_ranks), h->i_acc.as<double>(), coherent_slack(h), (CohStats*)nullptr);
-            }
-            k_pack_contrib<<<1, 64, 0, h->stream>>>(h->i_acc.as<double>(), it, contrib);
+            launch_fused_search<8>(h, contrib + kContribHdr, contrib_cap_for(h->dist_ranks), nullptr, false);
+            k_pack_contrib<<<1, 64, 0, h->stream>>>(h->i_acc.as<double>(), h->i_iter.as<IterState>(), contrib);
             h->have_match = true;
             break;
         }
         case 6:
             // fused iteration, global half: every rank reduces the SAME gathered blocks in the same order
             if (h->dist_ranks <= 0) return REG_BAD_ARGUMENT;
-            ++h->seq;
-            k_reduce_update<<<1, 1024, 0, h->stream>>>(nullptr, 0, h->i_iter.as<IterState>(), h->d_mirror, h->seq, 1,
-                                                       nullptr, h->i_w.as<float>(), nullptr, h->d_gathered.as<float>(),
-                                                       h->dist_ranks, h->dist_rank, nullptr);
+            update_fused_from_gathered(h);
             break;
-        case 10:
-            s = enqueue_match(h);
-            if (s != REG_OK) return s;
-            break;
-        case 11: {
-            if (h->prm.cost != REG_COST_P2PL || h->dist_nmax <= 0) return REG_BAD_ARGUMENT;
-            if (trim) {
-                const int64_t n_all = (int64_t)h->dist_gather_ranks * h->dist_nmax;
-                const float* d2_all = h->d_d2all.as<float>();
-                const int gb = (int)std::min<int64_t>(128, (n_all + 255) / 256);
-                k_hist_level0<<<gb, 256, 0, h->stream>>>(d2_all, n_all, h->shift0, hist0, it);
-                k_select_level<<<gb, 256, 0, h->stream>>>(d2_all, n_all, 1, h->shift0, h->prm.trim_ratio, hist0, hist0 + 2048,
-                                                          nullptr, st, it);
-                k_select_level<<<gb, 256, 0, h->stream>>>(d2_all, n_all, 2, h->shift0, h->prm.trim_ratio, hist0 + 2048,
-                                                          hist0 + 4096, hist0, st, it);
-            }
-            const FilterCfg f = make_filter_cfg(h, h->prm.use_trimmed ? 2 : 0);
-            k_linearize_p2pl<<<h->n_blocks, 256, 0, h->stream>>>(
-                h->s_xyz.as<float4>(), h->has_snrm ? h->s_nrm.as<float4>() : nullptr, h->n, it, h->i_pos.as<int>(),
-                h->i_d2.as<float>(), h->t_pts.as<float4>(), h->t_nrm.as<float4>(), f, st, hist0 + 4096, hist0 + 2048,
-                h->shift0, h->i_w.as<float>(), h->i_partials.as<double>(), h->i_cache.as<float4>());
-            k_partials_sum<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_sums.as<double>(), it);
-            break;
-        }
         // R8x on the distributed path, first iteration only: after phase 4 (which then only stashes the eigen-directions)
         //   7: this rank's share of the matched-point centre   -> caller all-reduces the 4 doubles of reg_dist_xicp_buffers
         //   8: this rank's share of the 12 information sums    -> caller all-reduces them
         //   9: decide, solve (constrained or not), update, report -- with the sequence number of phase 4
         case 7:
-        case 8: {
+        case 8:
             if (!h->prm.use_xicp) return REG_BAD_ARGUMENT;
-            const int blocks = (int)std::min<int64_t>(512, (h->n + 255) / 256);
-            if (phase == 7)
-                k_xicp_center<<<blocks, 256, 0, h->stream>>>(h->s_xyz.as<float4>(), h->n, it, h->i_pos.as<int>(),
-                                                             h->i_w.as<float>(), h->i_xicp.as<XicpState>());
-            else
-                k_xicp_detect<<<blocks, 256, 0, h->stream>>>(h->s_xyz.as<float4>(), h->n, it, h->i_pos.as<int>(),
-                                                             h->i_w.as<float>(), h->t_nrm.as<float4>(),
-                                                             h->i_xicp.as<XicpState>());
+            (phase == 7 ? launch_xicp_center : launch_xicp_detect)(h, h->i_pos.as<int>(), h->i_w.as<float>());
             break;
-        }
         case 9:
             if (!h->prm.use_xicp) return REG_BAD_ARGUMENT;
-            k_reduce_update<<<1, 1024, 0, h->stream>>>(nullptr, 0, h->i_iter.as<IterState>(), h->d_mirror, h->seq, 2, nullptr,
-                                                       nullptr, nullptr, nullptr, 0, 0, h->i_xicp.as<XicpState>());
+            update_xicp_finish(h);
             break;
         default:
             return REG_BAD_ARGUMENT;
@@ -515,35 +456,16 @@ reg_status reg_dist_finish(reg_handle* h, float T_out[16], reg_result* res) {
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     HIPCHK(h, hipGetLastError());
-    const HostMirror* mir = h->h_mirror;
     if (mirror_seq(h) <= h->dist_seq0) {
         h->err = "reg_dist_finish: no iteration has completed since reg_dist_begin";
         return REG_NOT_CONFIGURED;
     }
-    res->iterations = mir->iterations;
-    res->converged = mir->converged;
-    res->max_iter_reached = mir->max_iter_reached;
-    res->rank_last = mir->rank_last;
-    for (int k = 0; k < 6; ++k) {
-        res->localizable[k] = h->prm.use_xicp ? mir->localizable[k] : 1;
-        res->xicp_combined[k] = mir->xicp_comb[k];
-        res->xicp_high[k] = mir->xicp_high[k];
-    }
-    res->n_constraints = h->prm.use_xicp ? mir->n_constraints : 0;
     // the sums are the group's: fitness over the WHOLE reading where the handle knows its size (the group's count exchange,
     // reg_dist_prepare), unknown (NaN) otherwise -- never over this rank's slice
-    fill_result(h, mir->sums, res, h->n_total_hint > 0 ? (double)h->n_total_hint : (double)NAN);
-    if (mir->status != REG_OK) {
-        h->err = "ErrorMinimizer: no point to minimize";
-        return (reg_status)mir->status;
-    }
-    float T_iter[16], Tout_row[16];
-    std::memcpy(T_iter, mir->T, 64);
-    compose_rowmajor(h, T_iter, Tout_row);
-    row_to_col(T_iter, res->T_iter_last);
-    row_to_col(h->h_mirror->T_prev, res->T_iter_prev);
-    row_to_col(Tout_row, T_out);
-    return REG_OK;
+    s = write_result(h, h->prm.use_xicp != 0, /*xicp_sums=*/true, h->n_total_hint > 0 ? (double)h->n_total_hint : (double)NAN, /*mirror_seen=*/false,
+                     T_out, res);
+    if (s != REG_OK) h->err = "ErrorMinimizer: no point to minimize";
+    return s;
 }
 
 // ---- measurement hook -------------------------------------------------------------------------------
@@ -568,10 +490,7 @@ reg_status reg_profile_kernels(reg_handle* h, const float T_iter[16], int reps, 
         s = enqueue_match(h);
         if (s != REG_OK) return s;
         HIPCHK(h, hipEventRecord(e[1], h->stream));
-        if (trim) {
-            s = enqueue_select(h);
-            if (s != REG_OK) return s;
-        }
+        if (trim) enqueue_select(h);
         HIPCHK(h, hipEventRecord(e[2], h->stream));
         s = enqueue_linearize(h, false);
         if (s != REG_OK) return s;

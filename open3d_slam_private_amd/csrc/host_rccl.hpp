@@ -238,6 +238,11 @@ static reg_status dist_all_gather(reg_handle* h, const void* send, void* recv, i
     return REG_OK;
 }
 
+// The reply the steering reads from a status that holds a report
+static reg_dist_reply dist_reply_from(const reg_dist_status& st) {
+    return {/*available=*/1, st.iterations, st.done, st.stall, st.limit_last, st.limit_prev};
+}
+
 // Blocks until sequence `seq_rel` has reported (reply.available = 1) or can no longer report because the stream drained
 // without it (available = 0).
 static reg_status dist_wait_record(reg_handle* h, int64_t seq_rel, reg_dist_reply* out) {
@@ -250,18 +255,12 @@ static reg_status dist_wait_record(reg_handle* h, int64_t seq_rel, reg_dist_repl
             s = reg_dist_record(h, seq_rel, &st);   // the report may have landed between the two reads
             if (s != REG_OK) return s;
             if (st.sequences_done != seq_rel) {
-                std::memset(out, 0, sizeof(*out));
-                out->limit_last = out->limit_prev = INFINITY;
+                *out = {/*available=*/0, 0, 0, 0, INFINITY, INFINITY};
                 return REG_OK;
             }
         }
         if (st.sequences_done == seq_rel) {
-            out->available = 1;
-            out->iterations = st.iterations;
-            out->done = st.done;
-            out->stall = st.stall;
-            out->limit_last = st.limit_last;
-            out->limit_prev = st.limit_prev;
+            *out = dist_reply_from(st);
             return REG_OK;
         }
         if ((spins & 0xff) == 0xff && dl.expired())
@@ -282,12 +281,7 @@ static reg_status dist_drain(reg_handle* h, reg_dist_reply* out) {
     }
     reg_status s = reg_dist_poll(h, &st);
     if (s != REG_OK) return s;
-    out->available = 1;
-    out->iterations = st.iterations;
-    out->done = st.done;
-    out->stall = st.stall;
-    out->limit_last = st.limit_last;
-    out->limit_prev = st.limit_prev;
+    *out = dist_reply_from(st);
     return REG_OK;
 }
 

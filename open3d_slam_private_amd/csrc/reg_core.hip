@@ -54,7 +54,9 @@ using namespace o3dreg;
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
+#include "host_launch.hpp"
 #include "host_loop.hpp"
+#include "host_pm.hpp"
 #include "host_dist.hpp"
 #include "host_rccl.hpp"
 #include "host_filters.hpp"

@@ -119,7 +119,7 @@ def row_name(row):
 
 
 def is_plain_loop(row):
-    """The row switches nothing of reg_pm_chain on (pm_chain_is_default, host_loop.hpp): the handle runs the plain loop."""
+    """The row switches nothing of reg_pm_chain on (pm_chain_is_default, host_pm.hpp): the handle runs the plain loop."""
     return (row["knn"] == 1 and row["minimizer"] == "point2plane" and row.get("robust", "off") == "off" and
             row.get("min_dist") is None and row.get("median") is None and row.get("var") is None)
 
