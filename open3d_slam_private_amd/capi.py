@@ -1585,3 +1585,29 @@ def host_tail_plan(n, cus=256, tile=0):
     out = (C.c_int32 * 4)()
     lib.reg_host_tail_plan(int(n), int(cus), int(tile), out)
     return bool(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
+def host_predict_band(limit, prev=math.inf, prev2=math.inf, last_count=0, last_lo=math.inf, last_hi=math.inf, debug_narrow=0):
+    """The band [lo, hi) every loop path predicts for the next trimmed limit from the last three limits (newest first; inf:
+    none) and the population / edges of the last band (0 / inf: unknown) -- host-only (reg_host_predict_band).  float32."""
+    lib = load_library()
+    lib.reg_host_predict_band.argtypes = [C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_float, C.c_float, C.c_int32,
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.reg_host_predict_band.restype = None
+    out = (C.c_float * 2)()
+    lib.reg_host_predict_band(float(limit), float(prev), float(prev2), int(last_count), float(last_lo), float(last_hi),
+                              int(debug_narrow), out, None)
+    return np.float32(out[0]), np.float32(out[1])
+
+
+def host_band_constants():
+    """Constants of the band predictor as compiled: dict of kTailBandCap, kTailWideRel, floor, ratio_max, centre_gain,
+    geom_rel, guard_frac, forced_wide."""
+    lib = load_library()
+    lib.reg_host_predict_band.argtypes = [C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_float, C.c_float, C.c_int32,
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.reg_host_predict_band.restype = None
+    c = (C.c_float * 8)()
+    lib.reg_host_predict_band(math.inf, math.inf, math.inf, 0, math.inf, math.inf, 0, None, c)
+    names = ("band_cap", "wide_rel", "floor", "ratio_max", "centre_gain", "geom_rel", "guard_frac", "forced_wide")
+    return {k: float(np.float32(v)) for k, v in zip(names, c)}

@@ -143,7 +143,7 @@ static reg_status build_iter_state(reg_handle* h, const float* T_row, int update
     st->gicp_rel_rmse = h->prm.gicp_rel_rmse;
     st->n_total = (float)(h->n_total_hint > 0 ? h->n_total_hint : h->n);
     st->band_lo = st->band_hi = INFINITY;
-    st->limit_last = st->limit_prev = INFINITY;
+    st->limit_last = st->limit_prev = st->limit_prev2 = INFINITY;
     st->use_trim = (h->prm.cost == REG_COST_P2PL && h->prm.use_trimmed) ? 1 : 0;
     st->trim_ratio = h->prm.trim_ratio;
     st->band_cap = kBandCap;
@@ -777,6 +777,24 @@ void reg_host_tail_plan(int64_t n, int32_t cus, int32_t tile, int32_t plan[4]) {
     plan[1] = pl.grid;
     plan[2] = pl.wpc;
     plan[3] = pl.chunk8;
+}
+
+// The band predictor of every loop path (reg_state.hpp: predict_band) on the host, for the CPU tests and the band model:
+// band[0..1] = [lo, hi) predicted for the next trimmed limit from the last three (newest first; +inf: none) and from the
+// population / edges of the last band (0 / +inf: unknown).  consts[0..7] (may be null): kTailBandCap, kTailWideRel and the
+// predictor's constants in the order they are declared.
+REG_API void reg_host_predict_band(float limit, float prev, float prev2, uint32_t last_count, float last_lo, float last_hi,
+                                   int32_t debug_narrow, float band[2], float consts[8]) {
+    const Band b = predict_band(limit, prev, prev2, last_count, last_lo, last_hi, debug_narrow);
+    if (band) {
+        band[0] = b.lo;
+        band[1] = b.hi;
+    }
+    if (consts) {
+        const float c[8] = {(float)kTailBandCap, kTailWideRel, kBandFloor, kBandRatioMax, kBandCentreGain, kBandGeomRel, kBandGuardFrac,
+                            kBandForcedWide};
+        for (int i = 0; i < 8; ++i) consts[i] = c[i];
+    }
 }
 
 reg_status reg_prepare(reg_handle* h, const float T_init[16]) {

@@ -54,11 +54,10 @@ constexpr int kTailThreads = O3D_TAIL_THREADS;   // 8 waves = 2 per SIMD: 256 VG
 constexpr int kTailSlots = O3D_TAIL_SLOTS;   // reading-point slots per workgroup: thread t owns slots t and t + 512
 constexpr int kTailWgsPerCu = O3D_TAIL_WGS_PER_CU;   // co-resident workgroups per CU the plan may use (launch bounds follow)
 constexpr int kTailPts = kTailSlots / kTailThreads;
-constexpr int kTailBandCap = 1024;     // band records one iteration may hold in all (more: stall, select-based repair)
+// (kTailBandCap, kTailWideRel: reg_state.hpp, next to the band predictor that needs them)
 constexpr int kTailRec = 12;           // floats per band record: F0..F5, r, d2, kept, 0, kept d2, 0  (= a factor row)
 constexpr int kTailHistRow = 32;       // doubles per workgroup in the coarse-histogram rows (wide bands): 256 one-byte counts
 constexpr int kTailCoarse = 256;       // coarse bins of a wide band (second exchange of the iteration: see k_tail)
-constexpr float kTailWideRel = 0.02f;  // a band wider than this fraction of its lower edge takes the two-exchange form
 constexpr int kTailMaxIters = 64;      // iterations per launch
 constexpr int kTailSyncWords = 256;    // zero when a launch starts: arrival counters, record counters, error word, statistics
 constexpr int kTailRing = 4;           // epochs an accumulator set / record counter lives before it is reused
@@ -159,7 +158,7 @@ __device__ __forceinline__ unsigned tail_ld_u32(const unsigned* p) {
 // augmented 6x7 system, one entry per lane, fp64 (as in k_reduce_update), then x -> dT, T_iter <- dT * T_iter, the next
 // band and the checkers on lane 0.  Out of line: its register needs must not add to the search loop's.
 __device__ __noinline__ void tail_solve_update(IterState* sit, const double* tot, const uint32_t* misc, float* s_x, bool trim,
-                                               unsigned n_band_raw) {
+                                               unsigned n_band_raw, unsigned n_band_all) {
     const int lane = (int)(threadIdx.x & 63);
     const float r_limit_last = sit->limit_last, r_limit_sel = __uint_as_float(misc[2]);
     const int r_dbg_narrow = sit->debug_narrow_band & 1;
@@ -200,18 +199,16 @@ __device__ __noinline__ void tail_solve_update(IterState* sit, const double* tot
     for (int i = 0; i < 6; ++i) xsol[i] = __shfl(a, i * 8 + 6);
     if (lane != 0) return;
     const float limit = r_limit_sel;
+    const float r_limit_prev = sit->limit_prev;
+    sit->limit_prev2 = r_limit_prev;
     sit->limit_prev = r_limit_last;
     sit->limit_last = limit;
-    if (!trim || !(limit < INFINITY)) {
-        sit->band_lo = INFINITY;
-        sit->band_hi = INFINITY;
-    } else {
-        const float prev = r_limit_last;
-        float m = 0.3f;
-        if (prev < INFINITY && prev > 0.f) m = fminf(fmaxf(2.0f * fabsf(limit - prev) / limit + 0.003f, 0.003f), 0.6f);
-        if (r_dbg_narrow) m = 1e-7f;   // test hook: forces band mispredictions (stall + repair path)
-        sit->band_lo = limit * (1.0f - m);
-        sit->band_hi = limit * (1.0f + m);
+    {
+        // the band this iteration ran with and every point it held (a wide band: before it shrank to one coarse bin)
+        const Band nb = trim ? predict_band(limit, r_limit_last, r_limit_prev, n_band_all, sit->band_lo, sit->band_hi, r_dbg_narrow)
+                             : Band{INFINITY, INFINITY};
+        sit->band_lo = nb.lo;
+        sit->band_hi = nb.hi;
     }
     sit->band_count = n_band_raw;   // reported with the mirror (pad_nband)
     sit->stall = 0;
@@ -367,6 +364,7 @@ __device__ __noinline__ void tail_solve_update_gicp(IterState* sit, const double
     for (int i = 0; i < 6; ++i) xsol[i] = __shfl(a, i * 8 + 6);
     if (lane != 0) return;
     const double cnt = tot[28];
+    sit->limit_prev2 = sit->limit_prev;
     sit->limit_prev = sit->limit_last;
     sit->limit_last = INFINITY;
     sit->band_lo = INFINITY;
@@ -737,30 +735,14 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
                     const Best bb = nearest_group<G, O3D_COH_PRUNE != 0, true>(g, p2, sub, -1, &lvl, seg_lds + grp * kSegWords<G>,
                                                                                hv >= 2 ? hv - 2 : -1, &cov2, cfg.slack);
                     if (sub == 0) {
+                        // only what the search itself produced: anchor + bound, the winner's and the runner-up's positions (in the
+                        // .w of rows the gather pass below rewrites), d2, the hint.  The gathers that depend on the result -- the
+                        // matched point / normal (covariance) pair, the runner-up's coordinates -- used to sit here: one dependent
+                        // round trip per ROUND on one lane of every group, before the group could start its next search.
                         hnt[slot] = (uint8_t)(lvl + 1);
-                        const int pc = bb.pos >= 0 ? bb.pos : 0;
-                        float4 tq, nn;
-                        if (kGicp) {
-                            tq = g.pts[pc];
-                            nn = tgt_nrm[2 * (size_t)pc];                 // covariance xx xy xz yy
-                            float4 c1 = tgt_nrm[2 * (size_t)pc + 1];     // yz zz
-                            c1.w = 1.f;
-                            st_rows[4 * kTailSlots + slot] = c1;
-                        } else {
-                            tq = tgt_nrm[2 * (size_t)pc];       // {point, normal} pair: one line
-                            nn = tgt_nrm[2 * (size_t)pc + 1];
-                            nn.w = 1.f;
-                        }
-                        float4 ru = make_float4(INFINITY, INFINITY, INFINITY, 1.f);   // no runner-up seen: infinitely far
-                        if (bb.pos2 >= 0) {
-                            const float4 t2 = g.pts[bb.pos2];
-                            ru = make_float4(t2.x, t2.y, t2.z, 1.f);
-                        }
-                        tq.w = __int_as_float(bb.pos);
                         st_rows[slot] = make_float4(p2.x, p2.y, p2.z, bb.pos >= 0 ? fminf(bb.third, cov2) : -1.f);
-                        st_rows[kTailSlots + slot] = tq;
-                        st_rows[2 * kTailSlots + slot] = nn;
-                        st_rows[3 * kTailSlots + slot] = ru;
+                        st_rows[kTailSlots + slot].w = __int_as_float(bb.pos);
+                        st_rows[3 * kTailSlots + slot].w = __int_as_float(bb.pos2);
                         d2s[slot] = bb.pos >= 0 ? bb.d2 : INFINITY;
                     }
                 }
@@ -772,6 +754,31 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
         else
 #endif
             search_rounds(std::integral_constant<int, 8>());
+        __syncthreads();   // every round's positions are in LDS
+        // ---- ONE gather pass for all failures of the iteration: thread i takes failure i; the loads of a failure are independent of
+        //      each other and of every other failure's, all are issued before any is used -- one dependent round trip per iteration
+#pragma unroll 1
+        for (int fi = tv; fi < nf; fi += kTailThreads) {
+            const int slot = (int)fail[fi];
+            const int pos = __float_as_int(st_rows[kTailSlots + slot].w), pos2 = __float_as_int(st_rows[3 * kTailSlots + slot].w);
+            const size_t pc = (size_t)(pos >= 0 ? pos : 0), pc2 = (size_t)(pos2 >= 0 ? pos2 : 0);
+            // (every load of the failure is issued before the first is used)
+            const float4 t2 = g.pts[pc2];
+            float4 tq = kGicp ? g.pts[pc] : tgt_nrm[2 * pc];   // P2PL: {point, normal} pair, one line
+            float4 nn = kGicp ? tgt_nrm[2 * pc] : tgt_nrm[2 * pc + 1];   // GICP: covariance xx xy xz yy
+            if (kGicp) {
+                float4 c1 = tgt_nrm[2 * pc + 1];   // yz zz
+                c1.w = 1.f;
+                st_rows[4 * kTailSlots + slot] = c1;
+            } else {
+                nn.w = 1.f;
+            }
+            tq.w = __int_as_float(pos);
+            st_rows[kTailSlots + slot] = tq;
+            st_rows[2 * kTailSlots + slot] = nn;
+            st_rows[3 * kTailSlots + slot] = pos2 >= 0 ? make_float4(t2.x, t2.y, t2.z, 1.f)
+                                                       : make_float4(INFINITY, INFINITY, INFINITY, 1.f);   // no runner-up seen: infinitely far
+        }
         __syncthreads();   // search results visible to the owners
         TAIL_STAMP(1);   // own searches
         // ---- weights, class, factor row of this thread's points (coh_epilogue without the global writes), accumulated in
@@ -1122,7 +1129,7 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
             if (kGicp)
                 tail_solve_update_gicp(sit, tot, reinterpret_cast<double*>(s_x));
             else
-                tail_solve_update(sit, tot, misc, s_x, trim, n_band_raw);
+                tail_solve_update(sit, tot, misc, s_x, trim, n_band_raw, wide ? misc[12] : n_band_raw);
         }
         __syncthreads();
         TAIL_STAMP(11);   // solve, pose update, checkers

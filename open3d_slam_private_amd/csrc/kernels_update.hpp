@@ -520,21 +520,15 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
         // band for the next iteration from the limits seen so far
         const float limit = finish ? r_limit_last : r_limit_sel;
         if (!finish) {
+            const float r_limit_prev = sit->limit_prev;
+            sit->limit_prev2 = r_limit_prev;
             sit->limit_prev = r_limit_last;
             sit->limit_last = limit;
-        }
-        if (finish) {
-            // keep the band computed when the sums were reduced
-        } else if (!trim || !(limit < INFINITY)) {
-            sit->band_lo = INFINITY;   // no trimming / nothing to predict from: every finite match is "certainly kept"
-            sit->band_hi = INFINITY;
-        } else {
-            const float prev = r_limit_last;   // == the new limit_prev
-            float m = 0.3f;
-            if (prev < INFINITY && prev > 0.f) m = fminf(fmaxf(2.0f * fabsf(limit - prev) / limit + 0.003f, 0.003f), 0.6f);
-            if (r_dbg_narrow) m = 1e-7f;   // test hook: forces band mispredictions (stall + repair path)
-            sit->band_lo = limit * (1.0f - m);
-            sit->band_hi = limit * (1.0f + m);
+            // (finish: the band computed when the sums were reduced stays.  n_band: every rank's records -- the same on all ranks)
+            const Band nb = trim ? predict_band(limit, r_limit_last, r_limit_prev, n_band, sit->band_lo, sit->band_hi, r_dbg_narrow)
+                                 : Band{INFINITY, INFINITY};
+            sit->band_lo = nb.lo;
+            sit->band_hi = nb.hi;
         }
         const int nband_report = (int)r_band_count;
         sit->band_count = 0;

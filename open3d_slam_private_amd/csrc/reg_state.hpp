@@ -44,6 +44,7 @@ struct IterState {
     unsigned int* qcount;
     unsigned int band_cap;
     int debug_narrow_band;    // test hooks: bit 0 forces band mispredictions, bit 1 disables the direct band ranking
+    float limit_prev2;        // the trimmed limit before limit_prev (+inf: none): the band predictor extrapolates from three
     // R8x (X-ICP localizability, OptimizedEqualityConstraints)
     int xicp_stage;           // 0: off / analysed, 1: analysis pending (first iteration), 2: sums being collected
     int xicp_nc;              // number of non-localizable directions (constraints)
@@ -84,6 +85,59 @@ struct HostMirror {
     } ring[16];
 };
 constexpr int kSeqRing = 16;
+
+// ---- the band predicted for the next iteration's trimmed limit (every loop path: k_reduce_update and k_tail call this)
+constexpr int kTailBandCap = 1024;       // band records one tail iteration may hold in all (more: stall, select-based repair)
+constexpr float kTailWideRel = 0.02f;    // a band wider than this fraction of its lower edge takes the tail's two-exchange form
+constexpr float kBandFloor = 0.003f;     // margin (fraction of the limit) beyond every edge: the limit's jitter once it has settled
+constexpr float kBandRatioMax = 0.6f;    // a settling limit's successive changes shrink by 0.15 - 0.55: the reach covers 0.6,
+constexpr float kBandCentreGain = 1.5f;  // ... or 1.5 x the last observed ratio where that is larger
+constexpr float kBandGeomRel = 0.25f;    // the ratio of two changes means something only once both are small against the limit
+constexpr float kBandGuardFrac = 0.75f;  // a narrow band whose estimated population exceeds this share of kTailBandCap is widened
+constexpr float kBandForcedWide = 0.0205f;   // ... to this fraction of the limit: past kTailWideRel, the two-exchange form on purpose
+struct Band {
+    float lo, hi;
+};
+// limit / prev / prev2: the last three trimmed limits, newest first (+inf: none).  last_count points lay in the band
+// [last_lo, last_hi) of the iteration that produced `limit` (0 / +inf: unknown).
+//   * Fewer than three limits, changes of different sign, a change that did not shrink, or a change before it that was not small
+//     against the limit (the collapse after a far prior's plateau says nothing about the ratio of the settled regime): the
+//     symmetric band around the last limit, m = clamp(2 |L - P| / L + 0.003, 0.003, 0.6).
+//   * Otherwise the limit converges geometrically and keeps its direction: the band reaches from the last limit (ratio 0) to
+//     L + max(1.5 q, 0.6) (L - P), q = (L - P) / (P - PP) the last observed ratio, plus the floor margin on both sides.
+//   * Count guard: the population scales with the width (the density of d^2 around the limit changes by ~1 % per iteration); a
+//     narrow band expected to hold more than kBandGuardFrac * kTailBandCap points would overflow the record list and stall.
+__host__ __device__ inline Band predict_band(float limit, float prev, float prev2, unsigned last_count, float last_lo, float last_hi,
+                                             int debug_narrow) {
+    Band b = {INFINITY, INFINITY};
+    if (!(limit < INFINITY)) return b;   // nothing to predict from: every finite match is "certainly kept"
+    float m = 0.3f;
+    if (prev < INFINITY && prev > 0.f) m = fminf(fmaxf(2.0f * fabsf(limit - prev) / limit + kBandFloor, kBandFloor), 0.6f);
+    if (debug_narrow) m = 1e-7f;   // test hook: forces band mispredictions (stall + repair path)
+    b.lo = limit * (1.0f - m);
+    b.hi = limit * (1.0f + m);
+    if (debug_narrow) return b;
+    if (prev < INFINITY && prev > 0.f && prev2 < INFINITY && prev2 > 0.f) {
+        const float d = limit - prev, dp = prev - prev2;
+        if (d * dp > 0.f && fabsf(d) < fabsf(dp) && fabsf(dp) <= kBandGeomRel * limit) {
+            const float q = d / dp;
+            const float far_edge = limit + fmaxf(kBandCentreGain * q, kBandRatioMax) * d, pad = kBandFloor * limit;
+            b.lo = d < 0.f ? far_edge - pad : limit - pad;
+            b.hi = d < 0.f ? limit + pad : far_edge + pad;
+        }
+    }
+    if (last_count > 0u && last_hi < INFINITY && last_hi > last_lo) {
+        const float est = (float)last_count * (b.hi - b.lo) / (last_hi - last_lo);
+        if (est > kBandGuardFrac * (float)kTailBandCap && !(b.hi - b.lo > kTailWideRel * b.lo)) {
+            const float grow = 0.5f * (kBandForcedWide * limit - (b.hi - b.lo));
+            if (grow > 0.f) {
+                b.lo -= grow;
+                b.hi += grow;
+            }
+        }
+    }
+    return b;
+}
 constexpr int kQueues = 64;        // sub-queues of the coherent iteration's search queue (workgroup lb appends to lb % kQueues)
 constexpr int kQueueStride = 16;   // counters are 16 words (64 bytes) apart
 
