@@ -310,6 +310,58 @@ inline OverlapIndices overlapIndices(const double* source, int64_t n, const doub
     return out;
 }
 
+// The front of place recognition on the device (contract in o3dslam_reg.h; PARITY UNPINNED against Open3D
+// 0.15.1).  Both run on a handle of their own, which only lends its stream and workspace.
+template <class F>
+inline void withFeatureHandle(int device, F&& call) {
+    reg_params p;
+    reg_default_params(&p);
+    p.cost = REG_COST_O3D_P2P;
+    p.device = device;
+    reg_handle* h = nullptr;
+    reg_status s = reg_create(&p, &h);
+    if (s == REG_OK) s = call(h);
+    const std::string msg = s == REG_OK ? "" : (h ? reg_last_error(h) : "reg_create rejected the parameters");
+    if (h) reg_destroy(h);
+    if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+    if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+    if (s != REG_OK) throw std::runtime_error(msg);
+}
+
+// ComputeFPFHFeature(cloud, KDTreeSearchParamHybrid(radius, maxNn)) (Submap.cpp:267-269): points / normals n x 3 floats in
+// host memory; returns n x 33 doubles, row i = column i of Open3D's Feature::data_.
+inline std::vector<double> computeFPFH(const float* points, const float* normals, int64_t n, float radius, int maxNn = 100,
+                                       int device = 0) {
+    std::vector<double> fpfh((size_t)(n > 0 ? n : 0) * 33);
+    withFeatureHandle(device, [&](reg_handle* h) {
+        return reg_compute_fpfh(h, points, 3, normals, 3, n, 0, maxNn, radius, fpfh.data(), nullptr, nullptr, nullptr);
+    });
+    return fpfh;
+}
+
+// The correspondence set RegistrationRANSACBasedOnFeatureMatching(..., mutual_filter, ...) forms before it samples
+// (PlaceRecognition.cpp:81-84): rows of `source` (na x dim) and `target` (nb x dim) doubles in host memory; interleaved
+// (source, target) index pairs -- the mutual nearest neighbours when there are at least ransacN of them, else every
+// (a, nearest b), as Open3D falls back.
+inline std::vector<int32_t> matchFeatures(const double* source, int64_t na, const double* target, int64_t nb, int dim = 33,
+                                          bool mutualFilter = true, int ransacN = 3, int device = 0) {
+    std::vector<int32_t> nn((size_t)(na > 0 ? na : 0)), mutual(mutualFilter ? 2 * nn.size() : 0);
+    int64_t k = 0;
+    withFeatureHandle(device, [&](reg_handle* h) {
+        return reg_match_features(h, source, na, target, nb, dim, 0, nn.data(), nullptr, mutualFilter ? mutual.data() : nullptr, &k);
+    });
+    if (mutualFilter && k >= ransacN) {
+        mutual.resize((size_t)(2 * k));
+        return mutual;
+    }
+    std::vector<int32_t> all(2 * nn.size());
+    for (size_t a = 0; a < nn.size(); ++a) {
+        all[2 * a] = (int32_t)a;
+        all[2 * a + 1] = nn[a];
+    }
+    return all;
+}
+
 // SurfaceNormalDataPointsFilter (DataPointsFilters/SurfaceNormal.cpp:152-252) on the device: exact k-NN (the point
 // itself included) + PCA.  Outputs are written to caller-owned arrays laid out like the `normals` (3 x N),
 // `eigValues` (3 x N, ascending == sortEigen) and `matchedIds` (knn x N) descriptors.

@@ -819,6 +819,56 @@ REG_API reg_status reg_set_pair_overlap_f64(reg_handle* h, const double* src_xyz
                                             int64_t* n_tgt_kept);
 REG_API reg_status reg_get_source_source_indices(reg_handle* h, int32_t* idx);
 
+/* ---- FPFH features and mutual feature matching: the front of place recognition ---------------------
+   open3d_slam/src/Submap.cpp:255-275 (Submap::computeFeatures: ComputeFPFHFeature(sparseMapCloud_,
+   KDTreeSearchParamHybrid(featureRadius_, featureKnn_))) and the first step of
+   RegistrationRANSACBasedOnFeatureMatching(..., mutual_filter = true, ...) (PlaceRecognition.cpp:71-85).  Open3D 0.15.1
+   is not in the reference tree: PARITY UNPINNED; the contract below is this project's own.
+
+   reg_compute_fpfh.  xyz / normals: n points, strides in floats (>= 3); host pointers, or device pointers with
+   on_device != 0 (which covers fpfh, spfh and n_neighbours too).  2 <= max_nn <= 128, radius finite and > 0,
+   n <= 2^31 - 1 (else REG_BAD_ARGUMENT); n <= 0 is REG_EMPTY_SOURCE; a non-finite coordinate or normal component is
+   REG_BAD_ARGUMENT.  Outputs are fp64 (Feature::data_ is a double matrix; row i here is its column i): fpfh n x 33,
+   spfh n x 33 (may be NULL), n_neighbours n (m_i below, may be NULL); n_rescanned (may be NULL): points whose candidate
+   list exceeded the on-chip list (statistics; results are exact).
+
+   Numeric contract: one rounding per operation (the build forbids contraction).
+     neighbourhood of point i: the up to max_nn nearest points within radius, point i included in the count (FLANN's
+       hybrid search), formed on the fp32 coordinates with d2 = (dx*dx + dy*dy) + dz*dz, the test d2 <= fl(radius*radius)
+       and ascending (d2, index) order -- the order reg_estimate_normals reports.  Point i is then dropped BY INDEX
+       (deviation: Open3D drops whatever comes first, with duplicated points possibly the twin); m_i neighbours remain.
+     pair feature of (i, j), fp64 on the promoted fp32 values; a.b = (a.x*b.x + a.y*b.y) + a.z*b.z,
+       (a x b).x = a.y*b.z - a.z*b.y etc.:
+         d = p_j - p_i, L = sqrt(d.d); L == 0: (f0, f1, f2) = (0, 0, 0)
+         a1 = (n_i.d)/L, a2 = (n_j.d)/L
+         |a1| < |a2|: n1 = n_j, n2 = n_i, d = -d, f2 = -a2; otherwise (a tie included) n1 = n_i, n2 = n_j, f2 = a1
+           (deviation: Open3D tests acos(|a1|) > acos(|a2|), which agrees except within acos' own rounding)
+         v = d x n1, vn = sqrt(v.v); vn == 0: (0, 0, 0); v = v/vn
+         w = n1 x v, f1 = v.n2, f0 = atan2(w.n2, n1.n2)
+       Normals are used as given (FPFH does not normalise them).
+     bins: floor((11*(f0 + pi))/(2*pi)), floor((11*(f1 + 1))*0.5), floor((11*(f2 + 1))*0.5), each clamped to [0, 10],
+       counted in rows 0-10, 11-21, 22-32.
+     spfh[i][b] = count_i[b] * (100.0 / m_i) (integer counts, one multiplication); all zero when m_i == 0.
+     fpfh: acc[b] = sum over the neighbours j in ascending (d2, index) order of spfh[j][b] / d2_ij, d2_ij the fp64 d.d
+       above (the SQUARED distance, Open3D's own weight), neighbours with d2_ij == 0 skipped; s_t = the eleven acc of
+       sub-histogram t added in bin order; scale_t = 100.0 / s_t (0 when s_t == 0);
+       fpfh[i][b] = acc[b] * scale_t + spfh[i][b]. */
+REG_API reg_status reg_compute_fpfh(reg_handle* h, const float* xyz, int64_t xyz_stride, const float* normals,
+                                    int64_t nrm_stride, int64_t n, int on_device, int max_nn, float radius,
+                                    double* fpfh /* n x 33 */, double* spfh /* n x 33, may be NULL */,
+                                    int32_t* n_neighbours /* n, may be NULL */, int64_t* n_rescanned /* may be NULL */);
+
+/* reg_match_features: nearest neighbours between two sets of feature rows (na x dim, nb x dim doubles, 1 <= dim <= 64;
+   on_device covers fa, fb, nn_ab, nn_ba and mutual).  D(a, b) = sum_j (fa[a][j] - fb[b][j])^2 in fp64, j ascending, one
+   rounding per operation.  nn_ab[a] is the b of the smallest D, ties to the lowest b; nn_ba alike (may be NULL).
+   mutual (may be NULL; interleaved (a, b) pairs, capacity na pairs): the pairs (a, nn_ab[a]) with nn_ba[nn_ab[a]] == a,
+   ascending in a -- corres_mutual of Open3D's feature-matching front, the input of
+   RegistrationRANSACBasedOnCorrespondence; *n_mutual their number (required with mutual).  With nn_ba and mutual both
+   NULL only the forward search runs.  na <= 0: REG_EMPTY_SOURCE, nb <= 0: REG_EMPTY_TARGET. */
+REG_API reg_status reg_match_features(reg_handle* h, const double* fa, int64_t na, const double* fb, int64_t nb, int dim,
+                                      int on_device, int32_t* nn_ab /* na */, int32_t* nn_ba /* nb, may be NULL */,
+                                      int32_t* mutual /* 2 x capacity na: (a, b) pairs */, int64_t* n_mutual);
+
 /* Introspection of the search structure (tests, DESIGN.md numbers). */
 typedef struct {
     int64_t n_points;

@@ -335,7 +335,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_ssn_params", "reg_sampling_surface_normal", "reg_filter_points",
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks",
            "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid",
-           "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices"]
+           "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices",
+           "reg_compute_fpfh", "reg_match_features"]
 
 
 def lib_path() -> str:
@@ -417,6 +418,8 @@ def load_library():
     lib.reg_set_pair_overlap_f64.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, i64, C.c_int, C.POINTER(C.c_double), C.c_double,
                                              C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.reg_get_source_source_indices.argtypes = [vp, vp]
+    lib.reg_compute_fpfh.argtypes = [vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.POINTER(C.c_int64)]
+    lib.reg_match_features.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int64)]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -984,6 +987,62 @@ class Registration:
         idx = np.empty(max(getattr(self, "n_source_kept", 0), 1), np.int32)
         self._check(self._lib.reg_get_source_source_indices(self._h, _ptr(idx)))
         return idx[:self.n_source_kept]
+
+    # ---- FPFH features and mutual feature matching ----
+    def compute_fpfh(self, xyz, normals, radius, max_nn=100, want_spfh=False, want_counts=False):
+        """ComputeFPFHFeature with a hybrid search (Submap.cpp:255-275) on the device.  Returns a dict: `fpfh` (n, 33)
+        float64 (row i = column i of Open3D's Feature::data_), on request `spfh` (n, 33) and `n_neighbours` (n,), plus
+        `n_rescanned`."""
+        xyz, nrm = _f32(xyz), _f32(normals)
+        n = xyz.shape[0] if xyz.ndim == 2 else 0
+        out = {"fpfh": np.zeros((n, 33), np.float64)}
+        if want_spfh:
+            out["spfh"] = np.zeros((n, 33), np.float64)
+        if want_counts:
+            out["n_neighbours"] = np.zeros(n, np.int32)
+        resc = C.c_int64(0)
+        self._check(self._lib.reg_compute_fpfh(self._h, _ptr(xyz), xyz.shape[1] if xyz.ndim == 2 else 3, _ptr(nrm),
+                                               nrm.shape[1] if nrm.ndim == 2 else 3, n, 0, int(max_nn), float(radius),
+                                               _ptr(out["fpfh"]), _ptr(out.get("spfh")), _ptr(out.get("n_neighbours")),
+                                               C.byref(resc)))
+        out["n_rescanned"] = int(resc.value)
+        return out
+
+    def compute_fpfh_device(self, xyz_ptr, xyz_stride, nrm_ptr, nrm_stride, n, radius, max_nn, fpfh_ptr, spfh_ptr=None,
+                            n_neighbours_ptr=None):
+        """As compute_fpfh with the fp32 cloud and normals and the outputs (fpfh / spfh n x 33 doubles, n_neighbours n
+        int32) resident in HBM.  Returns n_rescanned."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        resc = C.c_int64(0)
+        self._check(self._lib.reg_compute_fpfh(self._h, vp(xyz_ptr), xyz_stride, vp(nrm_ptr), nrm_stride, n, 1, int(max_nn),
+                                               float(radius), vp(fpfh_ptr), vp(spfh_ptr), vp(n_neighbours_ptr),
+                                               C.byref(resc)))
+        return int(resc.value)
+
+    def match_features(self, fa, fb, backward=True, mutual=True):
+        """Nearest neighbours between two sets of feature rows (na x dim, nb x dim float64).  Returns (nn_ab, nn_ba,
+        mutual): nn_ba is None without `backward` and `mutual`, mutual (k, 2) int32 pairs (a, b) or None."""
+        a, b = np.ascontiguousarray(fa, np.float64), np.ascontiguousarray(fb, np.float64)
+        na, nb = (a.shape[0], b.shape[0]) if a.ndim == 2 and b.ndim == 2 else (0, 0)
+        dim = a.shape[1] if a.ndim == 2 else 0
+        if b.ndim == 2 and b.shape[1] != dim:
+            dim = 0                                   # the library reports the bad argument
+        nn_ab = np.full(max(na, 1), -1, np.int32)
+        nn_ba = np.full(max(nb, 1), -1, np.int32) if (backward or mutual) else None
+        mu = np.full((max(na, 1), 2), -1, np.int32) if mutual else None
+        km = C.c_int64(0)
+        self._check(self._lib.reg_match_features(self._h, _ptr(a), na, _ptr(b), nb, dim, 0, _ptr(nn_ab), _ptr(nn_ba),
+                                                 _ptr(mu), C.byref(km)))
+        return nn_ab[:na], (nn_ba[:nb] if nn_ba is not None else None), (mu[:int(km.value)].copy() if mutual else None)
+
+    def match_features_device(self, fa_ptr, na, fb_ptr, nb, dim, nn_ab_ptr, nn_ba_ptr=None, mutual_ptr=None):
+        """As match_features with the feature rows and the int32 outputs (nn_ab na, nn_ba nb, mutual 2 x na) resident in
+        HBM.  Returns n_mutual."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        km = C.c_int64(0)
+        self._check(self._lib.reg_match_features(self._h, vp(fa_ptr), na, vp(fb_ptr), nb, int(dim), 1, vp(nn_ab_ptr),
+                                                 vp(nn_ba_ptr), vp(mutual_ptr), C.byref(km)))
+        return int(km.value)
 
     def set_source(self, xyz, normals=None, covs=None):
         xyz = _f32(xyz)

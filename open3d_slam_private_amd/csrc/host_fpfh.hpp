@@ -1,0 +1,154 @@
+// host_fpfh.hpp -- reg_compute_fpfh and reg_match_features: Submap::computeFeatures (Submap.cpp:255-275) and the feature
+// matching front of RegistrationRANSACBasedOnFeatureMatching (PlaceRecognition.cpp:71-85)
+// Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
+#pragma once
+
+// One nearest-neighbour search of the rows of A among the rows of B into nn (device, na words)
+static reg_status mf_search(reg_handle* h, const double* d_a, int64_t na, const double* d_b, int64_t nb, int dim, int32_t* nn) {
+    const int n_chunks = (int)((nb + kMfChunk - 1) / kMfChunk);
+    HIPCHK(h, h->mf_part.reserve((size_t)n_chunks * (size_t)na * 12));
+    double* pd = h->mf_part.as<double>();
+    int32_t* pi = reinterpret_cast<int32_t*>(pd + (size_t)n_chunks * (size_t)na);
+    const dim3 grid((unsigned)grid_for(na), (unsigned)n_chunks);
+    if (dim == kFpfhDim)
+        k_mf_search<kFpfhDim><<<grid, 256, 0, h->stream>>>(d_a, na, d_b, nb, dim, pd, pi);
+    else
+        k_mf_search<kMfMaxDim><<<grid, 256, 0, h->stream>>>(d_a, na, d_b, nb, dim, pd, pi);
+    k_mf_merge<<<grid_for(na), 256, 0, h->stream>>>(pd, pi, na, n_chunks, nn);
+    return REG_OK;
+}
+
+extern "C" {
+
+reg_status reg_compute_fpfh(reg_handle* h, const float* xyz, int64_t xyz_stride, const float* normals, int64_t nrm_stride,
+                            int64_t n, int on_device, int max_nn, float radius, double* fpfh, double* spfh,
+                            int32_t* n_neighbours, int64_t* n_rescanned) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_rescanned) *n_rescanned = 0;
+    if (!xyz || xyz_stride < 3 || !normals || nrm_stride < 3 || !fpfh || max_nn < 2 || max_nn > kFpfhMaxNn ||
+        !(radius > 0.f) || !std::isfinite(radius) || n > 0x7fffffffLL) {
+        h->err = "reg_compute_fpfh: bad argument (2 <= max_nn <= 128, finite radius > 0, xyz, normals and fpfh != NULL)";
+        return REG_BAD_ARGUMENT;
+    }
+    if (n <= 0) {
+        h->err = "The point cloud is empty";
+        return REG_EMPTY_SOURCE;
+    }
+    REGCHK(normals_workspace(h, "reg_compute_fpfh"));
+    reg_handle* w = h->normals_ws;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const float *d_xyz = nullptr, *d_nrm = nullptr;
+    HIPCHK(h, staged_input(h, h->fp_xyz, xyz, (size_t)n * xyz_stride, on_device, &d_xyz));
+    HIPCHK(h, staged_input(h, h->fp_nrm, normals, (size_t)n * nrm_stride, on_device, &d_nrm));
+    HIPCHK(h, h->fp_misc.reserve(64));
+    uint32_t* misc = h->fp_misc.as<uint32_t>();   // [0] non-finite input, [1] rescanned points
+    HIPCHK(h, hipMemsetAsync(misc, 0, 8, h->stream));
+    k_fpfh_check<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, xyz_stride, d_nrm, nrm_stride, n, misc);
+    uint32_t back[2] = {0, 0};
+    HIPCHK(h, hipMemcpyAsync(&back[0], misc, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (back[0]) {
+        h->err = "reg_compute_fpfh: a coordinate or a normal component is not finite";
+        return REG_BAD_ARGUMENT;
+    }
+    w->prm.max_dist = radius;
+    const reg_status st = reg_set_target(w, d_xyz, xyz_stride, nullptr, 3, nullptr, n, 1);
+    if (st != REG_OK) {
+        h->err = w->err;
+        return st;
+    }
+    // first radius level expected to hold max_nn neighbours on a surface-like cloud (exactness does not depend on it)
+    const float per = (float)n / (float)std::max<int64_t>(1, w->info.n_cells_occupied);
+    const float need = w->info.cell_size * std::sqrt(1.3f * (float)max_nn / (3.14159265f * std::max(per, 1e-3f)));
+    int start = 0;
+    while (start < w->grid.n_levels - 1 && w->grid.rho[start] < need) ++start;
+    // workspace: ordered ids | counts, m; host callers get their outputs through fp_out
+    HIPCHK(h, h->fp_ids.reserve((size_t)n * max_nn * 4));
+    HIPCHK(h, h->fp_cnt.reserve((size_t)n * (kFpfhDim + 1) * 4));
+    int32_t* d_ids = h->fp_ids.as<int32_t>();
+    int32_t* d_cnt = h->fp_cnt.as<int32_t>();
+    int32_t* d_m = d_cnt + (size_t)n * kFpfhDim;
+    double *d_f = fpfh, *d_s = spfh;
+    if (!on_device) {
+        HIPCHK(h, h->fp_out.reserve((size_t)n * kFpfhDim * 8 * 2));
+        d_f = h->fp_out.as<double>();
+        if (spfh) d_s = d_f + (size_t)n * kFpfhDim;
+    }
+    const unsigned blocks = (unsigned)((n + kFpfhWaves - 1) / kFpfhWaves);
+    k_fpfh_spfh<<<blocks, 64 * kFpfhWaves, 0, h->stream>>>(w->grid, d_xyz, xyz_stride, d_nrm, nrm_stride, n, max_nn, start,
+                                                         d_ids, d_cnt, d_m, misc + 1);
+    k_fpfh_accum<<<blocks, 64 * kFpfhWaves, 0, h->stream>>>(d_xyz, xyz_stride, n, max_nn, d_ids, d_cnt, d_m, d_f, d_s);
+    HIPCHK(h, hipMemcpyAsync(&back[1], misc + 1, 4, hipMemcpyDeviceToHost, h->stream));
+    if (!on_device) {
+        HIPCHK(h, hipMemcpyAsync(fpfh, d_f, (size_t)n * kFpfhDim * 8, hipMemcpyDeviceToHost, h->stream));
+        if (spfh) HIPCHK(h, hipMemcpyAsync(spfh, d_s, (size_t)n * kFpfhDim * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (n_neighbours)
+        HIPCHK(h, hipMemcpyAsync(n_neighbours, d_m, (size_t)n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                                 h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (n_rescanned) *n_rescanned = back[1];
+    return REG_OK;
+}
+
+reg_status reg_match_features(reg_handle* h, const double* fa, int64_t na, const double* fb, int64_t nb, int dim, int on_device,
+                              int32_t* nn_ab, int32_t* nn_ba, int32_t* mutual, int64_t* n_mutual) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_mutual) *n_mutual = 0;
+    if (dim < 1 || dim > kMfMaxDim || na > 0x7fffffffLL || nb > 0x7fffffffLL || (mutual && !n_mutual)) {
+        h->err = "reg_match_features: bad argument (1 <= dim <= 64, na, nb <= 2^31 - 1, n_mutual != NULL with mutual)";
+        return REG_BAD_ARGUMENT;
+    }
+    if (na <= 0) {
+        h->err = "The source feature set is empty";
+        return REG_EMPTY_SOURCE;
+    }
+    if (nb <= 0) {
+        h->err = "The target feature set is empty";
+        return REG_EMPTY_TARGET;
+    }
+    if (!fa || !fb || !nn_ab) {
+        h->err = "reg_match_features: null array";
+        return REG_BAD_ARGUMENT;
+    }
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const bool backward = nn_ba != nullptr || mutual != nullptr;
+    const double *d_a = nullptr, *d_b = nullptr;
+    HIPCHK(h, staged_input(h, h->mf_a, fa, (size_t)na * dim, on_device, &d_a));
+    HIPCHK(h, staged_input(h, h->mf_b, fb, (size_t)nb * dim, on_device, &d_b));
+    // mf_nn: nn_ab | nn_ba | mutual pairs, for whatever the caller does not hold on the device
+    HIPCHK(h, h->mf_nn.reserve((size_t)(3 * na + nb) * 4));
+    int32_t* d_ab = on_device ? nn_ab : h->mf_nn.as<int32_t>();
+    int32_t* d_ba = (on_device && nn_ba) ? nn_ba : h->mf_nn.as<int32_t>() + na;
+    int32_t* d_mu = on_device ? mutual : h->mf_nn.as<int32_t>() + na + nb;
+    REGCHK(mf_search(h, d_a, na, d_b, nb, dim, d_ab));
+    int64_t km = 0;
+    if (backward) REGCHK(mf_search(h, d_b, nb, d_a, na, dim, d_ba));
+    if (mutual) {
+        HIPCHK(h, h->mf_flags.reserve((size_t)(na + 1) * 8));
+        uint32_t* flags = h->mf_flags.as<uint32_t>();
+        uint32_t* offs = flags + (na + 1);
+        k_mf_flags<<<grid_for(na + 1), 256, 0, h->stream>>>(d_ab, d_ba, na, flags);
+        REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)na + 1));
+        uint32_t total = 0;
+        HIPCHK(h, hipMemcpyAsync(&total, offs + na, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        km = total;
+        if (km > 0) k_mf_collect<<<grid_for(na), 256, 0, h->stream>>>(flags, offs, na, d_ab, d_mu);
+    }
+    if (!on_device) {
+        HIPCHK(h, hipMemcpyAsync(nn_ab, d_ab, (size_t)na * 4, hipMemcpyDeviceToHost, h->stream));
+        if (nn_ba) HIPCHK(h, hipMemcpyAsync(nn_ba, d_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+        if (km > 0) HIPCHK(h, hipMemcpyAsync(mutual, d_mu, (size_t)km * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (n_mutual) *n_mutual = km;
+    return REG_OK;
+}
+
+}  // extern "C"

@@ -117,6 +117,9 @@ struct reg_handle {
     bool structure_only = false;   // workspace handle of reg_estimate_normals: bin table only, no attributes
     reg_handle* normals_ws = nullptr;
     DevBuf n_out, n_eig, n_cov, n_ids, n_extra, n_mom;
+    // reg_compute_fpfh / reg_match_features (host_fpfh.hpp): staged inputs, ordered ids, counts + m, host-pointer outputs, flag
+    // words; staged feature rows, per-chunk partial bests, index outputs, mutual flags + offsets
+    DevBuf fp_xyz, fp_nrm, fp_ids, fp_cnt, fp_out, fp_misc, mf_a, mf_b, mf_part, mf_nn, mf_flags;
     DevBuf i_xicp;                 // XicpState (R8x first-iteration analysis)
     DevBuf c_in_xyz, c_in_nrm, c_in_cov, c_flags, c_offs, c_xyz, c_nrm, c_cov, c_idx;   // reg_set_target_f64
     DevBuf r_in_xyz, r_in_nrm, r_in_cov, r_xyz, r_nrm, r_cov;                            // reg_set_source_f64
@@ -388,6 +391,7 @@ void reg_destroy(reg_handle* h) {
     h->i_xicp.release();
     for (DevBuf* b : {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov, &h->c_flags, &h->c_offs, &h->c_xyz, &h->c_nrm, &h->c_cov, &h->c_idx, &h->v_fout, &h->v_oout, &h->v_oxyz, &h->v_onrm, &h->v_ocov, &h->v_ukeys, &h->v_ustart, &h->d_d2all, &h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov, &h->r_xyz, &h->r_nrm, &h->r_cov}) b->release();
     for (DevBuf* b : {&h->ov_keys[0], &h->ov_keys[1], &h->ov_sorted, &h->ov_ukeys[0], &h->ov_ukeys[1], &h->ov_ucnt[0], &h->ov_ucnt[1], &h->ov_flags[0], &h->ov_flags[1], &h->ov_offs[0], &h->ov_offs[1], &h->ov_misc, &h->ov_sidx, &h->i_info}) b->release();
+    for (DevBuf* b : {&h->fp_xyz, &h->fp_nrm, &h->fp_ids, &h->fp_cnt, &h->fp_out, &h->fp_misc, &h->mf_a, &h->mf_b, &h->mf_part, &h->mf_nn, &h->mf_flags}) b->release();
     h->n_eig.release();
     h->n_cov.release();
     h->n_ids.release();
@@ -1190,6 +1194,28 @@ reg_status reg_smooth_normals(reg_handle* h, float* normals, const int32_t* ids,
     return REG_OK;
 }
 
+// The workspace handle of the neighbourhood entry points (reg_estimate_normals, reg_compute_fpfh): a bin table over the
+// caller's cloud in its own frame, no attributes; created on first use, on the caller's stream, destroyed with it.
+static reg_status normals_workspace(reg_handle* h, const char* who) {
+    if (!h->normals_ws) {
+        reg_params p = h->prm;
+        p.cost = REG_COST_GICP;   // no centring: neighbourhoods are formed in the input frame
+        p.use_xicp = 0;
+        reg_handle* w = nullptr;
+        const reg_status cs = reg_create(&p, &w);
+        if (w) w->dbg.disable_halo = 1;   // the k-NN search uses the brick table only
+        if (cs != REG_OK) {
+            h->err = std::string(who) + ": workspace: " + reg_last_error(w);
+            reg_destroy(w);
+            return cs;
+        }
+        w->structure_only = true;
+        h->normals_ws = w;
+    }
+    (void)reg_set_stream(h->normals_ws, h->stream);
+    return REG_OK;
+}
+
 reg_status reg_estimate_normals(reg_handle* h, const float* xyz, int64_t xyz_stride, int64_t n, int on_device, int k,
                                 float max_dist, const float* viewpoint, int regularise, const reg_normals_out* out,
                                 int64_t* n_rescanned) {
@@ -1206,23 +1232,8 @@ reg_status reg_estimate_normals(reg_handle* h, const float* xyz, int64_t xyz_str
         h->err = "The point cloud is empty";
         return REG_EMPTY_SOURCE;
     }
-    if (!h->normals_ws) {
-        reg_params p = h->prm;
-        p.cost = REG_COST_GICP;   // no centring: neighbourhoods are formed in the input frame
-        p.use_xicp = 0;
-        reg_handle* w = nullptr;
-        const reg_status cs = reg_create(&p, &w);
-        if (w) w->dbg.disable_halo = 1;   // the k-NN search uses the brick table only
-        if (cs != REG_OK) {
-            h->err = std::string("reg_estimate_normals: workspace: ") + reg_last_error(w);
-            reg_destroy(w);
-            return cs;
-        }
-        w->structure_only = true;
-        h->normals_ws = w;
-    }
+    REGCHK(normals_workspace(h, "reg_estimate_normals"));
     reg_handle* w = h->normals_ws;
-    (void)reg_set_stream(w, h->stream);
     w->prm.max_dist = max_dist;
     reg_status st = reg_set_target(w, xyz, xyz_stride, nullptr, 3, nullptr, n, on_device);
     if (st != REG_OK) {

@@ -51,6 +51,7 @@ using namespace o3dreg;
 #include "kernels_filters.hpp"
 #include "kernels_octree.hpp"
 #include "kernels_overlap.hpp"
+#include "kernels_fpfh.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
@@ -63,6 +64,7 @@ using namespace o3dreg;
 #include "host_octree.hpp"
 #include "host_cloud_filters.hpp"
 #include "host_overlap.hpp"
+#include "host_fpfh.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

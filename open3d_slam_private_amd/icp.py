@@ -11,6 +11,10 @@
   computeIndicesOfOverlappingPoints <-> o3d_slam::computeIndicesOfOverlappingPoints (helpers.cpp:320-345)
   buildConstraint              <-> o3d_slam::buildConstraint (constraint_builders.cpp:43-90)
   refineLoopClosure            <-> the refinement of a loop-closure candidate (PlaceRecognition.cpp:97-149)
+  ComputeFPFHFeature           <-> open3d::pipelines::registration::ComputeFPFHFeature with KDTreeSearchParamHybrid
+  CorrespondencesFromFeatures  <-> the feature-matching front of RegistrationRANSACBasedOnFeatureMatching
+                                   (PlaceRecognition.cpp:81-84)
+  computeSubmapFeatures        <-> o3d_slam::Submap::computeFeatures (Submap.cpp:255-275)
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -1451,3 +1455,123 @@ def refineLoopClosure(source: DataPoints, target: DataPoints, T_ransac, registra
     finally:
         reg.close()
     return Constraint(sourceIdx, targetIdx, result.transformation_.copy(), info, True, False), result
+
+
+# ---- FPFH features and feature matching: the front of place recognition (Submap.cpp:255-275, PlaceRecognition.cpp:71-85;
+#      DESIGN.md 5p; PARITY UNPINNED against Open3D 0.15.1) ----------------------------------------------------------------------
+@dataclass
+class Feature:
+    """open3d::pipelines::registration::Feature: `data_` is 33 x n float64, one column per point."""
+    data_: np.ndarray = field(default_factory=lambda: np.zeros((33, 0)))
+
+    def Dimension(self) -> int:
+        return int(self.data_.shape[0])
+
+    def Num(self) -> int:
+        return int(self.data_.shape[1])
+
+
+@dataclass
+class PlaceRecognitionParameters:
+    """The fields of o3d_slam::PlaceRecognitionParameters that Submap::computeFeatures reads (Parameters.hpp:121-126)."""
+    normalEstimationRadius_: float = 1.0
+    featureVoxelSize_: float = 0.5
+    featureRadius_: float = 2.5
+    featureKnn_: int = 100
+    normalKnn_: int = 10
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _check_fpfh_args(radius, max_nn):
+    if not (isinstance(radius, (int, float, np.floating, np.integer)) and math.isfinite(radius) and radius > 0):
+        raise InvalidParameter(f"radius must be finite and > 0, got {radius!r}")
+    if not (_is_int(max_nn) and 2 <= max_nn <= 128):
+        raise InvalidParameter(f"max_nn must be an integer in [2, 128], got {max_nn!r}")
+
+
+def _feature_handle():
+    p = capi.default_params()
+    p.cost = capi.COST_O3D_P2P
+    return capi.Registration(p)
+
+
+def ComputeFPFHFeature(cloud: DataPoints, radius, max_nn=100) -> Feature:
+    """ComputeFPFHFeature(cloud, KDTreeSearchParamHybrid(radius, max_nn)) on the device (reg_compute_fpfh).  The cloud needs
+    the `normals` descriptor."""
+    _check_fpfh_args(radius, max_nn)
+    if cloud.normals is None:
+        raise InvalidField("FPFH needs normals on the cloud")
+    x = np.asarray(cloud.features)
+    if x.ndim != 2 or x.shape[1] not in (3, 4):
+        raise InvalidParameter(f"points must be N x 3 (or N x 4 homogeneous), got shape {x.shape}")
+    nr = np.asarray(cloud.normals)
+    if nr.ndim != 2 or nr.shape[0] != x.shape[0] or nr.shape[1] < 3:
+        raise InvalidParameter(f"normals must be {x.shape[0]} x 3, got shape {nr.shape}")
+    reg = _feature_handle()
+    try:
+        out = reg.compute_fpfh(x, nr, radius, max_nn)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    return Feature(np.ascontiguousarray(out["fpfh"].T))
+
+
+def _feature_rows(f, what):
+    d = np.asarray(f.data_ if isinstance(f, Feature) else f, np.float64)
+    if d.ndim != 2 or not (1 <= d.shape[0] <= 64):
+        raise InvalidParameter(f"{what}: data_ must be dim x n with 1 <= dim <= 64, got shape {d.shape}")
+    return np.ascontiguousarray(d.T)
+
+
+def CorrespondencesFromFeatures(source_feature, target_feature, mutual_filter=True, ransac_n=3) -> np.ndarray:
+    """The correspondence set RegistrationRANSACBasedOnFeatureMatching forms before it samples: (n, 2) int32 pairs
+    (source, target).  With mutual_filter the mutual nearest neighbours when there are at least ransac_n of them, else --
+    as Open3D falls back -- every (a, nearest b)."""
+    if not (_is_int(ransac_n) and ransac_n >= 1):
+        raise InvalidParameter(f"ransac_n must be an integer >= 1, got {ransac_n!r}")
+    a, b = _feature_rows(source_feature, "source_feature"), _feature_rows(target_feature, "target_feature")
+    if a.shape[1] != b.shape[1]:
+        raise InvalidParameter(f"the features have different dimensions ({a.shape[1]} and {b.shape[1]})")
+    reg = _feature_handle()
+    try:
+        nn_ab, _, mutual = reg.match_features(a, b, backward=bool(mutual_filter), mutual=bool(mutual_filter))
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    if mutual_filter and mutual.shape[0] >= ransac_n:
+        return mutual
+    return np.stack([np.arange(nn_ab.size, dtype=np.int32), nn_ab], axis=1)
+
+
+def computeSubmapFeatures(cloud_f64, params: "PlaceRecognitionParameters | None" = None):
+    """o3d_slam::Submap::computeFeatures (Submap.cpp:255-275) on one handle: voxel down-sampling of the whole fp64 cloud at
+    featureVoxelSize_ (reg_voxelize_within_volume), normals by hybrid search (normalKnn_, normalEstimationRadius_) oriented
+    towards the origin (reg_estimate_normals), FPFH (featureRadius_, featureKnn_).  Returns (DataPoints, Feature): the
+    sparse cloud with its normals, and its features.
+    Deviation: the voxel grid starts at 0, not at Open3D's min_bound - voxel/2, and the voxels come in ascending (z, y, x)
+    index order, where VoxelDownSample emits them in hash-map order."""
+    prm = params if params is not None else PlaceRecognitionParameters()
+    _check_fpfh_args(prm.featureRadius_, prm.featureKnn_)
+    _check_overlap_args(None, prm.featureVoxelSize_, 1)
+    if not (_is_int(prm.normalKnn_) and 1 <= prm.normalKnn_ <= 32):
+        raise InvalidParameter(f"normalKnn_ must be an integer in [1, 32], got {prm.normalKnn_!r}")
+    if not (prm.normalEstimationRadius_ > 0):
+        raise InvalidParameter(f"normalEstimationRadius_ must be > 0, got {prm.normalEstimationRadius_!r}")
+    x = _xyz64(cloud_f64, "cloud")
+    reg = _feature_handle()
+    try:
+        sparse, _, _, _ = reg.voxelize_within_volume(x, prm.featureVoxelSize_)
+        pts = sparse.astype(np.float32)
+        nrm = reg.estimate_normals(pts, k=prm.normalKnn_, max_dist=prm.normalEstimationRadius_,
+                                   viewpoint=np.zeros(3, np.float32))["normals"]
+        out = reg.compute_fpfh(pts, nrm, prm.featureRadius_, prm.featureKnn_)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    return DataPoints(pts, normals=nrm), Feature(np.ascontiguousarray(out["fpfh"].T))
