@@ -33,6 +33,12 @@ REG_API reg_status reg_debug_configure(reg_handle* h, const reg_debug_params* d)
  * bin that lists points; -1 where the search does not consult the directory (outside the halo grid, no halo level). */
 REG_API reg_status reg_debug_halo_bound(reg_handle* h, const float* xyz, int64_t n, float* out);
 
+/* Witnesses of the halo directory (tests): out[i] = original index of the reference point that the directory names for the
+ * halo bin of position i; -1 where the bin names none (or there is no halo level); -2 for a bin that lists points.  A
+ * position outside the halo grid lies in no bin: it gets what the search takes from the border bin it clamps to (that
+ * bin's witness, or the first record of its run), -1 without witnesses. */
+REG_API reg_status reg_debug_halo_witness(reg_handle* h, const float* xyz, int64_t n, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

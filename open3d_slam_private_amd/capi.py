@@ -321,7 +321,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dist_fused_buffers", "reg_dist_poll", "reg_estimate_normals", "reg_smooth_normals", "reg_host_solve6_xicp",
            "reg_set_target_f64", "reg_get_target_source_indices", "reg_voxelize_within_volume", "reg_carve_indices", "reg_dist_xicp_buffers", "reg_dist_gather_buffers",
            "reg_dist_record", "reg_dist_centroid_sums", "reg_dist_prepare",
-           "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure", "reg_debug_halo_bound",
+           "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure", "reg_debug_halo_bound", "reg_debug_halo_witness",
            "reg_dist_get_unique_id", "reg_dist_init", "reg_dist_init_custom", "reg_dist_register", "reg_dist_shutdown",
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
@@ -376,6 +376,7 @@ def load_library():
     lib.reg_set_stream.argtypes = [vp, vp]
     lib.reg_debug_configure.argtypes = [vp, C.POINTER(RegDebugParams)]
     lib.reg_debug_halo_bound.argtypes = [vp, f32p, i64, f32p]
+    lib.reg_debug_halo_witness.argtypes = [vp, f32p, i64, vp]
     lib.reg_dist_get_unique_id.argtypes = [C.c_char_p]
     lib.reg_dist_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
     lib.reg_dist_init_custom.argtypes = [vp, C.POINTER(Collectives), C.c_int, C.c_int]
@@ -1320,6 +1321,16 @@ class Registration:
         x = _f32(xyz)
         out = np.empty(x.shape[0], np.float32)
         self._check(self._lib.reg_debug_halo_bound(self._h, _ptr(x), x.shape[0], _ptr(out)))
+        return out
+
+    def halo_witness(self, xyz):
+        """reg_debug_halo_witness: per position (frame of set_target's input) the witness point that the halo directory names
+        for its bin, as an original index; -1 for none, -2 for a bin that lists points.  A position outside the halo grid
+        lies in no bin: it gets what the search takes from the border bin it clamps to (its witness, or the first record
+        of its run)."""
+        x = _f32(xyz)
+        out = np.empty(x.shape[0], np.int32)
+        self._check(self._lib.reg_debug_halo_witness(self._h, _ptr(x), x.shape[0], _ptr(out)))
         return out
 
     def prepare(self, T_init=None):

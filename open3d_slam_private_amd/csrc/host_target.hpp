@@ -38,6 +38,7 @@ struct EnvSwitches {
     bool halo_occ = true;       // O3D_NO_HALO_OCC: halo-bin edge from the floored bin edge instead of the density-derived one (A/B)
     bool no_dynprune = false;   // O3D_NO_DYNPRUNE: level scans keep the ball they started with (A/B)
     bool no_empty_bound = false;   // O3D_NO_EMPTY_BOUND: the halo directory carries no empty-space bound (A/B)
+    bool no_witness = false;       // O3D_NO_WITNESS: the empty bins of the halo directory name no witness point (A/B)
     bool no_burst = false;      // O3D_NO_BURST: trickle-feed the fused iterations (A/B of the burst submission)
     bool hints = false;         // O3D_HINTS: histogram of the terminating search level of the last iteration
     bool stamps = false;        // O3D_STAMPS: in-kernel cycle stamps of the update kernel
@@ -76,6 +77,7 @@ struct EnvSwitches {
         no_burst = getenv("O3D_NO_BURST") != nullptr;
         no_dynprune = getenv("O3D_NO_DYNPRUNE") != nullptr;
         no_empty_bound = getenv("O3D_NO_EMPTY_BOUND") != nullptr;
+        no_witness = getenv("O3D_NO_WITNESS") != nullptr;
         halo_occ = getenv("O3D_NO_HALO_OCC") == nullptr;
         hints = getenv("O3D_HINTS") != nullptr;
         stamps = getenv("O3D_STAMPS") != nullptr;
@@ -467,6 +469,60 @@ reg_status reg_debug_halo_bound(reg_handle* h, const float* xyz, int64_t n, floa
     return REG_OK;
 }
 
+// Diagnostic copy of the halo directory's witnesses, looked up as nearest_halo() looks them up: out[i] = original index of the
+// witness of position i's bin, -1 where the bin names none (or there is no halo level), -2 for a bin with a run.  A position
+// outside the halo grid lies in no bin: it gets what the search takes from the border bin it clamps to -- that bin's
+// witness, or the first record of its run (whichever record the fill pass put first), or -1 without witnesses.
+reg_status reg_debug_halo_witness(reg_handle* h, const float* xyz, int64_t n, int32_t* out) {
+    if (!h || !xyz || !out || n < 0) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    const Grid& g = h->grid;
+    for (int64_t i = 0; i < n; ++i) out[i] = -1;
+    if (h->m <= 0 || !g.use_halo) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const size_t nbins = (size_t)g.hdimx * g.hdimy * g.hdimz;
+    std::vector<uint2> dir(nbins);
+    std::vector<float4> pts((size_t)h->m);
+    const bool witness = (g.out_bound & 2) != 0;
+    std::vector<float4> recs(witness ? h->t_halo_pts.cap / sizeof(float4) : 0);   // the runs' records (positions outside the grid)
+    HIPCHK(h, hipMemcpyAsync(dir.data(), g.halo_dir, nbins * sizeof(uint2), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(pts.data(), g.pts, (size_t)h->m * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    if (!recs.empty()) HIPCHK(h, hipMemcpyAsync(recs.data(), g.halo_pts, recs.size() * sizeof(float4), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    auto bin = [](float v, float c, float o, float inv) {   // k_center_bbox, then bin_coord_f: one rounding per operation
+        volatile float q = v - c;
+        volatile float d = q - o;
+        volatile float s = d * inv;
+        return std::floor((float)s);
+    };
+    auto clampi = [](float f, int dim) { return (int)std::fmin(std::fmax(f, 0.f), (float)(dim - 1)); };
+    auto index_at = [&](uint32_t pos) {
+        uint32_t idx = 0xffffffffu;
+        if (pos < (uint32_t)h->m) std::memcpy(&idx, &pts[pos].w, 4);
+        return (int32_t)idx;   // (a witness is a sorted position: always in range)
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        const float fx = bin(xyz[3 * i], h->c_ref[0], g.hox, g.hinv_c), fy = bin(xyz[3 * i + 1], h->c_ref[1], g.hoy, g.hinv_c),
+                    fz = bin(xyz[3 * i + 2], h->c_ref[2], g.hoz, g.hinv_c);
+        const bool inside = fx >= 0.f && fy >= 0.f && fz >= 0.f && fx < (float)g.hdimx && fy < (float)g.hdimy && fz < (float)g.hdimz;
+        const uint2 hd = dir[((size_t)clampi(fz, g.hdimz) * g.hdimy + clampi(fy, g.hdimy)) * g.hdimx + clampi(fx, g.hdimx)];
+        if ((int)hd.y >= 0) {
+            out[i] = -2;
+            if (!inside) {
+                out[i] = -1;
+                if (witness && hd.x < recs.size()) {
+                    uint32_t pos;
+                    std::memcpy(&pos, &recs[hd.x].w, 4);
+                    out[i] = index_at(pos);
+                }
+            }
+        } else if (witness && hd.x != 0xffffffffu) {
+            out[i] = index_at(hd.x);
+        }
+    }
+    return REG_OK;
+}
+
 reg_status reg_set_stream(reg_handle* h, void* hip_stream) {
     if (!h) return REG_BAD_ARGUMENT;
     if (!h->device_ok) return REG_DEVICE_ERROR;
@@ -667,7 +723,10 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     hc.dimz = (int)dims[2];
     // t_halo_start: counts, then bin starts, then -- once the directory is written -- the fill pass's cursors.
     // t_halo_dir: the directory {start, count | bound} the search reads; before that, scratch of the bound's passes
-    // (bytes [0, 2 nbins): pass-x gaps, [4 nbins, 5 nbins): occupancy bytes).  t_halo_cursor: pass-y scratch (4 bytes per bin).
+    // (bytes [0, 2 nbins): pass-x gaps, [4 nbins, 5 nbins): occupancy bytes).  t_halo_cursor: pass-y scratch (4 bytes per bin);
+    // with witnesses, 9 bytes per bin: [4 nbins, 8 nbins) the arg-min offsets of pass y, [8 nbins, 9 nbins) those of pass x,
+    // and -- once the directory is written -- [0, 4 nbins) the representatives of the runs.  Like the rest of the build's scratch
+    // it stays with the handle for the next build (no allocation per set_target): 5 bytes per bin more than before.
     HIPCHK(h, h->t_halo_start.reserve((nbins + 1) * 4));
     HIPCHK(h, h->t_halo_dir.reserve(nbins * 8));
     HIPCHK(h, hipMemsetAsync(h->t_halo_start.p, 0, (nbins + 1) * 4, h->stream));
@@ -683,10 +742,11 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     bc.eps_bins = (float)std::max(dims[0], std::max(dims[1], dims[2])) * (1.0f / 2097152.0f);
     bc.sub = 2.f * abs_margin;
     const bool bound = !h->env.no_empty_bound && std::isfinite(h->prm.max_dist) && h->prm.max_dist > 0.f;
+    const bool witness = bound && !h->env.no_witness;   // (the arg-min rides on the bound's passes)
     uint8_t* const occ = (uint8_t*)h->t_halo_dir.p + 4 * nbins;
     if (bound) {
         bc.R = (int)std::min(64.0f, std::floor(h->prm.max_dist * inv) + 2.0f);   // (beyond 64 bins: a weaker, still valid bound)
-        HIPCHK(h, h->t_halo_cursor.reserve(nbins * 4));
+        HIPCHK(h, h->t_halo_cursor.reserve(nbins * (witness ? 9 : 4)));
         HIPCHK(h, hipMemsetAsync(occ, 0, nbins, h->stream));
     }
     k_halo_insert<<<grid_for(h->m), 256, 0, h->stream>>>(h->t_pts.as<float4>(), h->m, hc, 0,
@@ -694,17 +754,32 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     REGCHK(scan_excl(h, h->rp_tmp, h->t_halo_start.as<uint32_t>(), h->t_halo_start.as<uint32_t>(), nbins + 1));
     uint32_t total = 0;
     HIPCHK(h, hipMemcpyAsync(&total, h->t_halo_start.as<uint32_t>() + nbins, 4, hipMemcpyDeviceToHost, h->stream));
+    uint8_t* const xo = witness ? (uint8_t*)h->t_halo_cursor.p + 8 * nbins : nullptr;
+    uint32_t* const yo = witness ? h->t_halo_cursor.as<uint32_t>() + nbins : nullptr;
     if (bound) {
-        k_halo_gap_x<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(occ, h->t_halo_start.as<uint32_t>(), bc, h->t_halo_dir.as<uchar2>());
-        k_halo_gap_y<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_dir.as<uchar2>(), bc, h->t_halo_cursor.as<ushort2>());
+        k_halo_gap_x<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(occ, h->t_halo_start.as<uint32_t>(), bc, h->t_halo_dir.as<uchar2>(), xo);
+        k_halo_gap_y<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_dir.as<uchar2>(), bc, h->t_halo_cursor.as<ushort2>(), xo, yo);
     }
     k_halo_dir<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_start.as<uint32_t>(),
                                                                  bound ? h->t_halo_cursor.as<ushort2>() : nullptr, bc,
-                                                                 h->t_halo_dir.as<uint2>());
+                                                                 h->t_halo_dir.as<uint2>(), yo);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, h->t_halo_pts.reserve((size_t)std::max<uint32_t>(total, 1) * 16));
     k_halo_insert<<<grid_for(h->m), 256, 0, h->stream>>>(h->t_pts.as<float4>(), h->m, hc, 1,
                                                          h->t_halo_start.as<uint32_t>(), h->t_halo_pts.as<float4>(), nullptr);
+    if (witness) {
+        HaloRepCfg rc;
+        rc.ox = hc.ox;
+        rc.oy = hc.oy;
+        rc.oz = hc.oz;
+        rc.ch = ch;
+        rc.dimx = hc.dimx;
+        rc.dimy = hc.dimy;
+        rc.dimz = hc.dimz;
+        k_halo_rep<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_dir.as<uint2>(), h->t_halo_pts.as<float4>(), rc,
+                                                                     h->t_halo_cursor.as<uint32_t>());
+        k_halo_witness<<<grid_for((int64_t)nbins), 256, 0, h->stream>>>(h->t_halo_dir.as<uint2>(), h->t_halo_cursor.as<uint32_t>(), nbins);
+    }
     g.use_halo = 1;
     g.hox = hc.ox;
     g.hoy = hc.oy;
@@ -718,7 +793,7 @@ static reg_status build_halo(reg_handle* h, float c, const float bmin[3], const 
     g.hmaxy = bmax[1];
     g.hmaxz = bmax[2];
     g.lb_sub = 2.f * abs_margin;
-    g.out_bound = bound ? 1 : 0;
+    g.out_bound = (bound ? 1 : 0) | (witness ? 2 : 0);
     g.halo_pts = h->t_halo_pts.as<float4>();
     g.rho_h = rho_h;
     g.level_after_halo = g.n_levels - 1;

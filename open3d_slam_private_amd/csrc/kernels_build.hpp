@@ -230,64 +230,107 @@ struct HaloBoundCfg {
     float eps_bins;  // rounding of a bin coordinate fl(fl(v - o) * 1/c_h), in bins (2^-21 * largest dimension)
     float sub;       // absolute margin taken off (2 * abs_margin, as the halo radius carries)
 };
+// Witness of an empty bin: the passes below carry the arg-min of (b) along -- WHICH bin with a run is the nearest, as
+// signed bin offsets -- so that the last pass knows that bin, L, and the directory entry of an empty bin can name one real
+// reference point near it (the representative of L's run, k_halo_rep).  Tie rule, the same in every pass: the smallest
+// squared whole-bin gap S1 first; among equal S1, axis by axis in the order z, y, x: the smallest |d| and, between -d and +d,
+// the negative offset.  (Each pass walks d from -R to +R and replaces its choice only on a strictly smaller (S1, |d|).)  The
+// offsets live in arrays of their own (`xo`, `yo`), null when no witness is wanted: the bound's intermediates stay as they
+// were.  xo: offset + 128, 0 = no run in reach; yo: {dx + 128, dy + 128, 1, 0}, all 0 = none; S1 of the arg-min is kept
+// uncapped in yo's upper half so that a choice made at a gap beyond R (where the bound's S1 saturates at R^2) is still by gap.
 // pass x: whole bins between bin (x, y, z) and the nearest bin of its x-row that holds a point (.x: `occ` bytes) / that has a
 // run (.y: `start`, after its scan); 0: that bin itself or its neighbour; R: none within R + 1
 __global__ void k_halo_gap_x(const uint8_t* __restrict__ occ, const uint32_t* __restrict__ start, HaloBoundCfg c,
-                             uchar2* __restrict__ gx) {
+                             uchar2* __restrict__ gx, uint8_t* __restrict__ xo) {
     const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
     if (B >= nb) return;
     const int x = (int)(B % (size_t)c.dimx);
-    int own = c.R + 1, run = c.R + 1;
+    int own = c.R + 1, run = c.R + 1, at = -128;
     const int lo = max(-c.R - 1, -x), hi = min(c.R + 1, c.dimx - 1 - x);
     uint32_t prev = start[(ptrdiff_t)B + lo];
     for (int d = lo; d <= hi; ++d) {
         const uint32_t next = start[(ptrdiff_t)B + d + 1];
-        if (next != prev) run = min(run, abs(d));
+        if (next != prev) {
+            if (at == -128 || abs(d) < run) at = d;
+            run = min(run, abs(d));
+        }
         if (occ[(ptrdiff_t)B + d]) own = min(own, abs(d));
         prev = next;
     }
     gx[B] = make_uchar2((unsigned char)min(max(own - 1, 0), c.R), (unsigned char)min(max(run - 1, 0), c.R));
+    if (xo) xo[B] = (uint8_t)(at + 128);
 }
 // pass y: min over the bins of the same (x, z) column of gx^2 + gy^2
-__global__ void k_halo_gap_y(const uchar2* __restrict__ gx, HaloBoundCfg c, ushort2* __restrict__ sxy) {
+__global__ void k_halo_gap_y(const uchar2* __restrict__ gx, HaloBoundCfg c, ushort2* __restrict__ sxy,
+                             const uint8_t* __restrict__ xo, uint32_t* __restrict__ yo) {
     const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
     if (B >= nb) return;
     const int y = (int)((B / (size_t)c.dimx) % (size_t)c.dimy);
     int S0 = c.R * c.R, S1 = S0;
+    int wS = 0x7fffffff, wdy = 0, wdx = 0;   // arg-min of S1 over the rows that have a run in reach
     const int lo = max(-c.R, -y), hi = min(c.R, c.dimy - 1 - y);
     for (int d = lo; d <= hi; ++d) {
         const uchar2 v = gx[(ptrdiff_t)B + (ptrdiff_t)d * c.dimx];
         const int g = max(abs(d) - 1, 0);
         S0 = min(S0, g * g + (int)v.x * (int)v.x);
         S1 = min(S1, g * g + (int)v.y * (int)v.y);
+        if (xo) {
+            const int o = (int)xo[(ptrdiff_t)B + (ptrdiff_t)d * c.dimx];
+            const int s = g * g + (int)v.y * (int)v.y;
+            if (o != 0 && (s < wS || (s == wS && abs(d) < abs(wdy)))) {
+                wS = s;
+                wdy = d;
+                wdx = o - 128;
+            }
+        }
     }
     sxy[B] = make_ushort2((unsigned short)S0, (unsigned short)S1);
+    if (yo) yo[B] = wS == 0x7fffffff ? 0u : ((uint32_t)(wdx + 128) | ((uint32_t)(wdy + 128) << 8) | ((uint32_t)(wS + 1) << 16));
 }
 // pass z + directory: one aligned record per bin, {first halo record, count} -- or, for a bin whose run is empty,
-// {first, 0x80000000 | bits(lb)} (lb >= 0, rounded down by the margins below): the search reads it with the ONE load
-// that used to fetch the run's start.  sxy == null: no bound (lb = 0).
+// {witness, 0x80000000 | bits(lb)} (lb >= 0, rounded down by the margins below): the search reads it with the ONE load
+// that used to fetch the run's start.  sxy == null: no bound (lb = 0).  The witness field leaves this kernel as the linear
+// index of L, the nearest bin with a run (yo == null, or no run within R bins: kNoWitness); k_halo_witness turns it into
+// a reference point once the runs are filled.  (.x of an empty bin used to repeat the start of the next run; the search
+// only ever read it as an empty range.)
+constexpr uint32_t kNoWitness = 0xffffffffu;
 __global__ void k_halo_dir(const uint32_t* __restrict__ start, const ushort2* __restrict__ sxy, HaloBoundCfg c,
-                           uint2* __restrict__ dir) {
+                           uint2* __restrict__ dir, const uint32_t* __restrict__ yo) {
     const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
     if (B >= nb) return;
     const uint32_t s = start[B], cnt = start[B + 1] - s;
-    uint32_t second = cnt;
+    uint32_t first = s, second = cnt;
     if (cnt == 0) {
         float lb = 0.f;
+        first = kNoWitness;
         if (sxy) {
             const size_t plane = (size_t)c.dimx * c.dimy;
             const int z = (int)(B / plane);
             int S0 = c.R * c.R, S1 = S0;
+            int wS = 0x7fffffff, wdz = 0;
+            uint32_t wo = 0;
             const int lo = max(-c.R, -z), hi = min(c.R, c.dimz - 1 - z);
             for (int d = lo; d <= hi; ++d) {
                 const ushort2 v = sxy[(ptrdiff_t)B + (ptrdiff_t)d * (ptrdiff_t)plane];
                 const int g = max(abs(d) - 1, 0);
                 S0 = min(S0, g * g + (int)v.x);
                 S1 = min(S1, g * g + (int)v.y);
+                if (yo) {
+                    const uint32_t o = yo[(ptrdiff_t)B + (ptrdiff_t)d * (ptrdiff_t)plane];
+                    const int sw = g * g + (int)(o >> 16) - 1;
+                    if (o != 0u && (sw < wS || (sw == wS && abs(d) < abs(wdz)))) {
+                        wS = sw;
+                        wdz = d;
+                        wo = o;
+                    }
+                }
             }
+            if (wo != 0u)
+                first = (uint32_t)((ptrdiff_t)B + (ptrdiff_t)wdz * (ptrdiff_t)plane + ((ptrdiff_t)((wo >> 8) & 255u) - 128) * c.dimx +
+                                   ((ptrdiff_t)(wo & 255u) - 128));
             // bins -> metres, downward: 1e-3 relative (rounding of 1/c_h, of the distance the search computes and of its
             // comparison with rho), the rounding of the two bin coordinates per axis, the absolute margin of the radii
             const float down = 1.0f - 1e-3f;
@@ -299,5 +342,45 @@ __global__ void k_halo_dir(const uint32_t* __restrict__ start, const ushort2* __
         }
         second = 0x80000000u | __float_as_uint(lb);
     }
-    dir[B] = make_uint2(s, second);
+    dir[B] = make_uint2(first, second);
+}
+// Representative of a bin's run: the listed point nearest the centre of the bin's box, ties by the smallest sorted position --
+// a function of the run as a SET (its records arrive in atomic order).  One thread per bin with a run.
+struct HaloRepCfg {
+    float ox, oy, oz, ch;
+    int dimx, dimy, dimz;
+};
+__global__ void k_halo_rep(const uint2* __restrict__ dir, const float4* __restrict__ halo_pts, HaloRepCfg c,
+                           uint32_t* __restrict__ rep) {
+    const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    const size_t nb = (size_t)c.dimx * c.dimy * c.dimz;
+    if (B >= nb) return;
+    const uint2 hd = dir[B];
+    if ((int)hd.y < 0) return;
+    const int x = (int)(B % (size_t)c.dimx), y = (int)((B / (size_t)c.dimx) % (size_t)c.dimy), z = (int)(B / ((size_t)c.dimx * c.dimy));
+    const float cx = c.ox + ((float)x + 0.5f) * c.ch, cy = c.oy + ((float)y + 0.5f) * c.ch, cz = c.oz + ((float)z + 0.5f) * c.ch;
+    float bd = INFINITY;
+    uint32_t bp = kNoWitness;
+    for (uint32_t j = hd.x; j < hd.x + hd.y; ++j) {
+        const float4 t = halo_pts[j];
+        const float dx = t.x - cx, dy = t.y - cy, dz = t.z - cz;
+        float a = dx * dx;
+        float b = dy * dy;
+        float d2 = a + b;
+        a = dz * dz;
+        d2 = d2 + a;
+        const uint32_t pos = __float_as_uint(t.w);
+        if (d2 < bd || (d2 == bd && pos < bp)) {
+            bd = d2;
+            bp = pos;
+        }
+    }
+    rep[B] = bp;
+}
+// ... and the empty bins trade the index of L for L's representative (a sorted position into Grid::pts)
+__global__ void k_halo_witness(uint2* __restrict__ dir, const uint32_t* __restrict__ rep, size_t nb) {
+    const size_t B = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (B >= nb) return;
+    const uint2 hd = dir[B];
+    if ((int)hd.y < 0 && hd.x != kNoWitness) dir[B].x = rep[hd.x];
 }

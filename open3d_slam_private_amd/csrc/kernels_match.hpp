@@ -121,7 +121,7 @@ k_match_g8(const float4* __restrict__ src, int64_t n, const IterState* __restric
     uint32_t rnk = 0;
     if (q < n) {
         const int hv = hint ? (int)hraw : 0;
-        if (nearest_halo<G, false>(g, p, sub, gbase, -1, hv >= 2 ? hv - 2 : -1, b, cov, l, &lvl, &cov2)) {
+        if (nearest_halo<G, false, true>(g, p, sub, gbase, -1, hv >= 2 ? hv - 2 : -1, b, cov, l, &lvl, &cov2)) {
             if (sub == 0) emit(q, p, b, lvl, cov2);
 #if !O3D_MATCH_REGROUP
         } else if (true) {   // A/B: the levels at once, by the same lanes

@@ -52,10 +52,13 @@ struct Grid {
     int hdimx, hdimy, hdimz;
     // One aligned record per bin: {first halo record, count}; a bin whose run is EMPTY carries, in place of the count,
     // 0x80000000 | bits(lb): a lower bound (>= 0, rounded down) on the distance from any position bin_coord_f maps to
-    // that bin to any reference point -- the search skips the levels whose radius cannot reach that far.
+    // that bin to any reference point -- the search skips the levels whose radius cannot reach that far -- and, in place of
+    // the first record, its WITNESS: the sorted position (into `pts`) of one reference point of the nearest bin that has a
+    // run, or 0xffffffff for none.
     const uint2* halo_dir;       // [hdimx*hdimy*hdimz]
     // The same bound for a query OUTSIDE the halo grid: its distance to the reference's bounding box [hox.., hmax..] (every
     // reference point lies inside), less lb_sub; out_bound = 0 switches it off (unbounded max_dist, O3D_NO_EMPTY_BOUND).
+    // Bit 1 of out_bound: the directory carries witnesses (off: O3D_NO_WITNESS).
     float hmaxx, hmaxy, hmaxz, lb_sub;
     int out_bound;
     const float4* halo_pts;
@@ -727,7 +730,16 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
 // (level -1); otherwise `best` (the group's merged candidate of the halo run, if any, the same in every lane), `cov` and the regular
 // level `l` to continue at are what nearest_levels() needs -- by the same lanes or, handed over through LDS, by another group
 // (k_match_g8 regroups the unanswered queries of a workgroup so that whole waves are done after the halo part).
-template <int G, bool kTop2>
+//
+// kWitness (k_match_g8 only, whose first launches are the ones that meet empty bins in numbers): a query whose bin has no run
+// -- or which lies outside the halo grid -- used to reach the regular levels with no candidate, so its first level scan took the
+// level's whole box and the ball shrank only as candidates turned up, in brick order.  It now takes the directory's witness
+// (outside the grid: the witness of the clamped border bin, or the first record of that bin's run) as its first candidate,
+// and the existing candidate-bounded box of scan_level_rows does the rest.  Exactness: the witness is a real reference point
+// within max_dist; a box sized by a real point's distance (+ slack, x 1.001, + the level's margin) holds every point at most
+// as far, ties included, so the winner and its tie-break by original index are what they were; and the witness's own
+// distance is a valid `second` for the bound min(second, cov^2) the shortcut cache receives.
+template <int G, bool kTop2, bool kWitness = false>
 __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, int gbase, int first_level, int after_halo, Best& best,
                                              float& cov, int& l, int* level_out, float* cov2_out) {
     best.d2 = INFINITY;
@@ -759,6 +771,36 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
             a = oz * oz;
             s2 = s2 + a;
             lbd = __builtin_amdgcn_sqrtf(s2) * (1.0f - 1e-3f) - g.lb_sub;
+        }
+        // the witness becomes the group's candidate (every lane holds the same one, as after a merge); the climb starts at
+        // the first radius that covers it
+        auto take_witness = [&](uint32_t w, int from) {
+            const float4 t = g.pts[w];
+            const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
+            float a = dx * dx;
+            float b = dy * dy;
+            float d2 = a + b;
+            a = dz * dz;
+            d2 = d2 + a;
+            if (d2 <= g.max_d2) {   // (beyond max_dist it is no candidate: the empty-space bound alone applies)
+                best.d2 = d2;
+                best.idx = __float_as_uint(t.w);
+                best.pos = (int)w;
+                l = from;
+                while (l + 1 < g.n_levels && g.rho[l] * g.rho[l] < d2) ++l;
+            }
+        };
+        if (kWitness && !inside && (g.out_bound & 2) && !(lbd > g.rho[g.n_levels - 1])) {
+            // outside the grid: the border bin the query clamps to.  The first record of a run is whichever the fill pass's
+            // atomics put first: the winner, its d2 and tie-break do not depend on it (any real point bounds the box exactly),
+            // but the size of the box, the cov2 / second handed to the shortcut cache and the hint byte of such a query can
+            // differ from run to run on the same input -- and with them hint histograms and search statistics.
+            const int cx = (int)fminf(fmaxf(fx, 0.f), (float)(g.hdimx - 1)), cy = (int)fminf(fmaxf(fy, 0.f), (float)(g.hdimy - 1)),
+                      cz = (int)fminf(fmaxf(fz, 0.f), (float)(g.hdimz - 1));
+            const uint2 hd = g.halo_dir[((size_t)cz * g.hdimy + cy) * g.hdimx + cx];
+            uint32_t w = hd.x;
+            if ((int)hd.y >= 0) w = __float_as_uint(g.halo_pts[hd.x].w);
+            if (w != 0xffffffffu) take_witness(w, 0);
         }
         if (inside) {
             const size_t B = ((size_t)(int)fz * g.hdimy + (int)fy) * g.hdimx + (int)fx;
@@ -795,7 +837,10 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
                 while (l + 1 < g.n_levels && g.rho[l] * g.rho[l] < best.d2) ++l;
             } else {
                 l = max(g.level_after_halo, after_halo);
-                if (empty) lbd = __uint_as_float(hd.y & 0x7fffffffu);   // the directory's bound for this bin
+                if (empty) {
+                    lbd = __uint_as_float(hd.y & 0x7fffffffu);   // the directory's bound for this bin
+                    if (kWitness && hd.x != 0xffffffffu && !(lbd > g.rho[g.n_levels - 1])) take_witness(hd.x, g.level_after_halo);
+                }
             }
         }
         if (lbd > 0.f) {
