@@ -7,6 +7,7 @@
 //                   dp.getDescriptorViewByName("normals").data(), 3 }      (column-major Eigen == AoS per point)
 // and transforms as column-major float[16] == Eigen::Matrix4f::data().
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <limits>
@@ -360,6 +361,50 @@ inline std::vector<int32_t> matchFeatures(const double* source, int64_t na, cons
         all[2 * a + 1] = nn[a];
     }
     return all;
+}
+
+// RegistrationRANSACBasedOnCorrespondence with TransformationEstimationPointToPoint(false), the edge-length and the
+// distance checker (PlaceRecognition.cpp:78-91) on the device: `source` (n x 3) and `target` (m x 3) doubles and the
+// interleaved (source, target) pairs of matchFeatures in host memory.  A checker threshold <= 0 switches it off.
+// Deterministic for a given seed (include/o3dslam_reg.h, reg_ransac_correspondences).
+struct RansacResult {
+    std::array<double, 16> transformation{{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}};   // column-major
+    double fitness = 0.0, inlierRmse = 0.0;
+    std::vector<int32_t> correspondenceSet;   // interleaved (source, target) inlier pairs
+    int64_t iterations = 0, validated = 0, bestIteration = -1;
+};
+inline RansacResult ransacFromCorrespondences(const double* source, int64_t n, const double* target, int64_t m,
+                                              const std::vector<int32_t>& corres, double maxCorrespondenceDistance = 0.75,
+                                              int ransacN = 3, int64_t maxIteration = 1000000, double confidence = 0.99,
+                                              double checkerDistance = 0.75, double checkerEdgeLength = 0.5,
+                                              uint64_t seed = 0, int device = 0) {
+    RansacResult out;
+    const int64_t k = (int64_t)(corres.size() / 2);
+    if (k == 0) return out;
+    reg_ransac_params p{};
+    p.struct_size = (int32_t)sizeof(p);
+    p.ransac_n = ransacN;
+    p.max_iteration = maxIteration;
+    p.confidence = confidence;
+    p.max_correspondence_distance = maxCorrespondenceDistance;
+    p.distance_threshold = checkerDistance;
+    p.edge_similarity = checkerEdgeLength;
+    p.seed = seed;
+    reg_ransac_result r{};
+    r.struct_size = (int32_t)sizeof(r);
+    out.correspondenceSet.resize((size_t)(2 * k));
+    withFeatureHandle(device, [&](reg_handle* h) {
+        return reg_ransac_correspondences(h, source, n, target, m, corres.data(), k, 0, &p, &r, out.correspondenceSet.data(),
+                                          nullptr);
+    });
+    std::copy(r.T, r.T + 16, out.transformation.begin());
+    out.fitness = r.fitness;
+    out.inlierRmse = r.inlier_rmse;
+    out.correspondenceSet.resize((size_t)(2 * r.n_inliers));
+    out.iterations = r.n_iterations;
+    out.validated = r.n_validated;
+    out.bestIteration = r.best_iteration;
+    return out;
 }
 
 // SurfaceNormalDataPointsFilter (DataPointsFilters/SurfaceNormal.cpp:152-252) on the device: exact k-NN (the point

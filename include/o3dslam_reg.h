@@ -869,6 +869,85 @@ REG_API reg_status reg_match_features(reg_handle* h, const double* fa, int64_t n
                                       int on_device, int32_t* nn_ab /* na */, int32_t* nn_ba /* nb, may be NULL */,
                                       int32_t* mutual /* 2 x capacity na: (a, b) pairs */, int64_t* n_mutual);
 
+/* ---- RANSAC registration on correspondences: the hypothesis loop of place recognition ----------------
+   RegistrationRANSACBasedOnCorrespondence, the second half of RegistrationRANSACBasedOnFeatureMatching
+   (PlaceRecognition.cpp:78-91), between reg_match_features and reg_set_pair_overlap_f64.  Open3D 0.15.1 is not in the
+   reference tree: PARITY UNPINNED; the contract below is this project's own.
+
+   src_xyz n x 3, tgt_xyz m x 3 doubles; corres: k interleaved int32 pairs (a, b); on_device covers the clouds, corres,
+   inliers and iter_status.  params and result are host structs with struct_size set by the caller.
+   Returns: REG_BAD_ARGUMENT for a NULL params / result or a wrong struct_size, ransac_n outside [3, 8], max_iteration < 1,
+   confidence outside [0, 1], max_correspondence_distance not finite or <= 0, a NaN threshold, batch outside [0, 2^20],
+   n, m or k > 2^31 - 1; then REG_EMPTY_SOURCE for k <= 0; then REG_BAD_ARGUMENT for a NULL src_xyz, tgt_xyz, corres or
+   inliers or an empty cloud; then REG_OK with the default result (identity, zeros, best_iteration -1) for k < ransac_n,
+   as Open3D (the indices are not looked at); then REG_BAD_ARGUMENT for an index outside [0, n) / [0, m) (checked on
+   the device).  A valid run returns REG_OK even if nothing qualified.
+
+   Numeric contract: fp64, one rounding per operation (the build forbids contraction); |d|^2 = (dx*dx + dy*dy) + dz*dz.
+     sampling, with replacement as Open3D, counter based: slot j of iteration i draws, all mod 2^64,
+         ctr = i*ransac_n + j;  z = seed + (ctr + 1)*0x9E3779B97F4A7C15;  z = (z ^ z>>30)*0xBF58476D1CE4E5B9;
+         z = (z ^ z>>27)*0x94D049BB133111EB;  z ^= z>>31;  index = ((z >> 32)*k) >> 32
+       and s_j / t_j are the source / target point of correspondence `index`.
+     status of iteration i, the first rule that fails:
+       -1  two slots drew the same correspondence (deviation: Open3D goes on with a rank-deficient sample)
+       -2  edge-length checker (edge_similarity > 0): for some slots u < v, ds = |s_u - s_v|, dt = |t_u - t_v| (sqrt of the
+           form above): ds < dt*sim or dt < ds*sim.  It needs no transform and runs before the fit; the outcome is that
+           of Open3D's order.
+       -3  degenerate fit: sigma_2 <= 1e-12*sigma_1.  The fit is TransformationEstimationPointToPoint(false) (umeyama
+           without scale): sm, tm = (slot sums in slot order)/ransac_n, H = sum_j (s_j - sm)(t_j - tm)^T = U S V^T,
+           R = V diag(1, 1, det(V U^T)) U^T, t = tm - R sm.  The SVD method is not part of the contract.
+       -4  distance checker (distance_threshold > 0): some slot has |R s_j + t - t_j|^2 > fl(threshold*threshold), with
+           (R s + t).x = ((R00*s.x + R01*s.y) + R02*s.z) + t.x (y, z alike).
+       >= 0  the inlier count over all k correspondences (EvaluateRANSACBasedOnCorrespondence): correspondence (a, b) is
+           an inlier iff d2 = |R s_a + t - t_b|^2 < fl(maxd*maxd) (deviation: Open3D tests sqrt(d2) < maxd).
+           err2 = sum of d2 over the inliers: ascending k inside chunks of REG_RANSAC_CHUNK correspondences, each from 0,
+           then the chunk sums added in ascending chunk order.
+     best hypothesis, sequential semantics (deviation: Open3D's OpenMP loop is not deterministic), i = 0, 1, ...:
+       a hypothesis with count > 0 replaces the best iff count > best.count, or count == best.count and err2 < best.err2
+       (a tie keeps the earlier one); after each replacement
+           x = log(1 - confidence) / log(1 - pow(count/k, ransac_n));   est_k = min(est_k, trunc(x)) when x >= 0
+       on the host in libm (reg_host_ransac_est_k), est_k = max_iteration at the start.  An x that is not >= 0 changes
+       nothing: NaN (-inf / -inf: confidence 1 with count == k) and -inf (pow(count/k, ransac_n) < 2^-53, so that the
+       denominator is log(1) = +0; deviation from the IEEE quotient, which would end the loop where it knows least).  So
+       confidence 1 never stops early and count == k gives est_k = 0.  The loop ends at the first i >= est_k: the stop
+       index, max_iteration at the latest.  The device evaluates iterations in batches (params.batch, 0: the default);
+       iterations past the stop index are wasted work and change nothing: the result does not depend on batch.
+     result: T column-major (identity when nothing qualified), fitness = count/k, inlier_rmse = sqrt(err2/count),
+       n_inliers and the inlier pairs of T in ascending k, n_iterations = the stop index, n_validated = iterations before
+       it with status >= 0, best_iteration (-1: none), batch = the batch size that was used.  iter_status (may be NULL;
+       max_iteration words): the status of every i < stop index; untouched beyond. */
+#define REG_RANSAC_CHUNK 1024
+typedef struct {
+    int32_t  struct_size;                   /* sizeof(reg_ransac_params) */
+    int32_t  ransac_n;                      /* 3 .. 8 */
+    int64_t  max_iteration;                 /* >= 1 */
+    double   confidence;                    /* 0 .. 1 */
+    double   max_correspondence_distance;   /* finite, > 0 */
+    double   distance_threshold;            /* CorrespondenceCheckerBasedOnDistance; <= 0: off */
+    double   edge_similarity;               /* CorrespondenceCheckerBasedOnEdgeLength; <= 0: off */
+    uint64_t seed;
+    int32_t  batch;                         /* iterations per device batch; 0: the default */
+    int32_t  reserved;
+} reg_ransac_params;
+typedef struct {
+    int32_t struct_size;                    /* sizeof(reg_ransac_result), set by the caller */
+    int32_t batch;                          /* iterations per device batch that were used (statistics; 0: no batch ran) */
+    double  T[16];                          /* column-major */
+    double  fitness;
+    double  inlier_rmse;
+    int64_t n_inliers;
+    int64_t n_iterations;
+    int64_t n_validated;
+    int64_t best_iteration;
+} reg_ransac_result;
+REG_API reg_status reg_ransac_correspondences(reg_handle* h, const double* src_xyz, int64_t n, const double* tgt_xyz, int64_t m,
+                                              const int32_t* corres /* 2 x k */, int64_t k, int on_device,
+                                              const reg_ransac_params* params, reg_ransac_result* result,
+                                              int32_t* inliers /* 2 x capacity k */,
+                                              int32_t* iter_status /* max_iteration, may be NULL */);
+/* The stop rule above, host-only: est_k after a replacement by a hypothesis with `count` inliers of k. */
+REG_API double reg_host_ransac_est_k(double est_k, double confidence, int64_t count, int64_t k, int32_t ransac_n);
+
 /* Introspection of the search structure (tests, DESIGN.md numbers). */
 typedef struct {
     int64_t n_points;

@@ -252,6 +252,26 @@ class OctreeParams(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+class RansacParams(C.Structure):
+    """reg_ransac_params (include/o3dslam_reg.h): RegistrationRANSACBasedOnCorrespondence's parameters."""
+    _fields_ = [("struct_size", C.c_int32), ("ransac_n", C.c_int32), ("max_iteration", C.c_int64),
+                ("confidence", C.c_double), ("max_correspondence_distance", C.c_double),
+                ("distance_threshold", C.c_double), ("edge_similarity", C.c_double), ("seed", C.c_uint64),
+                ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RansacResult(C.Structure):
+    """reg_ransac_result (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("batch", C.c_int32), ("T", C.c_double * 16), ("fitness", C.c_double),
+                ("inlier_rmse", C.c_double), ("n_inliers", C.c_int64), ("n_iterations", C.c_int64),
+                ("n_validated", C.c_int64), ("best_iteration", C.c_int64)]
+
+
+def host_ransac_est_k(est_k, confidence, count, k, ransac_n) -> float:
+    """reg_host_ransac_est_k: the RANSAC stop rule after a replacement (libm on the host; no device)."""
+    return float(load_library().reg_host_ransac_est_k(float(est_k), float(confidence), int(count), int(k), int(ransac_n)))
+
+
 class OctreeOut(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("normals", C.c_void_p), ("covs", C.c_void_p), ("src_idx", C.c_void_p),
                 ("leaf_id", C.c_void_p), ("leaf_depth", C.c_void_p)]
@@ -336,7 +356,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks",
            "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid",
            "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices",
-           "reg_compute_fpfh", "reg_match_features"]
+           "reg_compute_fpfh", "reg_match_features", "reg_ransac_correspondences", "reg_host_ransac_est_k"]
 
 
 def lib_path() -> str:
@@ -421,6 +441,10 @@ def load_library():
     lib.reg_get_source_source_indices.argtypes = [vp, vp]
     lib.reg_compute_fpfh.argtypes = [vp, vp, i64, vp, i64, i64, C.c_int, C.c_int, C.c_float, vp, vp, vp, C.POINTER(C.c_int64)]
     lib.reg_match_features.argtypes = [vp, vp, i64, vp, i64, C.c_int, C.c_int, vp, vp, vp, C.POINTER(C.c_int64)]
+    lib.reg_ransac_correspondences.argtypes = [vp, vp, i64, vp, i64, vp, i64, C.c_int, C.POINTER(RansacParams),
+                                               C.POINTER(RansacResult), vp, vp]
+    lib.reg_host_ransac_est_k.argtypes = [C.c_double, C.c_double, i64, i64, C.c_int32]
+    lib.reg_host_ransac_est_k.restype = C.c_double
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -1044,6 +1068,64 @@ class Registration:
         self._check(self._lib.reg_match_features(self._h, vp(fa_ptr), na, vp(fb_ptr), nb, int(dim), 1, vp(nn_ab_ptr),
                                                  vp(nn_ba_ptr), vp(mutual_ptr), C.byref(km)))
         return int(km.value)
+
+    # ---- RANSAC registration on correspondences ----
+    @staticmethod
+    def _ransac_params(max_correspondence_distance, ransac_n, max_iteration, confidence, distance_threshold,
+                       edge_similarity, seed, batch):
+        p = RansacParams()
+        p.struct_size = C.sizeof(RansacParams)
+        p.ransac_n, p.max_iteration, p.confidence = int(ransac_n), int(max_iteration), float(confidence)
+        p.max_correspondence_distance = float(max_correspondence_distance)
+        p.distance_threshold, p.edge_similarity = float(distance_threshold), float(edge_similarity)
+        p.seed, p.batch = int(seed) & 0xFFFFFFFFFFFFFFFF, int(batch)
+        return p
+
+    @staticmethod
+    def _ransac_out(res, inliers=None, status=None):
+        out = {"T": np.array(res.T, np.float64).reshape(4, 4).T.copy(), "fitness": float(res.fitness),
+               "inlier_rmse": float(res.inlier_rmse), "n_inliers": int(res.n_inliers), "n_iterations": int(res.n_iterations),
+               "n_validated": int(res.n_validated), "best_iteration": int(res.best_iteration), "batch": int(res.batch)}
+        if inliers is not None:
+            out["inliers"] = inliers[:out["n_inliers"]].copy()
+        if status is not None:
+            out["iter_status"] = status
+        return out
+
+    def ransac_correspondences(self, src_xyz, tgt_xyz, corres, max_correspondence_distance, ransac_n=3,
+                               max_iteration=100000, confidence=0.999, distance_threshold=0.0, edge_similarity=0.0, seed=0,
+                               batch=0, want_status=False):
+        """RegistrationRANSACBasedOnCorrespondence on the device (reg_ransac_correspondences): fp64 clouds (n x 3, m x 3),
+        `corres` (k, 2) int32 pairs (source, target).  A checker threshold <= 0 switches that checker off.  Returns a dict:
+        `T` (4 x 4), `fitness`, `inlier_rmse`, `inliers` (count, 2), `n_inliers`, `n_iterations`, `n_validated`,
+        `best_iteration`, `batch` (the device batch size used), and with `want_status` `iter_status` (max_iteration,) int32, filled up to n_iterations (the rest
+        keeps the fill value -9)."""
+        s = np.ascontiguousarray(src_xyz, np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(tgt_xyz, np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(corres, np.int32).reshape(-1, 2)
+        p = self._ransac_params(max_correspondence_distance, ransac_n, max_iteration, confidence, distance_threshold,
+                                edge_similarity, seed, batch)
+        res = RansacResult()
+        res.struct_size = C.sizeof(RansacResult)
+        inl = np.full((max(c.shape[0], 1), 2), -1, np.int32)
+        status = np.full(max(int(max_iteration), 1), -9, np.int32) if want_status else None
+        self._check(self._lib.reg_ransac_correspondences(self._h, _ptr(s), s.shape[0], _ptr(t), t.shape[0], _ptr(c),
+                                                         c.shape[0], 0, C.byref(p), C.byref(res), _ptr(inl), _ptr(status)))
+        return self._ransac_out(res, inl, status)
+
+    def ransac_correspondences_device(self, src_ptr, n, tgt_ptr, m, corres_ptr, k, inliers_ptr, max_correspondence_distance,
+                                      ransac_n=3, max_iteration=100000, confidence=0.999, distance_threshold=0.0,
+                                      edge_similarity=0.0, seed=0, batch=0, iter_status_ptr=None):
+        """As ransac_correspondences with the fp64 clouds, the int32 pairs and the outputs (inliers 2 x k int32,
+        iter_status max_iteration int32) resident in HBM.  Returns the dict without the arrays."""
+        vp = lambda q: C.c_void_p(q) if q else None
+        p = self._ransac_params(max_correspondence_distance, ransac_n, max_iteration, confidence, distance_threshold,
+                                edge_similarity, seed, batch)
+        res = RansacResult()
+        res.struct_size = C.sizeof(RansacResult)
+        self._check(self._lib.reg_ransac_correspondences(self._h, vp(src_ptr), n, vp(tgt_ptr), m, vp(corres_ptr), k, 1,
+                                                         C.byref(p), C.byref(res), vp(inliers_ptr), vp(iter_status_ptr)))
+        return self._ransac_out(res)
 
     def set_source(self, xyz, normals=None, covs=None):
         xyz = _f32(xyz)

@@ -122,6 +122,10 @@ struct reg_handle {
     // reg_compute_fpfh / reg_match_features (host_fpfh.hpp): staged inputs, ordered ids, counts + m, host-pointer outputs, flag
     // words; staged feature rows, per-chunk partial bests, index outputs, mutual flags + offsets
     DevBuf fp_xyz, fp_nrm, fp_ids, fp_cnt, fp_out, fp_misc, mf_a, mf_b, mf_part, mf_nn, mf_flags;
+    // reg_ransac_correspondences (host_ransac.hpp): staged clouds and pairs; gathered pairs + inlier flags, offsets and output;
+    // the batch's hypotheses, statuses and survivor lists; chunk partials; carried state + records, and their host copy
+    DevBuf rs_src, rs_tgt, rs_cor, rs_pairs, rs_batch, rs_part, rs_rec;
+    std::vector<RsRecord> rs_head;
     DevBuf i_xicp;                 // XicpState (R8x first-iteration analysis)
     DevBuf c_in_xyz, c_in_nrm, c_in_cov, c_flags, c_offs, c_xyz, c_nrm, c_cov, c_idx;   // reg_set_target_f64
     DevBuf r_in_xyz, r_in_nrm, r_in_cov, r_xyz, r_nrm, r_cov;                            // reg_set_source_f64
@@ -394,6 +398,7 @@ void reg_destroy(reg_handle* h) {
     for (DevBuf* b : {&h->c_in_xyz, &h->c_in_nrm, &h->c_in_cov, &h->c_flags, &h->c_offs, &h->c_xyz, &h->c_nrm, &h->c_cov, &h->c_idx, &h->v_fout, &h->v_oout, &h->v_oxyz, &h->v_onrm, &h->v_ocov, &h->v_ukeys, &h->v_ustart, &h->d_d2all, &h->r_in_xyz, &h->r_in_nrm, &h->r_in_cov, &h->r_xyz, &h->r_nrm, &h->r_cov}) b->release();
     for (DevBuf* b : {&h->ov_keys[0], &h->ov_keys[1], &h->ov_sorted, &h->ov_ukeys[0], &h->ov_ukeys[1], &h->ov_ucnt[0], &h->ov_ucnt[1], &h->ov_flags[0], &h->ov_flags[1], &h->ov_offs[0], &h->ov_offs[1], &h->ov_misc, &h->ov_sidx, &h->i_info}) b->release();
     for (DevBuf* b : {&h->fp_xyz, &h->fp_nrm, &h->fp_ids, &h->fp_cnt, &h->fp_out, &h->fp_misc, &h->mf_a, &h->mf_b, &h->mf_part, &h->mf_nn, &h->mf_flags}) b->release();
+    for (DevBuf* b : {&h->rs_src, &h->rs_tgt, &h->rs_cor, &h->rs_pairs, &h->rs_batch, &h->rs_part, &h->rs_rec}) b->release();
     h->n_eig.release();
     h->n_cov.release();
     h->n_ids.release();

@@ -52,6 +52,7 @@ using namespace o3dreg;
 #include "kernels_octree.hpp"
 #include "kernels_overlap.hpp"
 #include "kernels_fpfh.hpp"
+#include "kernels_ransac.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_target.hpp"
@@ -65,6 +66,7 @@ using namespace o3dreg;
 #include "host_cloud_filters.hpp"
 #include "host_overlap.hpp"
 #include "host_fpfh.hpp"
+#include "host_ransac.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -15,6 +15,9 @@
   CorrespondencesFromFeatures  <-> the feature-matching front of RegistrationRANSACBasedOnFeatureMatching
                                    (PlaceRecognition.cpp:81-84)
   computeSubmapFeatures        <-> o3d_slam::Submap::computeFeatures (Submap.cpp:255-275)
+  RegistrationRANSACBasedOnCorrespondence / RegistrationRANSACBasedOnFeatureMatching
+                               <-> the Open3D operators of the same names (PlaceRecognition.cpp:78-85)
+  ransacLoopClosure            <-> the RANSAC step of a loop-closure candidate and its size check (PlaceRecognition.cpp:78-91)
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -1473,12 +1476,20 @@ class Feature:
 
 @dataclass
 class PlaceRecognitionParameters:
-    """The fields of o3d_slam::PlaceRecognitionParameters that Submap::computeFeatures reads (Parameters.hpp:121-126)."""
+    """o3d_slam::PlaceRecognitionParameters: the fields Submap::computeFeatures reads (Parameters.hpp:121-126), then the
+    RANSAC fields of PlaceRecognition.cpp:78-91 (Parameters.hpp:127-133)."""
     normalEstimationRadius_: float = 1.0
     featureVoxelSize_: float = 0.5
     featureRadius_: float = 2.5
     featureKnn_: int = 100
     normalKnn_: int = 10
+    ransacNumIter_: int = 1000000
+    ransacProbability_: float = 0.99
+    ransacModelSize_: int = 3
+    ransacMaxCorrespondenceDistance_: float = 0.75
+    correspondenceCheckerDistance_: float = 0.75
+    correspondenceCheckerEdgeLength_: float = 0.5
+    ransacMinCorrespondenceSetSize_: int = 25
 
 
 def _is_int(v) -> bool:
@@ -1575,3 +1586,125 @@ def computeSubmapFeatures(cloud_f64, params: "PlaceRecognitionParameters | None"
     finally:
         reg.close()
     return DataPoints(pts, normals=nrm), Feature(np.ascontiguousarray(out["fpfh"].T))
+
+
+# ---- RANSAC registration on feature correspondences: the hypothesis loop of place recognition (PlaceRecognition.cpp:78-91;
+#      DESIGN.md 5q; PARITY UNPINNED against Open3D 0.15.1) ------------------------------------------------------------------
+@dataclass
+class RANSACConvergenceCriteria:
+    """open3d::pipelines::registration::RANSACConvergenceCriteria."""
+    max_iteration_: int = 100000
+    confidence_: float = 0.999
+
+
+@dataclass
+class CorrespondenceCheckerBasedOnEdgeLength:
+    """The sampled edges of source and target must agree in length within similarity_threshold_ (both ways)."""
+    similarity_threshold_: float = 0.9
+
+
+@dataclass
+class CorrespondenceCheckerBasedOnDistance:
+    """The sampled points must lie within distance_threshold_ of their partners after the fitted transform."""
+    distance_threshold_: float
+
+
+def _is_real(v) -> bool:
+    return isinstance(v, (int, float, np.floating, np.integer)) and not isinstance(v, bool)
+
+
+def _check_ransac_args(max_correspondence_distance, ransac_n, checkers, criteria, seed):
+    """Validates and returns (distance_threshold, edge_similarity) of the checkers (0: absent)."""
+    if not (_is_real(max_correspondence_distance) and math.isfinite(max_correspondence_distance)
+            and max_correspondence_distance > 0):
+        raise InvalidParameter(f"max_correspondence_distance must be finite and > 0, got {max_correspondence_distance!r}")
+    if not (_is_int(ransac_n) and 3 <= ransac_n <= 8):
+        raise InvalidParameter(f"ransac_n must be an integer in [3, 8], got {ransac_n!r}")
+    if not isinstance(criteria, RANSACConvergenceCriteria):
+        raise InvalidParameter("criteria must be a RANSACConvergenceCriteria")
+    if not (_is_int(criteria.max_iteration_) and criteria.max_iteration_ >= 1):
+        raise InvalidParameter(f"max_iteration_ must be an integer >= 1, got {criteria.max_iteration_!r}")
+    if not (_is_real(criteria.confidence_) and 0.0 <= criteria.confidence_ <= 1.0):
+        raise InvalidParameter(f"confidence_ must lie in [0, 1], got {criteria.confidence_!r}")
+    if not (_is_int(seed) and 0 <= seed < 2 ** 64):
+        raise InvalidParameter(f"seed must be an integer in [0, 2^64), got {seed!r}")
+    dist, edge = 0.0, 0.0
+    for c in checkers:
+        if isinstance(c, CorrespondenceCheckerBasedOnDistance):
+            v = c.distance_threshold_
+            if not (_is_real(v) and math.isfinite(v) and v > 0) or dist:
+                raise InvalidParameter(f"one distance checker with a finite distance_threshold_ > 0, got {v!r}")
+            dist = float(v)
+        elif isinstance(c, CorrespondenceCheckerBasedOnEdgeLength):
+            v = c.similarity_threshold_
+            if not (_is_real(v) and 0 < v <= 1) or edge:
+                raise InvalidParameter(f"one edge-length checker with similarity_threshold_ in (0, 1], got {v!r}")
+            edge = float(v)
+        else:
+            raise InvalidModuleType(f"unsupported correspondence checker {type(c).__name__} (CorrespondenceCheckerBasedOnNormal "
+                                    "is not implemented)")
+    return dist, edge
+
+
+def RegistrationRANSACBasedOnCorrespondence(source, target, corres, max_correspondence_distance, ransac_n=3, checkers=(),
+                                            criteria=None, seed=0) -> RegistrationResult:
+    """open3d RegistrationRANSACBasedOnCorrespondence with TransformationEstimationPointToPoint(false) on the device
+    (reg_ransac_correspondences): `corres` (k, 2) integer pairs (source, target) into the fp64 points of the two clouds.
+    Deterministic for a given seed; fewer than ransac_n correspondences, or none that qualifies, give the default result."""
+    criteria = RANSACConvergenceCriteria() if criteria is None else criteria
+    dist, edge = _check_ransac_args(max_correspondence_distance, ransac_n, tuple(checkers), criteria, seed)
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")
+    c = np.asarray(corres)
+    if c.ndim != 2 or c.shape[1] != 2 or not np.issubdtype(c.dtype, np.integer):
+        raise InvalidParameter(f"corres must be k x 2 integers, got shape {c.shape} of {c.dtype}")
+    if c.shape[0] == 0:
+        return RegistrationResult(correspondence_set_=np.zeros((0, 2), np.int32))
+    if c.min() < 0 or c[:, 0].max() >= s.shape[0] or c[:, 1].max() >= t.shape[0]:
+        raise InvalidParameter("corres: an index lies outside its cloud")
+    reg = _feature_handle()
+    try:
+        out = reg.ransac_correspondences(s, t, c, max_correspondence_distance, ransac_n, criteria.max_iteration_,
+                                         criteria.confidence_, dist, edge, seed)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    return RegistrationResult(out["T"], out["fitness"], out["inlier_rmse"], out["inliers"])
+
+
+def RegistrationRANSACBasedOnFeatureMatching(source, target, source_feature, target_feature, mutual_filter,
+                                             max_correspondence_distance, ransac_n=3, checkers=(), criteria=None,
+                                             seed=0) -> RegistrationResult:
+    """open3d RegistrationRANSACBasedOnFeatureMatching: CorrespondencesFromFeatures, then
+    RegistrationRANSACBasedOnCorrespondence -- both on the device."""
+    criteria = RANSACConvergenceCriteria() if criteria is None else criteria
+    _check_ransac_args(max_correspondence_distance, ransac_n, tuple(checkers), criteria, seed)
+    s, t = _xyz64(source, "source"), _xyz64(target, "target")
+    a, b = _feature_rows(source_feature, "source_feature"), _feature_rows(target_feature, "target_feature")
+    if a.shape[0] != s.shape[0] or b.shape[0] != t.shape[0]:
+        raise InvalidParameter(f"one feature column per point: {a.shape[0]} / {s.shape[0]} and {b.shape[0]} / {t.shape[0]}")
+    corres = CorrespondencesFromFeatures(source_feature, target_feature, mutual_filter, ransac_n)
+    return RegistrationRANSACBasedOnCorrespondence(s, t, corres, max_correspondence_distance, ransac_n, checkers, criteria,
+                                                   seed)
+
+
+def ransacLoopClosure(sourceSparse, sourceFeature, targetSparse, targetFeature, params=None, seed=0):
+    """PlaceRecognition.cpp:78-91: RANSAC on mutually matched features with the edge-length and the distance checker, then
+    the size check on the inlier set.  Returns the RegistrationResult, or None when it holds fewer than
+    ransacMinCorrespondenceSetSize_ correspondences (the reference skips that candidate)."""
+    prm = params if params is not None else PlaceRecognitionParameters()
+    if not (_is_int(prm.ransacMinCorrespondenceSetSize_) and prm.ransacMinCorrespondenceSetSize_ >= 0):
+        raise InvalidParameter(f"ransacMinCorrespondenceSetSize_ must be an integer >= 0, got "
+                               f"{prm.ransacMinCorrespondenceSetSize_!r}")
+    for name in ("correspondenceCheckerDistance_", "correspondenceCheckerEdgeLength_"):
+        if not _is_real(getattr(prm, name)):
+            raise InvalidParameter(f"{name} must be a number, got {getattr(prm, name)!r}")
+    result = RegistrationRANSACBasedOnFeatureMatching(
+        sourceSparse, targetSparse, sourceFeature, targetFeature, True, prm.ransacMaxCorrespondenceDistance_,
+        prm.ransacModelSize_,
+        (CorrespondenceCheckerBasedOnEdgeLength(prm.correspondenceCheckerEdgeLength_),
+         CorrespondenceCheckerBasedOnDistance(prm.correspondenceCheckerDistance_)),
+        RANSACConvergenceCriteria(prm.ransacNumIter_, prm.ransacProbability_), seed)
+    if result.correspondence_set_.shape[0] < prm.ransacMinCorrespondenceSetSize_:
+        return None
+    return result
