@@ -110,8 +110,30 @@ enum UpdateMode { kUpdateSelect = 0, kUpdateFused = 1, kUpdateXicpFinish = 2 };
 static void launch_reduce_update(reg_handle* h, UpdateMode mode, const double* rows, int n_rows, XicpState* xs,
                                  const SelectState* sel = nullptr, const float* band = nullptr, float* w = nullptr,
                                  const float* gathered = nullptr, int n_ranks = 0, int rank = 0) {
-    k_reduce_update<<<1, 1024, 0, h->stream>>>(rows, n_rows, h->i_iter.as<IterState>(), h->d_mirror, h->seq, (int)mode, band, w, sel,
-                                               gathered, n_ranks, rank, xs);
+    // one kernel per path (kernels_update.hpp: UpdPath); O3D_UPDATE_GENERIC=1 keeps the select-based iteration and the finish
+    // pass on the kernel that serves every path behind run-time values (A/B, tests/test_gpu_update_paths.py)
+    IterState* it = h->i_iter.as<IterState>();
+    if ((mode == kUpdateSelect || mode == kUpdateXicpFinish) && h->env.update_generic)
+        k_reduce_update_generic<<<1, upd_threads(kUpdGeneric), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, (int)mode, band, w,
+                                                                               sel, gathered, n_ranks, rank, xs);
+    else if (mode == kUpdateSelect)
+        k_reduce_update<<<1, upd_threads(kUpdSelect), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, sel, xs);
+    else if (mode == kUpdateXicpFinish)
+        k_reduce_update_finish<<<1, upd_threads(kUpdFinish), 0, h->stream>>>(it, h->d_mirror, h->seq, xs);
+    else if (gathered)
+        k_reduce_update_gathered<<<1, upd_threads(kUpdGathered), 0, h->stream>>>(it, h->d_mirror, h->seq, w, gathered, n_ranks, rank);
+    else
+        k_reduce_update_fused<<<1, upd_threads(kUpdFused), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, band, w);
+}
+// select-free iteration of the Open3D costs: a new sequence from this GPU's rows of k_linearize_o3d
+static void update_o3d_from_partials(reg_handle* h) {
+    ++h->seq;
+    if (h->env.update_generic)
+        k_reduce_update_o3d_generic<<<1, upd_threads(kUpdGeneric), 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks,
+                                                                                   h->i_iter.as<IterState>(), h->d_mirror, h->seq);
+    else
+        k_reduce_update_o3d<<<1, kUpdO3dThreads, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_iter.as<IterState>(),
+                                                                 h->d_mirror, h->seq);
 }
 // a new sequence from this GPU's rows of k_linearize_* (single GPU)
 static void update_from_partials(reg_handle* h) {

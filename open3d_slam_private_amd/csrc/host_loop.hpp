@@ -241,9 +241,7 @@ static reg_status enqueue_linearize(reg_handle* h, bool want_w, bool limit_from_
             k_linearize_o3d<REG_COST_O3D_P2P><<<h->n_blocks, 256, 0, h->stream>>>(
                 h->s_xyz.as<float4>(), h->n, it, h->i_pos.as<int>(), h->i_d2.as<float>(), h->t_pts.as<float4>(), o, w,
                 h->i_partials.as<double>());
-        ++h->seq;
-        k_reduce_update_o3d<<<1, 1024, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_iter.as<IterState>(),
-                                                       h->d_mirror, h->seq);
+        update_o3d_from_partials(h);
         return REG_OK;
     } else {
         launch_linearize_gicp(h, w);

@@ -197,12 +197,21 @@ O3D_HD inline void jacobi_eig_sym3(double* A, double* V, double* lam) {
     lam[2] = A[8];
 }
 
-// rel_thr: eigenvalues <= rel_thr * max are treated as zero.
-O3D_HD inline int solve_sym6(const double* H, const double* g, double* x, double rel_thr) {
+// Work arrays of the eigen-solvers below.  The plain entry points keep them on the stack; the device passes a block of
+// shared memory instead (jacobi_eig_sym indexes at run time, which puts stack arrays into scratch memory there).
+struct Sym6Work {
     double M[36], V[36], lam[6];
+};
+
+// rel_thr: eigenvalues <= rel_thr * max are treated as zero.  n6 is 6: a caller that passes it as a value the compiler cannot
+// see keeps the loops of the eigen-decomposition rolled.
+O3D_HD inline int solve_sym6_in(const double* H, const double* g, double* x, double rel_thr, Sym6Work& w, int n6 = 6) {
+    double* const M = w.M;
+    double* const V = w.V;
+    double* const lam = w.lam;
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j) M[6 * i + j] = 0.5 * (H[6 * i + j] + H[6 * j + i]);
-    jacobi_eig_sym(6, M, V, lam);
+    jacobi_eig_sym(n6, M, V, lam);
     double lmax = 0;
     for (int k = 0; k < 6; ++k) lmax = fmax(lmax, fabs(lam[k]));
     int rank = 0;
@@ -217,19 +226,34 @@ O3D_HD inline int solve_sym6(const double* H, const double* g, double* x, double
     }
     return rank;
 }
+O3D_HD inline int solve_sym6(const double* H, const double* g, double* x, double rel_thr) {
+    Sym6Work w;
+    return solve_sym6_in(H, g, x, rel_thr, w);
+}
 
+constexpr double kP2plRankThr = 6.0 * 1.1920929e-07;   // size * eps_f32: the fp32 rank threshold of the reference's solver
 O3D_HD inline int solve6_p2pl(const float* A, const float* b, float* x) {
     double H[36], g[6], xd[6];
     for (int i = 0; i < 36; ++i) H[i] = A[i];
     for (int i = 0; i < 6; ++i) g[i] = b[i];
-    const int rank = solve_sym6(H, g, xd, 6.0 * 1.1920929e-07);
+    const int rank = solve_sym6(H, g, xd, kP2plRankThr);
+    for (int i = 0; i < 6; ++i) x[i] = (float)xd[i];
+    return rank;
+}
+// ... with every array in the caller's work area (H, g, xd: 36 + 6 + 6 doubles); n6: see solve_sym6_in
+O3D_HD inline int solve6_p2pl_in(const float* A, const float* b, float* x, double* H, double* g, double* xd, Sym6Work& w, int n6 = 6) {
+    for (int i = 0; i < 36; ++i) H[i] = A[i];
+    for (int i = 0; i < 6; ++i) g[i] = b[i];
+    const int rank = solve_sym6_in(H, g, xd, kP2plRankThr, w, n6);
     for (int i = 0; i < 6; ++i) x[i] = (float)xd[i];
     return rank;
 }
 
 // ---- R8x: X-ICP localizability (ICP.cpp:1580-1591, 2187-2444; PointToPlane.cpp:459-505) --------------------
 // Eigenvectors of a symmetric 3x3 block in DESCENDING eigenvalue order (the order of JacobiSVD's U for a PSD
-// matrix); V[3*r+k] = component r of eigenvector k.
+// matrix); V[3*r+k] = component r of eigenvector k.  kSel: the columns are picked by selects instead of run-time indices
+// (the same values; on the device W then stays in registers instead of scratch memory).
+template <bool kSel = false>
 O3D_HD inline void eig3_desc(const double* S, double* V) {
     double M[9], W[9], l[3];
     for (int i = 0; i < 9; ++i) M[i] = S[i];
@@ -239,13 +263,21 @@ O3D_HD inline void eig3_desc(const double* S, double* V) {
     if (l[o2] > l[o0]) { const int t = o0; o0 = o2; o2 = t; }
     if (l[o2] > l[o1]) { const int t = o1; o1 = o2; o2 = t; }
     for (int r = 0; r < 3; ++r) {
-        V[3 * r + 0] = W[3 * r + o0];
-        V[3 * r + 1] = W[3 * r + o1];
-        V[3 * r + 2] = W[3 * r + o2];
+        if (kSel) {
+            const double w0 = W[3 * r], w1 = W[3 * r + 1], w2 = W[3 * r + 2];
+            V[3 * r + 0] = o0 == 0 ? w0 : (o0 == 1 ? w1 : w2);
+            V[3 * r + 1] = o1 == 0 ? w0 : (o1 == 1 ? w1 : w2);
+            V[3 * r + 2] = o2 == 0 ? w0 : (o2 == 1 ? w1 : w2);
+        } else {
+            V[3 * r + 0] = W[3 * r + o0];
+            V[3 * r + 1] = W[3 * r + o1];
+            V[3 * r + 2] = W[3 * r + o2];
+        }
     }
 }
 
 // rotation (rows/cols 0-2) and translation (3-5) eigenvectors of the fp32 system matrix (row-major 6x6)
+template <bool kSel = false>
 O3D_HD inline void xicp_eigvecs(const float* A, double* Vr, double* Vt) {
     double Sr[9], St[9];
     for (int i = 0; i < 3; ++i)
@@ -253,19 +285,39 @@ O3D_HD inline void xicp_eigvecs(const float* A, double* Vr, double* Vt) {
             Sr[3 * i + j] = 0.5 * ((double)A[6 * i + j] + (double)A[6 * j + i]);
             St[3 * i + j] = 0.5 * ((double)A[6 * (i + 3) + j + 3] + (double)A[6 * (j + 3) + i + 3]);
         }
-    eig3_desc(Sr, Vr);
-    eig3_desc(St, Vt);
+    eig3_desc<kSel>(Sr, Vr);
+    eig3_desc<kSel>(St, Vt);
 }
+
+// Work arrays of the constrained solve (see Sym6Work: the stack for the plain entry points, shared memory on the device),
+// and where the solve finds each of them
+struct XicpWork {
+    double Vr[9], Vt[9], Z[36], xn[6], AZ[36], M[36], V[36], lam[6], g[6], bb[6], y[6];
+};
+struct XicpArrays {
+    double *Vr, *Vt, *Z, *xn, *AZ, *M, *V, *lam, *g, *bb, *y;
+};
 
 // Equality-constrained solve: v_k . x = rhs[k] along the non-localizable eigen-directions (flags[k] == 0).  Null-space form
 // of the reference's (6+c)x(6+c) KKT system: x = N d + Z y with N the constrained eigenvectors, d their right-hand sides,
 // Z the localizable ones and Z^T A Z y = Z^T (b - A N d).  kRhs = false is the constraint value 0 of the optimised method
 // (x = Z (Z^T A Z)^-1 Z^T b; rhs is not read); with kRhs = true an all-zero rhs returns the same bits: N d and A N d are
 // then +0, and adding +0 changes no term (tests/test_xicp_ternary_host.py).
-template <bool kRhs>
-O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* flags, const float* rhs, float* x) {
-    double Vr[9], Vt[9], Z[36], xn[6] = {0, 0, 0, 0, 0, 0};
-    xicp_eigvecs(A, Vr, Vt);
+template <bool kRhs, bool kSel = false>
+O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* flags, const float* rhs, float* x, const XicpArrays& w) {
+    double* const Vr = w.Vr;
+    double* const Vt = w.Vt;
+    double* const Z = w.Z;
+    double* const xn = w.xn;
+    double* const AZ = w.AZ;
+    double* const M = w.M;
+    double* const V = w.V;
+    double* const lam = w.lam;
+    double* const g = w.g;
+    double* const bb = w.bb;
+    double* const y = w.y;
+    for (int i = 0; i < 6; ++i) xn[i] = 0;
+    xicp_eigvecs<kSel>(A, Vr, Vt);
     int m = 0;
     for (int k = 0; k < 3; ++k)
         if (flags[k]) {
@@ -283,7 +335,6 @@ O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* fl
         }
     for (int i = 0; i < 6; ++i) x[i] = kRhs ? (float)xn[i] : 0.f;
     if (m == 0) return 0;
-    double AZ[36], M[36], V[36], lam[6], g[6], bb[6];
     for (int i = 0; i < 6; ++i) {
         bb[i] = (double)b[i];
         if (kRhs) {
@@ -318,7 +369,7 @@ O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* fl
     double lmax = 0;
     for (int k = 0; k < m; ++k) lmax = fmax(lmax, fabs(lam[k]));
     const double thr = lmax * (double)m * 1.1920929e-07;
-    double y[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 6; ++i) y[i] = 0;
     int rank = 0;
     for (int k = 0; k < m; ++k) {
         if (!(fabs(lam[k]) > thr)) continue;
@@ -336,11 +387,19 @@ O3D_HD inline int solve6_xicp_impl(const float* A, const float* b, const int* fl
     return rank;
 }
 O3D_HD inline int solve6_xicp(const float* A, const float* b, const int* flags, float* x) {
-    return solve6_xicp_impl<false>(A, b, flags, nullptr, x);
+    double Vr[9], Vt[9], Z[36], xn[6], AZ[36], M[36], V[36], lam[6], g[6], bb[6], y[6];
+    const XicpArrays w = {Vr, Vt, Z, xn, AZ, M, V, lam, g, bb, y};
+    return solve6_xicp_impl<false>(A, b, flags, nullptr, x, w);
+}
+O3D_HD inline int solve6_xicp_in(const float* A, const float* b, const int* flags, float* x, XicpWork& w) {
+    const XicpArrays a = {w.Vr, w.Vt, w.Z, w.xn, w.AZ, w.M, w.V, w.lam, w.g, w.bb, w.y};
+    return solve6_xicp_impl<false, true>(A, b, flags, nullptr, x, a);
 }
 // ... with right-hand sides on the constraint rows (EqualityConstraints: the constraint values of partial directions)
 O3D_HD inline int solve6_xicp_rhs(const float* A, const float* b, const int* flags, const float* rhs, float* x) {
-    return solve6_xicp_impl<true>(A, b, flags, rhs, x);
+    double Vr[9], Vt[9], Z[36], xn[6], AZ[36], M[36], V[36], lam[6], g[6], bb[6], y[6];
+    const XicpArrays w = {Vr, Vt, Z, xn, AZ, M, V, lam, g, bb, y};
+    return solve6_xicp_impl<true>(A, b, flags, rhs, x, w);
 }
 
 // ---- X-ICP ternary EqualityConstraints (ICP.cpp:1698-2125, 2504-2795; PointToPlane.cpp:459-505, 570-626) ----------
@@ -738,16 +797,20 @@ O3D_HD inline void o3d_x_to_T(const double* x, double* U) {
 
 // Point-to-plane: J^T J x = -J^T r (slots 0-20 packed upper triangle, 21-26).  LDL^T; a rank-deficient system takes the
 // minimum-norm eigen-solve (Open3D's Eigen LDLT returns some solution there: a documented deviation).  Returns the rank.
-O3D_HD inline int o3d_update_p2pl(const double* s, double* U) {
+O3D_HD inline int o3d_update_p2pl_in(const double* s, double* U, Sym6Work& w) {
     double H[36], g[6], x[6];
     int k = 0;
     for (int i = 0; i < 6; ++i)
         for (int j = i; j < 6; ++j) H[6 * i + j] = H[6 * j + i] = s[k++];
     for (int i = 0; i < 6; ++i) g[i] = -s[21 + i];
     int rank = 6;
-    if (!solve_ldlt6(H, g, x, 1e-10)) rank = solve_sym6(H, g, x, 1e-12);
+    if (!solve_ldlt6(H, g, x, 1e-10)) rank = solve_sym6_in(H, g, x, 1e-12, w);
     o3d_x_to_T(x, U);
     return rank;
+}
+O3D_HD inline int o3d_update_p2pl(const double* s, double* U) {
+    Sym6Work w;
+    return o3d_update_p2pl_in(s, U, w);
 }
 
 // Point-to-point: Umeyama without scaling from the sums about the origin o (slots 0-2 sum (p - o), 3-5 sum (q - o),

@@ -44,6 +44,7 @@ struct EnvSwitches {
     bool stamps = false;        // O3D_STAMPS: in-kernel cycle stamps of the update kernel
     bool coh_stats = false;     // O3D_COH_STATS: share of the reading points the coherent fused kernel had to search
     bool tail_always = false;   // O3D_TAIL_ALWAYS: take the persistent tail even while other registrations are in flight on the device (A/B)
+    bool update_generic = false;   // O3D_UPDATE_GENERIC=1: select-based / finish / Open3D updates launch the 1024-thread kernels that serve every path (A/B)
     bool no_tail = false;       // O3D_NO_TAIL: three-launch fused iterations instead of the persistent tail kernel (A/B, escape hatch)
     int tail_wpc = 0;           // O3D_TAIL_WPC: cap on the tail kernel's workgroups per XCD class (0: CUs / 8)
     double dist_timeout_s = 30.0; // O3D_DIST_TIMEOUT_S: deadline of every wait of the distributed path
@@ -84,6 +85,7 @@ struct EnvSwitches {
         coh_stats = getenv("O3D_COH_STATS") != nullptr;
         tail_always = getenv("O3D_TAIL_ALWAYS") != nullptr;
         no_tail = getenv("O3D_NO_TAIL") != nullptr;
+        if (const char* v = getenv("O3D_UPDATE_GENERIC")) update_generic = atoi(v) != 0;
         if (const char* v = getenv("O3D_TAIL_WPC")) tail_wpc = std::max(0, atoi(v));
         if (const char* v = getenv("O3D_DIST_TIMEOUT_S")) dist_timeout_s = std::max(0.5, atof(v));
         if (const char* v = getenv("O3D_TAIL_SETTLE")) tail_settle_tol = (float)atof(v);

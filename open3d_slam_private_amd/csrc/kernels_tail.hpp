@@ -123,8 +123,9 @@ struct TailLds {
     static constexpr int kMisc = kState + kStateBytes;                // 16 words
     static constexpr int kWtot = kMisc + 64;                          // uint32 [16] per-wave totals (band prefix, scans)
     static constexpr int kOff = kWtot + 64;                           // uint32 [257 -> 272] band offsets of the workgroups
-    static constexpr int kX = kOff + 272 * 4;                         // float s_x[8] + pad: scratch of the out-of-line solvers
-    static constexpr int kMirror = kX + 96;                           // HostMirror staging (workgroup 0)
+    static constexpr int kX = kOff + 272 * 4;                         // float s_x[8] + pad: results of the out-of-line solvers,
+    static constexpr int kWork = kX + 96;                             //   UpdWork: their work arrays
+    static constexpr int kMirror = kWork + kUpdWorkBytes;             // HostMirror staging (workgroup 0)
     static constexpr int kMirrorBytes = (int)((sizeof(HostMirror) + 15) & ~size_t(15));
     static constexpr int kHist = kMirror + kMirrorBytes;              // uint32 [kTailBins]
     static constexpr int kTotal = kHist + kTailBins * 4;
@@ -156,9 +157,10 @@ __device__ __forceinline__ unsigned tail_ld_u32(const unsigned* p) {
 
 // R8 + R9 of the tail kernel, wave 0 of every workgroup (identical inputs -> identical poses everywhere): Gauss-Jordan on the
 // augmented 6x7 system, one entry per lane, fp64 (as in k_reduce_update), then x -> dT, T_iter <- dT * T_iter, the next
-// band and the checkers on lane 0.  Out of line: its register needs must not add to the search loop's.
-__device__ __noinline__ void tail_solve_update(IterState* sit, const double* tot, const uint32_t* misc, float* s_x, bool trim,
-                                               unsigned n_band_raw, unsigned n_band_all) {
+// band and the checkers on lane 0.  Out of line: its register needs must not add to the search loop's.  Flattened: with the
+// rare solvers inlined this is a leaf, and only a function that calls another one has to park registers in scratch memory.
+__device__ __noinline__ __attribute__((flatten)) void tail_solve_update(IterState* sit, const double* tot, const uint32_t* misc, float* s_x, UpdWork* work,
+                                               bool trim, unsigned n_band_raw, unsigned n_band_all) {
     const int lane = (int)(threadIdx.x & 63);
     const float r_limit_last = sit->limit_last, r_limit_sel = __uint_as_float(misc[2]);
     const int r_dbg_narrow = sit->debug_narrow_band & 1;
@@ -221,12 +223,12 @@ __device__ __noinline__ void tail_solve_update(IterState* sit, const double* tot
     int rank = 6;
     if (r_xnc > 0) {
         // R8x: no update along the non-localizable eigen-directions of the CURRENT A (PointToPlane.cpp:459-505)
-        rank = upd_solve6_xicp(tot, sit->xicp_flags, s_x);
+        rank = upd_solve6_xicp_inl(tot, sit->xicp_flags, s_x, work);
         for (int i = 0; i < 6; ++i) x[i] = s_x[i];
     } else if (well) {
         for (int i = 0; i < 6; ++i) x[i] = (float)xsol[i];
     } else {
-        rank = upd_solve6_p2pl(tot, s_x);   // ill-conditioned / rank deficient: eigen-solve, minimum norm
+        rank = upd_solve6_p2pl_inl(tot, s_x, work);   // ill-conditioned / rank deficient: eigen-solve, minimum norm
         for (int i = 0; i < 6; ++i) x[i] = s_x[i];
     }
     sit->rank_last = rank;
@@ -239,7 +241,7 @@ __device__ __noinline__ void tail_solve_update(IterState* sit, const double* tot
     if (r_fixed > 0)
         iterate = r_iters + 1 < r_fixed;
     else
-        iterate = sit->chk.check(Tn);
+        iterate = sit->chk.check(sit->T);   // (= Tn, from shared memory: the checker indexes the matrix at run time)
     if (!iterate) sit->done = 1;
 }
 
@@ -332,7 +334,7 @@ __device__ __forceinline__ void tail_gicp_factor(const Xf& T, const float4 s, co
 
 // R8 + R9 of the tail kernel for the GICP cost: the arithmetic of k_reduce_update's GICP branch (fp64 Gauss-Jordan, se(3)
 // exponential, right-multiplied update, the two stop rules), wave 0 of every workgroup.
-__device__ __noinline__ void tail_solve_update_gicp(IterState* sit, const double* tot, double* s_dl) {
+__device__ __noinline__ __attribute__((flatten)) void tail_solve_update_gicp(IterState* sit, const double* tot, double* s_dl, UpdWork* work) {
     const int lane = (int)(threadIdx.x & 63);
     const int r = lane >> 3, c = lane & 7;
     double a = 0.0;
@@ -399,7 +401,7 @@ __device__ __noinline__ void tail_solve_update_gicp(IterState* sit, const double
     if (well) {
         for (int i = 0; i < 6; ++i) dl[i] = xsol[i];
     } else {
-        rank = upd_solve_sym6(tot, s_dl);
+        rank = upd_solve_sym6_inl(tot, s_dl, work);
         for (int i = 0; i < 6; ++i) dl[i] = s_dl[i];
     }
     sit->rank_last = rank;
@@ -459,6 +461,7 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
     uint32_t* const wtot = reinterpret_cast<uint32_t*>(lds + TailLds::kWtot);
     uint32_t* const off = reinterpret_cast<uint32_t*>(lds + TailLds::kOff);
     float* const s_x = reinterpret_cast<float*>(lds + TailLds::kX);
+    UpdWork* const work = reinterpret_cast<UpdWork*>(lds + TailLds::kWork);
     uint32_t* const mir_w = reinterpret_cast<uint32_t*>(lds + TailLds::kMirror);
     uint32_t* const hist = reinterpret_cast<uint32_t*>(lds + TailLds::kHist);
     double* const acc_g = reinterpret_cast<double*>(sync + kTailSyncWords);   // [epoch % 4][XCD class][32], zeroed with the sync words
@@ -1127,9 +1130,9 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
         if (t < kSums) sit->sums[t] = tot[t];
         if (wave == 0) {
             if (kGicp)
-                tail_solve_update_gicp(sit, tot, reinterpret_cast<double*>(s_x));
+                tail_solve_update_gicp(sit, tot, reinterpret_cast<double*>(s_x), work);
             else
-                tail_solve_update(sit, tot, misc, s_x, trim, n_band_raw, wide ? misc[12] : n_band_raw);
+                tail_solve_update(sit, tot, misc, s_x, work, trim, n_band_raw, wide ? misc[12] : n_band_raw);
         }
         __syncthreads();
         TAIL_STAMP(11);   // solve, pose update, checkers

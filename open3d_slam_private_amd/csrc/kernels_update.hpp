@@ -30,10 +30,25 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 // Rare, register-hungry branches of the update kernel's serial section, kept out of line: inlined, their fully
-// unrolled fp64 eigen-solves pushed the kernel (capped at 128 VGPRs by its 1024-thread workgroup) to ~700 spilled
-// registers, and the spill traffic landed on the common path as scratch round trips.  Results go through LDS so
-// that the caller's arrays stay in registers.
-__device__ __noinline__ void upd_load_sym6(const double* tot, float* H, float* b6) {
+// unrolled fp64 eigen-solves pushed the kernel to ~700 spilled registers, and the spill traffic landed on the common
+// path as scratch round trips.  Their arrays live in a block of shared memory the caller passes in (UpdWork): the
+// eigen-solvers index at run time, so stack arrays went to scratch memory -- 1.8 KB per lane, allocated for every
+// lane of the update kernel and of k_tail on behalf of one lane of a rare branch.  Results go to shared memory too.
+struct UpdWork {
+    union {
+        XicpWork xicp;   // upd_solve6_xicp
+        struct {         // upd_solve6_p2pl, upd_solve_sym6; upd_o3d: s alone
+            Sym6Work s;
+            double H[36], g[6], xd[6];
+        } sym;
+    };
+    float H[36], b6[6];
+};
+constexpr int kUpdWorkBytes = (int)((sizeof(UpdWork) + 15) & ~size_t(15));
+
+// (every solver below is flattened into a leaf: a function that calls another one keeps live registers in scratch memory across
+//  the call)
+__device__ __forceinline__ void upd_load_sym6_inl(const double* tot, float* H, float* b6) {
     int k = 0;
     for (int i = 0; i < 6; ++i)
         for (int j = i; j < 6; ++j) {
@@ -43,6 +58,40 @@ __device__ __noinline__ void upd_load_sym6(const double* tot, float* H, float* b
         }
     for (int i = 0; i < 6; ++i) b6[i] = -(float)tot[21 + i];
 }
+__device__ __noinline__ void upd_load_sym6(const double* tot, float* H, float* b6) { upd_load_sym6_inl(tot, H, b6); }
+// The 6 of a 6x6 eigen-decomposition as a value the compiler cannot see: unrolled, its fifteen rotations per sweep need more
+// scalar registers (masks of the nested branches) than a function may use without saving some -- to scratch memory.
+__device__ __forceinline__ int upd_opaque6() {
+    int n = 6;
+    asm volatile("" : "+v"(n));
+    return n;
+}
+// The bodies (inlined into tail_solve_update*, which are out of line themselves) ...
+__device__ __forceinline__ int upd_solve6_xicp_inl(const double* tot, const int* flags, float* x_out, UpdWork* w) {
+    upd_load_sym6_inl(tot, w->H, w->b6);
+    return solve6_xicp_in(w->H, w->b6, flags, x_out, w->xicp);
+}
+__device__ __forceinline__ int upd_solve6_p2pl_inl(const double* tot, float* x_out, UpdWork* w) {
+    upd_load_sym6_inl(tot, w->H, w->b6);
+    return solve6_p2pl_in(w->H, w->b6, x_out, w->sym.H, w->sym.g, w->sym.xd, w->sym.s, upd_opaque6());
+}
+__device__ __forceinline__ int upd_solve_sym6_inl(const double* tot, double* dl_out, UpdWork* w) {
+    double* const Hd = w->sym.H;
+    double* const g = w->sym.g;
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) Hd[6 * i + j] = Hd[6 * j + i] = tot[k++];
+    for (int i = 0; i < 6; ++i) g[i] = -tot[21 + i];
+    return solve_sym6_in(Hd, g, dl_out, 1e-12, w->sym.s, upd_opaque6());
+}
+// ... and the out-of-line functions of the update kernel.  kWg: the workgroup size of the calling kernel.  A device function
+// is compiled once, for the smallest register budget among its callers: one copy per budget keeps the 128-register cap of the
+// 1024-thread kernels (where the constrained solve spills) away from the kernels that have more.
+template <int kWg>
+__device__ __noinline__ __attribute__((flatten)) int upd_solve6_xicp(const double* tot, const int* flags, float* x_out, UpdWork* w) {
+    return upd_solve6_xicp_inl(tot, flags, x_out, w);
+}
+// (stack arrays: the chain's update kernel k_pm_update, one wave)
 __device__ __noinline__ int upd_solve6_xicp(const double* tot, const int* flags, float* x_out) {
     float H[36], b6[6], x[6];
     upd_load_sym6(tot, H, b6);
@@ -50,24 +99,16 @@ __device__ __noinline__ int upd_solve6_xicp(const double* tot, const int* flags,
     for (int i = 0; i < 6; ++i) x_out[i] = x[i];
     return rank;
 }
-__device__ __noinline__ int upd_solve6_p2pl(const double* tot, float* x_out) {
-    float H[36], b6[6], x[6];
-    upd_load_sym6(tot, H, b6);
-    const int rank = solve6_p2pl(H, b6, x);
-    for (int i = 0; i < 6; ++i) x_out[i] = x[i];
-    return rank;
+template <int kWg>
+__device__ __noinline__ __attribute__((flatten)) int upd_solve6_p2pl(const double* tot, float* x_out, UpdWork* w) {
+    return upd_solve6_p2pl_inl(tot, x_out, w);
 }
-__device__ __noinline__ int upd_solve_sym6(const double* tot, double* dl_out) {
-    double Hd[36], g[6], dl[6];
-    int k = 0;
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) Hd[6 * i + j] = Hd[6 * j + i] = tot[k++];
-    for (int i = 0; i < 6; ++i) g[i] = -tot[21 + i];
-    const int rank = solve_sym6(Hd, g, dl, 1e-12);
-    for (int i = 0; i < 6; ++i) dl_out[i] = dl[i];
-    return rank;
+template <int kWg>
+__device__ __noinline__ __attribute__((flatten)) int upd_solve_sym6(const double* tot, double* dl_out, UpdWork* w) {
+    return upd_solve_sym6_inl(tot, dl_out, w);
 }
-// R8x stage A for one 3x3 block (o = 0: rotation, 3: translation) of the system
+// R8x stage A for one 3x3 block (o = 0: rotation, 3: translation) of the system (kSel: see eig3_desc)
+template <bool kSel = false>
 __device__ __noinline__ void upd_xicp_stage_a(const double* tot, const float* Trd, float* dst, int o) {
     double S[9], V[9];
     for (int i = 0; i < 3; ++i)
@@ -75,7 +116,7 @@ __device__ __noinline__ void upd_xicp_stage_a(const double* tot, const float* Tr
             const int lo = (i < j ? i : j) + o, hi = (i < j ? j : i) + o;
             S[3 * i + j] = (double)(float)tot[lo * 6 - (lo * (lo - 1)) / 2 + (hi - lo)];
         }
-    eig3_desc(S, V);
+    eig3_desc<kSel>(S, V);
     for (int kk = 0; kk < 3; ++kk)
         for (int rr = 0; rr < 3; ++rr) {
             const float a0 = Trd[rr] * (float)V[kk], a1 = Trd[4 + rr] * (float)V[3 + kk];
@@ -86,32 +127,50 @@ __device__ __noinline__ void upd_xicp_stage_a(const double* tot, const float* Tr
 }
 
 // Open3D costs (REG_COST_O3D_P2PL / P2P): the update of o3d_update (host_math.hpp) on one lane; results through LDS.
-// One out-of-line function per cost: the point-to-plane eigen-solve fallback indexes its arrays at run time (scratch), and
-// sharing its frame put the Umeyama update's arrays into scratch too.
-template <bool kP2P>
-__device__ __noinline__ int upd_o3d(const double* tot, double* U_out) {
+// One out-of-line function per cost (sharing a frame put the Umeyama update's arrays into scratch) and workgroup size (kWg).
+template <bool kP2P, int kWg>
+__device__ __noinline__ __attribute__((flatten)) int upd_o3d(const double* tot, double* U_out, UpdWork* w) {
     double s[kSums], U[16];
     for (int i = 0; i < kSums; ++i) s[i] = tot[i];
-    const int rank = o3d_update(kP2P, s, U);
+    const int rank = kP2P ? o3d_update_p2p(s, U) : o3d_update_p2pl_in(s, U, w->sym.s);
     for (int i = 0; i < 16; ++i) U_out[i] = U[i];
     return rank;
 }
 
-// The whole kernel, once per update family: kO3d = false is k_reduce_update (P2PL / GICP, every path), kO3d = true is
+// The loop path an instantiation of the kernel serves.  A path known at compile time keeps only its own shared memory
+// and registers: the select-based and finish passes carry none of the band machinery of the fused ones.
+//   kUpdSelect    rows of k_linearize_* -> sums; the trimmed limit comes from the select kernels
+//   kUpdFused     rows + band records of launch_fused_search: band verification, exact quantile inside the band
+//   kUpdGathered  the same from the gathered contribution blocks of all ranks
+//   kUpdFinish    R8x: the sums are already in the state (first-iteration localizability analysis done in between),
+//                 only solve + update
+//   kUpdGeneric   every path behind run-time values (`fused`: 0 select-based, 1 fused, 2 finish; `gathered` != nullptr),
+//                 the kernel as it was before the paths were split: O3D_UPDATE_GENERIC=1 (A/B, tests)
+enum UpdPath { kUpdGeneric = 0, kUpdSelect, kUpdFused, kUpdGathered, kUpdFinish };
+// Threads of an instantiation: the band code ranks, scans and stages with 1024; without it 512 do -- a 256-register budget
+// (the 128 registers of a 1024-thread workgroup spill the serial section's fp64 matrices), and the rows of sums are loaded
+// 16 per thread and round instead of 8, so the number of load rounds stays what it was.  Measured: 512
+// and 1024 threads run the flagship 1 % faster than 256 -- the kernel is latency-bound outside its stamped sections.
+constexpr int kUpdLeanThreads = 512;
+constexpr int upd_threads(UpdPath p) { return (p == kUpdSelect || p == kUpdFinish) ? kUpdLeanThreads : 1024; }
+
+// The whole kernel, once per update family and path: kO3d = false is k_reduce_update* (P2PL / GICP), kO3d = true is
 // k_reduce_update_o3d (select-free iterations of the Open3D costs: left-multiplied fp64 update, Open3D stop rule).  The
 // Open3D branches exist only in their own instantiation, so they cannot cost k_reduce_update registers.
-template <bool kO3d>
+template <bool kO3d, UpdPath kPath>
 __device__ __forceinline__ void reduce_update_body(const double* __restrict__ partials, int n_blocks, IterState* it,
-                                                   HostMirror* host, unsigned long long seq, int fused,
+                                                   HostMirror* host, unsigned long long seq, int fused_arg,
                                                    const float* __restrict__ band, float* __restrict__ w_out,
-                                                   const SelectState* __restrict__ sel, const float* __restrict__ gathered,
+                                                   const SelectState* __restrict__ sel, const float* __restrict__ gathered_arg,
                                                    int n_ranks, int my_rank, XicpState* __restrict__ xs) {
+    constexpr int kThreads = upd_threads(kPath);
+    constexpr bool kBand = kPath == kUpdGeneric || kPath == kUpdFused || kPath == kUpdGathered;   // band code compiled in
+    static_assert(!kBand || kThreads == 1024, "the band code is written for 1024 threads");
+    const bool finish = kPath == kUpdGeneric ? fused_arg == 2 : kPath == kUpdFinish;
+    const int fused = kPath == kUpdGeneric ? (fused_arg == 1 ? 1 : 0) : ((kPath == kUpdFused || kPath == kUpdGathered) ? 1 : 0);
+    const float* __restrict__ const gathered = (kPath == kUpdGeneric || kPath == kUpdGathered) ? gathered_arg : nullptr;
     const int contrib_cap = contrib_cap_for(n_ranks);              // gathered blocks: per-rank record capacity
     const size_t contrib_stride = contrib_floats(contrib_cap);     // floats per rank block
-    // fused: 0 = select-based iteration, 1 = fused iteration (band verification), 2 = R8x finish: the sums are
-    // already in the state (first-iteration localizability analysis done in between), only solve + update
-    const bool finish = fused == 2;
-    if (finish) fused = 0;
     __shared__ double sh[32][kSums];
     __shared__ double tot[kSums];
     __shared__ uint32_t hist[2048 + 64];
@@ -130,6 +189,8 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
     __shared__ int s_skip_mirror;
     __shared__ float s_x[6];     // results of the out-of-line solvers (rare branches of the serial section)
     __shared__ double s_dl[6];
+    __shared__ __attribute__((aligned(16))) unsigned char s_work[kUpdWorkBytes];   // ... and their work arrays
+    UpdWork* const work = reinterpret_cast<UpdWork*>(s_work);
     // The whole iteration state is staged in LDS by one coalesced load (every separate `it->` access below would
     // cost an L2 round trip on a single lane); wave 0 writes the modified copy back at the end.  The accumulator
     // rows do not depend on the state, so their loads are issued in the same batch.
@@ -137,10 +198,37 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
     static_assert(sizeof(IterState) % 4 == 0 && kStateWords <= 1024, "IterState must be a whole number of words");
     __shared__ __attribute__((aligned(16))) uint32_t s_state[kStateWords];
     IterState* const sit = reinterpret_cast<IterState*>(s_state);
-    const int comp = threadIdx.x & (kSums - 1), part = threadIdx.x / kSums;  // 32 parts x 32 comps
-    if (threadIdx.x < kStateWords) s_state[threadIdx.x] = reinterpret_cast<const uint32_t*>(it)[threadIdx.x];
+    // 32 parts x 32 comps; a thread sums kPer consecutive parts (1024 threads: its own one)
+    constexpr int kPer = 1024 / kThreads;
+    static_assert(kPer == 1 || kPer % 2 == 0, "the parts are combined in pairs");
+    const int comp = threadIdx.x & (kSums - 1), part = threadIdx.x / kSums;
+    for (int w = threadIdx.x; w < kStateWords; w += kThreads) s_state[w] = reinterpret_cast<const uint32_t*>(it)[w];
     double t = 0;
-    if (!gathered && !finish) {
+    double tp[kPer];   // kPer > 1: the sums of parts kPer * part + j, each in the order a thread of its own would add them
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) tp[j] = 0;
+    if constexpr (kPer > 1) {
+        if (!finish) {
+            // a round is the 256 rows that 32 parts x eight loads cover: part p takes part in it while r0 + p < n_rows and
+            // adds 0.0 for its rows beyond the end, as its own thread would
+            for (int r0 = 0; r0 < n_blocks; r0 += 32 * 8) {
+                double v[kPer][8];
+#pragma unroll
+                for (int j = 0; j < kPer; ++j)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int b = r0 + kPer * part + j + 32 * u;
+                        v[j][u] = partials[(size_t)(b < n_blocks ? b : 0) * kSums + comp];
+                    }
+#pragma unroll
+                for (int j = 0; j < kPer; ++j)
+                    if (r0 + kPer * part + j < n_blocks) {
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) tp[j] += (r0 + kPer * part + j + 32 * u < n_blocks) ? v[j][u] : 0.0;
+                    }
+            }
+        }
+    } else if (!gathered && !finish) {
         // (eight loads in flight per thread: one after the other, the ~25 rows a part sums at C3 were a chain of 25 L2 / Infinity
         //  Cache round trips -- most of this kernel's 15 us on the select-based path)
         const int n_rows = fused ? kAccRows : n_blocks;
@@ -244,8 +332,13 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
             const_cast<double*>(partials)[(size_t)b * kSums + comp] = 0.0;   // ready for the next iteration
     }
     // 32 parts -> 1: the two parts of a wave by one shuffle, the 16 waves through LDS (fixed order: deterministic)
-    t += __shfl_xor(t, 32);
-    if ((threadIdx.x & 63) < 32) sh[threadIdx.x >> 6][comp] = t;
+    if constexpr (kPer > 1) {
+#pragma unroll
+        for (int j = 0; j < kPer / 2; ++j) sh[(kPer / 2) * part + j][comp] = tp[2 * j] + tp[2 * j + 1];
+    } else {
+        t += __shfl_xor(t, 32);
+        if ((threadIdx.x & 63) < 32) sh[threadIdx.x >> 6][comp] = t;
+    }
     if (threadIdx.x == 0) {
         s_limit = INFINITY;
     }
@@ -260,7 +353,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
     lds_barrier();
     const unsigned long long stA = __builtin_amdgcn_s_memtime();
     unsigned long long stB = stA, stC = stA, sx1 = stA, sx2 = stA, sx3 = stA;
-    if (fused && trim) {
+    if (kBand && fused && trim) {
         // ---- verify the predicted band with exact counts, then select the exact quantile inside it
         const uint32_t n_finite = (uint32_t)llround(tot[29]), n_below = (uint32_t)llround(tot[31]);
         const uint32_t k = trim_rank(n_finite, s_ratio);
@@ -515,7 +608,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
     // the analysis kernels that follow collect the information sums, then this kernel runs again (finish) to decide,
     // solve and update.  Nothing is reported to the host yet.
     const bool stage_a = !finish && r_update != 0 && p2pl && r_xstage == 1 && r_tot28 != 0.0 && xs != nullptr;
-    if (stage_a && lane < 2) upd_xicp_stage_a(tot, sit->xicp_Trd, lane == 0 ? xs->vr : xs->vt, lane == 0 ? 0 : 3);
+    if (stage_a && lane < 2) upd_xicp_stage_a<true>(tot, sit->xicp_Trd, lane == 0 ? xs->vr : xs->vt, lane == 0 ? 0 : 3);
     if (lane == 0) {
         // band for the next iteration from the limits seen so far
         const float limit = finish ? r_limit_last : r_limit_sel;
@@ -566,13 +659,13 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
                 int rank = 6;
                 if (r_xnc > 0) {
                     // R8x: no update along the non-localizable eigen-directions of the CURRENT A (PointToPlane.cpp:459-505)
-                    rank = upd_solve6_xicp(tot, sit->xicp_flags, s_x);
+                    rank = upd_solve6_xicp<kThreads>(tot, sit->xicp_flags, s_x, work);
                     for (int i = 0; i < 6; ++i) x[i] = s_x[i];
                 } else if (well) {
                     for (int i = 0; i < 6; ++i) x[i] = (float)xsol[i];
                 } else {
                     // ill-conditioned / rank deficient: eigen-solve with the fp32 rank threshold (minimum norm)
-                    rank = upd_solve6_p2pl(tot, s_x);
+                    rank = upd_solve6_p2pl<kThreads>(tot, s_x, work);
                     for (int i = 0; i < 6; ++i) x[i] = s_x[i];
                 }
                 sit->rank_last = rank;
@@ -585,7 +678,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
                 if (r_fixed > 0)
                     iterate = r_iters + 1 < r_fixed;
                 else
-                    iterate = sit->chk.check(Tn);
+                    iterate = sit->chk.check(sit->T);   // (= Tn, from shared memory: the checker indexes the matrix at run time)
                 if (!iterate) sit->done = 1;
             } else if ((kO3d || sit->gicp_stop_rule == 1) && sit->fixed_iters <= 0 &&
                        ((sit->iterations >= 1 &&
@@ -610,7 +703,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
                 if constexpr (kO3d) {
                     // Open3D: T <- U T (RegistrationICP: transformation = update * transformation)
                     double* U = &sh[0][0];   // the reduction's staging rows are free by now
-                    rank = sit->cost == REG_COST_O3D_P2P ? upd_o3d<true>(tot, U) : upd_o3d<false>(tot, U);
+                    rank = sit->cost == REG_COST_O3D_P2P ? upd_o3d<true, kThreads>(tot, U, work) : upd_o3d<false, kThreads>(tot, U, work);
                     for (int i = 0; i < 4; ++i)
                         for (int j = 0; j < 4; ++j) {
                             double v = 0;
@@ -624,7 +717,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
                     if (well) {
                         for (int i = 0; i < 6; ++i) dl[i] = xsol[i];
                     } else {
-                        rank = upd_solve_sym6(tot, s_dl);
+                        rank = upd_solve_sym6<kThreads>(tot, s_dl, work);
                         for (int i = 0; i < 6; ++i) dl[i] = s_dl[i];
                     }
                     sit->rank_last = rank;
@@ -721,19 +814,50 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
     }
 }
 
-__global__ void __launch_bounds__(1024)
-k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
-                unsigned long long seq, int fused, const float* __restrict__ band, float* __restrict__ w_out,
-                const SelectState* __restrict__ sel, const float* __restrict__ gathered, int n_ranks, int my_rank,
-                XicpState* __restrict__ xs) {
-    reduce_update_body<false>(partials, n_blocks, it, host, seq, fused, band, w_out, sel, gathered, n_ranks, my_rank, xs);
+// One entry per path (host_launch.hpp: launch_reduce_update picks).  k_reduce_update is the select-based iteration.
+__global__ void __launch_bounds__(upd_threads(kUpdSelect))
+k_reduce_update(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host, unsigned long long seq,
+                const SelectState* __restrict__ sel, XicpState* __restrict__ xs) {
+    reduce_update_body<false, kUpdSelect>(partials, n_blocks, it, host, seq, 0, nullptr, nullptr, sel, nullptr, 0, 0, xs);
+}
+__global__ void __launch_bounds__(upd_threads(kUpdFinish))
+k_reduce_update_finish(IterState* it, HostMirror* host, unsigned long long seq, XicpState* __restrict__ xs) {
+    reduce_update_body<false, kUpdFinish>(nullptr, 0, it, host, seq, 2, nullptr, nullptr, nullptr, nullptr, 0, 0, xs);
+}
+__global__ void __launch_bounds__(upd_threads(kUpdFused))
+k_reduce_update_fused(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
+                      unsigned long long seq, const float* __restrict__ band, float* __restrict__ w_out) {
+    reduce_update_body<false, kUpdFused>(partials, n_blocks, it, host, seq, 1, band, w_out, nullptr, nullptr, 0, 0, nullptr);
+}
+__global__ void __launch_bounds__(upd_threads(kUpdGathered))
+k_reduce_update_gathered(IterState* it, HostMirror* host, unsigned long long seq, float* __restrict__ w_out,
+                         const float* __restrict__ gathered, int n_ranks, int my_rank) {
+    reduce_update_body<false, kUpdGathered>(nullptr, 0, it, host, seq, 1, nullptr, w_out, nullptr, gathered, n_ranks, my_rank,
+                                            nullptr);
+}
+__global__ void __launch_bounds__(upd_threads(kUpdGeneric))
+k_reduce_update_generic(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
+                        unsigned long long seq, int fused, const float* __restrict__ band, float* __restrict__ w_out,
+                        const SelectState* __restrict__ sel, const float* __restrict__ gathered, int n_ranks, int my_rank,
+                        XicpState* __restrict__ xs) {
+    reduce_update_body<false, kUpdGeneric>(partials, n_blocks, it, host, seq, fused, band, w_out, sel, gathered, n_ranks, my_rank,
+                                           xs);
 }
 
-// Select-free iteration of the Open3D costs: sums of k_linearize_o3d -> update, Open3D convergence criteria, mirror.
-__global__ void __launch_bounds__(1024)
+// Select-free iteration of the Open3D costs: sums of k_linearize_o3d -> update, Open3D convergence criteria, mirror.  It is
+// the select-based path of the Open3D body (no band, no select state), hence that path's workgroup size.
+constexpr int kUpdO3dThreads = upd_threads(kUpdSelect);
+__global__ void __launch_bounds__(kUpdO3dThreads)
 k_reduce_update_o3d(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
                     unsigned long long seq) {
-    reduce_update_body<true>(partials, n_blocks, it, host, seq, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr);
+    reduce_update_body<true, kUpdSelect>(partials, n_blocks, it, host, seq, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr);
+}
+
+// ... and as it was before the paths were split (O3D_UPDATE_GENERIC=1): 1024 threads, one part of the row sum per thread
+__global__ void __launch_bounds__(upd_threads(kUpdGeneric))
+k_reduce_update_o3d_generic(const double* __restrict__ partials, int n_blocks, IterState* it, HostMirror* host,
+                            unsigned long long seq) {
+    reduce_update_body<true, kUpdGeneric>(partials, n_blocks, it, host, seq, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr);
 }
 
 // Stream-ordered distributed path: this rank's workgroup partials -> 32 doubles (summed over ranks by the caller's
