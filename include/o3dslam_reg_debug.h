@@ -3,7 +3,7 @@
  *
  * NOT part of the drop-in boundary (include/o3dslam_reg.h): nothing a maintainer of the reference binds to.  Used by
  * the parity tests (forcing the rare branches: band misprediction, histogram select, generic-only path), the A/B
- * scripts under tools/ and bench.py's kernel timing.  All zero in production.
+ * scripts under tools/, bench.py's kernel timing and the lifetime tests (reg_debug_live_resources).  All zero in production.
  */
 #ifndef O3DSLAM_REG_DEBUG_H
 #define O3DSLAM_REG_DEBUG_H
@@ -38,6 +38,11 @@ REG_API reg_status reg_debug_halo_bound(reg_handle* h, const float* xyz, int64_t
  * position outside the halo grid lies in no bin: it gets what the search takes from the border bin it clamps to (that
  * bin's witness, or the first record of its run), -1 without witnesses. */
 REG_API reg_status reg_debug_halo_witness(reg_handle* h, const float* xyz, int64_t n, int32_t* out);
+
+/* HIP resources the library holds in this process, all handles together (tests of the handles' lifetime): out[0] = device
+ * buffers, out[1] = their bytes (as reserved), out[2] = pinned host blocks, out[3] = events + streams the library created.
+ * Counted where a resource is created and where it is destroyed: a handle leaves all four as it found them. */
+REG_API reg_status reg_debug_live_resources(int64_t out[4]);
 
 #ifdef __cplusplus
 }

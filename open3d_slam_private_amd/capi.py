@@ -342,6 +342,7 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_set_target_f64", "reg_get_target_source_indices", "reg_voxelize_within_volume", "reg_carve_indices", "reg_dist_xicp_buffers", "reg_dist_gather_buffers",
            "reg_dist_record", "reg_dist_centroid_sums", "reg_dist_prepare",
            "reg_information_matrix", "reg_set_source_f64", "reg_debug_configure", "reg_debug_halo_bound", "reg_debug_halo_witness",
+           "reg_debug_live_resources",
            "reg_dist_get_unique_id", "reg_dist_init", "reg_dist_init_custom", "reg_dist_register", "reg_dist_shutdown",
            "reg_dist_info", "reg_dist_steer_create", "reg_dist_steer_destroy", "reg_dist_steer_step",
            "reg_dist_steer_counts", "reg_host_tail_plan", "reg_host_o3d_update",
@@ -397,6 +398,7 @@ def load_library():
     lib.reg_debug_configure.argtypes = [vp, C.POINTER(RegDebugParams)]
     lib.reg_debug_halo_bound.argtypes = [vp, f32p, i64, f32p]
     lib.reg_debug_halo_witness.argtypes = [vp, f32p, i64, vp]
+    lib.reg_debug_live_resources.argtypes = [C.POINTER(C.c_int64)]
     lib.reg_dist_get_unique_id.argtypes = [C.c_char_p]
     lib.reg_dist_init.argtypes = [vp, C.c_char_p, C.c_int, C.c_int]
     lib.reg_dist_init_custom.argtypes = [vp, C.POINTER(Collectives), C.c_int, C.c_int]
@@ -518,6 +520,16 @@ def load_library():
         getattr(lib, name)  # AttributeError if the library does not export what the header declares
     _lib = lib
     return lib
+
+
+def live_resources() -> tuple:
+    """reg_debug_live_resources: (device buffers, their bytes, pinned host blocks, events + owned streams) that the library
+    holds in this process, all handles together."""
+    out = (C.c_int64 * 4)()
+    st = load_library().reg_debug_live_resources(out)
+    if st != 0:
+        raise RegError(st)
+    return tuple(out)
 
 
 def default_params() -> RegParams:
@@ -813,12 +825,9 @@ class Registration:
                 self._lib.reg_destroy(self._h)
                 self._h = C.c_void_p()
             raise RegError(st, msg)
-        dbg = RegDebugParams()
-        dbg.struct_size = C.sizeof(RegDebugParams)
-        for k in _DEBUG_FIELDS:
-            setattr(dbg, k, int(getattr(p, k, 0)))
-        if any(getattr(dbg, k) for k in _DEBUG_FIELDS):
-            self._check(self._lib.reg_debug_configure(self._h, C.byref(dbg)))
+        dbg = {k: int(getattr(p, k, 0)) for k in _DEBUG_FIELDS}
+        if any(dbg.values()):
+            self.debug_configure(**dbg)
         self._keep = []
         self.n_source = 0
 
@@ -840,6 +849,16 @@ class Registration:
     def last_error(self) -> str:
         """reg_last_error: the message of the last failing call on this handle."""
         return self._lib.reg_last_error(self._h).decode()
+
+    def debug_configure(self, **switches):
+        """reg_debug_configure: the experiment switches of include/o3dslam_reg_debug.h; those not named are zero."""
+        dbg = RegDebugParams()
+        dbg.struct_size = C.sizeof(RegDebugParams)
+        for k, v in switches.items():
+            if k not in _DEBUG_FIELDS:
+                raise TypeError(f"unknown debug switch {k}")
+            setattr(dbg, k, int(v))
+        self._check(self._lib.reg_debug_configure(self._h, C.byref(dbg)))
 
     def set_stream(self, hip_stream: int):
         self._check(self._lib.reg_set_stream(self._h, C.c_void_p(hip_stream)))

@@ -481,8 +481,8 @@ reg_status reg_profile_kernels(reg_handle* h, const float T_iter[16], int reps, 
     HIPCHK(h, hipSetDevice(h->prm.device));
     s = init_iter_state(h, Tr, 0);
     if (s != REG_OK) return s;
-    hipEvent_t e[4];
-    for (int i = 0; i < 4; ++i) HIPCHK(h, hipEventCreate(&e[i]));
+    Event e[4];   // (every early return below releases them)
+    for (int i = 0; i < 4; ++i) HIPCHK(h, e[i].create());
     double acc[3] = {0, 0, 0};
     const bool trim = h->prm.cost == REG_COST_P2PL && h->prm.use_trimmed;
     for (int r = -1; r < reps; ++r) {  // r == -1: warm-up, not counted
@@ -503,7 +503,6 @@ reg_status reg_profile_kernels(reg_handle* h, const float T_iter[16], int reps, 
         }
     }
     for (int i = 0; i < 3; ++i) ms[i] = (float)(acc[i] / reps);
-    for (int i = 0; i < 4; ++i) (void)hipEventDestroy(e[i]);
     HIPCHK(h, hipGetLastError());
     return REG_OK;
 }

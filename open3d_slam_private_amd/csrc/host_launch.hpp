@@ -5,10 +5,10 @@
 
 static void prof_mark(reg_handle* h, int kind, bool start) {
     if (!h->profiling) return;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return;
+    Event e;
+    if (e.create() != hipSuccess) return;
     (void)hipEventRecord(e, h->stream);
-    h->prof_ev.push_back(e);
+    h->prof_ev.push_back(std::move(e));
     if (start) h->prof_kind.push_back(kind);
 }
 
@@ -17,15 +17,14 @@ static void prof_mark(reg_handle* h, int kind, bool start) {
 // gaps that events recorded around a launch include).  kind < 0: a plain launch whatever the handle profiles.
 template <class K, class... A>
 static void launch_timed(reg_handle* h, int kind, K kernel, dim3 grid, dim3 block, size_t lds, A... args) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (kind < 0 || !h->profiling || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (e0) (void)hipEventDestroy(e0);
+    Event e0, e1;
+    if (kind < 0 || !h->profiling || e0.create() != hipSuccess || e1.create() != hipSuccess) {
         hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, args...);
         return;
     }
     hipExtLaunchKernelGGL(kernel, grid, block, lds, h->stream, e0, e1, 0, args...);
-    h->prof_ev.push_back(e0);
-    h->prof_ev.push_back(e1);
+    h->prof_ev.push_back(std::move(e0));
+    h->prof_ev.push_back(std::move(e1));
     h->prof_kind.push_back(kind);
 }
 
@@ -114,26 +113,26 @@ static void launch_reduce_update(reg_handle* h, UpdateMode mode, const double* r
     // pass on the kernel that serves every path behind run-time values (A/B, tests/test_gpu_update_paths.py)
     IterState* it = h->i_iter.as<IterState>();
     if ((mode == kUpdateSelect || mode == kUpdateXicpFinish) && h->env.update_generic)
-        k_reduce_update_generic<<<1, upd_threads(kUpdGeneric), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, (int)mode, band, w,
+        k_reduce_update_generic<<<1, upd_threads(kUpdGeneric), 0, h->stream>>>(rows, n_rows, it, h->h_mirror.dev, h->seq, (int)mode, band, w,
                                                                                sel, gathered, n_ranks, rank, xs);
     else if (mode == kUpdateSelect)
-        k_reduce_update<<<1, upd_threads(kUpdSelect), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, sel, xs);
+        k_reduce_update<<<1, upd_threads(kUpdSelect), 0, h->stream>>>(rows, n_rows, it, h->h_mirror.dev, h->seq, sel, xs);
     else if (mode == kUpdateXicpFinish)
-        k_reduce_update_finish<<<1, upd_threads(kUpdFinish), 0, h->stream>>>(it, h->d_mirror, h->seq, xs);
+        k_reduce_update_finish<<<1, upd_threads(kUpdFinish), 0, h->stream>>>(it, h->h_mirror.dev, h->seq, xs);
     else if (gathered)
-        k_reduce_update_gathered<<<1, upd_threads(kUpdGathered), 0, h->stream>>>(it, h->d_mirror, h->seq, w, gathered, n_ranks, rank);
+        k_reduce_update_gathered<<<1, upd_threads(kUpdGathered), 0, h->stream>>>(it, h->h_mirror.dev, h->seq, w, gathered, n_ranks, rank);
     else
-        k_reduce_update_fused<<<1, upd_threads(kUpdFused), 0, h->stream>>>(rows, n_rows, it, h->d_mirror, h->seq, band, w);
+        k_reduce_update_fused<<<1, upd_threads(kUpdFused), 0, h->stream>>>(rows, n_rows, it, h->h_mirror.dev, h->seq, band, w);
 }
 // select-free iteration of the Open3D costs: a new sequence from this GPU's rows of k_linearize_o3d
 static void update_o3d_from_partials(reg_handle* h) {
     ++h->seq;
     if (h->env.update_generic)
         k_reduce_update_o3d_generic<<<1, upd_threads(kUpdGeneric), 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks,
-                                                                                   h->i_iter.as<IterState>(), h->d_mirror, h->seq);
+                                                                                   h->i_iter.as<IterState>(), h->h_mirror.dev, h->seq);
     else
         k_reduce_update_o3d<<<1, kUpdO3dThreads, 0, h->stream>>>(h->i_partials.as<double>(), h->n_blocks, h->i_iter.as<IterState>(),
-                                                                 h->d_mirror, h->seq);
+                                                                 h->h_mirror.dev, h->seq);
 }
 // a new sequence from this GPU's rows of k_linearize_* (single GPU)
 static void update_from_partials(reg_handle* h) {

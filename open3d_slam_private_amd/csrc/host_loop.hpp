@@ -79,7 +79,7 @@ static reg_status prepare_rowmajor(reg_handle* h, const float* T_init_row, const
     pa.use_override = c_override ? 1 : 0;
     pa.c_override = c_override ? make_float3(c_override[0], c_override[1], c_override[2]) : make_float3(0.f, 0.f, 0.f);
     pa.out = h->s_prep.as<PrepState>();
-    pa.host_out = h->d_prep_host;
+    pa.host_out = h->h_prep.dev;
     h->prep_pending = true;
     StateInit si;
     si.dst = nullptr;
@@ -395,7 +395,7 @@ static reg_status enqueue_tail(reg_handle* h, const TailPlan& pl, int max_iters)
     auto go = [&](auto kernel) {   // (the weights are always written: reg_get_correspondences reports them)
         launch_timed(h, 3, kernel, dim3(pl.grid), dim3(kTailThreads), kTailLdsBytes, (const float4*)h->s_xyz.as<float4>(), s_attr,
                      h->i_iter.as<IterState>(), h->grid, t_attr, f, h->i_pos.as<int>(), h->i_d2.as<float>(), h->i_w.as<float>(), hint,
-                     h->i_cache.as<float4>(), sync_cur, h->i_tail_rows.as<double>(), h->i_tail_band.as<float>(), h->d_mirror, cfg,
+                     h->i_cache.as<float4>(), sync_cur, h->i_tail_rows.as<double>(), h->i_tail_band.as<float>(), h->h_mirror.dev, cfg,
                      sync_next);
     };
     if (gicp)
@@ -758,7 +758,6 @@ static void loop_end_diagnostics(reg_handle* h, reg_result* res) {
                 res->prof_launches[kind] += 1;
             }
         }
-        for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
         h->prof_ev.clear();
         h->prof_kind.clear();
         h->profiling = false;
@@ -866,6 +865,7 @@ reg_status reg_register(reg_handle* h, const float T_init[16], float T_out[16], 
     if (s != REG_OK) return s;
     rmark("prepared");
     h->profiling = h->dbg.profile_loop != 0;
+    h->prof_ev.clear(), h->prof_kind.clear();   // (left by a profiled registration that failed before it read them)
     const bool event_timing = h->profiling || h->env.event_timing;
     if (event_timing) HIPCHK(h, hipEventRecord(h->ev0, h->stream));
     const auto t_loop_begin = std::chrono::steady_clock::now();

@@ -169,7 +169,7 @@ static reg_status enqueue_pm_iteration(reg_handle* h) {
     auto update = [&](bool extras, int p2p, int finish, XicpState* xicp, XtState* xt, const double* rows) {
         PmExtraState* xstate = extras ? h->pm_xstate.as<PmExtraState>() : nullptr;
         auto go = [&](auto kernel) {
-            kernel<<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->d_mirror, h->seq,
+            kernel<<<1, 256, 0, h->stream>>>(h->pm_partials.as<double>(), lb, h->i_iter.as<IterState>(), h->h_mirror.dev, h->seq,
                                              h->pm_state.as<PmState>(), p2p, cfg.use_trim, cfg.use_median, xc, xstate, finish, xicp,
                                              xt, rows, xt ? nb : 0);
         };

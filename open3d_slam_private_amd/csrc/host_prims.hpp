@@ -1,7 +1,7 @@
 // host_prims.hpp -- host primitives the entry points share: rocPRIM's temporary-storage protocol, scans and sorts on it,
 // the total of a flag array, the crop configuration, staged inputs
-// Part of the single translation unit reg_core.hip (included by host_target.hpp once reg_handle, DevBuf and HIPCHK are
-// complete; not a standalone header).
+// Part of the single translation unit reg_core.hip (included there after host_handle.hpp, which completes reg_handle and
+// HIPCHK, and before host_target.hpp; not a standalone header).
 #pragma once
 
 #define REGCHK(call)                                                                           \

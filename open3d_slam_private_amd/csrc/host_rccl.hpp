@@ -196,8 +196,8 @@ struct DistCtx {
     // per-reading bookkeeping
     unsigned long long src_epoch_seen = ~0ull;
     int64_t n_global = 0, n_max = 0;
-    DevBuf counts;              // n_ranks x int64: every rank's slice size
-    long long* h_count = nullptr;   // pinned: this rank's n (H2D) and the gathered counts (D2H)
+    Pinned<long long> h_count;  // this rank's n (H2D) and the gathered counts (D2H)
+    DevBuf counts;              // n_ranks x int64: every rank's slice size (declared last: freed first, as in reg_handle)
     double timeout_s = 30.0;
     float settle_tol = 0.05f;
     reg_dist_steer last_steer;
@@ -353,7 +353,8 @@ reg_status reg_dist_get_unique_id(char id[REG_DIST_ID_BYTES]) {
     return REG_OK;
 }
 
-static reg_status dist_init_common(reg_handle* h, int rank, int n_ranks, DistCtx** out) {
+// (the caller's unique_ptr frees a context that does not reach h->dist)
+static reg_status dist_init_common(reg_handle* h, int rank, int n_ranks, std::unique_ptr<DistCtx>& d) {
     if (!h || n_ranks < 1 || n_ranks > 64 || rank < 0 || rank >= n_ranks) return REG_BAD_ARGUMENT;
     if (!h->device_ok) return REG_DEVICE_ERROR;
     if (h->dist) {
@@ -361,52 +362,40 @@ static reg_status dist_init_common(reg_handle* h, int rank, int n_ranks, DistCtx
         return REG_BAD_ARGUMENT;
     }
     HIPCHK(h, hipSetDevice(h->prm.device));
-    DistCtx* d = new DistCtx();
+    d.reset(new DistCtx());
     d->n_ranks = n_ranks;
     d->rank = rank;
     std::memset(&d->custom, 0, sizeof(d->custom));
     d->timeout_s = h->env.dist_timeout_s;
     if (const char* v = getenv("O3D_DIST_SETTLE")) d->settle_tol = (float)atof(v);
-    if (hipHostMalloc((void**)&d->h_count, (size_t)(n_ranks + 1) * 8, hipHostMallocDefault) != hipSuccess) {
-        delete d;
-        return dist_fail(h, "hipHostMalloc failed");
-    }
-    *out = d;
+    if (d->h_count.alloc((size_t)(n_ranks + 1) * 8, hipHostMallocDefault) != hipSuccess) return dist_fail(h, "hipHostMalloc failed");
     return REG_OK;
 }
 
 reg_status reg_dist_init(reg_handle* h, const char id[REG_DIST_ID_BYTES], int rank, int n_ranks) {
     if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!id) return REG_BAD_ARGUMENT;
-    DistCtx* d = nullptr;
-    reg_status s = dist_init_common(h, rank, n_ranks, &d);
+    std::unique_ptr<DistCtx> d;
+    reg_status s = dist_init_common(h, rank, n_ranks, d);
     if (s != REG_OK) return s;
-    if (!g_rccl.load()) {
-        (void)hipHostFree(d->h_count);
-        delete d;
-        return dist_fail(h, g_rccl.err);
-    }
+    if (!g_rccl.load()) return dist_fail(h, g_rccl.err);
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof(u));
     const ncclResult_t r = g_rccl.CommInitRank(&d->comm, n_ranks, u, rank);
-    if (r != ncclSuccess) {
-        (void)hipHostFree(d->h_count);
-        delete d;
-        return dist_fail(h, std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "error"));
-    }
+    if (r != ncclSuccess) return dist_fail(h, std::string("ncclCommInitRank: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "error"));
     d->use_rccl = true;
-    h->dist = d;
+    h->dist = d.release();
     return REG_OK;
 }
 
 reg_status reg_dist_init_custom(reg_handle* h, const reg_collectives* c, int rank, int n_ranks) {
     if (h && dist_unsupported(h)) return o3d_dist_unsupported(h);
     if (!c || (n_ranks > 1 && (!c->all_reduce_sum || !c->all_gather))) return REG_BAD_ARGUMENT;
-    DistCtx* d = nullptr;
-    reg_status s = dist_init_common(h, rank, n_ranks, &d);
+    std::unique_ptr<DistCtx> d;
+    reg_status s = dist_init_common(h, rank, n_ranks, d);
     if (s != REG_OK) return s;
     d->custom = *c;
-    h->dist = d;
+    h->dist = d.release();
     return REG_OK;
 }
 
@@ -418,10 +407,8 @@ reg_status reg_dist_shutdown(reg_handle* h) {
     //  rather than destroyed -- ncclCommDestroy would wait for them)
     const bool drained = !h->stream || dist_stream_wait(h, d->timeout_s, "reg_dist_shutdown") == REG_OK;
     if (d->use_rccl && d->comm && drained) (void)g_rccl.CommDestroy(d->comm);
-    if (drained) {
-        d->counts.release();
-        if (d->h_count) (void)hipHostFree(d->h_count);
-    }   // else: hipFree / hipHostFree wait for the device, i.e. for the stuck stream -- the few bytes are abandoned with it
+    // hipFree / hipHostFree wait for the device, i.e. for the stuck stream -- the few bytes are abandoned with it
+    if (!drained) d->counts.abandon(), d->h_count.abandon();
     delete d;
     h->dist = nullptr;
     h->dist_ranks = 0;

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -55,6 +56,9 @@ using namespace o3dreg;
 #include "kernels_ransac.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
+#include "host_mem.hpp"
+#include "host_handle.hpp"
+#include "host_prims.hpp"
 #include "host_target.hpp"
 #include "host_launch.hpp"
 #include "host_loop.hpp"

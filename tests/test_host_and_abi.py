@@ -99,6 +99,20 @@ def test_no_gpu_means_loud_failure_not_fallback():
     assert e.value.status == 8 and "mandatory" in str(e.value)
 
 
+def test_no_gpu_handle_holds_nothing_and_destroys_cleanly():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    lib = capi.load_library()
+    before = capi.live_resources()
+    p, h = capi.default_params(), C.c_void_p()
+    assert lib.reg_create(C.byref(p), C.byref(h)) == 8 and h.value      # REG_DEVICE_ERROR, with a handle that explains
+    assert "mandatory" in lib.reg_last_error(h).decode()
+    assert capi.live_resources() == before
+    lib.reg_destroy(h)
+    assert capi.live_resources() == before
+
+
 def test_reg_create_rejects_bad_parameters():
     lib = capi.load_library()
     p = capi.default_params()
