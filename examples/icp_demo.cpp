@@ -72,6 +72,19 @@ int main() {
         const auto T64 = icp.computeF64(rd64.data(), rdn64.data(), N, false, o3dreg::identity4());
         bool same64 = true;
         for (int k = 0; k < 16; ++k) same64 = same64 && T64[k] == T[k];
+        // the scan front end in one call with every stage switched off (no croppers, no voxel grid, ratio 1, the scan's
+        // own normals): the merge cloud is the scan, the reading is the same fp32 cast, the transform the same again
+        reg_scan_params sp;
+        reg_default_scan_params(&sp);
+        sp.wide.type = sp.narrow.type = REG_CROP_NONE;
+        sp.voxel_size = 0.0;
+        std::vector<double> merge(3 * (size_t)N), mergen(3 * (size_t)N);
+        const reg_scan_result scan = icp.processScan(rd64.data(), rdn64.data(), nullptr, N, false, sp, merge.data(), mergen.data());
+        const auto Ts = icp.registerPair(o3dreg::identity4());
+        bool sameScan = scan.n_merge == N && scan.n_match == N && merge == rd64 && mergen == rdn64;
+        for (int k = 0; k < 16; ++k) sameScan = sameScan && Ts[k] == T[k];
+        std::printf("processScan (pass-through): %s\n", sameScan ? "identical" : "DIFFERENT");
+        same64 = same64 && sameScan;
         // the multi-GPU loop (C++ steering + RCCL collectives) with a group of ONE rank: the same transform again
         icp.joinGroup(o3dreg::ICP::makeGroupId(), 0, 1);
         const auto Tp = icp.computePartitioned(reading, o3dreg::identity4());

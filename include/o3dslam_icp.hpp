@@ -195,6 +195,30 @@ public:
         return idx;
     }
 
+    // ---- the scan front end (ScanToMapRegistration.cpp:36-69) ---------------------------------------------
+    // ScanToMapIcp::processForScanMatchingAndMerging in one call (reg_process_scan): wide crop, VoxelDownSample, normals
+    // where the cloud brings none, RandomDownSample, the merge cloud into the caller's fp64 arrays (n rows each; normals /
+    // covariances may be nullptr), narrow crop + fp32 cast installed as the reading.  Then registerPair(T_init) -- the
+    // reference is the one given to initReference -- and scanMatchIndices().  Empty after a crop: std::runtime_error.
+    reg_scan_result processScan(const double* points, const double* normals, const double* covs, int64_t n, bool on_device,
+                                const reg_scan_params& scanParams, double* mergePoints, double* mergeNormals = nullptr,
+                                double* mergeCovs = nullptr) {
+        ensure();
+        reg_scan_params p = scanParams;
+        p.struct_size = (int32_t)sizeof(reg_scan_params);
+        scan_ = reg_scan_result{};
+        scan_.struct_size = (int32_t)sizeof(reg_scan_result);
+        check(reg_process_scan(h_, points, normals, covs, n, on_device ? 1 : 0, &p, mergePoints, mergeNormals, mergeCovs, &scan_));
+        return scan_;
+    }
+    // rows of the merge cloud that form the reading (match_), ascending
+    std::vector<int32_t> scanMatchIndices() {
+        ensure();
+        std::vector<int32_t> idx((size_t)scan_.n_match);
+        if (!idx.empty()) check(reg_get_source_source_indices(h_, idx.data()));
+        return idx;
+    }
+
     // ---- one process per GPU, reading partitioned over the group (BASELINE config C4) --------------------------------
     // Rank 0 creates the 128-byte id (ICP::makeGroupId) and hands it to the other ranks; every rank joins with its rank.
     static std::array<char, REG_DIST_ID_BYTES> makeGroupId() {
@@ -275,6 +299,7 @@ private:
     reg_handle* h_ = nullptr;
     reg_result last_{};
     PairOverlap pair_{0, 0};
+    reg_scan_result scan_{};
     bool matcherIsInitialized_ = false;
 };
 
@@ -361,6 +386,54 @@ inline std::vector<int32_t> matchFeatures(const double* source, int64_t na, cons
         all[2 * a + 1] = nn[a];
     }
     return all;
+}
+
+// PointCloud::VoxelDownSample / RandomDownSample on the device (contract in o3dslam_reg.h; PARITY UNPINNED
+// against Open3D 0.15.1): Open3D's fp64 arrays in host memory (points / normals n x 3, covs n x 9 doubles; normals and covs
+// may be nullptr).  voxelDownSample: the grid starts at min_bound - voxelSize / 2, averaged normals are not re-normalised,
+// voxels in ascending (z, y, x) index.  randomDownSample: the kept set is a function of (n, ratio, seed) only; `indices`
+// are the ascending kept rows.
+struct SampledCloud {
+    std::vector<double> points, normals, covs;
+    std::vector<int32_t> indices;   // randomDownSample only
+    int64_t size() const { return (int64_t)(points.size() / 3); }
+};
+inline SampledCloud voxelDownSample(const double* points, const double* normals, const double* covs, int64_t n,
+                                    double voxelSize, int device = 0) {
+    const size_t rows = (size_t)(n > 0 ? n : 0);
+    SampledCloud out;
+    out.points.resize(rows * 3);
+    if (normals) out.normals.resize(rows * 3);
+    if (covs) out.covs.resize(rows * 9);
+    int64_t k = 0;
+    withFeatureHandle(device, [&](reg_handle* h) {
+        return reg_voxel_down_sample(h, points, normals, covs, n, 0, voxelSize, out.points.data(),
+                                     normals ? out.normals.data() : nullptr, covs ? out.covs.data() : nullptr, &k);
+    });
+    out.points.resize((size_t)k * 3);
+    if (normals) out.normals.resize((size_t)k * 3);
+    if (covs) out.covs.resize((size_t)k * 9);
+    return out;
+}
+inline SampledCloud randomDownSample(const double* points, const double* normals, const double* covs, int64_t n,
+                                     double ratio, uint64_t seed = 0, int device = 0) {
+    const size_t rows = (size_t)(n > 0 ? n : 0);
+    SampledCloud out;
+    out.indices.resize(rows);
+    if (points) out.points.resize(rows * 3);
+    if (normals) out.normals.resize(rows * 3);
+    if (covs) out.covs.resize(rows * 9);
+    int64_t k = 0;
+    withFeatureHandle(device, [&](reg_handle* h) {
+        return reg_random_down_sample(h, points, normals, covs, n, 0, ratio, seed, out.indices.data(),
+                                      points ? out.points.data() : nullptr, normals ? out.normals.data() : nullptr,
+                                      covs ? out.covs.data() : nullptr, &k);
+    });
+    out.indices.resize((size_t)k);
+    if (points) out.points.resize((size_t)k * 3);
+    if (normals) out.normals.resize((size_t)k * 3);
+    if (covs) out.covs.resize((size_t)k * 9);
+    return out;
 }
 
 // RegistrationRANSACBasedOnCorrespondence with TransformationEstimationPointToPoint(false), the edge-length and the

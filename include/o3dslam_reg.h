@@ -948,6 +948,91 @@ REG_API reg_status reg_ransac_correspondences(reg_handle* h, const double* src_x
 /* The stop rule above, host-only: est_k after a replacement by a hypothesis with `count` inliers of k. */
 REG_API double reg_host_ransac_est_k(double est_k, double confidence, int64_t count, int64_t k, int32_t ransac_n);
 
+/* ---- the scan front end: VoxelDownSample, RandomDownSample, processForScanMatchingAndMerging ----------
+   ScanToMapIcp::processForScanMatchingAndMerging (open3d_slam/src/ScanToMapRegistration.cpp:36-69, called at
+   Mapper.cpp:186,287; LidarOdometry::preprocess, Odometry.cpp:22-27, runs the same chain): wide crop, VoxelDownSample,
+   estimateNormalsOrCovariancesIfNeeded, RandomDownSample, narrow crop, open3dToPointmatcher.  Open3D 0.15.1 is not in the
+   reference tree: PARITY UNPINNED; the contracts below are this project's own, restated from Open3D's published semantics
+   and the tree's own copy of the accumulator (helpers.cpp:30-72).
+   Clouds are Open3D's fp64 arrays: points_ / normals_ n x 3, covariances_ n x 9 doubles; normals and covs may be NULL;
+   on_device covers every array of a call, outputs included.  fp64, one rounding per operation, no contraction.
+
+   reg_voxel_down_sample == PointCloud::VoxelDownSample(voxel_size).
+     origin, per axis: min_bound - 0.5*voxel_size, min_bound the exact fp64 minimum over the points.
+     voxel index, per axis: floor((p - origin) / voxel_size) -- a true division -- non-negative, 21 bits per axis.
+     one output point per occupied voxel, sums in double in ascending input index: points averaged; a normal with a NaN
+       component is skipped while its point still counts, the averaged normal is sum / count and NOT re-normalised
+       (Open3D's GetAverageNormal; reg_voxelize_within_volume re-normalises, as voxelizeWithinCroppingVolume does);
+       covariances averaged.
+     output order: ascending (z, y, x) voxel index (Open3D emits std::unordered_map order; as reg_voxelize_within_volume).
+     voxel_size <= 0 or non-finite: REG_BAD_ARGUMENT (Open3D raises); a non-finite coordinate or an index >= 2^21:
+     REG_BAD_ARGUMENT; n == 0: REG_OK with *n_out = 0.  The output arrays hold n rows. */
+REG_API reg_status reg_voxel_down_sample(reg_handle* h, const double* xyz, const double* normals, const double* covs,
+                                         int64_t n, int on_device, double voxel_size, double* out_xyz, double* out_normals,
+                                         double* out_covs, int64_t* n_out);
+/* reg_random_down_sample == PointCloud::RandomDownSample(ratio) under a determinism contract (Open3D shuffles with an
+   mt19937 seeded from std::random_device and keeps the first (int)(ratio n) indices; deviation: counter based, as
+   reg_ransac_correspondences).
+     count = (int64)(ratio * (double)n): the fp64 product, truncated.
+     key(i) = the 64-bit z of the sampler of reg_ransac_correspondences for ctr = i and `seed`, before its range reduction
+       (reg_host_scan_key).
+     kept: the count smallest (key, index) pairs, emitted in ascending index order with their normals and covariances.
+   The result is a function of (n, ratio, seed) only.  ratio == 1 copies through; ratio outside [0, 1] or non-finite:
+   REG_BAD_ARGUMENT.  out_idx (int32, ascending, may be NULL) and the out arrays hold count rows; xyz may be NULL when
+   only the indices are wanted. */
+REG_API reg_status reg_random_down_sample(reg_handle* h, const double* xyz, const double* normals, const double* covs,
+                                          int64_t n, int on_device, double ratio, uint64_t seed, int32_t* out_idx,
+                                          double* out_xyz, double* out_normals, double* out_covs, int64_t* n_out);
+/* key(i) above, on the host: the same code as the device. */
+REG_API uint64_t reg_host_scan_key(uint64_t seed, uint64_t index);
+
+/* reg_process_scan: the whole front end in one call, on the device throughout, in the reference's order:
+     1. wide crop (mapBuilderCropper_), order-preserving;
+     2. reg_voxel_down_sample (voxel_size <= 0 skips the stage, helpers.cpp:108-111);
+     3. a cloud without normals and normal_knn > 0: reg_estimate_normals on the fp32 cast of the voxelised cloud with
+        k = normal_knn, max_dist = (float)normal_radius, the viewpoint at the origin; the normals are widened to fp64; a
+        REG_COST_GICP handle also takes the regularise = 1 covariances of the same pass (unless the cloud brings its own).
+        A cloud that arrives with normals skips the stage (CloudRegistration.cpp:27,64);
+     4. reg_random_down_sample with `seed` (skipped when down_sampling_ratio >= 1, helpers.cpp:100-103);
+     5. the result is the merge cloud (merge_): written to merge_xyz / merge_normals / merge_covs (n rows each; the two
+        latter may be NULL), so that reg_carve_indices and reg_voxelize_within_volume can take device pointers directly;
+     6. narrow crop (scanMatcherCropper_ at the identity pose) of the merge cloud, cast per coordinate as
+        reg_set_source_f64 casts, installed as the handle's reading (match_ + open3dToPointmatcher);
+        reg_get_source_source_indices then maps reading rows to merge-cloud rows.
+   Statuses: REG_BAD_ARGUMENT for a bad struct_size, crop type, non-finite voxel_size, ratio < 0 or non-finite, normal_knn
+   outside [0, 32], normal_radius <= 0 with normal_knn > 0; REG_EMPTY_SOURCE for an empty cloud or one that is empty after
+   the wide or the narrow crop (the reference asserts, ScanToMapRegistration.cpp:66-67) -- no reading is set;
+   REG_MISSING_FIELD when the handle's cost needs normals / covariances that the cloud neither brings nor gets estimated
+   (normal_knn == 0), GICP with given normals and no covariances included.  Every failure leaves the handle without reading. */
+typedef struct {
+    int32_t  struct_size;          /* = sizeof(reg_scan_params); checked */
+    int32_t  reserved;
+    reg_crop wide;                 /* mapBuilderCropper_ */
+    reg_crop narrow;               /* scanMatcherCropper_ at the identity pose */
+    double   voxel_size;           /* scanProcessing_.voxelSize_; <= 0 skips the stage */
+    double   down_sampling_ratio;  /* scanProcessing_.downSamplingRatio_; >= 1 skips the stage */
+    uint64_t seed;
+    int32_t  normal_knn;           /* icp_.knn_; 0: no estimation */
+    int32_t  reserved2;
+    double   normal_radius;        /* icp_.maxDistanceKnn_ */
+} reg_scan_params;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_scan_result), set by the caller */
+    int32_t has_normals;           /* the merge cloud carries normals (given or estimated) */
+    int32_t has_covs;
+    float   scan_prep_ms;          /* the whole call on the handle's stream (HIP events), uploads and read-backs included */
+    int64_t n_wide;                /* points after the wide crop */
+    int64_t n_voxels;              /* ... after the voxel grid */
+    int64_t n_merge;               /* ... after the random selection: rows of the merge cloud */
+    int64_t n_match;               /* rows of the reading */
+} reg_scan_result;
+/* param/default/parameter_structure_definitions.lua as shipped: MinMaxRadius 2 / 100 for both croppers, voxel 0.01,
+   ratio 1, knn 20 within 1 m; seed 0. */
+REG_API void reg_default_scan_params(reg_scan_params* p);
+REG_API reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* normals, const double* covs, int64_t n,
+                                    int on_device, const reg_scan_params* params, double* merge_xyz, double* merge_normals,
+                                    double* merge_covs, reg_scan_result* result);
+
 /* Introspection of the search structure (tests, DESIGN.md numbers). */
 typedef struct {
     int64_t n_points;

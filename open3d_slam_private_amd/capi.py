@@ -267,6 +267,39 @@ class RansacResult(C.Structure):
                 ("n_validated", C.c_int64), ("best_iteration", C.c_int64)]
 
 
+class ScanParams(C.Structure):
+    """reg_scan_params (include/o3dslam_reg.h): the scan front end's croppers, voxel size, ratio, seed and normal search."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("wide", RegCrop), ("narrow", RegCrop),
+                ("voxel_size", C.c_double), ("down_sampling_ratio", C.c_double), ("seed", C.c_uint64),
+                ("normal_knn", C.c_int32), ("reserved2", C.c_int32), ("normal_radius", C.c_double)]
+
+
+class ScanResult(C.Structure):
+    """reg_scan_result (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("has_covs", C.c_int32),
+                ("scan_prep_ms", C.c_float), ("n_wide", C.c_int64), ("n_voxels", C.c_int64), ("n_merge", C.c_int64),
+                ("n_match", C.c_int64)]
+
+
+def host_scan_key(seed: int, index: int) -> int:
+    """reg_host_scan_key: the 64-bit key of reg_random_down_sample for point `index` (no device)."""
+    return int(load_library().reg_host_scan_key(int(seed), int(index)))
+
+
+def default_scan_params(**overrides) -> ScanParams:
+    """reg_default_scan_params; wide / narrow accept the crop dicts of Registration.set_target_f64."""
+    p = ScanParams()
+    load_library().reg_default_scan_params(C.byref(p))
+    for k, v in overrides.items():
+        if k in ("wide", "narrow"):
+            v = Registration._crop_struct(v if v is not None else {"type": CROP_NONE})
+        elif not hasattr(p, k):
+            raise TypeError(f"unknown scan parameter {k}")
+        setattr(p, k, v)
+    p.struct_size = C.sizeof(ScanParams)
+    return p
+
+
 def host_ransac_est_k(est_k, confidence, count, k, ransac_n) -> float:
     """reg_host_ransac_est_k: the RANSAC stop rule after a replacement (libm on the host; no device)."""
     return float(load_library().reg_host_ransac_est_k(float(est_k), float(confidence), int(count), int(k), int(ransac_n)))
@@ -357,7 +390,9 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_octree_params", "reg_octree_grid", "reg_host_octree_root", "reg_host_octree_random_picks",
            "reg_filter_cloud", "reg_host_glibc_rand", "reg_default_voxel_grid_params", "reg_voxel_grid",
            "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices",
-           "reg_compute_fpfh", "reg_match_features", "reg_ransac_correspondences", "reg_host_ransac_est_k"]
+           "reg_compute_fpfh", "reg_match_features", "reg_ransac_correspondences", "reg_host_ransac_est_k",
+           "reg_voxel_down_sample", "reg_random_down_sample", "reg_host_scan_key", "reg_default_scan_params",
+           "reg_process_scan"]
 
 
 def lib_path() -> str:
@@ -447,6 +482,14 @@ def load_library():
                                                C.POINTER(RansacResult), vp, vp]
     lib.reg_host_ransac_est_k.argtypes = [C.c_double, C.c_double, i64, i64, C.c_int32]
     lib.reg_host_ransac_est_k.restype = C.c_double
+    lib.reg_voxel_down_sample.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_double, vp, vp, vp, C.POINTER(C.c_int64)]
+    lib.reg_random_down_sample.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_double, C.c_uint64, vp, vp, vp, vp,
+                                           C.POINTER(C.c_int64)]
+    lib.reg_host_scan_key.argtypes = [C.c_uint64, C.c_uint64]
+    lib.reg_host_scan_key.restype = C.c_uint64
+    lib.reg_default_scan_params.argtypes = [C.POINTER(ScanParams)]
+    lib.reg_default_scan_params.restype = None
+    lib.reg_process_scan.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.POINTER(ScanParams), vp, vp, vp, C.POINTER(ScanResult)]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -969,6 +1012,89 @@ class Registration:
                                                 C.byref(c) if c is not None else None, float(voxel_size), float(max_ray),
                                                 float(truncation), float(min_dot), vp(removed_ptr), C.byref(n)))
         return int(n.value)
+
+    # ---- the scan front end ----
+    def voxel_down_sample(self, xyz, voxel_size, normals=None, covs=None):
+        """PointCloud::VoxelDownSample on the device.  Returns (xyz, normals, covs): one averaged row per occupied voxel,
+        in ascending (z, y, x) voxel index; averaged normals are not re-normalised."""
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        n = x.shape[0]
+        nr = np.ascontiguousarray(normals, np.float64).reshape(-1, 3) if normals is not None else None
+        cv = np.ascontiguousarray(covs, np.float64).reshape(-1, 9) if covs is not None else None
+        ox = np.empty((n, 3), np.float64)
+        on = np.empty((n, 3), np.float64) if nr is not None else None
+        oc = np.empty((n, 9), np.float64) if cv is not None else None
+        n_out = C.c_int64(0)
+        self._check(self._lib.reg_voxel_down_sample(self._h, _ptr(x), _ptr(nr), _ptr(cv), n, 0, float(voxel_size), _ptr(ox),
+                                                    _ptr(on), _ptr(oc), C.byref(n_out)))
+        k = int(n_out.value)
+        return ox[:k], (on[:k] if on is not None else None), (oc[:k] if oc is not None else None)
+
+    def voxel_down_sample_device(self, xyz_ptr, n, voxel_size, out_xyz_ptr, nrm_ptr=None, cov_ptr=None, out_nrm_ptr=None,
+                                 out_cov_ptr=None):
+        """As voxel_down_sample with the fp64 cloud and the fp64 outputs (n rows each) resident in HBM.  Returns n_out."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        n_out = C.c_int64(0)
+        self._check(self._lib.reg_voxel_down_sample(self._h, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), n, 1, float(voxel_size),
+                                                    vp(out_xyz_ptr), vp(out_nrm_ptr), vp(out_cov_ptr), C.byref(n_out)))
+        return int(n_out.value)
+
+    def random_down_sample(self, n, ratio, seed=0, xyz=None, normals=None, covs=None):
+        """PointCloud::RandomDownSample under the determinism contract of the header.  Returns (idx, xyz, normals, covs):
+        the ascending kept indices among `n` points and the kept rows of the arrays that were given."""
+        f64 = lambda a, w: np.ascontiguousarray(a, np.float64).reshape(-1, w) if a is not None else None
+        x, nr, cv = f64(xyz, 3), f64(normals, 3), f64(covs, 9)
+        n = int(n)
+        out = [np.empty((n, w), np.float64) if a is not None else None for a, w in ((x, 3), (nr, 3), (cv, 9))]
+        idx = np.empty(max(n, 1), np.int32)
+        n_out = C.c_int64(0)
+        self._check(self._lib.reg_random_down_sample(self._h, _ptr(x), _ptr(nr), _ptr(cv), n, 0, float(ratio), int(seed),
+                                                     _ptr(idx), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), C.byref(n_out)))
+        k = int(n_out.value)
+        return (idx[:k].copy(),) + tuple(a[:k] if a is not None else None for a in out)
+
+    def random_down_sample_device(self, n, ratio, seed, idx_ptr, xyz_ptr=None, nrm_ptr=None, cov_ptr=None, out_xyz_ptr=None,
+                                  out_nrm_ptr=None, out_cov_ptr=None):
+        """As random_down_sample with the int32 index output and the fp64 arrays resident in HBM.  Returns n_out."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        n_out = C.c_int64(0)
+        self._check(self._lib.reg_random_down_sample(self._h, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), n, 1, float(ratio),
+                                                     int(seed), vp(idx_ptr), vp(out_xyz_ptr), vp(out_nrm_ptr),
+                                                     vp(out_cov_ptr), C.byref(n_out)))
+        return int(n_out.value)
+
+    def process_scan(self, xyz, params: "ScanParams", normals=None, covs=None):
+        """processForScanMatchingAndMerging (ScanToMapRegistration.cpp:57-69) on the device: returns (merge_xyz,
+        merge_normals, merge_covs, result) and leaves the narrow-cropped match cloud installed as the reading;
+        source_source_indices() maps its rows to merge-cloud rows.  A failing status raises; `last_scan` keeps the counts."""
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        n = x.shape[0]
+        nr = np.ascontiguousarray(normals, np.float64).reshape(-1, 3) if normals is not None else None
+        cv = np.ascontiguousarray(covs, np.float64).reshape(-1, 9) if covs is not None else None
+        ox, on, oc = np.empty((n, 3), np.float64), np.empty((n, 3), np.float64), np.empty((n, 9), np.float64)
+        res = self._process_scan(_ptr(x), _ptr(nr), _ptr(cv), n, 0, params, _ptr(ox), _ptr(on), _ptr(oc))
+        k = int(res.n_merge)
+        return ox[:k], (on[:k] if res.has_normals else None), (oc[:k] if res.has_covs else None), res
+
+    def process_scan_device(self, xyz_ptr, n, params: "ScanParams", merge_xyz_ptr, nrm_ptr=None, cov_ptr=None,
+                            merge_nrm_ptr=None, merge_cov_ptr=None):
+        """As process_scan with the fp64 scan and the fp64 merge-cloud outputs (n rows each) resident in HBM.  Returns the
+        ScanResult."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._process_scan(vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), n, 1, params, vp(merge_xyz_ptr), vp(merge_nrm_ptr),
+                                  vp(merge_cov_ptr))
+
+    def _process_scan(self, x, nr, cv, n, on_device, params, ox, on, oc):
+        params.struct_size = C.sizeof(ScanParams)
+        res = ScanResult()
+        res.struct_size = C.sizeof(ScanResult)
+        st = self._lib.reg_process_scan(self._h, x, nr, cv, n, on_device, C.byref(params), ox, on, oc, C.byref(res))
+        self.last_scan = res
+        # n_source_kept sizes source_source_indices(), as after set_pair_overlap_f64
+        self.n_source_kept = int(res.n_match) if st == 0 else 0
+        self.n_source = self.n_source_kept
+        self._check(st)
+        return res
 
     def target_source_indices(self):
         idx = np.empty(self.n_target_kept, np.int32)

@@ -92,6 +92,7 @@ struct reg_handle {
     // pinned blocks stand ahead of every DevBuf, so the device buffers go first, then pinned blocks, events, the stream.
     Stream stream;
     Event ev0, ev1, ev_iter, ev_s0, ev_s1;
+    Event ev_p0, ev_p1;   // reg_process_scan's stage time; created by its first call
     // loop profiling (params.profile_loop): HIP events around the search kernels of every iteration
     std::vector<Event> prof_ev;   // pairs (start, stop)
     Pinned<HostMirror> h_mirror;   // mapped: written by the update kernel through h_mirror.dev
@@ -118,7 +119,13 @@ struct reg_handle {
     // unique keys + counts, flags + offsets; run counts and the invalid-key word; the reading's index map
     DevBuf ov_keys[2], ov_sorted, ov_ukeys[2], ov_ucnt[2], ov_flags[2], ov_offs[2], ov_misc, ov_sidx;
     DevBuf i_info;                                   // reg_information_matrix: one row of sums per workgroup
-    int64_t src_kept = 0;                            // > 0: ov_sidx maps the current reading back (reg_set_pair_overlap_f64)
+    int64_t src_kept = 0;                            // > 0: ov_sidx maps the current reading back (reg_set_pair_overlap_f64,
+                                                     // reg_process_scan)
+    // the scan front end (host_scanprep.hpp): staged inputs; the cloud after the wide crop, after the voxel grid, after the
+    // random selection (xyz, normals, covs each); the fp32 cast and the estimated fp32 normals / covariances; sort keys and
+    // values, flags + offsets, kept indices, min-bound rows + origin, the invalid-key word; the events of scan_prep_ms
+    DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_keys, sp_keys2, sp_vals, sp_vals2, sp_flags, sp_offs, sp_idx,
+        sp_part, sp_misc;
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;

@@ -195,7 +195,7 @@ reg_status reg_get_source_source_indices(reg_handle* h, int32_t* idx) {
     if (!h || !idx) return REG_BAD_ARGUMENT;
     if (!h->device_ok) return REG_DEVICE_ERROR;
     if (h->src_kept <= 0 || h->src_kept != h->n) {
-        h->err = "the current reading was not set through reg_set_pair_overlap_f64";
+        h->err = "the current reading was not set through reg_set_pair_overlap_f64 or reg_process_scan";
         return REG_NOT_CONFIGURED;
     }
     HIPCHK(h, hipSetDevice(h->prm.device));

@@ -557,8 +557,8 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
         REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n_in));
         uint32_t lv[2];
         REGCHK(flag_total_async(h, heads, vox, n_in, lv));
-        k_vox_reduce<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), h->t_vals2.as<uint32_t>(), n_in, heads, vox,
-                                                            d_xyz, d_nrm, d_cov, n_outs, d_oxyz, d_onrm, d_ocov);
+        k_vox_reduce<true><<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), h->t_vals2.as<uint32_t>(), n_in, heads,
+                                                                  vox, d_xyz, d_nrm, d_cov, n_outs, d_oxyz, d_onrm, d_ocov);
         HIPCHK(h, hipStreamSynchronize(h->stream));
         n_vox = flag_total(lv);
     }

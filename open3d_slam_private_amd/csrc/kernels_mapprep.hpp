@@ -121,7 +121,10 @@ __global__ void k_vox_heads(const uint64_t* __restrict__ keys, int64_t n, uint32
     flags[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 // one thread per voxel head: sequential sums in double over the voxel's points, which the stable sort left in
-// ascending index order (= the insertion order of the reference's accumulator)
+// ascending index order (= the insertion order of the reference's accumulator).  kRenormalise: the averaged normal is
+// re-normalised (voxelizeWithinCroppingVolume, helpers.cpp:56-63) or left as sum / count (Open3D's GetAverageNormal,
+// reg_voxel_down_sample); a compile-time switch, so that each form is the straight-line code it would be alone
+template <bool kRenormalise>
 __global__ void k_vox_reduce(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, int64_t n,
                              const uint32_t* __restrict__ heads, const uint32_t* __restrict__ vox_id,
                              const double* __restrict__ xyz, const double* __restrict__ nrm, const double* __restrict__ cov,
@@ -158,7 +161,7 @@ __global__ void k_vox_reduce(const uint64_t* __restrict__ keys, const uint32_t* 
         double z2 = u + v;
         u = a[2] * a[2];
         z2 = z2 + u;
-        if (z2 > 0.0) {   // Eigen normalized(): the zero vector stays zero
+        if (kRenormalise && z2 > 0.0) {   // Eigen normalized(): the zero vector stays zero
             const double r = sqrt(z2);
             a[0] = a[0] / r;
             a[1] = a[1] / r;

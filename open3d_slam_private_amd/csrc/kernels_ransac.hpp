@@ -36,11 +36,17 @@ struct RsState {
 };
 static_assert(sizeof(RsState) == 128, "the records start one unit after the state");
 
-__device__ __forceinline__ int64_t rs_draw(uint64_t seed, uint64_t ctr, int64_t K) {
+// The counter-based mixer of the contract (splitmix64's output for counter ctr of the stream `seed`), all mod 2^64; shared
+// with the keys of reg_random_down_sample (kernels_scanprep.hpp) and with the host (reg_host_scan_key)
+__host__ __device__ __forceinline__ uint64_t splitmix_key(uint64_t seed, uint64_t ctr) {
     uint64_t z = seed + (ctr + 1ull) * 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
+    return z;
+}
+__device__ __forceinline__ int64_t rs_draw(uint64_t seed, uint64_t ctr, int64_t K) {
+    const uint64_t z = splitmix_key(seed, ctr);
     return (int64_t)(((z >> 32) * (uint64_t)K) >> 32);
 }
 

@@ -1588,6 +1588,156 @@ def computeSubmapFeatures(cloud_f64, params: "PlaceRecognitionParameters | None"
     return DataPoints(pts, normals=nrm), Feature(np.ascontiguousarray(out["fpfh"].T))
 
 
+# ---- the scan front end: VoxelDownSample, RandomDownSample, processForScanMatchingAndMerging (ScanToMapRegistration.cpp:36-69;
+#      DESIGN.md 5r; PARITY UNPINNED against Open3D 0.15.1) ------------------------------------------------------------------
+@dataclass
+class PointCloud:
+    """The fields of open3d::geometry::PointCloud the front end touches: points_ / normals_ n x 3, covariances_ n x 9
+    (row-major Matrix3d), all float64."""
+    points_: np.ndarray
+    normals_: np.ndarray | None = None
+    covariances_: np.ndarray | None = None
+
+    def HasNormals(self) -> bool:
+        return self.normals_ is not None
+
+    def HasCovariances(self) -> bool:
+        return self.covariances_ is not None
+
+
+@dataclass
+class ProcessedScans:
+    """o3d_slam::ProcessedScans (ScanToMapRegistration.hpp): the narrow-cropped cloud that is matched, the wide one that is merged."""
+    match_: PointCloud
+    merge_: PointCloud
+
+
+def _cloud64(cloud, what="cloud") -> PointCloud:
+    """PointCloud, DataPoints (covariances N x 6) or a bare N x 3 array -> validated contiguous float64 arrays."""
+    if isinstance(cloud, PointCloud):
+        x = np.asarray(cloud.points_)
+        if x.ndim != 2 or x.shape[1] != 3:
+            raise InvalidParameter(f"{what}: points_ must be N x 3, got shape {x.shape}")
+        x = np.ascontiguousarray(x, np.float64)
+        cv = cloud.covariances_
+        if cv is not None:
+            cv = np.asarray(cv)
+            if cv.shape == (x.shape[0], 3, 3):
+                cv = cv.reshape(-1, 9)
+        return PointCloud(x, _field64(cloud.normals_, x.shape[0], 3, f"{what}: normals_"),
+                          _field64(cv, x.shape[0], 9, f"{what}: covariances_"))
+    if isinstance(cloud, DataPoints):
+        x = _xyz64(cloud, what)
+        return PointCloud(x, _field64(cloud.normals, x.shape[0], 3, f"{what}: normals"),
+                          _covs9(_field64(cloud.covariances, x.shape[0], 6, f"{what}: covariances")))
+    return PointCloud(_xyz64(cloud, what))
+
+
+def _check_voxel_size(voxel_size):
+    if not (_is_real(voxel_size) and math.isfinite(voxel_size) and voxel_size > 0):
+        raise InvalidParameter(f"voxel_size must be finite and > 0, got {voxel_size!r}")   # Open3D: "voxel_size <= 0."
+
+
+def _check_ratio_seed(ratio, seed):
+    if not (_is_real(ratio) and 0.0 <= ratio <= 1.0):
+        raise InvalidParameter(f"sampling_ratio must lie in [0, 1], got {ratio!r}")
+    if not (_is_int(seed) and 0 <= seed < 2 ** 64):
+        raise InvalidParameter(f"seed must be an integer in [0, 2^64), got {seed!r}")
+
+
+def VoxelDownSample(cloud, voxel_size) -> PointCloud:
+    """PointCloud::VoxelDownSample(voxel_size) on the device (reg_voxel_down_sample): the grid starts at min_bound -
+    voxel_size / 2, averaged normals are not re-normalised.  Deviation: the voxels come in ascending (z, y, x) index order,
+    where Open3D emits them in hash-map order."""
+    _check_voxel_size(voxel_size)
+    c = _cloud64(cloud)
+    reg = _feature_handle()
+    try:
+        return PointCloud(*reg.voxel_down_sample(c.points_, voxel_size, c.normals_, c.covariances_))
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+
+
+def RandomDownSample(cloud, sampling_ratio, seed=0) -> PointCloud:
+    """PointCloud::RandomDownSample(sampling_ratio) on the device (reg_random_down_sample).  Deviation: Open3D seeds an
+    mt19937 from std::random_device; here the kept set is a function of (n, sampling_ratio, seed) only."""
+    _check_ratio_seed(sampling_ratio, seed)
+    c = _cloud64(cloud)
+    reg = _feature_handle()
+    try:
+        _, x, nr, cv = reg.random_down_sample(c.points_.shape[0], sampling_ratio, seed, c.points_, c.normals_, c.covariances_)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        reg.close()
+    return PointCloud(x, nr, cv)
+
+
+class ScanToMapIcp:
+    """o3d_slam::ScanToMapIcp's scan side (ScanToMapRegistration.cpp:25-69) on one handle: processForScanMatchingAndMerging
+    runs the whole front end on the device (reg_process_scan) and leaves match_ installed as the reading of `icp`'s handle,
+    so that register() -- or any entry point that uses the current reading -- follows without an upload.
+    `icp`: a configured ICP / PointMatcherICP (default: ICP with the shipped parameters); the croppers are the crop dicts of
+    capi.Registration.set_target_f64 (None: no cropping); knn_ 0 turns the normal estimation off."""
+
+    def __init__(self, icp: "ICP | None" = None, *, mapBuilderCropper=None, scanMatcherCropper=None, voxelSize_=0.01,
+                 downSamplingRatio_=1.0, knn_=20, maxDistanceKnn_=1.0, seed=0):
+        if icp is None:
+            icp = ICP()
+            icp.params = capi.shipped_params()
+        self.icp = icp
+        self.mapBuilderCropper, self.scanMatcherCropper = mapBuilderCropper, scanMatcherCropper
+        self.voxelSize_, self.downSamplingRatio_ = voxelSize_, downSamplingRatio_
+        self.knn_, self.maxDistanceKnn_, self.seed = knn_, maxDistanceKnn_, seed
+        self.last_scan = None
+
+    def _check(self):
+        if not (_is_real(self.voxelSize_) and math.isfinite(self.voxelSize_)):     # <= 0 skips the stage (helpers.cpp:108-111)
+            raise InvalidParameter(f"voxelSize_ must be finite, got {self.voxelSize_!r}")
+        if not (_is_real(self.downSamplingRatio_) and math.isfinite(self.downSamplingRatio_) and self.downSamplingRatio_ >= 0):
+            raise InvalidParameter(f"downSamplingRatio_ must be finite and >= 0, got {self.downSamplingRatio_!r}")
+        _check_ratio_seed(0.0, self.seed)
+        if not (_is_int(self.knn_) and 0 <= self.knn_ <= 32):
+            raise InvalidParameter(f"knn_ must be an integer in [0, 32], got {self.knn_!r}")
+        if self.knn_ > 0 and not (_is_real(self.maxDistanceKnn_) and self.maxDistanceKnn_ > 0):
+            raise InvalidParameter(f"maxDistanceKnn_ must be > 0, got {self.maxDistanceKnn_!r}")   # assert_gt
+        for name in ("mapBuilderCropper", "scanMatcherCropper"):
+            crop = getattr(self, name)
+            if crop is not None and not (isinstance(crop, dict) and crop.get("type", 0) in (0, 1, 2, 3, 4)):
+                raise InvalidParameter(f"{name} must be a crop dict with a known type, got {crop!r}")
+
+    def processForScanMatchingAndMerging(self, cloud) -> ProcessedScans:
+        self._check()
+        c = _cloud64(cloud, "scan")
+        if c.points_.shape[0] == 0:
+            raise RuntimeError("The reading point cloud is empty.")
+        self.icp._ensure()
+        prm = capi.default_scan_params(wide=self.mapBuilderCropper, narrow=self.scanMatcherCropper,
+                                       voxel_size=float(self.voxelSize_), down_sampling_ratio=float(self.downSamplingRatio_),
+                                       seed=int(self.seed), normal_knn=int(self.knn_),
+                                       normal_radius=float(self.maxDistanceKnn_) if self.knn_ > 0 else 1.0)
+        reg = self.icp._reg
+        try:
+            x, nr, cv, res = reg.process_scan(c.points_, prm, c.normals_, c.covariances_)
+            idx = reg.source_source_indices()
+        except RegError as e:
+            raise _translate(e) from None
+        self.last_scan = res
+        pick = lambda a: a[idx] if a is not None else None
+        return ProcessedScans(PointCloud(x[idx], pick(nr), pick(cv)), PointCloud(x, nr, cv))
+
+    def register(self, T_init=None):
+        """ICP::compute on the reading processForScanMatchingAndMerging left on the handle: (T, result)."""
+        try:
+            T, res = self.icp._reg.register(np.eye(4, dtype=np.float32) if T_init is None else T_init)
+        except RegError as e:
+            raise _translate(e) from None
+        self.icp.last_result = res
+        return T, res
+
+
 # ---- RANSAC registration on feature correspondences: the hypothesis loop of place recognition (PlaceRecognition.cpp:78-91;
 #      DESIGN.md 5q; PARITY UNPINNED against Open3D 0.15.1) ------------------------------------------------------------------
 @dataclass
