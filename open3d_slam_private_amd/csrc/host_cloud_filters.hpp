@@ -188,33 +188,19 @@ reg_status reg_filter_cloud(reg_handle* h, const float* xyz, int64_t xyz_stride,
         reg_status st = pf_compact(h, idx, idx2, flag, pos, m);
         if (st != REG_OK) return st;
     }
-    // outputs: the caller's device pointers, else one staging buffer (xyz, every returned field, idx)
-    const size_t rows = (size_t)std::max(m, 1);
-    float* ox = out_xyz;
-    int32_t* oi = out_idx;
-    float* of[REG_MAX_FIELDS] = {nullptr};
-    for (int f = 0; f < n_fields; ++f) of[f] = (present[f] && fields[f].out) ? fields[f].out : nullptr;
-    if (!on_device) {
-        HIPCHK(h, h->f_out.reserve(rows * (3 + 1 + off[n_fields]) * 4));
-        float* stage = h->f_out.as<float>();
-        ox = stage;
-        oi = oi ? (int32_t*)(stage + rows * 3) : nullptr;
-        for (int f = 0; f < n_fields; ++f)
-            if (of[f]) of[f] = stage + rows * (4 + off[f]);
-    }
+    // outputs: xyz, idx, then every field that exists at the end of the chain (slot s_f0 + f)
+    StagedOut so(h, h->f_out, on_device);
+    const int s_xyz = so.add(out_xyz, 3), s_idx = so.add(out_idx, 1), s_f0 = s_idx + 1;
+    for (int f = 0; f < n_fields; ++f) so.add(present[f] ? fields[f].out : nullptr, (size_t)fields[f].span);
+    HIPCHK(h, so.reserve((size_t)m));
     if (m > 0) {
-        k_pf_gather<<<grid_for(m), 256, 0, s>>>(px, nullptr, nullptr, idx, m, ox, nullptr, nullptr, oi);
+        k_pf_gather<<<grid_for(m), 256, 0, s>>>(px, nullptr, nullptr, idx, m, so.at<float>(s_xyz), nullptr, nullptr,
+                                                so.at<int32_t>(s_idx));
         for (int f = 0; f < n_fields; ++f)
-            if (of[f])
-                k_fc_gather<<<grid_for((int64_t)m * fields[f].span), 256, 0, s>>>(field_ws(f), fields[f].span, idx, m, of[f]);
+            if (float* of = so.at<float>(s_f0 + f))
+                k_fc_gather<<<grid_for((int64_t)m * fields[f].span), 256, 0, s>>>(field_ws(f), fields[f].span, idx, m, of);
     }
-    if (!on_device && m > 0) {
-        HIPCHK(h, hipMemcpyAsync(out_xyz, ox, (size_t)m * 12, hipMemcpyDeviceToHost, s));
-        if (oi) HIPCHK(h, hipMemcpyAsync(out_idx, oi, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-        for (int f = 0; f < n_fields; ++f)
-            if (of[f])
-                HIPCHK(h, hipMemcpyAsync(fields[f].out, of[f], (size_t)m * fields[f].span * 4, hipMemcpyDeviceToHost, s));
-    }
+    HIPCHK(h, so.copy_back((size_t)m));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     *n_out = m;
@@ -263,18 +249,9 @@ reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, i
     HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
-    const uint32_t misc0[10] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->f_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, s));
     float* px = h->f_px.as<float>();
-    uint32_t* misc = h->f_misc.as<uint32_t>();
-    k_ssn_pack<<<grid_for(N), 256, 0, s>>>(d_in, xyz_stride, N, px, misc);
     uint32_t box[7];
-    HIPCHK(h, hipMemcpyAsync(box, misc, sizeof(box), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (box[6]) {
-        h->err = "reg_voxel_grid: non-finite input";
-        return REG_BAD_ARGUMENT;
-    }
+    REGCHK(pack_cloud_box(h, "reg_voxel_grid", d_in, xyz_stride, N, px, box));
     VoxelGridDev g{};
     unsigned __int128 total = 1;
     uint64_t nd[3];
@@ -331,32 +308,19 @@ reg_status reg_voxel_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, i
             fin[f] = w;
         }
     }
-    const size_t rows = (size_t)m;
-    float* ox = out_xyz;
-    int32_t* oi = out_idx;
-    float* of[REG_MAX_FIELDS] = {nullptr};
-    for (int f = 0; f < n_fields; ++f) of[f] = fields[f].out;
-    if (!on_device) {
-        HIPCHK(h, h->f_out.reserve(rows * (3 + 1 + off[n_fields]) * 4));
-        float* stage = h->f_out.as<float>();
-        ox = stage;
-        oi = oi ? (int32_t*)(stage + rows * 3) : nullptr;
-        for (int f = 0; f < n_fields; ++f)
-            if (of[f]) of[f] = stage + rows * (4 + off[f]);
-    }
-    k_vg_reduce<<<grid_for((int64_t)N * 3), 256, 0, s>>>(px, 3, 3, keys_s, idx, pos, N, 1, ox, oi);
+    StagedOut so(h, h->f_out, on_device);   // xyz, idx, then field f in slot s_f0 + f
+    const int s_xyz = so.add(out_xyz, 3), s_idx = so.add(out_idx, 1), s_f0 = s_idx + 1;
+    for (int f = 0; f < n_fields; ++f) so.add(fields[f].out, (size_t)fields[f].span);
+    HIPCHK(h, so.reserve((size_t)m));
+    k_vg_reduce<<<grid_for((int64_t)N * 3), 256, 0, s>>>(px, 3, 3, keys_s, idx, pos, N, 1, so.at<float>(s_xyz),
+                                                         so.at<int32_t>(s_idx));
     for (int f = 0; f < n_fields; ++f)
-        if (of[f])
+        if (float* of = so.at<float>(s_f0 + f))
             k_vg_reduce<<<grid_for((int64_t)N * fields[f].span), 256, 0, s>>>(fin[f], fields[f].span, fields[f].span, keys_s,
                                                                              idx, pos, N,
-                                                                             p->average_existing_descriptors ? 1 : 0,
-                                                                             of[f], nullptr);
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(out_xyz, ox, rows * 12, hipMemcpyDeviceToHost, s));
-        if (oi) HIPCHK(h, hipMemcpyAsync(out_idx, oi, rows * 4, hipMemcpyDeviceToHost, s));
-        for (int f = 0; f < n_fields; ++f)
-            if (of[f]) HIPCHK(h, hipMemcpyAsync(fields[f].out, of[f], rows * fields[f].span * 4, hipMemcpyDeviceToHost, s));
-    }
+                                                                             p->average_existing_descriptors ? 1 : 0, of,
+                                                                             nullptr);
+    HIPCHK(h, so.copy_back((size_t)m));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     *n_out = m;

@@ -156,19 +156,10 @@ reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t 
     HIPCHK(h, staged_input(h, h->f_in, xyz, (size_t)(N - 1) * (size_t)xyz_stride + 3, on_device, &d_in));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
-    // misc: [0..2] min, [3..5] max (orderable keys), [6] non-finite flag, [8..9] n_unfit (64-bit)
-    const uint32_t misc0[10] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->f_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, s));
     float* px = h->f_px.as<float>();
-    uint32_t* misc = h->f_misc.as<uint32_t>();
-    k_ssn_pack<<<grid_for(N), 256, 0, s>>>(d_in, xyz_stride, N, px, misc);
-    uint32_t bad = 0;
-    HIPCHK(h, hipMemcpyAsync(&bad, misc + 6, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (bad) {
-        h->err = "reg_sampling_surface_normal: non-finite input";
-        return REG_BAD_ARGUMENT;
-    }
+    uint32_t* misc = h->f_misc.as<uint32_t>();   // pack_cloud_box's words, then [8..9] n_unfit (64-bit)
+    uint32_t box[7];
+    REGCHK(pack_cloud_box(h, "reg_sampling_surface_normal", d_in, xyz_stride, N, px, box));
     SsnPlan P;
     ssn_plan(N, knn, P);
     const int n_leaves = (int)P.leaf_begin.size() - 1;
@@ -222,39 +213,23 @@ reg_status reg_sampling_surface_normal(reg_handle* h, const float* xyz, int64_t 
     HIPCHK(h, hipMemcpyAsync(&unfit, misc + 8, 8, hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipStreamSynchronize(s));
     const int M = (int)flag_total(tail);
-    // outputs: the caller's device pointers, else one staging buffer (rows of every array)
-    const size_t rows = (size_t)std::max(M, 1);
-    float *o_xyz = out->xyz, *o_nrm = out->normals, *o_den = out->densities, *o_eva = out->eigvals, *o_eve = out->eigvecs;
-    int32_t* o_src = out->src_idx;
-    HIPCHK(h, h->f_out.reserve(rows * (3 + 3 + 1 + 3 + 9 + 1) * 4));
-    float* stage = h->f_out.as<float>();
-    if (!on_device) {
-        o_xyz = stage;
-        o_nrm = out->normals ? stage + rows * 3 : nullptr;
-        o_den = out->densities ? stage + rows * 6 : nullptr;
-        o_eva = out->eigvals ? stage + rows * 7 : nullptr;
-        o_eve = out->eigvecs ? stage + rows * 10 : nullptr;
-    }
-    if (!on_device || !o_src) o_src = (int32_t*)(stage + rows * 19);
-    HIPCHK(h, h->f_mom2.reserve(rows * sizeof(PcaMoments)));
+    // outputs: k_ssn_scatter always writes src_idx, k_pca_finish always writes normals
+    StagedOut so(h, h->f_out, on_device);
+    const int s_xyz = so.add(out->xyz, 3), s_nrm = so.add(out->normals, 3, out->eigvals || out->eigvecs),
+              s_den = so.add(out->densities, 1), s_eva = so.add(out->eigvals, 3), s_eve = so.add(out->eigvecs, 9),
+              s_src = so.add(out->src_idx, 1, true);
+    HIPCHK(h, so.reserve((size_t)M));
+    HIPCHK(h, h->f_mom2.reserve((size_t)std::max(M, 1) * sizeof(PcaMoments)));
     if (M > 0) {
-        k_ssn_scatter<<<grid_for(N), 256, 0, s>>>(px, N, method, keep, pos, d_lid, h->f_mom.as<PcaMoments>(), o_xyz, o_src,
-                                                  o_den, h->f_mom2.as<PcaMoments>());
-        if (o_nrm || o_eva || o_eve) {
-            float* nrm_dst = o_nrm ? o_nrm : stage + rows * 3;   // k_pca_finish always writes normals
-            k_pca_finish<<<grid_for(M), 256, 0, s>>>(h->f_mom2.as<PcaMoments>(), M, 0.f, 0.f, 0.f, 0, 0, nrm_dst, o_eva,
-                                                     nullptr, o_eve, nullptr, nullptr);
-        }
+        k_ssn_scatter<<<grid_for(N), 256, 0, s>>>(px, N, method, keep, pos, d_lid, h->f_mom.as<PcaMoments>(),
+                                                  so.at<float>(s_xyz), so.at<int32_t>(s_src), so.at<float>(s_den),
+                                                  h->f_mom2.as<PcaMoments>());
+        if (so.at<float>(s_nrm))
+            k_pca_finish<<<grid_for(M), 256, 0, s>>>(h->f_mom2.as<PcaMoments>(), M, 0.f, 0.f, 0.f, 0, 0, so.at<float>(s_nrm),
+                                                     so.at<float>(s_eva), nullptr, so.at<float>(s_eve), nullptr, nullptr);
     }
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(out->xyz, o_xyz, (size_t)M * 12, hipMemcpyDeviceToHost, s));
-        if (out->normals) HIPCHK(h, hipMemcpyAsync(out->normals, o_nrm, (size_t)M * 12, hipMemcpyDeviceToHost, s));
-        if (out->densities) HIPCHK(h, hipMemcpyAsync(out->densities, o_den, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-        if (out->eigvals) HIPCHK(h, hipMemcpyAsync(out->eigvals, o_eva, (size_t)M * 12, hipMemcpyDeviceToHost, s));
-        if (out->eigvecs) HIPCHK(h, hipMemcpyAsync(out->eigvecs, o_eve, (size_t)M * 36, hipMemcpyDeviceToHost, s));
-        if (out->src_idx) HIPCHK(h, hipMemcpyAsync(out->src_idx, o_src, (size_t)M * 4, hipMemcpyDeviceToHost, s));
-        if (out->leaf_id) HIPCHK(h, hipMemcpyAsync(out->leaf_id, d_lid, (size_t)N * 4, hipMemcpyDeviceToHost, s));
-    }
+    HIPCHK(h, so.copy_back((size_t)M));
+    HIPCHK(h, copy_out(h, out->leaf_id, d_lid, (size_t)N * 4, on_device));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     *n_out = M;
@@ -310,24 +285,14 @@ reg_status reg_filter_points(reg_handle* h, const float* xyz, int64_t xyz_stride
         st = pf_compact(h, idx, idx2, flag, pos, m);
         if (st != REG_OK) return st;
     }
-    float *ox = out_xyz, *on = nrm ? out_nrm : nullptr, *oc = cov ? out_cov : nullptr;
-    int32_t* oi = out_idx;
-    if (!on_device) {
-        const size_t rows = (size_t)std::max(m, 1);
-        HIPCHK(h, h->f_out.reserve(rows * (3 + 3 + 6 + 1) * 4));
-        float* stage = h->f_out.as<float>();
-        ox = stage;
-        on = on ? stage + rows * 3 : nullptr;
-        oc = oc ? stage + rows * 6 : nullptr;
-        oi = oi ? (int32_t*)(stage + rows * 12) : nullptr;
-    }
-    if (m > 0) k_pf_gather<<<grid_for(m), 256, 0, s>>>(px, pn, pc, idx, m, ox, on, oc, oi);
-    if (!on_device && m > 0) {
-        HIPCHK(h, hipMemcpyAsync(out_xyz, ox, (size_t)m * 12, hipMemcpyDeviceToHost, s));
-        if (on) HIPCHK(h, hipMemcpyAsync(out_nrm, on, (size_t)m * 12, hipMemcpyDeviceToHost, s));
-        if (oc) HIPCHK(h, hipMemcpyAsync(out_cov, oc, (size_t)m * 24, hipMemcpyDeviceToHost, s));
-        if (oi) HIPCHK(h, hipMemcpyAsync(out_idx, oi, (size_t)m * 4, hipMemcpyDeviceToHost, s));
-    }
+    StagedOut so(h, h->f_out, on_device);   // normals / covariances go out only where they came in
+    const int s_xyz = so.add(out_xyz, 3), s_nrm = so.add(nrm ? out_nrm : nullptr, 3),
+              s_cov = so.add(cov ? out_cov : nullptr, 6), s_idx = so.add(out_idx, 1);
+    HIPCHK(h, so.reserve((size_t)m));
+    if (m > 0)
+        k_pf_gather<<<grid_for(m), 256, 0, s>>>(px, pn, pc, idx, m, so.at<float>(s_xyz), so.at<float>(s_nrm),
+                                                so.at<float>(s_cov), so.at<int32_t>(s_idx));
+    HIPCHK(h, so.copy_back((size_t)m));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     *n_out = m;

@@ -59,35 +59,24 @@ reg_status reg_compute_fpfh(reg_handle* h, const float* xyz, int64_t xyz_stride,
         h->err = w->err;
         return st;
     }
-    // first radius level expected to hold max_nn neighbours on a surface-like cloud (exactness does not depend on it)
-    const float per = (float)n / (float)std::max<int64_t>(1, w->info.n_cells_occupied);
-    const float need = w->info.cell_size * std::sqrt(1.3f * (float)max_nn / (3.14159265f * std::max(per, 1e-3f)));
-    int start = 0;
-    while (start < w->grid.n_levels - 1 && w->grid.rho[start] < need) ++start;
+    const int start = knn_start_level(w, n, max_nn);
     // workspace: ordered ids | counts, m; host callers get their outputs through fp_out
     HIPCHK(h, h->fp_ids.reserve((size_t)n * max_nn * 4));
     HIPCHK(h, h->fp_cnt.reserve((size_t)n * (kFpfhDim + 1) * 4));
     int32_t* d_ids = h->fp_ids.as<int32_t>();
     int32_t* d_cnt = h->fp_cnt.as<int32_t>();
     int32_t* d_m = d_cnt + (size_t)n * kFpfhDim;
-    double *d_f = fpfh, *d_s = spfh;
-    if (!on_device) {
-        HIPCHK(h, h->fp_out.reserve((size_t)n * kFpfhDim * 8 * 2));
-        d_f = h->fp_out.as<double>();
-        if (spfh) d_s = d_f + (size_t)n * kFpfhDim;
-    }
+    StagedOut so(h, h->fp_out, on_device);
+    const int s_f = so.add(fpfh, kFpfhDim), s_s = so.add(spfh, kFpfhDim);
+    HIPCHK(h, so.reserve((size_t)n));
     const unsigned blocks = (unsigned)((n + kFpfhWaves - 1) / kFpfhWaves);
     k_fpfh_spfh<<<blocks, 64 * kFpfhWaves, 0, h->stream>>>(w->grid, d_xyz, xyz_stride, d_nrm, nrm_stride, n, max_nn, start,
                                                          d_ids, d_cnt, d_m, misc + 1);
-    k_fpfh_accum<<<blocks, 64 * kFpfhWaves, 0, h->stream>>>(d_xyz, xyz_stride, n, max_nn, d_ids, d_cnt, d_m, d_f, d_s);
+    k_fpfh_accum<<<blocks, 64 * kFpfhWaves, 0, h->stream>>>(d_xyz, xyz_stride, n, max_nn, d_ids, d_cnt, d_m,
+                                                          so.at<double>(s_f), so.at<double>(s_s));
     HIPCHK(h, hipMemcpyAsync(&back[1], misc + 1, 4, hipMemcpyDeviceToHost, h->stream));
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(fpfh, d_f, (size_t)n * kFpfhDim * 8, hipMemcpyDeviceToHost, h->stream));
-        if (spfh) HIPCHK(h, hipMemcpyAsync(spfh, d_s, (size_t)n * kFpfhDim * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (n_neighbours)
-        HIPCHK(h, hipMemcpyAsync(n_neighbours, d_m, (size_t)n * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
-                                 h->stream));
+    HIPCHK(h, so.copy_back((size_t)n));
+    HIPCHK(h, copy_out(h, n_neighbours, d_m, (size_t)n * 4, on_device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_rescanned) *n_rescanned = back[1];
@@ -120,11 +109,11 @@ reg_status reg_match_features(reg_handle* h, const double* fa, int64_t na, const
     const double *d_a = nullptr, *d_b = nullptr;
     HIPCHK(h, staged_input(h, h->mf_a, fa, (size_t)na * dim, on_device, &d_a));
     HIPCHK(h, staged_input(h, h->mf_b, fb, (size_t)nb * dim, on_device, &d_b));
-    // mf_nn: nn_ab | nn_ba | mutual pairs, for whatever the caller does not hold on the device
-    HIPCHK(h, h->mf_nn.reserve((size_t)(3 * na + nb) * 4));
-    int32_t* d_ab = on_device ? nn_ab : h->mf_nn.as<int32_t>();
-    int32_t* d_ba = (on_device && nn_ba) ? nn_ba : h->mf_nn.as<int32_t>() + na;
-    int32_t* d_mu = on_device ? mutual : h->mf_nn.as<int32_t>() + na + nb;
+    // nn_ab (na rows), nn_ba (nb rows; the mutual test reads it whether the caller wants it or not), mutual pairs (<= na)
+    StagedOut so(h, h->mf_nn, on_device);
+    const int s_ab = so.add(nn_ab, 1), s_ba = so.add(nn_ba, 1, mutual != nullptr), s_mu = so.add(mutual, 2);
+    HIPCHK(h, so.reserve((size_t)std::max(na, nb)));
+    int32_t *d_ab = so.at<int32_t>(s_ab), *d_ba = so.at<int32_t>(s_ba), *d_mu = so.at<int32_t>(s_mu);
     REGCHK(mf_search(h, d_a, na, d_b, nb, dim, d_ab));
     int64_t km = 0;
     if (backward) REGCHK(mf_search(h, d_b, nb, d_a, na, dim, d_ba));
@@ -140,11 +129,9 @@ reg_status reg_match_features(reg_handle* h, const double* fa, int64_t na, const
         km = total;
         if (km > 0) k_mf_collect<<<grid_for(na), 256, 0, h->stream>>>(flags, offs, na, d_ab, d_mu);
     }
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(nn_ab, d_ab, (size_t)na * 4, hipMemcpyDeviceToHost, h->stream));
-        if (nn_ba) HIPCHK(h, hipMemcpyAsync(nn_ba, d_ba, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
-        if (km > 0) HIPCHK(h, hipMemcpyAsync(mutual, d_mu, (size_t)km * 8, hipMemcpyDeviceToHost, h->stream));
-    }
+    HIPCHK(h, so.copy_back(s_ab, (size_t)na));
+    HIPCHK(h, so.copy_back(s_ba, (size_t)nb));
+    HIPCHK(h, so.copy_back(s_mu, (size_t)km));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_mutual) *n_mutual = km;

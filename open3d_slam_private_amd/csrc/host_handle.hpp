@@ -101,7 +101,7 @@ struct reg_handle {
     bool device_ok = false;   // false: reg_create could not get a HIP device (every entry point then fails loudly)
     bool structure_only = false;   // workspace handle of reg_estimate_normals: bin table only, no attributes
     reg_handle* normals_ws = nullptr;
-    DevBuf n_out, n_eig, n_cov, n_ids, n_extra, n_mom;
+    DevBuf n_out, n_ids, n_extra, n_mom;
     // reg_compute_fpfh / reg_match_features (host_fpfh.hpp): staged inputs, ordered ids, counts + m, host-pointer outputs, flag
     // words; staged feature rows, per-chunk partial bests, index outputs, mutual flags + offsets
     DevBuf fp_xyz, fp_nrm, fp_ids, fp_cnt, fp_out, fp_misc, mf_a, mf_b, mf_part, mf_nn, mf_flags;
@@ -113,7 +113,7 @@ struct reg_handle {
     DevBuf c_in_xyz, c_in_nrm, c_in_cov, c_flags, c_offs, c_xyz, c_nrm, c_cov, c_idx;   // reg_set_target_f64
     DevBuf r_in_xyz, r_in_nrm, r_in_cov, r_xyz, r_nrm, r_cov;                            // reg_set_source_f64
     int64_t crop_kept = 0;
-    DevBuf v_fout, v_oout, v_oxyz, v_onrm, v_ocov;   // reg_voxelize_within_volume
+    DevBuf v_fout, v_oout, v_out;   // reg_voxelize_within_volume
     DevBuf v_ukeys, v_ustart;                        // reg_carve_indices
     // reg_overlap_indices / reg_set_pair_overlap_f64 (host_overlap.hpp): per layer (0: source, 1: target) keys, sorted keys,
     // unique keys + counts, flags + offsets; run counts and the invalid-key word; the reading's index map
@@ -123,9 +123,9 @@ struct reg_handle {
                                                      // reg_process_scan)
     // the scan front end (host_scanprep.hpp): staged inputs; the cloud after the wide crop, after the voxel grid, after the
     // random selection (xyz, normals, covs each); the fp32 cast and the estimated fp32 normals / covariances; sort keys and
-    // values, flags + offsets, kept indices, min-bound rows + origin, the invalid-key word; the events of scan_prep_ms
-    DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_keys, sp_keys2, sp_vals, sp_vals2, sp_flags, sp_offs, sp_idx,
-        sp_part, sp_misc;
+    // values, flags + offsets, min-bound rows + origin, the invalid-key word; the events of scan_prep_ms
+    DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_keys, sp_keys2, sp_vals, sp_vals2, sp_flags, sp_offs, sp_part,
+        sp_misc;
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;

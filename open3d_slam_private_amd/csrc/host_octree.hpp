@@ -105,19 +105,10 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
     HIPCHK(h, staged_input(h, h->f_in_cov, cov, (size_t)N * 6, on_device, &d_cov));
     HIPCHK(h, h->f_px.reserve((size_t)N * 12));
     HIPCHK(h, h->f_misc.reserve(64));
-    // misc: [0..2] min, [3..5] max (orderable keys), [6] non-finite flag, [8] any node still open
-    const uint32_t misc0[10] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-    HIPCHK(h, hipMemcpyAsync(h->f_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, s));
     float* px = h->f_px.as<float>();
-    uint32_t* misc = h->f_misc.as<uint32_t>();
-    k_ssn_pack<<<grid_for(N), 256, 0, s>>>(d_in, xyz_stride, N, px, misc);
+    uint32_t* misc = h->f_misc.as<uint32_t>();   // pack_cloud_box's words, then [8] any node still open
     uint32_t box[7];
-    HIPCHK(h, hipMemcpyAsync(box, misc, sizeof(box), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    if (box[6]) {
-        h->err = "reg_octree_grid: non-finite input";
-        return REG_BAD_ARGUMENT;
-    }
+    REGCHK(pack_cloud_box(h, "reg_octree_grid", d_in, xyz_stride, N, px, box));
     float lo[3], hi[3], c0[4] = {0.f, 0.f, 0.f, 0.f}, r0 = 0.f;
     for (int a = 0; a < 3; ++a) {
         lo[a] = float_from_orderable(box[a]);
@@ -211,31 +202,17 @@ reg_status reg_octree_grid(reg_handle* h, const float* xyz, int64_t xyz_stride, 
         HIPCHK(h, hipStreamSynchronize(s));   // rv is released on return from this block
         d_rand = h->o_rand.as<int32_t>();
     }
-    // outputs: the caller's device pointers, else one staging buffer
-    const size_t rows = (size_t)n_leaves;
-    float *ox = out->xyz, *on = (d_nrm && out->normals) ? out->normals : nullptr, *oc = (d_cov && out->covs) ? out->covs : nullptr;
-    int32_t* oi = out->src_idx;
-    HIPCHK(h, h->f_out.reserve(rows * (3 + 3 + 6 + 1) * 4));
-    float* stage = h->f_out.as<float>();
-    if (!on_device) {
-        ox = stage;
-        on = on ? stage + rows * 3 : nullptr;
-        oc = oc ? stage + rows * 6 : nullptr;
-    }
-    if (!on_device || !oi) oi = (int32_t*)(stage + rows * 12);
-    k_oct_sample<<<grid_for(n_leaves), 256, 0, s>>>(px, d_nrm, d_cov, idx, start, (int)n_leaves, method, d_rand, ox, on,
-                                                    oc, oi);
-    if (on_device) {
-        if (out->leaf_id) HIPCHK(h, hipMemcpyAsync(out->leaf_id, rank, N4, hipMemcpyDeviceToDevice, s));
-        if (out->leaf_depth) HIPCHK(h, hipMemcpyAsync(out->leaf_depth, depth, N4, hipMemcpyDeviceToDevice, s));
-    } else {
-        HIPCHK(h, hipMemcpyAsync(out->xyz, ox, rows * 12, hipMemcpyDeviceToHost, s));
-        if (on) HIPCHK(h, hipMemcpyAsync(out->normals, on, rows * 12, hipMemcpyDeviceToHost, s));
-        if (oc) HIPCHK(h, hipMemcpyAsync(out->covs, oc, rows * 24, hipMemcpyDeviceToHost, s));
-        if (out->src_idx) HIPCHK(h, hipMemcpyAsync(out->src_idx, oi, rows * 4, hipMemcpyDeviceToHost, s));
-        if (out->leaf_id) HIPCHK(h, hipMemcpyAsync(out->leaf_id, rank, N4, hipMemcpyDeviceToHost, s));
-        if (out->leaf_depth) HIPCHK(h, hipMemcpyAsync(out->leaf_depth, depth, N4, hipMemcpyDeviceToHost, s));
-    }
+    // outputs: normals / covariances go out only where they came in; k_oct_sample always writes src_idx
+    StagedOut so(h, h->f_out, on_device);
+    const int s_xyz = so.add(out->xyz, 3), s_nrm = so.add(d_nrm ? out->normals : nullptr, 3),
+              s_cov = so.add(d_cov ? out->covs : nullptr, 6), s_src = so.add(out->src_idx, 1, true);
+    HIPCHK(h, so.reserve((size_t)n_leaves));
+    k_oct_sample<<<grid_for(n_leaves), 256, 0, s>>>(px, d_nrm, d_cov, idx, start, (int)n_leaves, method, d_rand,
+                                                    so.at<float>(s_xyz), so.at<float>(s_nrm), so.at<float>(s_cov),
+                                                    so.at<int32_t>(s_src));
+    HIPCHK(h, so.copy_back((size_t)n_leaves));
+    HIPCHK(h, copy_out(h, out->leaf_id, rank, N4, on_device));
+    HIPCHK(h, copy_out(h, out->leaf_depth, depth, N4, on_device));
     HIPCHK(h, hipStreamSynchronize(s));
     HIPCHK(h, hipGetLastError());
     *n_out = (int64_t)n_leaves;

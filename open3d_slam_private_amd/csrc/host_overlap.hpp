@@ -99,17 +99,14 @@ reg_status reg_overlap_indices(reg_handle* h, const double* src_xyz, int64_t n, 
     if (s != REG_OK) return s;
     // ascending lists; host callers get them through the sorted-key buffer, which is free again (8 bytes per point of the
     // larger layer hold both lists)
-    int32_t *d_si = src_idx, *d_ti = tgt_idx;
-    if (!on_device) {
-        d_si = h->ov_sorted.as<int32_t>();
-        d_ti = d_si + ks;
-    }
+    StagedOut so(h, h->ov_sorted, on_device);
+    const int s_si = so.add(src_idx, 1), s_ti = so.add(tgt_idx, 1);
+    HIPCHK(h, so.reserve((size_t)std::max(ks, kt)));
+    int32_t *d_si = so.at<int32_t>(s_si), *d_ti = so.at<int32_t>(s_ti);
     if (ks > 0) k_carve_collect<<<grid_for(n), 256, 0, h->stream>>>(h->ov_flags[0].as<uint32_t>(), h->ov_offs[0].as<uint32_t>(), n, d_si);
     if (kt > 0) k_carve_collect<<<grid_for(m), 256, 0, h->stream>>>(h->ov_flags[1].as<uint32_t>(), h->ov_offs[1].as<uint32_t>(), m, d_ti);
-    if (!on_device) {
-        if (ks > 0) HIPCHK(h, hipMemcpyAsync(src_idx, d_si, (size_t)ks * 4, hipMemcpyDeviceToHost, h->stream));
-        if (kt > 0) HIPCHK(h, hipMemcpyAsync(tgt_idx, d_ti, (size_t)kt * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+    HIPCHK(h, so.copy_back(s_si, (size_t)ks));
+    HIPCHK(h, so.copy_back(s_ti, (size_t)kt));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_src) *n_src = ks;

@@ -1,5 +1,8 @@
 // host_prims.hpp -- host primitives the entry points share: rocPRIM's temporary-storage protocol, scans and sorts on it,
-// the total of a flag array, the crop configuration, staged inputs
+// the total of a flag array, the crop configuration, staged inputs; the outputs of the operators that have a host and a
+// device-pointer form (StagedOut: one declaration per output gives its device pointer, its share of the staging buffer and
+// its copy-back; copy_out for an output held in a working buffer); the pack / bounding box / non-finite front of the box
+// filters
 // Part of the single translation unit reg_core.hip (included there after host_handle.hpp, which completes reg_handle and
 // HIPCHK, and before host_target.hpp; not a standalone header).
 #pragma once
@@ -92,4 +95,78 @@ static hipError_t staged_input(reg_handle* h, DevBuf& buf, const T* src, size_t 
     if (e != hipSuccess) return e;
     *out = buf.as<T>();
     return hipMemcpyAsync(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice, h->stream);
+}
+
+// The outputs of an operator that has a host and a device-pointer form.  The entry point declares each output once --
+// add(the caller's pointer or null, elements per row) -- calls reserve(row capacity), hands at<T>(slot) to its kernels and
+// ends with copy_back(rows).  Device-pointer form: at() is the caller's pointer and nothing is copied.  Host form: at() is a
+// 16-byte aligned slice of `buf`, and copy_back enqueues rows * bytes-per-row of every output the caller asked for on
+// h->stream (rows == 0: nothing); the caller synchronises.  An absent output is null, unless it was declared `always`
+// (the kernel writes it whether the caller wants it or not): then it is a scratch slice in both forms.  at() reads buf.p
+// when it is called, so reserve() comes first.
+struct StagedOut {
+    struct Slot {
+        void* user;
+        size_t row_bytes, off;
+        bool staged;
+    };
+    reg_handle* h;
+    DevBuf& buf;
+    const int on_device;
+    Slot s[REG_MAX_FIELDS + 8];   // the widest caller: xyz, idx and REG_MAX_FIELDS descriptor fields
+    int n = 0;
+    StagedOut(reg_handle* h_, DevBuf& buf_, int on_device_) : h(h_), buf(buf_), on_device(on_device_) {}
+    template <class T>
+    int add(T* user, size_t per_row, bool always = false) {
+        s[n] = {user, per_row * sizeof(T), 0, on_device ? (always && !user) : (always || user)};
+        return n++;
+    }
+    hipError_t reserve(size_t rows) {
+        size_t bytes = 0;
+        for (int i = 0; i < n; ++i)
+            if (s[i].staged) {
+                s[i].off = bytes;
+                bytes += (std::max<size_t>(rows, 1) * s[i].row_bytes + 15) & ~(size_t)15;
+            }
+        return buf.reserve(bytes);
+    }
+    template <class T>
+    T* at(int i) const {
+        return s[i].staged ? (T*)((char*)buf.p + s[i].off) : (T*)(on_device ? s[i].user : nullptr);
+    }
+    hipError_t copy_back(int i, size_t rows) const {   // one output, for an operator whose outputs differ in their rows
+        if (on_device || !s[i].user || rows == 0) return hipSuccess;
+        return hipMemcpyAsync(s[i].user, at<char>(i), rows * s[i].row_bytes, hipMemcpyDeviceToHost, h->stream);
+    }
+    hipError_t copy_back(size_t rows) const {
+        for (int i = 0; i < n; ++i) {
+            const hipError_t e = copy_back(i, rows);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+};
+
+// An output that already lives in a working buffer: `bytes` from there to the caller's array (null: not wanted; the buffer
+// itself, where a kernel wrote through the caller's device pointer: nothing to do), enqueued on h->stream.
+static hipError_t copy_out(reg_handle* h, void* user, const void* src, size_t bytes, int on_device) {
+    if (!user || user == src || bytes == 0) return hipSuccess;
+    return hipMemcpyAsync(user, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream);
+}
+
+// The common front of the box-based filters: packs the cloud into px (n x 3), takes its bounding box and rejects
+// non-finite input ("<who>: non-finite input").  misc (h->f_misc, >= 10 words) is left as [0..2] min, [3..5] max
+// (orderable keys), [6] the non-finite flag, [7..9] zero; box receives words 0..6.  One synchronisation.
+static reg_status pack_cloud_box(reg_handle* h, const char* who, const float* d_in, int64_t xyz_stride, int N, float* px,
+                                 uint32_t box[7]) {
+    const uint32_t misc0[10] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    HIPCHK(h, hipMemcpyAsync(h->f_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, h->stream));
+    k_ssn_pack<<<grid_for(N), 256, 0, h->stream>>>(d_in, xyz_stride, N, px, h->f_misc.as<uint32_t>());
+    HIPCHK(h, hipMemcpyAsync(box, h->f_misc.p, 7 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (box[6]) {
+        h->err = std::string(who) + ": non-finite input";
+        return REG_BAD_ARGUMENT;
+    }
+    return REG_OK;
 }

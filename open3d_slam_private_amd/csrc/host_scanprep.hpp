@@ -108,21 +108,18 @@ reg_status reg_voxel_down_sample(reg_handle* h, const double* xyz, const double*
     if (n == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
     const double* d_in[3] = {xyz, normals, covs};
-    double* d_out[3] = {out_xyz, out_normals, out_covs};
+    double* const user[3] = {out_xyz, out_normals, out_covs};
+    StagedOut so(h, h->sp_b[0], on_device);   // slot k: points, normals, covariances; an output goes with its input
     for (int k = 0; k < 3; ++k) {
         HIPCHK(h, staged_input(h, h->sp_in[k], d_in[k], (size_t)n * kSpWidth[k], on_device, &d_in[k]));
-        if (!on_device && d_in[k]) {
-            HIPCHK(h, h->sp_b[k].reserve((size_t)n * kSpWidth[k] * 8));
-            d_out[k] = h->sp_b[k].as<double>();
-        }
+        so.add(d_in[k] ? user[k] : nullptr, kSpWidth[k]);
     }
+    HIPCHK(h, so.reserve((size_t)n));
     int64_t n_vox = 0;
-    REGCHK(sp_voxel_device(h, d_in[0], d_in[1], d_in[2], n, voxel_size, d_out[0], d_out[1], d_out[2], &n_vox));
-    if (!on_device) {
-        double* host_out[3] = {out_xyz, out_normals, out_covs};
-        for (int k = 0; k < 3; ++k)
-            if (d_in[k])
-                HIPCHK(h, hipMemcpyAsync(host_out[k], d_out[k], (size_t)n_vox * kSpWidth[k] * 8, hipMemcpyDeviceToHost, h->stream));
+    REGCHK(sp_voxel_device(h, d_in[0], d_in[1], d_in[2], n, voxel_size, so.at<double>(0), so.at<double>(1), so.at<double>(2),
+                           &n_vox));
+    if (!on_device) {   // (the device form is synchronised by sp_voxel_device)
+        HIPCHK(h, so.copy_back((size_t)n_vox));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     if (n_out) *n_out = n_vox;
@@ -145,29 +142,19 @@ reg_status reg_random_down_sample(reg_handle* h, const double* xyz, const double
     if (count == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
     const double* d_in[3] = {xyz, normals, covs};
-    double* d_out[3] = {out_xyz, out_normals, out_covs};
-    int32_t* d_idx = out_idx;
+    double* const user[3] = {out_xyz, out_normals, out_covs};
+    StagedOut so(h, h->sp_c[0], on_device);   // slot k: points, normals, covariances (each with its input); slot 3: indices
     for (int k = 0; k < 3; ++k) {
         HIPCHK(h, staged_input(h, h->sp_in[k], d_in[k], (size_t)n * kSpWidth[k], on_device, &d_in[k]));
-        if (!on_device && d_in[k]) {
-            HIPCHK(h, h->sp_c[k].reserve((size_t)count * kSpWidth[k] * 8));
-            d_out[k] = h->sp_c[k].as<double>();
-        }
+        so.add(d_in[k] ? user[k] : nullptr, kSpWidth[k]);
     }
-    if (!on_device && out_idx) {
-        HIPCHK(h, h->sp_idx.reserve((size_t)count * 4));
-        d_idx = h->sp_idx.as<int32_t>();
-    }
+    const int s_idx = so.add(out_idx, 1);
+    HIPCHK(h, so.reserve((size_t)count));
     REGCHK(sp_random_flags(h, n, count, seed));
     k_sp_gather_f64<<<grid_for(n), 256, 0, h->stream>>>(d_in[0], d_in[1], d_in[2], n, h->sp_flags.as<uint32_t>(),
-                                                        h->sp_offs.as<uint32_t>(), d_out[0], d_out[1], d_out[2], d_idx);
-    if (!on_device) {
-        double* host_out[3] = {out_xyz, out_normals, out_covs};
-        for (int k = 0; k < 3; ++k)
-            if (d_in[k])
-                HIPCHK(h, hipMemcpyAsync(host_out[k], d_out[k], (size_t)count * kSpWidth[k] * 8, hipMemcpyDeviceToHost, h->stream));
-        if (out_idx) HIPCHK(h, hipMemcpyAsync(out_idx, d_idx, (size_t)count * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+                                                        h->sp_offs.as<uint32_t>(), so.at<double>(0), so.at<double>(1),
+                                                        so.at<double>(2), so.at<int32_t>(s_idx));
+    HIPCHK(h, so.copy_back((size_t)count));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_out) *n_out = count;
@@ -304,9 +291,7 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
     // 5. the merge cloud (merge_) goes to the caller's arrays
     double* merge[3] = {merge_xyz, merge_normals, merge_covs};
     for (int k = 0; k < 3; ++k)
-        if (cur[k] && merge[k])
-            HIPCHK(h, hipMemcpyAsync(merge[k], cur[k], (size_t)m * kSpWidth[k] * 8,
-                                     on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+        if (cur[k]) HIPCHK(h, copy_out(h, merge[k], cur[k], (size_t)m * kSpWidth[k] * 8, on_device));
     // 6. narrow crop (scanMatcherCropper_ at the identity pose) + open3dToPointmatcher: match_ becomes the reading
     HIPCHK(h, h->sp_flags.reserve((size_t)m * 4));
     HIPCHK(h, h->sp_offs.reserve((size_t)m * 4));

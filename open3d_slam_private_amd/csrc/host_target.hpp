@@ -492,7 +492,6 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
     CropCfg c;
     if (!crop_cfg(volume, &c)) return REG_BAD_ARGUMENT;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const hipMemcpyKind out_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (!(voxel_size > 0.0)) {   // helpers.cpp:121-124: nothing to do
         HIPCHK(h, hipMemcpyAsync(out_xyz, xyz, (size_t)m * 24, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost, h->stream));
         if (normals) HIPCHK(h, hipMemcpyAsync(out_normals, normals, (size_t)m * 24, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToHost, h->stream));
@@ -506,19 +505,11 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
     HIPCHK(h, staged_input(h, h->c_in_xyz, xyz, (size_t)m * 3, on_device, &d_xyz));
     HIPCHK(h, staged_input(h, h->c_in_nrm, normals, (size_t)m * 3, on_device, &d_nrm));
     HIPCHK(h, staged_input(h, h->c_in_cov, covs, (size_t)m * 9, on_device, &d_cov));
-    double *d_oxyz = out_xyz, *d_onrm = out_normals, *d_ocov = out_covs;
-    if (!on_device) {
-        HIPCHK(h, h->v_oxyz.reserve((size_t)m * 24));
-        d_oxyz = h->v_oxyz.as<double>();
-        if (normals) {
-            HIPCHK(h, h->v_onrm.reserve((size_t)m * 24));
-            d_onrm = h->v_onrm.as<double>();
-        }
-        if (covs) {
-            HIPCHK(h, h->v_ocov.reserve((size_t)m * 72));
-            d_ocov = h->v_ocov.as<double>();
-        }
-    }
+    StagedOut so(h, h->v_out, on_device);
+    const int s_xyz = so.add(out_xyz, 3), s_nrm = so.add(normals ? out_normals : nullptr, 3),
+              s_cov = so.add(covs ? out_covs : nullptr, 9);
+    HIPCHK(h, so.reserve((size_t)m));
+    double *d_oxyz = so.at<double>(s_xyz), *d_onrm = so.at<double>(s_nrm), *d_ocov = so.at<double>(s_cov);
     const double inv = 1.0 / voxel_size;   // fromVoxelSize (VoxelHashMap.hpp:43-45)
     HIPCHK(h, h->c_flags.reserve((size_t)m * 4));
     HIPCHK(h, h->c_offs.reserve((size_t)m * 4));
@@ -563,11 +554,7 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
         n_vox = flag_total(lv);
     }
     const int64_t total = n_outs + n_vox;
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(out_xyz, d_oxyz, (size_t)total * 24, out_kind, h->stream));
-        if (normals) HIPCHK(h, hipMemcpyAsync(out_normals, d_onrm, (size_t)total * 24, out_kind, h->stream));
-        if (covs) HIPCHK(h, hipMemcpyAsync(out_covs, d_ocov, (size_t)total * 72, out_kind, h->stream));
-    }
+    HIPCHK(h, so.copy_back((size_t)total));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_out) *n_out = total;
@@ -651,16 +638,12 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
     REGCHK(flag_total_async(h, mark, o_mark, m, rt));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int64_t nr = flag_total(rt);
-    int32_t* d_out = removed;
-    if (!on_device) {
-        HIPCHK(h, h->c_idx.reserve((size_t)std::max<int64_t>(nr, 1) * 4));
-        d_out = h->c_idx.as<int32_t>();
-        h->crop_kept = 0;   // c_idx no longer holds the crop map of reg_set_target_f64
-    }
-    if (nr > 0) {
-        k_carve_collect<<<grid_for(m), 256, 0, h->stream>>>(mark, o_mark, m, d_out);
-        if (!on_device) HIPCHK(h, hipMemcpyAsync(removed, d_out, (size_t)nr * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+    StagedOut so(h, h->c_idx, on_device);
+    const int s_rem = so.add(removed, 1);
+    HIPCHK(h, so.reserve((size_t)nr));
+    if (!on_device) h->crop_kept = 0;   // c_idx no longer holds the crop map of reg_set_target_f64
+    if (nr > 0) k_carve_collect<<<grid_for(m), 256, 0, h->stream>>>(mark, o_mark, m, so.at<int32_t>(s_rem));
+    HIPCHK(h, so.copy_back((size_t)nr));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_removed) *n_removed = nr;
@@ -747,6 +730,16 @@ static reg_status normals_workspace(reg_handle* h, const char* who) {
     return REG_OK;
 }
 
+// First radius level of the workspace's table expected to hold k neighbours on a surface-like cloud of n points (exactness
+// does not depend on it)
+static int knn_start_level(const reg_handle* w, int64_t n, int k) {
+    const float per = (float)n / (float)std::max<int64_t>(1, w->info.n_cells_occupied);
+    const float need = w->info.cell_size * std::sqrt(1.3f * (float)k / (3.14159265f * std::max(per, 1e-3f)));
+    int start = 0;
+    while (start < w->grid.n_levels - 1 && w->grid.rho[start] < need) ++start;
+    return start;
+}
+
 reg_status reg_estimate_normals(reg_handle* h, const float* xyz, int64_t xyz_stride, int64_t n, int on_device, int k,
                                 float max_dist, const float* viewpoint, int regularise, const reg_normals_out* out,
                                 int64_t* n_rescanned) {
@@ -771,38 +764,14 @@ reg_status reg_estimate_normals(reg_handle* h, const float* xyz, int64_t xyz_str
         h->err = w->err;
         return st;
     }
-    // first radius level expected to hold k neighbours on a surface-like cloud (exactness does not depend on it)
-    const float per = (float)n / (float)std::max<int64_t>(1, w->info.n_cells_occupied);
-    const float need = w->info.cell_size * std::sqrt(1.3f * (float)k / (3.14159265f * std::max(per, 1e-3f)));
-    int start = 0;
-    while (start < w->grid.n_levels - 1 && w->grid.rho[start] < need) ++start;
+    const int start = knn_start_level(w, n, k);
     const float* d_raw = on_device ? xyz : w->t_raw.as<float>();
     HIPCHK(h, hipSetDevice(h->prm.device));
-    float *d_n = normals, *d_e = eigvals, *d_c = covs, *d_v = out->eigvecs, *d_d = out->densities, *d_m = out->mean_dists;
-    int32_t* d_i = ids;
-    if (!on_device) {
-        HIPCHK(h, h->n_out.reserve((size_t)n * 12));
-        d_n = h->n_out.as<float>();
-        if (eigvals) {
-            HIPCHK(h, h->n_eig.reserve((size_t)n * 12));
-            d_e = h->n_eig.as<float>();
-        }
-        if (covs) {
-            HIPCHK(h, h->n_cov.reserve((size_t)n * 24));
-            d_c = h->n_cov.as<float>();
-        }
-        if (ids) {
-            HIPCHK(h, h->n_ids.reserve((size_t)n * k * 4));
-            d_i = h->n_ids.as<int32_t>();
-        }
-        if (out->eigvecs || out->densities || out->mean_dists) {
-            HIPCHK(h, h->n_extra.reserve((size_t)n * (9 + 1 + 1) * 4));
-            float* base = h->n_extra.as<float>();
-            if (out->eigvecs) d_v = base;
-            if (out->densities) d_d = base + (size_t)n * 9;
-            if (out->mean_dists) d_m = base + (size_t)n * 10;
-        }
-    }
+    StagedOut so(h, h->n_out, on_device);
+    const int s_n = so.add(normals, 3), s_e = so.add(eigvals, 3), s_c = so.add(covs, 6), s_i = so.add(ids, (size_t)k),
+              s_v = so.add(out->eigvecs, 9), s_d = so.add(out->densities, 1), s_m = so.add(out->mean_dists, 1);
+    HIPCHK(h, so.reserve((size_t)n));
+    int32_t* d_i = so.at<int32_t>(s_i);
     HIPCHK(h, w->t_misc.reserve(256));
     HIPCHK(h, hipMemsetAsync(w->t_misc.p, 0, 4, h->stream));
     const float vp[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
@@ -815,18 +784,11 @@ reg_status reg_estimate_normals(reg_handle* h, const float* xyz, int64_t xyz_str
         k_knn_pca<256><<<(unsigned)blocks, 256, 0, h->stream>>>(w->grid, d_raw, xyz_stride, n, k, start, d_i,
                                                                 w->t_misc.as<uint32_t>(), h->n_mom.as<PcaMoments>());
     k_pca_finish<<<grid_for(n), 256, 0, h->stream>>>(h->n_mom.as<PcaMoments>(), n, vp[0], vp[1], vp[2], viewpoint ? 1 : 0,
-                                                     regularise, d_n, d_e, d_c, d_v, d_d, d_m);
+                                                     regularise, so.at<float>(s_n), so.at<float>(s_e), so.at<float>(s_c),
+                                                     so.at<float>(s_v), so.at<float>(s_d), so.at<float>(s_m));
     uint32_t resc = 0;
     HIPCHK(h, hipMemcpyAsync(&resc, w->t_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
-    if (!on_device) {
-        HIPCHK(h, hipMemcpyAsync(normals, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-        if (eigvals) HIPCHK(h, hipMemcpyAsync(eigvals, d_e, (size_t)n * 12, hipMemcpyDeviceToHost, h->stream));
-        if (covs) HIPCHK(h, hipMemcpyAsync(covs, d_c, (size_t)n * 24, hipMemcpyDeviceToHost, h->stream));
-        if (ids) HIPCHK(h, hipMemcpyAsync(ids, d_i, (size_t)n * k * 4, hipMemcpyDeviceToHost, h->stream));
-        if (out->eigvecs) HIPCHK(h, hipMemcpyAsync(out->eigvecs, d_v, (size_t)n * 36, hipMemcpyDeviceToHost, h->stream));
-        if (out->densities) HIPCHK(h, hipMemcpyAsync(out->densities, d_d, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-        if (out->mean_dists) HIPCHK(h, hipMemcpyAsync(out->mean_dists, d_m, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    }
+    HIPCHK(h, so.copy_back((size_t)n));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (n_rescanned) *n_rescanned = resc;

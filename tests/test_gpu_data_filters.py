@@ -243,3 +243,56 @@ def test_bad_arguments_give_documented_codes(reg):
     assert status(lambda: reg.filter_points(xyz, [{"type": "FixStepSampling", "startStep": 3, "phase": 3}])) == 6
     assert status(lambda: reg.filter_points(xyz, [{"type": "MaxQuantileOnAxis", "dim": -1}])) == 6
     assert status(lambda: reg.filter_points(xyz, [{"type": "MaxDist", "dim": 3}])) == 6
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_ssn_output_subsets_equal_the_full_call(so_reg):
+    """Each optional output alone (eigenvalues without normals among them) and none, host form, 300 points."""
+    full = SO.check_subsets(so_reg, SO.OPS["ssn"](so_reg), SO.f32_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+def test_ssn_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["ssn"](so_reg), SO.f32_inputs(300))
+
+
+def test_ssn_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["ssn"](so_reg), SO.f32_inputs(300))
+
+
+def test_ssn_larger_cloud_after_a_smaller_one(so_reg):
+    SO.check_grown(so_reg, SO.OPS["ssn"], SO.f32_inputs)
+
+
+def test_filter_points_output_subsets_equal_the_full_call(so_reg):
+    full = SO.check_subsets(so_reg, SO.OPS["filter_points"](so_reg, SO.PM_CHAIN), SO.f32_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+def test_filter_points_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["filter_points"](so_reg, SO.PM_CHAIN), SO.f32_inputs(300))
+
+
+def test_filter_points_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["filter_points"](so_reg, SO.PM_CHAIN), SO.f32_inputs(300))
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_filter_points_zero_rows_leave_the_outputs_untouched(so_reg, form):
+    SO.check_zero_rows(so_reg, SO.OPS["filter_points"](so_reg, SO.BOX_OUT + SO.PM_CHAIN), SO.f32_inputs(300), form)
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_filter_points_forms_agree_at_edge_sizes(so_reg, n):
+    SO.check_forms_agree(so_reg, SO.OPS["filter_points"](so_reg, [{"type": "FixStepSampling", "startStep": 1}]),
+                         SO.f32_inputs(n))

@@ -443,3 +443,51 @@ def test_voxel_grid_stage_in_a_chain_and_end_to_end(reg):
     icp.readingDataPointsFilters = []                                    # an empty chain forgets the last chain's fields
     icp.compute(DataPoints(rd), DataPoints(ref[:, :3], ref[:, 3:6]))
     assert icp.readingFilteredIndices() is None
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_filter_cloud_output_subsets_equal_the_full_call(so_reg):
+    """Among the subsets: a created field returned alone while the other created field's `out` is null."""
+    full = SO.check_subsets(so_reg, SO.OPS["filter_cloud"](so_reg, SO.FC_CHAIN), SO.f32_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+def test_filter_cloud_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["filter_cloud"](so_reg, SO.FC_CHAIN), SO.f32_inputs(300))
+
+
+def test_filter_cloud_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["filter_cloud"](so_reg, SO.FC_CHAIN), SO.f32_inputs(300))
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_filter_cloud_zero_rows_leave_the_outputs_untouched(so_reg, form):
+    SO.check_zero_rows(so_reg, SO.OPS["filter_cloud"](so_reg, SO.BOX_OUT + SO.FC_CHAIN), SO.f32_inputs(300), form)
+
+
+def test_voxel_grid_output_subsets_equal_the_full_call(so_reg):
+    full = SO.check_subsets(so_reg, SO.OPS["voxel_grid"](so_reg), SO.field_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+def test_voxel_grid_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["voxel_grid"](so_reg), SO.field_inputs(300))
+
+
+def test_voxel_grid_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["voxel_grid"](so_reg), SO.field_inputs(300))
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_voxel_grid_forms_agree_at_edge_sizes(so_reg, n):
+    SO.check_forms_agree(so_reg, SO.OPS["voxel_grid"](so_reg, 0.5), SO.field_inputs(n))

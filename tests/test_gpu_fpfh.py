@@ -315,3 +315,32 @@ def test_compute_submap_features_equals_the_three_calls():
     assert np.array_equal(sparse.features, pts) and np.array_equal(sparse.normals, nrm)
     assert feature.data_.shape == (33, pts.shape[0]) and np.array_equal(feature.data_, out["fpfh"].T)
     assert np.isfinite(feature.data_).all() and feature.data_.any()
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_fpfh_output_subsets_equal_the_full_call(so_reg):
+    SO.check_subsets(so_reg, SO.OPS["fpfh"](so_reg), SO.f32_inputs(300))
+
+
+def test_fpfh_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["fpfh"](so_reg), SO.f32_inputs(300))
+
+
+def test_match_features_output_subsets_equal_the_full_call(so_reg):
+    """Among the subsets: mutual without nn_ba (the backward search then runs into a scratch slice)."""
+    full = SO.check_subsets(so_reg, SO.OPS["match_features"](so_reg, 257, 33), SO.feature_inputs(300, 257, 33))
+    assert full.counts["km"] > 0
+
+
+def test_match_features_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["match_features"](so_reg, 257, 33), SO.feature_inputs(300, 257, 33))

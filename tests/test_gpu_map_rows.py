@@ -376,3 +376,22 @@ def test_carve_device_pointers(case):
     torch.cuda.synchronize()
     o = out.cpu().numpy()
     assert n == host.size and np.array_equal(o[:n], host) and np.all(o[n:] == -1)   # nothing written past n_removed
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_voxelize_output_subsets_equal_the_full_call(so_reg):
+    """With and without normals / covariances, host form, and the device-pointer form against it."""
+    op, inputs = SO.OPS["voxelize"](so_reg), SO.f64_inputs(300)
+    full = SO.check_subsets(so_reg, op, inputs)
+    assert 0 < full.counts["outside"] < full.counts["m"] < 300
+    SO.check_forms_agree(so_reg, op, inputs)

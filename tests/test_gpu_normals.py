@@ -269,3 +269,32 @@ def test_smooth_normals_rejects_a_neighbour_id_beyond_the_cloud():
     out, passes = reg.smooth_normals(normals, ids)
     assert np.isfinite(out).all() and passes >= 1
     reg.close()
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_estimate_normals_output_subsets_equal_the_full_call(so_reg):
+    """eigvecs, densities and mean_dists each alone among the subsets, host form, 300 points."""
+    SO.check_subsets(so_reg, SO.OPS["estimate_normals"](so_reg), SO.f32_inputs(300))
+
+
+def test_estimate_normals_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["estimate_normals"](so_reg), SO.f32_inputs(300))
+
+
+@pytest.mark.parametrize("n", [1, 255, 257])
+def test_estimate_normals_forms_agree_at_edge_sizes(so_reg, n):
+    SO.check_forms_agree(so_reg, SO.OPS["estimate_normals"](so_reg, k=1 if n == 1 else 8), SO.f32_inputs(n))
+
+
+def test_estimate_normals_larger_cloud_after_a_smaller_one(so_reg):
+    SO.check_grown(so_reg, SO.OPS["estimate_normals"], SO.f32_inputs)

@@ -217,3 +217,28 @@ def test_bad_arguments_give_documented_codes(reg):
     huge = np.array([[-3e38, 0, 0], [3e38, 0, 0]], F32)
     assert status(cloud=huge) == 6                                  # extent overflows the root box
     assert status(cloud=np.zeros((0, 3), F32)) == 2                 # REG_EMPTY_SOURCE
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+def test_octree_output_subsets_equal_the_full_call(so_reg):
+    """Each optional output alone and none (so also without src_idx, which the sampling kernel always writes)."""
+    full = SO.check_subsets(so_reg, SO.OPS["octree"](so_reg), SO.f32_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+def test_octree_device_form_without_optional_outputs(so_reg):
+    SO.check_device_without_optionals(so_reg, SO.OPS["octree"](so_reg), SO.f32_inputs(300))
+
+
+def test_octree_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["octree"](so_reg), SO.f32_inputs(300))

@@ -310,3 +310,43 @@ def test_process_scan_statuses(reg):
     res = capi.ScanResult()
     st = reg._lib.reg_process_scan(reg._h, x.ctypes.data_as(C.c_void_p), None, None, 4000, 0, C.byref(p), None, None, None, C.byref(res))
     assert st == BAD_ARGUMENT                                       # result.struct_size not set
+
+
+# ---- the output paths that the calls above leave thin: absent outputs, scratch slices, zero rows, edge sizes ---------------
+from tests import staged_output_cases as SO  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def so_reg():
+    r = capi.Registration(capi.default_params())
+    yield r
+    r.close()
+
+
+@pytest.mark.parametrize("name", ["voxel_down_sample", "random_down_sample"])
+def test_down_sample_output_subsets_equal_the_full_call(so_reg, name):
+    full = SO.check_subsets(so_reg, SO.OPS[name](so_reg), SO.f64_inputs(300))
+    assert 0 < full.counts["m"] < 300
+
+
+@pytest.mark.parametrize("name", ["voxel_down_sample", "random_down_sample"])
+def test_down_sample_device_form_without_optional_outputs(so_reg, name):
+    SO.check_device_without_optionals(so_reg, SO.OPS[name](so_reg), SO.f64_inputs(300))
+
+
+def test_random_down_sample_writes_nothing_past_the_reported_rows(so_reg):
+    SO.check_nothing_past_the_rows(so_reg, SO.OPS["random_down_sample"](so_reg), SO.f64_inputs(300))
+
+
+@pytest.mark.parametrize("form", ["host", "device"])
+def test_random_down_sample_zero_rows_leave_the_outputs_untouched(so_reg, form):
+    """300 * 0.003 truncates to 0."""
+    SO.check_zero_rows(so_reg, SO.OPS["random_down_sample"](so_reg, ratio=0.003), SO.f64_inputs(300), form)
+
+
+def test_process_scan_merge_cloud_subsets_equal_the_full_call(so_reg):
+    """merge_normals / merge_covs each alone and neither, host form, and the device-pointer form against it."""
+    op, inputs = SO.OPS["process_scan"](so_reg), SO.f64_inputs(300)
+    full = SO.check_subsets(so_reg, op, inputs)
+    assert 0 < full.counts["m"] < 300
+    SO.check_forms_agree(so_reg, op, inputs)
