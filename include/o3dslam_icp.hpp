@@ -677,4 +677,126 @@ public:
     }
 };
 
+// o3d_slam::VoxelizedPointCloud -- the dense map of a submap -- resident on the device (reg_dense_map; contract in
+// include/o3dslam_reg.h).  RAII, move-only.  The map owns a handle that only lends its stream and working storage, and
+// destroys itself before it.  Clouds are Open3D's fp64 arrays in host memory (n x 3 doubles each; normals / colors may be
+// nullptr); transforms are column-major double[16] (Eigen::Matrix4d::data(), nullptr: identity).  Departures from the
+// reference: voxels are exported in ascending (z, y, x) key order; a non-finite point or a voxel index outside +-(2^20 - 1)
+// throws InvalidParameter and leaves the map unchanged; the carve's loops are bounded.  Reproduced oddity: transform() maps
+// the position and normal SUMS by R S + t and keeps the keys, as Voxel.cpp:49-64 does.
+class DenseMap {
+public:
+    struct Cloud {
+        std::vector<double> points, normals, colors;
+        std::vector<int32_t> keys, counts;   // keys: (x, y, z) per voxel
+        int64_t size() const { return (int64_t)(points.size() / 3); }
+    };
+
+    explicit DenseMap(double voxelSize, int device = 0) {
+        reg_params p;
+        reg_default_params(&p);
+        p.cost = REG_COST_O3D_P2P;   // no field requirements
+        p.device = device;
+        reg_status s = reg_create(&p, &h_);
+        if (s == REG_OK) s = reg_dense_map_create(h_, voxelSize, &m_);
+        if (s != REG_OK) {
+            const std::string msg = h_ ? reg_last_error(h_) : "reg_create rejected the parameters";
+            release();
+            raise(s, msg);
+        }
+    }
+    ~DenseMap() { release(); }
+    DenseMap(const DenseMap&) = delete;
+    DenseMap& operator=(const DenseMap&) = delete;
+    DenseMap(DenseMap&& o) noexcept : h_(o.h_), m_(o.m_) { o.h_ = nullptr, o.m_ = nullptr; }
+    DenseMap& operator=(DenseMap&& o) noexcept {
+        if (this != &o) {
+            release();
+            h_ = o.h_, m_ = o.m_;
+            o.h_ = nullptr, o.m_ = nullptr;
+        }
+        return *this;
+    }
+
+    // VoxelizedPointCloud::insert(transform(T, cloud)); returns the number of new voxels
+    int64_t insert(const double* points, const double* normals, const double* colors, int64_t n, const double* T = nullptr) {
+        int64_t nVoxels = 0, nNew = 0;
+        check(reg_dense_map_insert(m_, points, normals, colors, n, 0, T, &nVoxels, &nNew));
+        return nNew;
+    }
+    // Submap.cpp:99-106: dense-map cropper, ColorRangeCropper, transform, insert; returns the points that passed the croppers
+    int64_t insertScan(const double* points, const double* normals, const double* colors, int64_t n,
+                       const reg_dense_scan_params& params, const double* mapToRangeSensor) {
+        int64_t nInserted = 0, nVoxels = 0;
+        check(reg_dense_map_insert_scan(m_, points, normals, colors, n, 0, &params, mapToRangeSensor, &nInserted, &nVoxels));
+        return nInserted;
+    }
+    // getKeysOfCarvedPoints + removeKey (helpers.cpp:360-390, Submap.cpp:153-156): the erased keys, (x, y, z) per voxel
+    std::vector<int32_t> carve(const double* scan, int64_t n, const double sensor[3], const reg_dense_carve_params& params) {
+        std::vector<int32_t> keys((size_t)info().n_voxels * 3);
+        int64_t k = 0;
+        check(reg_dense_map_carve(m_, scan, n, 0, sensor, &params, keys.data(), &k));
+        keys.resize((size_t)k * 3);
+        return keys;
+    }
+    void transform(const double T[16]) { check(reg_dense_map_transform(m_, T)); }
+    std::array<double, 3> center() {
+        std::array<double, 3> c{};
+        check(reg_dense_map_center(m_, c.data()));
+        return c;
+    }
+    void clear() { check(reg_dense_map_clear(m_)); }
+    reg_dense_map_info info() const {
+        reg_dense_map_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_dense_map_get_info(m_, &i));
+        return i;
+    }
+    int64_t size() const { return info().n_voxels; }
+    bool empty() const { return size() == 0; }
+    // toPointCloud (+ keys and counts)
+    Cloud exportCloud(bool wantKeys = false, bool wantCounts = false) {
+        const reg_dense_map_info i = info();
+        const size_t rows = (size_t)i.n_voxels;
+        Cloud out;
+        out.points.resize(rows * 3);
+        if (i.has_normals) out.normals.resize(rows * 3);
+        if (i.has_colors) out.colors.resize(rows * 3);
+        if (wantKeys) out.keys.resize(rows * 3);
+        if (wantCounts) out.counts.resize(rows);
+        int64_t k = 0;
+        check(reg_dense_map_export(m_, 0, out.points.data(), i.has_normals ? out.normals.data() : nullptr,
+                                   i.has_colors ? out.colors.data() : nullptr, wantKeys ? out.keys.data() : nullptr,
+                                   wantCounts ? out.counts.data() : nullptr, i.n_voxels, &k));
+        return out;
+    }
+    // removeDuplicatePointsWithinSameVoxels (Voxel.cpp:162-191): ascending indices of the first point of every voxel
+    std::vector<int32_t> dedupVoxels(const double* points, int64_t n, double voxelSize) {
+        std::vector<int32_t> idx((size_t)(n > 0 ? n : 0));
+        int64_t k = 0;
+        check(reg_dedup_voxels(h_, points, n, 0, voxelSize, idx.data(), &k));
+        idx.resize((size_t)k);
+        return idx;
+    }
+    reg_dense_map* map() const { return m_; }
+    reg_handle* handle() const { return h_; }
+
+private:
+    static void raise(reg_status s, const std::string& msg) {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    void check(reg_status s) const {
+        if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    void release() {
+        if (m_) reg_dense_map_destroy(m_);   // the map goes before its handle
+        if (h_) reg_destroy(h_);
+        m_ = nullptr, h_ = nullptr;
+    }
+    reg_handle* h_ = nullptr;
+    reg_dense_map* m_ = nullptr;
+};
+
 }  // namespace o3dreg

@@ -1275,6 +1275,110 @@ REG_API void reg_host_octree_root(const float min[3], const float max[3], int ce
                                   float* radius);
 REG_API reg_status reg_host_octree_random_picks(const int64_t* sizes, int64_t n_leaves, int64_t* picks);
 
+/* ---- the dense map: VoxelizedPointCloud insert, carve, export -----------------------------------------
+   The reference keeps a second, dense map per submap (o3d_slam::VoxelizedPointCloud, open3d_slam/src/Voxel.cpp:38-114),
+   filled from every raw scan by its own worker (SlamWrapper.cpp:963-986 -> Submap::insertScanDenseMap, Submap.cpp:98-113).
+   reg_dense_map is that object, resident on the device across calls.  It is created from a handle, uses that handle's
+   stream and working storage, is as non-re-entrant as the handle, and MUST BE DESTROYED BEFORE THE HANDLE.  Several maps
+   may live on one handle (one per submap); they are independent.
+
+   Storage: structure-of-arrays, sorted by ascending key: uint64 key (offset binary, z<<42 | y<<21 | x, the packing of
+   reg_voxelize_within_volume), int32 count, fp64 position / normal / colour sums (the two latter allocated when a cloud
+   first brings the field).  Every column is double-buffered: a mutating call builds its result in the spare buffers and
+   swaps at the end, so a call that fails -- on a bad point or a failed allocation -- leaves the map exactly as it was.
+   Buffers grow geometrically; at most 2^31 - 1 voxels.
+
+   Numeric contract: fp64, one rounding per operation (the build forbids contraction).
+     map key, per axis: floor(p * (1.0 / voxel_size)) (VoxelHashMap.hpp:48-51,127).  Departure: a non-finite coordinate or an
+       index outside +-(2^20 - 1) anywhere in the (transformed) input returns REG_BAD_ARGUMENT and leaves the map unchanged
+       (the reference casts to int there).
+     insert (VoxelizedPointCloud::insert, Voxel.cpp:66-88): a voxel's position, normal and colour sums are running sums in
+       the order the points arrived; onto an existing voxel the new points are added one by one, ((S + p1) + p2) ..., not
+       S + (p1 + p2 + ...).  count counts every point; a cloud without normals / colours adds nothing to those sums but still
+       counts; has_normals / has_colors are sticky once a cloud brought the field; NaN normals are added as they are.
+     transform before the insert (T == NULL: identity, no transform pass): the formula of reg_overlap_indices,
+         w  = ((T30*x + T31*y) + T32*z) + T33,   x' = (((T00*x + T01*y) + T02*z) + T03) / w   (y', z' alike);
+       normals (T (n, 0)).head<3>(): nx' = (T00*nx + T01*ny) + T02*nz; colours pass through (helpers.cpp:283-318).
+       Departure: the identity shortcut of helpers.cpp:285-288, which appends the cloud to a copy of itself, is not reproduced.
+     export (toPointCloud, Voxel.cpp:90-114): position, normal, colour = sum / count; normals are not re-normalised.
+       Departure: voxels come in ascending key order, i.e. ascending (z, y, x) (the reference: std::unordered_map order).
+     carve (getKeysOfCarvedPoints, helpers.cpp:360-390): per scan point, length, direction and the skip of zero-length or
+       non-finite rays as reg_carve_indices; step = 2 r; reach = max(step, min(length - truncation, max_ray)); distance is
+       the running sum 0, +step, +step ... while distance < reach; sample = distance*dir + sensor.  Per sample the
+       neighbourhood of VoxelHashMap.cpp:13-45: per-axis offsets are the running sum -r, +v, +v ... while <= r
+       (reg_host_dense_offsets); for each test point t = sample + offset the lookup key is floor(t / v) per axis -- a
+       DIVISION, unlike the map key -- the centre k*v + v*0.5, and t is accepted if sqrt((d0^2 + d1^2) + d2^2) <= r.  The
+       sample's own floor(sample / v) key is always looked up too.  Every key found in the map is erased; lookup keys
+       outside +-(2^20 - 1) cannot be in the map and are skipped.  Departure (loop bounds): r and max_ray finite and > 0
+       (the reference loops forever at r <= 0), truncation finite, at most 16 offsets per axis, max_ray / step <= 65536,
+       else REG_BAD_ARGUMENT.  Result: the number of erased voxels and, optionally, their keys in ascending key order.
+     de-duplication (removeDuplicatePointsWithinSameVoxels, Voxel.cpp:162-191): the lowest-index point of every voxel,
+       map-key formula; ascending indices.
+     transform of the map (VoxelizedPointCloud::transform, Voxel.cpp:49-64), REPRODUCED LITERALLY: keys stay; position sum
+       and normal sum each become R S + t, per row ((R0*x + R1*y) + R2*z) + t; colour sum and count untouched.  This is the
+       reference's behaviour and it is wrong for any t != 0 (a sum of k points should move by k t, a normal by none, and
+       the keys should follow).
+     centre (computeCenter, helpers.cpp:392-402): the sum of the averaged positions in key order, divided by (n + 1e-6).
+   Matrices: const double[16], column-major.  Clouds: n x 3 doubles each (points, normals, colours); on_device covers every
+   cloud array and every array output of a call.  n == 0 is REG_OK and a no-op; an empty map carves to 0.  Plain argument
+   checks come before any device work (REG_BAD_ARGUMENT even on a handle without a device); then REG_DEVICE_ERROR. */
+typedef struct reg_dense_map reg_dense_map;
+typedef struct {
+    int32_t  struct_size;          /* = sizeof(reg_dense_scan_params); checked */
+    int32_t  reserved;
+    reg_crop crop;                 /* denseMapCropper_; its centre is the caller's (the reference sets the identity pose) */
+    double   rgb_min[3];           /* ColorRangeCropper (croppers.cpp:178-239): rgb_min <= c <= rgb_max on every channel; */
+    double   rgb_max[3];           /*   a cloud without colours passes whole */
+} reg_dense_scan_params;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_dense_carve_params); checked */
+    int32_t reserved;
+    double  neighborhood_radius;   /* neighborhoodRadiusDenseMap_ */
+    double  max_ray;               /* maxRaytracingLength_ */
+    double  truncation;            /* truncationDistance_ */
+} reg_dense_carve_params;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_dense_map_info), set by the caller */
+    int32_t has_normals;
+    int32_t has_colors;
+    int32_t reserved;
+    int64_t n_voxels;
+    int64_t capacity;              /* rows the current buffers hold */
+    double  voxel_size;
+} reg_dense_map_info;
+REG_API reg_status reg_dense_map_create(reg_handle* h, double voxel_size, reg_dense_map** out);
+REG_API void reg_dense_map_destroy(reg_dense_map* m);   /* before reg_destroy of its handle */
+REG_API reg_status reg_dense_map_clear(reg_dense_map* m);   /* drops the voxels; the has-field flags stay, as the reference's */
+REG_API reg_status reg_dense_map_insert(reg_dense_map* m, const double* xyz, const double* normals, const double* colors,
+                                        int64_t n, int on_device, const double T[16] /* NULL: identity */, int64_t* n_voxels,
+                                        int64_t* n_new);
+/* no crop, colours within [0, 1] */
+REG_API void reg_default_dense_scan_params(reg_dense_scan_params* p);
+/* Submap.cpp:99-106 in one call: crop, ColorRangeCropper, transform, insert; the intermediate clouds never leave the device.
+   *n_inserted: points that passed both croppers. */
+REG_API reg_status reg_dense_map_insert_scan(reg_dense_map* m, const double* xyz, const double* normals, const double* colors,
+                                             int64_t n, int on_device, const reg_dense_scan_params* params,
+                                             const double T_map_to_sensor[16] /* NULL: identity */, int64_t* n_inserted,
+                                             int64_t* n_voxels);
+/* SpaceCarvingParameters as shipped (Parameters.hpp:88-95): radius 0.1, max ray 20, truncation 0.1 */
+REG_API void reg_default_dense_carve_params(reg_dense_carve_params* p);
+REG_API reg_status reg_dense_map_carve(reg_dense_map* m, const double* scan_xyz, int64_t n_scan, int on_device,
+                                       const double sensor[3], const reg_dense_carve_params* params,
+                                       int32_t* removed_keys /* may be NULL; n_voxels x 3: (x, y, z) per row */,
+                                       int64_t* n_removed);
+REG_API reg_status reg_dense_map_transform(reg_dense_map* m, const double T[16]);
+REG_API reg_status reg_dense_map_center(reg_dense_map* m, double center[3]);
+REG_API reg_status reg_dense_map_get_info(const reg_dense_map* m, reg_dense_map_info* info);
+/* Any output may be NULL; normals / colors are written only when the map has met the field (reg_dense_map_get_info);
+   keys: n x 3 int32 (x, y, z); capacity_rows < n_voxels returns REG_BAD_ARGUMENT. */
+REG_API reg_status reg_dense_map_export(reg_dense_map* m, int on_device, double* xyz, double* normals, double* colors,
+                                        int32_t* keys, int32_t* counts, int64_t capacity_rows, int64_t* n_out);
+REG_API reg_status reg_dedup_voxels(reg_handle* h, const double* xyz, int64_t n, int on_device, double voxel_size,
+                                    int32_t* kept_idx /* capacity n */, int64_t* n_kept);
+/* The per-axis neighbourhood offsets of the carve, on the host: returns their number (offsets may be NULL; capacity 16),
+   or -1 for arguments reg_dense_map_carve refuses. */
+REG_API int32_t reg_host_dense_offsets(double neighborhood_radius, double voxel_size, double* offsets);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ import ctypes as C
 import math
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -281,6 +282,57 @@ class ScanResult(C.Structure):
                 ("n_match", C.c_int64)]
 
 
+class DenseScanParams(C.Structure):
+    """reg_dense_scan_params (include/o3dslam_reg.h): the dense-map cropper and the colour range of insert_scan."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("crop", RegCrop), ("rgb_min", C.c_double * 3),
+                ("rgb_max", C.c_double * 3)]
+
+
+class DenseCarveParams(C.Structure):
+    """reg_dense_carve_params (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("neighborhood_radius", C.c_double),
+                ("max_ray", C.c_double), ("truncation", C.c_double)]
+
+
+class DenseMapInfo(C.Structure):
+    """reg_dense_map_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("has_colors", C.c_int32), ("reserved", C.c_int32),
+                ("n_voxels", C.c_int64), ("capacity", C.c_int64), ("voxel_size", C.c_double)]
+
+
+def default_dense_scan_params(crop=None, rgb_min=None, rgb_max=None) -> DenseScanParams:
+    """reg_default_dense_scan_params (no crop, colours within [0, 1]); crop: a crop dict of Registration.set_target_f64."""
+    p = DenseScanParams()
+    load_library().reg_default_dense_scan_params(C.byref(p))
+    if crop is not None:
+        p.crop = Registration._crop_struct(crop)
+    for name, v in (("rgb_min", rgb_min), ("rgb_max", rgb_max)):
+        if v is not None:
+            setattr(p, name, (C.c_double * 3)(*[float(x) for x in v]))
+    return p
+
+
+def default_dense_carve_params(**overrides) -> DenseCarveParams:
+    """reg_default_dense_carve_params: SpaceCarvingParameters as shipped (radius 0.1, max ray 20, truncation 0.1)."""
+    p = DenseCarveParams()
+    load_library().reg_default_dense_carve_params(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("neighborhood_radius", "max_ray", "truncation"):
+            raise TypeError(f"unknown carve parameter {k}")
+        setattr(p, k, float(v))
+    return p
+
+
+def host_dense_offsets(neighborhood_radius: float, voxel_size: float) -> np.ndarray:
+    """reg_host_dense_offsets: the per-axis neighbourhood offsets of DenseMap.carve (no device); ValueError for arguments the
+    carve refuses (more than 16 offsets, radius or voxel size not finite and > 0)."""
+    out = np.zeros(16, np.float64)
+    k = load_library().reg_host_dense_offsets(float(neighborhood_radius), float(voxel_size), out.ctypes.data_as(C.c_void_p))
+    if k < 0:
+        raise ValueError(f"no neighbourhood for radius {neighborhood_radius!r}, voxel size {voxel_size!r}")
+    return out[:k].copy()
+
+
 def host_scan_key(seed: int, index: int) -> int:
     """reg_host_scan_key: the 64-bit key of reg_random_down_sample for point `index` (no device)."""
     return int(load_library().reg_host_scan_key(int(seed), int(index)))
@@ -392,7 +444,11 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_overlap_indices", "reg_set_pair_overlap_f64", "reg_get_source_source_indices",
            "reg_compute_fpfh", "reg_match_features", "reg_ransac_correspondences", "reg_host_ransac_est_k",
            "reg_voxel_down_sample", "reg_random_down_sample", "reg_host_scan_key", "reg_default_scan_params",
-           "reg_process_scan"]
+           "reg_process_scan",
+           "reg_dense_map_create", "reg_dense_map_destroy", "reg_dense_map_clear", "reg_dense_map_insert",
+           "reg_default_dense_scan_params", "reg_dense_map_insert_scan", "reg_default_dense_carve_params",
+           "reg_dense_map_carve", "reg_dense_map_transform", "reg_dense_map_center", "reg_dense_map_get_info",
+           "reg_dense_map_export", "reg_dedup_voxels", "reg_host_dense_offsets"]
 
 
 def lib_path() -> str:
@@ -490,6 +546,25 @@ def load_library():
     lib.reg_default_scan_params.argtypes = [C.POINTER(ScanParams)]
     lib.reg_default_scan_params.restype = None
     lib.reg_process_scan.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.POINTER(ScanParams), vp, vp, vp, C.POINTER(ScanResult)]
+    pd16, pi64 = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+    lib.reg_dense_map_create.argtypes = [vp, C.c_double, C.POINTER(vp)]
+    lib.reg_dense_map_destroy.argtypes = [vp]
+    lib.reg_dense_map_destroy.restype = None
+    lib.reg_dense_map_clear.argtypes = [vp]
+    lib.reg_dense_map_insert.argtypes = [vp, vp, vp, vp, i64, C.c_int, pd16, pi64, pi64]
+    lib.reg_default_dense_scan_params.argtypes = [C.POINTER(DenseScanParams)]
+    lib.reg_default_dense_scan_params.restype = None
+    lib.reg_dense_map_insert_scan.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.POINTER(DenseScanParams), pd16, pi64, pi64]
+    lib.reg_default_dense_carve_params.argtypes = [C.POINTER(DenseCarveParams)]
+    lib.reg_default_dense_carve_params.restype = None
+    lib.reg_dense_map_carve.argtypes = [vp, vp, i64, C.c_int, pd16, C.POINTER(DenseCarveParams), vp, pi64]
+    lib.reg_dense_map_transform.argtypes = [vp, pd16]
+    lib.reg_dense_map_center.argtypes = [vp, pd16]
+    lib.reg_dense_map_get_info.argtypes = [vp, C.POINTER(DenseMapInfo)]
+    lib.reg_dense_map_export.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, i64, pi64]
+    lib.reg_dedup_voxels.argtypes = [vp, vp, i64, C.c_int, C.c_double, vp, pi64]
+    lib.reg_host_dense_offsets.argtypes = [C.c_double, C.c_double, vp]
+    lib.reg_host_dense_offsets.restype = C.c_int32
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -876,6 +951,8 @@ class Registration:
 
     def close(self):
         if getattr(self, "_h", None):
+            for m in list(getattr(self, "_dense_maps", ())):   # a reg_dense_map is destroyed before its handle
+                m.close()
             self._lib.reg_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1095,6 +1172,23 @@ class Registration:
         self.n_source = self.n_source_kept
         self._check(st)
         return res
+
+    # ---- the dense map: maps are DenseMap objects on this handle ----
+    def dedup_voxels(self, xyz, voxel_size):
+        """removeDuplicatePointsWithinSameVoxels (Voxel.cpp:162-191) on the device: the ascending indices of the
+        lowest-index point of every voxel, key floor(p * (1 / voxel_size))."""
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        idx = np.empty(max(x.shape[0], 1), np.int32)
+        n = C.c_int64(0)
+        self._check(self._lib.reg_dedup_voxels(self._h, _ptr(x), x.shape[0], 0, float(voxel_size), _ptr(idx), C.byref(n)))
+        return idx[:int(n.value)].copy()
+
+    def dedup_voxels_device(self, xyz_ptr, n, voxel_size, idx_ptr) -> int:
+        """As dedup_voxels with the fp64 cloud and the int32 output (capacity n) resident in HBM.  Returns n_kept."""
+        k = C.c_int64(0)
+        self._check(self._lib.reg_dedup_voxels(self._h, C.c_void_p(xyz_ptr) if xyz_ptr else None, n, 1, float(voxel_size),
+                                               C.c_void_p(idx_ptr) if idx_ptr else None, C.byref(k)))
+        return int(k.value)
 
     def target_source_indices(self):
         idx = np.empty(self.n_target_kept, np.int32)
@@ -1787,6 +1881,137 @@ class Registration:
         sums = np.zeros(32, np.float64)
         self._check(self._lib.reg_reduce_local(self._h, _ptr(_T_in(T_iter)), trim_limit, _ptr(sums)))
         return sums
+
+
+class DenseMap:
+    """One dense map (== one reg_dense_map; o3d_slam::VoxelizedPointCloud) on the handle of `reg`: per-voxel running sums
+    resident on the device, sorted by key.  It uses the stream and the working storage of `reg` and must be closed before
+    it (close() of either order is safe here: the map keeps `reg` alive and closes itself first)."""
+
+    def __init__(self, reg: Registration, voxel_size: float):
+        self._lib = load_library()
+        self.reg = reg
+        self._m = C.c_void_p()
+        reg._check(self._lib.reg_dense_map_create(reg._h, float(voxel_size), C.byref(self._m)))
+        self.voxel_size = float(voxel_size)
+        if not hasattr(reg, "_dense_maps"):
+            reg._dense_maps = weakref.WeakSet()
+        reg._dense_maps.add(self)
+
+    def close(self):
+        if getattr(self, "_m", None) and getattr(self.reg, "_h", None):
+            self._lib.reg_dense_map_destroy(self._m)
+        self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        self.reg._check(st)
+
+    @staticmethod
+    def _f64(a):
+        return np.ascontiguousarray(a, np.float64).reshape(-1, 3) if a is not None else None
+
+    def insert(self, xyz, normals=None, colors=None, T=None):
+        """VoxelizedPointCloud::insert of T * cloud (T None: no transform).  Returns (n_voxels, n_new)."""
+        x, nr, cl = self._f64(xyz), self._f64(normals), self._f64(colors)
+        return self._insert(_ptr(x), _ptr(nr), _ptr(cl), x.shape[0], 0, T)
+
+    def insert_device(self, xyz_ptr, n, nrm_ptr=None, col_ptr=None, T=None):
+        """As insert with the fp64 arrays (n x 3 each) resident in HBM."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._insert(vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr), n, 1, T)
+
+    def _insert(self, x, nr, cl, n, on_device, T):
+        nv, nn = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_dense_map_insert(self._m, x, nr, cl, n, on_device, _T_in_f64(T), C.byref(nv), C.byref(nn)))
+        return int(nv.value), int(nn.value)
+
+    def insert_scan(self, xyz, params: DenseScanParams, normals=None, colors=None, T=None):
+        """Submap.cpp:99-106: dense-map cropper, ColorRangeCropper, transform by T (map to sensor), insert.  Returns
+        (n_inserted, n_voxels)."""
+        x, nr, cl = self._f64(xyz), self._f64(normals), self._f64(colors)
+        return self._insert_scan(_ptr(x), _ptr(nr), _ptr(cl), x.shape[0], 0, params, T)
+
+    def insert_scan_device(self, xyz_ptr, n, params: DenseScanParams, nrm_ptr=None, col_ptr=None, T=None):
+        """As insert_scan with the fp64 arrays (n x 3 each) resident in HBM."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._insert_scan(vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr), n, 1, params, T)
+
+    def _insert_scan(self, x, nr, cl, n, on_device, params, T):
+        params.struct_size = C.sizeof(DenseScanParams)
+        ni, nv = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.reg_dense_map_insert_scan(self._m, x, nr, cl, n, on_device, C.byref(params), _T_in_f64(T),
+                                                        C.byref(ni), C.byref(nv)))
+        return int(ni.value), int(nv.value)
+
+    def carve(self, scan_xyz, sensor, params: "DenseCarveParams | None" = None, want_keys=True):
+        """getKeysOfCarvedPoints + removeKey (helpers.cpp:360-390, Submap.cpp:153-156).  Returns the erased keys (k x 3
+        int32, (x, y, z) per row, ascending key order), or their number with want_keys=False."""
+        x = self._f64(scan_xyz)
+        keys = np.empty((max(self.info().n_voxels, 1), 3), np.int32) if want_keys else None
+        k = self._carve(_ptr(x), x.shape[0], 0, sensor, params, _ptr(keys))
+        return keys[:k].copy() if want_keys else k
+
+    def carve_device(self, scan_ptr, n_scan, sensor, params: "DenseCarveParams | None" = None, keys_ptr=None) -> int:
+        """As carve with the fp64 scan and the int32 key output (n_voxels x 3, may be None) resident in HBM.  Returns
+        n_removed."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._carve(vp(scan_ptr), n_scan, 1, sensor, params, vp(keys_ptr))
+
+    def _carve(self, x, n, on_device, sensor, params, keys):
+        p = params if params is not None else default_dense_carve_params()
+        p.struct_size = C.sizeof(DenseCarveParams)
+        sen = (C.c_double * 3)(*[float(v) for v in sensor])
+        k = C.c_int64(0)
+        self._check(self._lib.reg_dense_map_carve(self._m, x, n, on_device, sen, C.byref(p), keys, C.byref(k)))
+        return int(k.value)
+
+    def transform(self, T):
+        """VoxelizedPointCloud::transform, literally: every position and normal SUM becomes R S + t; keys stay."""
+        self._check(self._lib.reg_dense_map_transform(self._m, _T_in_f64(T)))
+
+    def center(self) -> np.ndarray:
+        """computeCenter (helpers.cpp:392-402)."""
+        c = (C.c_double * 3)()
+        self._check(self._lib.reg_dense_map_center(self._m, c))
+        return np.array(c, np.float64)
+
+    def clear(self):
+        self._check(self._lib.reg_dense_map_clear(self._m))
+
+    def info(self) -> DenseMapInfo:
+        i = DenseMapInfo()
+        i.struct_size = C.sizeof(DenseMapInfo)
+        self._check(self._lib.reg_dense_map_get_info(self._m, C.byref(i)))
+        return i
+
+    def export(self, want_keys=True, want_counts=True):
+        """toPointCloud (+ raw keys and counts): dict(xyz, normals, colors, keys, counts) in ascending key order; normals /
+        colors are None while the map has not met the field."""
+        i = self.info()
+        n = int(i.n_voxels)
+        f = lambda on, w, t: np.empty((max(n, 1), w), t) if on else None
+        x, nr, cl = f(True, 3, np.float64), f(i.has_normals, 3, np.float64), f(i.has_colors, 3, np.float64)
+        ky, ct = f(want_keys, 3, np.int32), f(want_counts, 1, np.int32)
+        k = C.c_int64(0)
+        self._check(self._lib.reg_dense_map_export(self._m, 0, _ptr(x), _ptr(nr), _ptr(cl), _ptr(ky), _ptr(ct), max(n, 1),
+                                                   C.byref(k)))
+        cut = lambda a: a[:int(k.value)] if a is not None else None
+        return dict(xyz=cut(x), normals=cut(nr), colors=cut(cl), keys=cut(ky),
+                    counts=cut(ct).reshape(-1) if ct is not None else None)
+
+    def export_device(self, capacity_rows, xyz_ptr=None, nrm_ptr=None, col_ptr=None, keys_ptr=None, counts_ptr=None) -> int:
+        """As export into arrays resident in HBM (capacity_rows rows each; any may be None).  Returns n_voxels."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        k = C.c_int64(0)
+        self._check(self._lib.reg_dense_map_export(self._m, 1, vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr), vp(keys_ptr),
+                                                   vp(counts_ptr), int(capacity_rows), C.byref(k)))
+        return int(k.value)
 
 
 def dist_unique_id() -> bytes:

@@ -1,0 +1,449 @@
+// host_densemap.hpp -- the dense map on the device: reg_dense_map (o3d_slam::VoxelizedPointCloud, Voxel.cpp:38-114)
+// with insert, insert_scan (Submap.cpp:99-106), carve (helpers.cpp:360-390), transform, centre, export; reg_dedup_voxels
+// Part of the single translation unit reg_core.hip (included there, after the other host headers; not a standalone header).
+#pragma once
+
+// One side of the double-buffered columns.  Every mutating call builds its result in the spare side and swaps at the end,
+// so a call that fails leaves the map as it was.
+struct DmSide {
+    DevBuf key, cnt, pos, nrm, col;
+};
+struct reg_dense_map {
+    reg_handle* h = nullptr;
+    double voxel = 0.0, inv = 0.0;   // inv = 1.0 / voxel (VoxelHashMap.hpp:43-45)
+    int64_t n = 0;                   // voxels
+    int cur = 0;                     // the side that holds the map
+    bool has_nrm = false, has_col = false;   // sticky (isHasNormals_ / isHasColors_)
+    DmSide side[2];
+};
+
+constexpr int64_t kDmMaxRows = 0x7fffffffLL;
+constexpr size_t kDmMinRows = 1024;
+
+// grows geometrically: at least `rows` rows of `row_bytes`, at least twice what the buffer held
+static hipError_t dm_grow(DevBuf& b, size_t rows, size_t row_bytes) {
+    if (b.cap >= rows * row_bytes) return hipSuccess;
+    const size_t want = std::max(std::max(rows, 2 * (b.cap / row_bytes)), kDmMinRows);
+    return b.reserve(std::min<size_t>(want, (size_t)kDmMaxRows) * row_bytes);
+}
+static hipError_t dm_reserve_spare(reg_dense_map* m, size_t rows, bool nrm, bool col) {
+    DmSide& s = m->side[m->cur ^ 1];
+    hipError_t e = dm_grow(s.key, rows, 8);
+    if (e == hipSuccess) e = dm_grow(s.cnt, rows, 4);
+    if (e == hipSuccess) e = dm_grow(s.pos, rows, 24);
+    if (e == hipSuccess && nrm) e = dm_grow(s.nrm, rows, 24);
+    if (e == hipSuccess && col) e = dm_grow(s.col, rows, 24);
+    return e;
+}
+static DmCols dm_cols(reg_dense_map* m, int side, bool nrm, bool col) {
+    DmSide& s = m->side[side];
+    return DmCols{s.key.as<uint64_t>(), s.cnt.as<int32_t>(), s.pos.as<double>(), nrm ? s.nrm.as<double>() : nullptr,
+                  col ? s.col.as<double>() : nullptr};
+}
+static void dm_swap(reg_dense_map* m, int64_t n, bool nrm, bool col) {
+    m->cur ^= 1;
+    m->n = n;
+    m->has_nrm = nrm;
+    m->has_col = col;
+}
+static DmT dm_rows(const double* T) {   // column-major double[16] -> rows
+    DmT t;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) t.m[4 * r + c] = T[4 * c + r];
+    return t;
+}
+
+// keys (+ transformed cloud when T is given) of a device cloud, sorted with their indices, run heads and run ids.
+// Leaves dm_keys2 / dm_vals2 / dm_heads / dm_run filled; *runs = number of distinct keys.  One synchronisation.
+static reg_status dm_sorted_keys(reg_handle* h, const char* who, const double* d_xyz, const double* d_nrm, int64_t n,
+                                 const double* T, double inv, int64_t* runs) {
+    HIPCHK(h, h->dm_keys.reserve((size_t)n * 8));
+    HIPCHK(h, h->dm_keys2.reserve((size_t)n * 8));
+    HIPCHK(h, h->dm_vals.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_vals2.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_heads.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_run.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_misc.reserve(256));
+    if (T) {
+        HIPCHK(h, h->dm_tf[0].reserve((size_t)n * 24));
+        if (d_nrm) HIPCHK(h, h->dm_tf[1].reserve((size_t)n * 24));
+    }
+    DmT t;
+    std::memset(&t, 0, sizeof(t));
+    if (T) t = dm_rows(T);
+    uint64_t *keys = h->dm_keys.as<uint64_t>(), *sorted = h->dm_keys2.as<uint64_t>();
+    uint32_t *vals = h->dm_vals.as<uint32_t>(), *svals = h->dm_vals2.as<uint32_t>();
+    uint32_t *heads = h->dm_heads.as<uint32_t>(), *run = h->dm_run.as<uint32_t>();
+    HIPCHK(h, hipMemsetAsync(h->dm_misc.p, 0, 4, h->stream));
+    k_dm_keys<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, d_nrm, n, T ? 1 : 0, t, inv, h->dm_tf[0].as<double>(),
+                                                  h->dm_tf[1].as<double>(), keys, vals, h->dm_misc.as<uint32_t>());
+    uint32_t bad = 0;
+    HIPCHK(h, hipMemcpyAsync(&bad, h->dm_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
+    REGCHK(sort_pairs(h, h->rp_tmp, keys, sorted, vals, svals, (size_t)n, 0, 3 * kVoxBits));
+    k_vox_heads<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads);
+    REGCHK(scan_excl(h, h->rp_tmp, heads, run, (size_t)n));
+    uint32_t tail[2];
+    REGCHK(flag_total_async(h, heads, run, n, tail));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (bad) {
+        h->err = std::string(who) + ((bad & 1u) ? ": non-finite coordinate" : ": voxel index outside +-2^20");
+        return REG_BAD_ARGUMENT;
+    }
+    *runs = flag_total(tail);
+    return REG_OK;
+}
+
+// VoxelizedPointCloud::insert of a device cloud (n > 0), after the optional transform
+static reg_status dm_insert_device(reg_dense_map* m, const char* who, const double* d_xyz, const double* d_nrm,
+                                   const double* d_col, int64_t n, const double* T, int64_t* n_new_out) {
+    reg_handle* h = m->h;
+    int64_t runs = 0;
+    REGCHK(dm_sorted_keys(h, who, d_xyz, d_nrm, n, T, m->inv, &runs));
+    const double* px = T ? h->dm_tf[0].as<double>() : d_xyz;
+    const double* pn = d_nrm ? (T ? h->dm_tf[1].as<double>() : d_nrm) : nullptr;
+    HIPCHK(h, h->dm_rank.reserve((size_t)runs * 4));
+    HIPCHK(h, h->dm_new.reserve((size_t)runs * 4));
+    HIPCHK(h, h->dm_newoff.reserve((size_t)runs * 4));
+    HIPCHK(h, h->dm_newkeys.reserve((size_t)runs * 8));
+    HIPCHK(h, h->dm_mark.reserve((size_t)std::max<int64_t>(m->n, 1) * 4));
+    const uint64_t* sorted = h->dm_keys2.as<uint64_t>();
+    const uint32_t *svals = h->dm_vals2.as<uint32_t>(), *heads = h->dm_heads.as<uint32_t>(), *run = h->dm_run.as<uint32_t>();
+    uint32_t *rank = h->dm_rank.as<uint32_t>(), *is_new = h->dm_new.as<uint32_t>(), *new_off = h->dm_newoff.as<uint32_t>();
+    uint32_t* touched = h->dm_mark.as<uint32_t>();
+    uint64_t* new_keys = h->dm_newkeys.as<uint64_t>();
+    const DmCols in = dm_cols(m, m->cur, m->has_nrm, m->has_col);
+    if (m->n > 0) HIPCHK(h, hipMemsetAsync(touched, 0, (size_t)m->n * 4, h->stream));
+    k_dm_rank<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads, run, in.key, m->n, rank, is_new, touched);
+    REGCHK(scan_excl(h, h->rp_tmp, is_new, new_off, (size_t)runs));
+    uint32_t tail[2];
+    REGCHK(flag_total_async(h, is_new, new_off, runs, tail));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    const int64_t n_new = flag_total(tail), total = m->n + n_new;
+    if (total > kDmMaxRows) {
+        h->err = std::string(who) + ": the map would exceed 2^31 - 1 voxels";
+        return REG_BAD_ARGUMENT;
+    }
+    const bool nrm = m->has_nrm || pn, col = m->has_col || d_col;
+    HIPCHK(h, dm_reserve_spare(m, (size_t)total, nrm, col));
+    const DmCols out = dm_cols(m, m->cur ^ 1, nrm, col);
+    if (n_new > 0) k_dm_new_keys<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads, run, is_new, new_off, new_keys);
+    if (m->n > 0) k_dm_copy<<<grid_for(m->n), 256, 0, h->stream>>>(in, m->n, touched, new_keys, n_new, out);
+    k_dm_accumulate<<<grid_for(n), 256, 0, h->stream>>>(sorted, svals, n, heads, run, rank, is_new, new_off, new_keys, n_new, px,
+                                                        pn, d_col, in, out);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    dm_swap(m, total, nrm, col);
+    *n_new_out = n_new;
+    return REG_OK;
+}
+
+static bool dm_cloud_args_ok(const double* xyz, int64_t n) { return n >= 0 && n <= kDmMaxRows && (n == 0 || xyz); }
+
+// the running sum -r, +v, +v, ... while <= r (VoxelHashMap.cpp:25-27); false: more than kDmMaxOffsets
+static bool dm_offsets(double r, double v, DmOffsets* o) {
+    o->n = 0;
+    for (double d = -r; d <= r; d += v) {
+        if (o->n == kDmMaxOffsets) return false;
+        o->d[o->n++] = d;
+    }
+    for (int k = o->n; k < kDmMaxOffsets; ++k) o->d[k] = 0.0;
+    return true;
+}
+
+extern "C" {
+
+int32_t reg_host_dense_offsets(double neighborhood_radius, double voxel_size, double* offsets) {
+    DmOffsets o;
+    if (!(neighborhood_radius > 0.0) || !std::isfinite(neighborhood_radius) || !(voxel_size > 0.0) || !std::isfinite(voxel_size) ||
+        !dm_offsets(neighborhood_radius, voxel_size, &o))
+        return -1;
+    if (offsets)
+        for (int k = 0; k < o.n; ++k) offsets[k] = o.d[k];
+    return o.n;
+}
+
+reg_status reg_dense_map_create(reg_handle* h, double voxel_size, reg_dense_map** out) {
+    if (!h || !out) return REG_BAD_ARGUMENT;
+    *out = nullptr;
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) {
+        h->err = "reg_dense_map_create: voxel_size must be finite and > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    reg_dense_map* m = new reg_dense_map();   // holds no device memory until the first insert
+    m->h = h;
+    m->voxel = voxel_size;
+    m->inv = 1.0 / voxel_size;
+    *out = m;
+    return REG_OK;
+}
+
+void reg_dense_map_destroy(reg_dense_map* m) {
+    if (!m) return;
+    if (m->h->device_ok && hipSetDevice(m->h->prm.device) == hipSuccess) (void)hipStreamSynchronize(m->h->stream);
+    delete m;
+}
+
+reg_status reg_dense_map_clear(reg_dense_map* m) {
+    if (!m) return REG_BAD_ARGUMENT;
+    m->n = 0;   // VoxelHashMap::clear drops the voxels; the has-field flags stay, as isHasNormals_ / isHasColors_ do
+    return REG_OK;
+}
+
+reg_status reg_dense_map_get_info(const reg_dense_map* m, reg_dense_map_info* info) {
+    if (!m || !info || info->struct_size != (int32_t)sizeof(reg_dense_map_info)) return REG_BAD_ARGUMENT;
+    info->has_normals = m->has_nrm;
+    info->has_colors = m->has_col;
+    info->reserved = 0;
+    info->n_voxels = m->n;
+    info->capacity = (int64_t)(m->side[m->cur].key.cap / 8);
+    info->voxel_size = m->voxel;
+    return REG_OK;
+}
+
+reg_status reg_dense_map_insert(reg_dense_map* m, const double* xyz, const double* normals, const double* colors, int64_t n,
+                                int on_device, const double T[16], int64_t* n_voxels, int64_t* n_new) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (n_voxels) *n_voxels = m->n;
+    if (n_new) *n_new = 0;
+    if (!dm_cloud_args_ok(xyz, n)) {
+        h->err = "reg_dense_map_insert: 0 <= n <= 2^31 - 1 and a cloud for n > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d[3] = {xyz, normals, colors};
+    for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->dm_in[k], d[k], (size_t)n * 3, on_device, &d[k]));
+    int64_t added = 0;
+    REGCHK(dm_insert_device(m, "reg_dense_map_insert", d[0], d[1], d[2], n, T, &added));
+    if (n_voxels) *n_voxels = m->n;
+    if (n_new) *n_new = added;
+    return REG_OK;
+}
+
+void reg_default_dense_scan_params(reg_dense_scan_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(reg_dense_scan_params);
+    p->crop.type = REG_CROP_NONE;
+    for (int k = 0; k < 3; ++k) p->rgb_min[k] = 0.0, p->rgb_max[k] = 1.0;
+}
+
+reg_status reg_dense_map_insert_scan(reg_dense_map* m, const double* xyz, const double* normals, const double* colors, int64_t n,
+                                     int on_device, const reg_dense_scan_params* p, const double T_map_to_sensor[16],
+                                     int64_t* n_inserted, int64_t* n_voxels) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (n_inserted) *n_inserted = 0;
+    if (n_voxels) *n_voxels = m->n;
+    CropCfg crop;
+    bool ok = p && p->struct_size == (int32_t)sizeof(reg_dense_scan_params) && crop_cfg(&p->crop, &crop);
+    for (int k = 0; ok && k < 3; ++k) ok = !(p->rgb_min[k] != p->rgb_min[k]) && !(p->rgb_max[k] != p->rgb_max[k]);
+    if (!ok) {
+        h->err = "reg_dense_map_insert_scan: params missing, of the wrong struct_size, an unknown crop type or a NaN colour bound";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!dm_cloud_args_ok(xyz, n)) {
+        h->err = "reg_dense_map_insert_scan: 0 <= n <= 2^31 - 1 and a cloud for n > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d[3] = {xyz, normals, colors};
+    for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->dm_in[k], d[k], (size_t)n * 3, on_device, &d[k]));
+    int64_t kept = n;
+    if (crop.type != REG_CROP_NONE || d[2]) {   // denseMapCropper_->crop, then colorCropper_.crop: one order-preserving pass
+        HIPCHK(h, h->dm_keep.reserve((size_t)n * 4));
+        HIPCHK(h, h->dm_off2.reserve((size_t)n * 4));
+        uint32_t *flags = h->dm_keep.as<uint32_t>(), *offs = h->dm_off2.as<uint32_t>();
+        k_dm_scan_flags<<<grid_for(n), 256, 0, h->stream>>>(d[0], d[2], n, crop, p->rgb_min[0], p->rgb_min[1], p->rgb_min[2],
+                                                            p->rgb_max[0], p->rgb_max[1], p->rgb_max[2], flags);
+        REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n));
+        uint32_t tail[2];
+        REGCHK(flag_total_async(h, flags, offs, n, tail));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+        kept = flag_total(tail);
+        if (kept > 0 && kept < n) {
+            double* o[3] = {nullptr, nullptr, nullptr};
+            for (int k = 0; k < 3; ++k)
+                if (d[k]) {
+                    HIPCHK(h, h->dm_crop[k].reserve((size_t)kept * 24));
+                    o[k] = h->dm_crop[k].as<double>();
+                }
+            k_dm_gather3<<<grid_for(n), 256, 0, h->stream>>>(d[0], d[1], d[2], n, flags, offs, o[0], o[1], o[2]);
+            for (int k = 0; k < 3; ++k) d[k] = o[k];
+        }
+    }
+    if (kept == 0) return REG_OK;
+    int64_t added = 0;
+    REGCHK(dm_insert_device(m, "reg_dense_map_insert_scan", d[0], d[1], d[2], kept, T_map_to_sensor, &added));
+    if (n_inserted) *n_inserted = kept;
+    if (n_voxels) *n_voxels = m->n;
+    return REG_OK;
+}
+
+void reg_default_dense_carve_params(reg_dense_carve_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(reg_dense_carve_params);
+    p->neighborhood_radius = 0.1;   // SpaceCarvingParameters, Parameters.hpp:88-95
+    p->max_ray = 20.0;
+    p->truncation = 0.1;
+}
+
+reg_status reg_dense_map_carve(reg_dense_map* m, const double* scan_xyz, int64_t n_scan, int on_device, const double sensor[3],
+                               const reg_dense_carve_params* p, int32_t* removed_keys, int64_t* n_removed) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (n_removed) *n_removed = 0;
+    if (!p || p->struct_size != (int32_t)sizeof(reg_dense_carve_params) || !sensor || !dm_cloud_args_ok(scan_xyz, n_scan)) {
+        h->err = "reg_dense_map_carve: params / sensor missing, a wrong struct_size, or a bad scan";
+        return REG_BAD_ARGUMENT;
+    }
+    const double r = p->neighborhood_radius, step = 2.0 * r;
+    DmOffsets off;
+    // the bounds of the longest loop a lane can run: offsets per axis, samples per ray (the reference loops forever at r <= 0)
+    if (!(r > 0.0) || !std::isfinite(r) || !(p->max_ray > 0.0) || !std::isfinite(p->max_ray) || !std::isfinite(p->truncation) ||
+        !std::isfinite(step) || !dm_offsets(r, m->voxel, &off) || p->max_ray / step > 65536.0) {
+        h->err = "reg_dense_map_carve: neighborhood_radius and max_ray finite and > 0, truncation finite, at most 16 offsets per "
+                 "axis, max_ray / (2 neighborhood_radius) <= 65536";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_scan == 0 || m->n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d_scan = scan_xyz;
+    HIPCHK(h, staged_input(h, h->dm_in[0], d_scan, (size_t)n_scan * 3, on_device, &d_scan));
+    const int64_t n = m->n;
+    HIPCHK(h, h->dm_mark.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_off1.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_keep.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_off2.reserve((size_t)n * 4));
+    uint32_t *mark = h->dm_mark.as<uint32_t>(), *rem_off = h->dm_off1.as<uint32_t>();
+    uint32_t *keep = h->dm_keep.as<uint32_t>(), *keep_off = h->dm_off2.as<uint32_t>();
+    const DmCols in = dm_cols(m, m->cur, m->has_nrm, m->has_col);
+    HIPCHK(h, hipMemsetAsync(mark, 0, (size_t)n * 4, h->stream));
+    k_dm_carve<<<grid_for(n_scan, 4), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], step, p->max_ray,
+                                                           p->truncation, r, m->voxel, m->voxel * 0.5, off, in.key, n, mark);
+    REGCHK(scan_excl(h, h->rp_tmp, mark, rem_off, (size_t)n));
+    uint32_t tail[2];
+    REGCHK(flag_total_async(h, mark, rem_off, n, tail));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    const int64_t removed = flag_total(tail);
+    if (removed == 0) return REG_OK;
+    StagedOut so(h, h->dm_out, on_device);
+    const int s_keys = so.add(removed_keys, 3);
+    HIPCHK(h, so.reserve((size_t)removed));
+    HIPCHK(h, dm_reserve_spare(m, (size_t)(n - removed), m->has_nrm, m->has_col));
+    const DmCols out = dm_cols(m, m->cur ^ 1, m->has_nrm, m->has_col);
+    k_dm_keep_flags<<<grid_for(n), 256, 0, h->stream>>>(mark, n, keep);
+    REGCHK(scan_excl(h, h->rp_tmp, keep, keep_off, (size_t)n));
+    k_dm_erase<<<grid_for(n), 256, 0, h->stream>>>(in, n, mark, keep_off, rem_off, out, so.at<int32_t>(s_keys));
+    HIPCHK(h, so.copy_back((size_t)removed));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    dm_swap(m, n - removed, m->has_nrm, m->has_col);
+    if (n_removed) *n_removed = removed;
+    return REG_OK;
+}
+
+reg_status reg_dense_map_transform(reg_dense_map* m, const double T[16]) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (!T) {
+        h->err = "reg_dense_map_transform: T is missing";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (m->n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, dm_reserve_spare(m, (size_t)m->n, m->has_nrm, m->has_col));
+    k_dm_transform<<<grid_for(m->n), 256, 0, h->stream>>>(dm_cols(m, m->cur, m->has_nrm, m->has_col), m->n, dm_rows(T),
+                                                          dm_cols(m, m->cur ^ 1, m->has_nrm, m->has_col));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    dm_swap(m, m->n, m->has_nrm, m->has_col);
+    return REG_OK;
+}
+
+reg_status reg_dense_map_center(reg_dense_map* m, double center[3]) {
+    if (!m || !center) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    center[0] = center[1] = center[2] = 0.0;   // an empty map: 0 / 1e-6
+    if (m->n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->dm_misc.reserve(256));
+    double* d_out = (double*)((char*)h->dm_misc.p + 64);
+    k_dm_center<<<1, 64, 0, h->stream>>>(dm_cols(m, m->cur, false, false), m->n, d_out);
+    HIPCHK(h, hipMemcpyAsync(center, d_out, 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return REG_OK;
+}
+
+reg_status reg_dense_map_export(reg_dense_map* m, int on_device, double* xyz, double* normals, double* colors, int32_t* keys,
+                                int32_t* counts, int64_t capacity_rows, int64_t* n_out) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (n_out) *n_out = 0;
+    if (capacity_rows < m->n) {
+        h->err = "reg_dense_map_export: capacity_rows is below the number of voxels";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_out) *n_out = m->n;
+    if (m->n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    StagedOut so(h, h->dm_out, on_device);   // normals / colours only when the map has met the field
+    const int s_xyz = so.add(xyz, 3), s_nrm = so.add(m->has_nrm ? normals : nullptr, 3),
+              s_col = so.add(m->has_col ? colors : nullptr, 3), s_keys = so.add(keys, 3), s_cnt = so.add(counts, 1);
+    HIPCHK(h, so.reserve((size_t)m->n));
+    k_dm_export<<<grid_for(m->n), 256, 0, h->stream>>>(dm_cols(m, m->cur, m->has_nrm, m->has_col), m->n, so.at<double>(s_xyz),
+                                                       so.at<double>(s_nrm), so.at<double>(s_col), so.at<int32_t>(s_keys),
+                                                       so.at<int32_t>(s_cnt));
+    HIPCHK(h, so.copy_back((size_t)m->n));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    return REG_OK;
+}
+
+reg_status reg_dedup_voxels(reg_handle* h, const double* xyz, int64_t n, int on_device, double voxel_size, int32_t* kept_idx,
+                            int64_t* n_kept) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (n_kept) *n_kept = 0;
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size) || !dm_cloud_args_ok(xyz, n) || (n > 0 && !kept_idx)) {
+        h->err = "reg_dedup_voxels: voxel_size finite and > 0, 0 <= n <= 2^31 - 1, a cloud and an index array for n > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d_xyz = xyz;
+    HIPCHK(h, staged_input(h, h->dm_in[0], d_xyz, (size_t)n * 3, on_device, &d_xyz));
+    int64_t runs = 0;
+    REGCHK(dm_sorted_keys(h, "reg_dedup_voxels", d_xyz, nullptr, n, nullptr, 1.0 / voxel_size, &runs));
+    HIPCHK(h, h->dm_mark.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm_off1.reserve((size_t)n * 4));
+    uint32_t *flags = h->dm_mark.as<uint32_t>(), *offs = h->dm_off1.as<uint32_t>();
+    StagedOut so(h, h->dm_out, on_device);
+    const int s_idx = so.add(kept_idx, 1);
+    HIPCHK(h, so.reserve((size_t)runs));
+    HIPCHK(h, hipMemsetAsync(flags, 0, (size_t)n * 4, h->stream));
+    k_dm_dedup_mark<<<grid_for(n), 256, 0, h->stream>>>(h->dm_heads.as<uint32_t>(), h->dm_vals2.as<uint32_t>(), n, flags);
+    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n));
+    k_carve_collect<<<grid_for(n), 256, 0, h->stream>>>(flags, offs, n, so.at<int32_t>(s_idx));
+    HIPCHK(h, so.copy_back((size_t)runs));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    if (n_kept) *n_kept = runs;
+    return REG_OK;
+}
+
+}  // extern "C"

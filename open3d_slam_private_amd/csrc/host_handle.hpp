@@ -126,6 +126,12 @@ struct reg_handle {
     // values, flags + offsets, min-bound rows + origin, the invalid-key word; the events of scan_prep_ms
     DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_keys, sp_keys2, sp_vals, sp_vals2, sp_flags, sp_offs, sp_part,
         sp_misc;
+    // the dense maps of this handle (host_densemap.hpp) share their working set: staged inputs (points, normals, colours),
+    // the cloud after the croppers, after the transform (points, normals); sort keys and values, run heads and ids; per run
+    // the rank, the new flag, its scan and the new keys; touched / erase marks, keep flags and the scans of both; the
+    // invalid-key word + centre; host-pointer outputs
+    DevBuf dm_in[3], dm_crop[3], dm_tf[2], dm_keys, dm_keys2, dm_vals, dm_vals2, dm_heads, dm_run, dm_rank, dm_new, dm_newoff,
+        dm_newkeys, dm_mark, dm_keep, dm_off1, dm_off2, dm_misc, dm_out;
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;

@@ -55,6 +55,7 @@ using namespace o3dreg;
 #include "kernels_fpfh.hpp"
 #include "kernels_ransac.hpp"
 #include "kernels_scanprep.hpp"
+#include "kernels_densemap.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_mem.hpp"
@@ -73,6 +74,7 @@ using namespace o3dreg;
 #include "host_fpfh.hpp"
 #include "host_ransac.hpp"
 #include "host_scanprep.hpp"
+#include "host_densemap.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -1592,17 +1592,21 @@ def computeSubmapFeatures(cloud_f64, params: "PlaceRecognitionParameters | None"
 #      DESIGN.md 5r; PARITY UNPINNED against Open3D 0.15.1) ------------------------------------------------------------------
 @dataclass
 class PointCloud:
-    """The fields of open3d::geometry::PointCloud the front end touches: points_ / normals_ n x 3, covariances_ n x 9
-    (row-major Matrix3d), all float64."""
+    """The fields of open3d::geometry::PointCloud the front end and the dense map touch: points_ / normals_ n x 3,
+    covariances_ n x 9 (row-major Matrix3d), colors_ n x 3, all float64."""
     points_: np.ndarray
     normals_: np.ndarray | None = None
     covariances_: np.ndarray | None = None
+    colors_: np.ndarray | None = None
 
     def HasNormals(self) -> bool:
         return self.normals_ is not None
 
     def HasCovariances(self) -> bool:
         return self.covariances_ is not None
+
+    def HasColors(self) -> bool:
+        return self.colors_ is not None
 
 
 @dataclass
@@ -1625,7 +1629,8 @@ def _cloud64(cloud, what="cloud") -> PointCloud:
             if cv.shape == (x.shape[0], 3, 3):
                 cv = cv.reshape(-1, 9)
         return PointCloud(x, _field64(cloud.normals_, x.shape[0], 3, f"{what}: normals_"),
-                          _field64(cv, x.shape[0], 9, f"{what}: covariances_"))
+                          _field64(cv, x.shape[0], 9, f"{what}: covariances_"),
+                          _field64(cloud.colors_, x.shape[0], 3, f"{what}: colors_"))
     if isinstance(cloud, DataPoints):
         x = _xyz64(cloud, what)
         return PointCloud(x, _field64(cloud.normals, x.shape[0], 3, f"{what}: normals"),
@@ -1736,6 +1741,248 @@ class ScanToMapIcp:
             raise _translate(e) from None
         self.icp.last_result = res
         return T, res
+
+
+# ---- the dense map: VoxelizedPointCloud, ColorRangeCropper, space carving, Submap::insertScanDenseMap (Voxel.cpp:38-191,
+#      croppers.cpp:178-239, helpers.cpp:360-402, Submap.cpp:98-113,146-157) ------------------------------------
+def _check_T(T, what):
+    if T is None:
+        return None
+    T = np.asarray(T, np.float64)
+    if T.shape != (4, 4):
+        raise InvalidParameter(f"{what} must be 4 x 4, got shape {T.shape}")
+    return T
+
+
+@dataclass
+class SpaceCarvingParameters:
+    """o3d_slam::SpaceCarvingParameters (Parameters.hpp:88-95): the fields the dense map reads."""
+    maxRaytracingLength_: float = 20.0
+    truncationDistance_: float = 0.1
+    carveSpaceEveryNscans_: int = 10
+    neighborhoodRadiusDenseMap_: float = 0.1
+
+    def check(self, voxelSize):
+        r, mr, tr = self.neighborhoodRadiusDenseMap_, self.maxRaytracingLength_, self.truncationDistance_
+        if not (_is_real(r) and math.isfinite(r) and r > 0 and _is_real(mr) and math.isfinite(mr) and mr > 0
+                and _is_real(tr) and math.isfinite(tr)):
+            raise InvalidParameter("carving: neighborhoodRadiusDenseMap_ and maxRaytracingLength_ must be finite and > 0, "
+                                   "truncationDistance_ finite (the reference loops forever at a radius <= 0)")
+        if not (_is_int(self.carveSpaceEveryNscans_) and self.carveSpaceEveryNscans_ >= 1):
+            raise InvalidParameter(f"carveSpaceEveryNscans_ must be an integer >= 1, got {self.carveSpaceEveryNscans_!r}")
+        n, d = 0, -float(r)
+        while d <= r:                     # the running sum of VoxelHashMap.cpp:25-27
+            n, d = n + 1, d + float(voxelSize)
+            if n > 16:
+                raise InvalidParameter("carving: more than 16 neighbourhood offsets per axis (radius / voxel size too large)")
+        if mr / (2.0 * r) > 65536.0:
+            raise InvalidParameter("carving: maxRaytracingLength_ / (2 neighborhoodRadiusDenseMap_) must not exceed 65536")
+
+    def params(self) -> "capi.DenseCarveParams":
+        return capi.default_dense_carve_params(neighborhood_radius=self.neighborhoodRadiusDenseMap_,
+                                               max_ray=self.maxRaytracingLength_, truncation=self.truncationDistance_)
+
+
+class ColorRangeCropper:
+    """o3d_slam::ColorRangeCropper (croppers.cpp:178-239): keeps rgbMin <= c <= rgbMax on every channel; a cloud without
+    colours passes whole.  On the device it is one stage of DenseMapBuilder.insertScanDenseMap (reg_dense_map_insert_scan);
+    getIndicesWithValidColor / crop here are the host-side views of the same rule for callers that hold numpy clouds."""
+
+    def __init__(self, rgbMin=(0.0, 0.0, 0.0), rgbMax=(1.0, 1.0, 1.0)):
+        self.setMinBounds(rgbMin)
+        self.setMaxBounds(rgbMax)
+
+    @staticmethod
+    def _bound(v, what):
+        try:
+            a = np.asarray(v, np.float64)
+        except (TypeError, ValueError):
+            a = np.zeros(0)
+        if a.shape != (3,) or np.isnan(a).any():
+            raise InvalidParameter(f"{what} must be three numbers, got {v!r}")
+        return a
+
+    def setMinBounds(self, rgbMin):
+        self.rgbMin_ = self._bound(rgbMin, "rgbMin")
+
+    def setMaxBounds(self, rgbMax):
+        self.rgbMax_ = self._bound(rgbMax, "rgbMax")
+
+    def isValidColor(self, c) -> bool:
+        c = np.asarray(c, np.float64)
+        return bool(np.all(self.rgbMin_ <= c) and np.all(c <= self.rgbMax_))
+
+    def getIndicesWithValidColor(self, cloud) -> np.ndarray:
+        c = _cloud64(cloud)
+        if not c.HasColors():
+            return np.arange(c.points_.shape[0])
+        return np.nonzero(np.all((self.rgbMin_ <= c.colors_) & (c.colors_ <= self.rgbMax_), axis=1))[0]
+
+    def crop(self, cloud) -> PointCloud:
+        c = _cloud64(cloud)
+        if not c.HasColors():
+            return c
+        idx = self.getIndicesWithValidColor(c)
+        pick = lambda a: a[idx] if a is not None else None
+        return PointCloud(c.points_[idx], pick(c.normals_), pick(c.covariances_), c.colors_[idx])
+
+
+class VoxelizedPointCloud:
+    """o3d_slam::VoxelizedPointCloud (Voxel.cpp:38-114) resident on the device (capi.DenseMap): per-voxel running sums of
+    positions, normals and colours.  `reg`: the capi.Registration whose stream and working storage the map uses (default:
+    a handle of its own).  Departures: toPointCloud emits the voxels in ascending (z, y, x) key order (the reference: hash-map
+    order); a non-finite point or a voxel index outside +-(2^20 - 1) raises InvalidParameter and leaves the map unchanged.
+    transform reproduces the reference literally: it maps every position and normal SUM by R S + t and keeps the keys,
+    which is wrong for any t != 0."""
+
+    def __init__(self, voxelSize=0.25, reg: "capi.Registration | None" = None):
+        _check_voxel_size(voxelSize)
+        self._own = reg is None
+        self._reg = reg if reg is not None else _feature_handle()
+        self.map = capi.DenseMap(self._reg, voxelSize)
+        self.voxelSize_ = float(voxelSize)
+
+    def close(self):
+        self.map.close()
+        if self._own:
+            self._reg.close()
+
+    def getVoxelSize(self) -> float:
+        return self.voxelSize_
+
+    def insert(self, cloud, T=None):
+        """VoxelizedPointCloud::insert(transform(T, cloud)) (T None: the cloud as it is).  Returns (n_voxels, n_new)."""
+        c = _cloud64(cloud)
+        try:
+            return self.map.insert(c.points_, c.normals_, c.colors_, _check_T(T, "T"))
+        except RegError as e:
+            raise _translate(e) from None
+
+    def transform(self, T):
+        try:
+            self.map.transform(_check_T(np.eye(4) if T is None else T, "T"))
+        except RegError as e:
+            raise _translate(e) from None
+
+    def toPointCloud(self) -> PointCloud:
+        e = self.map.export(want_keys=False, want_counts=False)
+        return PointCloud(e["xyz"], e["normals"], None, e["colors"])
+
+    def size(self) -> int:
+        return int(self.map.info().n_voxels)
+
+    def empty(self) -> bool:
+        return self.size() == 0
+
+    def clear(self):
+        self.map.clear()
+
+    def hasColors(self) -> bool:
+        return bool(self.map.info().has_colors)
+
+    def hasNormals(self) -> bool:
+        return bool(self.map.info().has_normals)
+
+    def computeCenter(self) -> np.ndarray:
+        """o3d_slam::computeCenter (helpers.cpp:392-402)."""
+        return self.map.center()
+
+
+def removeDuplicatePointsWithinSameVoxels(cloud, voxelSize, reg: "capi.Registration | None" = None) -> PointCloud:
+    """o3d_slam::removeDuplicatePointsWithinSameVoxels (Voxel.cpp:162-191) on the device (reg_dedup_voxels): the first point of
+    every voxel, in input order, with its normal and colour."""
+    _check_voxel_size(voxelSize)
+    c = _cloud64(cloud)
+    own = reg is None
+    reg = _feature_handle() if own else reg
+    try:
+        idx = reg.dedup_voxels(c.points_, voxelSize)
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        if own:
+            reg.close()
+    pick = lambda a: a[idx] if a is not None else None
+    return PointCloud(c.points_[idx], pick(c.normals_), pick(c.covariances_), pick(c.colors_))
+
+
+def getKeysOfCarvedPoints(scan, cloud: VoxelizedPointCloud, sensorPosition, param: "SpaceCarvingParameters | None" = None):
+    """o3d_slam::getKeysOfCarvedPoints (helpers.cpp:360-390) on the device, TOGETHER WITH the removeKey loop its only caller
+    runs on the result (Submap.cpp:153-156): the voxels are erased from `cloud` by the same call.  Returns their keys,
+    k x 3 int32 (x, y, z), in ascending (z, y, x) order (the reference: hash-set order)."""
+    param = param if param is not None else SpaceCarvingParameters()
+    param.check(cloud.voxelSize_)
+    s = np.asarray(sensorPosition, np.float64)
+    if s.shape != (3,):
+        raise InvalidParameter(f"sensorPosition must be three numbers, got shape {s.shape}")
+    try:
+        return cloud.map.carve(_cloud64(scan, "scan").points_, s, param.params())
+    except RegError as e:
+        raise _translate(e) from None
+
+
+class DenseMapBuilder:
+    """The dense-map half of o3d_slam::Submap: insertScanDenseMap (Submap.cpp:98-113) and carve (Submap.cpp:146-157) on
+    one device-resident map.  Per scan: dense-map cropper (a crop dict of capi.Registration.set_target_f64, at the pose the
+    caller gives it -- the reference sets identity), ColorRangeCropper, transform by mapToRangeSensor, insert -- one call,
+    reg_dense_map_insert_scan -- then, when nScansInsertedDenseMap_ % carveSpaceEveryNscans_ == 1 and the map is not empty,
+    the carve on the de-duplicated scan.
+
+    Oddity reproduced: the reference carves with the RAW, untransformed scan (sensor frame) against the map-frame sensor
+    position mapToRangeSensor.translation(); that is the default here.  carveInMapFrame=True transforms the scan first, which
+    is what the geometry asks for."""
+
+    def __init__(self, voxelSize=0.03, cropper=None, colorCropper: "ColorRangeCropper | None" = None,
+                 carving: "SpaceCarvingParameters | None" = None, carveInMapFrame=False, reg: "capi.Registration | None" = None):
+        self.carving_ = carving if carving is not None else SpaceCarvingParameters()
+        self.carving_.check(voxelSize)
+        if cropper is not None and not (isinstance(cropper, dict) and cropper.get("type", 0) in (0, 1, 2, 3, 4)):
+            raise InvalidParameter(f"cropper must be a crop dict with a known type, got {cropper!r}")
+        self.denseMap_ = VoxelizedPointCloud(voxelSize, reg)
+        self.denseMapCropper_ = cropper
+        self.colorCropper_ = colorCropper if colorCropper is not None else ColorRangeCropper()
+        self.carveInMapFrame = bool(carveInMapFrame)
+        self.nScansInsertedDenseMap_ = 0
+        self.lastCarvedKeys_ = None
+
+    def close(self):
+        self.denseMap_.close()
+
+    def insertScanDenseMap(self, rawScan, mapToRangeSensor, isPerformCarving=True) -> bool:
+        T = _check_T(mapToRangeSensor, "mapToRangeSensor")
+        if T is None:
+            raise InvalidParameter("mapToRangeSensor is missing")
+        c = _cloud64(rawScan, "rawScan")
+        prm = capi.default_dense_scan_params(self.denseMapCropper_, self.colorCropper_.rgbMin_, self.colorCropper_.rgbMax_)
+        try:
+            self.denseMap_.map.insert_scan(c.points_, prm, c.normals_, c.colors_, T)
+        except RegError as e:
+            raise _translate(e) from None
+        self.lastCarvedKeys_ = None
+        if isPerformCarving:
+            self.carve(c, T)
+        self.nScansInsertedDenseMap_ += 1
+        return True
+
+    def carve(self, scan: PointCloud, mapToRangeSensor):
+        """Submap::carve for the dense map (Submap.cpp:146-157)."""
+        if self.denseMap_.empty() or not (self.nScansInsertedDenseMap_ % self.carving_.carveSpaceEveryNscans_ == 1):
+            return
+        reg, x = self.denseMap_._reg, scan.points_
+        try:
+            if self.carveInMapFrame:
+                x = _transform_points(mapToRangeSensor, x)
+            x = x[reg.dedup_voxels(x, self.denseMap_.voxelSize_)]
+            self.lastCarvedKeys_ = self.denseMap_.map.carve(x, mapToRangeSensor[:3, 3], self.carving_.params())
+        except RegError as e:
+            raise _translate(e) from None
+
+
+def _transform_points(T, x):
+    """o3d_slam::transform's point formula (helpers.cpp:302-303; the contract at reg_overlap_indices), one rounding per
+    operation: w = ((T30 x + T31 y) + T32 z) + T33, x' = (((T00 x + T01 y) + T02 z) + T03) / w."""
+    w = ((T[3, 0] * x[:, 0] + T[3, 1] * x[:, 1]) + T[3, 2] * x[:, 2]) + T[3, 3]
+    return np.stack([(((T[r, 0] * x[:, 0] + T[r, 1] * x[:, 1]) + T[r, 2] * x[:, 2]) + T[r, 3]) / w for r in range(3)], axis=1)
 
 
 # ---- RANSAC registration on feature correspondences: the hypothesis loop of place recognition (PlaceRecognition.cpp:78-91;
