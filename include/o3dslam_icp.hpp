@@ -799,4 +799,115 @@ private:
     reg_dense_map* m_ = nullptr;
 };
 
+// o3d_slam::Submap's scan-matching map (mapCloud_) resident on the device (reg_map_cloud; contract in
+// include/o3dslam_reg.h): insertScan (Submap.cpp:39-96: carve, append, setPose, voxelise), setAsReference (cropSubmap +
+// initReference), transform, centre, export.  RAII, move-only.  The map lives on a registration handle: one it creates from
+// `reg` and owns, or the caller's (borrowed; the map must go before it) -- setAsReference installs the patch on that handle,
+// which handle() hands to the registration calls.  Clouds are Open3D's fp64 arrays in host memory (n x 3 doubles; covariances
+// n x 9); transforms are column-major double[16].  Followed from the reference: the carve runs when nScansInsertedMap_ %
+// carve_every_n_scans == 1 and uses the cropper pose of the previous insert.  Departures: the field set is fixed at
+// construction and a scan with other fields throws InvalidParameter; voxels come in ascending (z, y, x) order.
+class MapCloud {
+public:
+    struct Cloud {
+        std::vector<double> points, normals, covariances;
+        int64_t size() const { return (int64_t)(points.size() / 3); }
+    };
+
+    MapCloud(const reg_map_cloud_params& params, const reg_params& reg) : owns_(true) {
+        reg_status s = reg_create(&reg, &h_);
+        if (s == REG_OK) s = reg_map_cloud_create(h_, &params, &m_);
+        if (s != REG_OK) {
+            const std::string msg = h_ ? reg_last_error(h_) : "reg_create rejected the parameters";
+            release();
+            raise(s, msg);
+        }
+    }
+    MapCloud(reg_handle* handle, const reg_map_cloud_params& params) : h_(handle), owns_(false) {
+        const reg_status s = reg_map_cloud_create(h_, &params, &m_);
+        if (s != REG_OK) raise(s, h_ ? reg_last_error(h_) : "no handle");
+    }
+    ~MapCloud() { release(); }
+    MapCloud(const MapCloud&) = delete;
+    MapCloud& operator=(const MapCloud&) = delete;
+    MapCloud(MapCloud&& o) noexcept : h_(o.h_), m_(o.m_), owns_(o.owns_) { o.h_ = nullptr, o.m_ = nullptr; }
+    MapCloud& operator=(MapCloud&& o) noexcept {
+        if (this != &o) {
+            release();
+            h_ = o.h_, m_ = o.m_, owns_ = o.owns_;
+            o.h_ = nullptr, o.m_ = nullptr;
+        }
+        return *this;
+    }
+
+    // the isUseInitialMap_ branch (Submap.cpp:47-52); returns the rows of the map
+    int64_t set(const double* points, const double* normals, const double* covariances, int64_t n, double voxelSize) {
+        check(reg_map_cloud_set(m_, points, normals, covariances, n, 0, voxelSize));
+        return size();
+    }
+    // Submap::insertScan (Submap.cpp:54-95)
+    reg_map_cloud_insert_result insertScan(const double* rawScan, int64_t nRaw, const double* points, const double* normals,
+                                           const double* covariances, int64_t n, const double mapToRangeSensor[16],
+                                           bool isPerformCarving = true) {
+        reg_map_cloud_insert_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_map_cloud_insert_scan(m_, rawScan, nRaw, points, normals, covariances, n, 0, mapToRangeSensor,
+                                        isPerformCarving ? 1 : 0, &r));
+        return r;
+    }
+    // cropSubmap + open3dToPointmatcher + initReference on handle(); returns the rows of the patch
+    int64_t setAsReference(const reg_crop* crop) {
+        int64_t kept = 0;
+        check(reg_map_cloud_set_target(m_, crop, &kept));
+        return kept;
+    }
+    void transform(const double T[16]) { check(reg_map_cloud_transform(m_, T)); }
+    std::array<double, 3> center() {
+        std::array<double, 3> c{};
+        check(reg_map_cloud_center(m_, c.data()));
+        return c;
+    }
+    void clear() { check(reg_map_cloud_clear(m_)); }
+    reg_map_cloud_info info() const {
+        reg_map_cloud_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_map_cloud_get_info(m_, &i));
+        return i;
+    }
+    int64_t size() const { return info().n_rows; }
+    bool empty() const { return size() == 0; }
+    Cloud exportCloud() {
+        const reg_map_cloud_info i = info();
+        const size_t rows = (size_t)i.n_rows;
+        Cloud out;
+        out.points.resize(rows * 3);
+        if (i.has_normals) out.normals.resize(rows * 3);
+        if (i.has_covariances) out.covariances.resize(rows * 9);
+        int64_t k = 0;
+        check(reg_map_cloud_export(m_, 0, out.points.data(), i.has_normals ? out.normals.data() : nullptr,
+                                   i.has_covariances ? out.covariances.data() : nullptr, i.n_rows, &k));
+        return out;
+    }
+    reg_map_cloud* map() const { return m_; }
+    reg_handle* handle() const { return h_; }
+
+private:
+    static void raise(reg_status s, const std::string& msg) {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    void check(reg_status s) const {
+        if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    void release() {
+        if (m_) reg_map_cloud_destroy(m_);   // the map goes before its handle
+        if (h_ && owns_) reg_destroy(h_);
+        m_ = nullptr, h_ = nullptr;
+    }
+    reg_handle* h_ = nullptr;
+    reg_map_cloud* m_ = nullptr;
+    bool owns_ = false;
+};
+
 }  // namespace o3dreg

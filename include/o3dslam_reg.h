@@ -1379,6 +1379,114 @@ REG_API reg_status reg_dedup_voxels(reg_handle* h, const double* xyz, int64_t n,
    or -1 for arguments reg_dense_map_carve refuses. */
 REG_API int32_t reg_host_dense_offsets(double neighborhood_radius, double voxel_size, double* offsets);
 
+/* ---- the map cloud: Submap::mapCloud_ resident on the device -- insertScan, carve, set as target ----------
+   The scan-matching map of a submap (open3d_slam/src/Submap.cpp:39-144) and the per-scan cycle around it:
+   Submap::insertScan (transform, carve, operator+=, setPose, voxelizeInsideCroppingVolume) and cropSubmap + initReference
+   (ScanToMapRegistration.cpp:90-96).  reg_map_cloud is that object, resident on the device across calls.  It is created
+   from a handle, uses that handle's stream and working storage, is as non-re-entrant as the handle, and MUST BE DESTROYED
+   BEFORE THE HANDLE.  Several maps may live on one handle (one per submap); they are independent.
+
+   Storage: fp64 structure-of-arrays in the reference's point order: points n x 3, optional normals n x 3, optional
+   covariances n x 9 (Eigen's Matrix3d: element (r, c) at 3 c + r).  Every column is double-buffered: a mutating call builds
+   its result in the spare side and swaps at the end, so a call that fails -- a refused point, a failed allocation, a bad
+   argument found on the device -- leaves the points, the stored cropper centre and the scan counter exactly as they were.
+   Buffers grow geometrically; at most 2^31 - 1 rows, map + scan during an insert included.
+
+   Fields: the field set is fixed at creation (has_normals / has_covariances).  A cloud that brings other fields -- more or
+   fewer -- is refused with REG_BAD_ARGUMENT.  Departure: Open3D's operator+= silently drops a field that one side lacks.
+   Colours are not carried (as reg_voxelize_within_volume).
+
+   Numeric contract: fp64, one rounding per operation (the build forbids contraction).
+     transform (o3d_slam::transform, helpers.cpp:283-318; PointCloud::Transform for reg_map_cloud_transform), the formula of
+       reg_overlap_indices and the dense map:
+         w  = ((T30*x + T31*y) + T32*z) + T33,   x' = (((T00*x + T01*y) + T02*z) + T03) / w   (y', z' alike);
+       normals (T (n, 0)).head<3>(): nx' = (T00*nx + T01*ny) + T02*nz;
+       covariances R C R^T in this order: M = R C with M(r, c) = (R(r,0)*C(0,c) + R(r,1)*C(1,c)) + R(r,2)*C(2,c), then
+       C'(r, c) = (M(r,0)*R(c,0) + M(r,1)*R(c,1)) + M(r,2)*R(c,2).  The result is as symmetric as that arithmetic leaves it.
+       Departure: the identity shortcut of helpers.cpp:285-288, which appends the cloud to a copy of itself, is not reproduced.
+     reg_map_cloud_insert_scan, in the reference's order (Submap.cpp:54-95):
+       1. carve (Submap.cpp:130-144) runs only when all three hold: perform_carving, the map is non-empty, and
+          scans_inserted % carve_every_n_scans == 1.  Two consequences of that rule, followed: it never runs with
+          carve_every_n_scans == 1 (x % 1 is never 1), and it never runs on the first insert (the counter is 0).  The rays are
+          the whole transformed raw scan, not de-duplicated, from the sensor at the translation of T.  The subset of the map
+          that takes part is the map builder's volume at the pose stored by the PREVIOUS insert (at first: the centre given
+          at creation), because setPose comes after the carve (Submap.cpp:85) -- an oddity of the reference, followed.
+          Everything else is as reg_carve_indices, its refusal of a map point beyond the key range inside the volume included.
+          The survivors are compacted in their order (removeByIds).  An empty raw scan carves nothing.
+       2. append: the transformed scan rows follow the map rows (operator+=); then the stored cropper centre becomes the
+          translation of T (setPose).
+       3. voxelise: voxelizeWithinCroppingVolume with the contract of reg_voxelize_within_volume at the new centre: the
+          outside rows first, in order; then one row per occupied voxel in ascending (z, y, x); sums in row order, so
+          resident rows come before scan rows; NaN normals are skipped, the averaged normal is re-normalised, covariances
+          are averaged.  map_voxel_size <= 0 leaves the concatenation as it is (n_outside = n_rows, n_voxels = 0).  A voxel
+          index beyond +-(2^20 - 1), or a non-finite coordinate, inside the volume returns REG_BAD_ARGUMENT, map unchanged.
+       4. the scan counter goes up by one.
+       n_scan == 0 is REG_OK and a no-op (Submap.cpp:41-43): no carve, no counter, no pose.
+     reg_map_cloud_set: the isUseInitialMap_ branch (Submap.cpp:47-52): the map becomes the cloud, voxel-down-sampled as
+       reg_voxel_down_sample when voxel_size > 0 (and refused as there); it is not transformed and the counter and the
+       cropper centre are untouched.  n == 0 empties the map.
+     reg_map_cloud_set_target: exactly reg_set_target_f64 of the resident arrays as device pointers with that crop, its
+       statuses included (REG_EMPTY_TARGET for an empty map or an empty patch; the previous reference is gone either way).
+       reg_get_target_source_indices then indexes map rows, valid until the next mutating call on the map.
+     centre (GetCenter): the sequential sum of the rows in order, divided by n; an empty map gives zero.
+   Parity: PointCloud::Transform, GetCenter and operator+= live in un-vendored Open3D 0.15.1: PARITY UNPINNED, restated.
+   Matrices: const double[16], column-major.  on_device covers every cloud array and every array output of a call.  Plain
+   argument checks come before any device work (REG_BAD_ARGUMENT even on a handle without a device); then REG_DEVICE_ERROR. */
+typedef struct reg_map_cloud reg_map_cloud;
+typedef struct {
+    int32_t  struct_size;          /* = sizeof(reg_map_cloud_params); checked */
+    int32_t  has_normals;          /* the field set, fixed at creation */
+    int32_t  has_covariances;
+    int32_t  carve_every_n_scans;  /* carving_.carveSpaceEveryNscans_; >= 1 */
+    double   map_voxel_size;       /* mapBuilder_.mapVoxelSize_; <= 0: no voxelisation */
+    reg_crop crop;                 /* mapBuilderCropper_; its centre is owned by the map from then on */
+    double   carve_voxel_size;     /* carving_.voxelSize_; finite and > 0 */
+    double   carve_max_ray;        /* carving_.maxRaytracingLength_ */
+    double   carve_truncation;     /* carving_.truncationDistance_ */
+    double   carve_min_dot;        /* carving_.minDotProductWithNormal_ */
+} reg_map_cloud_params;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_map_cloud_info), set by the caller */
+    int32_t has_normals;
+    int32_t has_covariances;
+    int32_t reserved;
+    int64_t n_rows;
+    int64_t capacity;              /* rows the current buffers hold */
+    int64_t scans_inserted;        /* nScansInsertedMap_ */
+    double  crop_center[3];        /* the cropper centre the next carve uses */
+} reg_map_cloud_info;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_map_cloud_insert_result), set by the caller */
+    int32_t carved;                /* the carve rule held for this insert */
+    int64_t n_carved;              /* rows the carve removed */
+    int64_t n_outside;             /* rows outside the volume, passed through */
+    int64_t n_voxels;              /* rows that stand for one voxel each */
+    int64_t n_rows;                /* rows of the map after the call = n_outside + n_voxels */
+} reg_map_cloud_insert_result;
+/* Parameters.hpp:51-57,88-101 as shipped: map voxel 0.03, MaxRadius 20 at the origin, carve voxel 0.1, ray 20, truncation
+   0.1, min dot 0.5, every 10 scans; normals, no covariances. */
+REG_API void reg_default_map_cloud_params(reg_map_cloud_params* p);
+REG_API reg_status reg_map_cloud_create(reg_handle* h, const reg_map_cloud_params* params, reg_map_cloud** out);
+REG_API void reg_map_cloud_destroy(reg_map_cloud* m);   /* before reg_destroy of its handle */
+REG_API reg_status reg_map_cloud_clear(reg_map_cloud* m);   /* drops the points; cropper centre and scan counter stay */
+REG_API reg_status reg_map_cloud_get_info(const reg_map_cloud* m, reg_map_cloud_info* info);
+REG_API reg_status reg_map_cloud_set(reg_map_cloud* m, const double* xyz, const double* normals, const double* covs, int64_t n,
+                                     int on_device, double voxel_size);
+/* Submap::insertScan (Submap.cpp:54-95) in one call; no intermediate cloud or index list leaves the device.
+   raw_xyz: the raw scan in the sensor frame (the carve's rays; may be NULL with n_raw == 0); scan_*: the pre-processed scan
+   (the merge cloud of reg_process_scan) in the sensor frame; result may be NULL. */
+REG_API reg_status reg_map_cloud_insert_scan(reg_map_cloud* m, const double* raw_xyz, int64_t n_raw, const double* scan_xyz,
+                                             const double* scan_normals, const double* scan_covs, int64_t n_scan,
+                                             int on_device, const double T_map_to_sensor[16], int perform_carving,
+                                             reg_map_cloud_insert_result* result);
+REG_API reg_status reg_map_cloud_set_target(reg_map_cloud* m, const reg_crop* crop, int64_t* n_kept);
+REG_API reg_status reg_map_cloud_transform(reg_map_cloud* m, const double T[16]);
+REG_API reg_status reg_map_cloud_center(reg_map_cloud* m, double center[3]);
+/* Any output may be NULL; normals / covs are written only when the map has the field; capacity_rows < n_rows returns
+   REG_BAD_ARGUMENT. */
+REG_API reg_status reg_map_cloud_export(reg_map_cloud* m, int on_device, double* xyz, double* normals, double* covs,
+                                        int64_t capacity_rows, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

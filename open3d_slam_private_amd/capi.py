@@ -300,6 +300,44 @@ class DenseMapInfo(C.Structure):
                 ("n_voxels", C.c_int64), ("capacity", C.c_int64), ("voxel_size", C.c_double)]
 
 
+class MapCloudParams(C.Structure):
+    """reg_map_cloud_params (include/o3dslam_reg.h): the field set, the map builder's voxel size and cropper, the carve."""
+    _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("has_covariances", C.c_int32),
+                ("carve_every_n_scans", C.c_int32), ("map_voxel_size", C.c_double), ("crop", RegCrop),
+                ("carve_voxel_size", C.c_double), ("carve_max_ray", C.c_double), ("carve_truncation", C.c_double),
+                ("carve_min_dot", C.c_double)]
+
+
+class MapCloudInfo(C.Structure):
+    """reg_map_cloud_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("has_normals", C.c_int32), ("has_covariances", C.c_int32),
+                ("reserved", C.c_int32), ("n_rows", C.c_int64), ("capacity", C.c_int64), ("scans_inserted", C.c_int64),
+                ("crop_center", C.c_double * 3)]
+
+
+class MapCloudInsertResult(C.Structure):
+    """reg_map_cloud_insert_result (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("carved", C.c_int32), ("n_carved", C.c_int64), ("n_outside", C.c_int64),
+                ("n_voxels", C.c_int64), ("n_rows", C.c_int64)]
+
+
+def default_map_cloud_params(crop=None, **overrides) -> MapCloudParams:
+    """reg_default_map_cloud_params: the shipped map builder (voxel 0.03, MaxRadius 20, carve voxel 0.1 / ray 20 /
+    truncation 0.1 / min dot 0.5 every 10 scans; normals, no covariances); crop: a crop dict of Registration.set_target_f64."""
+    p = MapCloudParams()
+    load_library().reg_default_map_cloud_params(C.byref(p))
+    if crop is not None:
+        p.crop = Registration._crop_struct(crop)
+    for k, v in overrides.items():
+        if k in ("has_normals", "has_covariances", "carve_every_n_scans"):
+            setattr(p, k, int(v))
+        elif k in ("map_voxel_size", "carve_voxel_size", "carve_max_ray", "carve_truncation", "carve_min_dot"):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"unknown map cloud parameter {k}")
+    return p
+
+
 def default_dense_scan_params(crop=None, rgb_min=None, rgb_max=None) -> DenseScanParams:
     """reg_default_dense_scan_params (no crop, colours within [0, 1]); crop: a crop dict of Registration.set_target_f64."""
     p = DenseScanParams()
@@ -448,7 +486,10 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dense_map_create", "reg_dense_map_destroy", "reg_dense_map_clear", "reg_dense_map_insert",
            "reg_default_dense_scan_params", "reg_dense_map_insert_scan", "reg_default_dense_carve_params",
            "reg_dense_map_carve", "reg_dense_map_transform", "reg_dense_map_center", "reg_dense_map_get_info",
-           "reg_dense_map_export", "reg_dedup_voxels", "reg_host_dense_offsets"]
+           "reg_dense_map_export", "reg_dedup_voxels", "reg_host_dense_offsets",
+           "reg_default_map_cloud_params", "reg_map_cloud_create", "reg_map_cloud_destroy", "reg_map_cloud_clear",
+           "reg_map_cloud_get_info", "reg_map_cloud_set", "reg_map_cloud_insert_scan", "reg_map_cloud_set_target",
+           "reg_map_cloud_transform", "reg_map_cloud_center", "reg_map_cloud_export"]
 
 
 def lib_path() -> str:
@@ -565,6 +606,20 @@ def load_library():
     lib.reg_dedup_voxels.argtypes = [vp, vp, i64, C.c_int, C.c_double, vp, pi64]
     lib.reg_host_dense_offsets.argtypes = [C.c_double, C.c_double, vp]
     lib.reg_host_dense_offsets.restype = C.c_int32
+    lib.reg_default_map_cloud_params.argtypes = [C.POINTER(MapCloudParams)]
+    lib.reg_default_map_cloud_params.restype = None
+    lib.reg_map_cloud_create.argtypes = [vp, C.POINTER(MapCloudParams), C.POINTER(vp)]
+    lib.reg_map_cloud_destroy.argtypes = [vp]
+    lib.reg_map_cloud_destroy.restype = None
+    lib.reg_map_cloud_clear.argtypes = [vp]
+    lib.reg_map_cloud_get_info.argtypes = [vp, C.POINTER(MapCloudInfo)]
+    lib.reg_map_cloud_set.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_double]
+    lib.reg_map_cloud_insert_scan.argtypes = [vp, vp, i64, vp, vp, vp, i64, C.c_int, pd16, C.c_int,
+                                              C.POINTER(MapCloudInsertResult)]
+    lib.reg_map_cloud_set_target.argtypes = [vp, C.POINTER(RegCrop), pi64]
+    lib.reg_map_cloud_transform.argtypes = [vp, pd16]
+    lib.reg_map_cloud_center.argtypes = [vp, pd16]
+    lib.reg_map_cloud_export.argtypes = [vp, C.c_int, vp, vp, vp, i64, pi64]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -952,6 +1007,8 @@ class Registration:
     def close(self):
         if getattr(self, "_h", None):
             for m in list(getattr(self, "_dense_maps", ())):   # a reg_dense_map is destroyed before its handle
+                m.close()
+            for m in list(getattr(self, "_map_clouds", ())):   # and so is a reg_map_cloud
                 m.close()
             self._lib.reg_destroy(self._h)
             self._h = C.c_void_p()
@@ -2011,6 +2068,126 @@ class DenseMap:
         k = C.c_int64(0)
         self._check(self._lib.reg_dense_map_export(self._m, 1, vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr), vp(keys_ptr),
                                                    vp(counts_ptr), int(capacity_rows), C.byref(k)))
+        return int(k.value)
+
+
+class MapCloud:
+    """One map cloud (== one reg_map_cloud; Submap::mapCloud_, the scan-matching map of a submap) on the handle of `reg`:
+    fp64 points, optional normals and covariances resident on the device in the reference's point order.  It uses the
+    stream and the working storage of `reg` and must be closed before it (close() of either order is safe here: the map
+    keeps `reg` alive and closes itself first)."""
+
+    def __init__(self, reg: Registration, params: "MapCloudParams | None" = None):
+        self._lib = load_library()
+        self.reg = reg
+        self._m = C.c_void_p()
+        p = params if params is not None else default_map_cloud_params()
+        p.struct_size = C.sizeof(MapCloudParams)
+        reg._check(self._lib.reg_map_cloud_create(reg._h, C.byref(p), C.byref(self._m)))
+        self.params = p
+        if not hasattr(reg, "_map_clouds"):
+            reg._map_clouds = weakref.WeakSet()
+        reg._map_clouds.add(self)
+
+    def close(self):
+        if getattr(self, "_m", None) and getattr(self.reg, "_h", None):
+            self._lib.reg_map_cloud_destroy(self._m)
+        self._m = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        self.reg._check(st)
+
+    @staticmethod
+    def _f64(a, width=3):
+        return np.ascontiguousarray(a, np.float64).reshape(-1, width) if a is not None else None
+
+    def set(self, xyz, normals=None, covs=None, voxel_size=0.0):
+        """The isUseInitialMap_ branch (Submap.cpp:47-52): the map becomes the cloud, voxel-down-sampled when voxel_size > 0;
+        not transformed, the scan counter untouched.  Returns the rows of the map."""
+        x, nr, cv = self._f64(xyz), self._f64(normals), self._f64(covs, 9)
+        self._check(self._lib.reg_map_cloud_set(self._m, _ptr(x), _ptr(nr), _ptr(cv), x.shape[0], 0, float(voxel_size)))
+        return int(self.info().n_rows)
+
+    def set_device(self, xyz_ptr, n, nrm_ptr=None, cov_ptr=None, voxel_size=0.0):
+        """As set with the fp64 arrays resident in HBM."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        self._check(self._lib.reg_map_cloud_set(self._m, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), n, 1, float(voxel_size)))
+        return int(self.info().n_rows)
+
+    def insert_scan(self, raw_xyz, scan_xyz, T, scan_normals=None, scan_covs=None, perform_carving=True) -> MapCloudInsertResult:
+        """Submap::insertScan (Submap.cpp:54-95): carve with the transformed raw scan, append the transformed pre-processed
+        scan, move the cropper to the translation of T (map to sensor), voxelise within it."""
+        r = self._f64(raw_xyz)
+        x, nr, cv = self._f64(scan_xyz), self._f64(scan_normals), self._f64(scan_covs, 9)
+        return self._insert_scan(_ptr(r), r.shape[0] if r is not None else 0, _ptr(x), _ptr(nr), _ptr(cv), x.shape[0], 0, T,
+                                 perform_carving)
+
+    def insert_scan_device(self, raw_ptr, n_raw, scan_ptr, n_scan, T, scan_nrm_ptr=None, scan_cov_ptr=None,
+                           perform_carving=True) -> MapCloudInsertResult:
+        """As insert_scan with the fp64 arrays resident in HBM (the merge cloud of process_scan_device, for instance)."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._insert_scan(vp(raw_ptr), n_raw, vp(scan_ptr), vp(scan_nrm_ptr), vp(scan_cov_ptr), n_scan, 1, T,
+                                 perform_carving)
+
+    def _insert_scan(self, r, n_raw, x, nr, cv, n, on_device, T, carve):
+        res = MapCloudInsertResult()
+        res.struct_size = C.sizeof(MapCloudInsertResult)
+        self._check(self._lib.reg_map_cloud_insert_scan(self._m, r, n_raw, x, nr, cv, n, on_device, _T_in_f64(T),
+                                                        int(bool(carve)), C.byref(res)))
+        return res
+
+    def set_target(self, crop=None) -> int:
+        """cropSubmap + open3dToPointmatcher + initReference from the resident arrays onto the handle of `reg`: exactly
+        Registration.set_target_f64_device of the map.  Returns the rows kept; target_source_indices() indexes map rows."""
+        c = Registration._crop_struct(crop)
+        kept = C.c_int64(0)
+        st = self._lib.reg_map_cloud_set_target(self._m, C.byref(c) if c is not None else None, C.byref(kept))
+        self.reg.n_target_kept = int(kept.value)
+        self._check(st)
+        return self.reg.n_target_kept
+
+    def transform(self, T):
+        """PointCloud::Transform as Submap::transform applies it to mapCloud_."""
+        self._check(self._lib.reg_map_cloud_transform(self._m, _T_in_f64(T)))
+
+    def center(self) -> np.ndarray:
+        """GetCenter: the sequential sum of the rows divided by their number."""
+        c = (C.c_double * 3)()
+        self._check(self._lib.reg_map_cloud_center(self._m, c))
+        return np.array(c, np.float64)
+
+    def clear(self):
+        self._check(self._lib.reg_map_cloud_clear(self._m))
+
+    def info(self) -> MapCloudInfo:
+        i = MapCloudInfo()
+        i.struct_size = C.sizeof(MapCloudInfo)
+        self._check(self._lib.reg_map_cloud_get_info(self._m, C.byref(i)))
+        return i
+
+    def export(self):
+        """dict(xyz, normals, covs) in the map's row order; normals / covs are None when the map lacks the field."""
+        i = self.info()
+        n = int(i.n_rows)
+        f = lambda on, w: np.empty((max(n, 1), w), np.float64) if on else None
+        x, nr, cv = f(True, 3), f(i.has_normals, 3), f(i.has_covariances, 9)
+        k = C.c_int64(0)
+        self._check(self._lib.reg_map_cloud_export(self._m, 0, _ptr(x), _ptr(nr), _ptr(cv), max(n, 1), C.byref(k)))
+        cut = lambda a: a[:int(k.value)] if a is not None else None
+        return dict(xyz=cut(x), normals=cut(nr), covs=cut(cv))
+
+    def export_device(self, capacity_rows, xyz_ptr=None, nrm_ptr=None, cov_ptr=None) -> int:
+        """As export into arrays resident in HBM (capacity_rows rows each; any may be None).  Returns n_rows."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        k = C.c_int64(0)
+        self._check(self._lib.reg_map_cloud_export(self._m, 1, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), int(capacity_rows),
+                                                   C.byref(k)))
         return int(k.value)
 
 

@@ -132,6 +132,9 @@ struct reg_handle {
     // invalid-key word + centre; host-pointer outputs
     DevBuf dm_in[3], dm_crop[3], dm_tf[2], dm_keys, dm_keys2, dm_vals, dm_vals2, dm_heads, dm_run, dm_rank, dm_new, dm_newoff,
         dm_newkeys, dm_mark, dm_keep, dm_off1, dm_off2, dm_misc, dm_out;
+    // the map clouds of this handle (host_mapcloud.hpp): staged inputs (scan points, normals, covariances; raw scan), the
+    // transformed raw scan, and the working cloud an insert voxelises (survivors of the carve + the transformed scan)
+    DevBuf mc_in[4], mc_raw, mc_cat[3];
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;

@@ -562,26 +562,13 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
     return REG_OK;
 }
 
-reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double* map_normals, int64_t m,
-                             const double* scan_xyz, int64_t n_scan, int on_device, const double sensor[3],
-                             const reg_crop* subset, double voxel_size, double max_ray, double truncation, double min_dot,
-                             int32_t* removed, int64_t* n_removed) {
-    if (!h) return REG_BAD_ARGUMENT;
-    if (!h->device_ok) return REG_DEVICE_ERROR;
-    if (n_removed) *n_removed = 0;
-    if (m < 0 || n_scan < 0 || m > 0x7fffffffLL || n_scan > 0x7fffffffLL || !sensor || !(voxel_size > 0.0) ||
-        (m > 0 && (!map_xyz || !removed)) || (n_scan > 0 && !scan_xyz)) {
-        if (h) h->err = "reg_carve_indices: bad argument (voxel_size > 0, sensor, arrays)";
-        return REG_BAD_ARGUMENT;
-    }
-    if (m == 0 || n_scan == 0) return REG_OK;
-    CropCfg c;
-    if (!crop_cfg(subset, &c)) return REG_BAD_ARGUMENT;
-    HIPCHK(h, hipSetDevice(h->prm.device));
-    const double *d_map = nullptr, *d_nrm = nullptr, *d_scan = nullptr;
-    HIPCHK(h, staged_input(h, h->c_in_xyz, map_xyz, (size_t)m * 3, on_device, &d_map));
-    HIPCHK(h, staged_input(h, h->c_in_nrm, map_normals, (size_t)m * 3, on_device, &d_nrm));
-    HIPCHK(h, staged_input(h, h->c_in_cov, scan_xyz, (size_t)n_scan * 3, on_device, &d_scan));   // (the third staging buffer)
+// Steps 1-4 of reg_carve_indices on device arrays (m > 0, n_scan > 0): on return h->v_fout holds the 0 / 1 marks over the
+// map rows and h->v_oout their exclusive scan, *n_marked their total.  *n_candidates: map rows inside the volume; with
+// none, nothing further runs and the marks are not written.
+static reg_status carve_marks(reg_handle* h, const double* d_map, const double* d_nrm, int64_t m, const double* d_scan,
+                              int64_t n_scan, const double sensor[3], const CropCfg& c, double voxel_size, double max_ray,
+                              double truncation, double min_dot, int64_t* n_candidates, int64_t* n_marked) {
+    *n_candidates = *n_marked = 0;
     const double inv = 1.0 / voxel_size;
     // 1. candidate map points (inside the subset volume), keyed by voxel, stably sorted
     HIPCHK(h, h->c_flags.reserve((size_t)m * 4));
@@ -602,7 +589,7 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
         h->err = "voxel_size too small for the extent of the map (voxel index exceeds 2^20)";
         return REG_BAD_ARGUMENT;
     }
-    const int64_t n_in = flag_total(tail);
+    const int64_t n_in = *n_candidates = flag_total(tail);
     if (n_in == 0) return REG_OK;
     HIPCHK(h, h->t_keys.reserve((size_t)n_in * 8));
     HIPCHK(h, h->t_keys2.reserve((size_t)n_in * 8));
@@ -637,7 +624,34 @@ reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double*
     uint32_t rt[2];
     REGCHK(flag_total_async(h, mark, o_mark, m, rt));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t nr = flag_total(rt);
+    *n_marked = flag_total(rt);
+    return REG_OK;
+}
+
+reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double* map_normals, int64_t m,
+                             const double* scan_xyz, int64_t n_scan, int on_device, const double sensor[3],
+                             const reg_crop* subset, double voxel_size, double max_ray, double truncation, double min_dot,
+                             int32_t* removed, int64_t* n_removed) {
+    if (!h) return REG_BAD_ARGUMENT;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_removed) *n_removed = 0;
+    if (m < 0 || n_scan < 0 || m > 0x7fffffffLL || n_scan > 0x7fffffffLL || !sensor || !(voxel_size > 0.0) ||
+        (m > 0 && (!map_xyz || !removed)) || (n_scan > 0 && !scan_xyz)) {
+        if (h) h->err = "reg_carve_indices: bad argument (voxel_size > 0, sensor, arrays)";
+        return REG_BAD_ARGUMENT;
+    }
+    if (m == 0 || n_scan == 0) return REG_OK;
+    CropCfg c;
+    if (!crop_cfg(subset, &c)) return REG_BAD_ARGUMENT;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double *d_map = nullptr, *d_nrm = nullptr, *d_scan = nullptr;
+    HIPCHK(h, staged_input(h, h->c_in_xyz, map_xyz, (size_t)m * 3, on_device, &d_map));
+    HIPCHK(h, staged_input(h, h->c_in_nrm, map_normals, (size_t)m * 3, on_device, &d_nrm));
+    HIPCHK(h, staged_input(h, h->c_in_cov, scan_xyz, (size_t)n_scan * 3, on_device, &d_scan));   // (the third staging buffer)
+    int64_t n_in = 0, nr = 0;
+    REGCHK(carve_marks(h, d_map, d_nrm, m, d_scan, n_scan, sensor, c, voxel_size, max_ray, truncation, min_dot, &n_in, &nr));
+    if (n_in == 0) return REG_OK;
+    const uint32_t *mark = h->v_fout.as<uint32_t>(), *o_mark = h->v_oout.as<uint32_t>();
     StagedOut so(h, h->c_idx, on_device);
     const int s_rem = so.add(removed, 1);
     HIPCHK(h, so.reserve((size_t)nr));

@@ -56,6 +56,7 @@ using namespace o3dreg;
 #include "kernels_ransac.hpp"
 #include "kernels_scanprep.hpp"
 #include "kernels_densemap.hpp"
+#include "kernels_mapcloud.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_mem.hpp"
@@ -75,6 +76,7 @@ using namespace o3dreg;
 #include "host_ransac.hpp"
 #include "host_scanprep.hpp"
 #include "host_densemap.hpp"
+#include "host_mapcloud.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

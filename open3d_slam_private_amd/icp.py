@@ -1610,6 +1610,16 @@ class PointCloud:
 
 
 @dataclass
+class DeviceCloud:
+    """A cloud resident in HBM: torch float64 tensors (points_ >= n x 3, normals_ / covariances_ >= n x 3 / n x 9 or None)
+    of which the first n rows count.  The tensors keep the memory alive."""
+    points_: object
+    normals_: object = None
+    covariances_: object = None
+    n: int = 0
+
+
+@dataclass
 class ProcessedScans:
     """o3d_slam::ProcessedScans (ScanToMapRegistration.hpp): the narrow-cropped cloud that is matched, the wide one that is merged."""
     match_: PointCloud
@@ -1733,6 +1743,31 @@ class ScanToMapIcp:
         pick = lambda a: a[idx] if a is not None else None
         return ProcessedScans(PointCloud(x[idx], pick(nr), pick(cv)), PointCloud(x, nr, cv))
 
+    def processForScanMatchingAndMergingDevice(self, cloud) -> "DeviceCloud":
+        """As processForScanMatchingAndMerging, with merge_ left in device arrays (torch tensors) and no host copy of it:
+        the DeviceCloud goes straight into Submap.insertScan.  match_ is the reading installed on the handle."""
+        import torch
+        self._check()
+        c = _cloud64(cloud, "scan")
+        n = c.points_.shape[0]
+        if n == 0:
+            raise RuntimeError("The reading point cloud is empty.")
+        self.icp._ensure()
+        prm = capi.default_scan_params(wide=self.mapBuilderCropper, narrow=self.scanMatcherCropper,
+                                       voxel_size=float(self.voxelSize_), down_sampling_ratio=float(self.downSamplingRatio_),
+                                       seed=int(self.seed), normal_knn=int(self.knn_),
+                                       normal_radius=float(self.maxDistanceKnn_) if self.knn_ > 0 else 1.0)
+        dev = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda") if a is not None else None
+        x, nr, cv = dev(c.points_), dev(c.normals_), dev(c.covariances_)
+        ox, on, oc = (torch.empty((n, w), dtype=torch.float64, device="cuda") for w in (3, 3, 9))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            res = self.icp._reg.process_scan_device(ptr(x), n, prm, ptr(ox), ptr(nr), ptr(cv), ptr(on), ptr(oc))
+        except RegError as e:
+            raise _translate(e) from None
+        self.last_scan = res
+        return DeviceCloud(ox, on if res.has_normals else None, oc if res.has_covs else None, int(res.n_merge))
+
     def register(self, T_init=None):
         """ICP::compute on the reading processForScanMatchingAndMerging left on the handle: (T, result)."""
         try:
@@ -1761,6 +1796,8 @@ class SpaceCarvingParameters:
     truncationDistance_: float = 0.1
     carveSpaceEveryNscans_: int = 10
     neighborhoodRadiusDenseMap_: float = 0.1
+    voxelSize_: float = 0.1                    # the two fields only the first map's carve reads (icp.Submap)
+    minDotProductWithNormal_: float = 0.5
 
     def check(self, voxelSize):
         r, mr, tr = self.neighborhoodRadiusDenseMap_, self.maxRaytracingLength_, self.truncationDistance_
@@ -1974,6 +2011,137 @@ class DenseMapBuilder:
                 x = _transform_points(mapToRangeSensor, x)
             x = x[reg.dedup_voxels(x, self.denseMap_.voxelSize_)]
             self.lastCarvedKeys_ = self.denseMap_.map.carve(x, mapToRangeSensor[:3, 3], self.carving_.params())
+        except RegError as e:
+            raise _translate(e) from None
+
+
+# ---- the first map of a submap: Submap::insertScan / carve / transform, cropSubmap + initReference (Submap.cpp:39-144,
+#      ScanToMapRegistration.cpp:90-96) -------------------------------------------------------------------------
+def _check_crop(crop, what):
+    if crop is not None and not (isinstance(crop, dict) and crop.get("type", 0) in (0, 1, 2, 3, 4)):
+        raise InvalidParameter(f"{what} must be a crop dict with a known type, got {crop!r}")
+
+
+class Submap:
+    """The scan-matching half of o3d_slam::Submap on one device-resident map cloud (capi.MapCloud): insertScan
+    (Submap.cpp:39-96), transform, computeSubmapCenter, getMapPointCloud, and setAsReference = cropSubmap + initReference on
+    the same handle.  Built from a ScanToMapIcp it shares that object's handle and map builder cropper, so that
+    processForScanMatchingAndMergingDevice -> register -> insertScan -> setAsReference never passes a cloud through the host.
+    Otherwise `reg` is the capi.Registration to live on (default: a handle of its own).
+
+    Followed from the reference: the carve runs when nScansInsertedMap_ % carveSpaceEveryNscans_ == 1 (never at 1, never on
+    the first insert) and uses the cropper pose of the PREVIOUS insert.  Departure: the field set (normals, covariances) is
+    fixed at construction and a scan with other fields raises InvalidParameter (Open3D's operator+= drops the field)."""
+
+    def __init__(self, scanToMap: "ScanToMapIcp | None" = None, *, reg: "capi.Registration | None" = None, mapVoxelSize_=0.03,
+                 mapBuilderCropper=None, carving: "SpaceCarvingParameters | None" = None, hasNormals=True, hasCovariances=False,
+                 isUseInitialMap_=False, isCarvingEnabled_=True):
+        c = carving if carving is not None else SpaceCarvingParameters()
+        if not (_is_real(mapVoxelSize_) and not math.isnan(mapVoxelSize_)):
+            raise InvalidParameter(f"mapVoxelSize_ must be a number, got {mapVoxelSize_!r}")
+        if not (_is_real(c.voxelSize_) and math.isfinite(c.voxelSize_) and c.voxelSize_ > 0):
+            raise InvalidParameter(f"carving.voxelSize_ must be finite and > 0, got {c.voxelSize_!r}")
+        for name in ("maxRaytracingLength_", "truncationDistance_", "minDotProductWithNormal_"):
+            v = getattr(c, name)
+            if not (_is_real(v) and not math.isnan(v)):
+                raise InvalidParameter(f"carving.{name} must be a number, got {v!r}")
+        if not (_is_int(c.carveSpaceEveryNscans_) and c.carveSpaceEveryNscans_ >= 1):
+            raise InvalidParameter(f"carveSpaceEveryNscans_ must be an integer >= 1, got {c.carveSpaceEveryNscans_!r}")
+        if scanToMap is not None and mapBuilderCropper is None:
+            mapBuilderCropper = scanToMap.mapBuilderCropper
+        _check_crop(mapBuilderCropper, "mapBuilderCropper")
+        self.carving_ = c
+        self.isUseInitialMap_, self.isCarvingEnabled_ = bool(isUseInitialMap_), bool(isCarvingEnabled_)
+        self.mapVoxelSize_ = float(mapVoxelSize_)
+        self._own = scanToMap is None and reg is None
+        if scanToMap is not None:
+            scanToMap.icp._ensure()
+            reg = scanToMap.icp._reg
+        self._reg = reg if reg is not None else _feature_handle()
+        prm = capi.default_map_cloud_params(mapBuilderCropper if mapBuilderCropper is not None else dict(type=capi.CROP_NONE),
+                                            has_normals=bool(hasNormals), has_covariances=bool(hasCovariances),
+                                            carve_every_n_scans=c.carveSpaceEveryNscans_, map_voxel_size=self.mapVoxelSize_,
+                                            carve_voxel_size=c.voxelSize_, carve_max_ray=c.maxRaytracingLength_,
+                                            carve_truncation=c.truncationDistance_, carve_min_dot=c.minDotProductWithNormal_)
+        try:
+            self.map = capi.MapCloud(self._reg, prm)
+        except RegError as e:
+            raise _translate(e) from None
+        self.lastInsert_ = None
+
+    def close(self):
+        self.map.close()
+        if self._own:
+            self._reg.close()
+
+    @property
+    def nScansInsertedMap_(self) -> int:
+        return int(self.map.info().scans_inserted)
+
+    @staticmethod
+    def _device_args(c):
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        return ptr(c.points_), ptr(c.normals_), ptr(c.covariances_), int(c.n)
+
+    @staticmethod
+    def _to_device(c: PointCloud) -> DeviceCloud:
+        import torch
+        dev = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda") if a is not None else None
+        return DeviceCloud(dev(c.points_), dev(c.normals_), dev(c.covariances_), c.points_.shape[0])
+
+    def insertScan(self, rawScan, preProcessedScan, mapToRangeSensor, isPerformCarving=True) -> bool:
+        """Submap::insertScan.  Either cloud may be a DeviceCloud (then the other is uploaded once); rawScan may be None."""
+        T = _check_T(mapToRangeSensor, "mapToRangeSensor")
+        if T is None:
+            raise InvalidParameter("mapToRangeSensor is missing")
+        on_device = isinstance(preProcessedScan, DeviceCloud) or isinstance(rawScan, DeviceCloud)
+        scan = preProcessedScan if isinstance(preProcessedScan, DeviceCloud) else _cloud64(preProcessedScan, "preProcessedScan")
+        raw = rawScan if rawScan is None or isinstance(rawScan, DeviceCloud) else _cloud64(rawScan, "rawScan")
+        n_scan = scan.n if isinstance(scan, DeviceCloud) else scan.points_.shape[0]
+        if n_scan == 0:
+            return True                                                         # Submap.cpp:41-43
+        carve = self.isCarvingEnabled_ and bool(isPerformCarving)
+        try:
+            if on_device:
+                scan = scan if isinstance(scan, DeviceCloud) else self._to_device(scan)
+                raw = raw if raw is None or isinstance(raw, DeviceCloud) else self._to_device(raw)
+                x, nr, cv, n = self._device_args(scan)
+                if self.isUseInitialMap_ and self.map.info().n_rows == 0:       # Submap.cpp:47-52
+                    self.map.set_device(x, n, nr, cv, self.mapVoxelSize_)
+                    return True
+                rp, rn = (raw.points_.data_ptr(), int(raw.n)) if raw is not None else (None, 0)
+                self.lastInsert_ = self.map.insert_scan_device(rp, rn, x, n, T, nr, cv, carve)
+            else:
+                if self.isUseInitialMap_ and self.map.info().n_rows == 0:
+                    self.map.set(scan.points_, scan.normals_, scan.covariances_, self.mapVoxelSize_)
+                    return True
+                self.lastInsert_ = self.map.insert_scan(raw.points_ if raw is not None else None, scan.points_, T, scan.normals_,
+                                                        scan.covariances_, carve)
+        except RegError as e:
+            raise _translate(e) from None
+        return True
+
+    def getMapPointCloud(self) -> PointCloud:
+        e = self.map.export()
+        return PointCloud(e["xyz"], e["normals"], e["covs"])
+
+    def transform(self, T):
+        """Submap::transform's mapCloud_.Transform(T)."""
+        try:
+            self.map.transform(_check_T(np.eye(4) if T is None else T, "T"))
+        except RegError as e:
+            raise _translate(e) from None
+
+    def computeSubmapCenter(self) -> np.ndarray:
+        """mapCloud_.GetCenter() (Submap::computeSubmapCenter)."""
+        return self.map.center()
+
+    def setAsReference(self, crop=None) -> int:
+        """cropSubmap (scanMatcherCropper_ at its pose: `crop`) + open3dToPointmatcher + initReference from the resident map
+        onto the handle.  Returns the rows of the patch; raises as an empty reference does."""
+        _check_crop(crop, "crop")
+        try:
+            return self.map.set_target(crop)
         except RegError as e:
             raise _translate(e) from None
 
