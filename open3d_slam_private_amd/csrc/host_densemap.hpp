@@ -46,44 +46,25 @@ static void dm_swap(reg_dense_map* m, int64_t n, bool nrm, bool col) {
     m->has_nrm = nrm;
     m->has_col = col;
 }
-static DmT dm_rows(const double* T) {   // column-major double[16] -> rows
-    DmT t;
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) t.m[4 * r + c] = T[4 * c + r];
-    return t;
-}
 
 // keys (+ transformed cloud when T is given) of a device cloud, sorted with their indices, run heads and run ids.
-// Leaves dm_keys2 / dm_vals2 / dm_heads / dm_run filled; *runs = number of distinct keys.  One synchronisation.
+// Leaves the sorted keys and values, the run heads and the run ids of h->dm filled; *runs = number of distinct keys.  One
+// synchronisation.
 static reg_status dm_sorted_keys(reg_handle* h, const char* who, const double* d_xyz, const double* d_nrm, int64_t n,
                                  const double* T, double inv, int64_t* runs) {
-    HIPCHK(h, h->dm_keys.reserve((size_t)n * 8));
-    HIPCHK(h, h->dm_keys2.reserve((size_t)n * 8));
-    HIPCHK(h, h->dm_vals.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_vals2.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_heads.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_run.reserve((size_t)n * 4));
+    HIPCHK(h, h->dm.reserve((size_t)n));
     HIPCHK(h, h->dm_misc.reserve(256));
     if (T) {
         HIPCHK(h, h->dm_tf[0].reserve((size_t)n * 24));
         if (d_nrm) HIPCHK(h, h->dm_tf[1].reserve((size_t)n * 24));
     }
-    DmT t;
-    std::memset(&t, 0, sizeof(t));
-    if (T) t = dm_rows(T);
-    uint64_t *keys = h->dm_keys.as<uint64_t>(), *sorted = h->dm_keys2.as<uint64_t>();
-    uint32_t *vals = h->dm_vals.as<uint32_t>(), *svals = h->dm_vals2.as<uint32_t>();
-    uint32_t *heads = h->dm_heads.as<uint32_t>(), *run = h->dm_run.as<uint32_t>();
+    const RunArrays a = h->dm.arrays();
     HIPCHK(h, hipMemsetAsync(h->dm_misc.p, 0, 4, h->stream));
-    k_dm_keys<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, d_nrm, n, T ? 1 : 0, t, inv, h->dm_tf[0].as<double>(),
-                                                  h->dm_tf[1].as<double>(), keys, vals, h->dm_misc.as<uint32_t>());
-    uint32_t bad = 0;
+    k_dm_keys<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, d_nrm, n, T ? 1 : 0, xform_rows(T), inv, h->dm_tf[0].as<double>(),
+                                                  h->dm_tf[1].as<double>(), a.keys, a.vals, h->dm_misc.as<uint32_t>());
+    uint32_t bad = 0, tail[2];
     HIPCHK(h, hipMemcpyAsync(&bad, h->dm_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
-    REGCHK(sort_pairs(h, h->rp_tmp, keys, sorted, vals, svals, (size_t)n, 0, 3 * kVoxBits));
-    k_vox_heads<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads);
-    REGCHK(scan_excl(h, h->rp_tmp, heads, run, (size_t)n));
-    uint32_t tail[2];
-    REGCHK(flag_total_async(h, heads, run, n, tail));
+    REGCHK(sort_runs(h, a, n, tail));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     if (bad) {
@@ -107,20 +88,19 @@ static reg_status dm_insert_device(reg_dense_map* m, const char* who, const doub
     HIPCHK(h, h->dm_newoff.reserve((size_t)runs * 4));
     HIPCHK(h, h->dm_newkeys.reserve((size_t)runs * 8));
     HIPCHK(h, h->dm_mark.reserve((size_t)std::max<int64_t>(m->n, 1) * 4));
-    const uint64_t* sorted = h->dm_keys2.as<uint64_t>();
-    const uint32_t *svals = h->dm_vals2.as<uint32_t>(), *heads = h->dm_heads.as<uint32_t>(), *run = h->dm_run.as<uint32_t>();
+    const RunArrays a = h->dm.arrays();   // as dm_sorted_keys left them
+    const uint64_t* sorted = a.sorted;
+    const uint32_t *svals = a.svals, *heads = a.heads, *run = a.run;
     uint32_t *rank = h->dm_rank.as<uint32_t>(), *is_new = h->dm_new.as<uint32_t>(), *new_off = h->dm_newoff.as<uint32_t>();
     uint32_t* touched = h->dm_mark.as<uint32_t>();
     uint64_t* new_keys = h->dm_newkeys.as<uint64_t>();
     const DmCols in = dm_cols(m, m->cur, m->has_nrm, m->has_col);
     if (m->n > 0) HIPCHK(h, hipMemsetAsync(touched, 0, (size_t)m->n * 4, h->stream));
     k_dm_rank<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads, run, in.key, m->n, rank, is_new, touched);
-    REGCHK(scan_excl(h, h->rp_tmp, is_new, new_off, (size_t)runs));
-    uint32_t tail[2];
-    REGCHK(flag_total_async(h, is_new, new_off, runs, tail));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int64_t n_new = 0;
+    REGCHK(scan_total(h, is_new, new_off, runs, &n_new));
     HIPCHK(h, hipGetLastError());
-    const int64_t n_new = flag_total(tail), total = m->n + n_new;
+    const int64_t total = m->n + n_new;
     if (total > kDmMaxRows) {
         h->err = std::string(who) + ": the map would exceed 2^31 - 1 voxels";
         return REG_BAD_ARGUMENT;
@@ -262,12 +242,8 @@ reg_status reg_dense_map_insert_scan(reg_dense_map* m, const double* xyz, const 
         uint32_t *flags = h->dm_keep.as<uint32_t>(), *offs = h->dm_off2.as<uint32_t>();
         k_dm_scan_flags<<<grid_for(n), 256, 0, h->stream>>>(d[0], d[2], n, crop, p->rgb_min[0], p->rgb_min[1], p->rgb_min[2],
                                                             p->rgb_max[0], p->rgb_max[1], p->rgb_max[2], flags);
-        REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n));
-        uint32_t tail[2];
-        REGCHK(flag_total_async(h, flags, offs, n, tail));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        REGCHK(scan_total(h, flags, offs, n, &kept));
         HIPCHK(h, hipGetLastError());
-        kept = flag_total(tail);
         if (kept > 0 && kept < n) {
             double* o[3] = {nullptr, nullptr, nullptr};
             for (int k = 0; k < 3; ++k)
@@ -275,7 +251,8 @@ reg_status reg_dense_map_insert_scan(reg_dense_map* m, const double* xyz, const 
                     HIPCHK(h, h->dm_crop[k].reserve((size_t)kept * 24));
                     o[k] = h->dm_crop[k].as<double>();
                 }
-            k_dm_gather3<<<grid_for(n), 256, 0, h->stream>>>(d[0], d[1], d[2], n, flags, offs, o[0], o[1], o[2]);
+            k_gather_rows<3, true><<<grid_for(n), 256, 0, h->stream>>>(cols64_in(d[0], d[1], d[2]), n, flags, offs,
+                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
             for (int k = 0; k < 3; ++k) d[k] = o[k];
         }
     }
@@ -330,12 +307,9 @@ reg_status reg_dense_map_carve(reg_dense_map* m, const double* scan_xyz, int64_t
     HIPCHK(h, hipMemsetAsync(mark, 0, (size_t)n * 4, h->stream));
     k_dm_carve<<<grid_for(n_scan, 4), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], step, p->max_ray,
                                                            p->truncation, r, m->voxel, m->voxel * 0.5, off, in.key, n, mark);
-    REGCHK(scan_excl(h, h->rp_tmp, mark, rem_off, (size_t)n));
-    uint32_t tail[2];
-    REGCHK(flag_total_async(h, mark, rem_off, n, tail));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    int64_t removed = 0;
+    REGCHK(scan_total(h, mark, rem_off, n, &removed));
     HIPCHK(h, hipGetLastError());
-    const int64_t removed = flag_total(tail);
     if (removed == 0) return REG_OK;
     StagedOut so(h, h->dm_out, on_device);
     const int s_keys = so.add(removed_keys, 3);
@@ -364,7 +338,7 @@ reg_status reg_dense_map_transform(reg_dense_map* m, const double T[16]) {
     if (m->n == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
     HIPCHK(h, dm_reserve_spare(m, (size_t)m->n, m->has_nrm, m->has_col));
-    k_dm_transform<<<grid_for(m->n), 256, 0, h->stream>>>(dm_cols(m, m->cur, m->has_nrm, m->has_col), m->n, dm_rows(T),
+    k_dm_transform<<<grid_for(m->n), 256, 0, h->stream>>>(dm_cols(m, m->cur, m->has_nrm, m->has_col), m->n, xform_rows(T),
                                                           dm_cols(m, m->cur ^ 1, m->has_nrm, m->has_col));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
@@ -436,7 +410,7 @@ reg_status reg_dedup_voxels(reg_handle* h, const double* xyz, int64_t n, int on_
     const int s_idx = so.add(kept_idx, 1);
     HIPCHK(h, so.reserve((size_t)runs));
     HIPCHK(h, hipMemsetAsync(flags, 0, (size_t)n * 4, h->stream));
-    k_dm_dedup_mark<<<grid_for(n), 256, 0, h->stream>>>(h->dm_heads.as<uint32_t>(), h->dm_vals2.as<uint32_t>(), n, flags);
+    k_dm_dedup_mark<<<grid_for(n), 256, 0, h->stream>>>(h->dm.heads.as<uint32_t>(), h->dm.vals2.as<uint32_t>(), n, flags);
     REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n));
     k_carve_collect<<<grid_for(n), 256, 0, h->stream>>>(flags, offs, n, so.at<int32_t>(s_idx));
     HIPCHK(h, so.copy_back((size_t)runs));

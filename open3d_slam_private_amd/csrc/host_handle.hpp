@@ -122,16 +122,18 @@ struct reg_handle {
     int64_t src_kept = 0;                            // > 0: ov_sidx maps the current reading back (reg_set_pair_overlap_f64,
                                                      // reg_process_scan)
     // the scan front end (host_scanprep.hpp): staged inputs; the cloud after the wide crop, after the voxel grid, after the
-    // random selection (xyz, normals, covs each); the fp32 cast and the estimated fp32 normals / covariances; sort keys and
-    // values, flags + offsets, min-bound rows + origin, the invalid-key word; the events of scan_prep_ms
-    DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_keys, sp_keys2, sp_vals, sp_vals2, sp_flags, sp_offs, sp_part,
-        sp_misc;
+    // random selection (xyz, normals, covs each); the fp32 cast and the estimated fp32 normals / covariances; min-bound rows
+    // + origin, the invalid-key word; sort keys and values, run heads and ids (heads / run double as the flags + offsets of
+    // the crops and of the random selection); the events of scan_prep_ms
+    DevBuf sp_in[3], sp_a[3], sp_b[3], sp_c[3], sp_f32[3], sp_part, sp_misc;
+    RunBufs sp;
     // the dense maps of this handle (host_densemap.hpp) share their working set: staged inputs (points, normals, colours),
-    // the cloud after the croppers, after the transform (points, normals); sort keys and values, run heads and ids; per run
-    // the rank, the new flag, its scan and the new keys; touched / erase marks, keep flags and the scans of both; the
-    // invalid-key word + centre; host-pointer outputs
-    DevBuf dm_in[3], dm_crop[3], dm_tf[2], dm_keys, dm_keys2, dm_vals, dm_vals2, dm_heads, dm_run, dm_rank, dm_new, dm_newoff,
-        dm_newkeys, dm_mark, dm_keep, dm_off1, dm_off2, dm_misc, dm_out;
+    // the cloud after the croppers, after the transform (points, normals); per run the rank, the new flag, its scan and the
+    // new keys; touched / erase marks, keep flags and the scans of both; the invalid-key word + centre; host-pointer
+    // outputs; sort keys and values, run heads and ids
+    DevBuf dm_in[3], dm_crop[3], dm_tf[2], dm_rank, dm_new, dm_newoff, dm_newkeys, dm_mark, dm_keep, dm_off1, dm_off2, dm_misc,
+        dm_out;
+    RunBufs dm;
     // the map clouds of this handle (host_mapcloud.hpp): staged inputs (scan points, normals, covariances; raw scan), the
     // transformed raw scan, and the working cloud an insert voxelises (survivors of the carve + the transformed scan)
     DevBuf mc_in[4], mc_raw, mc_cat[3];

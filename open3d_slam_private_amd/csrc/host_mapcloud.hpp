@@ -25,11 +25,11 @@ static hipError_t mc_reserve(McSide& s, size_t rows, bool nrm, bool cov) {
     if (e == hipSuccess && cov) e = dm_grow(s.cov, rows, 72);
     return e;
 }
-static McCols mc_cols(McSide& s, bool nrm, bool cov) {
-    return McCols{s.xyz.as<double>(), nrm ? s.nrm.as<double>() : nullptr, cov ? s.cov.as<double>() : nullptr};
+static Cols64 mc_cols(McSide& s, bool nrm, bool cov) {
+    return Cols64{s.xyz.as<double>(), nrm ? s.nrm.as<double>() : nullptr, cov ? s.cov.as<double>() : nullptr};
 }
-static McCols mc_cur(reg_map_cloud* m) { return mc_cols(m->side[m->cur], m->prm.has_normals, m->prm.has_covariances); }
-static McCols mc_spare(reg_map_cloud* m) { return mc_cols(m->side[m->cur ^ 1], m->prm.has_normals, m->prm.has_covariances); }
+static Cols64 mc_cur(reg_map_cloud* m) { return mc_cols(m->side[m->cur], m->prm.has_normals, m->prm.has_covariances); }
+static Cols64 mc_spare(reg_map_cloud* m) { return mc_cols(m->side[m->cur ^ 1], m->prm.has_normals, m->prm.has_covariances); }
 static reg_crop mc_crop_at(const reg_map_cloud* m, const double c[3]) {
     reg_crop crop = m->prm.crop;
     for (int k = 0; k < 3; ++k) crop.center[k] = c[k];
@@ -125,13 +125,13 @@ reg_status reg_map_cloud_set(reg_map_cloud* m, const double* xyz, const double* 
     const double* d[3] = {xyz, normals, covs};
     for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->mc_in[k], d[k], (size_t)n * kSpWidth[k], on_device, &d[k]));
     HIPCHK(h, mc_reserve(m->side[m->cur ^ 1], (size_t)n, d[1], d[2]));
-    const McCols out = mc_spare(m);
+    const Cols64 out = mc_spare(m);
     int64_t rows = n;
     if (voxel_size > 0.0) {   // voxelize(mapVoxelSize_, &mapCloud_): PointCloud::VoxelDownSample
-        REGCHK(sp_voxel_device(h, d[0], d[1], d[2], n, voxel_size, out.xyz, out.nrm, out.cov, &rows));
+        REGCHK(sp_voxel_device(h, d[0], d[1], d[2], n, voxel_size, out.xyz, out.nrm, out.aux, &rows));
     } else {
-        k_mc_compact<<<grid_for(n), 256, 0, h->stream>>>(McCols{(double*)d[0], (double*)d[1], (double*)d[2]}, n, nullptr, nullptr,
-                                                         out);
+        k_gather_rows<9, false><<<grid_for(n), 256, 0, h->stream>>>(cols64_in(d[0], d[1], d[2]), n, nullptr, nullptr, out,
+                                                                    nullptr);   // no flags: a plain copy
         HIPCHK(h, hipStreamSynchronize(h->stream));
         HIPCHK(h, hipGetLastError());
     }
@@ -166,9 +166,9 @@ reg_status reg_map_cloud_insert_scan(reg_map_cloud* m, const double* raw_xyz, in
     HIPCHK(h, hipSetDevice(h->prm.device));
     const double *d_raw = raw_xyz, *d[3] = {scan_xyz, scan_normals, scan_covs};
     for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->mc_in[k], d[k], (size_t)n_scan * kSpWidth[k], on_device, &d[k]));
-    const DmT t = dm_rows(T);
+    const Xform64 t = xform_rows(T);
     const bool nrm = m->prm.has_normals, cov = m->prm.has_covariances;
-    const McCols in = mc_cur(m);
+    const Cols64 in = mc_cur(m);
 
     // carve (Submap.cpp:130-144): the rule, the whole transformed raw scan as rays, the volume at the pose of the PREVIOUS insert
     const bool carve = perform_carving && m->n > 0 && (m->scans % m->prm.carve_every_n_scans) == 1;
@@ -176,8 +176,8 @@ reg_status reg_map_cloud_insert_scan(reg_map_cloud* m, const double* raw_xyz, in
     if (carve && n_raw > 0) {
         HIPCHK(h, staged_input(h, h->mc_in[3], d_raw, (size_t)n_raw * 3, on_device, &d_raw));
         HIPCHK(h, h->mc_raw.reserve((size_t)n_raw * 24));
-        k_mc_transform_append<<<grid_for(n_raw), 256, 0, h->stream>>>(McCols{(double*)d_raw, nullptr, nullptr}, n_raw, t,
-                                                                      McCols{h->mc_raw.as<double>(), nullptr, nullptr}, 0);
+        k_mc_transform_append<<<grid_for(n_raw), 256, 0, h->stream>>>(cols64_in(d_raw, nullptr, nullptr), n_raw, t,
+                                                                      Cols64{h->mc_raw.as<double>(), nullptr, nullptr}, 0);
         const double sensor[3] = {T[12], T[13], T[14]};   // mapToRangeSensor.translation()
         const reg_crop prev = mc_crop_at(m, m->center);
         CropCfg c;
@@ -191,22 +191,22 @@ reg_status reg_map_cloud_insert_scan(reg_map_cloud* m, const double* raw_xyz, in
     HIPCHK(h, dm_grow(h->mc_cat[0], (size_t)n_cat, 24));
     if (nrm) HIPCHK(h, dm_grow(h->mc_cat[1], (size_t)n_cat, 24));
     if (cov) HIPCHK(h, dm_grow(h->mc_cat[2], (size_t)n_cat, 72));
-    const McCols cat{h->mc_cat[0].as<double>(), nrm ? h->mc_cat[1].as<double>() : nullptr,
+    const Cols64 cat{h->mc_cat[0].as<double>(), nrm ? h->mc_cat[1].as<double>() : nullptr,
                      cov ? h->mc_cat[2].as<double>() : nullptr};
     if (m->n > 0)
-        k_mc_compact<<<grid_for(m->n), 256, 0, h->stream>>>(in, m->n, n_carved > 0 ? h->v_fout.as<uint32_t>() : nullptr,
-                                                           n_carved > 0 ? h->v_oout.as<uint32_t>() : nullptr, cat);
-    k_mc_transform_append<<<grid_for(n_scan), 256, 0, h->stream>>>(McCols{(double*)d[0], (double*)d[1], (double*)d[2]}, n_scan,
-                                                                    t, cat, n_left);
+        k_gather_rows<9, false><<<grid_for(m->n), 256, 0, h->stream>>>(in, m->n, n_carved > 0 ? h->v_fout.as<uint32_t>() : nullptr,
+                                                                       n_carved > 0 ? h->v_oout.as<uint32_t>() : nullptr, cat,
+                                                                       nullptr);   // the carve's marks leave
+    k_mc_transform_append<<<grid_for(n_scan), 256, 0, h->stream>>>(cols64_in(d[0], d[1], d[2]), n_scan, t, cat, n_left);
 
     // setPose (Submap.cpp:85), then voxelizeInsideCroppingVolume from the working cloud into the spare side
     const double center[3] = {T[12], T[13], T[14]};
     const reg_crop volume = mc_crop_at(m, center);
     HIPCHK(h, mc_reserve(m->side[m->cur ^ 1], (size_t)n_cat, nrm, cov));
-    const McCols out = mc_spare(m);
+    const Cols64 out = mc_spare(m);
     int64_t n_out = 0, n_outside = 0;
-    REGCHK(reg_voxelize_within_volume(h, cat.xyz, cat.nrm, cat.cov, n_cat, 1, &volume, m->prm.map_voxel_size, out.xyz, out.nrm,
-                                      out.cov, &n_out, &n_outside));
+    REGCHK(reg_voxelize_within_volume(h, cat.xyz, cat.nrm, cat.aux, n_cat, 1, &volume, m->prm.map_voxel_size, out.xyz, out.nrm,
+                                      out.aux, &n_out, &n_outside));
     m->cur ^= 1;
     m->n = n_out;
     m->scans += 1;
@@ -224,8 +224,8 @@ reg_status reg_map_cloud_insert_scan(reg_map_cloud* m, const double* raw_xyz, in
 reg_status reg_map_cloud_set_target(reg_map_cloud* m, const reg_crop* crop, int64_t* n_kept) {
     if (!m) return REG_BAD_ARGUMENT;
     if (n_kept) *n_kept = 0;
-    const McCols in = mc_cur(m);   // cropSubmap + open3dToPointmatcher + initReference: reg_set_target_f64 of the resident arrays
-    return reg_set_target_f64(m->h, in.xyz, in.nrm, in.cov, m->n, 1, crop, n_kept);
+    const Cols64 in = mc_cur(m);   // cropSubmap + open3dToPointmatcher + initReference: reg_set_target_f64 of the resident arrays
+    return reg_set_target_f64(m->h, in.xyz, in.nrm, in.aux, m->n, 1, crop, n_kept);
 }
 
 reg_status reg_map_cloud_transform(reg_map_cloud* m, const double T[16]) {
@@ -239,7 +239,7 @@ reg_status reg_map_cloud_transform(reg_map_cloud* m, const double T[16]) {
     if (m->n == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
     HIPCHK(h, mc_reserve(m->side[m->cur ^ 1], (size_t)m->n, m->prm.has_normals, m->prm.has_covariances));
-    k_mc_transform_append<<<grid_for(m->n), 256, 0, h->stream>>>(mc_cur(m), m->n, dm_rows(T), mc_spare(m), 0);
+    k_mc_transform_append<<<grid_for(m->n), 256, 0, h->stream>>>(mc_cur(m), m->n, xform_rows(T), mc_spare(m), 0);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     m->cur ^= 1;
@@ -275,11 +275,11 @@ reg_status reg_map_cloud_export(reg_map_cloud* m, int on_device, double* xyz, do
     if (n_out) *n_out = m->n;
     if (m->n == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
-    const McCols in = mc_cur(m);   // the columns are the export's layout already: plain copies
+    const Cols64 in = mc_cur(m);   // the columns are the export's layout already: plain copies
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (xyz) HIPCHK(h, hipMemcpyAsync(xyz, in.xyz, (size_t)m->n * 24, kind, h->stream));
     if (normals && in.nrm) HIPCHK(h, hipMemcpyAsync(normals, in.nrm, (size_t)m->n * 24, kind, h->stream));
-    if (covs && in.cov) HIPCHK(h, hipMemcpyAsync(covs, in.cov, (size_t)m->n * 72, kind, h->stream));
+    if (covs && in.aux) HIPCHK(h, hipMemcpyAsync(covs, in.aux, (size_t)m->n * 72, kind, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return REG_OK;
 }

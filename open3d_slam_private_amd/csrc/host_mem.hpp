@@ -32,6 +32,27 @@ struct DevBuf : NoCopy {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// The six arrays of "sort the keys, find the runs" (sort_runs, host_prims.hpp): keys and values as written and as sorted,
+// the 0 / 1 heads of the runs of equal sorted keys, and the exclusive scan of the heads (the run id at every position).
+struct RunArrays {
+    uint64_t *keys, *sorted;
+    uint32_t *vals, *svals, *heads, *run;
+};
+struct RunBufs {   // their owner; what sort_runs left in them stays until the next use of the same set
+    DevBuf keys, keys2, vals, vals2, heads, run;
+    hipError_t reserve(size_t n) {
+        hipError_t e = keys.reserve(n * 8);
+        if (e == hipSuccess) e = keys2.reserve(n * 8);
+        for (DevBuf* b : {&vals, &vals2, &heads, &run})
+            if (e == hipSuccess) e = b->reserve(n * 4);
+        return e;
+    }
+    RunArrays arrays() const {
+        return RunArrays{keys.as<uint64_t>(), keys2.as<uint64_t>(), vals.as<uint32_t>(),
+                         vals2.as<uint32_t>(), heads.as<uint32_t>(), run.as<uint32_t>()};
+    }
+};
+
 // Pinned host block; a mapped one (hipHostMallocMapped) also holds its device view.  alloc / Event::create: once per owner
 template <class T>
 struct Pinned : NoCopy {

@@ -10,15 +10,7 @@ enum { kOvlBad = 0, kOvlRuns = 1 };
 // the selected counts.  d_src / d_tgt: device pointers, n, m >= 1.  One synchronisation: the invalid-key word and the counts.
 static reg_status ovl_select(reg_handle* h, const double* d_src, int64_t n, const double* d_tgt, int64_t m, const double* T_col,
                              double voxel_size, int32_t min_points, int64_t* n_src, int64_t* n_tgt) {
-    OvlT Ts;
-    std::memset(&Ts, 0, sizeof(Ts));
-    if (T_col) {
-        for (int r = 0; r < 4; ++r)
-            for (int c = 0; c < 4; ++c) Ts.m[4 * r + c] = T_col[4 * c + r];
-        Ts.on = 1;
-    }
-    OvlT Tt;
-    std::memset(&Tt, 0, sizeof(Tt));
+    const Xform64 T = xform_rows(T_col);   // applied to the source layer only
     const double inv = 1.0 / voxel_size;   // fromVoxelSize (VoxelHashMap.hpp:43-45)
     HIPCHK(h, h->ov_misc.reserve(64));
     HIPCHK(h, hipMemsetAsync(h->ov_misc.p, 0, 64, h->stream));
@@ -33,7 +25,8 @@ static reg_status ovl_select(reg_handle* h, const double* d_src, int64_t n, cons
         HIPCHK(h, h->ov_ucnt[l].reserve((size_t)c * 4));
         HIPCHK(h, h->ov_flags[l].reserve((size_t)(c + 1) * 4));
         HIPCHK(h, h->ov_offs[l].reserve((size_t)(c + 1) * 4));
-        k_ovl_keys<<<grid_for(c), 256, 0, h->stream>>>(pts[l], c, l == 0 ? Ts : Tt, inv, h->ov_keys[l].as<uint64_t>(), misc + kOvlBad);
+        k_ovl_keys<<<grid_for(c), 256, 0, h->stream>>>(pts[l], c, l == 0 && T_col ? 1 : 0, T, inv, h->ov_keys[l].as<uint64_t>(),
+                                                       misc + kOvlBad);
         REGCHK(sort_keys(h, h->rp_tmp, h->ov_keys[l].as<uint64_t>(), h->ov_sorted.as<uint64_t>(), (size_t)c, 0, 64));
         REGCHK(with_tmp(h, h->rp_tmp, [&](void* t, size_t& b) {
             return rocprim::run_length_encode(t, b, h->ov_sorted.as<uint64_t>(), (unsigned int)c, h->ov_ukeys[l].as<uint64_t>(),

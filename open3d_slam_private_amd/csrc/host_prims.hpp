@@ -1,5 +1,5 @@
 // host_prims.hpp -- host primitives the entry points share: rocPRIM's temporary-storage protocol, scans and sorts on it,
-// the total of a flag array, the crop configuration, staged inputs; the outputs of the operators that have a host and a
+// the total of a flag array, the sort of voxel keys into runs (sort_runs), the crop configuration, staged inputs; the outputs of the operators that have a host and a
 // device-pointer form (StagedOut: one declaration per output gives its device pointer, its share of the staging buffer and
 // its copy-back; copy_out for an output held in a working buffer); the pack / bounding box / non-finite front of the box
 // filters
@@ -69,6 +69,25 @@ static reg_status flag_total_async(reg_handle* h, const uint32_t* flags, const u
     return REG_OK;
 }
 static inline int64_t flag_total(const uint32_t tail[2]) { return (int64_t)tail[0] + (int64_t)tail[1]; }
+// The whole of it where no further word is read back in the same synchronisation: scan, read-back, one synchronisation
+static reg_status scan_total(reg_handle* h, const uint32_t* flags, uint32_t* offs, int64_t n, int64_t* total) {
+    uint32_t tail[2];
+    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n));
+    REGCHK(flag_total_async(h, flags, offs, n, tail));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *total = flag_total(tail);
+    return REG_OK;
+}
+
+// "Sort the keys, find the runs" of n > 0 voxel keys: the stable sort of (keys, vals) on the 3 * kVoxBits key bits into
+// (sorted, svals), heads = 1 at the first position of every run of equal sorted keys, run = the exclusive scan of heads.
+// Enqueues the read-back of the number of runs into tail and does not synchronise: the caller does, then reads flag_total.
+static reg_status sort_runs(reg_handle* h, const RunArrays& a, int64_t n, uint32_t tail[2]) {
+    REGCHK(sort_pairs(h, h->rp_tmp, a.keys, a.sorted, a.vals, a.svals, (size_t)n, 0, 3 * kVoxBits));
+    k_vox_heads<<<grid_for(n), 256, 0, h->stream>>>(a.sorted, n, a.heads);
+    REGCHK(scan_excl(h, h->rp_tmp, a.heads, a.run, (size_t)n));
+    return flag_total_async(h, a.heads, a.run, n, tail);
+}
 
 // reg_crop (null: no cropping) -> the kernels' CropCfg; false: unknown type
 static bool crop_cfg(const reg_crop* crop, CropCfg* c) {

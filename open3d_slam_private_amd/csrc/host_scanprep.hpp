@@ -8,23 +8,16 @@ static const size_t kSpWidth[3] = {3, 3, 9};   // doubles per row of points_, no
 // VoxelDownSample of a device cloud into device arrays of n rows (d_onrm / d_ocov are written iff d_nrm / d_cov are given)
 static reg_status sp_voxel_device(reg_handle* h, const double* d_xyz, const double* d_nrm, const double* d_cov, int64_t n,
                                   double voxel, double* d_oxyz, double* d_onrm, double* d_ocov, int64_t* n_vox) {
-    HIPCHK(h, h->sp_keys.reserve((size_t)n * 8));
-    HIPCHK(h, h->sp_keys2.reserve((size_t)n * 8));
-    HIPCHK(h, h->sp_vals.reserve((size_t)n * 4));
-    HIPCHK(h, h->sp_vals2.reserve((size_t)n * 4));
-    HIPCHK(h, h->sp_flags.reserve((size_t)n * 4));
-    HIPCHK(h, h->sp_offs.reserve((size_t)n * 4));
+    HIPCHK(h, h->sp.reserve((size_t)n));
     HIPCHK(h, h->sp_misc.reserve(256));
     const int rows = (int)std::min<int64_t>(grid_for(n), kSpMinRows);
     HIPCHK(h, h->sp_part.reserve(((size_t)rows * 3 + 6) * 8));
     double *part = h->sp_part.as<double>(), *bound = part + (size_t)rows * 3;   // bound: min_bound[3], origin[3]
-    uint64_t *keys = h->sp_keys.as<uint64_t>(), *sorted = h->sp_keys2.as<uint64_t>();
-    uint32_t *vals = h->sp_vals.as<uint32_t>(), *svals = h->sp_vals2.as<uint32_t>();
-    uint32_t *heads = h->sp_flags.as<uint32_t>(), *vox = h->sp_offs.as<uint32_t>();
+    const RunArrays a = h->sp.arrays();
     HIPCHK(h, hipMemsetAsync(h->sp_misc.p, 0, 4, h->stream));
     k_sp_min_partial<<<rows, 256, 0, h->stream>>>(d_xyz, n, part);
     k_sp_min_final<<<1, 256, 0, h->stream>>>(part, rows, voxel, bound);
-    k_sp_vox_keys<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, n, bound + 3, voxel, keys, vals, h->sp_misc.as<uint32_t>());
+    k_sp_vox_keys<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, n, bound + 3, voxel, a.keys, a.vals, h->sp_misc.as<uint32_t>());
     uint32_t bad = 0;
     HIPCHK(h, hipMemcpyAsync(&bad, h->sp_misc.p, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -33,40 +26,34 @@ static reg_status sp_voxel_device(reg_handle* h, const double* d_xyz, const doub
                             : "reg_voxel_down_sample: voxel_size too small for the extent of the cloud (voxel index exceeds 2^21)";
         return REG_BAD_ARGUMENT;
     }
-    REGCHK(sort_pairs(h, h->rp_tmp, keys, sorted, vals, svals, (size_t)n, 0, 3 * kVoxBits));
-    k_vox_heads<<<grid_for(n), 256, 0, h->stream>>>(sorted, n, heads);
-    REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n));
     uint32_t tail[2];
-    REGCHK(flag_total_async(h, heads, vox, n, tail));
-    k_vox_reduce<false><<<grid_for(n), 256, 0, h->stream>>>(sorted, svals, n, heads, vox, d_xyz, d_nrm, d_cov, 0, d_oxyz, d_onrm,
-                                                            d_ocov);
+    REGCHK(sort_runs(h, a, n, tail));
+    k_vox_reduce<false><<<grid_for(n), 256, 0, h->stream>>>(a.sorted, a.svals, n, a.heads, a.run, d_xyz, d_nrm, d_cov, 0, d_oxyz,
+                                                            d_onrm, d_ocov);
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
     *n_vox = flag_total(tail);
     return REG_OK;
 }
 
-// Flags (sp_flags) and their exclusive scan (sp_offs) of the `count` smallest (key, index) pairs among n
+// Flags (sp.heads) and their exclusive scan (sp.run) of the `count` smallest (key, index) pairs among n
 static reg_status sp_random_flags(reg_handle* h, int64_t n, int64_t count, uint64_t seed) {
-    HIPCHK(h, h->sp_flags.reserve((size_t)n * 4));
-    HIPCHK(h, h->sp_offs.reserve((size_t)n * 4));
-    uint32_t* flags = h->sp_flags.as<uint32_t>();
+    HIPCHK(h, h->sp.heads.reserve((size_t)n * 4));
+    HIPCHK(h, h->sp.run.reserve((size_t)n * 4));
+    uint32_t* flags = h->sp.heads.as<uint32_t>();
     if (count >= n) {   // ratio == 1 copies through
         HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)flags, 1, (size_t)n, h->stream));
     } else {
         HIPCHK(h, hipMemsetAsync(flags, 0, (size_t)n * 4, h->stream));
         if (count > 0) {
-            HIPCHK(h, h->sp_keys.reserve((size_t)n * 8));
-            HIPCHK(h, h->sp_keys2.reserve((size_t)n * 8));
-            HIPCHK(h, h->sp_vals.reserve((size_t)n * 4));
-            HIPCHK(h, h->sp_vals2.reserve((size_t)n * 4));
-            k_sp_rand_keys<<<grid_for(n), 256, 0, h->stream>>>(seed, n, h->sp_keys.as<uint64_t>(), h->sp_vals.as<uint32_t>());
-            REGCHK(sort_pairs(h, h->rp_tmp, h->sp_keys.as<uint64_t>(), h->sp_keys2.as<uint64_t>(), h->sp_vals.as<uint32_t>(),
-                              h->sp_vals2.as<uint32_t>(), (size_t)n, 0, 64));
-            k_sp_rand_mark<<<grid_for(count), 256, 0, h->stream>>>(h->sp_vals2.as<uint32_t>(), count, flags);
+            HIPCHK(h, h->sp.reserve((size_t)n));   // (heads and run are there already)
+            const RunArrays a = h->sp.arrays();
+            k_sp_rand_keys<<<grid_for(n), 256, 0, h->stream>>>(seed, n, a.keys, a.vals);
+            REGCHK(sort_pairs(h, h->rp_tmp, a.keys, a.sorted, a.vals, a.svals, (size_t)n, 0, 64));
+            k_sp_rand_mark<<<grid_for(count), 256, 0, h->stream>>>(a.svals, count, flags);
         }
     }
-    REGCHK(scan_excl(h, h->rp_tmp, flags, h->sp_offs.as<uint32_t>(), (size_t)n));
+    REGCHK(scan_excl(h, h->rp_tmp, flags, h->sp.run.as<uint32_t>(), (size_t)n));
     return REG_OK;
 }
 
@@ -151,9 +138,9 @@ reg_status reg_random_down_sample(reg_handle* h, const double* xyz, const double
     const int s_idx = so.add(out_idx, 1);
     HIPCHK(h, so.reserve((size_t)count));
     REGCHK(sp_random_flags(h, n, count, seed));
-    k_sp_gather_f64<<<grid_for(n), 256, 0, h->stream>>>(d_in[0], d_in[1], d_in[2], n, h->sp_flags.as<uint32_t>(),
-                                                        h->sp_offs.as<uint32_t>(), so.at<double>(0), so.at<double>(1),
-                                                        so.at<double>(2), so.at<int32_t>(s_idx));
+    k_gather_rows<9, true><<<grid_for(n), 256, 0, h->stream>>>(
+        cols64_in(d_in[0], d_in[1], d_in[2]), n, h->sp.heads.as<uint32_t>(), h->sp.run.as<uint32_t>(),
+        Cols64{so.at<double>(0), so.at<double>(1), so.at<double>(2)}, so.at<int32_t>(s_idx));
     HIPCHK(h, so.copy_back((size_t)count));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipGetLastError());
@@ -202,17 +189,14 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
     const double* cur[3] = {xyz, normals, covs};   // the cloud as it stands after each stage (device pointers)
     for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->sp_in[k], cur[k], (size_t)n * kSpWidth[k], on_device, &cur[k]));
     int64_t m = n;
-    uint32_t tail[2];
     // 1. wide crop (mapBuilderCropper_), order-preserving
     if (wide.type != REG_CROP_NONE) {
-        HIPCHK(h, h->sp_flags.reserve((size_t)m * 4));
-        HIPCHK(h, h->sp_offs.reserve((size_t)m * 4));
-        uint32_t *flags = h->sp_flags.as<uint32_t>(), *offs = h->sp_offs.as<uint32_t>();
+        HIPCHK(h, h->sp.heads.reserve((size_t)m * 4));
+        HIPCHK(h, h->sp.run.reserve((size_t)m * 4));
+        uint32_t *flags = h->sp.heads.as<uint32_t>(), *offs = h->sp.run.as<uint32_t>();
         k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(cur[0], m, wide, flags);
-        REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)m));
-        REGCHK(flag_total_async(h, flags, offs, m, tail));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        const int64_t kept = flag_total(tail);
+        int64_t kept = 0;
+        REGCHK(scan_total(h, flags, offs, m, &kept));
         if (kept > 0) {
             double* o[3] = {nullptr, nullptr, nullptr};
             for (int k = 0; k < 3; ++k)
@@ -220,7 +204,8 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
                     HIPCHK(h, h->sp_a[k].reserve((size_t)kept * kSpWidth[k] * 8));
                     o[k] = h->sp_a[k].as<double>();
                 }
-            k_sp_gather_f64<<<grid_for(m), 256, 0, h->stream>>>(cur[0], cur[1], cur[2], m, flags, offs, o[0], o[1], o[2], nullptr);
+            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m, flags, offs,
+                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
             for (int k = 0; k < 3; ++k) cur[k] = o[k];
         }
         m = kept;
@@ -275,8 +260,9 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
                     HIPCHK(h, h->sp_c[k].reserve((size_t)count * kSpWidth[k] * 8));
                     o[k] = h->sp_c[k].as<double>();
                 }
-            k_sp_gather_f64<<<grid_for(m), 256, 0, h->stream>>>(cur[0], cur[1], cur[2], m, h->sp_flags.as<uint32_t>(),
-                                                                h->sp_offs.as<uint32_t>(), o[0], o[1], o[2], nullptr);
+            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m,
+                                                                       h->sp.heads.as<uint32_t>(), h->sp.run.as<uint32_t>(),
+                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
             for (int k = 0; k < 3; ++k) cur[k] = o[k];
         }
         m = count;
@@ -293,14 +279,12 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
     for (int k = 0; k < 3; ++k)
         if (cur[k]) HIPCHK(h, copy_out(h, merge[k], cur[k], (size_t)m * kSpWidth[k] * 8, on_device));
     // 6. narrow crop (scanMatcherCropper_ at the identity pose) + open3dToPointmatcher: match_ becomes the reading
-    HIPCHK(h, h->sp_flags.reserve((size_t)m * 4));
-    HIPCHK(h, h->sp_offs.reserve((size_t)m * 4));
-    uint32_t *flags = h->sp_flags.as<uint32_t>(), *offs = h->sp_offs.as<uint32_t>();
+    HIPCHK(h, h->sp.heads.reserve((size_t)m * 4));
+    HIPCHK(h, h->sp.run.reserve((size_t)m * 4));
+    uint32_t *flags = h->sp.heads.as<uint32_t>(), *offs = h->sp.run.as<uint32_t>();
     k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(cur[0], m, narrow, flags);
-    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)m));
-    REGCHK(flag_total_async(h, flags, offs, m, tail));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t kept = flag_total(tail);
+    int64_t kept = 0;
+    REGCHK(scan_total(h, flags, offs, m, &kept));
     res->n_match = kept;
     if (kept == 0) {
         h->err = "ScanToMapIcp::narrow cropped size is zero";   // ScanToMapRegistration.cpp:66

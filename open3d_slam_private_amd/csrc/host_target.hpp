@@ -442,11 +442,8 @@ reg_status reg_set_target_f64(reg_handle* h, const double* xyz, const double* no
     HIPCHK(h, h->c_offs.reserve((size_t)m * 4));
     uint32_t *flags = h->c_flags.as<uint32_t>(), *offs = h->c_offs.as<uint32_t>();
     k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, m, c, flags);
-    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)m));
-    uint32_t last[2];
-    REGCHK(flag_total_async(h, flags, offs, m, last));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    const int64_t kept = flag_total(last);
+    int64_t kept = 0;
+    REGCHK(scan_total(h, flags, offs, m, &kept));
     if (n_kept) *n_kept = kept;
     if (kept == 0) {
         h->m = 0;
@@ -477,6 +474,13 @@ reg_status reg_get_target_source_indices(reg_handle* h, int32_t* idx) {
     HIPCHK(h, hipMemcpyAsync(idx, h->c_idx.p, (size_t)h->crop_kept * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return REG_OK;
+}
+
+// The reference's t_* buffers as the arrays of sort_runs: the table build shares them, so they stay loose fields and are
+// reserved where they are used.
+static RunArrays target_run_arrays(reg_handle* h) {
+    return RunArrays{h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
+                     h->t_vals2.as<uint32_t>(), h->t_flags.as<uint32_t>(), h->t_scan.as<uint32_t>()};
 }
 
 reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const double* normals, const double* covs, int64_t m,
@@ -539,17 +543,13 @@ reg_status reg_voxelize_within_volume(reg_handle* h, const double* xyz, const do
     k_vox_scatter<<<grid_for(m), 256, 0, h->stream>>>(d_xyz, d_nrm, d_cov, m, inv, f_in, o_in, o_out, h->t_keys.as<uint64_t>(),
                                                       h->t_vals.as<uint32_t>(), d_oxyz, d_onrm, d_ocov);
     if (n_in > 0) {
-        REGCHK(sort_pairs(h, h->rp_tmp, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
-                          h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits));
         HIPCHK(h, h->t_flags.reserve((size_t)n_in * 4));
         HIPCHK(h, h->t_scan.reserve((size_t)n_in * 4));
-        uint32_t *heads = h->t_flags.as<uint32_t>(), *vox = h->t_scan.as<uint32_t>();
-        k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads);
-        REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n_in));
+        const RunArrays a = target_run_arrays(h);
         uint32_t lv[2];
-        REGCHK(flag_total_async(h, heads, vox, n_in, lv));
-        k_vox_reduce<true><<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), h->t_vals2.as<uint32_t>(), n_in, heads,
-                                                                  vox, d_xyz, d_nrm, d_cov, n_outs, d_oxyz, d_onrm, d_ocov);
+        REGCHK(sort_runs(h, a, n_in, lv));
+        k_vox_reduce<true><<<grid_for(n_in), 256, 0, h->stream>>>(a.sorted, a.svals, n_in, a.heads, a.run, d_xyz, d_nrm, d_cov, n_outs,
+                                                                  d_oxyz, d_onrm, d_ocov);
         HIPCHK(h, hipStreamSynchronize(h->stream));
         n_vox = flag_total(lv);
     }
@@ -596,21 +596,17 @@ static reg_status carve_marks(reg_handle* h, const double* d_map, const double* 
     HIPCHK(h, h->t_vals.reserve((size_t)n_in * 4));
     HIPCHK(h, h->t_vals2.reserve((size_t)n_in * 4));
     k_carve_keys<<<grid_for(m), 256, 0, h->stream>>>(d_map, m, inv, f_in, o_in, h->t_keys.as<uint64_t>(), h->t_vals.as<uint32_t>());
-    REGCHK(sort_pairs(h, h->rp_tmp, h->t_keys.as<uint64_t>(), h->t_keys2.as<uint64_t>(), h->t_vals.as<uint32_t>(),
-                      h->t_vals2.as<uint32_t>(), (size_t)n_in, 0, 3 * kVoxBits));
     // 2. unique voxels
     HIPCHK(h, h->t_flags.reserve((size_t)n_in * 4));
     HIPCHK(h, h->t_scan.reserve((size_t)n_in * 4));
-    uint32_t *heads = h->t_flags.as<uint32_t>(), *vox = h->t_scan.as<uint32_t>();
-    k_vox_heads<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads);
-    REGCHK(scan_excl(h, h->rp_tmp, heads, vox, (size_t)n_in));
+    const RunArrays a = target_run_arrays(h);
     uint32_t lv[2];
-    REGCHK(flag_total_async(h, heads, vox, n_in, lv));
+    REGCHK(sort_runs(h, a, n_in, lv));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     const int64_t nu = flag_total(lv);
     HIPCHK(h, h->v_ukeys.reserve((size_t)nu * 8));
     HIPCHK(h, h->v_ustart.reserve((size_t)(nu + 1) * 4));
-    k_carve_unique<<<grid_for(n_in), 256, 0, h->stream>>>(h->t_keys2.as<uint64_t>(), n_in, heads, vox, h->v_ukeys.as<uint64_t>(),
+    k_carve_unique<<<grid_for(n_in), 256, 0, h->stream>>>(a.sorted, n_in, a.heads, a.run, h->v_ukeys.as<uint64_t>(),
                                                           h->v_ustart.as<uint32_t>());
     const uint32_t n_in32 = (uint32_t)n_in;
     HIPCHK(h, hipMemcpyAsync(h->v_ustart.as<uint32_t>() + nu, &n_in32, 4, hipMemcpyHostToDevice, h->stream));
@@ -618,14 +614,9 @@ static reg_status carve_marks(reg_handle* h, const double* d_map, const double* 
     HIPCHK(h, hipMemsetAsync(mark, 0, (size_t)m * 4, h->stream));
     k_carve_rays<<<grid_for(n_scan), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], voxel_size, max_ray,
                                                           truncation, min_dot, inv, h->v_ukeys.as<uint64_t>(),
-                                                          h->v_ustart.as<uint32_t>(), nu, h->t_vals2.as<uint32_t>(), d_nrm, mark);
+                                                          h->v_ustart.as<uint32_t>(), nu, a.svals, d_nrm, mark);
     // 4. ascending list of marked map indices
-    REGCHK(scan_excl(h, h->rp_tmp, mark, o_mark, (size_t)m));
-    uint32_t rt[2];
-    REGCHK(flag_total_async(h, mark, o_mark, m, rt));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    *n_marked = flag_total(rt);
-    return REG_OK;
+    return scan_total(h, mark, o_mark, m, n_marked);
 }
 
 reg_status reg_carve_indices(reg_handle* h, const double* map_xyz, const double* map_normals, int64_t m,

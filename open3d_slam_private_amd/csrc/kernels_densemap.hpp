@@ -1,85 +1,43 @@
 // kernels_densemap.hpp -- the dense map (o3d_slam::VoxelizedPointCloud, Voxel.cpp:38-114): a resident table of
 // per-voxel running sums, sorted by ascending 64-bit key; merge of a cloud into it, neighbourhood carve, export, transform,
-// centre, first-wins de-duplication.  fp64, one rounding per operation (the build forbids contraction).
+// centre, first-wins de-duplication.  fp64, one rounding per operation (the build forbids contraction).  The transform, the
+// voxel key, the lower bound and the gather of insert_scan are those of kernels_cloud64.hpp.
 // Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
 #pragma once
 
-struct DmT {   // a 4x4 transform, row-major: m[4 * r + c]
-    double m[16];
-};
 constexpr int kDmMaxOffsets = 16;   // neighbourhood offsets per axis at most (reg_dense_map_carve)
 struct DmOffsets {
     double d[kDmMaxOffsets];   // the running sum -r, +v, +v, ... while <= r, built on the host
     int n;
 };
 
-__device__ __forceinline__ bool dm_fits(double fx, double fy, double fz) {   // false for NaN too
-    return fabs(fx) < (double)kVoxOff && fabs(fy) < (double)kVoxOff && fabs(fz) < (double)kVoxOff;
-}
-__device__ __forceinline__ uint64_t dm_pack(double fx, double fy, double fz) {   // the packing of k_vox_scatter
-    return ((uint64_t)((long long)fz + kVoxOff) << (2 * kVoxBits)) | ((uint64_t)((long long)fy + kVoxOff) << kVoxBits) |
-           (uint64_t)((long long)fx + kVoxOff);
-}
-// first position of keys[0, n) that is >= key
-__device__ __forceinline__ int64_t dm_lower_bound(const uint64_t* __restrict__ keys, int64_t n, uint64_t key) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
-    return lo;
-}
-
-// ---- insert, stage 1: optional transform (the formula of reg_overlap_indices) and the map key floor(p * (1 / voxel)) ----
-// use_T: the transformed points go to oxyz (normals (T (n, 0)).head<3>() to onrm) and the later stages read those.
+// ---- insert, stage 1: optional transform (xform_point, xform_dir) and the map key (vox_index, vox_pack) ----
+// use_T: the transformed points go to oxyz (the normals to onrm) and the later stages read those.
 // *bad: bit 0 a non-finite coordinate, bit 1 an index outside +-2^20
-__global__ void k_dm_keys(const double* __restrict__ xyz, const double* __restrict__ nrm, int64_t n, int use_T, DmT T, double inv,
-                          double* __restrict__ oxyz, double* __restrict__ onrm, uint64_t* __restrict__ keys,
+__global__ void k_dm_keys(const double* __restrict__ xyz, const double* __restrict__ nrm, int64_t n, int use_T, Xform64 T,
+                          double inv, double* __restrict__ oxyz, double* __restrict__ onrm, uint64_t* __restrict__ keys,
                           uint32_t* __restrict__ vals, uint32_t* __restrict__ bad) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
     if (use_T) {
-        const double x = p[0], y = p[1], z = p[2];
-        double a = T.m[12] * x;
-        double b = T.m[13] * y;
-        double w = a + b;
-        a = T.m[14] * z;
-        w = w + a;
-        w = w + T.m[15];
-        for (int r = 0; r < 3; ++r) {
-            a = T.m[4 * r] * x;
-            b = T.m[4 * r + 1] * y;
-            double s = a + b;
-            a = T.m[4 * r + 2] * z;
-            s = s + a;
-            s = s + T.m[4 * r + 3];
-            p[r] = s / w;
-            oxyz[3 * i + r] = p[r];
-        }
+        xform_point(T, p[0], p[1], p[2], p);
+        for (int r = 0; r < 3; ++r) oxyz[3 * i + r] = p[r];
         if (nrm) {
-            const double nx = nrm[3 * i], ny = nrm[3 * i + 1], nz = nrm[3 * i + 2];
-            for (int r = 0; r < 3; ++r) {
-                a = T.m[4 * r] * nx;
-                b = T.m[4 * r + 1] * ny;
-                double s = a + b;
-                a = T.m[4 * r + 2] * nz;
-                onrm[3 * i + r] = s + a;
-            }
+            double d[3];
+            xform_dir(T, nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2], d);
+            for (int r = 0; r < 3; ++r) onrm[3 * i + r] = d[r];
         }
     }
     vals[i] = (uint32_t)i;
     const bool finite = fabs(p[0]) < INFINITY && fabs(p[1]) < INFINITY && fabs(p[2]) < INFINITY;   // false for NaN too
-    const double fx = floor(p[0] * inv), fy = floor(p[1] * inv), fz = floor(p[2] * inv);
-    if (!finite || !dm_fits(fx, fy, fz)) {
+    const double fx = vox_index(p[0], inv), fy = vox_index(p[1], inv), fz = vox_index(p[2], inv);
+    if (!finite || !vox_fits(fx, fy, fz)) {
         atomicOr(bad, finite ? 2u : 1u);
         keys[i] = 0;
         return;
     }
-    keys[i] = dm_pack(fx, fy, fz);
+    keys[i] = vox_pack(fx, fy, fz);
 }
 
 // ---- insert, stage 4: one thread per run head of the sorted cloud keys.  rank[run] = position of the run's key among the
@@ -90,7 +48,7 @@ __global__ void k_dm_rank(const uint64_t* __restrict__ skeys, int64_t n, const u
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n || !heads[i]) return;
     const uint64_t key = skeys[i];
-    const int64_t lb = dm_lower_bound(rkeys, n_res, key);
+    const int64_t lb = key_lower_bound(rkeys, n_res, key);
     const bool found = lb < n_res && rkeys[lb] == key;
     const uint32_t r = run[i];
     rank[r] = (uint32_t)lb;
@@ -121,7 +79,7 @@ __global__ void k_dm_copy(DmCols in, int64_t n_res, const uint32_t* __restrict__
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n_res || touched[i]) return;
     const uint64_t key = in.key[i];
-    const size_t o = (size_t)(i + dm_lower_bound(new_keys, n_new, key));
+    const size_t o = (size_t)(i + key_lower_bound(new_keys, n_new, key));
     out.key[o] = key;
     out.cnt[o] = in.cnt[i];
     for (int k = 0; k < 3; ++k) out.pos[3 * o + k] = in.pos[3 * i + k];
@@ -150,7 +108,7 @@ __global__ void k_dm_accumulate(const uint64_t* __restrict__ skeys, const uint32
     if (is_new[r]) {
         o = lb + new_off[r];
     } else {
-        o = lb + (size_t)dm_lower_bound(new_keys, n_new, key);
+        o = lb + (size_t)key_lower_bound(new_keys, n_new, key);
         cnt = in.cnt[lb];
         for (int k = 0; k < 3; ++k) {
             p[k] = in.pos[3 * lb + k];
@@ -184,8 +142,8 @@ __global__ void k_dm_accumulate(const uint64_t* __restrict__ skeys, const uint32
         for (int k = 0; k < 3; ++k) out.col[3 * o + k] = cc[k];
 }
 
-// ---- insert_scan: the dense-map cropper and ColorRangeCropper (croppers.cpp:178-239) as one flag; compaction of the three
-// fp64 x 3 arrays (offs = exclusive scan of flags; nrm / col may be null)
+// ---- insert_scan: the dense-map cropper and ColorRangeCropper (croppers.cpp:178-239) as one flag; the compaction of the
+// three fp64 x 3 arrays is k_gather_rows<3, true>
 __global__ void k_dm_scan_flags(const double* __restrict__ xyz, const double* __restrict__ col, int64_t n, CropCfg c, double lo0,
                                 double lo1, double lo2, double hi0, double hi1, double hi2, uint32_t* __restrict__ flags) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -196,18 +154,6 @@ __global__ void k_dm_scan_flags(const double* __restrict__ xyz, const double* __
         keep = keep && lo0 <= r && lo1 <= g && lo2 <= b && r <= hi0 && g <= hi1 && b <= hi2;
     }
     flags[i] = keep ? 1u : 0u;
-}
-__global__ void k_dm_gather3(const double* __restrict__ xyz, const double* __restrict__ nrm, const double* __restrict__ col,
-                             int64_t n, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ offs,
-                             double* __restrict__ oxyz, double* __restrict__ onrm, double* __restrict__ ocol) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= n || !flags[i]) return;
-    const size_t o = offs[i];
-    for (int k = 0; k < 3; ++k) oxyz[3 * o + k] = xyz[3 * i + k];
-    if (nrm)
-        for (int k = 0; k < 3; ++k) onrm[3 * o + k] = nrm[3 * i + k];
-    if (col)
-        for (int k = 0; k < 3; ++k) ocol[3 * o + k] = col[3 * i + k];
 }
 
 // ---- carve (getKeysOfCarvedPoints, helpers.cpp:360-390; getVoxelsWithinPointNeighborhood, VoxelHashMap.cpp:13-45) ----
@@ -256,7 +202,7 @@ __global__ void __launch_bounds__(256) k_dm_carve(const double* __restrict__ sca
                 tz = pz + s_off[iz];
             }
             const double kx = floor(tx / voxel), ky = floor(ty / voxel), kz = floor(tz / voxel);
-            if (!dm_fits(kx, ky, kz)) continue;   // cannot be in the map (NaN included)
+            if (!vox_fits(kx, ky, kz)) continue;   // cannot be in the map (NaN included)
             if (c < cube) {
                 double cx = kx * voxel;
                 cx = cx + half_voxel;
@@ -272,8 +218,8 @@ __global__ void __launch_bounds__(256) k_dm_carve(const double* __restrict__ sca
                 q = q + u;
                 if (!(sqrt(q) <= radius)) continue;
             }
-            const uint64_t key = dm_pack(kx, ky, kz);
-            const int64_t lb = dm_lower_bound(rkeys, n_res, key);
+            const uint64_t key = vox_pack(kx, ky, kz);
+            const int64_t lb = key_lower_bound(rkeys, n_res, key);
             if (lb < n_res && rkeys[lb] == key) mark[lb] = 1u;
         }
         distance += step;
@@ -286,18 +232,12 @@ __global__ void k_dm_keep_flags(const uint32_t* __restrict__ mark, int64_t n, ui
     if (i >= n) return;
     keep[i] = mark[i] ? 0u : 1u;
 }
-__device__ __forceinline__ void dm_unpack(uint64_t key, int32_t* __restrict__ out) {
-    const uint64_t mask = (1ull << kVoxBits) - 1;
-    out[0] = (int32_t)((long long)(key & mask) - kVoxOff);
-    out[1] = (int32_t)((long long)((key >> kVoxBits) & mask) - kVoxOff);
-    out[2] = (int32_t)((long long)((key >> (2 * kVoxBits)) & mask) - kVoxOff);
-}
 __global__ void k_dm_erase(DmCols in, int64_t n, const uint32_t* __restrict__ mark, const uint32_t* __restrict__ keep_off,
                            const uint32_t* __restrict__ rem_off, DmCols out, int32_t* __restrict__ removed) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (mark[i]) {
-        if (removed) dm_unpack(in.key[i], removed + 3 * (size_t)rem_off[i]);
+        if (removed) vox_unpack(in.key[i], removed + 3 * (size_t)rem_off[i]);
         return;
     }
     const size_t o = keep_off[i];
@@ -322,13 +262,14 @@ __global__ void k_dm_export(DmCols in, int64_t n, double* __restrict__ oxyz, dou
         for (int k = 0; k < 3; ++k) onrm[3 * i + k] = in.nrm[3 * i + k] / dc;
     if (ocol)
         for (int k = 0; k < 3; ++k) ocol[3 * i + k] = in.col[3 * i + k] / dc;
-    if (okeys) dm_unpack(in.key[i], okeys + 3 * i);
+    if (okeys) vox_unpack(in.key[i], okeys + 3 * i);
     if (ocnt) ocnt[i] = in.cnt[i];
 }
 
-// ---- VoxelizedPointCloud::transform (Voxel.cpp:49-64), literally: position sum and normal sum each become R S + t, per
-// row ((R0 x + R1 y) + R2 z) + t; keys, colour sums and counts stay.  Written into the spare side.
-__global__ void k_dm_transform(DmCols in, int64_t n, DmT T, DmCols out) {
+// ---- VoxelizedPointCloud::transform (Voxel.cpp:49-64), literally: position sum and normal sum each become R S + t
+// (xform_row with the translation, and no division by w: this kernel's own rule); keys, colour sums and counts stay.
+// Written into the spare side.
+__global__ void k_dm_transform(DmCols in, int64_t n, Xform64 T, DmCols out) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
     out.key[i] = in.key[i];
@@ -338,14 +279,8 @@ __global__ void k_dm_transform(DmCols in, int64_t n, DmT T, DmCols out) {
         double* d = f ? out.nrm : out.pos;
         if (!s) continue;
         const double x = s[3 * i], y = s[3 * i + 1], z = s[3 * i + 2];
-        for (int r = 0; r < 3; ++r) {
-            double a = T.m[4 * r] * x;
-            double b = T.m[4 * r + 1] * y;
-            double v = a + b;
-            a = T.m[4 * r + 2] * z;
-            v = v + a;
-            d[3 * i + r] = v + T.m[4 * r + 3];
-        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) d[3 * i + r] = xform_row<true>(T, r, x, y, z);
     }
     if (out.col)
         for (int k = 0; k < 3; ++k) out.col[3 * i + k] = in.col[3 * i + k];

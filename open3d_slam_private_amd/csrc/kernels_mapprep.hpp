@@ -1,4 +1,5 @@
-// kernels_mapprep.hpp -- target-side preparation rows: cropping volume, fp64 -> fp32, voxelize-within-volume
+// kernels_mapprep.hpp -- target-side preparation rows: cropping volume, fp64 -> fp32, voxelize-within-volume, space carving.
+// The voxel key, the row copy and the fp32 row cast are those of kernels_cloud64.hpp.
 // Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
 #pragma once
 
@@ -39,23 +40,7 @@ __global__ void k_crop_gather(const double* __restrict__ xyz, const double* __re
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= m || !flags[i]) return;
     const size_t o = offs[i];
-    oxyz[3 * o + 0] = (float)xyz[3 * i + 0];
-    oxyz[3 * o + 1] = (float)xyz[3 * i + 1];
-    oxyz[3 * o + 2] = (float)xyz[3 * i + 2];
-    if (nrm) {
-        onrm[3 * o + 0] = (float)nrm[3 * i + 0];
-        onrm[3 * o + 1] = (float)nrm[3 * i + 1];
-        onrm[3 * o + 2] = (float)nrm[3 * i + 2];
-    }
-    if (cov) {
-        const double* c = cov + 9 * i;   // Matrix3d, symmetric: xx xy xz / . yy yz / . . zz
-        ocov[6 * o + 0] = (float)c[0];
-        ocov[6 * o + 1] = (float)c[1];
-        ocov[6 * o + 2] = (float)c[2];
-        ocov[6 * o + 3] = (float)c[4];
-        ocov[6 * o + 4] = (float)c[5];
-        ocov[6 * o + 5] = (float)c[8];
-    }
+    cast_row_f32(xyz, nrm, cov, i, oxyz, onrm, ocov, o);
     oidx[o] = (int32_t)i;
 }
 
@@ -64,23 +49,10 @@ __global__ void k_cast_cloud_f64(const double* __restrict__ xyz, const double* _
                                  int64_t n, float* __restrict__ oxyz, float* __restrict__ onrm, float* __restrict__ ocov) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    for (int k = 0; k < 3; ++k) oxyz[3 * i + k] = (float)xyz[3 * i + k];
-    if (nrm)
-        for (int k = 0; k < 3; ++k) onrm[3 * i + k] = (float)nrm[3 * i + k];
-    if (cov) {
-        const double* c = cov + 9 * i;   // Matrix3d, symmetric: xx xy xz / . yy yz / . . zz
-        ocov[6 * i + 0] = (float)c[0];
-        ocov[6 * i + 1] = (float)c[1];
-        ocov[6 * i + 2] = (float)c[2];
-        ocov[6 * i + 3] = (float)c[4];
-        ocov[6 * i + 4] = (float)c[5];
-        ocov[6 * i + 5] = (float)c[8];
-    }
+    cast_row_f32(xyz, nrm, cov, i, oxyz, onrm, ocov, (size_t)i);
 }
 
 // ---- voxelizeWithinCroppingVolume (helpers.cpp:117-192) ----
-constexpr int kVoxBits = 21;                       // voxel index bits per axis in the sort key (offset binary)
-constexpr long long kVoxOff = 1ll << (kVoxBits - 1);
 __global__ void k_vox_classify(const double* __restrict__ xyz, int64_t m, CropCfg c, double inv, uint32_t* __restrict__ f_in,
                                uint32_t* __restrict__ f_out, uint32_t* __restrict__ overflow) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -89,10 +61,7 @@ __global__ void k_vox_classify(const double* __restrict__ xyz, int64_t m, CropCf
     const bool in = crop_inside(c, x, y, z);
     f_in[i] = in ? 1u : 0u;
     f_out[i] = in ? 0u : 1u;
-    if (in) {
-        const double vx = floor(x * inv), vy = floor(y * inv), vz = floor(z * inv);
-        if (!(fabs(vx) < (double)kVoxOff && fabs(vy) < (double)kVoxOff && fabs(vz) < (double)kVoxOff)) atomicOr(overflow, 1u);
-    }
+    if (in && !vox_fits(vox_index(x, inv), vox_index(y, inv), vox_index(z, inv))) atomicOr(overflow, 1u);
 }
 __global__ void k_vox_scatter(const double* __restrict__ xyz, const double* __restrict__ nrm, const double* __restrict__ cov,
                               int64_t m, double inv, const uint32_t* __restrict__ f_in, const uint32_t* __restrict__ o_in,
@@ -101,18 +70,10 @@ __global__ void k_vox_scatter(const double* __restrict__ xyz, const double* __re
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= m) return;
     if (f_in[i]) {
-        const long long vx = (long long)floor(xyz[3 * i] * inv) + kVoxOff;
-        const long long vy = (long long)floor(xyz[3 * i + 1] * inv) + kVoxOff;
-        const long long vz = (long long)floor(xyz[3 * i + 2] * inv) + kVoxOff;
-        keys[o_in[i]] = ((uint64_t)vz << (2 * kVoxBits)) | ((uint64_t)vy << kVoxBits) | (uint64_t)vx;
+        keys[o_in[i]] = vox_pack(vox_index(xyz[3 * i], inv), vox_index(xyz[3 * i + 1], inv), vox_index(xyz[3 * i + 2], inv));
         vals[o_in[i]] = (uint32_t)i;
     } else {
-        const size_t o = o_out[i];
-        for (int k = 0; k < 3; ++k) oxyz[3 * o + k] = xyz[3 * i + k];
-        if (nrm)
-            for (int k = 0; k < 3; ++k) onrm[3 * o + k] = nrm[3 * i + k];
-        if (cov)
-            for (int k = 0; k < 9; ++k) ocov[9 * o + k] = cov[9 * i + k];
+        copy_row<9>(cols64_in(xyz, nrm, cov), i, Cols64{oxyz, onrm, ocov}, (int64_t)o_out[i]);
     }
 }
 __global__ void k_vox_heads(const uint64_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ flags) {
@@ -179,10 +140,7 @@ __global__ void k_carve_keys(const double* __restrict__ xyz, int64_t m, double i
                              const uint32_t* __restrict__ o_in, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= m || !f_in[i]) return;
-    const long long vx = (long long)floor(xyz[3 * i] * inv) + kVoxOff;
-    const long long vy = (long long)floor(xyz[3 * i + 1] * inv) + kVoxOff;
-    const long long vz = (long long)floor(xyz[3 * i + 2] * inv) + kVoxOff;
-    keys[o_in[i]] = ((uint64_t)vz << (2 * kVoxBits)) | ((uint64_t)vy << kVoxBits) | (uint64_t)vx;
+    keys[o_in[i]] = vox_pack(vox_index(xyz[3 * i], inv), vox_index(xyz[3 * i + 1], inv), vox_index(xyz[3 * i + 2], inv));
     vals[o_in[i]] = (uint32_t)i;
 }
 // unique voxel keys and the first sorted position of each (ustart[nu] = n is written by the host)
@@ -217,18 +175,10 @@ __global__ void k_carve_rays(const double* __restrict__ scan, int64_t n_scan, do
         const double py = t + sy;
         t = distance * uz;
         const double pz = t + sz;
-        const double fx = floor(px * inv), fy = floor(py * inv), fz = floor(pz * inv);
-        if (fabs(fx) < (double)kVoxOff && fabs(fy) < (double)kVoxOff && fabs(fz) < (double)kVoxOff) {
-            const uint64_t key = ((uint64_t)((long long)fz + kVoxOff) << (2 * kVoxBits)) |
-                                 ((uint64_t)((long long)fy + kVoxOff) << kVoxBits) | (uint64_t)((long long)fx + kVoxOff);
-            int64_t lo = 0, hi = nu;   // first ukeys[lo] >= key
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (ukeys[mid] < key)
-                    lo = mid + 1;
-                else
-                    hi = mid;
-            }
+        const double fx = vox_index(px, inv), fy = vox_index(py, inv), fz = vox_index(pz, inv);
+        if (vox_fits(fx, fy, fz)) {
+            const uint64_t key = vox_pack(fx, fy, fz);
+            const int64_t lo = key_lower_bound(ukeys, nu, key);
             if (lo < nu && ukeys[lo] == key) {
                 for (uint32_t j = ustart[lo]; j < ustart[lo + 1]; ++j) {
                     const uint32_t id = vals[j];

@@ -2,56 +2,29 @@
 // Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
 #pragma once
 
-// sourceToTarget, row-major, by value; on == 0: identity, the points are keyed as they are
-struct OvlT {
-    double m[16];
-    int on;
-};
-
 constexpr uint64_t kOvlBadKey = ~0ull;   // a valid key has bit 63 clear
 
-// One thread per point: optional transform (helpers.cpp:302-303: T * (x, y, z, 1), divided by w), then the voxel key of
-// VoxelHashMap.hpp:43-51 in the packing of k_carve_keys.  A non-finite coordinate or an index outside +-2^20 raises *bad.
-__global__ void k_ovl_keys(const double* __restrict__ xyz, int64_t n, OvlT T, double inv, uint64_t* __restrict__ keys,
-                           uint32_t* __restrict__ bad) {
+// One thread per point: with use_T the point goes through sourceToTarget first (helpers.cpp:302-303; xform_point), then the
+// map voxel key (vox_index, vox_pack).  A non-finite coordinate or an index outside +-2^20 raises *bad.
+__global__ void k_ovl_keys(const double* __restrict__ xyz, int64_t n, int use_T, Xform64 T, double inv,
+                           uint64_t* __restrict__ keys, uint32_t* __restrict__ bad) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    if (T.on) {
-        double r[4];
-        for (int k = 0; k < 4; ++k) {
-            double a = T.m[4 * k] * x;
-            double b = T.m[4 * k + 1] * y;
-            double s = a + b;
-            a = T.m[4 * k + 2] * z;
-            s = s + a;
-            r[k] = s + T.m[4 * k + 3];
-        }
-        x = r[0] / r[3];
-        y = r[1] / r[3];
-        z = r[2] / r[3];
-    }
-    const double vx = floor(x * inv), vy = floor(y * inv), vz = floor(z * inv);
-    if (!(fabs(vx) < (double)kVoxOff && fabs(vy) < (double)kVoxOff && fabs(vz) < (double)kVoxOff)) {
+    double p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+    if (use_T) xform_point(T, p[0], p[1], p[2], p);
+    const double vx = vox_index(p[0], inv), vy = vox_index(p[1], inv), vz = vox_index(p[2], inv);
+    if (!vox_fits(vx, vy, vz)) {
         atomicOr(bad, 1u);
         keys[i] = kOvlBadKey;
         return;
     }
-    keys[i] = ((uint64_t)((long long)vz + kVoxOff) << (2 * kVoxBits)) | ((uint64_t)((long long)vy + kVoxOff) << kVoxBits) |
-              (uint64_t)((long long)vx + kVoxOff);
+    keys[i] = vox_pack(vx, vy, vz);
 }
 
-// points of a layer in the voxel `key`: binary search in the layer's ascending unique keys (0: the layer has none there)
+// points of a layer in the voxel `key`: its place in the layer's ascending unique keys (0: the layer has none there)
 __device__ __forceinline__ uint32_t ovl_count(const uint64_t* __restrict__ ukeys, const uint32_t* __restrict__ ucnt,
                                               int64_t nu, uint64_t key) {
-    int64_t lo = 0, hi = nu;   // first ukeys[lo] >= key
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ukeys[mid] < key)
-            lo = mid + 1;
-        else
-            hi = mid;
-    }
+    const int64_t lo = key_lower_bound(ukeys, nu, key);
     return (lo < nu && ukeys[lo] == key) ? ucnt[lo] : 0u;
 }
 

@@ -1,5 +1,6 @@
 // kernels_scanprep.hpp -- the scan front end (ScanToMapRegistration.cpp:36-69): Open3D's VoxelDownSample and
-// RandomDownSample restated, the fp64 gather both share with the wide crop, the widening of estimated normals
+// RandomDownSample restated, the widening of estimated normals.  The fp64 gather of the random selection and
+// of the wide crop is k_gather_rows of kernels_cloud64.hpp.
 // Part of the single translation unit reg_core.hip (included there, in this order; not a standalone header).
 #pragma once
 
@@ -49,7 +50,9 @@ __global__ void __launch_bounds__(256) k_sp_min_final(const double* __restrict__
         out[3 + t] = sm[t][0] - half;
     }
 }
-// keys in (z, y, x) significance, value = input index.  *bad: bit 0 a non-finite coordinate, bit 1 an index >= 2^21
+// keys in (z, y, x) significance, value = input index.  *bad: bit 0 a non-finite coordinate, bit 1 an index >= 2^21.
+// Open3D's index rule (origin subtraction, a division, the unsigned range [0, 2^21)), not the map's vox_index / vox_pack
+// of kernels_cloud64.hpp: the formula and the packing below are this kernel's own on purpose.
 __global__ void k_sp_vox_keys(const double* __restrict__ xyz, int64_t n, const double* __restrict__ origin, double voxel,
                               uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* __restrict__ bad) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -84,23 +87,6 @@ __global__ void k_sp_rand_mark(const uint32_t* __restrict__ sorted_vals, int64_t
     const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (j >= count) return;
     flags[sorted_vals[j]] = 1u;
-}
-
-// offs = exclusive scan of flags: order-preserving compaction of the fp64 rows (any array and oidx may be null)
-__global__ void k_sp_gather_f64(const double* __restrict__ xyz, const double* __restrict__ nrm, const double* __restrict__ cov,
-                                int64_t n, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ offs,
-                                double* __restrict__ oxyz, double* __restrict__ onrm, double* __restrict__ ocov,
-                                int32_t* __restrict__ oidx) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i >= n || !flags[i]) return;
-    const size_t o = offs[i];
-    if (xyz)
-        for (int k = 0; k < 3; ++k) oxyz[3 * o + k] = xyz[3 * i + k];
-    if (nrm)
-        for (int k = 0; k < 3; ++k) onrm[3 * o + k] = nrm[3 * i + k];
-    if (cov)
-        for (int k = 0; k < 9; ++k) ocov[9 * o + k] = cov[9 * i + k];
-    if (oidx) oidx[o] = (int32_t)i;
 }
 
 // estimated fp32 normals (and the six covariance entries xx xy xz yy yz zz) -> Open3D's fp64 rows (exact)

@@ -40,6 +40,7 @@ using namespace o3dreg;
 #include "kernels_reading.hpp"
 #include "kernels_match.hpp"
 #include "kernels_fused.hpp"
+#include "kernels_cloud64.hpp"
 #include "kernels_mapprep.hpp"
 #include "kernels_xicp.hpp"
 #include "kernels_update.hpp"

@@ -16,7 +16,8 @@ def _f(v):
 
 
 def map_key(p, voxel):
-    """floor(p * (1.0 / voxel)) per axis -> (x, y, z); ValueError for a non-finite coordinate or an index outside +-2^20."""
+    """floor(p * (1.0 / voxel)) per axis -> (x, y, z); ValueError for a non-finite coordinate or an index outside +-2^20.
+    On the device: vox_index / vox_fits / vox_pack of csrc/kernels_cloud64.hpp, called from k_dm_keys."""
     inv = _f(1.0) / _f(voxel)
     out = []
     for c in p:

@@ -17,7 +17,8 @@ class Refused(ValueError):
 
 
 def transform_point(T, p):
-    """w = ((T30 x + T31 y) + T32 z) + T33; x' = (((T00 x + T01 y) + T02 z) + T03) / w"""
+    """w = ((T30 x + T31 y) + T32 z) + T33; x' = (((T00 x + T01 y) + T02 z) + T03) / w.  On the device: xform_point;
+    transform_normal and transform_cov below: xform_dir, xform_cov (csrc/kernels_cloud64.hpp)."""
     x, y, z = (np.float64(v) for v in p)
     with np.errstate(invalid="ignore"):        # 0 * inf and NaN rows pass through as the arithmetic leaves them
         w = ((T[3, 0] * x + T[3, 1] * y) + T[3, 2] * z) + T[3, 3]
@@ -59,8 +60,8 @@ def center(xyz):
 
 
 def check_keys(xyz, mask, voxel, what):
-    """The refusal of k_vox_classify: a row inside the volume whose index floor(p * (1 / voxel)) is not within +-(2^20 - 1)
-    on every axis (a non-finite coordinate included)."""
+    """The refusal of k_vox_classify (vox_index / vox_fits of csrc/kernels_cloud64.hpp): a row inside the
+    volume whose index floor(p * (1 / voxel)) is not within +-(2^20 - 1) on every axis (a non-finite coordinate included)."""
     inv = np.float64(1.0) / np.float64(voxel)
     for p in np.asarray(xyz, np.float64)[mask]:
         for c in p:
