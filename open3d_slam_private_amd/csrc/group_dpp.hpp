@@ -144,4 +144,36 @@ __device__ __forceinline__ double wave_xor_f64(double v) {
 #endif
 }
 
+// LDS written by some lanes of a wave becomes visible to its other lanes: the lane groups of the k-NN kernels (and whole
+// waves that work alone) exchange through LDS without a workgroup barrier.
+__device__ __forceinline__ void group_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// Sum over a workgroup of 256 threads (4 waves) of NV doubles per lane: thread c < NV returns the total of component c,
+// the waves added in the fixed order (0 + 1) + (2 + 3); the other threads return 0.  v[] is left with the wave's sums.
+// A second call with the same NV in one kernel needs a __syncthreads() in between (the LDS rows are reused).
+template <int NV>
+__device__ __forceinline__ double block_sum(double* v) {
+    __shared__ double red[4][NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) red[wave][k] = v[k];
+    __syncthreads();
+    if (threadIdx.x >= NV) return 0.0;
+    return (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+// ... stored to dst[NV] (global or LDS; a reader in the same workgroup needs a barrier first)
+template <int NV>
+__device__ __forceinline__ void block_sum_store(double* v, double* dst) {
+    const double t = block_sum<NV>(v);
+    if (threadIdx.x < NV) dst[threadIdx.x] = t;
+}
+
 }  // namespace o3dreg

@@ -364,11 +364,7 @@ __global__ void k_halo_rep(const uint2* __restrict__ dir, const float4* __restri
     for (uint32_t j = hd.x; j < hd.x + hd.y; ++j) {
         const float4 t = halo_pts[j];
         const float dx = t.x - cx, dy = t.y - cy, dz = t.z - cz;
-        float a = dx * dx;
-        float b = dy * dy;
-        float d2 = a + b;
-        a = dz * dz;
-        d2 = d2 + a;
+        const float d2 = sum_sq3(dx, dy, dz);
         const uint32_t pos = __float_as_uint(t.w);
         if (d2 < bd || (d2 == bd && pos < bp)) {
             bd = d2;

@@ -175,12 +175,7 @@ __global__ void __launch_bounds__(256) k_dm_carve(const double* __restrict__ sca
     const int64_t i = blockIdx.x * (int64_t)4 + (threadIdx.x >> 6);
     if (i >= n_scan) return;   // wave-uniform, after the only barrier
     const double dx = scan[3 * i] - sx, dy = scan[3 * i + 1] - sy, dz = scan[3 * i + 2] - sz;
-    double a = dx * dx;
-    double b = dy * dy;
-    double s2 = a + b;
-    a = dz * dz;
-    s2 = s2 + a;
-    const double length = sqrt(s2);
+    const double length = sqrt(sum_sq3(dx, dy, dz));
     if (!(length > 0.0) || !(length < INFINITY)) return;   // as k_carve_rays: zero-length and non-finite rays are skipped
     const double ux = dx / length, uy = dy / length, uz = dz / length;
     const double reach = fmax(step, fmin(length - trunc, max_ray));

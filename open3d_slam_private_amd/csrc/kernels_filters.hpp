@@ -133,24 +133,12 @@ k_ssn_children(const float* __restrict__ px, const int32_t* __restrict__ perm, c
     }
 }
 
-// Same rank rule as k_pca_finish: eigenvalues of C (fp64 Jacobi), rank = |lambda| > 3 eps_f32 |lambda|_max.
+// Rank of the scatter sums C: eigenvalues by fp64 Jacobi, the rank rule of k_pca_finish (pca_rank).
 __device__ __forceinline__ int ssn_rank(const float* C) {
     double M[9] = {C[0], C[1], C[2], C[1], C[3], C[4], C[2], C[4], C[5]}, V[9], lam[3];
     jacobi_eig_sym3(M, V, lam);
-    const double lmax = fabs(fmax(lam[0], fmax(lam[1], lam[2])));   // |largest eigenvalue|, as k_pca_finish
-    int rank = 0;
-    for (int a = 0; a < 3; ++a)
-        if (lmax > 0 && fabs(lam[a]) > lmax * 3.0 * 1.1920929e-07) ++rank;
-    return rank;
-}
-
-// utils.h computeDensity with the fp32 operation order of k_pca_finish
-__device__ __forceinline__ float ssn_density(int m, float mx) {
-    const float tq = (float)(4. / 3.), pi = (float)3.14159265358979323846;
-    const float c0 = tq * pi;
-    const float r3 = mx * sqrtf(mx);
-    const float volume = c0 * r3;
-    return volume > 0.f ? (float)m / volume : 0.f;
+    int o[3];
+    return pca_rank(lam, o);
 }
 
 // One thread per leaf (fuseRange): actual extent vs maxBoxDim, fp32 sequential mean / scatter, rank test when an
@@ -165,7 +153,6 @@ k_ssn_leaf(const float* __restrict__ px, const int32_t* __restrict__ perm, const
     const int b = leaf_begin[L], e = leaf_begin[L + 1];
     const int m = e - b;
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    float mean[3] = {0.f, 0.f, 0.f};
     int32_t min_idx = 0x7fffffff;
     for (int r = b; r < e; ++r) {
         const int32_t p = perm[r];
@@ -174,42 +161,19 @@ k_ssn_leaf(const float* __restrict__ px, const int32_t* __restrict__ perm, const
             const float v = px[3 * (size_t)p + a];
             lo[a] = fminf(lo[a], v);
             hi[a] = fmaxf(hi[a], v);
-            mean[a] = mean[a] + v;
         }
     }
     float dim = hi[0] - lo[0];
     for (int a = 1; a < 3; ++a) dim = fmaxf(dim, hi[a] - lo[a]);
     bool fit = !(dim > max_box_dim);
-    const float fm = (float)m;
-    for (int a = 0; a < 3; ++a) mean[a] = mean[a] / fm;
-    float C[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float mx = 0.f;
-    for (int r = b; r < e; ++r) {
-        const size_t p = (size_t)perm[r];
-        const float dx = px[3 * p] - mean[0], dy = px[3 * p + 1] - mean[1], dz = px[3 * p + 2] - mean[2];
-        float u;
-        u = dx * dx; C[0] = C[0] + u;
-        u = dx * dy; C[1] = C[1] + u;
-        u = dx * dz; C[2] = C[2] + u;
-        u = dy * dy; C[3] = C[3] + u;
-        u = dy * dz; C[4] = C[4] + u;
-        u = dz * dz; C[5] = C[5] + u;
-        float s = dx * dx;
-        float t = dy * dy;
-        float s2 = s + t;
-        s = dz * dz;
-        s2 = s2 + s;
-        mx = fmaxf(mx, s2);
-    }
-    if (fit && need_eig && ssn_rank(C) + 1 < 3) fit = false;
     PcaMoments rec;
-    for (int a = 0; a < 3; ++a) {
-        rec.mean[a] = mean[a];
-        rec.p[a] = mean[a];
-    }
-    for (int a = 0; a < 6; ++a) rec.C[a] = C[a];
-    rec.m = fm;
-    rec.max_d2 = mx;
+    pca_moments(m, [&](int r) {
+        const size_t p = (size_t)perm[b + r];
+        return make_float3(px[3 * p], px[3 * p + 1], px[3 * p + 2]);
+    }, rec.mean, rec.C, rec.max_d2);
+    if (fit && need_eig && ssn_rank(rec.C) + 1 < 3) fit = false;
+    for (int a = 0; a < 3; ++a) rec.p[a] = rec.mean[a];
+    rec.m = (float)m;
     rec.idx = (uint32_t)min_idx;
     rec.pad = fit ? 1u : 0u;
     leaf_mom[L] = rec;
@@ -237,7 +201,7 @@ k_ssn_scatter(const float* __restrict__ px, int n, int method, const uint32_t* _
         for (int a = 0; a < 3; ++a) rec.p[a] = px[3 * (size_t)i + a];
     for (int a = 0; a < 3; ++a) out_xyz[3 * (size_t)s + a] = rec.p[a];
     src_idx[s] = i;
-    if (densities) densities[s] = ssn_density((int)rec.m, rec.max_d2);
+    if (densities) densities[s] = pca_density((int)rec.m, rec.max_d2);
     rec.idx = s;
     out_mom[s] = rec;
 }

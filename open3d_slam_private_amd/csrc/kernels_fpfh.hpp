@@ -8,11 +8,6 @@ constexpr int kFpfhMaxNn = 128;   // largest max_nn: two neighbours per lane of 
 constexpr int kFpfhWaves = 4;     // query points per workgroup, one wave each
 constexpr int kFpfhCap = 1024;    // candidate keys per query point held in LDS (8 B each: 32 KB per workgroup)
 
-__device__ __forceinline__ void fpfh_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // (d2, original index) as one ascending key: d2 >= 0, so its bit pattern orders like its value
 __device__ __forceinline__ uint64_t fpfh_key(float d2, uint32_t idx) {
     return ((uint64_t)__float_as_uint(d2) << 32) | (uint64_t)idx;
@@ -31,40 +26,16 @@ __global__ void k_fpfh_check(const float* __restrict__ xyz, int64_t xs, const fl
 }
 
 // Calls f(target point, d2) for every target point inside the bin box of level l around p that lies within max_dist: the
-// box of pca_scan_box, its rows dealt to the 64 lanes of one wave (a lane walks its row alone, so f may not synchronise).
+// rows of level_box, dealt to the 64 lanes of one wave (a lane walks its row_run alone, so f may not synchronise).
 template <class F>
 __device__ __forceinline__ void fpfh_scan_box(const Grid& g, const float3 p, int l, int lane, F&& f) {
-    const float rb = g.rho_box[l];
-    const int lox = (int)fminf(fmaxf(bin_coord_f(p.x - rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-    const int loy = (int)fminf(fmaxf(bin_coord_f(p.y - rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-    const int loz = (int)fminf(fmaxf(bin_coord_f(p.z - rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-    const int hix = (int)fminf(fmaxf(bin_coord_f(p.x + rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-    const int hiy = (int)fminf(fmaxf(bin_coord_f(p.y + rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-    const int hiz = (int)fminf(fmaxf(bin_coord_f(p.z + rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-    const int ny = hiy - loy + 1, nz = hiz - loz + 1;
-    const int bx0 = lox >> kBrickLog2;
-    const int nbx = (hix >> kBrickLog2) - bx0 + 1;
-    const int nrow = nbx * ny;
-    const int64_t total = (int64_t)nrow * nz;
-    for (int64_t t = lane; t < total; t += 64) {
-        const int iz = (int)(t / nrow), rem = (int)(t - (int64_t)iz * nrow);
-        const int iy = rem / nbx, ix = rem - iy * nbx;
-        const int bx = bx0 + ix, cy = loy + iy, cz = loz + iz;
-        const int bid = brick_lookup(g, bx, cy >> kBrickLog2, cz >> kBrickLog2);
-        if (bid < 0) continue;
-        const int x0 = max(lox, bx << kBrickLog2) & (kBrickDim - 1);
-        const int x1 = min(hix, (bx << kBrickLog2) + kBrickDim - 1) & (kBrickDim - 1);
-        const uint32_t* cs = g.cell_start + (size_t)bid * kBrickCells +
-                             (((cz & (kBrickDim - 1)) << (2 * kBrickLog2)) | ((cy & (kBrickDim - 1)) << kBrickLog2));
-        const uint32_t s = cs[x0], e = cs[x1 + 1];
+    const LevelBox b = level_box(g, p, l);
+    for (int64_t t = lane; t < b.total; t += 64) {
+        uint32_t s, e;
+        row_run(g, b, t, s, e);
         for (uint32_t j = s; j < e; ++j) {
             const float4 tpt = g.pts[j];
-            const float dx = p.x - tpt.x, dy = p.y - tpt.y, dz = p.z - tpt.z;
-            float a = dx * dx;
-            float b = dy * dy;
-            float d2 = a + b;
-            a = dz * dz;
-            d2 = d2 + a;
+            const float d2 = nc5_d2(p, tpt);
             if (d2 <= g.max_d2) f(tpt, d2);
         }
     }
@@ -155,12 +126,12 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
     bool overflow = false;
     for (int l = min(start_level, g.n_levels - 1); l < g.n_levels; ++l) {
         if (lane == 0) l_cnt[wv] = 0;
-        fpfh_wave_sync();
+        group_sync();
         fpfh_scan_box(g, p, l, lane, [&](const float4& tpt, float d2) {
             const uint32_t slot = atomicAdd(&l_cnt[wv], 1u);
             if (slot < (uint32_t)kFpfhCap) key[slot] = fpfh_key(d2, __float_as_uint(tpt.w));
         });
-        fpfh_wave_sync();
+        group_sync();
         uint32_t cnt = l_cnt[wv];
         if (cnt > (uint32_t)kFpfhCap) {
             overflow = true;
@@ -184,7 +155,7 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
                 }
             }
             if (lane == 0) l_cnt[wv] = 0;
-            fpfh_wave_sync();
+            group_sync();
             fpfh_scan_box(g, p, l, lane, [&](const float4& tpt, float d2) {
                 const uint64_t kk = fpfh_key(d2, __float_as_uint(tpt.w));
                 if (kk <= bound) {
@@ -192,14 +163,14 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
                     if (slot < (uint32_t)kFpfhCap) key[slot] = kk;
                 }
             });
-            fpfh_wave_sync();
+            group_sync();
             cnt = min(l_cnt[wv], (uint32_t)kFpfhCap);
         }
         // bitonic sort of the list, padded to a power of two
         uint32_t P = 1;
         while (P < cnt) P <<= 1;
         for (uint32_t t = cnt + (uint32_t)lane; t < P; t += 64) key[t] = ~0ull;
-        fpfh_wave_sync();
+        group_sync();
         for (uint32_t k2 = 2; k2 <= P; k2 <<= 1) {
             for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
                 for (uint32_t t = (uint32_t)lane; t < (P >> 1); t += 64) {
@@ -210,7 +181,7 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
                         key[i1] = a;
                     }
                 }
-                fpfh_wave_sync();
+                group_sync();
             }
         }
         m_all = (int)min(cnt, (uint32_t)max_nn);
@@ -231,7 +202,7 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
     }
     const int m = m_all - (self < m_all ? 1 : 0);
     if (lane < kFpfhDim) l_hist[wv][lane] = 0;
-    fpfh_wave_sync();
+    group_sync();
     const float* nq = nrm + (size_t)my_idx * ns;
     const double pi[3] = {(double)p.x, (double)p.y, (double)p.z};
     const double ni[3] = {(double)nq[0], (double)nq[1], (double)nq[2]};
@@ -252,7 +223,7 @@ k_fpfh_spfh(Grid g, const float* __restrict__ raw_xyz, int64_t xs, const float* 
         }
         ids[(size_t)my_idx * max_nn + r] = id;
     }
-    fpfh_wave_sync();
+    group_sync();
     if (lane < kFpfhDim) counts[(size_t)my_idx * kFpfhDim + lane] = l_hist[wv][lane];
     if (lane == 0) {
         m_out[my_idx] = m;
@@ -284,12 +255,7 @@ k_fpfh_accum(const float* __restrict__ xyz, int64_t xs, int64_t n, int max_nn, c
         if (r < m) {
             const int32_t j = ids[(size_t)i * max_nn + r];
             const float* sp = xyz + (size_t)j * xs;
-            const double dx = (double)sp[0] - px, dy = (double)sp[1] - py, dz = (double)sp[2] - pz;
-            double s = dx * dx;
-            double t = dy * dy;
-            s = s + t;
-            t = dz * dz;
-            s = s + t;
+            const double s = sum_sq3((double)sp[0] - px, (double)sp[1] - py, (double)sp[2] - pz);
             const int mj = m_arr[j];
             nid[h] = j;
             if (mj > 0) {

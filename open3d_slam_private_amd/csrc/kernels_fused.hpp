@@ -208,8 +208,7 @@ k_iter_fused(const float4* __restrict__ src, const float4* __restrict__ src_nrm,
             if (hint) hint[q] = (uint8_t)(lvl + 1);
             if (w_out) w_out[q] = (cls == 2) ? 0.f : w;   // band points: provisional, patched by the update kernel
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // E written by lane 0, read by the whole group (same wave)
-        __builtin_amdgcn_wave_barrier();
+        group_sync();   // E written by lane 0, read by the whole group (same wave)
         // certainly-kept contributions: lane `sub` owns components sub*CP .. sub*CP+CP-1
 #pragma unroll
         for (int j = 0; j < CP; ++j) {
@@ -379,6 +378,28 @@ __device__ __forceinline__ double coh_component(const float* E, int rows, int co
     return acc;
 }
 
+// Does the neighbour of the last search (tq) provably remain the nearest one of p?  c: the anchor (where that search
+// ran) with, in w, the squared bound within which it saw no other point; ru: its runner-up (w = 1: valid, and the bound
+// excludes it).  d2 is the NC5 distance of the pair, the value a full search would compute.
+__device__ __forceinline__ bool shortcut_holds(const Grid& g, const float3& p, const float4& c, const float4& tq, const float4& ru,
+                                               float& d2) {
+    d2 = nc5_d2(p, tq);
+    const float ex = p.x - c.x, ey = p.y - c.y, ez = p.z - c.z;
+    const float delta = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez);
+    const float lhs = (__builtin_amdgcn_sqrtf(d2) + delta) * 1.00001f + 1e-30f;
+    const float rhs = __builtin_amdgcn_sqrtf(c.w) * 0.99999f;
+    bool pass = d2 <= g.max_d2 && lhs < rhs;
+    if (ru.w == 1.f) {
+        // Two-candidate form: the bound c.w covers every point EXCEPT the winner and the runner-up of the last search, so
+        // the runner-up is tested by itself -- with the comparison the full search would make (fp32 d2, strict: an exact
+        // tie is decided by the original indices, which only the full search knows).  Reading points that sit between
+        // two nearly equidistant reference points (8 % of C3, 25 % of C4 with the one-candidate bound) keep their match.
+        const float r2 = nc5_d2(p, ru);
+        pass = pass && d2 < r2;
+    }
+    return pass;
+}
+
 __global__ void __launch_bounds__(256)
 k_coh_check(const float4* __restrict__ src, const float4* __restrict__ src_nrm, int64_t n, IterState* __restrict__ it,
             Grid g, const float4* __restrict__ tgt_nrm, FilterCfg f, int* __restrict__ pos_io, float* __restrict__ d2_out,
@@ -417,30 +438,8 @@ k_coh_check(const float4* __restrict__ src, const float4* __restrict__ src_nrm, 
     bool pass = false;
     float md2 = INFINITY;
     if (q < n && c.w > 0.f && pprev >= 0 && nn.w == 1.f) {   // nn.w: matched point + normal of `pprev` are cached
-        const float dx = p.x - tq.x, dy = p.y - tq.y, dz = p.z - tq.z;
-        float a = dx * dx;
-        float b = dy * dy;
-        float d2 = a + b;
-        a = dz * dz;
-        d2 = d2 + a;                                   // NC5: the value the full search would compute for this pair
-        const float ex = p.x - c.x, ey = p.y - c.y, ez = p.z - c.z;
-        const float delta = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez);
-        const float lhs = (__builtin_amdgcn_sqrtf(d2) + delta) * 1.00001f + 1e-30f;
-        const float rhs = __builtin_amdgcn_sqrtf(c.w) * 0.99999f;
-        pass = d2 <= g.max_d2 && lhs < rhs;
-        if (ru.w == 1.f) {
-            // Two-candidate form: the bound c.w covers every point EXCEPT the winner and the runner-up of the last search, so
-            // the runner-up is tested by itself -- with the comparison the full search would make (fp32 d2, strict: an exact
-            // tie is decided by the original indices, which only the full search knows).  Reading points that sit between
-            // two nearly equidistant reference points (8 % of C3, 25 % of C4 with the one-candidate bound) keep their match.
-            const float fx = p.x - ru.x, fy = p.y - ru.y, fz = p.z - ru.z;
-            float a2 = fx * fx;
-            float b2 = fy * fy;
-            float r2 = a2 + b2;
-            a2 = fz * fz;
-            r2 = r2 + a2;
-            pass = pass && d2 < r2;
-        }
+        float d2;
+        pass = shortcut_holds(g, p, c, tq, ru, d2);
         md2 = d2;
     }
     const bool need = q < n && !pass;

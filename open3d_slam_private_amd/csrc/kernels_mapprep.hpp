@@ -17,12 +17,7 @@ __device__ __forceinline__ bool crop_inside(const CropCfg& c, double x, double y
         const double d = sqrt(a + b);
         return z >= c.zmin && z <= c.zmax && d <= c.rmax;
     }
-    double a = dx * dx;
-    double b = dy * dy;
-    double s2 = a + b;
-    a = dz * dz;
-    s2 = s2 + a;
-    const double d = sqrt(s2);
+    const double d = sqrt(sum_sq3(dx, dy, dz));
     if (c.type == REG_CROP_MAX_RADIUS) return d <= c.rmax;
     if (c.type == REG_CROP_MIN_RADIUS) return d >= c.rmin;
     return d <= c.rmax && d >= c.rmin;
@@ -158,12 +153,7 @@ __global__ void k_carve_rays(const double* __restrict__ scan, int64_t n_scan, do
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (i >= n_scan) return;
     const double dx = scan[3 * i] - sx, dy = scan[3 * i + 1] - sy, dz = scan[3 * i + 2] - sz;
-    double a = dx * dx;
-    double b = dy * dy;
-    double s2 = a + b;
-    a = dz * dz;
-    s2 = s2 + a;
-    const double length = sqrt(s2);
+    const double length = sqrt(sum_sq3(dx, dy, dz));
     if (!(length > 0.0) || !(length < INFINITY)) return;
     const double ux = dx / length, uy = dy / length, uz = dz / length;
     const double reach = fmax(step, fmin(length - trunc, max_ray));

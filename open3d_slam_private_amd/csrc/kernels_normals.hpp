@@ -11,64 +11,9 @@
 // LDS list, then extracts the k smallest (d2, original index) one by one; the k-th distance <= rho^2 proves the
 // list held every closer point (same exactness argument as the 1-NN search).
 // =================================================================================================
-constexpr int kPcaGroup = 16;
 // candidates per point and level held in LDS (8 B each): a template parameter of the kernel -- 128 (25 KB per workgroup,
 // 6 workgroups per CU) is enough for small k, 256 (41 KB, 3 per CU) keeps the rescans rare for k up to 32
 constexpr int kPcaMaxK = 32;
-
-// Calls f(j, target point j, d2) on the lanes of one 16-lane group for every target point inside the bin box of
-// level l around p that lies within max_dist.
-template <class F>
-__device__ __forceinline__ void pca_scan_box(const Grid& g, const float3 p, int l, int sub, int gbase, F&& f) {
-    const float rb = g.rho_box[l];
-    const int lox = (int)fminf(fmaxf(bin_coord_f(p.x - rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-    const int loy = (int)fminf(fmaxf(bin_coord_f(p.y - rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-    const int loz = (int)fminf(fmaxf(bin_coord_f(p.z - rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-    const int hix = (int)fminf(fmaxf(bin_coord_f(p.x + rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-    const int hiy = (int)fminf(fmaxf(bin_coord_f(p.y + rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-    const int hiz = (int)fminf(fmaxf(bin_coord_f(p.z + rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-    const int ny = hiy - loy + 1, nz = hiz - loz + 1;
-    const int bx0 = lox >> kBrickLog2;
-    const int nbx = (hix >> kBrickLog2) - bx0 + 1;
-    const int nrow = nbx * ny;
-    const int64_t total = (int64_t)nrow * nz;
-    for (int64_t base = 0; base < total; base += kPcaGroup) {
-        uint32_t s = 0, e = 0;
-        const int64_t t = base + sub;
-        if (t < total) {
-            const int iz = (int)(t / nrow), rem = (int)(t - (int64_t)iz * nrow);
-            const int iy = rem / nbx, ix = rem - iy * nbx;
-            const int bx = bx0 + ix, cy = loy + iy, cz = loz + iz;
-            const int bid = brick_lookup(g, bx, cy >> kBrickLog2, cz >> kBrickLog2);
-            if (bid >= 0) {
-                const int x0 = max(lox, bx << kBrickLog2) & (kBrickDim - 1);
-                const int x1 = min(hix, (bx << kBrickLog2) + kBrickDim - 1) & (kBrickDim - 1);
-                const uint32_t* cs = g.cell_start + (size_t)bid * kBrickCells +
-                                     (((cz & (kBrickDim - 1)) << (2 * kBrickLog2)) |
-                                      ((cy & (kBrickDim - 1)) << kBrickLog2));
-                s = cs[x0];
-                e = cs[x1 + 1];
-            }
-        }
-        unsigned mask = (unsigned)((__ballot(e > s) >> gbase) & 0xffffull);
-        while (mask) {
-            const int it = __ffs((int)mask) - 1;
-            mask &= mask - 1;
-            const uint32_t si = (uint32_t)__shfl((int)s, gbase + it);
-            const uint32_t ei = (uint32_t)__shfl((int)e, gbase + it);
-            for (uint32_t j = si + (uint32_t)sub; j < ei; j += kPcaGroup) {
-                const float4 tpt = g.pts[j];
-                const float dx = p.x - tpt.x, dy = p.y - tpt.y, dz = p.z - tpt.z;
-                float a = dx * dx;
-                float b = dy * dy;
-                float d2 = a + b;
-                a = dz * dz;
-                d2 = d2 + a;
-                if (d2 <= g.max_d2) f(j, tpt, d2);
-            }
-        }
-    }
-}
 
 // Per-point result of the neighbourhood kernel, consumed by k_pca_finish (one thread per point: the eigen-decomposition
 // ran on ONE lane of a 16-lane group before -- 6 % lane utilisation for the most expensive arithmetic of the kernel).
@@ -104,8 +49,7 @@ k_knn_pca(Grid g, const float* __restrict__ raw_xyz, int64_t raw_stride, int64_t
     bool overflow = false;
     for (int l = min(start_level, g.n_levels - 1); l < g.n_levels; ++l) {
         if (sub == 0) l_cnt[grp] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        group_sync();
         pca_scan_box(g, p, l, sub, gbase, [&](uint32_t, const float4& tpt, float d2) {
             const uint32_t slot = atomicAdd(&l_cnt[grp], 1u);
             if (slot < (uint32_t)kPcaCap) {
@@ -113,8 +57,7 @@ k_knn_pca(Grid g, const float* __restrict__ raw_xyz, int64_t raw_stride, int64_t
                 l_idx[grp][slot] = __float_as_uint(tpt.w);
             }
         });
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        group_sync();
         const uint32_t cnt = l_cnt[grp];
         const bool listed = cnt <= (uint32_t)kPcaCap;
         if (!listed) overflow = true;   // too many candidates for LDS: every extraction round rescans the box
@@ -163,8 +106,7 @@ k_knn_pca(Grid g, const float* __restrict__ raw_xyz, int64_t raw_stride, int64_t
         const float r2 = g.rho[l] * g.rho[l];
         if ((m == k && last_d2 <= r2) || l == g.n_levels - 1) break;
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    group_sync();
     // neighbour coordinates (input frame == table frame: the workspace table is not centred) and ids, in parallel
     for (int r = sub; r < k; r += kPcaGroup) {
         if (r < m) {
@@ -178,50 +120,15 @@ k_knn_pca(Grid g, const float* __restrict__ raw_xyz, int64_t raw_stride, int64_t
             ids_out[(size_t)my_idx * k + r] = -1;
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    group_sync();
     if (sub != 0) return;
     if (overflow && n_overflow) atomicAdd(n_overflow, 1u);   // statistics only: the result is still exact
-    // PCA: fp32 sequential sums in neighbour order (numeric contract), eigen-decomposition in fp64
-    float mean[3] = {0.f, 0.f, 0.f};
-    for (int r = 0; r < m; ++r) {
-        mean[0] = mean[0] + nb_xyz[grp][r][0];
-        mean[1] = mean[1] + nb_xyz[grp][r][1];
-        mean[2] = mean[2] + nb_xyz[grp][r][2];
-    }
-    const float fm = (float)m;
-    if (m > 0) {
-        mean[0] = mean[0] / fm;
-        mean[1] = mean[1] / fm;
-        mean[2] = mean[2] / fm;
-    }
-    float C[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int r = 0; r < m; ++r) {
-        const float dx = nb_xyz[grp][r][0] - mean[0], dy = nb_xyz[grp][r][1] - mean[1], dz = nb_xyz[grp][r][2] - mean[2];
-        float u;
-        u = dx * dx; C[0] = C[0] + u;
-        u = dx * dy; C[1] = C[1] + u;
-        u = dx * dz; C[2] = C[2] + u;
-        u = dy * dy; C[3] = C[3] + u;
-        u = dy * dz; C[4] = C[4] + u;
-        u = dz * dz; C[5] = C[5] + u;
-    }
-    float mx = 0.f;
-    for (int r = 0; r < m; ++r) {
-        const float dx = nb_xyz[grp][r][0] - mean[0], dy = nb_xyz[grp][r][1] - mean[1], dz = nb_xyz[grp][r][2] - mean[2];
-        float u = dx * dx;
-        float v2 = dy * dy;
-        float s2 = u + v2;
-        u = dz * dz;
-        s2 = s2 + u;
-        mx = fmaxf(mx, s2);
-    }
+    // PCA: fp32 sequential sums in neighbour order (numeric contract); the eigen-decomposition is k_pca_finish's
     PcaMoments rec;
-    rec.mean[0] = mean[0]; rec.mean[1] = mean[1]; rec.mean[2] = mean[2];
-    for (int a = 0; a < 6; ++a) rec.C[a] = C[a];
-    rec.m = fm;
+    pca_moments(m, [&](int r) { return make_float3(nb_xyz[grp][r][0], nb_xyz[grp][r][1], nb_xyz[grp][r][2]); }, rec.mean, rec.C,
+                rec.max_d2);
+    rec.m = (float)m;
     rec.p[0] = p.x; rec.p[1] = p.y; rec.p[2] = p.z;
-    rec.max_d2 = mx;
     rec.idx = my_idx;
     rec.pad = 0;
     mom[q] = rec;
@@ -242,14 +149,9 @@ k_pca_finish(const PcaMoments* __restrict__ mom, int64_t n, float vx, float vy, 
     const uint32_t my_idx = rec.idx;
     double M[9] = {C[0], C[1], C[2], C[1], C[3], C[4], C[2], C[4], C[5]}, V[9], lam[3];
     jacobi_eig_sym3(M, V, lam);
-    int o0 = 0, o1 = 1, o2 = 2;
-    if (lam[o1] < lam[o0]) { const int t = o0; o0 = o1; o1 = t; }
-    if (lam[o2] < lam[o0]) { const int t = o0; o0 = o2; o2 = t; }
-    if (lam[o2] < lam[o1]) { const int t = o1; o1 = o2; o2 = t; }
-    const double lmax = fabs(lam[o2]);
-    int rank = 0;
-    for (int a = 0; a < 3; ++a)
-        if (lmax > 0 && fabs(lam[a]) > lmax * 3.0 * 1.1920929e-07) ++rank;
+    int oo[3];
+    const int rank = pca_rank(lam, oo);
+    const int o0 = oo[0], o1 = oo[1], o2 = oo[2];
     float nv[3] = {0.f, 0.f, 0.f};
     if (m >= 3 && rank + 1 >= 3) {
         const double v[3] = {V[0 * 3 + o0], V[1 * 3 + o0], V[2 * 3 + o0]};
@@ -279,39 +181,18 @@ k_pca_finish(const PcaMoments* __restrict__ mom, int64_t n, float vx, float vy, 
         eigvals[3 * oi + 2] = (float)lam[o2];
     }
     if (eigvecs) {   // "eigVectors": eigenvector k (ascending eigenvalue), components contiguous; zero when degenerate
-        const int oo[3] = {o0, o1, o2};
         for (int kk = 0; kk < 3; ++kk)
             for (int a = 0; a < 3; ++a) eigvecs[9 * oi + 3 * kk + a] = degenerate ? 0.f : (float)V[a * 3 + oo[kk]];
     }
-    if (densities) {   // utils.h:106-128: m / (4/3 pi r^3), r^2 = largest squared distance of a neighbour from the mean
-        float dens = 0.f;
-        if (!degenerate) {
-            const float mx = rec.max_d2;
-            const float tq = (float)(4. / 3.), pi = (float)3.14159265358979323846;
-            const float c0 = tq * pi;
-            const float r3 = mx * sqrtf(mx);
-            const float volume = c0 * r3;
-            dens = volume > 0.f ? (float)m / volume : 0.f;
-        }
-        densities[oi] = dens;
-    }
+    if (densities) densities[oi] = degenerate ? 0.f : pca_density(m, rec.max_d2);
     if (mean_dists) {   // SurfaceNormal.cpp:243-252
         float md = 18446744073709551615.0f;   // (float)std::numeric_limits<std::size_t>::max()
-        if (!degenerate) {
-            const float dx = p.x - mean[0], dy = p.y - mean[1], dz = p.z - mean[2];
-            float u = dx * dx;
-            float v2 = dy * dy;
-            float s2 = u + v2;
-            u = dz * dz;
-            s2 = s2 + u;
-            md = sqrtf(s2);
-        }
+        if (!degenerate) md = sqrtf(sum_sq3(p.x - mean[0], p.y - mean[1], p.z - mean[2]));
         mean_dists[oi] = md;
     }
     if (covs) {
         double Cn[9];
         if (regularise) {
-            const int oo[3] = {o0, o1, o2};
             const double w[3] = {1e-3, 1.0, 1.0};
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {

@@ -50,9 +50,9 @@ struct PmState {
 };
 
 // Exact k nearest reference points of every transformed reading point, within max_dist.  16 lanes per point, level
-// by level as k_knn_pca: the level's bin box is gathered into an LDS list, the knn smallest (d2, original index) are
-// extracted one by one, and the search ends once the knn-th distance is within the level's radius (every closer point
-// was in the box).  d2 is the same fp32 expression as every other search of the table.
+// by level as k_knn_pca: the level's bin box is gathered into an LDS list (pca_scan_box, kernels_neighbours.hpp), the knn
+// smallest (d2, original index) are extracted one by one, and the search ends once the knn-th distance is within the
+// level's radius (every closer point was in the box).  d2 is the NC5 value of every other search of the table.
 template <int K>
 __global__ void __launch_bounds__(256)
 k_match_knn(Grid g, const float4* __restrict__ src, int64_t n, int knn, const IterState* __restrict__ it,
@@ -76,8 +76,7 @@ k_match_knn(Grid g, const float4* __restrict__ src, int64_t n, int knn, const It
     int m = 0;
     for (int l = 0; l < g.n_levels; ++l) {
         if (sub == 0) l_cnt[grp] = 0;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        group_sync();
         pca_scan_box(g, p, l, sub, gbase, [&](uint32_t j, const float4& tpt, float d2) {
             const uint32_t slot = atomicAdd(&l_cnt[grp], 1u);
             if (slot < (uint32_t)kPmCap) {
@@ -86,8 +85,7 @@ k_match_knn(Grid g, const float4* __restrict__ src, int64_t n, int knn, const It
                 l_pos[grp][slot] = j;
             }
         });
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        group_sync();
         const uint32_t cnt = l_cnt[grp];
         const bool listed = cnt <= (uint32_t)kPmCap;
         float last_d2 = -1.f;
@@ -133,8 +131,7 @@ k_match_knn(Grid g, const float4* __restrict__ src, int64_t n, int knn, const It
         const float r2 = g.rho[l] * g.rho[l];
         if ((m == kk && last_d2 <= r2) || l == g.n_levels - 1) break;
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    group_sync();
     for (int r = sub; r < kk; r += kPcaGroup) {
         const size_t o = (size_t)q * (size_t)kk + (size_t)r;
         kpos[o] = r < m ? nb_pos[grp][r] : -1;

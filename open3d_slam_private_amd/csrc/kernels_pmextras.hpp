@@ -233,22 +233,6 @@ __device__ __noinline__ bool pmx_bound_check(const float* Tn, const PmExtraCfg& 
 
 // ---- post-loop reductions ------------------------------------------------------------------------------------------
 
-// Workgroup sum of NV doubles per lane -> dst[NV] (256 threads = 4 waves; the wave order is fixed)
-template <int NV>
-__device__ __forceinline__ void pmx_block_store(double (&v)[NV], double* __restrict__ dst) {
-    __shared__ double red[4][NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < NV) dst[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
 // Fixed-order sum of n_rows rows of NV doubles: P parts of the rows side by side, the parts added in order.
 // One workgroup of 256 lanes.  Returns the total of component threadIdx.x in tot[] (LDS) after a barrier.
 template <int NV>
@@ -307,7 +291,7 @@ k_pmx_pair_means(const float4* __restrict__ src, int64_t n, int knn, const IterS
         v[5] += (double)q.z;
         v[6] += 1.0;
     }
-    pmx_block_store<kPmxRow>(v, rows + (size_t)blockIdx.x * kPmxRow);
+    block_sum_store<kPmxRow>(v, rows + (size_t)blockIdx.x * kPmxRow);
 }
 
 // The per-pair terms of PointToPlaneWithCovErrorMinimizer::estimateCovariance (PointToPlaneWithCov.cpp:110-146) in fp32,
@@ -457,7 +441,7 @@ k_pmx_cov_terms(const float4* __restrict__ src, int64_t n, int knn, const IterSt
                 ++k;
             }
     }
-    pmx_block_store<kPmxCovSums>(acc, rows + (size_t)blockIdx.x * kPmxCovSums);
+    block_sum_store<kPmxCovSums>(acc, rows + (size_t)blockIdx.x * kPmxCovSums);
 }
 
 __global__ void __launch_bounds__(256)
@@ -501,5 +485,5 @@ k_pmx_stats(const float* __restrict__ kw, int64_t n, int knn, double* __restrict
         v[2] += (double)(knn - used);
         if (used == 0) v[3] += 1.0;
     }
-    pmx_block_store<kPmxRow>(v, rows + (size_t)blockIdx.x * kPmxRow);
+    block_sum_store<kPmxRow>(v, rows + (size_t)blockIdx.x * kPmxRow);
 }

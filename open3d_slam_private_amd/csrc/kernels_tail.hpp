@@ -688,26 +688,8 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
             bool pass = false;
             const float attr_ok = kGicp ? st_rows[4 * kTailSlots + sl].w : nn.w;   // matched point + attribute rows are cached
             if (valid[u] && c.w > 0.f && pprev >= 0 && attr_ok == 1.f) {
-                const float dx = p[u].x - tq.x, dy = p[u].y - tq.y, dz = p[u].z - tq.z;
-                float a = dx * dx;
-                float b2 = dy * dy;
-                float d2 = a + b2;
-                a = dz * dz;
-                d2 = d2 + a;                                   // NC5: the value the full search would compute for this pair
-                const float ex = p[u].x - c.x, ey = p[u].y - c.y, ez = p[u].z - c.z;
-                const float delta = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez);
-                const float lhs = (__builtin_amdgcn_sqrtf(d2) + delta) * 1.00001f + 1e-30f;
-                const float rhs = __builtin_amdgcn_sqrtf(c.w) * 0.99999f;
-                pass = d2 <= g.max_d2 && lhs < rhs;
-                if (ru.w == 1.f) {   // two-candidate form (see k_coh_check)
-                    const float fx = p[u].x - ru.x, fy = p[u].y - ru.y, fz = p[u].z - ru.z;
-                    float a2 = fx * fx;
-                    float b3 = fy * fy;
-                    float r2 = a2 + b3;
-                    a2 = fz * fz;
-                    r2 = r2 + a2;
-                    pass = pass && d2 < r2;
-                }
+                float d2;
+                pass = shortcut_holds(g, p[u], c, tq, ru, d2);
                 if (pass) d2s[sl] = d2;
             }
             if (valid[u] && !pass) {
@@ -1229,8 +1211,7 @@ k_tail(const float4* __restrict__ src, const float4* __restrict__ src_nrm /* GIC
         if (sit->stall == 0) sit->band_count = 0;
     }
     if (lane < kSums) reinterpret_cast<HostMirror*>(mir_w)->sums[lane] = sit->sums[lane];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
+    group_sync();
     for (int w2 = lane; w2 < kStateWords; w2 += 64) reinterpret_cast<uint32_t*>(it_g)[w2] = s_state[w2];
     constexpr int kMirrorWords = (int)(offsetof(HostMirror, seq) / 4);
     uint32_t* hw = reinterpret_cast<uint32_t*>(host);

@@ -787,8 +787,7 @@ __device__ __forceinline__ void reduce_update_body(const double* __restrict__ pa
         m->stamps[7] = ((sx2 - sx1) << 32) | (sx3 - sx2);
     }
     if (lane < kSums) reinterpret_cast<HostMirror*>(mir_w)->sums[lane] = tot[lane];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");   // LDS writes of lane 0 visible to the wave
-    __builtin_amdgcn_wave_barrier();
+    group_sync();   // LDS writes of lane 0 visible to the wave
     // write the modified state back (coalesced); the next kernel of the stream reads it from global memory
     for (int w = lane; w < kStateWords; w += 64) reinterpret_cast<uint32_t*>(it)[w] = s_state[w];
     if (s_skip_mirror) return;   // R8x analysis pending: the finish pass reports

@@ -22,22 +22,11 @@ __device__ __forceinline__ float3 xicp_to_data_frame_vec(const float* Trd, const
     return r;
 }
 
+// Workgroup sum of NV doubles per lane, added to dst[NV] (atomics: dst is shared by the workgroups)
 template <int NV>
 __device__ __forceinline__ void xicp_block_add(double* v, double* dst) {
-    __shared__ double red[4][NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const double t = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        if (t != 0.0) unsafeAtomicAdd(&dst[threadIdx.x], t);
-    }
+    const double t = block_sum<NV>(v);
+    if (threadIdx.x < NV && t != 0.0) unsafeAtomicAdd(&dst[threadIdx.x], t);
 }
 
 __global__ void __launch_bounds__(256)
@@ -100,11 +89,7 @@ k_xicp_detect(const float4* __restrict__ src, int64_t n, const IterState* __rest
         u = ps.y * nn.z; q = ps.z * nn.y; cr[0] = u - q;
         u = ps.z * nn.x; q = ps.x * nn.z; cr[1] = u - q;
         u = ps.x * nn.y; q = ps.y * nn.x; cr[2] = u - q;
-        float a = cr[0] * cr[0], b2 = cr[1] * cr[1];
-        float s2 = a + b2;
-        a = cr[2] * cr[2];
-        s2 = s2 + a;
-        const float nrm = sqrtf(s2);
+        const float nrm = sqrtf(sum_sq3(cr[0], cr[1], cr[2]));
         if (!(nrm < 1.0f)) {
             cr[0] = cr[0] / nrm;
             cr[1] = cr[1] / nrm;

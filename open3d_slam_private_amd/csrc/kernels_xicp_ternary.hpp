@@ -46,23 +46,6 @@ struct XtState {
     double psums[kXtPart];
 };
 
-// Workgroup sum of NV doubles per lane (256 threads = 4 waves, fixed order) -> dst[NV] (global or LDS)
-template <int NV>
-__device__ __forceinline__ void xt_block_sum(double (&v)[NV], double* dst) {
-    __shared__ double red[4][NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) red[wave][k] = v[k];
-    __syncthreads();
-    if (threadIdx.x < NV) dst[threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-    __syncthreads();
-}
-
 // Eigenvectors of one 3x3 block (o = 0: rotation, 3: translation) of the system: upd_xicp_stage_a, which also keeps the
 // optimisation-frame vectors (the fp32 rounding of the decomposition, before the rotation into the data frame)
 __device__ __noinline__ void xt_stage_a(const double* tot, const float* Trd, float* dst_data, float* dst_opt, int o) {
@@ -101,7 +84,7 @@ k_xt_center(const float4* __restrict__ src, int64_t n, const IterState* __restri
         v[2] += (double)ps.z;
         v[3] += 1.0;
     }
-    xt_block_sum<4>(v, rows + kXtRowsCenter + (size_t)blockIdx.x * 4);
+    block_sum_store<4>(v, rows + kXtRowsCenter + (size_t)blockIdx.x * 4);
 }
 
 // Both alignment vectors of one pair against the six eigenvectors: ar[k] rotation, at[k] translation (k_xicp_detect)
@@ -119,11 +102,7 @@ __device__ __forceinline__ void xt_alignments(const XtFrame& f, const float3 p, 
     u = ps.y * nn.z; q = ps.z * nn.y; cr[0] = u - q;
     u = ps.z * nn.x; q = ps.x * nn.z; cr[1] = u - q;
     u = ps.x * nn.y; q = ps.y * nn.x; cr[2] = u - q;
-    float a = cr[0] * cr[0], b2 = cr[1] * cr[1];
-    float s2 = a + b2;
-    a = cr[2] * cr[2];
-    s2 = s2 + a;
-    const float nrm = sqrtf(s2);
+    const float nrm = sqrtf(sum_sq3(cr[0], cr[1], cr[2]));
     if (!(nrm < 1.0f)) {
         cr[0] = cr[0] / nrm;
         cr[1] = cr[1] / nrm;
@@ -151,7 +130,8 @@ __device__ __forceinline__ void xt_load_frame(const XtState* __restrict__ xt, co
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = rows[kXtRowsCenter + (size_t)threadIdx.x * 4 + k];
     }
-    xt_block_sum<4>(v, cen);
+    block_sum_store<4>(v, cen);
+    __syncthreads();
 #pragma unroll
     for (int k = 0; k < 12; ++k) f.Trd[k] = xt->Trd[k];
 #pragma unroll
@@ -197,7 +177,7 @@ k_xt_detect(const float4* __restrict__ src, int64_t n, const IterState* __restri
             if (at[k] > cos_strong) { v[9 + k] += (double)at[k]; v[21 + k] += 1.0; }
         }
     }
-    xt_block_sum<kXtDet>(v, rows + kXtRowsDet + (size_t)blockIdx.x * kXtDet);
+    block_sum_store<kXtDet>(v, rows + kXtRowsDet + (size_t)blockIdx.x * kXtDet);
 }
 
 // One workgroup: the 24 totals in a fixed order, then the decision on one lane
@@ -308,7 +288,7 @@ k_xt_partial(const float4* __restrict__ src, int64_t n, const IterState* __restr
                 for (int c = 0; c < 9; ++c) v[9 * k + c] += (double)pr[9 * (k / 3) + c];
             }
     }
-    xt_block_sum<kXtPart>(v, rows + kXtRowsPart + (size_t)blockIdx.x * kXtPart);
+    block_sum_store<kXtPart>(v, rows + kXtRowsPart + (size_t)blockIdx.x * kXtPart);
 }
 
 // Finish of the analysis on the lane of k_pm_update that solves: constraint values of the partial directions, flags and

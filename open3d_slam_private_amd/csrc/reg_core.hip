@@ -45,6 +45,7 @@ using namespace o3dreg;
 #include "kernels_xicp.hpp"
 #include "kernels_update.hpp"
 #include "kernels_tail.hpp"
+#include "kernels_neighbours.hpp"
 #include "kernels_normals.hpp"
 #include "kernels_pmextras.hpp"
 #include "kernels_xicp_ternary.hpp"

@@ -87,6 +87,27 @@ __device__ __forceinline__ float3 xf_point(const Xf& T, float x, float y, float 
     a = T.m[8] * x; b = T.m[9] * y; s = a + b; a = T.m[10] * z; s = s + a; r.z = s + T.m[11];
     return r;
 }
+// (x^2 + y^2) + z^2, one rounding per operation, in this order (fp32 and fp64).
+__device__ __forceinline__ float sum_sq3(float x, float y, float z) {
+    float a = x * x;
+    float b = y * y;
+    float s = a + b;
+    a = z * z;
+    return s + a;
+}
+__device__ __forceinline__ double sum_sq3(double x, double y, double z) {
+    double a = x * x;
+    double b = y * y;
+    double s = a + b;
+    a = z * z;
+    return s + a;
+}
+// NC5: the squared distance of a query p to a reference point t.  Every search of the table, every shortcut test and
+// every k-NN kernel takes the fp32 value of a pair from here, so that all of them agree on it bit for bit.
+__device__ __forceinline__ float nc5_d2(const float3& p, const float4& t) {
+    return sum_sq3(p.x - t.x, p.y - t.y, p.z - t.z);
+}
+
 __device__ __forceinline__ float3 xf_rot(const Xf& T, float x, float y, float z) {
     float3 r;
     float a, b, s;
@@ -142,6 +163,30 @@ struct Best {
     float third;   // smallest d2 among the scanned points that are neither the winner nor the runner-up (+inf: none)
 };
 
+// Bin box of radius level l around p, clamped to the grid (inclusive bounds), and its x-rows: one row per
+// (brick column along x, bin y, bin z), nbx * ny * nz of them (row_run in kernels_neighbours.hpp decodes one).
+struct LevelBox {
+    int lox, loy, loz, hix, hiy, hiz;
+    int bx0, nbx, nrow;   // first brick column, brick columns, rows per z slice
+    int64_t total;        // rows of the box
+};
+__device__ __forceinline__ LevelBox level_box(const Grid& g, const float3 p, int l) {
+    const float rb = g.rho_box[l];
+    LevelBox b;
+    // clamp in float before converting: handles +-inf radii and far-away queries
+    b.lox = (int)fminf(fmaxf(bin_coord_f(p.x - rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
+    b.loy = (int)fminf(fmaxf(bin_coord_f(p.y - rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
+    b.loz = (int)fminf(fmaxf(bin_coord_f(p.z - rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
+    b.hix = (int)fminf(fmaxf(bin_coord_f(p.x + rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
+    b.hiy = (int)fminf(fmaxf(bin_coord_f(p.y + rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
+    b.hiz = (int)fminf(fmaxf(bin_coord_f(p.z + rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
+    b.bx0 = b.lox >> kBrickLog2;
+    b.nbx = (b.hix >> kBrickLog2) - b.bx0 + 1;
+    b.nrow = b.nbx * (b.hiy - b.loy + 1);
+    b.total = (int64_t)b.nrow * (b.hiz - b.loz + 1);
+    return b;
+}
+
 // Scan every target point in bins [lo, hi] (inclusive, already clamped to the grid).
 __device__ __forceinline__ void scan_box(const Grid& g, float3 p, int lox, int loy, int loz, int hix, int hiy,
                                          int hiz, Best& best) {
@@ -164,12 +209,7 @@ __device__ __forceinline__ void scan_box(const Grid& g, float3 p, int lox, int l
                         const uint32_t e = cs[row + x1 + 1];
                         for (uint32_t j = s; j < e; ++j) {
                             const float4 t = g.pts[j];
-                            const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
-                            float a = dx * dx;
-                            float b = dy * dy;
-                            float d2 = a + b;
-                            a = dz * dz;
-                            d2 = d2 + a;
+                            const float d2 = nc5_d2(p, t);
                             const uint32_t idx = __float_as_uint(t.w);
                             if (d2 <= g.max_d2 && (d2 < best.d2 || (d2 == best.d2 && idx < best.idx))) {
                                 best.d2 = d2;
@@ -191,15 +231,8 @@ __device__ __forceinline__ Best nearest(const Grid& g, float3 p) {
     best.pos2 = -1;
     best.third = INFINITY;
     for (int l = 0; l < g.n_levels; ++l) {
-        const float rb = g.rho_box[l];
-        // clamp in float before converting: handles +-inf radii and far-away queries
-        const float fx0 = fminf(fmaxf(bin_coord_f(p.x - rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-        const float fy0 = fminf(fmaxf(bin_coord_f(p.y - rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-        const float fz0 = fminf(fmaxf(bin_coord_f(p.z - rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-        const float fx1 = fminf(fmaxf(bin_coord_f(p.x + rb, g.ox, g.inv_c), 0.f), g.dimx - 1.f);
-        const float fy1 = fminf(fmaxf(bin_coord_f(p.y + rb, g.oy, g.inv_c), 0.f), g.dimy - 1.f);
-        const float fz1 = fminf(fmaxf(bin_coord_f(p.z + rb, g.oz, g.inv_c), 0.f), g.dimz - 1.f);
-        scan_box(g, p, (int)fx0, (int)fy0, (int)fz0, (int)fx1, (int)fy1, (int)fz1, best);
+        const LevelBox b = level_box(g, p, l);
+        scan_box(g, p, b.lox, b.loy, b.loz, b.hix, b.hiy, b.hiz, best);
         const float r = g.rho[l];
         float r2 = r * r;
         if (best.pos >= 0 && best.d2 <= r2) break;  // every point within rho was inside the box: exact
@@ -246,12 +279,7 @@ __device__ __forceinline__ void search_sec(int i) {
 
 template <bool kTop2 = false>
 __device__ __forceinline__ void consider(const Grid& g, float3 p, const float4 t, int j, Best& best) {
-    const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
-    float a = dx * dx;
-    float b = dy * dy;
-    float d2 = a + b;
-    a = dz * dz;
-    d2 = d2 + a;
+    const float d2 = nc5_d2(p, t);
     const uint32_t idx = __float_as_uint(t.w);
     if (d2 <= g.max_d2 && j != best.pos && (!kTop2 || j != best.pos2)) {   // (the clamped tail of a flattened scan re-reads its last point)
         if (d2 < best.d2 || (d2 == best.d2 && idx < best.idx)) {
@@ -331,12 +359,7 @@ __device__ __forceinline__ Best group_min(Best b) {
 // fetched when two candidates are exactly equidistant.
 template <bool kTop2 = false>
 __device__ __forceinline__ void consider_pos(const Grid& g, float3 p, const float4 t, Best& best) {
-    const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
-    float a = dx * dx;
-    float b = dy * dy;
-    float d2 = a + b;
-    a = dz * dz;
-    d2 = d2 + a;
+    const float d2 = nc5_d2(p, t);
     const int pos = (int)__float_as_uint(t.w);
     if (d2 <= g.max_d2 && pos != best.pos && (!kTop2 || pos != best.pos2)) {
         if (d2 < best.d2) {
@@ -643,8 +666,7 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
             }
             // compact the non-empty segments into the group's LDS list, in segment order
             SEARCH_SEC(2);
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            group_sync();
             uint32_t run_pts = 0, run_seg = 0;
 #pragma unroll
             for (int u = 0; u < S; ++u) {
@@ -672,8 +694,7 @@ __device__ __forceinline__ float scan_level_rows(const Grid& g, const float3 p, 
 #endif
             if (run_pts == 0) continue;
             if (sub == 0) seg_ex[run_seg] = run_pts;   // sentinel: end of the last segment
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-            __builtin_amdgcn_wave_barrier();
+            group_sync();
             SEARCH_SEC(3);
             // phase 2: flattened scan, 4 independent 16-byte loads in flight per lane
             uint32_t k = 0, cur_ex = 0, cur_st = seg_st[0], next_ex = seg_ex[1];
@@ -765,23 +786,13 @@ __device__ __forceinline__ bool nearest_halo(const Grid& g, float3 p, int sub, i
         if (!inside && g.out_bound) {
             const float ox = fmaxf(fmaxf(g.hox - p.x, p.x - g.hmaxx), 0.f), oy = fmaxf(fmaxf(g.hoy - p.y, p.y - g.hmaxy), 0.f),
                         oz = fmaxf(fmaxf(g.hoz - p.z, p.z - g.hmaxz), 0.f);
-            float a = ox * ox;
-            float b = oy * oy;
-            float s2 = a + b;
-            a = oz * oz;
-            s2 = s2 + a;
-            lbd = __builtin_amdgcn_sqrtf(s2) * (1.0f - 1e-3f) - g.lb_sub;
+            lbd = __builtin_amdgcn_sqrtf(sum_sq3(ox, oy, oz)) * (1.0f - 1e-3f) - g.lb_sub;
         }
         // the witness becomes the group's candidate (every lane holds the same one, as after a merge); the climb starts at
         // the first radius that covers it
         auto take_witness = [&](uint32_t w, int from) {
             const float4 t = g.pts[w];
-            const float dx = p.x - t.x, dy = p.y - t.y, dz = p.z - t.z;
-            float a = dx * dx;
-            float b = dy * dy;
-            float d2 = a + b;
-            a = dz * dz;
-            d2 = d2 + a;
+            const float d2 = nc5_d2(p, t);
             if (d2 <= g.max_d2) {   // (beyond max_dist it is no candidate: the empty-space bound alone applies)
                 best.d2 = d2;
                 best.idx = __float_as_uint(t.w);
