@@ -92,7 +92,39 @@ int main() {
         float dmax = 0.f;
         for (int k = 0; k < 16; ++k) dmax = std::fmax(dmax, std::fabs(Tp[k] - T[k]));
         std::printf("fp64 reading: %s; partitioned loop (1 rank, RCCL): max |dT| = %.2e\n", same64 ? "identical" : "DIFFERENT", dmax);
-        const bool ok2 = same64 && dmax < 1e-5f;
+        // motion compensation of the fp64 scan on the device: zero velocities return it bit for bit, a moving sensor does not
+        reg_params up;
+        reg_default_params(&up);
+        up.cost = REG_COST_O3D_P2P;
+        reg_handle* uh = nullptr;
+        if (reg_create(&up, &uh) != REG_OK) {
+            reg_destroy(uh);
+            return 5;
+        }
+        reg_undistort_params und{};
+        und.struct_size = (int32_t)sizeof(und);
+        und.spinning_clockwise = 1;
+        und.scan_duration = 0.1;
+        const bool still = o3dreg::undistortScan(uh, rd64.data(), N, und) == rd64;
+        // the velocities from five poses 0.1 s apart, 0.1 m forward and 0.05 rad of yaw each: 1 m/s and 0.5 rad/s in the sensor frame
+        std::vector<o3dreg::StampedPose> poses;
+        for (int i = 0; i < 5; ++i) {
+            o3dreg::StampedPose sp{(int64_t)i * 100000000, {}};
+            const double yaw = 0.05 * i, cy = std::cos(yaw), sy = std::sin(yaw);
+            sp.pose = {cy, sy, 0, 0, -sy, cy, 0, 0, 0, 0, 1, 0, 0.1 * i, 0, 0, 1};
+            poses.push_back(sp);
+        }
+        o3dreg::estimateLinearAndAngularVelocity(poses, 500000000, 3, und.linear_velocity, und.angular_velocity_rpy);
+        const bool velOk = std::fabs(und.angular_velocity_rpy[2] - 0.5) < 1e-4 && std::fabs(und.linear_velocity[0] - 1.0) < 0.02 &&
+                           std::fabs(und.angular_velocity_rpy[0]) < 1e-12 && std::fabs(und.linear_velocity[2]) < 1e-12;
+        const std::vector<double> moved = o3dreg::undistortScan(uh, rd64.data(), N, und);
+        double far = 0.0;
+        for (size_t k = 0; k < moved.size(); ++k) far = std::fmax(far, std::fabs(moved[k] - rd64[k]));
+        reg_destroy(uh);
+        const bool undOk = still && velOk && far > 0.01 && far < 1.0;
+        std::printf("undistortScan: zero velocities %s, 1 m/s + 0.5 rad/s moves a point by at most %.3f m\n",
+                    still ? "identical" : "DIFFERENT", far);
+        const bool ok2 = same64 && dmax < 1e-5f && undOk;
         std::printf(ok && ok2 ? "OK\n" : "MISMATCH\n");
         return ok && ok2 ? 0 : 1;
     } catch (const std::exception& e) {

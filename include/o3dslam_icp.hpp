@@ -9,6 +9,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <limits>
 #include <stdexcept>
@@ -909,5 +910,48 @@ private:
     reg_map_cloud* m_ = nullptr;
     bool owns_ = false;
 };
+
+// reg_undistort_scan on host arrays through `handle` (contract in include/o3dslam_reg.h):
+// ConstantVelocityMotionCompensation::undistortInputPointCloud for given velocities.  Points are n x 3 doubles.
+inline std::vector<double> undistortScan(reg_handle* handle, const double* points, int64_t n, const reg_undistort_params& params) {
+    std::vector<double> out((size_t)n * 3);
+    const reg_status s = reg_undistort_scan(handle, points, n, 0, &params, out.data());
+    if (s != REG_OK) {
+        const std::string msg = handle ? reg_last_error(handle) : "no handle";
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    return out;
+}
+
+// ConstantVelocityMotionCompensation::estimateLinearAndAngularVelocity (MotionCompensation.cpp:32-57) over a pose list, oldest
+// first, written as the reference evidently intends it (its own const buffer returns the latest pose for every offset, so it
+// can only throw): from the latest pose and the one numPoses before it, dT = start^-1 * finish,
+// linear = dT.translation / (dt + 1e-6), angularRpy = roll / pitch / yaw of dT.rotation / (dt + 1e-6).  Both are zero while
+// the list holds no more than numPoses poses or already reaches stampNs.  Host arithmetic; poses are column-major double[16],
+// rigid; stamps are nanoseconds.  The result fills reg_undistort_params::linear_velocity / angular_velocity_rpy.
+struct StampedPose {
+    int64_t stampNs;
+    std::array<double, 16> pose;
+};
+inline void estimateLinearAndAngularVelocity(const std::vector<StampedPose>& buffer, int64_t stampNs, int numPoses,
+                                             double linear[3], double angularRpy[3]) {
+    for (int k = 0; k < 3; ++k) linear[k] = angularRpy[k] = 0.0;
+    if (numPoses < 1) throw InvalidParameter("numPosesVelocityEstimation_ must be >= 1");
+    if (buffer.size() <= (size_t)numPoses || !(buffer.back().stampNs < stampNs)) return;
+    const StampedPose &fin = buffer.back(), &start = buffer[buffer.size() - 1 - (size_t)numPoses];
+    const double dt = (double)(fin.stampNs - start.stampNs) * 1e-9;
+    if (!(dt > 0.0)) throw std::runtime_error("dt should be > 0!!!!");
+    const double *A = start.pose.data(), *B = fin.pose.data();   // m(r, c) = pose[4 c + r]; start^-1 = (R^T, -R^T t)
+    double R[9], t[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = A[4 * r] * B[4 * c] + A[4 * r + 1] * B[4 * c + 1] + A[4 * r + 2] * B[4 * c + 2];
+        t[r] = A[4 * r] * (B[12] - A[12]) + A[4 * r + 1] * (B[13] - A[13]) + A[4 * r + 2] * (B[14] - A[14]);
+    }
+    // toRPY of R = Rz(yaw) Ry(pitch) Rx(roll) (math.hpp:30-42 reads the same three angles off the quaternion)
+    const double rpy[3] = {std::atan2(R[7], R[8]), std::asin(std::max(-1.0, std::min(1.0, -R[6]))), std::atan2(R[3], R[0])};
+    for (int k = 0; k < 3; ++k) linear[k] = t[k] / (dt + 1e-6), angularRpy[k] = rpy[k] / (dt + 1e-6);
+}
 
 }  // namespace o3dreg

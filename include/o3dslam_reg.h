@@ -1487,6 +1487,48 @@ REG_API reg_status reg_map_cloud_center(reg_map_cloud* m, double center[3]);
 REG_API reg_status reg_map_cloud_export(reg_map_cloud* m, int on_device, double* xyz, double* normals, double* covs,
                                         int64_t capacity_rows, int64_t* n_out);
 
+/* ---- motion compensation of a raw scan: the first step of both workers of the reference ------------------
+   ConstantVelocityMotionCompensation::undistortInputPointCloud (MotionCompensation.cpp:64-139; called at
+   SlamWrapper.cpp:730,890) for GIVEN velocities.  fp64 with one rounding per operation (the build forbids contraction); every
+   sum of three products is (a0 b0 + a1 b1) + a2 b2.  on_device covers both arrays.  Plain argument checks come before any
+   device work (they answer even on a handle without a device); then n == 0 returns REG_OK; then REG_DEVICE_ERROR.
+     Finding: the reference's own velocity estimate is dead code.  buffer_ is a const reference, the const overload of
+     latest_measurement(int) ignores its offset (TransformInterpolationBuffer.cpp:66-84), so start == finish, dt == 0 and
+     assert_gt(dt, 0.0) throws (MotionCompensation.cpp:41-47).  The device side therefore takes the two velocities as
+     arguments; the estimate as evidently intended lives in the Python and C++ mirrors (a departure).
+     Per point p = (x, y, z), one thread each, in this order (MotionCompensation.cpp:82-139, math.cpp:32-37):
+       a = atan2(y, x);  aw = a < 0 ? a + 2pi : a, with 2pi = 2.0 * M_PI;
+       phase = 0 when aw == 0; clockwise: 1 - aw / 2pi; otherwise aw / 2pi;
+       s = phase * scan_duration;  t = s * linear_velocity;  (roll, pitch, yaw) = s * angular_velocity_rpy;
+       q = qz(yaw) qy(pitch) qx(roll), each factor (cos(0.5 angle), sin(0.5 angle) axis), two Hamilton products
+         (qz qy) qx, every component summed left to right in Eigen's term order
+           w = a.w b.w - a.x b.x - a.y b.y - a.z b.z     x = a.w b.x + a.x b.w + a.y b.z - a.z b.y
+           y = a.w b.y + a.y b.w + a.z b.x - a.x b.z     z = a.w b.z + a.z b.w + a.x b.y - a.y b.x
+         (the zero components take part); then q / sqrt(((w w + x x) + y y) + z z), each component divided;
+       R = Eigen's toRotationMatrix: tx = 2x, ty = 2y, tz = 2z, twx = tx w, twy = ty w, twz = tz w, txx = tx x, txy = ty x,
+         txz = tz x, tyy = ty y, tyz = tz y, tzz = tz z;  R00 = 1 - (tyy + tzz), R01 = txy - twz, R02 = txz + twy,
+         R10 = txy + twz, R11 = 1 - (txx + tzz), R12 = tyz - twx, R20 = txz - twy, R21 = tyz + twx, R22 = 1 - (txx + tyy);
+       p' = ((Rr0 x + Rr1 y) + Rr2 z) + t_r.
+     Departure: when the three components of t and the three angles all compare equal to zero the motion is the identity
+     and p' = p, copied (the arithmetic would only turn a -0.0 coordinate into +0.0).  So zero velocities, and the points
+     of phase 0 (y = +-0, x > 0), come back bit for bit.
+     atan2, sin, cos are the platform's (libm on the host, the device math library on the GPU); everything else is exact
+     to the formula.  Normals and colours of a cloud pass through untouched (the reference rewrites points_ only), so the
+     call takes points only.  out_xyz may be xyz itself.
+     scan_duration <= 0 or non-finite, a non-finite velocity or a bad struct_size: REG_BAD_ARGUMENT (setParameters asserts
+     scan_duration > 0); n == 0: REG_OK.
+   reg_host_undistort_point: the same code for one point on the host. */
+typedef struct {
+    int32_t struct_size;              /* = sizeof(reg_undistort_params); checked */
+    int32_t spinning_clockwise;       /* isSpinningClockwise_ */
+    double  scan_duration;            /* scanDuration_ [s]; finite and > 0 */
+    double  linear_velocity[3];       /* of the sensor, in its own frame [m/s] */
+    double  angular_velocity_rpy[3];  /* roll, pitch, yaw rates [rad/s] */
+} reg_undistort_params;
+REG_API reg_status reg_undistort_scan(reg_handle* h, const double* xyz, int64_t n, int on_device,
+                                      const reg_undistort_params* params, double* out_xyz);
+REG_API reg_status reg_host_undistort_point(const double p[3], const reg_undistort_params* params, double out[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,6 +338,34 @@ def default_map_cloud_params(crop=None, **overrides) -> MapCloudParams:
     return p
 
 
+class UndistortParams(C.Structure):
+    """reg_undistort_params (include/o3dslam_reg.h): spin direction, scan duration and the two velocities of the sensor."""
+    _fields_ = [("struct_size", C.c_int32), ("spinning_clockwise", C.c_int32), ("scan_duration", C.c_double),
+                ("linear_velocity", C.c_double * 3), ("angular_velocity_rpy", C.c_double * 3)]
+
+
+def undistort_params(scan_duration, linear_velocity=(0.0, 0.0, 0.0), angular_velocity_rpy=(0.0, 0.0, 0.0),
+                     spinning_clockwise=True) -> UndistortParams:
+    """reg_undistort_params for given velocities (validated by the call that takes them)."""
+    u = UndistortParams()
+    u.struct_size = C.sizeof(UndistortParams)
+    u.spinning_clockwise = int(bool(spinning_clockwise))
+    u.scan_duration = float(scan_duration)
+    u.linear_velocity = (C.c_double * 3)(*[float(v) for v in linear_velocity])
+    u.angular_velocity_rpy = (C.c_double * 3)(*[float(v) for v in angular_velocity_rpy])
+    return u
+
+
+def host_undistort_point(p, params: UndistortParams) -> np.ndarray:
+    """reg_host_undistort_point: one point of reg_undistort_scan on the host (no device)."""
+    a = (C.c_double * 3)(*[float(v) for v in p])
+    out = (C.c_double * 3)()
+    st = load_library().reg_host_undistort_point(a, C.byref(params), out)
+    if st != 0:
+        raise RegError(st, "reg_host_undistort_point")
+    return np.array(out, np.float64)
+
+
 def default_dense_scan_params(crop=None, rgb_min=None, rgb_max=None) -> DenseScanParams:
     """reg_default_dense_scan_params (no crop, colours within [0, 1]); crop: a crop dict of Registration.set_target_f64."""
     p = DenseScanParams()
@@ -489,7 +517,8 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_dense_map_export", "reg_dedup_voxels", "reg_host_dense_offsets",
            "reg_default_map_cloud_params", "reg_map_cloud_create", "reg_map_cloud_destroy", "reg_map_cloud_clear",
            "reg_map_cloud_get_info", "reg_map_cloud_set", "reg_map_cloud_insert_scan", "reg_map_cloud_set_target",
-           "reg_map_cloud_transform", "reg_map_cloud_center", "reg_map_cloud_export"]
+           "reg_map_cloud_transform", "reg_map_cloud_center", "reg_map_cloud_export",
+           "reg_undistort_scan", "reg_host_undistort_point"]
 
 
 def lib_path() -> str:
@@ -620,6 +649,8 @@ def load_library():
     lib.reg_map_cloud_transform.argtypes = [vp, pd16]
     lib.reg_map_cloud_center.argtypes = [vp, pd16]
     lib.reg_map_cloud_export.argtypes = [vp, C.c_int, vp, vp, vp, i64, pi64]
+    lib.reg_undistort_scan.argtypes = [vp, vp, i64, C.c_int, C.POINTER(UndistortParams), vp]
+    lib.reg_host_undistort_point.argtypes = [pd16, C.POINTER(UndistortParams), pd16]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -1229,6 +1260,19 @@ class Registration:
         self.n_source = self.n_source_kept
         self._check(st)
         return res
+
+    # ---- motion compensation of a raw scan ----
+    def undistort_scan(self, xyz, params: "UndistortParams"):
+        """reg_undistort_scan: ConstantVelocityMotionCompensation::undistortInputPointCloud for given velocities; n x 3 fp64."""
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        out = np.empty_like(x)
+        self._check(self._lib.reg_undistort_scan(self._h, _ptr(x), x.shape[0], 0, C.byref(params), _ptr(out)))
+        return out
+
+    def undistort_scan_device(self, xyz_ptr, n, params: "UndistortParams", out_xyz_ptr):
+        """As undistort_scan with the fp64 arrays resident in HBM (out_xyz_ptr may be xyz_ptr)."""
+        self._check(self._lib.reg_undistort_scan(self._h, C.c_void_p(xyz_ptr) if xyz_ptr else None, n, 1, C.byref(params),
+                                                 C.c_void_p(out_xyz_ptr) if out_xyz_ptr else None))
 
     # ---- the dense map (DESIGN.md 5t): maps are DenseMap objects on this handle ----
     def dedup_voxels(self, xyz, voxel_size):

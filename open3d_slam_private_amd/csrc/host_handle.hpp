@@ -137,6 +137,8 @@ struct reg_handle {
     // the map clouds of this handle (host_mapcloud.hpp): staged inputs (scan points, normals, covariances; raw scan), the
     // transformed raw scan, and the working cloud an insert voxelises (survivors of the carve + the transformed scan)
     DevBuf mc_in[4], mc_raw, mc_cat[3];
+    // reg_undistort_scan (host_odometry.hpp): staged input and host-pointer output
+    DevBuf od_in, od_out;
     DevBuf d_d2all;                                  // select-by-gather (multi-GPU): all ranks' squared distances
     int64_t dist_nmax = 0;
     int dist_gather_ranks = 0;

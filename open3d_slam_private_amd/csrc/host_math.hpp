@@ -989,4 +989,85 @@ O3D_HD inline uint32_t pm_quantile_rank(uint32_t total, float ratio) {
     return r >= total ? total - 1 : r;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Motion compensation of the odometry worker (include/o3dslam_reg.h): the per-point undistortion, shared by
+// the device kernel (kernels_odometry.hpp) and reg_host_undistort_point.  fp64, one rounding per operation; every sum of
+// three products is (a0 b0 + a1 b1) + a2 b2.
+// ---------------------------------------------------------------------------------------------
+O3D_HD inline double dot3_ordered(double a0, double b0, double a1, double b1, double a2, double b2) {
+    double p = a0 * b0;
+    double q = a1 * b1;
+    double s = p + q;
+    p = a2 * b2;
+    return s + p;
+}
+
+// Hamilton product a b of (w, x, y, z) quaternions, every component summed left to right
+O3D_HD inline void quat_mul_ordered(const double* a, const double* b, double* o) {
+    double w = a[0] * b[0], x = a[0] * b[1], y = a[0] * b[2], z = a[0] * b[3];
+    w = w - a[1] * b[1];
+    x = x + a[1] * b[0];
+    y = y + a[2] * b[0];
+    z = z + a[3] * b[0];
+    w = w - a[2] * b[2];
+    x = x + a[2] * b[3];
+    y = y + a[3] * b[1];
+    z = z + a[1] * b[2];
+    w = w - a[3] * b[3];
+    x = x - a[3] * b[2];
+    y = y - a[1] * b[3];
+    z = z - a[2] * b[1];
+    o[0] = w;
+    o[1] = x;
+    o[2] = y;
+    o[3] = z;
+}
+
+// ConstantVelocityMotionCompensation::computePhase (MotionCompensation.cpp:120-139)
+O3D_HD inline double undistort_phase(double x, double y, int clockwise) {
+    const double two_pi = 2.0 * 3.14159265358979323846;
+    const double a = atan2(y, x);
+    const double aw = a < 0.0 ? a + two_pi : a;
+    if (aw == 0.0) return 0.0;
+    const double f = aw / two_pi;
+    return clockwise ? 1.0 - f : f;
+}
+
+// One point of undistortInputPointCloud (MotionCompensation.cpp:82-100) for given velocities: lin = linear velocity, rpy =
+// angular velocity as roll / pitch / yaw rates.  A motion whose six components all compare equal to zero is the identity
+// and copies the point (the arithmetic below would only turn a -0.0 coordinate into +0.0).
+O3D_HD inline void undistort_point(const double* p, int clockwise, double scan_duration, const double* lin, const double* rpy,
+                                   double* out) {
+    const double s = undistort_phase(p[0], p[1], clockwise) * scan_duration;
+    const double t[3] = {s * lin[0], s * lin[1], s * lin[2]};
+    const double e[3] = {s * rpy[0], s * rpy[1], s * rpy[2]};
+    if (t[0] == 0.0 && t[1] == 0.0 && t[2] == 0.0 && e[0] == 0.0 && e[1] == 0.0 && e[2] == 0.0) {
+        out[0] = p[0];
+        out[1] = p[1];
+        out[2] = p[2];
+        return;
+    }
+    const double hr = e[0] * 0.5, hp = e[1] * 0.5, hy = e[2] * 0.5;
+    const double qx[4] = {cos(hr), sin(hr), 0.0, 0.0};
+    const double qy[4] = {cos(hp), 0.0, sin(hp), 0.0};
+    const double qz[4] = {cos(hy), 0.0, 0.0, sin(hy)};
+    double qzy[4], q[4];
+    quat_mul_ordered(qz, qy, qzy);   // fromRPY: yaw * pitch * roll (math.cpp:32-37)
+    quat_mul_ordered(qzy, qx, q);
+    double n2 = q[0] * q[0];
+    n2 = n2 + q[1] * q[1];
+    n2 = n2 + q[2] * q[2];
+    n2 = n2 + q[3] * q[3];
+    const double nn = sqrt(n2);
+    const double w = q[0] / nn, x = q[1] / nn, y = q[2] / nn, z = q[3] / nn;
+    // Eigen's QuaternionBase::toRotationMatrix
+    const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const double R[9] = {1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz),
+                         tyz - twx, txz - twy, tyz + twx, 1.0 - (txx + tyy)};   // row-major
+    for (int r = 0; r < 3; ++r) out[r] = dot3_ordered(R[3 * r], p[0], R[3 * r + 1], p[1], R[3 * r + 2], p[2]) + t[r];
+}
+
 }  // namespace o3dreg

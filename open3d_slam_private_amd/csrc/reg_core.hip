@@ -59,6 +59,7 @@ using namespace o3dreg;
 #include "kernels_scanprep.hpp"
 #include "kernels_densemap.hpp"
 #include "kernels_mapcloud.hpp"
+#include "kernels_odometry.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_mem.hpp"
@@ -79,6 +80,7 @@ using namespace o3dreg;
 #include "host_scanprep.hpp"
 #include "host_densemap.hpp"
 #include "host_mapcloud.hpp"
+#include "host_odometry.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

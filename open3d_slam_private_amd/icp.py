@@ -18,6 +18,10 @@
   RegistrationRANSACBasedOnCorrespondence / RegistrationRANSACBasedOnFeatureMatching
                                <-> the Open3D operators of the same names (PlaceRecognition.cpp:78-85)
   ransacLoopClosure            <-> the RANSAC step of a loop-closure candidate and its size check (PlaceRecognition.cpp:78-91)
+  TransformInterpolationBuffer <-> o3d_slam::TransformInterpolationBuffer, interpolate and getTransform
+                                   (TransformInterpolationBuffer.cpp, Transform.cpp:16-67); host arithmetic
+  ConstantVelocityMotionCompensation <-> the class of the same name (MotionCompensation.cpp:30-139); the velocity estimate
+                                   is host arithmetic, the undistortion runs on the device
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -2273,3 +2277,219 @@ def ransacLoopClosure(sourceSparse, sourceFeature, targetSparse, targetFeature, 
     if result.correspondence_set_.shape[0] < prm.ransacMinCorrespondenceSetSize_:
         return None
     return result
+
+
+# ---- motion compensation and the pose buffer it reads (MotionCompensation.cpp, TransformInterpolationBuffer.cpp).
+#      Times are integer nanoseconds. ------------------------------------------------------------------------------------------
+def _quat_from_R(R):
+    """Eigen's Quaterniond(Matrix3d): (w, x, y, z)."""
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    if t > 0.0:
+        t = math.sqrt(t + 1.0)
+        w = 0.5 * t
+        t = 0.5 / t
+        return np.array([w, (R[2, 1] - R[1, 2]) * t, (R[0, 2] - R[2, 0]) * t, (R[1, 0] - R[0, 1]) * t])
+    i = 0
+    if R[1, 1] > R[0, 0]:
+        i = 1
+    if R[2, 2] > R[i, i]:
+        i = 2
+    j, k = (i + 1) % 3, (i + 2) % 3
+    t = math.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+    q = np.zeros(4)
+    q[1 + i] = 0.5 * t
+    t = 0.5 / t
+    q[0] = (R[k, j] - R[j, k]) * t
+    q[1 + j] = (R[j, i] + R[i, j]) * t
+    q[1 + k] = (R[k, i] + R[i, k]) * t
+    return q
+
+
+def _R_from_quat(q):
+    """Eigen's toRotationMatrix of (w, x, y, z)."""
+    w, x, y, z = q
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    return np.array([[1.0 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1.0 - (txx + tzz), tyz - twx],
+                     [txz - twy, tyz + twx, 1.0 - (txx + tyy)]])
+
+
+def _slerp(t, a, b):
+    """Eigen's QuaternionBase::slerp: the shorter arc, linear when the two nearly coincide."""
+    d = float(np.dot(a, b))
+    ad = abs(d)
+    if ad >= 1.0 - np.finfo(np.float64).eps:
+        s0, s1 = 1.0 - t, t
+    else:
+        theta = math.acos(ad)
+        st = math.sin(theta)
+        s0, s1 = math.sin((1.0 - t) * theta) / st, math.sin(t * theta) / st
+    if d < 0.0:
+        s1 = -s1
+    return s0 * a + s1 * b
+
+
+def toRPY(q):
+    """o3d_slam::toRPY (math.cpp:39-46, math.hpp:30-42) of (w, x, y, z), normalised first."""
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([math.atan2(2 * (w * x + y * z), 1 - 2 * (x * x + y * y)), math.asin(2 * (w * y - x * z)),
+                     math.atan2(2 * (w * z + x * y), 1 - 2 * (y * y + z * z))])
+
+
+def interpolate(start, end, time):
+    """o3d_slam::interpolate (Transform.cpp:16-67) of two (time, 4x4) pairs: linear translation, slerp rotation, factor =
+    (time - start) / (duration + 1e-6) in seconds; a reversed pair is swapped, a time outside it raises RuntimeError."""
+    (t0, T0), (t1, T1) = (start, end) if start[0] <= end[0] else (end, start)
+    if time > t1 or time < t0:
+        raise RuntimeError("transform interpolate:: query time is not between start and end time")
+    factor = ((time - t0) * 1e-9) / ((t1 - t0) * 1e-9 + 1e-6)
+    T = np.eye(4)
+    T[:3, :3] = _R_from_quat(_slerp(factor, _quat_from_R(T0[:3, :3]), _quat_from_R(T1[:3, :3])))
+    T[:3, 3] = T0[:3, 3] + (T1[:3, 3] - T0[:3, 3]) * factor
+    return time, T
+
+
+class TransformInterpolationBuffer:
+    """o3d_slam::TransformInterpolationBuffer: (time, transform) pairs pushed in order, capped at a size limit (2000,
+    TransformInterpolationBuffer.cpp:16) with the oldest dropped first.  Departure: latest_measurement honours its offset
+    (the reference's const overload ignores it, which is what makes its velocity estimate throw)."""
+
+    def __init__(self, bufferSize=2000):
+        if not (_is_int(bufferSize) and bufferSize >= 1):
+            raise InvalidParameter(f"bufferSize must be an integer >= 1, got {bufferSize!r}")
+        self.bufferSizeLimit_ = bufferSize
+        self.transforms_ = []
+
+    def push(self, time, tf) -> bool:
+        """False (and nothing stored) for a time earlier than the earliest or than the latest measurement
+        (TransformInterpolationBuffer.cpp:22-46)."""
+        if self.transforms_ and (time < self.earliest_time() or time < self.latest_time()):
+            return False
+        self.transforms_.append((int(time), np.array(tf, np.float64).reshape(4, 4)))
+        self._trim()
+        return True
+
+    def _trim(self):
+        while len(self.transforms_) > self.bufferSizeLimit_:
+            self.transforms_.pop(0)
+
+    def setSizeLimit(self, n):
+        if not (_is_int(n) and n >= 1):
+            raise InvalidParameter(f"the size limit must be an integer >= 1, got {n!r}")
+        self.bufferSizeLimit_ = n
+        self._trim()
+
+    def clear(self):
+        self.transforms_ = []
+
+    def empty(self) -> bool:
+        return not self.transforms_
+
+    def size(self) -> int:
+        return len(self.transforms_)
+
+    def size_limit(self) -> int:
+        return self.bufferSizeLimit_
+
+    def _need(self):
+        if not self.transforms_:
+            raise RuntimeError("TransformInterpolationBuffer:: Empty buffer")
+
+    def earliest_time(self):
+        self._need()
+        return self.transforms_[0][0]
+
+    def latest_time(self):
+        self._need()
+        return self.transforms_[-1][0]
+
+    def latest_measurement(self, offsetFromLastElement=0):
+        """The measurement `offsetFromLastElement` places before the latest one; RuntimeError for an empty buffer,
+        InvalidParameter for an offset that is no integer in [0, size())."""
+        self._need()
+        k = offsetFromLastElement
+        if not (_is_int(k) and 0 <= k < len(self.transforms_)):
+            raise InvalidParameter(f"offsetFromLastElement must be an integer in [0, {len(self.transforms_)}), got {k!r}")
+        return self.transforms_[-1 - k]
+
+    def has(self, time) -> bool:
+        return bool(self.transforms_) and self.earliest_time() <= time <= self.latest_time()
+
+    def lookup(self, time) -> np.ndarray:
+        """The transform at `time`: stored, or interpolated between its two neighbours (lookup, :100-142)."""
+        if not self.has(time):
+            raise RuntimeError(f"TransformInterpolationBuffer:: Missing transform for: {time}")
+        if len(self.transforms_) == 1:
+            return self.transforms_[0][1].copy()
+        k = next(i for i, (t, _) in enumerate(self.transforms_) if time <= t)
+        if self.transforms_[k][0] == time:
+            return self.transforms_[k][1].copy()
+        return interpolate(self.transforms_[k - 1], self.transforms_[k], time)[1]
+
+
+def getTransform(time, buffer: TransformInterpolationBuffer) -> np.ndarray:
+    """o3d_slam::getTransform (:182-192): a time outside the buffer is clamped to its ends."""
+    return buffer.lookup(min(max(time, buffer.earliest_time()), buffer.latest_time()))
+
+
+class ConstantVelocityMotionCompensation:
+    """o3d_slam::ConstantVelocityMotionCompensation over a TransformInterpolationBuffer.  The undistortion is
+    reg_undistort_scan on the device; the velocity estimate is host arithmetic, written as the reference evidently intends
+    it (its own throws: see TransformInterpolationBuffer) -- a departure.  `reg`: the capi.Registration to run on; without
+    one the first undistortInputPointCloud creates a handle that close() frees."""
+
+    def __init__(self, buffer: TransformInterpolationBuffer, isSpinningClockwise_=True, scanDuration_=0.1,
+                 numPosesVelocityEstimation_=3, reg: "capi.Registration | None" = None):
+        if not (_is_real(scanDuration_) and math.isfinite(scanDuration_) and scanDuration_ > 0.0):
+            raise InvalidParameter(f"lidar scanDuration_: must be finite and > 0, got {scanDuration_!r}")   # setParameters
+        if not (_is_int(numPosesVelocityEstimation_) and numPosesVelocityEstimation_ >= 1):
+            raise InvalidParameter(f"numPosesVelocityEstimation_ must be an integer >= 1, got {numPosesVelocityEstimation_!r}")
+        self.buffer_ = buffer
+        self.isSpinningClockwise_ = bool(isSpinningClockwise_)
+        self.scanDuration_ = float(scanDuration_)
+        self.numPosesVelocityEstimation_ = numPosesVelocityEstimation_
+        self._reg = reg
+        self._own = False   # True once undistortInputPointCloud has made a handle of its own: close() frees it
+
+    def close(self):
+        """Frees the registration handle this object created (a handle given as `reg` stays the caller's)."""
+        if self._own and self._reg is not None:
+            self._reg.close()
+            self._reg, self._own = None, False
+
+    def computePhase(self, x, y) -> float:
+        angle = math.atan2(y, x)
+        wrapped = angle + 2.0 * math.pi if angle < 0.0 else angle
+        if wrapped == 0.0:
+            return 0.0
+        return 1.0 - wrapped / (2.0 * math.pi) if self.isSpinningClockwise_ else wrapped / (2.0 * math.pi)
+
+    def estimateLinearAndAngularVelocity(self, timestamp):
+        """(linear, angular rpy) of the sensor from the latest pose and the one numPosesVelocityEstimation_ before it;
+        zero while the buffer holds no more poses than that, or already holds the timestamp."""
+        offset = self.numPosesVelocityEstimation_
+        if self.buffer_.size() <= offset or not (self.buffer_.latest_time() < timestamp):
+            return np.zeros(3), np.zeros(3)
+        t1, T1 = self.buffer_.latest_measurement()
+        t0, T0 = self.buffer_.latest_measurement(offset)
+        dT = np.linalg.inv(T0) @ T1
+        dt = (t1 - t0) * 1e-9
+        if not dt > 0.0:
+            raise RuntimeError("dt should be > 0!!!!")
+        q = _quat_from_R(dT[:3, :3])
+        return dT[:3, 3] / (dt + 1e-6), toRPY(q / np.linalg.norm(q)) / (dt + 1e-6)
+
+    def params(self, timestamp) -> "capi.UndistortParams":
+        lin, ang = self.estimateLinearAndAngularVelocity(timestamp)
+        return capi.undistort_params(self.scanDuration_, lin, ang, self.isSpinningClockwise_)
+
+    def undistortInputPointCloud(self, xyz, timestamp) -> np.ndarray:
+        """n x 3 fp64 points of the raw scan, motion-compensated on the device."""
+        if self._reg is None:
+            self._reg, self._own = _feature_handle(), True   # kept for the next scan; close() frees it
+        try:
+            return self._reg.undistort_scan(xyz, self.params(timestamp))
+        except RegError as e:
+            raise _translate(e) from None
