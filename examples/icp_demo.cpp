@@ -124,7 +124,30 @@ int main() {
         const bool undOk = still && velOk && far > 0.01 && far < 1.0;
         std::printf("undistortScan: zero velocities %s, 1 m/s + 0.5 rad/s moves a point by at most %.3f m\n",
                     still ? "identical" : "DIFFERENT", far);
-        const bool ok2 = same64 && dmax < 1e-5f && undOk;
+        // the resident LidarOdometry with the GICP operator on a scan that brings its normals: the first scan is kept, the
+        // same scan again registers onto itself (identity, fitness 1) and the pose buffer gets one entry per scan
+        reg_params gp;
+        reg_default_params(&gp);
+        gp.cost = REG_COST_GICP;
+        gp.use_trimmed = 0;
+        gp.gicp_stop_rule = 1;
+        gp.max_dist = 0.5f;
+        reg_odometry_params op;
+        reg_default_odometry_params(&op);
+        op.use_odometry_topic = 0;
+        op.crop.type = REG_CROP_NONE;
+        op.voxel_size = 0.0;
+        op.normal_knn = 0;
+        o3dreg::LidarOdometry odom(op, gp);
+        const bool first = odom.addRangeScan(rd64.data(), rdn64.data(), N, 0);
+        const bool second = odom.addRangeScan(rd64.data(), rdn64.data(), N, 100000000);
+        const reg_odometry_result& orr = odom.lastResult();
+        const bool odomOk = first && second && orr.registered && orr.fitness > 0.99 && std::fabs(orr.cumulative[12]) < 1e-4 &&
+                            odom.getBuffer().size() == 2 && odom.getPreProcessedCloud().covariances.size() == 9 * (size_t)N &&
+                            o3dreg::covariancesFromNormals(odom.handle(), rdn64.data(), N) == odom.getPreProcessedCloud().covariances;
+        std::printf("LidarOdometry (GICP from normals): fitness %.3f, %d iterations, %s\n", orr.fitness, orr.iterations,
+                    odomOk ? "consistent" : "INCONSISTENT");
+        const bool ok2 = same64 && dmax < 1e-5f && undOk && odomOk;
         std::printf(ok && ok2 ? "OK\n" : "MISMATCH\n");
         return ok && ok2 ? 0 : 1;
     } catch (const std::exception& e) {

@@ -954,4 +954,129 @@ inline void estimateLinearAndAngularVelocity(const std::vector<StampedPose>& buf
     for (int k = 0; k < 3; ++k) linear[k] = t[k] / (dt + 1e-6), angularRpy[k] = rpy[k] / (dt + 1e-6);
 }
 
+// reg_covariances_from_normals on host arrays through `handle` (contract in include/o3dslam_reg.h): the
+// covariances Open3D's GeneralizedICP derives from normals.  n x 3 doubles in, n x 9 doubles out.
+inline std::vector<double> covariancesFromNormals(reg_handle* handle, const double* normals, int64_t n, double epsilon = 1e-3) {
+    std::vector<double> out((size_t)(n > 0 ? n : 0) * 9);
+    const reg_status s = reg_covariances_from_normals(handle, normals, n, 0, epsilon, out.data());
+    if (s != REG_OK) {
+        const std::string msg = handle ? reg_last_error(handle) : "no handle";
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    return out;
+}
+
+// o3d_slam::LidarOdometry over reg_odometry (Odometry.cpp): the previous pre-processed cloud stays on the device
+// between scans.  RAII, move-only.  The object lives on a registration handle: one it creates from `reg` and owns, or the
+// caller's (borrowed; the object must go before it).  `reg` selects the operator: REG_COST_GICP, REG_COST_O3D_P2PL or
+// REG_COST_O3D_P2P, configured as the Open3D operators are (use_trimmed = 0; gicp_stop_rule = 1 for GICP).  The buffer of
+// stamped poses is the caller's side of getOdomToRangeSensor: addRangeScan appends (stamp, cumulative) whenever the library
+// says pose_updated.  Clouds are host arrays (n x 3 doubles); stamps are nanoseconds; poses column-major double[16].
+class LidarOdometry {
+public:
+    struct Cloud {
+        std::vector<double> points, normals, covariances;
+        int64_t size() const { return (int64_t)(points.size() / 3); }
+    };
+
+    LidarOdometry(const reg_odometry_params& params, const reg_params& reg) : owns_(true) {
+        reg_status s = reg_create(&reg, &h_);
+        if (s == REG_OK) s = reg_odometry_create(h_, &params, &o_);
+        if (s != REG_OK) {
+            const std::string msg = h_ ? reg_last_error(h_) : "reg_create rejected the parameters";
+            release();
+            raise(s, msg);
+        }
+    }
+    LidarOdometry(reg_handle* handle, const reg_odometry_params& params) : h_(handle), owns_(false) {
+        const reg_status s = reg_odometry_create(h_, &params, &o_);
+        if (s != REG_OK) raise(s, h_ ? reg_last_error(h_) : "no handle");
+    }
+    ~LidarOdometry() { release(); }
+    LidarOdometry(const LidarOdometry&) = delete;
+    LidarOdometry& operator=(const LidarOdometry&) = delete;
+    LidarOdometry(LidarOdometry&& o) noexcept : buffer_(std::move(o.buffer_)), last_(o.last_), h_(o.h_), o_(o.o_), owns_(o.owns_) {
+        o.h_ = nullptr, o.o_ = nullptr;
+    }
+    LidarOdometry& operator=(LidarOdometry&& o) noexcept {
+        if (this != &o) {
+            release();
+            buffer_ = std::move(o.buffer_), last_ = o.last_, h_ = o.h_, o_ = o.o_, owns_ = o.owns_;
+            o.h_ = nullptr, o.o_ = nullptr;
+        }
+        return *this;
+    }
+
+    // addRangeScan (Odometry.cpp:29-84); normals may be null.  lastResult() keeps the counts, the transform and the times.
+    bool addRangeScan(const double* points, const double* normals, int64_t n, int64_t stampNs) {
+        reg_odometry_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_odometry_add_scan(o_, points, normals, n, 0, stampNs, &r));
+        last_ = r;
+        if (r.pose_updated) {
+            StampedPose p{stampNs, {}};
+            std::copy(r.cumulative, r.cumulative + 16, p.pose.begin());
+            buffer_.push_back(p);
+        }
+        return r.accepted != 0;
+    }
+    // false (and nothing changes) while an earlier initial transform is still pending
+    bool setInitialTransform(const double T[16]) {
+        int32_t applied = 0;
+        check(reg_odometry_set_initial_transform(o_, T, &applied));
+        return applied != 0;
+    }
+    void clear() {
+        check(reg_odometry_clear(o_));
+        buffer_.clear();
+    }
+    reg_odometry_info info() const {
+        reg_odometry_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_odometry_get_info(o_, &i));
+        return i;
+    }
+    // getPreProcessedCloud: sized from the library's own row count, which the export checks again
+    Cloud getPreProcessedCloud() {
+        const reg_odometry_info i = info();
+        const size_t rows = (size_t)i.n_rows;
+        Cloud out;
+        out.points.resize(rows * 3);
+        if (i.has_normals) out.normals.resize(rows * 3);
+        if (i.has_covariances) out.covariances.resize(rows * 9);
+        int64_t k = 0;
+        check(reg_odometry_export_cloud(o_, 0, out.points.data(), i.has_normals ? out.normals.data() : nullptr,
+                                        i.has_covariances ? out.covariances.data() : nullptr, i.n_rows, &k));
+        return out;
+    }
+    const std::vector<StampedPose>& getBuffer() const { return buffer_; }
+    bool hasProcessedMeasurements() const { return !buffer_.empty(); }
+    const reg_odometry_result& lastResult() const { return last_; }
+    reg_odometry* odometry() const { return o_; }
+    reg_handle* handle() const { return h_; }
+
+private:
+    static void raise(reg_status s, const std::string& msg) {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_MISSING_FIELD) throw InvalidField(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    void check(reg_status s) const {
+        if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    void release() {
+        if (o_) reg_odometry_destroy(o_);   // the object goes before its handle
+        if (h_ && owns_) reg_destroy(h_);
+        o_ = nullptr, h_ = nullptr;
+    }
+    std::vector<StampedPose> buffer_;
+    reg_odometry_result last_{};
+    reg_handle* h_ = nullptr;
+    reg_odometry* o_ = nullptr;
+    bool owns_ = false;
+};
+
 }  // namespace o3dreg

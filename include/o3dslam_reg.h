@@ -1529,6 +1529,151 @@ REG_API reg_status reg_undistort_scan(reg_handle* h, const double* xyz, int64_t 
                                       const reg_undistort_params* params, double* out_xyz);
 REG_API reg_status reg_host_undistort_point(const double p[3], const reg_undistort_params* params, double out[3]);
 
+/* ---- rows of the reading the handle holds -----------------------------------------------------------------
+   The number of rows reg_get_correspondences / reg_get_correspondences_k write per array: the reading as it stands,
+   whoever installed it (reg_set_source*, reg_process_scan, reg_set_pair_overlap_f64, reg_odometry_add_scan); 0 when there
+   is none.  A binding sizes its arrays from this, never from a count of its own. */
+REG_API reg_status reg_get_source_count(const reg_handle* h, int64_t* n_rows);
+
+/* ---- GICP covariances from normals ------------------------------------------------------------------------
+   What Open3D 0.15.1's RegistrationGeneralizedICP derives for a cloud that has normals and no covariances
+   (InitializePointCloudForGeneralizedICP, GetRotationFromE1ToX), restated: Open3D is not vendored, PARITY UNPINNED.
+   fp64, one rounding per operation (the build forbids contraction); every sum of three products is (a0 b0 + a1 b1) + a2 b2.
+   Per normal x = (x0, x1, x2), NOT normalised first, in this order:
+     v = e1 x x as Eigen's cross: v0 = 0 x2 - 0 x1, v1 = 0 x0 - 1 x2, v2 = 1 x1 - 0 x0;  c = (1 x0 + 0 x1) + 0 x2;
+     c < -0.99: Rx = I.  (Oddity reproduced: Open3D's comment says "x and e1 are in the same direction"; they are opposite,
+       and the identity does not rotate e1 onto x.  So the normal -e1 gets diag(epsilon, 1, 1), which happens to be right.)
+     otherwise S = [v]x = [0 -v2 v1; v2 0 -v0; -v1 v0 0], f = 1 / (1 + c),
+       S2(i,j) = (S(i,0) S(0,j) + S(i,1) S(1,j)) + S(i,2) S(2,j),  Rx(i,j) = (I(i,j) + S(i,j)) + S2(i,j) f;
+     M(i,0) = Rx(i,0) epsilon, M(i,1) = Rx(i,1) 1, M(i,2) = Rx(i,2) 1;
+     cov(i,j) = (M(i,0) Rx(j,0) + M(i,1) Rx(j,1)) + M(i,2) Rx(j,2), stored row-major: the covariances_ layout of reg_set_*_f64.
+   A non-finite component yields whatever this arithmetic yields.  normals: n x 3 doubles, out_covs: n x 9 doubles, both host
+   or both device pointers.  epsilon non-finite or <= 0, n < 0 or n > 2^31 - 1, a missing array for n > 0: REG_BAD_ARGUMENT,
+   decided before any device work; then n == 0: REG_OK, with or without a device; then REG_DEVICE_ERROR.
+   reg_host_covariance_from_normal: the same code for one normal on the host. */
+REG_API reg_status reg_covariances_from_normals(reg_handle* h, const double* normals, int64_t n, int on_device, double epsilon,
+                                                double* out_covs);
+REG_API reg_status reg_host_covariance_from_normal(const double normal[3], double epsilon, double out_cov[9]);
+
+/* ---- LidarOdometry resident on the device (Odometry.cpp:22-141) ---------------------------------------------
+   One object per handle use: it keeps cloudPrev_ (fp64 points, optional normals and covariances) in two sides on the device
+   and the cumulative pose, the pending initial transform and the last stamp on the host.  It works on the handle's stream
+   and working storage and installs its own reference and reading on the handle; destroy it before the handle.
+   The handle's cost selects the operator of cloudRegistrationFactory: REG_COST_GICP, REG_COST_O3D_P2PL or REG_COST_O3D_P2P
+   (REG_COST_P2PL: REG_BAD_ARGUMENT, the factory has no libpointmatcher operator).  Configure the handle as the Open3D
+   operators are configured: use_trimmed = 0, and gicp_stop_rule = 1 for GICP.
+   reg_odometry_add_scan, in this order (flags in the result):
+     first scan (no previous cloud): preprocess, keep as the previous cloud, record the stamp; accepted = pose_updated = 1
+       (the caller pushes the unchanged cumulative pose, Odometry.cpp:33);
+     timestamp < last stamp: accepted = 0, nothing changes (an equal stamp goes on: the reference tests <);
+     use_odometry_topic: accepted = 1, pose_updated = 0, nothing else happens;
+     preprocess (Odometry.cpp:22-27): crop, reg_voxel_down_sample (voxel_size <= 0 skips it), normals as reg_process_scan
+       estimates them (viewpoint at the origin) when the scan brings none and the operator is GICP or O3D_P2PL,
+       reg_random_down_sample (ratio >= 1 skips it).  There is no narrow crop.  A scan that brings normals keeps them;
+     GICP: covariances of the NEW cloud from its normals, reg_covariances_from_normals with gicp_epsilon (the previous cloud
+       keeps those it got when it was new);
+     register: reading = the PREVIOUS cloud, reference = the NEW cloud (reg_set_target_f64 then reg_set_source_f64 of the
+       resident arrays, no crop), T_init = identity (registerClouds(cloudPrev_, *preProcessed, I), Odometry.cpp:53);
+     fitness > min_fitness fails: accepted = 0, the new cloud replaces the previous one, pose and stamp stay;
+     otherwise: a pending initial transform BECOMES the cumulative pose and the registration result is discarded (oddity
+       reproduced, Odometry.cpp:73-75); else cumulative = cumulative * T^-1 (reg_host_odometry_accumulate); the new cloud
+       becomes the previous one, the stamp is recorded, pose_updated = 1.
+   The hand-over is a swap of the two sides.  A call that returns an error status leaves cloud, pose and stamp as they were.
+   Departure: a scan that is empty after preprocessing is REG_EMPTY_SOURCE with the state unchanged (the reference would run
+   Open3D on an empty cloud).  GICP or O3D_P2PL with neither normals nor normal_knn > 0: REG_MISSING_FIELD.
+   Every entry point that writes a caller array takes its capacity in rows and returns REG_BAD_ARGUMENT, writing nothing,
+   when it is too small. */
+typedef struct reg_odometry reg_odometry;
+typedef struct {
+    int32_t  struct_size;          /* = sizeof(reg_odometry_params); checked */
+    int32_t  use_odometry_topic;   /* useOdometryTopic_ (true as shipped) */
+    reg_crop crop;                 /* scanProcessing_.cropper_ */
+    double   voxel_size;           /* scanProcessing_.voxelSize_; finite; <= 0: no voxel grid */
+    double   down_sampling_ratio;  /* scanProcessing_.downSamplingRatio_; in [0, 1] */
+    uint64_t seed;                 /* of reg_random_down_sample */
+    int32_t  normal_knn;           /* 0 .. 32; 0: never estimate */
+    int32_t  reserved;
+    double   normal_radius;        /* > 0 when normal_knn > 0 */
+    double   gicp_epsilon;         /* Open3D's epsilon (1e-3); finite and > 0 */
+    double   min_fitness;          /* the fitness gate (0.1, "todo magic", Odometry.cpp:56); finite */
+} reg_odometry_params;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_odometry_result), set by the caller */
+    int32_t accepted;              /* addRangeScan's return value */
+    int32_t pose_updated;          /* the caller pushes (timestamp, cumulative) into its buffer */
+    int32_t registered;            /* a registration ran in this call */
+    int32_t iterations;
+    int32_t reserved;
+    int64_t n_crop, n_voxels, n_selected;   /* rows after crop / voxel grid / random selection */
+    int64_t n_source, n_target;    /* rows of the registration: previous cloud, new cloud */
+    double  fitness, inlier_rmse;
+    double  cumulative[16];        /* column-major, after the call */
+    float   T[16];                 /* the registration result, column-major (identity when none ran) */
+    float   prep_ms, register_ms;  /* device time of preprocess (+ covariances) and of target + source + loop (HIP events) */
+} reg_odometry_result;
+typedef struct {
+    int32_t struct_size;           /* = sizeof(reg_odometry_info), set by the caller */
+    int32_t has_cloud;             /* a previous cloud is held */
+    int32_t has_normals, has_covariances;
+    int32_t has_stamp;             /* a stamp has been recorded */
+    int32_t initial_pending;       /* an initial transform waits for the next accepted registration */
+    int64_t n_rows;
+    int64_t last_stamp_ns;
+    double  cumulative[16];
+} reg_odometry_info;
+/* Parameters.hpp:59-86 and the shipped Lua: the scan croppper and processing of reg_default_scan_params (MinMaxRadius 2 ..
+   100, z -50 .. 50, voxel 0.01, ratio 1, knn 20 within 1 m), gicp_epsilon 1e-3, min_fitness 0.1, use_odometry_topic 1. */
+REG_API void reg_default_odometry_params(reg_odometry_params* p);
+/* The validation reg_odometry_create runs, without a device: REG_BAD_ARGUMENT for a wrong struct_size of either struct,
+   cost P2PL, an unknown crop type, a non-finite voxel_size, a ratio outside [0, 1], normal_knn outside [0, 32],
+   normal_radius <= 0 with normal_knn > 0, gicp_epsilon non-finite or <= 0, a non-finite min_fitness. */
+REG_API reg_status reg_check_odometry_params(const reg_params* p, const reg_odometry_params* o);
+/* sizeof of reg_odometry_params, reg_odometry_result, reg_odometry_info, for a binding to compare its mirrors with */
+REG_API void reg_odometry_struct_sizes(int32_t sizes[3]);
+REG_API reg_status reg_odometry_create(reg_handle* h, const reg_odometry_params* params, reg_odometry** out);
+REG_API void reg_odometry_destroy(reg_odometry* o);   /* before reg_destroy of its handle */
+REG_API reg_status reg_odometry_clear(reg_odometry* o);   /* a fresh LidarOdometry: no cloud, no stamp, identity pose */
+REG_API reg_status reg_odometry_get_info(const reg_odometry* o, reg_odometry_info* info);
+/* setInitialTransform (Odometry.cpp:110-126): *applied = 0 and nothing changes while an earlier one is pending (the reference
+   prints and skips); otherwise the cumulative pose is set at once and the transform stays pending.  T: column-major. */
+REG_API reg_status reg_odometry_set_initial_transform(reg_odometry* o, const double T[16], int32_t* applied);
+/* xyz: n x 3 doubles, normals: n x 3 or NULL, both host or both device pointers; timestamp in nanoseconds. */
+REG_API reg_status reg_odometry_add_scan(reg_odometry* o, const double* xyz, const double* normals, int64_t n, int on_device,
+                                         int64_t timestamp_ns, reg_odometry_result* result);
+/* getPreProcessedCloud: the previous cloud.  Any output may be NULL; normals / covs are written only when held. */
+REG_API reg_status reg_odometry_export_cloud(reg_odometry* o, int on_device, double* xyz, double* normals, double* covs,
+                                             int64_t capacity_rows, int64_t* n_out);
+/* Correspondences of the last registration of this object (host arrays; rows = its n_source; ids index the new cloud, -1:
+   none).  REG_NOT_CONFIGURED when the handle's reading is no longer the one this object installed. */
+REG_API reg_status reg_odometry_get_correspondences(reg_odometry* o, int64_t capacity_rows, int32_t* ids, float* d2);
+
+/* The branch logic of addRangeScan as one host function (no device).  Inputs: has_previous, the two stamps,
+   use_odometry_topic, the rows of the preprocessed scan, the fitness, min_fitness, initial_pending.  Returns the bits that
+   apply.  rows and fitness matter only where REG_ODOM_REGISTER is set: the object calls it once to learn whether to
+   preprocess and register, and again with the outcome. */
+enum {
+    REG_ODOM_ACCEPTED = 1, REG_ODOM_POSE_UPDATED = 2, REG_ODOM_REPLACE_CLOUD = 4, REG_ODOM_POSE_FROM_INITIAL = 8,
+    REG_ODOM_ACCUMULATE = 16, REG_ODOM_RECORD_STAMP = 32, REG_ODOM_PREPROCESS = 64, REG_ODOM_REGISTER = 128
+};
+REG_API int32_t reg_host_odometry_decide(int32_t has_previous, int64_t timestamp_ns, int64_t last_stamp_ns,
+                                         int32_t use_odometry_topic, int64_t n_rows, double fitness, double min_fitness,
+                                         int32_t initial_pending);
+/* cumulative = cumulative * T^-1 in fp64, both column-major; T is the float result widened exactly.  One rounding per
+   operation.  The inverse is the GENERAL cofactor inverse (no rigidity assumed, as Matrix4d::inverse() assumes none; bit
+   parity with Eigen's vectorised inverse is unpinned).  With a(r,c) = T(r,c):
+     s0 = a00 a11 - a10 a01, s1 = a00 a12 - a10 a02, s2 = a00 a13 - a10 a03, s3 = a01 a12 - a11 a02, s4 = a01 a13 - a11 a03,
+     s5 = a02 a13 - a12 a03, c5 = a22 a33 - a32 a23, c4 = a21 a33 - a31 a23, c3 = a21 a32 - a31 a22, c2 = a20 a33 - a30 a23,
+     c1 = a20 a32 - a30 a22, c0 = a20 a31 - a30 a21 (each product rounded, then the difference);
+     det = ((((s0 c5 - s1 c4) + s2 c3) + s3 c2) - s4 c1) + s5 c0;  id = 1 / det;  with t(x,p,y,q,z,r) = (x p - y q) + z r:
+     b00 =  t(a11,c5,a12,c4,a13,c3) id   b01 = -t(a01,c5,a02,c4,a03,c3) id   b02 =  t(a31,s5,a32,s4,a33,s3) id
+     b03 = -t(a21,s5,a22,s4,a23,s3) id   b10 = -t(a10,c5,a12,c2,a13,c1) id   b11 =  t(a00,c5,a02,c2,a03,c1) id
+     b12 = -t(a30,s5,a32,s2,a33,s1) id   b13 =  t(a20,s5,a22,s2,a23,s1) id   b20 =  t(a10,c4,a11,c2,a13,c0) id
+     b21 = -t(a00,c4,a01,c2,a03,c0) id   b22 =  t(a30,s4,a31,s2,a33,s0) id   b23 = -t(a20,s4,a21,s2,a23,s0) id
+     b30 = -t(a10,c3,a11,c1,a12,c0) id   b31 =  t(a00,c3,a01,c1,a02,c0) id   b32 = -t(a30,s3,a31,s1,a32,s0) id
+     b33 =  t(a20,s3,a21,s1,a22,s0) id   (the sign applied to t, then the product with id);
+     out(i,j) = ((cum(i,0) b0j + cum(i,1) b1j) + cum(i,2) b2j) + cum(i,3) b3j. */
+REG_API reg_status reg_host_odometry_accumulate(double cumulative[16], const float T[16]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -366,6 +366,97 @@ def host_undistort_point(p, params: UndistortParams) -> np.ndarray:
     return np.array(out, np.float64)
 
 
+class OdometryParams(C.Structure):
+    """reg_odometry_params (include/o3dslam_reg.h): the scan cropper and processing, GICP's epsilon, the fitness gate."""
+    _fields_ = [("struct_size", C.c_int32), ("use_odometry_topic", C.c_int32), ("crop", RegCrop), ("voxel_size", C.c_double),
+                ("down_sampling_ratio", C.c_double), ("seed", C.c_uint64), ("normal_knn", C.c_int32), ("reserved", C.c_int32),
+                ("normal_radius", C.c_double), ("gicp_epsilon", C.c_double), ("min_fitness", C.c_double)]
+
+
+class OdometryResult(C.Structure):
+    """reg_odometry_result (include/o3dslam_reg.h); T_matrix() / cumulative_matrix() give the 4 x 4 math layout."""
+    _fields_ = [("struct_size", C.c_int32), ("accepted", C.c_int32), ("pose_updated", C.c_int32), ("registered", C.c_int32),
+                ("iterations", C.c_int32), ("reserved", C.c_int32), ("n_crop", C.c_int64), ("n_voxels", C.c_int64),
+                ("n_selected", C.c_int64), ("n_source", C.c_int64), ("n_target", C.c_int64), ("fitness", C.c_double),
+                ("inlier_rmse", C.c_double), ("cumulative", C.c_double * 16), ("T", C.c_float * 16), ("prep_ms", C.c_float),
+                ("register_ms", C.c_float)]
+
+    def T_matrix(self) -> np.ndarray:
+        return _T_out(self.T)
+
+    def cumulative_matrix(self) -> np.ndarray:
+        return np.array(self.cumulative, np.float64).reshape(4, 4).T.copy()
+
+
+class OdometryInfo(C.Structure):
+    """reg_odometry_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("has_cloud", C.c_int32), ("has_normals", C.c_int32),
+                ("has_covariances", C.c_int32), ("has_stamp", C.c_int32), ("initial_pending", C.c_int32),
+                ("n_rows", C.c_int64), ("last_stamp_ns", C.c_int64), ("cumulative", C.c_double * 16)]
+
+
+ODOM_ACCEPTED, ODOM_POSE_UPDATED, ODOM_REPLACE_CLOUD, ODOM_POSE_FROM_INITIAL = 1, 2, 4, 8
+ODOM_ACCUMULATE, ODOM_RECORD_STAMP, ODOM_PREPROCESS, ODOM_REGISTER = 16, 32, 64, 128
+
+
+def default_odometry_params(crop=None, **overrides) -> OdometryParams:
+    """reg_default_odometry_params (the shipped scan cropper and processing, gicp_epsilon 1e-3, min_fitness 0.1,
+    use_odometry_topic 1); crop: a crop dict of Registration.set_target_f64; overrides by field name."""
+    p = OdometryParams()
+    load_library().reg_default_odometry_params(C.byref(p))
+    if crop is not None:
+        p.crop = Registration._crop_struct(crop)
+    for k, v in overrides.items():
+        if k in ("use_odometry_topic", "normal_knn", "seed"):
+            setattr(p, k, int(v))
+        elif k in ("voxel_size", "down_sampling_ratio", "normal_radius", "gicp_epsilon", "min_fitness"):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"unknown odometry parameter {k}")
+    return p
+
+
+def check_odometry_params(params: "RegParams", odometry: OdometryParams) -> int:
+    """reg_check_odometry_params: the validation of Odometry(), without a device.  Returns the status."""
+    return int(load_library().reg_check_odometry_params(C.byref(params), C.byref(odometry)))
+
+
+def odometry_struct_sizes() -> tuple:
+    """reg_odometry_struct_sizes: sizeof of (reg_odometry_params, reg_odometry_result, reg_odometry_info) in the library."""
+    out = (C.c_int32 * 3)()
+    load_library().reg_odometry_struct_sizes(out)
+    return tuple(out)
+
+
+def host_covariance_from_normal(normal, epsilon=1e-3) -> np.ndarray:
+    """reg_host_covariance_from_normal: one row of reg_covariances_from_normals on the host (no device); 3 x 3."""
+    a = (C.c_double * 3)(*[float(v) for v in normal])
+    out = (C.c_double * 9)()
+    st = load_library().reg_host_covariance_from_normal(a, float(epsilon), out)
+    if st != 0:
+        raise RegError(st, "reg_host_covariance_from_normal")
+    return np.array(out, np.float64).reshape(3, 3)
+
+
+def host_odometry_decide(has_previous, timestamp, last_stamp, use_odometry_topic, n_rows, fitness, min_fitness,
+                         initial_pending) -> int:
+    """reg_host_odometry_decide: the ODOM_* bits of addRangeScan's branch for these inputs (no device)."""
+    return int(load_library().reg_host_odometry_decide(int(bool(has_previous)), int(timestamp), int(last_stamp),
+                                                       int(bool(use_odometry_topic)), int(n_rows), float(fitness),
+                                                       float(min_fitness), int(bool(initial_pending))))
+
+
+def host_odometry_accumulate(cumulative, T) -> np.ndarray:
+    """reg_host_odometry_accumulate: cumulative (4 x 4 float64) times the inverse of T (4 x 4, cast to float32 as the
+    registration returns it), on the host (no device)."""
+    cum = _T_in_f64(cumulative)
+    Tf = _T_in(T)
+    st = load_library().reg_host_odometry_accumulate(cum, _ptr(Tf))
+    if st != 0:
+        raise RegError(st, "reg_host_odometry_accumulate")
+    return np.array(cum, np.float64).reshape(4, 4).T.copy()
+
+
 def default_dense_scan_params(crop=None, rgb_min=None, rgb_max=None) -> DenseScanParams:
     """reg_default_dense_scan_params (no crop, colours within [0, 1]); crop: a crop dict of Registration.set_target_f64."""
     p = DenseScanParams()
@@ -518,7 +609,12 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_map_cloud_params", "reg_map_cloud_create", "reg_map_cloud_destroy", "reg_map_cloud_clear",
            "reg_map_cloud_get_info", "reg_map_cloud_set", "reg_map_cloud_insert_scan", "reg_map_cloud_set_target",
            "reg_map_cloud_transform", "reg_map_cloud_center", "reg_map_cloud_export",
-           "reg_undistort_scan", "reg_host_undistort_point"]
+           "reg_undistort_scan", "reg_host_undistort_point",
+           "reg_get_source_count", "reg_covariances_from_normals", "reg_host_covariance_from_normal",
+           "reg_default_odometry_params", "reg_check_odometry_params", "reg_odometry_struct_sizes", "reg_odometry_create",
+           "reg_odometry_destroy", "reg_odometry_clear", "reg_odometry_get_info", "reg_odometry_set_initial_transform",
+           "reg_odometry_add_scan", "reg_odometry_export_cloud", "reg_odometry_get_correspondences",
+           "reg_host_odometry_decide", "reg_host_odometry_accumulate"]
 
 
 def lib_path() -> str:
@@ -651,6 +747,26 @@ def load_library():
     lib.reg_map_cloud_export.argtypes = [vp, C.c_int, vp, vp, vp, i64, pi64]
     lib.reg_undistort_scan.argtypes = [vp, vp, i64, C.c_int, C.POINTER(UndistortParams), vp]
     lib.reg_host_undistort_point.argtypes = [pd16, C.POINTER(UndistortParams), pd16]
+    lib.reg_get_source_count.argtypes = [vp, pi64]
+    lib.reg_covariances_from_normals.argtypes = [vp, vp, i64, C.c_int, C.c_double, vp]
+    lib.reg_host_covariance_from_normal.argtypes = [pd16, C.c_double, pd16]
+    lib.reg_default_odometry_params.argtypes = [C.POINTER(OdometryParams)]
+    lib.reg_default_odometry_params.restype = None
+    lib.reg_check_odometry_params.argtypes = [C.POINTER(RegParams), C.POINTER(OdometryParams)]
+    lib.reg_odometry_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
+    lib.reg_odometry_struct_sizes.restype = None
+    lib.reg_odometry_create.argtypes = [vp, C.POINTER(OdometryParams), C.POINTER(vp)]
+    lib.reg_odometry_destroy.argtypes = [vp]
+    lib.reg_odometry_destroy.restype = None
+    lib.reg_odometry_clear.argtypes = [vp]
+    lib.reg_odometry_get_info.argtypes = [vp, C.POINTER(OdometryInfo)]
+    lib.reg_odometry_set_initial_transform.argtypes = [vp, pd16, C.POINTER(C.c_int32)]
+    lib.reg_odometry_add_scan.argtypes = [vp, vp, vp, i64, C.c_int, i64, C.POINTER(OdometryResult)]
+    lib.reg_odometry_export_cloud.argtypes = [vp, C.c_int, vp, vp, vp, i64, pi64]
+    lib.reg_odometry_get_correspondences.argtypes = [vp, i64, vp, vp]
+    lib.reg_host_odometry_decide.argtypes = [C.c_int32, i64, i64, C.c_int32, i64, C.c_double, C.c_double, C.c_int32]
+    lib.reg_host_odometry_decide.restype = C.c_int32
+    lib.reg_host_odometry_accumulate.argtypes = [pd16, vp]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -1041,6 +1157,8 @@ class Registration:
                 m.close()
             for m in list(getattr(self, "_map_clouds", ())):   # and so is a reg_map_cloud
                 m.close()
+            for m in list(getattr(self, "_odometries", ())):   # and a reg_odometry
+                m.close()
             self._lib.reg_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -1273,6 +1391,20 @@ class Registration:
         """As undistort_scan with the fp64 arrays resident in HBM (out_xyz_ptr may be xyz_ptr)."""
         self._check(self._lib.reg_undistort_scan(self._h, C.c_void_p(xyz_ptr) if xyz_ptr else None, n, 1, C.byref(params),
                                                  C.c_void_p(out_xyz_ptr) if out_xyz_ptr else None))
+
+    # ---- GICP covariances from normals (DESIGN.md 5y) ----
+    def covariances_from_normals(self, normals, epsilon=1e-3):
+        """reg_covariances_from_normals: what Open3D's GeneralizedICP derives for a cloud with normals and no covariances;
+        n x 3 fp64 normals (not normalised here) -> n x 9 fp64, the covariances_ layout of set_*_f64."""
+        nr = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+        out = np.empty((nr.shape[0], 9), np.float64)
+        self._check(self._lib.reg_covariances_from_normals(self._h, _ptr(nr), nr.shape[0], 0, float(epsilon), _ptr(out)))
+        return out
+
+    def covariances_from_normals_device(self, nrm_ptr, n, out_cov_ptr, epsilon=1e-3):
+        """As covariances_from_normals with the fp64 arrays (n x 3 in, n x 9 out) resident in HBM."""
+        self._check(self._lib.reg_covariances_from_normals(self._h, C.c_void_p(nrm_ptr) if nrm_ptr else None, n, 1,
+                                                           float(epsilon), C.c_void_p(out_cov_ptr) if out_cov_ptr else None))
 
     # ---- the dense map (DESIGN.md 5t): maps are DenseMap objects on this handle ----
     def dedup_voxels(self, xyz, voxel_size):
@@ -1768,8 +1900,15 @@ class Registration:
         self._check(self._lib.reg_linearize(self._h, _ptr(Ti), _ptr(H), _ptr(b), C.byref(err), C.byref(cnt)))
         return H.reshape(6, 6), b, err.value, cnt.value
 
+    def source_count(self) -> int:
+        """reg_get_source_count: the rows of the reading the handle holds, whoever installed it.  n_source is a cached copy."""
+        n = C.c_int64(0)
+        self._check(self._lib.reg_get_source_count(self._h, C.byref(n)))
+        self.n_source = int(n.value)
+        return self.n_source
+
     def correspondences(self, want_w=True):
-        n = self.n_source
+        n = self.source_count()
         ids = np.empty(n, np.int32)
         d2 = np.empty(n, np.float32)
         w = np.empty(n, np.float32) if want_w else None
@@ -1801,7 +1940,7 @@ class Registration:
         """(ids, d2, w) of the last iteration, each n x knn, reading input order, ascending (d2, id)."""
         if knn is None:
             knn = self.pm_chain.knn if getattr(self, "pm_chain", None) is not None else 1
-        n = self.n_source
+        n = self.source_count()
         ids = np.empty((n, knn), np.int32)
         d2 = np.empty((n, knn), np.float32)
         w = np.empty((n, knn), np.float32) if want_w else None
@@ -2233,6 +2372,110 @@ class MapCloud:
         self._check(self._lib.reg_map_cloud_export(self._m, 1, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), int(capacity_rows),
                                                    C.byref(k)))
         return int(k.value)
+
+
+class Odometry:
+    """One LidarOdometry (== one reg_odometry; Odometry.cpp) on the handle of `reg`: the previous pre-processed cloud stays
+    on the device between scans, the cumulative pose on the host inside the library.  It uses the stream and the working
+    storage of `reg`, installs its own reference and reading there, and must be closed before it (close() of either order is
+    safe here: the object keeps `reg` alive and closes itself first).  Every row count comes from the library."""
+
+    def __init__(self, reg: Registration, params: "OdometryParams | None" = None):
+        self._lib = load_library()
+        self.reg = reg
+        self._o = C.c_void_p()
+        p = params if params is not None else default_odometry_params()
+        p.struct_size = C.sizeof(OdometryParams)
+        reg._check(self._lib.reg_odometry_create(reg._h, C.byref(p), C.byref(self._o)))
+        self.params = p
+        if not hasattr(reg, "_odometries"):
+            reg._odometries = weakref.WeakSet()
+        reg._odometries.add(self)
+
+    def close(self):
+        if getattr(self, "_o", None) and getattr(self.reg, "_h", None):
+            self._lib.reg_odometry_destroy(self._o)
+        self._o = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        self.reg._check(st)
+
+    def add_scan(self, xyz, timestamp, normals=None) -> OdometryResult:
+        """addRangeScan: n x 3 fp64 points (and normals) of a scan in the sensor frame, the stamp in nanoseconds."""
+        x = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
+        nr = np.ascontiguousarray(normals, np.float64).reshape(-1, 3) if normals is not None else None
+        return self._add_scan(_ptr(x), _ptr(nr), x.shape[0], 0, timestamp)
+
+    def add_scan_device(self, xyz_ptr, n, timestamp, nrm_ptr=None) -> OdometryResult:
+        """As add_scan with the fp64 arrays resident in HBM."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._add_scan(vp(xyz_ptr), vp(nrm_ptr), n, 1, timestamp)
+
+    def _add_scan(self, x, nr, n, on_device, timestamp):
+        res = OdometryResult()
+        res.struct_size = C.sizeof(OdometryResult)
+        st = self._lib.reg_odometry_add_scan(self._o, x, nr, n, on_device, int(timestamp), C.byref(res))
+        self.last_result = res
+        self._check(st)
+        return res
+
+    def set_initial_transform(self, T) -> bool:
+        """setInitialTransform: False (nothing changes) while an earlier one is still pending."""
+        applied = C.c_int32(0)
+        self._check(self._lib.reg_odometry_set_initial_transform(self._o, _T_in_f64(T), C.byref(applied)))
+        return bool(applied.value)
+
+    def clear(self):
+        self._check(self._lib.reg_odometry_clear(self._o))
+
+    def info(self) -> OdometryInfo:
+        i = OdometryInfo()
+        i.struct_size = C.sizeof(OdometryInfo)
+        self._check(self._lib.reg_odometry_get_info(self._o, C.byref(i)))
+        return i
+
+    def cumulative(self) -> np.ndarray:
+        """odomToRangeSensorCumulative_ as a 4 x 4 float64 matrix."""
+        return np.array(self.info().cumulative, np.float64).reshape(4, 4).T.copy()
+
+    def export_cloud(self):
+        """getPreProcessedCloud: dict(xyz, normals, covs); normals / covs are None when the cloud lacks the field."""
+        i = self.info()
+        n = int(i.n_rows)
+        f = lambda on, w: np.empty((max(n, 1), w), np.float64) if on else None
+        x, nr, cv = f(True, 3), f(i.has_normals, 3), f(i.has_covariances, 9)
+        k = C.c_int64(0)
+        self._check(self._lib.reg_odometry_export_cloud(self._o, 0, _ptr(x), _ptr(nr), _ptr(cv), max(n, 1), C.byref(k)))
+        cut = lambda a: a[:int(k.value)] if a is not None else None
+        return dict(xyz=cut(x), normals=cut(nr), covs=cut(cv))
+
+    def export_cloud_device(self, capacity_rows, xyz_ptr=None, nrm_ptr=None, cov_ptr=None) -> int:
+        """As export_cloud into arrays resident in HBM (capacity_rows rows each; any may be None).  Returns n_rows."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        k = C.c_int64(0)
+        self._check(self._lib.reg_odometry_export_cloud(self._o, 1, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), int(capacity_rows),
+                                                        C.byref(k)))
+        return int(k.value)
+
+    def correspondences(self):
+        """(ids, d2) of the last registration of this object: one row per point of the then previous cloud, ids into the
+        then new cloud (-1: none)."""
+        n = int(self.last_result.n_source) if getattr(self, "last_result", None) is not None else 0
+        ids, d2 = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.float32)
+        self._check(self._lib.reg_odometry_get_correspondences(self._o, ids.shape[0], _ptr(ids), _ptr(d2)))
+        return ids[:n], d2[:n]
 
 
 def dist_unique_id() -> bytes:

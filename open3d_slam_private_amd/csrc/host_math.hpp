@@ -1070,4 +1070,102 @@ O3D_HD inline void undistort_point(const double* p, int clockwise, double scan_d
     for (int r = 0; r < 3; ++r) out[r] = dot3_ordered(R[3 * r], p[0], R[3 * r + 1], p[1], R[3 * r + 2], p[2]) + t[r];
 }
 
+// ---------------------------------------------------------------------------------------------
+// The odometry object (include/o3dslam_reg.h): the covariance Open3D's GeneralizedICP derives from a normal
+// (shared by k_cov_from_normals and reg_host_covariance_from_normal) and the pose update.  fp64, one rounding per operation.
+// ---------------------------------------------------------------------------------------------
+
+// InitializePointCloudForGeneralizedICP for one point: cov = Rx diag(eps, 1, 1) Rx^T with Rx = GetRotationFromE1ToX(x), row-major.
+// x is not normalised.  Oddity reproduced: c < -0.99 returns Rx = I (Open3D's comment calls this "the same direction").
+O3D_HD inline void cov_from_normal(const double* x, double eps, double* out) {
+    const double v[3] = {0.0 * x[2] - 0.0 * x[1], 0.0 * x[0] - 1.0 * x[2], 1.0 * x[1] - 0.0 * x[0]};   // e1 x x, Eigen's cross
+    const double c = dot3_ordered(1.0, x[0], 0.0, x[1], 0.0, x[2]);
+    double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
+    if (!(c < -0.99)) {
+        const double sv[9] = {0.0, -v[2], v[1], v[2], 0.0, -v[0], -v[1], v[0], 0.0};
+        const double f = 1.0 / (1.0 + c);
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double s2 = dot3_ordered(sv[3 * i], sv[j], sv[3 * i + 1], sv[3 + j], sv[3 * i + 2], sv[6 + j]);
+                const double a = R[3 * i + j] + sv[3 * i + j];
+                R[3 * i + j] = a + s2 * f;
+            }
+    }
+    double M[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        M[3 * i] = R[3 * i] * eps;
+        M[3 * i + 1] = R[3 * i + 1] * 1.0;
+        M[3 * i + 2] = R[3 * i + 2] * 1.0;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            out[3 * i + j] = dot3_ordered(M[3 * i], R[3 * j], M[3 * i + 1], R[3 * j + 1], M[3 * i + 2], R[3 * j + 2]);
+}
+
+// a b - c d, each product rounded, then the difference
+O3D_HD inline double det2_ordered(double a, double b, double c, double d) {
+    const double p = a * b;
+    const double q = c * d;
+    return p - q;
+}
+
+// cum = cum * inverse(T): both column-major 4x4, fp64.  The inverse is the general cofactor inverse over the six 2x2
+// minors of the upper and of the lower row pair (no rigidity assumed, as Matrix4d::inverse() assumes none); the product sums
+// each entry left to right over k.  The order is written out in include/o3dslam_reg.h.
+O3D_HD inline void odometry_accumulate(double* cum, const double* T) {
+#define A_(r, c) T[(c) * 4 + (r)]
+    const double s0 = det2_ordered(A_(0, 0), A_(1, 1), A_(1, 0), A_(0, 1)), s1 = det2_ordered(A_(0, 0), A_(1, 2), A_(1, 0), A_(0, 2));
+    const double s2 = det2_ordered(A_(0, 0), A_(1, 3), A_(1, 0), A_(0, 3)), s3 = det2_ordered(A_(0, 1), A_(1, 2), A_(1, 1), A_(0, 2));
+    const double s4 = det2_ordered(A_(0, 1), A_(1, 3), A_(1, 1), A_(0, 3)), s5 = det2_ordered(A_(0, 2), A_(1, 3), A_(1, 2), A_(0, 3));
+    const double c5 = det2_ordered(A_(2, 2), A_(3, 3), A_(3, 2), A_(2, 3)), c4 = det2_ordered(A_(2, 1), A_(3, 3), A_(3, 1), A_(2, 3));
+    const double c3 = det2_ordered(A_(2, 1), A_(3, 2), A_(3, 1), A_(2, 2)), c2 = det2_ordered(A_(2, 0), A_(3, 3), A_(3, 0), A_(2, 3));
+    const double c1 = det2_ordered(A_(2, 0), A_(3, 2), A_(3, 0), A_(2, 2)), c0 = det2_ordered(A_(2, 0), A_(3, 1), A_(3, 0), A_(2, 1));
+    double det = s0 * c5;
+    det = det - s1 * c4;
+    det = det + s2 * c3;
+    det = det + s3 * c2;
+    det = det - s4 * c1;
+    det = det + s5 * c0;
+    const double id = 1.0 / det;
+    // x y0 - y y1 + z y2, left to right
+    auto t3 = [](double x, double y0, double y, double y1, double z, double y2) {
+        double r = x * y0;
+        r = r - y * y1;
+        return r + z * y2;
+    };
+    double B[16];   // the inverse, row-major
+    B[0] = t3(A_(1, 1), c5, A_(1, 2), c4, A_(1, 3), c3) * id;
+    B[1] = -t3(A_(0, 1), c5, A_(0, 2), c4, A_(0, 3), c3) * id;
+    B[2] = t3(A_(3, 1), s5, A_(3, 2), s4, A_(3, 3), s3) * id;
+    B[3] = -t3(A_(2, 1), s5, A_(2, 2), s4, A_(2, 3), s3) * id;
+    B[4] = -t3(A_(1, 0), c5, A_(1, 2), c2, A_(1, 3), c1) * id;
+    B[5] = t3(A_(0, 0), c5, A_(0, 2), c2, A_(0, 3), c1) * id;
+    B[6] = -t3(A_(3, 0), s5, A_(3, 2), s2, A_(3, 3), s1) * id;
+    B[7] = t3(A_(2, 0), s5, A_(2, 2), s2, A_(2, 3), s1) * id;
+    B[8] = t3(A_(1, 0), c4, A_(1, 1), c2, A_(1, 3), c0) * id;
+    B[9] = -t3(A_(0, 0), c4, A_(0, 1), c2, A_(0, 3), c0) * id;
+    B[10] = t3(A_(3, 0), s4, A_(3, 1), s2, A_(3, 3), s0) * id;
+    B[11] = -t3(A_(2, 0), s4, A_(2, 1), s2, A_(2, 3), s0) * id;
+    B[12] = -t3(A_(1, 0), c3, A_(1, 1), c1, A_(1, 2), c0) * id;
+    B[13] = t3(A_(0, 0), c3, A_(0, 1), c1, A_(0, 2), c0) * id;
+    B[14] = -t3(A_(3, 0), s3, A_(3, 1), s1, A_(3, 2), s0) * id;
+    B[15] = t3(A_(2, 0), s3, A_(2, 1), s1, A_(2, 2), s0) * id;
+#undef A_
+    double P[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double r = cum[i] * B[j];   // cum(i, 0) * B(0, j)
+            r = r + cum[4 + i] * B[4 + j];
+            r = r + cum[8 + i] * B[8 + j];
+            r = r + cum[12 + i] * B[12 + j];
+            P[j * 4 + i] = r;
+        }
+    for (int k = 0; k < 16; ++k) cum[k] = P[k];
+}
+
 }  // namespace o3dreg

@@ -57,6 +57,95 @@ static reg_status sp_random_flags(reg_handle* h, int64_t n, int64_t count, uint6
     return REG_OK;
 }
 
+// Stages 1-4 of the front end on a device cloud: crop, VoxelDownSample, estimateNormalsOrCovariancesIfNeeded, RandomDownSample.
+// cur[3] (points, normals, covariances; null: absent) and *rows are the cloud on entry and on return; the result lies in the
+// handle's sp_a / sp_b / sp_c buffers (or is the input itself when no stage moved it).  An empty crop is REG_EMPTY_SOURCE.
+static reg_status sp_front(reg_handle* h, const double* cur[3], int64_t* rows, const CropCfg& crop, double voxel, bool estimate,
+                           bool est_cov, int knn, double radius, double ratio, uint64_t seed, int64_t* n_crop, int64_t* n_vox) {
+    int64_t m = *rows;
+    // 1. crop, order-preserving
+    if (crop.type != REG_CROP_NONE) {
+        HIPCHK(h, h->sp.heads.reserve((size_t)m * 4));
+        HIPCHK(h, h->sp.run.reserve((size_t)m * 4));
+        uint32_t *flags = h->sp.heads.as<uint32_t>(), *offs = h->sp.run.as<uint32_t>();
+        k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(cur[0], m, crop, flags);
+        int64_t kept = 0;
+        REGCHK(scan_total(h, flags, offs, m, &kept));
+        if (kept > 0) {
+            double* o[3] = {nullptr, nullptr, nullptr};
+            for (int k = 0; k < 3; ++k)
+                if (cur[k]) {
+                    HIPCHK(h, h->sp_a[k].reserve((size_t)kept * kSpWidth[k] * 8));
+                    o[k] = h->sp_a[k].as<double>();
+                }
+            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m, flags, offs,
+                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
+            for (int k = 0; k < 3; ++k) cur[k] = o[k];
+        }
+        m = kept;
+    }
+    *n_crop = m;
+    if (m == 0) {
+        *rows = 0;
+        h->err = "ScanToMapIcp::wideCropped cropped size is zero";   // ScanToMapRegistration.cpp:67
+        return REG_EMPTY_SOURCE;
+    }
+    // 2. VoxelDownSample (helpers.cpp:108-111: voxel_size <= 0 skips it)
+    if (voxel > 0.0) {
+        double* o[3] = {nullptr, nullptr, nullptr};
+        for (int k = 0; k < 3; ++k)
+            if (cur[k]) {
+                HIPCHK(h, h->sp_b[k].reserve((size_t)m * kSpWidth[k] * 8));
+                o[k] = h->sp_b[k].as<double>();
+            }
+        int64_t kept = 0;
+        REGCHK(sp_voxel_device(h, cur[0], cur[1], cur[2], m, voxel, o[0], o[1], o[2], &kept));
+        for (int k = 0; k < 3; ++k) cur[k] = o[k];
+        m = kept;
+    }
+    *n_vox = m;
+    // 3. estimateNormalsOrCovariancesIfNeeded: a cloud that brings normals keeps them (CloudRegistration.cpp:27,64)
+    if (estimate) {
+        HIPCHK(h, h->sp_f32[0].reserve((size_t)m * 12));
+        HIPCHK(h, h->sp_f32[1].reserve((size_t)m * 12));
+        if (est_cov) HIPCHK(h, h->sp_f32[2].reserve((size_t)m * 24));
+        float *fx = h->sp_f32[0].as<float>(), *fn = h->sp_f32[1].as<float>(), *fc = est_cov ? h->sp_f32[2].as<float>() : nullptr;
+        k_cast_cloud_f64<<<grid_for(m), 256, 0, h->stream>>>(cur[0], nullptr, nullptr, m, fx, nullptr, nullptr);
+        reg_normals_out no;
+        std::memset(&no, 0, sizeof(no));
+        no.normals = fn;
+        no.covs = fc;
+        const float origin[3] = {0.f, 0.f, 0.f};
+        REGCHK(reg_estimate_normals(h, fx, 3, m, 1, knn, (float)radius, origin, 1, &no, nullptr));
+        HIPCHK(h, h->sp_b[1].reserve((size_t)m * 24));
+        if (est_cov) HIPCHK(h, h->sp_b[2].reserve((size_t)m * 72));
+        double *on = h->sp_b[1].as<double>(), *oc = est_cov ? h->sp_b[2].as<double>() : nullptr;
+        k_sp_widen<<<grid_for(m), 256, 0, h->stream>>>(fn, fc, m, on, oc);
+        cur[1] = on;
+        if (est_cov) cur[2] = oc;
+    }
+    // 4. RandomDownSample (helpers.cpp:100-103: ratio >= 1 skips it)
+    if (ratio < 1.0) {
+        const int64_t count = (int64_t)(ratio * (double)m);
+        if (count > 0) {
+            REGCHK(sp_random_flags(h, m, count, seed));
+            double* o[3] = {nullptr, nullptr, nullptr};
+            for (int k = 0; k < 3; ++k)
+                if (cur[k]) {
+                    HIPCHK(h, h->sp_c[k].reserve((size_t)count * kSpWidth[k] * 8));
+                    o[k] = h->sp_c[k].as<double>();
+                }
+            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m,
+                                                                       h->sp.heads.as<uint32_t>(), h->sp.run.as<uint32_t>(),
+                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
+            for (int k = 0; k < 3; ++k) cur[k] = o[k];
+        }
+        m = count;
+    }
+    *rows = m;
+    return REG_OK;
+}
+
 static bool sp_ratio_ok(double ratio) { return ratio >= 0.0 && ratio <= 1.0; }   // false for NaN
 
 extern "C" {
@@ -189,84 +278,9 @@ reg_status reg_process_scan(reg_handle* h, const double* xyz, const double* norm
     const double* cur[3] = {xyz, normals, covs};   // the cloud as it stands after each stage (device pointers)
     for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->sp_in[k], cur[k], (size_t)n * kSpWidth[k], on_device, &cur[k]));
     int64_t m = n;
-    // 1. wide crop (mapBuilderCropper_), order-preserving
-    if (wide.type != REG_CROP_NONE) {
-        HIPCHK(h, h->sp.heads.reserve((size_t)m * 4));
-        HIPCHK(h, h->sp.run.reserve((size_t)m * 4));
-        uint32_t *flags = h->sp.heads.as<uint32_t>(), *offs = h->sp.run.as<uint32_t>();
-        k_crop_flags<<<grid_for(m), 256, 0, h->stream>>>(cur[0], m, wide, flags);
-        int64_t kept = 0;
-        REGCHK(scan_total(h, flags, offs, m, &kept));
-        if (kept > 0) {
-            double* o[3] = {nullptr, nullptr, nullptr};
-            for (int k = 0; k < 3; ++k)
-                if (cur[k]) {
-                    HIPCHK(h, h->sp_a[k].reserve((size_t)kept * kSpWidth[k] * 8));
-                    o[k] = h->sp_a[k].as<double>();
-                }
-            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m, flags, offs,
-                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
-            for (int k = 0; k < 3; ++k) cur[k] = o[k];
-        }
-        m = kept;
-    }
-    res->n_wide = m;
-    if (m == 0) {
-        h->err = "ScanToMapIcp::wideCropped cropped size is zero";   // ScanToMapRegistration.cpp:67
-        return REG_EMPTY_SOURCE;
-    }
-    // 2. VoxelDownSample (helpers.cpp:108-111: voxel_size <= 0 skips it)
-    if (p->voxel_size > 0.0) {
-        double* o[3] = {nullptr, nullptr, nullptr};
-        for (int k = 0; k < 3; ++k)
-            if (cur[k]) {
-                HIPCHK(h, h->sp_b[k].reserve((size_t)m * kSpWidth[k] * 8));
-                o[k] = h->sp_b[k].as<double>();
-            }
-        int64_t n_vox = 0;
-        REGCHK(sp_voxel_device(h, cur[0], cur[1], cur[2], m, p->voxel_size, o[0], o[1], o[2], &n_vox));
-        for (int k = 0; k < 3; ++k) cur[k] = o[k];
-        m = n_vox;
-    }
-    res->n_voxels = m;
-    // 3. estimateNormalsOrCovariancesIfNeeded: a cloud that brings normals keeps them (CloudRegistration.cpp:27,64)
-    if (estimate) {
-        HIPCHK(h, h->sp_f32[0].reserve((size_t)m * 12));
-        HIPCHK(h, h->sp_f32[1].reserve((size_t)m * 12));
-        if (est_cov) HIPCHK(h, h->sp_f32[2].reserve((size_t)m * 24));
-        float *fx = h->sp_f32[0].as<float>(), *fn = h->sp_f32[1].as<float>(), *fc = est_cov ? h->sp_f32[2].as<float>() : nullptr;
-        k_cast_cloud_f64<<<grid_for(m), 256, 0, h->stream>>>(cur[0], nullptr, nullptr, m, fx, nullptr, nullptr);
-        reg_normals_out no;
-        std::memset(&no, 0, sizeof(no));
-        no.normals = fn;
-        no.covs = fc;
-        const float origin[3] = {0.f, 0.f, 0.f};
-        REGCHK(reg_estimate_normals(h, fx, 3, m, 1, p->normal_knn, (float)p->normal_radius, origin, 1, &no, nullptr));
-        HIPCHK(h, h->sp_b[1].reserve((size_t)m * 24));
-        if (est_cov) HIPCHK(h, h->sp_b[2].reserve((size_t)m * 72));
-        double *on = h->sp_b[1].as<double>(), *oc = est_cov ? h->sp_b[2].as<double>() : nullptr;
-        k_sp_widen<<<grid_for(m), 256, 0, h->stream>>>(fn, fc, m, on, oc);
-        cur[1] = on;
-        if (est_cov) cur[2] = oc;
-    }
-    // 4. RandomDownSample (helpers.cpp:100-103: ratio >= 1 skips it)
-    if (p->down_sampling_ratio < 1.0) {
-        const int64_t count = (int64_t)(p->down_sampling_ratio * (double)m);
-        if (count > 0) {
-            REGCHK(sp_random_flags(h, m, count, p->seed));
-            double* o[3] = {nullptr, nullptr, nullptr};
-            for (int k = 0; k < 3; ++k)
-                if (cur[k]) {
-                    HIPCHK(h, h->sp_c[k].reserve((size_t)count * kSpWidth[k] * 8));
-                    o[k] = h->sp_c[k].as<double>();
-                }
-            k_gather_rows<9, true><<<grid_for(m), 256, 0, h->stream>>>(cols64_in(cur[0], cur[1], cur[2]), m,
-                                                                       h->sp.heads.as<uint32_t>(), h->sp.run.as<uint32_t>(),
-                                                                       Cols64{o[0], o[1], o[2]}, nullptr);
-            for (int k = 0; k < 3; ++k) cur[k] = o[k];
-        }
-        m = count;
-    }
+    // 1-4. wide crop (mapBuilderCropper_), voxel grid, normals / covariances, random selection
+    REGCHK(sp_front(h, cur, &m, wide, p->voxel_size, estimate, est_cov, p->normal_knn, p->normal_radius, p->down_sampling_ratio,
+                    p->seed, &res->n_wide, &res->n_voxels));
     res->n_merge = m;
     res->has_normals = cur[1] != nullptr;
     res->has_covs = cur[2] != nullptr;

@@ -1168,6 +1168,7 @@ class RegistrationIcpGeneralized:
         self.max_iteration_ = max_iteration_
         self.relative_fitness_ = 1e-6   # open3d::pipelines::registration::ICPConvergenceCriteria defaults
         self.relative_rmse_ = 1e-6
+        self.epsilon_ = 1e-3            # TransformationEstimationForGeneralizedICP's default
         self._reg = None
 
     def params(self) -> RegParams:
@@ -1183,11 +1184,24 @@ class RegistrationIcpGeneralized:
         p.gicp_rel_rmse = self.relative_rmse_
         return p
 
+    @staticmethod
+    def _needs_covariances(cloud: DataPoints) -> bool:
+        return cloud.covariances is None and cloud.normals is not None
+
+    def _set(self, reg, cloud: DataPoints, setter32, setter64):
+        """A cloud with covariances goes in as before; one with normals only gets the covariances Open3D's GeneralizedICP
+        derives from them (reg_covariances_from_normals, epsilon_), as the reference's clouds do."""
+        if not self._needs_covariances(cloud):
+            return setter32(cloud.features, None, cloud.covariances)
+        x = _xyz64(cloud, "cloud")
+        covs = reg.covariances_from_normals(_field64(cloud.normals, x.shape[0], 3, "normals"), self.epsilon_)
+        return setter64(x, None, covs)
+
     def registerClouds(self, source: DataPoints, target: DataPoints, init=None) -> RegistrationResult:
         reg = capi.Registration(self.params())
         try:
-            reg.set_target(target.features, None, target.covariances)
-            reg.set_source(source.features, None, source.covariances)
+            self._set(reg, target, reg.set_target, reg.set_target_f64)
+            self._set(reg, source, reg.set_source, reg.set_source_f64)
             T, res = reg.register(np.eye(4) if init is None else init)
             ids, _, _ = reg.correspondences(want_w=False)
         except RegError as e:
@@ -2491,5 +2505,109 @@ class ConstantVelocityMotionCompensation:
             self._reg, self._own = _feature_handle(), True   # kept for the next scan; close() frees it
         try:
             return self._reg.undistort_scan(xyz, self.params(timestamp))
+        except RegError as e:
+            raise _translate(e) from None
+
+
+# ---- LidarOdometry (Odometry.cpp) --------------------------------------------------------------------------------
+@dataclass
+class OdometryParameters:
+    """o3d_slam::OdometryParameters (Parameters.hpp:59-86), the fields LidarOdometry reads: scanMatcher_ (regType_ and its
+    IcpParameters), scanProcessing_ (ratio, voxel size, cropper) and useOdometryTopic_.  `cropper_` is a crop dict of
+    capi.Registration.set_target_f64; seed_, gicpEpsilon_ and minFitness_ have no field in the reference (the selection's
+    seed, Open3D's epsilon and the "todo magic" 0.1 of Odometry.cpp:56)."""
+    regType_: object = "PointToPlaneIcp"
+    maxNumIter_: int = 50
+    maxCorrespondenceDistance_: float = 0.2
+    knn_: int = 5
+    maxDistanceKnn_: float = 10.0
+    downSamplingRatio_: float = 1.0
+    voxelSize_: float = 0.03
+    cropper_: dict = field(default_factory=lambda: dict(type=capi.CROP_MAX_RADIUS, radius_min=0.0, radius_max=20.0,
+                                                        min_z=-10.0, max_z=10.0))
+    useOdometryTopic_: bool = True
+    seed_: int = 0
+    gicpEpsilon_: float = 1e-3
+    minFitness_: float = 0.1
+
+
+class LidarOdometry:
+    """o3d_slam::LidarOdometry on the device (capi.Odometry on a handle of its own): the previous cloud never leaves HBM
+    between scans; the pose buffer is the host TransformInterpolationBuffer, pushed into whenever the library says
+    pose_updated.  Times are integer nanoseconds.  close() frees the handle."""
+
+    def __init__(self, params: "OdometryParameters | None" = None):
+        self.odomToRangeSensorBuffer_ = TransformInterpolationBuffer()
+        self._reg = self._odom = None
+        self.setParameters(params if params is not None else OdometryParameters())
+
+    def close(self):
+        if self._odom is not None:
+            self._odom.close()
+        if self._reg is not None:
+            self._reg.close()
+        self._reg = self._odom = None
+
+    def setParameters(self, p: OdometryParameters):
+        """setParameters (Odometry.cpp:104-108): a new cropper and a new operator; the previous cloud and the pose stay in
+        the reference, and here the object starts afresh only before its first scan."""
+        if self._odom is not None and self._odom.info().has_cloud:
+            raise InvalidParameter("LidarOdometry.setParameters after the first scan is not supported: the cloud lives on "
+                                   "the handle of the operator it was made for")
+        self.close()
+        self.params_ = p
+        # cloudRegistrationFactory picks the operator, and with it the configuration of the handle
+        self._operator = cloudRegistrationFactory(p.regType_, p.maxCorrespondenceDistance_, p.maxNumIter_, p.knn_,
+                                                  p.maxDistanceKnn_)
+        estimates = not isinstance(self._operator, RegistrationIcpPointToPoint)
+        self._oparams = capi.default_odometry_params(
+            crop=p.cropper_, voxel_size=p.voxelSize_, down_sampling_ratio=p.downSamplingRatio_, seed=p.seed_,
+            normal_knn=p.knn_ if estimates else 0, normal_radius=p.maxDistanceKnn_, gicp_epsilon=p.gicpEpsilon_,
+            min_fitness=p.minFitness_, use_odometry_topic=int(bool(p.useOdometryTopic_)))
+        if capi.check_odometry_params(self._operator.params(), self._oparams) != 0:
+            raise InvalidParameter("LidarOdometry: parameters refused by reg_check_odometry_params")
+
+    def _ensure(self):
+        if self._odom is None:
+            try:
+                self._reg = capi.Registration(self._operator.params())
+                self._odom = capi.Odometry(self._reg, self._oparams)
+            except RegError as e:
+                raise _translate(e) from None
+        return self._odom
+
+    def addRangeScan(self, cloud, timestamp) -> bool:
+        """addRangeScan (Odometry.cpp:29-84): PointCloud, DataPoints or a bare N x 3 array in the sensor frame."""
+        c = _cloud64(cloud)
+        try:
+            res = self._ensure().add_scan(c.points_, timestamp, c.normals_)
+        except RegError as e:
+            raise _translate(e) from None
+        self.last_result = res
+        if res.pose_updated:
+            self.odomToRangeSensorBuffer_.push(int(timestamp), res.cumulative_matrix())
+        return bool(res.accepted)
+
+    def getOdomToRangeSensor(self, t) -> np.ndarray:
+        return getTransform(t, self.odomToRangeSensorBuffer_)
+
+    def getPreProcessedCloud(self) -> PointCloud:
+        if self._odom is None:
+            return PointCloud(np.empty((0, 3), np.float64))
+        c = self._odom.export_cloud()
+        return PointCloud(c["xyz"], c["normals"], c["covs"])
+
+    def getBuffer(self) -> TransformInterpolationBuffer:
+        return self.odomToRangeSensorBuffer_
+
+    def hasProcessedMeasurements(self) -> bool:
+        return not self.odomToRangeSensorBuffer_.empty()
+
+    def setInitialTransform(self, initialTransform) -> bool:
+        """setInitialTransform (Odometry.cpp:110-126): False while an earlier one is still pending (the reference prints
+        and skips)."""
+        _check_T(initialTransform, "initialTransform")
+        try:
+            return self._ensure().set_initial_transform(initialTransform)
         except RegError as e:
             raise _translate(e) from None
