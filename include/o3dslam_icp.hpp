@@ -1079,4 +1079,110 @@ private:
     bool owns_ = false;
 };
 
+// Open3D's PoseGraph + GlobalOptimization over reg_pose_graph (OptimizationProblem.cpp:25-44).  RAII, move-only,
+// on a caller's registration handle (borrowed; the object must go before it).  Every matrix is ROW-major double: poses and
+// edge transformations 16 per item, information matrices 36.  Parity with Open3D 0.15.1 is unpinned (include/o3dslam_reg.h).
+class PoseGraph {
+public:
+    struct Edge {
+        int32_t source = 0, target = 0;
+        std::array<double, 16> transformation{};
+        std::array<double, 36> information{};
+        bool uncertain = false;
+        double confidence = 1.0;
+    };
+    struct Graph {
+        std::vector<std::array<double, 16>> poses;
+        std::vector<int32_t> source, target, ids;   // ids: the edge's index in the list set() received
+        std::vector<double> confidence;
+    };
+
+    static reg_pose_graph_params defaults() {
+        reg_pose_graph_params p;
+        reg_default_pose_graph_params(&p);
+        return p;
+    }
+    explicit PoseGraph(reg_handle* handle, const reg_pose_graph_params& params = defaults()) : h_(handle) {
+        const reg_status s = reg_pose_graph_create(h_, &params, &g_);
+        if (s != REG_OK) raise(s, h_ ? reg_last_error(h_) : "no handle");
+    }
+    ~PoseGraph() { release(); }
+    PoseGraph(const PoseGraph&) = delete;
+    PoseGraph& operator=(const PoseGraph&) = delete;
+    PoseGraph(PoseGraph&& o) noexcept : h_(o.h_), g_(o.g_) { o.h_ = nullptr, o.g_ = nullptr; }
+    PoseGraph& operator=(PoseGraph&& o) noexcept {
+        if (this != &o) {
+            release();
+            h_ = o.h_, g_ = o.g_;
+            o.h_ = nullptr, o.g_ = nullptr;
+        }
+        return *this;
+    }
+
+    void set(const std::vector<std::array<double, 16>>& poses, const std::vector<Edge>& edges) {
+        const size_t E = edges.size();
+        std::vector<int32_t> src(E), tgt(E), unc(E);
+        std::vector<double> X(E * 16), info(E * 36), conf(E);
+        for (size_t e = 0; e < E; ++e) {
+            src[e] = edges[e].source, tgt[e] = edges[e].target, unc[e] = edges[e].uncertain, conf[e] = edges[e].confidence;
+            std::copy(edges[e].transformation.begin(), edges[e].transformation.end(), X.begin() + 16 * e);
+            std::copy(edges[e].information.begin(), edges[e].information.end(), info.begin() + 36 * e);
+        }
+        check(reg_pose_graph_set(g_, poses.empty() ? nullptr : poses[0].data(), (int64_t)poses.size(), src.data(), tgt.data(),
+                                 X.data(), info.data(), unc.data(), conf.data(), (int64_t)E));
+    }
+    void clear() { check(reg_pose_graph_clear(g_)); }
+    // one Levenberg-Marquardt pass on the graph as it stands
+    reg_pose_graph_result optimize() {
+        reg_pose_graph_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_pose_graph_optimize(g_, &r));
+        return r;
+    }
+    // GlobalOptimization: pass, prune, pass, prune, reference compensation
+    std::array<reg_pose_graph_result, 2> globalOptimize() {
+        std::array<reg_pose_graph_result, 2> r{};
+        r[0].struct_size = r[1].struct_size = (int32_t)sizeof(reg_pose_graph_result);
+        check(reg_pose_graph_global_optimize(g_, r.data()));
+        return r;
+    }
+    reg_pose_graph_info info() const {
+        reg_pose_graph_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_pose_graph_get_info(g_, &i));
+        return i;
+    }
+    // sized from the library's own counts, which the getters check again
+    Graph get() {
+        const reg_pose_graph_info i = info();
+        Graph out;
+        out.poses.resize((size_t)i.n_nodes);
+        out.source.resize((size_t)i.n_edges), out.target.resize((size_t)i.n_edges), out.ids.resize((size_t)i.n_edges);
+        out.confidence.resize((size_t)i.n_edges);
+        int64_t k = 0;
+        check(reg_pose_graph_get(g_, i.n_nodes, out.poses.empty() ? nullptr : out.poses[0].data(), i.n_edges, out.source.data(),
+                                 out.target.data(), out.confidence.data(), &k));
+        if (i.n_edges > 0) check(reg_pose_graph_get_edge_ids(g_, i.n_edges, out.ids.data()));
+        return out;
+    }
+    reg_pose_graph* graph() const { return g_; }
+    reg_handle* handle() const { return h_; }
+
+private:
+    static void raise(reg_status s, const std::string& msg) {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);   // REG_BAD_TRANSFORM: a pivot of the factorisation (the message names its row)
+    }
+    void check(reg_status s) const {
+        if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    void release() {
+        if (g_) reg_pose_graph_destroy(g_);   // the object goes before its handle
+        g_ = nullptr, h_ = nullptr;
+    }
+    reg_handle* h_ = nullptr;
+    reg_pose_graph* g_ = nullptr;
+};
+
 }  // namespace o3dreg

@@ -1674,6 +1674,125 @@ REG_API int32_t reg_host_odometry_decide(int32_t has_previous, int64_t timestamp
      out(i,j) = ((cum(i,0) b0j + cum(i,1) b1j) + cum(i,2) b2j) + cum(i,3) b3j. */
 REG_API reg_status reg_host_odometry_accumulate(double cumulative[16], const float T[16]);
 
+/* ---- Pose-graph optimisation: o3d_slam::OptimizationProblem::solve (OptimizationProblem.cpp:25-44) ----
+   What Open3D's GlobalOptimization does to the pose graph the mapper builds from its constraints: Levenberg-Marquardt with
+   line processes on the uncertain (loop-closure) edges, a prune, a second pass, the compensation of the reference node.
+   Open3D 0.15.1 is not vendored: the text below is the contract, its oracle is tests/pose_graph_restatement.py, and parity
+   with Open3D 0.15.1 is unpinned.  fp64 throughout; every 4 x 4 matrix of this section is ROW-major, every 6 x 6 too.
+   Graph: n_nodes poses; n_edges edges {source, target, X, info, uncertain, confidence}.
+   Products and sums, in this order (one rounding per operation; the build forbids contraction):
+     (A B)(i,j) = ((A(i,0) B(0,j) + A(i,1) B(1,j)) + A(i,2) B(2,j)) + A(i,3) B(3,j), all four rows and columns;
+     rigid inverse of [R | t]: [R^T | t'], t'_i = -((R(0,i) t0 + R(1,i) t1) + R(2,i) t2) (DEPARTURE: Open3D takes Eigen's
+       general 4 x 4 inverse);
+     lin6(M) = [(M21 - M12) 0.5, (M02 - M20) 0.5, (M10 - M01) 0.5, M03, M13, M23];
+     generators G0..G2: rotations about x, y, z (G0(1,2) = -1, G0(2,1) = 1; G1(0,2) = 1, G1(2,0) = -1; G2(0,1) = -1,
+       G2(1,0) = 1), G3..G5: the unit translations in column 3;
+     per edge A = X^-1 Tt^-1; zeta = lin6(A Ts); column k of Js = lin6((A Gk) Ts); column k of Jt = lin6((A (-Gk)) Ts);
+     W = L J with L = info: W(i,c) = sum over j = 0..5 left to right of L(i,j) J(j,c); (J^T W)(a,c) = sum over i left to right
+       of J(i,a) W(i,c); v = L zeta likewise; J^T v likewise; e^T L e = sum over i left to right of zeta_i v_i;
+     H(s,s) += l Js^T L Js, H(s,t) += l Js^T L Jt, H(t,s) += l Jt^T L Js, H(t,t) += l Jt^T L Jt, b(s) -= l Js^T L e,
+       b(t) -= l Jt^T L e with l = confidence, every element summed IN EDGE ORDER from zero, without atomics;
+     line-process weight w = (preference (d d)) (sum of info(5,5) in edge order / n_edges), d = max_correspondence_distance;
+       0 without edges; confidence of an uncertain edge = (w / (w + e^T L e))^2;
+     residual = sum in edge order of l e^T L e + w (sqrt(l) - 1)^2;
+     pose step: pose <- V(d) pose, V(al, be, ga, a, b, c) = [Rz(ga) Ry(be) Rx(al) | (a, b, c)] with
+       V00 = cg cb, V01 = (cg sb) sa - sg ca, V02 = (cg sb) ca + sg sa, V10 = sg cb, V11 = (sg sb) sa + cg ca,
+       V12 = (sg sb) ca - cg sa, V20 = -sb, V21 = cb sa, V22 = cb ca;
+     pose vector (read by the increment test only): sy = sqrt(R00 R00 + R10 R10); sy >= 1e-6: (atan2(R21, R22),
+       atan2(-R20, sy), atan2(R10, R00)), else (atan2(-R12, R11), atan2(-R20, sy), 0); then the translation.
+   One LM pass (reg_pose_graph_optimize): zeta; current = new = residual; confidences; (H, b); lambda = 1e-5 max diag H;
+   nu = 2; stop at once if max b < min_right_term.  Outer iteration iter = 0, 1, ...: lm_count = 0; inner loop: solve
+   (H + lambda I) d = b; stop if |d| < min_relative_increment (|x| + min_relative_increment); trial poses, zeta and residual
+   with the CURRENT confidences; rho = (current - new) / (d . (lambda d + b) + 1e-3); rho > 0: stop if current - new <
+   min_relative_residual_increment current, else lambda *= max(lower, min(upper, 1 - (2 rho - 1)^3)), nu = 2, the trial
+   becomes the state, then x, confidences, (H, b), and stop if the right-term test fires; rho <= 0: lambda *= nu, nu *= 2;
+   lm_count++, stop if lm_count >= max_iteration_lm; repeat until rho > 0 or stop.  After the inner loop: stop if current <
+   min_residual or iter >= max_iteration.
+   reg_pose_graph_global_optimize: pass 1; prune (every certain edge stays, an uncertain one stays when its confidence is
+   above edge_prune_threshold); pass 2 on the pruned graph (the edges keep their confidences); prune; C = pose_before(ref)
+   pose_after(ref)^-1 (rigid inverse), pose <- C pose for every node (skipped when reference_node is out of range).
+   The solver is a dense blocked Cholesky of H + lambda I on the device: its contract is a backward-error bar,
+   and run-to-run bit equality.  A pivot that is not positive and finite: REG_BAD_TRANSFORM, reg_last_error names the row,
+   the graph is left as it was.  Known open point: Open3D is believed to refuse certain edges between non-consecutive
+   nodes; that is not reproduced. */
+#define REG_POSE_GRAPH_MAX_NODES 2048
+typedef struct reg_pose_graph reg_pose_graph;
+typedef struct {
+    int32_t struct_size;                       /* = sizeof(reg_pose_graph_params); checked */
+    int32_t reference_node;                    /* 0 (Parameters.hpp:146); out of range: no compensation */
+    double  max_correspondence_distance;       /* 10.0 (Parameters.hpp:143); finite, >= 0 */
+    double  preference_loop_closure;           /* 2.0 (:144); finite, >= 0 */
+    double  edge_prune_threshold;              /* 0.2 (:145); finite */
+    int32_t max_iteration;                     /* 100; >= 0 */
+    int32_t max_iteration_lm;                  /* 20; >= 1 */
+    double  min_relative_increment;            /* 1e-6 */
+    double  min_relative_residual_increment;   /* 1e-6 */
+    double  min_right_term;                    /* 1e-6 */
+    double  min_residual;                      /* 1e-6 */
+    double  upper_scale_factor;                /* 2/3 */
+    double  lower_scale_factor;                /* 1/3 */
+} reg_pose_graph_params;
+typedef enum {
+    REG_PG_STOP_NONE = 0,
+    REG_PG_STOP_RIGHT_TERM = 1,          /* max b < min_right_term */
+    REG_PG_STOP_INCREMENT = 2,           /* |d| < min_relative_increment (|x| + min_relative_increment) */
+    REG_PG_STOP_RESIDUAL_INCREMENT = 3,  /* current - new < min_relative_residual_increment current */
+    REG_PG_STOP_MAX_ITERATION_LM = 4,    /* lm_count >= max_iteration_lm */
+    REG_PG_STOP_MIN_RESIDUAL = 5,        /* current < min_residual */
+    REG_PG_STOP_MAX_ITERATION = 6        /* iter >= max_iteration */
+} reg_pose_graph_stop;
+typedef struct {
+    int32_t struct_size;       /* = sizeof(reg_pose_graph_result), set by the caller */
+    int32_t outer_iterations;  /* outer iterations entered */
+    int32_t lm_solves;         /* solves of (H + lambda I) d = b */
+    int32_t accepted_steps;    /* steps with rho > 0 that became the state */
+    int32_t stop_reason;       /* reg_pose_graph_stop */
+    int32_t valid_edges;       /* edges with confidence above edge_prune_threshold after the pass */
+    double  first_residual, last_residual, last_lambda, weight;
+} reg_pose_graph_result;
+typedef struct {
+    int32_t struct_size;       /* = sizeof(reg_pose_graph_info), set by the caller */
+    int32_t n_nodes, n_edges, n_uncertain;
+    int64_t solver_rows;       /* rows of the padded factor buffer held (0: none yet) */
+    int64_t device_bytes;      /* device memory the object holds */
+} reg_pose_graph_info;
+REG_API void reg_default_pose_graph_params(reg_pose_graph_params* p);
+/* The validation reg_pose_graph_create runs, without a device. */
+REG_API reg_status reg_check_pose_graph_params(const reg_pose_graph_params* p);
+/* sizeof of reg_pose_graph_params, reg_pose_graph_result, reg_pose_graph_info */
+REG_API void reg_pose_graph_struct_sizes(int32_t sizes[3]);
+REG_API reg_status reg_pose_graph_create(reg_handle* h, const reg_pose_graph_params* params, reg_pose_graph** out);
+REG_API void reg_pose_graph_destroy(reg_pose_graph* g);   /* before reg_destroy of its handle */
+REG_API reg_status reg_pose_graph_clear(reg_pose_graph* g);   /* no nodes, no edges; the device buffers stay */
+/* Replaces the graph (host arrays): poses n_nodes x 16, src / tgt / uncertain n_edges int32, X n_edges x 16, info n_edges x
+   36, confidence n_edges (NULL: all 1).  REG_BAD_ARGUMENT before any device work for 1 <= n_nodes <=
+   REG_POSE_GRAPH_MAX_NODES or n_edges >= 0 violated, an id out of range, source == target, a confidence outside [0, 1],
+   a non-finite entry. */
+REG_API reg_status reg_pose_graph_set(reg_pose_graph* g, const double* poses, int64_t n_nodes, const int32_t* src,
+                                      const int32_t* tgt, const double* X, const double* info, const int32_t* uncertain,
+                                      const double* confidence, int64_t n_edges);
+/* The factor-level hook (as reg_linearize): H (6 n x 6 n, may be NULL), b (6 n), zeta (n_edges x 6), the residual and the
+   line-process weight at the current poses and confidences.  Any output may be NULL. */
+REG_API reg_status reg_pose_graph_linearize(reg_pose_graph* g, double* H, double* b, double* zeta, double* residual,
+                                            double* weight);
+REG_API reg_status reg_pose_graph_optimize(reg_pose_graph* g, reg_pose_graph_result* result);             /* one LM pass */
+REG_API reg_status reg_pose_graph_global_optimize(reg_pose_graph* g, reg_pose_graph_result result[2]);   /* GlobalOptimization */
+/* The graph as it stands: poses (capacity_nodes x 16), src / tgt / confidence (capacity_edges each); any may be NULL.
+   REG_BAD_ARGUMENT, writing nothing, when a capacity is below the rows. */
+REG_API reg_status reg_pose_graph_get(reg_pose_graph* g, int64_t capacity_nodes, double* poses, int64_t capacity_edges,
+                                      int32_t* src, int32_t* tgt, double* confidence, int64_t* n_edges);
+/* For every edge of the graph as it stands its index in the list reg_pose_graph_set received (which edges a prune kept). */
+REG_API reg_status reg_pose_graph_get_edge_ids(reg_pose_graph* g, int64_t capacity_edges, int32_t* ids);
+REG_API reg_status reg_pose_graph_get_info(const reg_pose_graph* g, reg_pose_graph_info* info);
+/* Host-only (no device): one edge's zeta (6), Js, Jt (6 x 6 row-major, either may be NULL); the pose vector; the pose step;
+   the line-process weight of n_edges information matrices (n_edges x 36). */
+REG_API reg_status reg_host_pose_graph_edge(const double Ts[16], const double Tt[16], const double X[16], double zeta[6],
+                                            double Js[36], double Jt[36]);
+REG_API reg_status reg_host_pose_vector(const double T[16], double x[6]);
+REG_API reg_status reg_host_pose_step(const double delta[6], const double pose[16], double out[16]);
+REG_API reg_status reg_host_line_process_weight(const double* info, int64_t n_edges, double preference,
+                                                double max_correspondence_distance, double* weight);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,13 @@ REG_API reg_status reg_debug_halo_witness(reg_handle* h, const float* xyz, int64
  * Counted where a resource is created and where it is destroyed: a handle leaves all four as it found them. */
 REG_API reg_status reg_debug_live_resources(int64_t out[4]);
 
+/* The pose graph's dense solver on a caller's system (tests): A is n x n row-major, symmetric (the lower triangle is read),
+   1 <= n <= 6 * REG_POSE_GRAPH_MAX_NODES; x solves A x = b through the blocked Cholesky of DESIGN.md 5z.  *status = 0, or
+   1 + the row of the first pivot that is not positive and finite; then the return value is REG_BAD_TRANSFORM, x is not
+   written and reg_last_error names the row.  Host arrays. */
+REG_API reg_status reg_debug_spd_solve_f64(reg_handle* h, int64_t n, const double* A, const double* b, double* x,
+                                           int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

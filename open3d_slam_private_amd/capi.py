@@ -366,6 +366,107 @@ def host_undistort_point(p, params: UndistortParams) -> np.ndarray:
     return np.array(out, np.float64)
 
 
+class PoseGraphParams(C.Structure):
+    """reg_pose_graph_params (include/o3dslam_reg.h): GlobalOptimizationOption and GlobalOptimizationConvergenceCriteria."""
+    _fields_ = [("struct_size", C.c_int32), ("reference_node", C.c_int32), ("max_correspondence_distance", C.c_double),
+                ("preference_loop_closure", C.c_double), ("edge_prune_threshold", C.c_double), ("max_iteration", C.c_int32),
+                ("max_iteration_lm", C.c_int32), ("min_relative_increment", C.c_double),
+                ("min_relative_residual_increment", C.c_double), ("min_right_term", C.c_double), ("min_residual", C.c_double),
+                ("upper_scale_factor", C.c_double), ("lower_scale_factor", C.c_double)]
+
+
+class PoseGraphResult(C.Structure):
+    """reg_pose_graph_result (include/o3dslam_reg.h): the statistics of one Levenberg-Marquardt pass."""
+    _fields_ = [("struct_size", C.c_int32), ("outer_iterations", C.c_int32), ("lm_solves", C.c_int32),
+                ("accepted_steps", C.c_int32), ("stop_reason", C.c_int32), ("valid_edges", C.c_int32),
+                ("first_residual", C.c_double), ("last_residual", C.c_double), ("last_lambda", C.c_double),
+                ("weight", C.c_double)]
+
+
+class PoseGraphInfo(C.Structure):
+    """reg_pose_graph_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_nodes", C.c_int32), ("n_edges", C.c_int32), ("n_uncertain", C.c_int32),
+                ("solver_rows", C.c_int64), ("device_bytes", C.c_int64)]
+
+
+POSE_GRAPH_MAX_NODES = 2048   # REG_POSE_GRAPH_MAX_NODES
+PG_STOP_NAMES = {0: "NONE", 1: "RIGHT_TERM", 2: "INCREMENT", 3: "RESIDUAL_INCREMENT", 4: "MAX_ITERATION_LM",
+                 5: "MIN_RESIDUAL", 6: "MAX_ITERATION"}
+
+
+def default_pose_graph_params(**overrides) -> PoseGraphParams:
+    """reg_default_pose_graph_params (Parameters.hpp:142-147 and Open3D's criteria defaults); overrides by field name."""
+    p = PoseGraphParams()
+    load_library().reg_default_pose_graph_params(C.byref(p))
+    for k, v in overrides.items():
+        if k in ("reference_node", "max_iteration", "max_iteration_lm"):
+            setattr(p, k, int(v))
+        elif k != "struct_size" and k in dict(PoseGraphParams._fields_):
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"unknown pose graph parameter {k}")
+    return p
+
+
+def check_pose_graph_params(params: PoseGraphParams) -> int:
+    """reg_check_pose_graph_params: the validation of PoseGraph(), without a device.  Returns the status."""
+    return int(load_library().reg_check_pose_graph_params(C.byref(params)))
+
+
+def pose_graph_struct_sizes() -> tuple:
+    """reg_pose_graph_struct_sizes: sizeof of (reg_pose_graph_params, reg_pose_graph_result, reg_pose_graph_info)."""
+    out = (C.c_int32 * 3)()
+    load_library().reg_pose_graph_struct_sizes(out)
+    return tuple(out)
+
+
+def _rows16(T) -> np.ndarray:
+    a = np.ascontiguousarray(T, np.float64)
+    if a.size != 16:
+        raise ValueError("a 4 x 4 matrix is expected")
+    return a.reshape(16)
+
+
+def host_pose_graph_edge(Ts, Tt, X):
+    """reg_host_pose_graph_edge: (zeta (6), Js, Jt (6 x 6)) of one edge on the host (no device)."""
+    z, Js, Jt = np.empty(6), np.empty((6, 6)), np.empty((6, 6))
+    st = load_library().reg_host_pose_graph_edge(_ptr(_rows16(Ts)), _ptr(_rows16(Tt)), _ptr(_rows16(X)), _ptr(z), _ptr(Js),
+                                                 _ptr(Jt))
+    if st != 0:
+        raise RegError(st, "reg_host_pose_graph_edge")
+    return z, Js, Jt
+
+
+def host_pose_vector(T) -> np.ndarray:
+    """reg_host_pose_vector: (alpha, beta, gamma, x, y, z) of a pose on the host (no device)."""
+    x = np.empty(6)
+    st = load_library().reg_host_pose_vector(_ptr(_rows16(T)), _ptr(x))
+    if st != 0:
+        raise RegError(st, "reg_host_pose_vector")
+    return x
+
+
+def host_pose_step(delta, pose) -> np.ndarray:
+    """reg_host_pose_step: V(delta) pose on the host (no device)."""
+    d = np.ascontiguousarray(delta, np.float64).reshape(6)
+    out = np.empty((4, 4))
+    st = load_library().reg_host_pose_step(_ptr(d), _ptr(_rows16(pose)), _ptr(out))
+    if st != 0:
+        raise RegError(st, "reg_host_pose_step")
+    return out
+
+
+def host_line_process_weight(info, preference, max_correspondence_distance) -> float:
+    """reg_host_line_process_weight of E x 6 x 6 information matrices on the host (no device)."""
+    a = np.ascontiguousarray(info, np.float64).reshape(-1, 36)
+    w = C.c_double(0.0)
+    st = load_library().reg_host_line_process_weight(_ptr(a) if a.shape[0] else None, a.shape[0], float(preference),
+                                                     float(max_correspondence_distance), C.byref(w))
+    if st != 0:
+        raise RegError(st, "reg_host_line_process_weight")
+    return float(w.value)
+
+
 class OdometryParams(C.Structure):
     """reg_odometry_params (include/o3dslam_reg.h): the scan cropper and processing, GICP's epsilon, the fitness gate."""
     _fields_ = [("struct_size", C.c_int32), ("use_odometry_topic", C.c_int32), ("crop", RegCrop), ("voxel_size", C.c_double),
@@ -614,7 +715,12 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_default_odometry_params", "reg_check_odometry_params", "reg_odometry_struct_sizes", "reg_odometry_create",
            "reg_odometry_destroy", "reg_odometry_clear", "reg_odometry_get_info", "reg_odometry_set_initial_transform",
            "reg_odometry_add_scan", "reg_odometry_export_cloud", "reg_odometry_get_correspondences",
-           "reg_host_odometry_decide", "reg_host_odometry_accumulate"]
+           "reg_host_odometry_decide", "reg_host_odometry_accumulate",
+           "reg_default_pose_graph_params", "reg_check_pose_graph_params", "reg_pose_graph_struct_sizes",
+           "reg_pose_graph_create", "reg_pose_graph_destroy", "reg_pose_graph_clear", "reg_pose_graph_set",
+           "reg_pose_graph_linearize", "reg_pose_graph_optimize", "reg_pose_graph_global_optimize", "reg_pose_graph_get",
+           "reg_pose_graph_get_edge_ids", "reg_pose_graph_get_info", "reg_host_pose_graph_edge", "reg_host_pose_vector", "reg_host_pose_step",
+           "reg_host_line_process_weight", "reg_debug_spd_solve_f64"]
 
 
 def lib_path() -> str:
@@ -767,6 +873,27 @@ def load_library():
     lib.reg_host_odometry_decide.argtypes = [C.c_int32, i64, i64, C.c_int32, i64, C.c_double, C.c_double, C.c_int32]
     lib.reg_host_odometry_decide.restype = C.c_int32
     lib.reg_host_odometry_accumulate.argtypes = [pd16, vp]
+    lib.reg_default_pose_graph_params.argtypes = [C.POINTER(PoseGraphParams)]
+    lib.reg_default_pose_graph_params.restype = None
+    lib.reg_check_pose_graph_params.argtypes = [C.POINTER(PoseGraphParams)]
+    lib.reg_pose_graph_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
+    lib.reg_pose_graph_struct_sizes.restype = None
+    lib.reg_pose_graph_create.argtypes = [vp, C.POINTER(PoseGraphParams), C.POINTER(vp)]
+    lib.reg_pose_graph_destroy.argtypes = [vp]
+    lib.reg_pose_graph_destroy.restype = None
+    lib.reg_pose_graph_clear.argtypes = [vp]
+    lib.reg_pose_graph_set.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64]
+    lib.reg_pose_graph_linearize.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.reg_pose_graph_optimize.argtypes = [vp, C.POINTER(PoseGraphResult)]
+    lib.reg_pose_graph_global_optimize.argtypes = [vp, C.POINTER(PoseGraphResult)]
+    lib.reg_pose_graph_get.argtypes = [vp, i64, vp, i64, vp, vp, vp, pi64]
+    lib.reg_pose_graph_get_edge_ids.argtypes = [vp, i64, vp]
+    lib.reg_pose_graph_get_info.argtypes = [vp, C.POINTER(PoseGraphInfo)]
+    lib.reg_host_pose_graph_edge.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.reg_host_pose_vector.argtypes = [vp, vp]
+    lib.reg_host_pose_step.argtypes = [vp, vp, vp]
+    lib.reg_host_line_process_weight.argtypes = [vp, i64, C.c_double, C.c_double, C.POINTER(C.c_double)]
+    lib.reg_debug_spd_solve_f64.argtypes = [vp, i64, vp, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -1158,6 +1285,8 @@ class Registration:
             for m in list(getattr(self, "_map_clouds", ())):   # and so is a reg_map_cloud
                 m.close()
             for m in list(getattr(self, "_odometries", ())):   # and a reg_odometry
+                m.close()
+            for m in list(getattr(self, "_pose_graphs", ())):  # and a reg_pose_graph
                 m.close()
             self._lib.reg_destroy(self._h)
             self._h = C.c_void_p()
@@ -2476,6 +2605,123 @@ class Odometry:
         ids, d2 = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.float32)
         self._check(self._lib.reg_odometry_get_correspondences(self._o, ids.shape[0], _ptr(ids), _ptr(d2)))
         return ids[:n], d2[:n]
+
+
+class PoseGraph:
+    """One pose graph (== one reg_pose_graph) on the handle of `reg`: Open3D's GlobalOptimization as
+    OptimizationProblem::solve runs it.  The graph lives on the host inside the library; a pass uploads it and works on the
+    stream of `reg`; the dense factor buffer is sized on first use and kept.  All matrices are row-major fp64."""
+
+    def __init__(self, reg: "Registration", params: "PoseGraphParams | None" = None):
+        self._lib = load_library()
+        self.reg = reg
+        self._g = C.c_void_p()
+        p = params if params is not None else default_pose_graph_params()
+        p.struct_size = C.sizeof(PoseGraphParams)
+        reg._check(self._lib.reg_pose_graph_create(reg._h, C.byref(p), C.byref(self._g)))
+        self.params = p
+        if not hasattr(reg, "_pose_graphs"):
+            reg._pose_graphs = weakref.WeakSet()
+        reg._pose_graphs.add(self)
+
+    def close(self):
+        if getattr(self, "_g", None) and getattr(self.reg, "_h", None):
+            self._lib.reg_pose_graph_destroy(self._g)
+        self._g = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        self.reg._check(st)
+
+    def set(self, poses, src, tgt, X, info, uncertain, confidence=None):
+        """poses n x 4 x 4; per edge source and target ids, X (4 x 4), info (6 x 6), uncertain, confidence (None: 1)."""
+        P = np.ascontiguousarray(poses, np.float64).reshape(-1, 16)
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        t = np.ascontiguousarray(tgt, np.int32).reshape(-1)
+        E = s.shape[0]
+        Xa = np.ascontiguousarray(X, np.float64).reshape(E, 16)
+        Ia = np.ascontiguousarray(info, np.float64).reshape(E, 36)
+        u = np.ascontiguousarray(np.asarray(uncertain).astype(bool), np.int32).reshape(E)
+        c = np.ascontiguousarray(confidence, np.float64).reshape(E) if confidence is not None else None
+        if t.shape[0] != E:
+            raise ValueError("src and tgt differ in length")
+        e = lambda a: _ptr(a) if E else None
+        self._check(self._lib.reg_pose_graph_set(self._g, _ptr(P), P.shape[0], e(s), e(t), e(Xa), e(Ia), e(u),
+                                                 e(c) if c is not None else None, E))
+
+    def clear(self):
+        self._check(self._lib.reg_pose_graph_clear(self._g))
+
+    def info(self) -> PoseGraphInfo:
+        i = PoseGraphInfo()
+        i.struct_size = C.sizeof(PoseGraphInfo)
+        self._check(self._lib.reg_pose_graph_get_info(self._g, C.byref(i)))
+        return i
+
+    def linearize(self, want_H=True):
+        """reg_pose_graph_linearize at the current poses and confidences: dict(H, b, zeta, residual, weight)."""
+        i = self.info()
+        M, E = 6 * int(i.n_nodes), int(i.n_edges)
+        H = np.empty((M, M)) if want_H else None
+        b, zeta = np.empty(M), np.empty((max(E, 1), 6))
+        r, w = C.c_double(0.0), C.c_double(0.0)
+        self._check(self._lib.reg_pose_graph_linearize(self._g, _ptr(H), _ptr(b), _ptr(zeta), C.byref(r), C.byref(w)))
+        return dict(H=H, b=b, zeta=zeta[:E], residual=float(r.value), weight=float(w.value))
+
+    def optimize(self) -> PoseGraphResult:
+        """One Levenberg-Marquardt pass on the graph as it stands."""
+        res = PoseGraphResult()
+        res.struct_size = C.sizeof(PoseGraphResult)
+        self._check(self._lib.reg_pose_graph_optimize(self._g, C.byref(res)))
+        return res
+
+    def global_optimize(self):
+        """GlobalOptimization: pass, prune, pass, prune, reference compensation.  Returns the two passes' results."""
+        res = (PoseGraphResult * 2)()
+        for r in res:
+            r.struct_size = C.sizeof(PoseGraphResult)
+        self._check(self._lib.reg_pose_graph_global_optimize(self._g, res))
+        return [res[0], res[1]]
+
+    def get(self):
+        """dict(poses n x 4 x 4, src, tgt, confidence, ids) of the graph as it stands; ids: every edge's index in the list
+        set() received."""
+        i = self.info()
+        n, E = int(i.n_nodes), int(i.n_edges)
+        P = np.empty((max(n, 1), 4, 4))
+        s, t, c = np.empty(max(E, 1), np.int32), np.empty(max(E, 1), np.int32), np.empty(max(E, 1))
+        k = C.c_int64(0)
+        self._check(self._lib.reg_pose_graph_get(self._g, P.shape[0], _ptr(P), s.shape[0], _ptr(s), _ptr(t), _ptr(c),
+                                                 C.byref(k)))
+        ids = np.empty(max(E, 1), np.int32)
+        self._check(self._lib.reg_pose_graph_get_edge_ids(self._g, ids.shape[0], _ptr(ids)))
+        E = int(k.value)
+        return dict(poses=P[:n], src=s[:E], tgt=t[:E], confidence=c[:E], ids=ids[:E])
+
+
+def debug_spd_solve(reg: "Registration", A, b):
+    """reg_debug_spd_solve_f64: (x, status) of the pose graph's dense solver on A x = b; x is None when a pivot fails
+    (status = 1 + its row)."""
+    A = np.ascontiguousarray(A, np.float64)
+    b = np.ascontiguousarray(b, np.float64).reshape(-1)
+    x = np.empty_like(b)
+    status = C.c_int32(0)
+    st = load_library().reg_debug_spd_solve_f64(reg._h, b.shape[0], _ptr(A), _ptr(b), _ptr(x), C.byref(status))
+    if st == 4:   # REG_BAD_TRANSFORM: a pivot
+        return None, int(status.value)
+    reg._check(st)
+    return x, int(status.value)
 
 
 def dist_unique_id() -> bytes:

@@ -1168,4 +1168,179 @@ O3D_HD inline void odometry_accumulate(double* cum, const double* T) {
     for (int k = 0; k < 16; ++k) cum[k] = P[k];
 }
 
+// ---- pose graph (the order of every product and sum is written out in include/o3dslam_reg.h) ----
+// All 4x4 matrices row-major fp64.  C = A B, every entry ((a0 b0 + a1 b1) + a2 b2) + a3 b3 over k; C may not alias A or B.
+O3D_HD inline void pg_mul(const double* A, const double* B, double* C) {
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double r = A[4 * i] * B[j];
+            r = r + A[4 * i + 1] * B[4 + j];
+            r = r + A[4 * i + 2] * B[8 + j];
+            r = r + A[4 * i + 3] * B[12 + j];
+            C[4 * i + j] = r;
+        }
+}
+
+// The rigid inverse (R^T, -R^T t): t'_i = -(((R0i t0) + R1i t1) + R2i t2); last row 0 0 0 1
+O3D_HD inline void pg_rigid_inverse(const double* T, double* O) {
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) O[4 * i + j] = T[4 * j + i];
+        double r = T[i] * T[3];
+        r = r + T[4 + i] * T[7];
+        r = r + T[8 + i] * T[11];
+        O[4 * i + 3] = -r;
+    }
+    O[12] = O[13] = O[14] = 0.0;
+    O[15] = 1.0;
+}
+
+O3D_HD inline void pg_lin6(const double* M, double* v) {
+    v[0] = (M[9] - M[6]) * 0.5;
+    v[1] = (M[2] - M[8]) * 0.5;
+    v[2] = (M[4] - M[1]) * 0.5;
+    v[3] = M[3];
+    v[4] = M[7];
+    v[5] = M[11];
+}
+
+// Generator k (0..2: rotation about x, y, z; 3..5: unit translation), times sign
+O3D_HD inline void pg_generator(int k, double sign, double* G) {
+    for (int i = 0; i < 16; ++i) G[i] = 0.0;
+    if (k == 0) G[6] = -sign, G[9] = sign;
+    else if (k == 1) G[2] = sign, G[8] = -sign;
+    else if (k == 2) G[1] = -sign, G[4] = sign;
+    else G[4 * (k - 3) + 3] = sign;
+}
+
+// One edge: A = X^-1 Tt^-1; zeta = lin6(A Ts); column k of Js = lin6((A Gk) Ts), of Jt = lin6((A (-Gk)) Ts).
+// Js, Jt: 6 x 6 row-major (row = component of zeta, column = k); either may be null.
+O3D_HD inline void pg_edge(const double* Ts, const double* Tt, const double* X, double* zeta, double* Js, double* Jt) {
+    double Xi[16], Tti[16], A[16], M[16], G[16], AG[16], v[6];
+    pg_rigid_inverse(X, Xi);
+    pg_rigid_inverse(Tt, Tti);
+    pg_mul(Xi, Tti, A);
+    pg_mul(A, Ts, M);
+    pg_lin6(M, zeta);
+    for (int side = 0; side < 2; ++side) {
+        double* J = side ? Jt : Js;
+        if (!J) continue;
+        for (int k = 0; k < 6; ++k) {
+            pg_generator(k, side ? -1.0 : 1.0, G);
+            pg_mul(A, G, AG);
+            pg_mul(AG, Ts, M);
+            pg_lin6(M, v);
+            for (int i = 0; i < 6; ++i) J[6 * i + k] = v[i];
+        }
+    }
+}
+
+// out = A^T B over 6 x 6 row-major blocks, every entry summed left to right over the row index
+O3D_HD inline void pg_atb6(const double* A, const double* B, double* out) {
+    for (int a = 0; a < 6; ++a)
+        for (int c = 0; c < 6; ++c) {
+            double r = A[a] * B[c];
+            for (int i = 1; i < 6; ++i) r = r + A[6 * i + a] * B[6 * i + c];
+            out[6 * a + c] = r;
+        }
+}
+
+// The record of one edge (kPgRec doubles): Js^T L Js, Js^T L Jt, Jt^T L Js, Jt^T L Jt (36 each), Js^T L e, Jt^T L e (6 each)
+// with L = info; W = L J first (rows left to right over the column of L), then J^T W.  Returns e^T L e = sum e_i (L e)_i.
+constexpr int kPgRec = 4 * 36 + 12;
+O3D_HD inline double pg_edge_record(const double* Ts, const double* Tt, const double* X, const double* info, double* zeta,
+                                    double* rec) {
+    double Js[36], Jt[36], Ws[36], Wt[36], v[6];
+    pg_edge(Ts, Tt, X, zeta, Js, Jt);
+    for (int i = 0; i < 6; ++i) {
+        for (int c = 0; c < 6; ++c) {
+            double rs = info[6 * i] * Js[c], rt = info[6 * i] * Jt[c];
+            for (int j = 1; j < 6; ++j) {
+                rs = rs + info[6 * i + j] * Js[6 * j + c];
+                rt = rt + info[6 * i + j] * Jt[6 * j + c];
+            }
+            Ws[6 * i + c] = rs;
+            Wt[6 * i + c] = rt;
+        }
+        double r = info[6 * i] * zeta[0];
+        for (int j = 1; j < 6; ++j) r = r + info[6 * i + j] * zeta[j];
+        v[i] = r;
+    }
+    if (rec) {
+        pg_atb6(Js, Ws, rec);
+        pg_atb6(Js, Wt, rec + 36);
+        pg_atb6(Jt, Ws, rec + 72);
+        pg_atb6(Jt, Wt, rec + 108);
+        for (int a = 0; a < 6; ++a) {
+            double rs = Js[a] * v[0], rt = Jt[a] * v[0];
+            for (int i = 1; i < 6; ++i) {
+                rs = rs + Js[6 * i + a] * v[i];
+                rt = rt + Jt[6 * i + a] * v[i];
+            }
+            rec[144 + a] = rs;
+            rec[150 + a] = rt;
+        }
+    }
+    double q = zeta[0] * v[0];
+    for (int i = 1; i < 6; ++i) q = q + zeta[i] * v[i];
+    return q;
+}
+
+// e^T L e alone (the trial step), the same order as pg_edge_record
+O3D_HD inline double pg_edge_cost(const double* Ts, const double* Tt, const double* X, const double* info, double* zeta) {
+    pg_edge(Ts, Tt, X, zeta, nullptr, nullptr);
+    double q = 0.0;
+    for (int i = 0; i < 6; ++i) {
+        double r = info[6 * i] * zeta[0];
+        for (int j = 1; j < 6; ++j) r = r + info[6 * i + j] * zeta[j];
+        q = i ? q + zeta[i] * r : zeta[i] * r;
+    }
+    return q;
+}
+
+// pose <- V(d) pose, V(al, be, ga, a, b, c) = [Rz(ga) Ry(be) Rx(al) | (a, b, c)]
+O3D_HD inline void pg_pose_step(const double* d, const double* pose, double* out) {
+    const double sa = sin(d[0]), ca = cos(d[0]), sb = sin(d[1]), cb = cos(d[1]), sg = sin(d[2]), cg = cos(d[2]);
+    double V[16];
+    V[0] = cg * cb;
+    V[1] = (cg * sb) * sa - sg * ca;
+    V[2] = (cg * sb) * ca + sg * sa;
+    V[3] = d[3];
+    V[4] = sg * cb;
+    V[5] = (sg * sb) * sa + cg * ca;
+    V[6] = (sg * sb) * ca - cg * sa;
+    V[7] = d[4];
+    V[8] = -sb;
+    V[9] = cb * sa;
+    V[10] = cb * ca;
+    V[11] = d[5];
+    V[12] = V[13] = V[14] = 0.0;
+    V[15] = 1.0;
+    pg_mul(V, pose, out);
+}
+
+// The pose vector (only the increment test reads it): the inverse map of V
+O3D_HD inline void pg_pose_vector(const double* T, double* x) {
+    const double sy = sqrt(T[0] * T[0] + T[4] * T[4]);
+    if (sy >= 1e-6) {
+        x[0] = atan2(T[9], T[10]);
+        x[1] = atan2(-T[8], sy);
+        x[2] = atan2(T[4], T[0]);
+    } else {
+        x[0] = atan2(-T[6], T[5]);
+        x[1] = atan2(-T[8], sy);
+        x[2] = 0.0;
+    }
+    x[3] = T[3];
+    x[4] = T[7];
+    x[5] = T[11];
+}
+
+// w = (preference * (d * d)) * (sum of info(5,5) in edge order / n); 0 for no edges
+O3D_HD inline double pg_line_process_weight(const double* info55, long long n, long long stride, double preference, double d) {
+    if (n <= 0) return 0.0;
+    double s = 0.0;
+    for (long long e = 0; e < n; ++e) s = s + info55[e * stride];
+    return (preference * (d * d)) * (s / (double)n);
+}
+
 }  // namespace o3dreg

@@ -60,6 +60,7 @@ using namespace o3dreg;
 #include "kernels_densemap.hpp"
 #include "kernels_mapcloud.hpp"
 #include "kernels_odometry.hpp"
+#include "kernels_posegraph.hpp"
 
 // host side: one handle = one non-re-entrant registration context (include/o3dslam_reg.h)
 #include "host_mem.hpp"
@@ -81,6 +82,7 @@ using namespace o3dreg;
 #include "host_densemap.hpp"
 #include "host_mapcloud.hpp"
 #include "host_odometry.hpp"
+#include "host_posegraph.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -22,6 +22,8 @@
                                    (TransformInterpolationBuffer.cpp, Transform.cpp:16-67); host arithmetic
   ConstantVelocityMotionCompensation <-> the class of the same name (MotionCompensation.cpp:30-139); the velocity estimate
                                    is host arithmetic, the undistortion runs on the device
+  OptimizationProblem, GlobalOptimization, transformSubmaps <-> o3d_slam::OptimizationProblem (OptimizationProblem.cpp),
+                                   Open3D's GlobalOptimization and SubmapCollection::transform (SubmapCollection.cpp:322-373)
 
 Same method names, argument meaning and error behaviour (exceptions named after the reference's);
 all compute goes through the C ABI (capi.Registration) to the HIP kernels -- nothing is computed here.
@@ -2611,3 +2613,223 @@ class LidarOdometry:
             return self._ensure().set_initial_transform(initialTransform)
         except RegError as e:
             raise _translate(e) from None
+
+
+# ---- pose-graph optimisation: Open3D's GlobalOptimization as OptimizationProblem::solve runs it (OptimizationProblem.cpp,
+#      SubmapCollection.cpp:322-373).  Parity with Open3D 0.15.1 is unpinned: the contract is the text of
+#      include/o3dslam_reg.h ----------------------------------------------------------------------------------------------
+@dataclass
+class GlobalOptimizationOption:
+    """open3d::pipelines::registration::GlobalOptimizationOption with the mapper's values (Parameters.hpp:142-147)."""
+    max_correspondence_distance: float = 10.0
+    edge_prune_threshold: float = 0.2
+    preference_loop_closure: float = 2.0
+    reference_node: int = 0
+
+
+@dataclass
+class GlobalOptimizationConvergenceCriteria:
+    """open3d::pipelines::registration::GlobalOptimizationConvergenceCriteria, Open3D's defaults."""
+    max_iteration: int = 100
+    min_relative_increment: float = 1e-6
+    min_relative_residual_increment: float = 1e-6
+    min_right_term: float = 1e-6
+    min_residual: float = 1e-6
+    max_iteration_lm: int = 20
+    upper_scale_factor: float = 2.0 / 3.0
+    lower_scale_factor: float = 1.0 / 3.0
+
+
+@dataclass
+class PoseGraphNode:
+    pose_: np.ndarray = field(default_factory=lambda: np.eye(4))
+
+
+@dataclass
+class PoseGraphEdge:
+    source_node_id_: int = -1
+    target_node_id_: int = -1
+    transformation_: np.ndarray = field(default_factory=lambda: np.eye(4))
+    information_: np.ndarray = field(default_factory=lambda: np.eye(6))
+    uncertain_: bool = False
+    confidence_: float = 1.0
+
+
+class PoseGraph:
+    """open3d::pipelines::registration::PoseGraph: nodes_ and edges_."""
+
+    def __init__(self, nodes=None, edges=None):
+        self.nodes_ = list(nodes) if nodes is not None else []
+        self.edges_ = list(edges) if edges is not None else []
+
+    def copy(self) -> "PoseGraph":
+        return PoseGraph([PoseGraphNode(np.array(n.pose_, np.float64)) for n in self.nodes_],
+                         [PoseGraphEdge(e.source_node_id_, e.target_node_id_, np.array(e.transformation_, np.float64),
+                                        np.array(e.information_, np.float64), bool(e.uncertain_), float(e.confidence_))
+                          for e in self.edges_])
+
+
+def _pose_graph_params(option, criteria) -> "capi.PoseGraphParams":
+    o = option if option is not None else GlobalOptimizationOption()
+    c = criteria if criteria is not None else GlobalOptimizationConvergenceCriteria()
+    for name, v in list(vars(o).items()) + list(vars(c).items()):
+        if not (_is_real(v) and math.isfinite(v)):
+            raise InvalidParameter(f"{name} must be a finite number, got {v!r}")
+    p = capi.default_pose_graph_params(**vars(o), **vars(c))
+    if capi.check_pose_graph_params(p) != 0:
+        raise InvalidParameter("GlobalOptimization: a negative distance, preference or max_iteration, max_iteration_lm < 1, or "
+                               "scale factors that are not 0 < lower <= upper")
+    return p
+
+
+def GlobalOptimization(pose_graph: PoseGraph, method=None, criteria=None, option=None, reg: "capi.Registration | None" = None):
+    """open3d::pipelines::registration::GlobalOptimization on the device, in place on pose_graph: both Levenberg-Marquardt
+    passes, the prunes and the reference compensation (`method` is accepted for the signature; Levenberg-Marquardt is the
+    one the mapper uses and the one built).  Returns the two passes' capi.PoseGraphResult."""
+    params = _pose_graph_params(option, criteria)
+    n, edges = len(pose_graph.nodes_), pose_graph.edges_
+    if n == 0:
+        raise InvalidParameter("GlobalOptimization: the pose graph has no nodes")
+    own = reg is None
+    reg = reg if reg is not None else _feature_handle()
+    try:
+        with capi.PoseGraph(reg, params) as g:
+            g.set(np.stack([_check_T(x.pose_, "pose_") for x in pose_graph.nodes_]),
+                  [e.source_node_id_ for e in edges], [e.target_node_id_ for e in edges],
+                  np.stack([_check_T(e.transformation_, "transformation_") for e in edges]) if edges else np.zeros((0, 4, 4)),
+                  np.stack([np.asarray(e.information_, np.float64).reshape(6, 6) for e in edges]) if edges else np.zeros((0, 6, 6)),
+                  [bool(e.uncertain_) for e in edges], [float(e.confidence_) for e in edges])
+            res = g.global_optimize()
+            out = g.get()
+    except RegError as e:
+        raise _translate(e) from None
+    finally:
+        if own:
+            reg.close()
+    kept = []
+    for k, c in zip(out["ids"], out["confidence"]):
+        e = edges[int(k)]
+        kept.append(PoseGraphEdge(e.source_node_id_, e.target_node_id_, e.transformation_, e.information_, e.uncertain_, float(c)))
+    pose_graph.nodes_ = [PoseGraphNode(out["poses"][i].copy()) for i in range(n)]
+    pose_graph.edges_ = kept
+    return res
+
+
+class OptimizationProblem:
+    """o3d_slam::OptimizationProblem (OptimizationProblem.cpp): collects icp.Constraint objects as buildConstraint and
+    refineLoopClosure produce them, builds the pose graph and solves it on the device.  Two oddities of the reference:
+    its sort of the odometry constraints compares source with the OTHER constraint's target (line 67), which is no strict
+    weak order; restated as a stable sort by source index.  getOptimizedTransformIncrements returns the optimised pose
+    itself, not a difference (lines 195-198); reproduced."""
+
+    def __init__(self, option: "GlobalOptimizationOption | None" = None, reg: "capi.Registration | None" = None):
+        self.option_ = option if option is not None else GlobalOptimizationOption()
+        self._reg = reg
+        self.odometryConstraints_, self.loopClosureConstraints_ = [], []
+        self.poseGraph_, self.poseGraphOptimized_, self.poseGraphNonOptimized_ = PoseGraph(), PoseGraph(), PoseGraph()
+        self.numOdometryEdgesPrev_ = 0
+        self.lastResults_ = None
+
+    def close(self):
+        self._reg = None
+
+    def setParameters(self, option: GlobalOptimizationOption):
+        self.option_ = option
+
+    def addOdometryConstraint(self, c: Constraint):
+        self.odometryConstraints_.append(c)
+
+    def addLoopClosureConstraint(self, c: Constraint):
+        self.loopClosureConstraints_.append(c)
+
+    def insertOdometryConstraints(self, cs):
+        self.odometryConstraints_.extend(cs)
+
+    def insertLoopClosureConstraints(self, cs):
+        """A constraint between a pair of submaps that already has one is dropped (lines 177-189)."""
+        for c in cs:
+            if not any(c.sourceSubmapIdx_ == k.sourceSubmapIdx_ and c.targetSubmapIdx_ == k.targetSubmapIdx_
+                       for k in self.loopClosureConstraints_):
+                self.loopClosureConstraints_.append(c)
+
+    def clearOdometryConstraints(self):
+        self.odometryConstraints_.clear()
+
+    def clearLoopClosureConstraints(self):
+        self.loopClosureConstraints_.clear()
+
+    def getLoopClosureConstraints(self):
+        return self.loopClosureConstraints_
+
+    def updateLoopClosureConstraint(self, idx: int, c: Constraint):
+        if not 0 <= idx < len(self.loopClosureConstraints_):
+            raise IndexError(f"loop closure constraint {idx} of {len(self.loopClosureConstraints_)}")   # vector::at
+        self.loopClosureConstraints_[idx] = c
+
+    def buildOptimizationProblem(self, submaps=None):
+        """setupOdometryEdgesAndPoseGraphNodes + setupLoopClosureEdges (lines 50-121); `submaps` is unused, as there."""
+        g = self.poseGraph_
+        g.edges_ = []
+        self.odometryConstraints_.sort(key=lambda c: c.sourceSubmapIdx_)   # stable
+        for c in self.odometryConstraints_:
+            if not c.targetSubmapIdx_ > c.sourceSubmapIdx_:
+                raise InvalidParameter("id_source should always be less than id_target for the odometry constraints")
+            g.edges_.append(PoseGraphEdge(c.sourceSubmapIdx_, c.targetSubmapIdx_, np.array(c.sourceToTarget_, np.float64),
+                                          np.array(c.informationMatrix_, np.float64), False))
+        if len(self.poseGraphOptimized_.edges_) > 0:
+            odometry = np.linalg.inv(self.poseGraphOptimized_.nodes_[-1].pose_)
+        else:
+            g.nodes_.append(PoseGraphNode(np.eye(4)))
+            odometry = np.eye(4)
+        for c in self.odometryConstraints_[self.numOdometryEdgesPrev_:]:
+            odometry = np.asarray(c.sourceToTarget_, np.float64) @ odometry
+            g.nodes_.append(PoseGraphNode(np.linalg.inv(odometry)))
+        self.numOdometryEdgesPrev_ = len(self.odometryConstraints_)
+        for c in self.loopClosureConstraints_:
+            if not c.isInformationMatrixValid_:
+                raise InvalidParameter(f"Invalid information matrix between: {c.sourceSubmapIdx_} and {c.targetSubmapIdx_}")
+            if not c.sourceSubmapIdx_ > c.targetSubmapIdx_:
+                raise InvalidParameter("Optimization problem, loop closure constraints: source must be greater than target")
+            g.edges_.append(PoseGraphEdge(c.sourceSubmapIdx_, c.targetSubmapIdx_, np.array(c.sourceToTarget_, np.float64),
+                                          np.array(c.informationMatrix_, np.float64), True))
+
+    def solve(self):
+        """OptimizationProblem::solve (lines 25-44): GlobalOptimization with the criteria's defaults and this option."""
+        self.poseGraphNonOptimized_ = self.poseGraph_.copy()
+        self.lastResults_ = GlobalOptimization(self.poseGraph_, None, GlobalOptimizationConvergenceCriteria(), self.option_,
+                                               reg=self._reg)
+        self.poseGraphOptimized_ = self.poseGraph_.copy()
+        return self.lastResults_
+
+    def getOptimizedTransformIncrements(self):
+        """[(dT_, submapId_)]: dT_ is the optimised pose itself (the reference's oddity)."""
+        if len(self.poseGraphOptimized_.nodes_) != len(self.poseGraph_.nodes_):
+            raise InvalidParameter("Graphs are not of same size, did you run the optimization?")
+        return [(np.array(n.pose_, np.float64), i) for i, n in enumerate(self.poseGraphOptimized_.nodes_)]
+
+
+def _apply_submap_transform(submap, T):
+    submap.transform(T)
+
+
+def transformSubmaps(submaps, parentIds, increments):
+    """SubmapCollection::transform (SubmapCollection.cpp:322-373): every submap named by an increment moves by it; every other
+    submap moves by the increment of the first ancestor (parentIds[i] = the parent of submap i) that is in the graph.
+    A submap that is its own parent and not in the graph: RuntimeError("Stuck in a loop, this should not happen").  Runs on
+    Submap.transform (reg_map_cloud_transform / reg_dense_map_transform): no kernel of its own."""
+    increments = list(increments)
+    optimized = []
+    for T, idx in increments:
+        if 0 <= idx < len(submaps):
+            _apply_submap_transform(submaps[idx], T)
+            optimized.append(idx)
+    missing = [i for i in range(len(submaps)) if i not in set(optimized)]
+    for idx in missing:
+        current = idx
+        while increments:
+            current = parentIds[current]
+            if current not in missing:   # the parent is in the pose graph
+                _apply_submap_transform(submaps[idx], increments[current][0])   # transformIncrements.at(currentNode)
+                break
+            if current == parentIds[current]:
+                raise RuntimeError("Stuck in a loop, this should not happen")
