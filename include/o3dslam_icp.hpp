@@ -1185,4 +1185,361 @@ private:
     reg_pose_graph* g_ = nullptr;
 };
 
+// One submap collection (== one reg_submaps; o3d_slam::SubmapCollection) on the caller's handle, which must
+// outlive it: every submap's map cloud, its occupancy keys and the overlap ring stay on the device; the switching state
+// machine, the queues and the adjacency matrix live on the host inside the library.  Clouds are Open3D's fp64 arrays in host
+// memory unless onDevice is set; transforms are column-major double[16]; stamps are nanoseconds.  The contract of every call
+// is the header's text (include/o3dslam_reg.h).
+class SubmapCollection {
+public:
+    struct Stamped { int32_t submapId; int64_t stampNs; };
+
+    SubmapCollection(reg_handle* handle, const reg_submaps_params& params) : h_(handle), prm_(params) {
+        const reg_status s = reg_submaps_create(h_, &params, &s_);
+        if (s != REG_OK) raise(s, h_ ? reg_last_error(h_) : "no handle");
+    }
+    ~SubmapCollection() { if (s_) reg_submaps_destroy(s_); }   // before its handle
+    SubmapCollection(const SubmapCollection&) = delete;
+    SubmapCollection& operator=(const SubmapCollection&) = delete;
+
+    void setMapToRangeSensor(const double T[16]) { check(reg_submaps_set_map_to_sensor(s_, T)); }
+    // SubmapCollection::insertScan (SubmapCollection.cpp:189-245)
+    reg_submaps_insert_result insertScan(const double* rawScan, int64_t nRaw, const double* points, const double* normals,
+                                         const double* covariances, int64_t n, const double mapToRangeSensor[16], int64_t stampNs,
+                                         bool onDevice = false) {
+        reg_submaps_insert_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_submaps_insert_scan(s_, rawScan, nRaw, points, normals, covariances, n, onDevice ? 1 : 0, mapToRangeSensor,
+                                      stampNs, &r));
+        return r;
+    }
+    reg_submaps_insert_result forceNewSubmapCreation() {
+        reg_submaps_insert_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_submaps_force_new_submap(s_, &r));
+        return r;
+    }
+    // Submap::computeFeatures on the device from the resident map: the gate, the sparse cloud with its normals, its FPFH
+    // features (n x 33) and the occupancy set; `ran` is false when the gate held (then nothing is handed out)
+    struct Features {
+        bool ran = false;
+        std::vector<float> points, normals;
+        std::vector<double> fpfh;
+    };
+    Features computeFeatures(int32_t submapId, double nowSeconds, const reg_submap_feature_params& params) {
+        const size_t cap = (size_t)std::max<int64_t>(submapInfo(submapId).n_rows, 1);
+        Features f;
+        f.points.resize(cap * 3), f.normals.resize(cap * 3), f.fpfh.resize(cap * 33);
+        int64_t n = 0;
+        int32_t done = 0;
+        check(reg_submaps_compute_features(s_, submapId, nowSeconds, &params, 0, f.points.data(), f.normals.data(), f.fpfh.data(),
+                                           (int64_t)cap, &n, &done));
+        f.ran = done != 0;
+        f.points.resize((size_t)n * 3), f.normals.resize((size_t)n * 3), f.fpfh.resize((size_t)n * 33);
+        return f;
+    }
+    // the gate and the occupancy set only; true when it ran
+    bool computeFeatures(int32_t submapId, double nowSeconds) {
+        int32_t done = 0;
+        check(reg_submaps_compute_features(s_, submapId, nowSeconds, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, &done));
+        return done != 0;
+    }
+    bool isActiveSubmapEmpty() const { return submapInfo(info().active).n_rows == 0; }
+    // cropSubmap + initReference of the active submap on handle(); returns the rows of the patch, 0 for an empty map or patch
+    // (REG_EMPTY_TARGET: initReference returns false)
+    int64_t setAsReference(const reg_crop* crop) {
+        int64_t kept = 0;
+        const reg_status st = reg_submaps_set_target(s_, crop, &kept);
+        if (st == REG_EMPTY_TARGET) return 0;
+        check(st);
+        return kept;
+    }
+    void transform(const std::vector<int32_t>& ids, const std::vector<double>& dT) {
+        if (dT.size() != ids.size() * 16) throw InvalidParameter("transform: dT must hold 16 doubles per id");
+        check(reg_submaps_transform(s_, ids.data(), dT.data(), (int32_t)ids.size()));
+    }
+    void updateAdjacencyMatrix(const std::vector<int32_t>& source, const std::vector<int32_t>& target) {
+        if (source.size() != target.size()) throw InvalidParameter("updateAdjacencyMatrix: one target per source");
+        check(reg_submaps_add_loop_closure_edges(s_, source.data(), target.data(), (int32_t)source.size()));
+    }
+    std::vector<Stamped> popFinishedSubmapIds() { return pop(reg_submaps_pop_finished, info().n_finished); }
+    std::vector<Stamped> popLoopClosureCandidates() {
+        return pop(reg_submaps_pop_loop_closure_candidates, info().n_loop_closure_candidates);
+    }
+    void pushLoopClosureCandidate(int32_t submapId, int64_t stampNs) {
+        check(reg_submaps_push_loop_closure_candidate(s_, submapId, stampNs));
+    }
+    std::vector<int32_t> getLoopClosureCandidatesIdxs(int32_t lastFinishedSubmapIdx) const {
+        std::vector<int32_t> out((size_t)info().n_submaps);
+        int32_t n = 0;
+        check(reg_submaps_loop_closure_candidates(s_, lastFinishedSubmapIdx, out.data(), (int32_t)out.size(), &n));
+        out.resize((size_t)n);
+        return out;
+    }
+    // Mapper::getAssembledMapPointCloud
+    MapCloud::Cloud getAssembledMapPointCloud() {
+        MapCloud::Cloud out;
+        const int64_t rows = info().total_points;
+        out.points.resize((size_t)rows * 3);
+        if (prm_.map.has_normals) out.normals.resize((size_t)rows * 3);
+        if (prm_.map.has_covariances) out.covariances.resize((size_t)rows * 9);
+        int64_t k = 0;
+        check(reg_submaps_export(s_, 0, out.points.data(), prm_.map.has_normals ? out.normals.data() : nullptr,
+                                 prm_.map.has_covariances ? out.covariances.data() : nullptr, rows, &k));
+        return out;
+    }
+    reg_submaps_info info() const {
+        reg_submaps_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_submaps_get_info(s_, &i));
+        return i;
+    }
+    reg_submap_info submapInfo(int32_t idx) const {
+        reg_submap_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_submaps_get_submap_info(s_, idx, &i));
+        return i;
+    }
+    reg_submaps* submaps() const { return s_; }
+    reg_handle* handle() const { return h_; }
+
+private:
+    template <class F>
+    std::vector<Stamped> pop(F fn, int32_t n) {
+        std::vector<int32_t> ids((size_t)std::max(n, 1));
+        std::vector<int64_t> stamps(ids.size());
+        int32_t k = 0;
+        check(fn(s_, ids.data(), stamps.data(), (int32_t)ids.size(), &k));
+        std::vector<Stamped> out;
+        for (int32_t i = 0; i < k; ++i) out.push_back(Stamped{ids[(size_t)i], stamps[(size_t)i]});
+        return out;
+    }
+    static void raise(reg_status s, const std::string& msg) {
+        if (s == REG_BAD_ARGUMENT) throw InvalidParameter(msg);
+        if (s == REG_DEVICE_ERROR) throw DeviceError(msg);
+        throw std::runtime_error(msg);
+    }
+    void check(reg_status s) const {
+        if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    reg_handle* h_ = nullptr;
+    reg_submaps_params prm_;
+    reg_submaps* s_ = nullptr;
+};
+
+// o3d_slam::TransformInterpolationBuffer as the Mapper uses it: (stamp, pose) pairs pushed in order (an earlier stamp is
+// refused), capped at `limit`; lookup interpolates between the two neighbours (linear translation, slerp, factor =
+// dt / (duration + 1e-6), Transform.cpp:16-67); getTransform clamps the time to the buffer.  Poses are column-major double[16].
+class TransformBuffer {
+public:
+    explicit TransformBuffer(size_t limit = 2000) : limit_(limit) {}
+    bool push(int64_t stampNs, const double T[16]) {
+        if (!data_.empty() && stampNs < data_.back().stampNs) return false;
+        StampedPose p;
+        p.stampNs = stampNs;
+        std::copy(T, T + 16, p.pose.begin());
+        data_.push_back(p);
+        if (data_.size() > limit_) data_.erase(data_.begin());
+        return true;
+    }
+    bool empty() const { return data_.empty(); }
+    size_t size() const { return data_.size(); }
+    const std::vector<StampedPose>& entries() const { return data_; }
+    int64_t earliestTime() const { need(); return data_.front().stampNs; }
+    int64_t latestTime() const { need(); return data_.back().stampNs; }
+    bool has(int64_t t) const { return !data_.empty() && earliestTime() <= t && t <= latestTime(); }
+    std::array<double, 16> getTransform(int64_t t) const {   // o3d_slam::getTransform: clamped to the ends
+        need();
+        t = std::min(std::max(t, earliestTime()), latestTime());
+        size_t k = 0;
+        while (data_[k].stampNs < t) ++k;
+        if (data_[k].stampNs == t || k == 0) return data_[k].pose;
+        const StampedPose &a = data_[k - 1], &b = data_[k];
+        const double f = ((double)(t - a.stampNs) * 1e-9) / ((double)(b.stampNs - a.stampNs) * 1e-9 + 1e-6);
+        double qa[4], qb[4], q[4];
+        quat(a.pose.data(), qa), quat(b.pose.data(), qb);
+        double d = qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2] + qa[3] * qb[3], s0 = 1.0 - f, s1 = f;
+        if (std::fabs(d) < 1.0 - std::numeric_limits<double>::epsilon()) {
+            const double th = std::acos(std::fabs(d)), st = std::sin(th);
+            s0 = std::sin((1.0 - f) * th) / st, s1 = std::sin(f * th) / st;
+        }
+        if (d < 0.0) s1 = -s1;
+        for (int i = 0; i < 4; ++i) q[i] = s0 * qa[i] + s1 * qb[i];
+        std::array<double, 16> T{};
+        const double w = q[0], x = q[1], y = q[2], z = q[3], tx = 2 * x, ty = 2 * y, tz = 2 * z;
+        T[0] = 1 - (ty * y + tz * z), T[4] = ty * x - tz * w, T[8] = tz * x + ty * w;
+        T[1] = ty * x + tz * w, T[5] = 1 - (tx * x + tz * z), T[9] = tz * y - tx * w;
+        T[2] = tz * x - ty * w, T[6] = tz * y + tx * w, T[10] = 1 - (tx * x + ty * y);
+        for (int i = 0; i < 3; ++i) T[12 + i] = a.pose[12 + i] + (b.pose[12 + i] - a.pose[12 + i]) * f;
+        T[15] = 1.0;
+        return T;
+    }
+
+private:
+    void need() const { if (data_.empty()) throw std::runtime_error("TransformInterpolationBuffer:: Empty buffer"); }
+    static void quat(const double* T, double* q) {   // Eigen's Quaterniond(Matrix3d): (w, x, y, z); R(r, c) = T[4 c + r]
+        auto R = [T](int r, int c) { return T[4 * c + r]; };
+        double t = R(0, 0) + R(1, 1) + R(2, 2);
+        if (t > 0.0) {
+            t = std::sqrt(t + 1.0);
+            q[0] = 0.5 * t, t = 0.5 / t;
+            q[1] = (R(2, 1) - R(1, 2)) * t, q[2] = (R(0, 2) - R(2, 0)) * t, q[3] = (R(1, 0) - R(0, 1)) * t;
+            return;
+        }
+        int i = R(1, 1) > R(0, 0) ? 1 : 0;
+        if (R(2, 2) > R(i, i)) i = 2;
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        t = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0);
+        q[1 + i] = 0.5 * t, t = 0.5 / t;
+        q[0] = (R(k, j) - R(j, k)) * t, q[1 + j] = (R(j, i) + R(i, j)) * t, q[1 + k] = (R(k, i) + R(i, k)) * t;
+    }
+    size_t limit_;
+    std::vector<StampedPose> data_;
+};
+
+// o3d_slam::Mapper::addRangeMeasurement (Mapper.cpp:168-484) over one handle that carries the ICP configuration, a
+// SubmapCollection on that handle and the odometry buffer (the Python mirror is icp.Mapper).  Per scan:
+// reg_process_scan (the reading stays on the handle), reg_submaps_set_target when the reference is due, reg_register,
+// reg_submaps_insert_scan.  Scans are host arrays (n x 3 doubles, sensor frame); stamps are nanoseconds; poses column-major.
+// lastBranch() names the branch the last call ended in.  Departure: the map patch is cropped (and found empty) only when the
+// reference is re-initialised.
+struct MapperParameters {   // what addRangeMeasurement reads of o3d_slam::MapperParameters, Parameters.hpp:71,166,178-182
+    bool isUseInitialMap = false, isMergeScansIntoMap = true;
+    double mapMergeDelayInSeconds = 10.0, minMovementBetweenMappingSteps = 0.0, referenceCloudSettingPeriod = 1.0;
+};
+class Mapper {
+public:
+    using Parameters = MapperParameters;
+    using Pose = std::array<double, 16>;
+
+    Mapper(reg_handle* handle, SubmapCollection* submaps, const reg_scan_params& scan, const Parameters& params = Parameters())
+        : h_(handle), submaps_(submaps), scan_(scan), params_(params) {
+        cur_ = prev_ = lastInsertion_ = calibration_ = identity();
+    }
+    TransformBuffer& odometryBuffer() { return odom_; }
+    const TransformBuffer& mapToRangeSensorBuffer() const { return poses_; }
+    const TransformBuffer& bestGuessBuffer() const { return guesses_; }
+    void setExternalOdometryFrameToCloudFrameCalibration(const double T[16]) { std::copy(T, T + 16, calibration_.begin()), calibrationSet_ = true; }
+    void setMapToRangeSensor(const double T[16]) { std::copy(T, T + 16, cur_.begin()); }
+    void setMapToRangeSensorInitial(const double T[16]) {
+        if (newValueSet_) return;
+        std::copy(T, T + 16, cur_.begin());
+        prev_ = cur_, newValueSet_ = true;
+    }
+    const Pose& mapToRangeSensor() const { return cur_; }
+    Pose getMapToRangeSensor(int64_t stampNs) const { return poses_.getTransform(stampNs); }
+    MapCloud::Cloud getAssembledMapPointCloud() { return submaps_->getAssembledMapPointCloud(); }
+    int referenceInitializations() const { return nReferenceInits_; }
+    const std::string& lastBranch() const { return branch_; }
+
+    bool addRangeMeasurement(const double* rawScan, int64_t n, int64_t stampNs) {
+        if (!params_.isUseInitialMap && !calibrationSet_) return end("calibration_not_set", false);   // Mapper.cpp:169-174
+        submaps_->setMapToRangeSensor(cur_.data());
+        if (submaps_->isActiveSubmapEmpty()) {                                                          // :179-194
+            if (params_.isUseInitialMap) {
+                submaps_->insertScan(rawScan, n, rawScan, nullptr, nullptr, n, cur_.data(), stampNs);
+                return end("first_scan_initial_map", true);
+            }
+            prev_ = cur_;
+            const int64_t m = process(rawScan, n);
+            submaps_->insertScan(rawScan, n, mergeXyz_.data(), mergeNrm(), nullptr, m, cur_.data(), stampNs);
+            poses_.push(stampNs, cur_.data()), guesses_.push(stampNs, cur_.data());
+            return end("first_scan", true);
+        }
+        if (stampNs <= lastStamp_) {                                                                    // :196-235
+            const int64_t latest = odom_.latestTime();
+            cur_ = guess(latest);
+            poses_.push(latest, cur_.data()), guesses_.push(latest, prev_.data());
+            submaps_->setMapToRangeSensor(cur_.data());
+            prev_ = cur_;
+            return end("out_of_order", true);
+        }
+        Pose estimate = prev_;
+        if (odom_.has(stampNs) && !newValueSet_ && !ignoreOdometry_) estimate = guess(stampNs);        // :237-260
+        ignoreOdometry_ = false;
+        const int64_t m = process(rawScan, n);
+        // :325-326: whole milliseconds, truncated (C++ division truncates towards zero); never initialised: always due
+        const bool never = lastReferenceInit_ == std::numeric_limits<int64_t>::min();
+        const double passed = never ? 0.0 : (double)((stampNs - lastReferenceInit_) / 1000000) / 1e3;
+        if (newValueSet_ || never || passed >= params_.referenceCloudSettingPeriod) {                            // :329-347
+            reg_crop crop = scan_.narrow;
+            for (int k = 0; k < 3; ++k) crop.center[k] = cur_[12 + k];
+            if (submaps_->setAsReference(&crop) == 0) return end("empty_map_patch", false);
+            lastReferenceInit_ = stampNs;
+            ++nReferenceInits_;
+        }
+        float Ti[16], To[16];
+        for (int k = 0; k < 16; ++k) Ti[k] = To[k] = (float)estimate[k];
+        reg_result res{};
+        const reg_status st = reg_register(h_, Ti, To, &res);                                           // :372-373
+        std::string branch = "registered";
+        if (st == REG_DEVICE_ERROR || st == REG_BAD_ARGUMENT) throw std::runtime_error(reg_last_error(h_));
+        if (st != REG_OK) {                                                                             // :400-402
+            branch = "icp_exception";
+            std::copy(Ti, Ti + 16, To);
+        }
+        if (newValueSet_) {                                                                             // :420-435
+            initTime_ = stampNs, prev_ = cur_;
+            poses_.push(stampNs, cur_.data()), guesses_.push(stampNs, estimate.data());
+            newValueSet_ = false, ignoreOdometry_ = true;
+            return end("new_value_set", true);
+        }
+        for (int k = 0; k < 16; ++k) cur_[k] = (double)To[k];                                           // :438-442
+        poses_.push(stampNs, cur_.data()), guesses_.push(stampNs, estimate.data());
+        submaps_->setMapToRangeSensor(cur_.data());
+        const double sinceInit = (double)(stampNs - initTime_) * 1e-9;
+        if (params_.isUseInitialMap && (!params_.isMergeScansIntoMap || sinceInit < params_.mapMergeDelayInSeconds)) {   // :445-459
+            lastStamp_ = stampNs, prev_ = cur_;
+            return end("merge_delay", true);
+        }
+        const double dx = cur_[12] - lastInsertion_[12], dy = cur_[13] - lastInsertion_[13], dz = cur_[14] - lastInsertion_[14];
+        double mv[3];                                                                                   // :463-469: R_L^T (t_M - t_L)
+        for (int i = 0; i < 3; ++i) mv[i] = (lastInsertion_[4 * i] * dx + lastInsertion_[4 * i + 1] * dy) + lastInsertion_[4 * i + 2] * dz;
+        if (!(std::sqrt((mv[0] * mv[0] + mv[1] * mv[1]) + mv[2] * mv[2]) < params_.minMovementBetweenMappingSteps)) {
+            lastInsert_ = submaps_->insertScan(rawScan, n, mergeXyz_.data(), mergeNrm(), nullptr, m, cur_.data(), stampNs);
+            lastInsertion_ = cur_;
+        } else {
+            branch += "_moved_too_little";
+        }
+        lastStamp_ = stampNs, prev_ = cur_;
+        return end(branch, true);
+    }
+    const reg_submaps_insert_result& lastInsert() const { return lastInsert_; }
+
+private:
+    static Pose identity() { return Pose{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; }
+    bool end(const std::string& name, bool value) { branch_ = name; return value; }
+    Pose guess(int64_t now) const {
+        Pose out;
+        const Pose a = odom_.getTransform(lastStamp_), b = odom_.getTransform(now);
+        if (reg_host_mapper_initial_guess(prev_.data(), a.data(), b.data(), calibration_.data(), out.data()) != REG_OK)
+            throw std::runtime_error("reg_host_mapper_initial_guess");
+        return out;
+    }
+    const double* mergeNrm() const { return hasNormals_ ? mergeNrm_.data() : nullptr; }
+    int64_t process(const double* raw, int64_t n) {   // processForScanMatchingAndMerging: match_ becomes the reading
+        if (n <= 0) throw std::runtime_error("The reading point cloud is empty.");
+        mergeXyz_.resize((size_t)n * 3), mergeNrm_.resize((size_t)n * 3);
+        reg_scan_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        const reg_status st = reg_process_scan(h_, raw, nullptr, nullptr, n, 0, &scan_, mergeXyz_.data(), mergeNrm_.data(), nullptr, &r);
+        if (st == REG_BAD_ARGUMENT) throw InvalidParameter(reg_last_error(h_));
+        if (st != REG_OK) throw std::runtime_error(reg_last_error(h_));
+        hasNormals_ = r.has_normals != 0;
+        return r.n_merge;
+    }
+    reg_handle* h_;
+    SubmapCollection* submaps_;
+    reg_scan_params scan_;
+    Parameters params_;
+    TransformBuffer odom_, poses_, guesses_;
+    Pose cur_, prev_, lastInsertion_, calibration_;
+    bool calibrationSet_ = false, newValueSet_ = false, ignoreOdometry_ = false, hasNormals_ = false;
+    int64_t lastStamp_ = std::numeric_limits<int64_t>::min(), lastReferenceInit_ = std::numeric_limits<int64_t>::min(), initTime_ = 0;
+    int nReferenceInits_ = 0;
+    std::string branch_;
+    std::vector<double> mergeXyz_, mergeNrm_;
+    reg_submaps_insert_result lastInsert_{};
+};
+
 }  // namespace o3dreg

@@ -1793,6 +1793,240 @@ REG_API reg_status reg_host_pose_step(const double delta[6], const double pose[1
 REG_API reg_status reg_host_line_process_weight(const double* info, int64_t n_edges, double preference,
                                                 double max_correspondence_distance, double* weight);
 
+/* ---- the submap collection, resident on the device: o3d_slam::SubmapCollection ----------------------------
+   SubmapCollection (SubmapCollection.cpp) with its AdjacencyMatrix (AdjacencyMatrix.cpp), the candidate rule of
+   PlaceRecognition::getLoopClosureCandidatesIdxs (PlaceRecognition.cpp:231-284) and the pair selection of
+   computeOdometryConstraints (constraint_builders.cpp:92-118).  reg_submaps is that object on a handle: it owns up to
+   max_submaps map clouds (each a reg_map_cloud with the contract of that section, created from `map`), per submap the
+   occupancy set of Submap::voxelMap_ as ascending unique 64-bit voxel keys (8 bytes per voxel), and the overlap buffer as a
+   ring of num_scans_overlap device copies of pre-processed scans (points, optional normals / covariances, pose, stamp).  It
+   works on the handle's stream and working storage, is as non-re-entrant as the handle and MUST BE DESTROYED BEFORE IT.
+   Submap index == submap id (the reference never removes a submap).  Matrices: double[16], column-major.
+
+   Occupancy set and revisiting fitness (Submap.cpp:239-240,260-264; SubmapCollection.cpp:390-402):
+     key of a point: floor(p * inv) per axis with inv = 1.0 / (voxel_expansion_factor * map.map_voxel_size) -- a multiplication
+       by the inverse (VoxelHashMap.hpp:48-51), not a division -- packed as the map voxel key of the other sections;
+     DEPARTURE (the dense map's refused-keys rule): a row with a NaN or infinite coordinate or an index beyond
+       +-(2^20 - 1) gets NO key (the reference hashes any int triple); a scan point without a key counts as not contained;
+     the scan point is p' = R p + t with each row ((R0 x + R1 y) + R2 z) + t (no division by w: Isometry * point);
+     count = scan points whose key is in the candidate's set (an integer; the same on every run);
+     fitness = (double)count / (double)n_scan; n_scan == 0 gives NaN, and NaN is not > revisit_min_fitness: the check fails.
+     Oddities reproduced: the set is rebuilt ONLY by reg_submaps_compute_features; reg_submaps_transform leaves it where it
+       was (Submap::transform does not touch voxelMap_, Submap.cpp:115-128); a submap whose features were never computed
+       has an empty set, so every revisit of it fails the check.
+
+   reg_submaps_create: the constructor's first submap: id 0, parent 0, origin identity (SubmapCollection.cpp:28-32);
+     num_scans_overlap == 0 is refused (:253).
+   reg_submaps_insert_scan is SubmapCollection::insertScan (:189-245) with updateActiveSubmap (:94-148) inside, in this order:
+     1. mapToRangeSensor_ and timestamp_ become the call's; the pre-processed scan is copied into the ring (the oldest entry
+        leaves when the ring is full) BEFORE the decision;
+     2. the decision is reg_host_submaps_decide on: the force flag; the scans merged into the active submap against
+        min_num_range_data; is_use_initial_map; the closest submap over getMapToSubmapCenter() -- the translation of the origin
+        until a centre has been computed -- where the FIRST minimum wins on ties; the rows of the active map against
+        max_num_points, which only SETS the force flag: it takes effect at the NEXT call (reproduced); the distance to the
+        closest centre against radius (strictly less); adjacency; the fitness verdict, computed only when it is reached;
+        the distance to the active centre against radius (strictly greater).  Distances are sqrt((dx dx + dy dy) + dz dz).
+     3. unchanged active submap: it receives the scan as reg_map_cloud_insert_scan with carving.
+        changed (switched or created; a created submap has the next id, parent = the previous active index, origin = T):
+        the PREVIOUS submap receives the scan with carving; its centre is computed (GetCenter) and marked computed; it is
+        pushed to the finished queue with the stamp; the scans-merged counter returns to 0; the edge previous -- active is
+        added (both loop-closure marks are cleared: AdjacencyMatrix::addEdge writes false, reproduced); the ring is drained,
+        oldest first, into the now active submap with rawScan = scan and no carving (:87-92).
+     4. the scans-merged counter goes up by one.
+     A non-empty scan sets the receiving submap's own mapToRangeSensor_ (Submap.cpp:45).  is_carving_enabled == 0 never
+     carves.  is_use_initial_map with an empty receiving map: the map becomes the scan as reg_map_cloud_set with
+     map.map_voxel_size (Submap.cpp:47-52).  An empty scan inserts nothing but still enters the ring and the decision.
+     Departure: the reference's assert "submap should not be empty after switching" is not raised.
+   reg_submaps_force_new_submap (:180-187): the force flag, an insert of an EMPTY scan at the stored pose and stamp, flag off.
+   reg_submaps_compute_features: the device half of Submap::computeFeatures (Submap.cpp:255-275), in this order:
+     the gate `features computed before && now_seconds - last < min_seconds_between_features` (then *computed = 0 and nothing
+     is written); with feature params: the sparse cloud = reg_voxel_down_sample of the map's points at feature_voxel_size,
+     cast to fp32; its normals = reg_estimate_normals (normal_knn within normal_radius, oriented towards the origin, unit
+     length); its features = reg_compute_fpfh (feature_knn within feature_radius), each with the contract of that operator
+     and all on device pointers of this handle -- the map is not copied back; then the occupancy set is rebuilt from the
+     current map cloud and the clock value is stored.  The outputs (n_sparse x 3 floats, x 3 floats, x 33 doubles, host or
+     device pointers by on_device, any may be NULL) are written last; capacity_rows below the sparse rows is
+     REG_BAD_ARGUMENT with nothing changed (the rows of the map are always enough).  params == NULL: the occupancy set only.
+     An empty map gives n_sparse = 0.  The finished entry is then pushed to the loop-closure candidate queue by
+     reg_submaps_push_loop_closure_candidate (SubmapCollection.cpp:268).
+   reg_submaps_transform is SubmapCollection::transform (:322-373): every listed submap gets its own increment; every other
+     submap walks up its parents to the first listed one (the plan is reg_host_submaps_transform_plan); "Stuck in a loop"
+     becomes REG_BAD_TRANSFORM with nothing changed; the ring is flushed.  Per submap as Submap::transform: the map cloud
+     (PointCloud::Transform), mapToRangeSensor_ = mapToRangeSensor_ * T, centre = T * centre (rows ((T0 x + T1 y) + T2 z) + T3);
+     the origin mapToSubmap_ and the occupancy set stay (oddities reproduced).  Oddity reproduced: an unlisted submap reads
+     transformIncrements.at(parent), the parent's POSITION in the list, not the entry whose id is the parent; a position
+     beyond the list throws in the reference and is REG_BAD_TRANSFORM here.  An id >= the number of submaps is skipped.  An
+     empty list only flushes the ring.
+   Failure contract.  Bad arguments, unknown indices and an exhausted max_submaps (REG_BAD_ARGUMENT) are detected before
+     anything changes.  Each device step commits by its map cloud's buffer swap; host state -- active index, queues,
+     adjacency, counters, poses, the ring -- is committed only after the last device step of a call succeeded.  If a device
+     step fails in the middle of a switch, the map clouds the earlier steps completed keep their new content (the previous
+     submap already holds the scan; some ring scans may already be in the target submap) while every piece of host state
+     is as before the call: repeating the call would insert those scans twice.  A REG_BAD_ARGUMENT of a map cloud step
+     (a refused voxel key) behaves the same way.  In reg_submaps_transform the same holds per submap.
+   Out of scope: each submap's dense map (a reg_dense_map per id stays with the caller, who applies reg_dense_map_transform
+     with the plan), dumpToFile, the feature thread, the mutexes, building the constraints (reg_set_pair_overlap_f64). */
+typedef struct reg_submaps reg_submaps;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submaps_params); checked */
+    int32_t max_submaps;                  /* 1 .. 4096 (the reference reserves 500); default 64 */
+    int32_t num_scans_overlap;            /* submaps_.numScansOverlap_ (3); >= 1 */
+    int32_t min_num_range_data;           /* submaps_.minNumRangeData_ (5) */
+    int32_t is_use_initial_map;           /* isUseInitialMap_ (0) */
+    int32_t is_carving_enabled;           /* isCarvingEnabled_ (0, Parameters.hpp:181) */
+    int32_t min_submaps_between_loop_closures;   /* placeRecognition_.minSubmapsBetweenLoopClosures_ (2) */
+    int32_t reserved;
+    int64_t max_num_points;               /* submaps_.maxNumPoints_ (400000); >= 0 */
+    double  radius;                       /* submaps_.radius_ (20) */
+    double  revisit_min_fitness;          /* submaps_.adjacencyBasedRevisitingMinFitness_ (0.4) */
+    double  voxel_expansion_factor;       /* magic::voxelExpansionFactorAdjacencyBasedRevisiting (2.5); factor * voxel finite, > 0 */
+    double  min_seconds_between_features; /* submaps_.minSecondsBetweenFeatureComputation_ (5) */
+    double  loop_closure_search_radius;   /* placeRecognition_.loopClosureSearchRadius_ (20) */
+    reg_map_cloud_params map;             /* of every submap's map cloud; map_voxel_size > 0 */
+} reg_submaps_params;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submaps_info), set by the caller */
+    int32_t n_submaps;
+    int32_t active;                       /* activeSubmapIdx_ */
+    int32_t force_new_submap;             /* isForceNewSubmapCreation_ */
+    int32_t scans_in_active;              /* numScansMergedInActiveSubmap_ */
+    int32_t ring_size;                    /* scans in the overlap buffer */
+    int32_t n_finished;                   /* entries of the finished queue */
+    int32_t n_loop_closure_candidates;
+    int32_t last_finished;                /* lastFinishedSubmapIdx_ (0 at first) */
+    int32_t reserved;
+    int64_t total_points;                 /* getTotalNumPoints */
+    int64_t stamp_ns;                     /* timestamp_ */
+    double  T_map_to_sensor[16];          /* mapToRangeSensor_ */
+} reg_submaps_info;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submap_info), set by the caller */
+    int32_t id, parent;
+    int32_t center_computed;              /* isCenterComputed_ */
+    int32_t features_computed;            /* reg_submaps_compute_features has run on it */
+    int32_t reserved;
+    int64_t n_rows, scans_inserted;       /* of its map cloud */
+    int64_t n_keys;                       /* occupied voxels of the occupancy set */
+    double  origin[16];                   /* mapToSubmap_ */
+    double  center[3];                    /* getMapToSubmapCenter(): the computed centre, else the origin's translation */
+    double  crop_center[3];               /* the cropper centre of its map cloud */
+    double  T_map_to_sensor[16];          /* the submap's own mapToRangeSensor_ */
+    double  feature_clock;                /* now_seconds of the last feature computation */
+} reg_submap_info;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submaps_insert_result), set by the caller */
+    int32_t decision;                     /* the bits of reg_host_submaps_decide */
+    int32_t previous_active, active;
+    int32_t fitness_computed;             /* the revisiting check ran */
+    int32_t ring_drained;                 /* scans moved from the ring into the now active submap */
+    int64_t fitness_count;                /* its count */
+    double  fitness;                      /* and its fitness (NaN for an empty scan) */
+    reg_map_cloud_insert_result insert;   /* of the scan into the submap that received it with carving */
+} reg_submaps_insert_result;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submap_feature_params); checked */
+    int32_t normal_knn;                   /* placeRecognition_.normalKnn_ (10); 1 .. 32 */
+    int32_t feature_knn;                  /* placeRecognition_.featureKnn_ (100); 2 .. 128 */
+    int32_t reserved;
+    double  feature_voxel_size;           /* placeRecognition_.featureVoxelSize_ (0.5); finite, > 0 */
+    double  normal_radius;                /* placeRecognition_.normalEstimationRadius_ (1.0); > 0 */
+    double  feature_radius;               /* placeRecognition_.featureRadius_ (2.5); finite, > 0 */
+} reg_submap_feature_params;
+REG_API void reg_default_submaps_params(reg_submaps_params* p);
+REG_API void reg_default_submap_feature_params(reg_submap_feature_params* p);
+/* The validation reg_submaps_create runs, without a device. */
+REG_API reg_status reg_check_submaps_params(const reg_submaps_params* p);
+/* sizeof of reg_submaps_params, reg_submaps_info, reg_submap_info, reg_submaps_insert_result, reg_submap_feature_params */
+REG_API void reg_submaps_struct_sizes(int32_t sizes[5]);
+REG_API reg_status reg_submaps_create(reg_handle* h, const reg_submaps_params* params, reg_submaps** out);
+REG_API void reg_submaps_destroy(reg_submaps* s);   /* before reg_destroy of its handle */
+REG_API reg_status reg_submaps_get_info(const reg_submaps* s, reg_submaps_info* info);
+REG_API reg_status reg_submaps_get_submap_info(const reg_submaps* s, int32_t idx, reg_submap_info* info);
+/* setMapToRangeSensor (SubmapCollection.cpp:34-36) */
+REG_API reg_status reg_submaps_set_map_to_sensor(reg_submaps* s, const double T[16]);
+/* raw_xyz: the raw scan in the sensor frame (the carve's rays; NULL with n_raw == 0); scan_*: the pre-processed scan in the
+   sensor frame with exactly the fields of `map`; all host or all device pointers; result may be NULL and is written only
+   by a call that returns REG_OK.  A host raw scan is uploaded only when the carve of the receiving map is due. */
+REG_API reg_status reg_submaps_insert_scan(reg_submaps* s, const double* raw_xyz, int64_t n_raw, const double* scan_xyz,
+                                           const double* scan_normals, const double* scan_covs, int64_t n_scan, int on_device,
+                                           const double T_map_to_sensor[16], int64_t stamp_ns,
+                                           reg_submaps_insert_result* result);
+REG_API reg_status reg_submaps_force_new_submap(reg_submaps* s, reg_submaps_insert_result* result);
+REG_API reg_status reg_submaps_compute_features(reg_submaps* s, int32_t idx, double now_seconds,
+                                                const reg_submap_feature_params* params, int on_device, float* sparse_xyz,
+                                                float* sparse_normals, double* fpfh, int64_t capacity_rows, int64_t* n_sparse,
+                                                int32_t* computed);
+/* The occupancy keys of a submap, ascending (a host array of capacity_rows uint64; may be NULL to learn *n_out). */
+REG_API reg_status reg_submaps_get_keys(reg_submaps* s, int32_t idx, uint64_t* keys, int64_t capacity_rows, int64_t* n_out);
+/* The factor-level hook of the revisiting check: count and fitness of a scan at pose T against the set of submap idx. */
+REG_API reg_status reg_submaps_switch_fitness(reg_submaps* s, int32_t idx, const double* scan_xyz, int64_t n, int on_device,
+                                              const double T[16], int64_t* count, double* fitness);
+/* cropSubmap + initReference of the ACTIVE submap: reg_map_cloud_set_target of its map cloud. */
+REG_API reg_status reg_submaps_set_target(reg_submaps* s, const reg_crop* crop, int64_t* n_kept);
+/* One submap's map cloud as reg_map_cloud_export. */
+REG_API reg_status reg_submaps_export_submap(reg_submaps* s, int32_t idx, int on_device, double* xyz, double* normals,
+                                             double* covs, int64_t capacity_rows, int64_t* n_out);
+/* Mapper::getAssembledMapPointCloud: every submap's rows in submap order, one copy per submap and column into the caller's
+   arrays; capacity_rows < total_points returns REG_BAD_ARGUMENT, writing nothing. */
+REG_API reg_status reg_submaps_export(reg_submaps* s, int on_device, double* xyz, double* normals, double* covs,
+                                      int64_t capacity_rows, int64_t* n_out);
+/* ids[n] with dT[16 n] (column-major), in the order of the reference's transformIncrements. */
+REG_API reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const double* dT, int32_t n);
+/* updateAdjacencyMatrix (:75-81): per constraint addEdge(source, target), then both marked as loop-closure submaps. */
+REG_API reg_status reg_submaps_add_loop_closure_edges(reg_submaps* s, const int32_t* source, const int32_t* target, int32_t n);
+/* The adjacency matrix: adj (capacity x capacity bytes, row-major, 1 = an entry of adjacency_) and marks (capacity
+   int32: -1 no entry in isLoopClosureSubmap_, 0 false, 1 true); capacity >= n_submaps, either output may be NULL. */
+REG_API reg_status reg_submaps_get_adjacency(const reg_submaps* s, uint8_t* adj, int32_t* marks, int32_t capacity);
+/* popFinishedSubmapIds / popLoopClosureCandidates: the queue in order, then emptied; capacity below the entries returns
+   REG_BAD_ARGUMENT and pops nothing. */
+REG_API reg_status reg_submaps_pop_finished(reg_submaps* s, int32_t* ids, int64_t* stamps_ns, int32_t capacity, int32_t* n_out);
+REG_API reg_status reg_submaps_pop_loop_closure_candidates(reg_submaps* s, int32_t* ids, int64_t* stamps_ns, int32_t capacity,
+                                                           int32_t* n_out);
+REG_API reg_status reg_submaps_push_loop_closure_candidate(reg_submaps* s, int32_t id, int64_t stamp_ns);
+/* getLoopClosureCandidatesIdxs for last_finished against the active submap, in ascending index order, with these tests in
+   this order: i == active; isAdjacent(i, active); |i - last_finished| == 1 or isAdjacent(i, last_finished); centre distance
+   > loop_closure_search_radius; |i - last_finished| <= ceil(search radius / radius); the BFS distance of last_finished
+   to the nearest loop-closure submap < min_submaps_between_loop_closures. */
+REG_API reg_status reg_submaps_loop_closure_candidates(const reg_submaps* s, int32_t last_finished, int32_t* out,
+                                                       int32_t capacity, int32_t* n_out);
+/* The pair selection of computeOdometryConstraints.  candidates != NULL (constraint_builders.cpp:92-106): per candidate id >=
+   1 the pair (parent, id).  candidates == NULL (:108-118): every submap 1 .. n - 1 whose pair touches neither end the
+   active submap.  A pair already in existing (n_existing x 2: source, target) or chosen earlier in this call is skipped
+   (hasConstraint).  out: capacity x 2. */
+REG_API reg_status reg_submaps_odometry_constraint_pairs(const reg_submaps* s, const int32_t* candidates, int32_t n_candidates,
+                                                         const int32_t* existing, int32_t n_existing, int32_t* out,
+                                                         int32_t capacity, int32_t* n_out);
+
+/* Pure host functions (no device, no object). */
+enum {
+    REG_SUBMAPS_KEEP = 0, REG_SUBMAPS_SWITCH = 1, REG_SUBMAPS_CREATE = 2, REG_SUBMAPS_NEED_FITNESS = 3,   /* bits 0..1 */
+    REG_SUBMAPS_ACTION_MASK = 3,
+    REG_SUBMAPS_SET_FORCE_FLAG = 4,    /* the active map exceeds max_num_points: the flag is set for the NEXT call */
+    REG_SUBMAPS_FORCED = 8             /* the force flag was consumed (and cleared) by this creation */
+};
+/* The branch table of updateActiveSubmap.  fitness_ok: 1 / 0 the verdict of the revisiting check, -1 not known yet: then
+   REG_SUBMAPS_NEED_FITNESS is returned exactly where the reference would run the check (the caller computes it and asks
+   again).  closest_is_active: findClosestSubmap returned the active index; adjacent: isAdjacent(closest, active). */
+REG_API int32_t reg_host_submaps_decide(int32_t force_flag, int32_t scans_in_active, int32_t min_num_range_data,
+                                        int32_t is_use_initial_map, int64_t active_points, int64_t max_num_points,
+                                        int32_t closest_is_active, double distance_to_closest, double distance_to_active,
+                                        double radius, int32_t adjacent, int32_t fitness_ok);
+/* getDistanceToNearestLoopClosureSubmap on an n x n byte matrix and marks as reg_submaps_get_adjacency returns them:
+   INT_MAX when no node has a mark entry; a BFS in ascending neighbour order from id to the first marked node popped;
+   max(0, hops - 1); when no marked node is reachable the walk ends at the LAST node popped and its hops count (reproduced).
+   -1: bad arguments, or the reference would throw (a popped node without a mark entry or without adjacency). */
+REG_API int32_t reg_host_adjacency_distance(const uint8_t* adj, const int32_t* marks, int32_t n, int32_t id);
+/* Which increment each submap receives in SubmapCollection::transform: plan[i] = the POSITION in ids of the increment
+   applied to submap i (several listed entries for one id all apply, in list order: plan holds the last), or -1 for
+   none.  Returns REG_BAD_TRANSFORM for "Stuck in a loop" and for a position beyond the list. */
+REG_API reg_status reg_host_submaps_transform_plan(const int32_t* parents, int32_t n_submaps, const int32_t* ids, int32_t n,
+                                                   int32_t* plan);
+/* The Mapper's initial guess (Mapper.cpp:250-260) in fp64 with rigid inverses (as DESIGN 5z chose), column-major:
+   Ci = calib^-1; A = odom_now Ci; B = odom_prev Ci; M = B^-1 A (odometryMotion); out = prev_map_to_sensor M.  Every product
+   entry is ((a0 b0 + a1 b1) + a2 b2) + a3 b3; the rigid inverse is [R^T | -((R0i t0 + R1i t1) + R2i t2)]. */
+REG_API reg_status reg_host_mapper_initial_guess(const double prev_map_to_sensor[16], const double odom_prev[16],
+                                                 const double odom_now[16], const double calib[16], double out[16]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,6 +338,132 @@ def default_map_cloud_params(crop=None, **overrides) -> MapCloudParams:
     return p
 
 
+class SubmapsParams(C.Structure):
+    """reg_submaps_params (include/o3dslam_reg.h): SubmapParameters, the place-recognition gates and every submap's map cloud."""
+    _fields_ = [("struct_size", C.c_int32), ("max_submaps", C.c_int32), ("num_scans_overlap", C.c_int32),
+                ("min_num_range_data", C.c_int32), ("is_use_initial_map", C.c_int32), ("is_carving_enabled", C.c_int32),
+                ("min_submaps_between_loop_closures", C.c_int32), ("reserved", C.c_int32), ("max_num_points", C.c_int64),
+                ("radius", C.c_double), ("revisit_min_fitness", C.c_double), ("voxel_expansion_factor", C.c_double),
+                ("min_seconds_between_features", C.c_double), ("loop_closure_search_radius", C.c_double),
+                ("map", MapCloudParams)]
+
+
+class SubmapsInfo(C.Structure):
+    """reg_submaps_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("n_submaps", C.c_int32), ("active", C.c_int32), ("force_new_submap", C.c_int32),
+                ("scans_in_active", C.c_int32), ("ring_size", C.c_int32), ("n_finished", C.c_int32),
+                ("n_loop_closure_candidates", C.c_int32), ("last_finished", C.c_int32), ("reserved", C.c_int32),
+                ("total_points", C.c_int64), ("stamp_ns", C.c_int64), ("T_map_to_sensor", C.c_double * 16)]
+
+
+class SubmapInfo(C.Structure):
+    """reg_submap_info (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("id", C.c_int32), ("parent", C.c_int32), ("center_computed", C.c_int32),
+                ("features_computed", C.c_int32), ("reserved", C.c_int32), ("n_rows", C.c_int64), ("scans_inserted", C.c_int64),
+                ("n_keys", C.c_int64), ("origin", C.c_double * 16), ("center", C.c_double * 3), ("crop_center", C.c_double * 3),
+                ("T_map_to_sensor", C.c_double * 16), ("feature_clock", C.c_double)]
+
+
+class SubmapsInsertResult(C.Structure):
+    """reg_submaps_insert_result (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("decision", C.c_int32), ("previous_active", C.c_int32), ("active", C.c_int32),
+                ("fitness_computed", C.c_int32), ("ring_drained", C.c_int32), ("fitness_count", C.c_int64),
+                ("fitness", C.c_double), ("insert", MapCloudInsertResult)]
+
+
+class SubmapFeatureParams(C.Structure):
+    """reg_submap_feature_params (include/o3dslam_reg.h): what Submap::computeFeatures reads of PlaceRecognitionParameters."""
+    _fields_ = [("struct_size", C.c_int32), ("normal_knn", C.c_int32), ("feature_knn", C.c_int32), ("reserved", C.c_int32),
+                ("feature_voxel_size", C.c_double), ("normal_radius", C.c_double), ("feature_radius", C.c_double)]
+
+
+def default_submap_feature_params(**overrides) -> SubmapFeatureParams:
+    """reg_default_submap_feature_params: knn 10 within 1 m, voxel 0.5 m, FPFH 100 within 2.5 m (Parameters.hpp:121-126)."""
+    p = SubmapFeatureParams()
+    load_library().reg_default_submap_feature_params(C.byref(p))
+    for k, v in overrides.items():
+        if k not in ("normal_knn", "feature_knn", "feature_voxel_size", "normal_radius", "feature_radius"):
+            raise TypeError(f"unknown feature parameter {k}")
+        setattr(p, k, int(v) if k.endswith("knn") else float(v))
+    return p
+
+
+SUBMAPS_KEEP, SUBMAPS_SWITCH, SUBMAPS_CREATE, SUBMAPS_NEED_FITNESS = 0, 1, 2, 3
+SUBMAPS_ACTION_MASK, SUBMAPS_SET_FORCE_FLAG, SUBMAPS_FORCED = 3, 4, 8
+_SUBMAPS_INT = ("max_submaps", "num_scans_overlap", "min_num_range_data", "is_use_initial_map", "is_carving_enabled",
+                "min_submaps_between_loop_closures", "max_num_points")
+_SUBMAPS_FLOAT = ("radius", "revisit_min_fitness", "voxel_expansion_factor", "min_seconds_between_features",
+                  "loop_closure_search_radius")
+
+
+def default_submaps_params(map_params: "MapCloudParams | None" = None, **overrides) -> SubmapsParams:
+    """reg_default_submaps_params: SubmapParameters as shipped (radius 20, 5 scans, 400000 points, fitness 0.4, overlap 3),
+    factor 2.5, 64 submaps, the default map cloud; map_params replaces the map cloud's."""
+    p = SubmapsParams()
+    load_library().reg_default_submaps_params(C.byref(p))
+    if map_params is not None:
+        p.map = map_params
+        p.map.struct_size = C.sizeof(MapCloudParams)
+    for k, v in overrides.items():
+        if k in _SUBMAPS_INT:
+            setattr(p, k, int(v))
+        elif k in _SUBMAPS_FLOAT:
+            setattr(p, k, float(v))
+        else:
+            raise TypeError(f"unknown submaps parameter {k}")
+    return p
+
+
+def check_submaps_params(params: SubmapsParams) -> int:
+    """reg_check_submaps_params: the status reg_submaps_create would return for these parameters (no device)."""
+    return int(load_library().reg_check_submaps_params(C.byref(params)))
+
+
+def submaps_struct_sizes() -> tuple:
+    """sizeof of reg_submaps_params, reg_submaps_info, reg_submap_info, reg_submaps_insert_result,
+    reg_submap_feature_params in the library."""
+    out = (C.c_int32 * 5)()
+    load_library().reg_submaps_struct_sizes(out)
+    return tuple(out)
+
+
+def host_submaps_decide(force_flag, scans_in_active, min_num_range_data, is_use_initial_map, active_points, max_num_points,
+                        closest_is_active, distance_to_closest, distance_to_active, radius, adjacent, fitness_ok) -> int:
+    """reg_host_submaps_decide: the SUBMAPS_* bits of updateActiveSubmap's branch for these inputs (no device)."""
+    return int(load_library().reg_host_submaps_decide(int(bool(force_flag)), int(scans_in_active), int(min_num_range_data),
+                                                      int(bool(is_use_initial_map)), int(active_points), int(max_num_points),
+                                                      int(bool(closest_is_active)), float(distance_to_closest),
+                                                      float(distance_to_active), float(radius), int(bool(adjacent)),
+                                                      int(fitness_ok)))
+
+
+def host_adjacency_distance(adj, marks, node) -> int:
+    """reg_host_adjacency_distance: getDistanceToNearestLoopClosureSubmap on an n x n 0 / 1 matrix and marks (-1 / 0 / 1)."""
+    a = np.ascontiguousarray(adj, np.uint8)
+    m = np.ascontiguousarray(marks, np.int32)
+    return int(load_library().reg_host_adjacency_distance(_ptr(a), _ptr(m), int(m.shape[0]), int(node)))
+
+
+def host_submaps_transform_plan(parents, ids):
+    """reg_host_submaps_transform_plan: (status, plan); plan[i] = position in ids of the increment submap i receives, -1 none."""
+    pa = np.ascontiguousarray(parents, np.int32)
+    i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    plan = np.full(pa.shape[0], -1, np.int32)
+    st = load_library().reg_host_submaps_transform_plan(_ptr(pa), int(pa.shape[0]), _ptr(i) if i.size else None, int(i.size),
+                                                        _ptr(plan))
+    return int(st), plan
+
+
+def host_mapper_initial_guess(prev_map_to_sensor, odom_prev, odom_now, calib=None) -> np.ndarray:
+    """reg_host_mapper_initial_guess: prev * ((odom_prev calib^-1)^-1 (odom_now calib^-1)) in fp64 with rigid inverses."""
+    out = (C.c_double * 16)()
+    st = load_library().reg_host_mapper_initial_guess(_T_in_f64(prev_map_to_sensor), _T_in_f64(odom_prev), _T_in_f64(odom_now),
+                                                      _T_in_f64(np.eye(4) if calib is None else calib), out)
+    if st != 0:
+        raise RegError(st)
+    return np.array(out, np.float64).reshape(4, 4).T.copy()
+
+
 class UndistortParams(C.Structure):
     """reg_undistort_params (include/o3dslam_reg.h): spin direction, scan duration and the two velocities of the sensor."""
     _fields_ = [("struct_size", C.c_int32), ("spinning_clockwise", C.c_int32), ("scan_duration", C.c_double),
@@ -720,7 +846,15 @@ EXPORTS = ["reg_default_params", "reg_shipped_params", "reg_create", "reg_destro
            "reg_pose_graph_create", "reg_pose_graph_destroy", "reg_pose_graph_clear", "reg_pose_graph_set",
            "reg_pose_graph_linearize", "reg_pose_graph_optimize", "reg_pose_graph_global_optimize", "reg_pose_graph_get",
            "reg_pose_graph_get_edge_ids", "reg_pose_graph_get_info", "reg_host_pose_graph_edge", "reg_host_pose_vector", "reg_host_pose_step",
-           "reg_host_line_process_weight", "reg_debug_spd_solve_f64"]
+           "reg_host_line_process_weight", "reg_debug_spd_solve_f64",
+           "reg_default_submaps_params", "reg_default_submap_feature_params", "reg_check_submaps_params", "reg_submaps_struct_sizes", "reg_submaps_create",
+           "reg_submaps_destroy", "reg_submaps_get_info", "reg_submaps_get_submap_info", "reg_submaps_set_map_to_sensor",
+           "reg_submaps_insert_scan", "reg_submaps_force_new_submap", "reg_submaps_compute_features", "reg_submaps_get_keys",
+           "reg_submaps_switch_fitness", "reg_submaps_set_target", "reg_submaps_export_submap", "reg_submaps_export",
+           "reg_submaps_transform", "reg_submaps_add_loop_closure_edges", "reg_submaps_get_adjacency",
+           "reg_submaps_pop_finished", "reg_submaps_pop_loop_closure_candidates", "reg_submaps_push_loop_closure_candidate",
+           "reg_submaps_loop_closure_candidates", "reg_submaps_odometry_constraint_pairs", "reg_host_submaps_decide",
+           "reg_host_adjacency_distance", "reg_host_submaps_transform_plan", "reg_host_mapper_initial_guess"]
 
 
 def lib_path() -> str:
@@ -894,6 +1028,43 @@ def load_library():
     lib.reg_host_pose_step.argtypes = [vp, vp, vp]
     lib.reg_host_line_process_weight.argtypes = [vp, i64, C.c_double, C.c_double, C.POINTER(C.c_double)]
     lib.reg_debug_spd_solve_f64.argtypes = [vp, i64, vp, vp, vp, C.POINTER(C.c_int32)]
+    i32, pi32_ = C.c_int32, C.POINTER(C.c_int32)
+    lib.reg_default_submaps_params.argtypes = [C.POINTER(SubmapsParams)]
+    lib.reg_default_submaps_params.restype = None
+    lib.reg_check_submaps_params.argtypes = [C.POINTER(SubmapsParams)]
+    lib.reg_submaps_struct_sizes.argtypes = [pi32_]
+    lib.reg_submaps_struct_sizes.restype = None
+    lib.reg_submaps_create.argtypes = [vp, C.POINTER(SubmapsParams), C.POINTER(vp)]
+    lib.reg_submaps_destroy.argtypes = [vp]
+    lib.reg_submaps_destroy.restype = None
+    lib.reg_submaps_get_info.argtypes = [vp, C.POINTER(SubmapsInfo)]
+    lib.reg_submaps_get_submap_info.argtypes = [vp, i32, C.POINTER(SubmapInfo)]
+    lib.reg_submaps_set_map_to_sensor.argtypes = [vp, pd16]
+    lib.reg_submaps_insert_scan.argtypes = [vp, vp, i64, vp, vp, vp, i64, C.c_int, pd16, i64, C.POINTER(SubmapsInsertResult)]
+    lib.reg_submaps_force_new_submap.argtypes = [vp, C.POINTER(SubmapsInsertResult)]
+    lib.reg_default_submap_feature_params.argtypes = [C.POINTER(SubmapFeatureParams)]
+    lib.reg_default_submap_feature_params.restype = None
+    lib.reg_submaps_compute_features.argtypes = [vp, i32, C.c_double, C.POINTER(SubmapFeatureParams), C.c_int, vp, vp, vp, i64, pi64,
+                                                 pi32_]
+    lib.reg_submaps_get_keys.argtypes = [vp, i32, vp, i64, pi64]
+    lib.reg_submaps_switch_fitness.argtypes = [vp, i32, vp, i64, C.c_int, pd16, pi64, C.POINTER(C.c_double)]
+    lib.reg_submaps_set_target.argtypes = [vp, C.POINTER(RegCrop), pi64]
+    lib.reg_submaps_export_submap.argtypes = [vp, i32, C.c_int, vp, vp, vp, i64, pi64]
+    lib.reg_submaps_export.argtypes = [vp, C.c_int, vp, vp, vp, i64, pi64]
+    lib.reg_submaps_transform.argtypes = [vp, vp, vp, i32]
+    lib.reg_submaps_add_loop_closure_edges.argtypes = [vp, vp, vp, i32]
+    lib.reg_submaps_get_adjacency.argtypes = [vp, vp, vp, i32]
+    lib.reg_submaps_pop_finished.argtypes = [vp, vp, vp, i32, pi32_]
+    lib.reg_submaps_pop_loop_closure_candidates.argtypes = [vp, vp, vp, i32, pi32_]
+    lib.reg_submaps_push_loop_closure_candidate.argtypes = [vp, i32, i64]
+    lib.reg_submaps_loop_closure_candidates.argtypes = [vp, i32, vp, i32, pi32_]
+    lib.reg_submaps_odometry_constraint_pairs.argtypes = [vp, vp, i32, vp, i32, vp, i32, pi32_]
+    lib.reg_host_submaps_decide.argtypes = [i32, i32, i32, i32, i64, i64, i32, C.c_double, C.c_double, C.c_double, i32, i32]
+    lib.reg_host_submaps_decide.restype = i32
+    lib.reg_host_adjacency_distance.argtypes = [vp, vp, i32, i32]
+    lib.reg_host_adjacency_distance.restype = i32
+    lib.reg_host_submaps_transform_plan.argtypes = [vp, i32, vp, i32, vp]
+    lib.reg_host_mapper_initial_guess.argtypes = [pd16, pd16, pd16, pd16, pd16]
     lib.reg_host_centroid.argtypes = [f32p, i64, i64, f32p]
     lib.reg_host_o3d_update.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int32)]
     lib.reg_get_target_info.argtypes = [vp, C.POINTER(TargetInfo)]
@@ -1287,6 +1458,8 @@ class Registration:
             for m in list(getattr(self, "_odometries", ())):   # and a reg_odometry
                 m.close()
             for m in list(getattr(self, "_pose_graphs", ())):  # and a reg_pose_graph
+                m.close()
+            for m in list(getattr(self, "_submaps", ())):      # and a reg_submaps
                 m.close()
             self._lib.reg_destroy(self._h)
             self._h = C.c_void_p()
@@ -2501,6 +2674,214 @@ class MapCloud:
         self._check(self._lib.reg_map_cloud_export(self._m, 1, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), int(capacity_rows),
                                                    C.byref(k)))
         return int(k.value)
+
+
+class Submaps:
+    """One submap collection (== one reg_submaps; o3d_slam::SubmapCollection) on the handle of `reg`: every submap's map
+    cloud, its occupancy keys and the overlap ring stay on the device; the active index, the queues and the adjacency matrix
+    live on the host inside the library.  It uses the stream and the working storage of `reg` and must be closed before it
+    (close() of either order is safe here: the object keeps `reg` alive and closes itself first)."""
+
+    def __init__(self, reg: Registration, params: "SubmapsParams | None" = None):
+        self._lib = load_library()
+        self.reg = reg
+        self._s = C.c_void_p()
+        p = params if params is not None else default_submaps_params()
+        p.struct_size = C.sizeof(SubmapsParams)
+        reg._check(self._lib.reg_submaps_create(reg._h, C.byref(p), C.byref(self._s)))
+        self.params = p
+        if not hasattr(reg, "_submaps"):
+            reg._submaps = weakref.WeakSet()
+        reg._submaps.add(self)
+
+    def close(self):
+        if getattr(self, "_s", None) and getattr(self.reg, "_h", None):
+            self._lib.reg_submaps_destroy(self._s)
+        self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, st):
+        self.reg._check(st)
+
+    def info(self) -> SubmapsInfo:
+        i = SubmapsInfo()
+        i.struct_size = C.sizeof(SubmapsInfo)
+        self._check(self._lib.reg_submaps_get_info(self._s, C.byref(i)))
+        return i
+
+    def submap_info(self, idx) -> SubmapInfo:
+        i = SubmapInfo()
+        i.struct_size = C.sizeof(SubmapInfo)
+        self._check(self._lib.reg_submaps_get_submap_info(self._s, int(idx), C.byref(i)))
+        return i
+
+    def set_map_to_sensor(self, T):
+        self._check(self._lib.reg_submaps_set_map_to_sensor(self._s, _T_in_f64(T)))
+
+    def insert_scan(self, raw_xyz, scan_xyz, T, stamp_ns, scan_normals=None, scan_covs=None) -> SubmapsInsertResult:
+        """SubmapCollection::insertScan: the scan enters the ring, updateActiveSubmap decides, the scan is merged (and on a
+        change of the active submap the ring is drained into the new one)."""
+        f = MapCloud._f64
+        r, x, nr, cv = f(raw_xyz), f(scan_xyz), f(scan_normals), f(scan_covs, 9)
+        return self._insert(_ptr(r), r.shape[0] if r is not None else 0, _ptr(x), _ptr(nr), _ptr(cv), x.shape[0], 0, T, stamp_ns)
+
+    def insert_scan_device(self, raw_ptr, n_raw, scan_ptr, n_scan, T, stamp_ns, scan_nrm_ptr=None,
+                           scan_cov_ptr=None) -> SubmapsInsertResult:
+        """As insert_scan with the fp64 arrays resident in HBM."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        return self._insert(vp(raw_ptr), n_raw, vp(scan_ptr), vp(scan_nrm_ptr), vp(scan_cov_ptr), n_scan, 1, T, stamp_ns)
+
+    def _insert(self, r, n_raw, x, nr, cv, n, on_device, T, stamp_ns):
+        res = SubmapsInsertResult()
+        res.struct_size = C.sizeof(SubmapsInsertResult)
+        self._check(self._lib.reg_submaps_insert_scan(self._s, r, n_raw, x, nr, cv, n, on_device, _T_in_f64(T), int(stamp_ns),
+                                                      C.byref(res)))
+        return res
+
+    def force_new_submap(self) -> SubmapsInsertResult:
+        res = SubmapsInsertResult()
+        res.struct_size = C.sizeof(SubmapsInsertResult)
+        self._check(self._lib.reg_submaps_force_new_submap(self._s, C.byref(res)))
+        return res
+
+    def compute_features(self, idx, now_seconds, params: "SubmapFeatureParams | None" = None):
+        """Submap::computeFeatures on the caller's clock.  Without params: the gate and the occupancy keys; returns whether it
+        ran.  With params also the sparse cloud, its normals and FPFH features, computed on the device from the resident map:
+        returns None when the gate held, else dict(xyz n x 3 float32, normals n x 3 float32, fpfh n x 33 float64)."""
+        done = C.c_int32(0)
+        if params is None:
+            self._check(self._lib.reg_submaps_compute_features(self._s, int(idx), float(now_seconds), None, 0, None, None, None, 0,
+                                                               None, C.byref(done)))
+            return bool(done.value)
+        cap = max(int(self.submap_info(idx).n_rows), 1)
+        x, nr, f = np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32), np.empty((cap, 33), np.float64)
+        n = C.c_int64(0)
+        params.struct_size = C.sizeof(SubmapFeatureParams)
+        self._check(self._lib.reg_submaps_compute_features(self._s, int(idx), float(now_seconds), C.byref(params), 0, _ptr(x), _ptr(nr),
+                                                           _ptr(f), cap, C.byref(n), C.byref(done)))
+        if not done.value:
+            return None
+        k = int(n.value)
+        return dict(xyz=x[:k].copy(), normals=nr[:k].copy(), fpfh=f[:k].copy())
+
+    def compute_features_device(self, idx, now_seconds, params: "SubmapFeatureParams", capacity_rows, xyz_ptr=None, nrm_ptr=None,
+                                fpfh_ptr=None):
+        """As compute_features with the outputs resident in HBM.  Returns (ran, sparse rows)."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        done, n = C.c_int32(0), C.c_int64(0)
+        params.struct_size = C.sizeof(SubmapFeatureParams)
+        self._check(self._lib.reg_submaps_compute_features(self._s, int(idx), float(now_seconds), C.byref(params), 1, vp(xyz_ptr),
+                                                           vp(nrm_ptr), vp(fpfh_ptr), int(capacity_rows), C.byref(n), C.byref(done)))
+        return bool(done.value), int(n.value)
+
+    def keys(self, idx) -> np.ndarray:
+        """The occupancy keys of a submap, ascending uint64."""
+        n = C.c_int64(0)
+        self._check(self._lib.reg_submaps_get_keys(self._s, int(idx), None, 0, C.byref(n)))
+        out = np.empty(max(int(n.value), 1), np.uint64)
+        self._check(self._lib.reg_submaps_get_keys(self._s, int(idx), _ptr(out), out.shape[0], C.byref(n)))
+        return out[:int(n.value)]
+
+    def switch_fitness(self, idx, scan_xyz, T):
+        """(count, fitness) of the revisiting check of a host scan at pose T against submap idx."""
+        x = MapCloud._f64(scan_xyz)
+        return self._fitness(idx, _ptr(x) if x.shape[0] else None, x.shape[0], 0, T)
+
+    def switch_fitness_device(self, idx, scan_ptr, n, T):
+        return self._fitness(idx, C.c_void_p(scan_ptr) if scan_ptr else None, n, 1, T)
+
+    def _fitness(self, idx, x, n, on_device, T):
+        c, f = C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.reg_submaps_switch_fitness(self._s, int(idx), x, n, on_device, _T_in_f64(T), C.byref(c), C.byref(f)))
+        return int(c.value), float(f.value)
+
+    def set_target(self, crop=None) -> int:
+        """cropSubmap + initReference of the ACTIVE submap onto the handle of `reg`."""
+        c = Registration._crop_struct(crop)
+        kept = C.c_int64(0)
+        st = self._lib.reg_submaps_set_target(self._s, C.byref(c) if c is not None else None, C.byref(kept))
+        self.reg.n_target_kept = int(kept.value)
+        self._check(st)
+        return self.reg.n_target_kept
+
+    def _export(self, n, call):
+        p = self.params.map
+        f = lambda on, w: np.empty((max(n, 1), w), np.float64) if on else None
+        x, nr, cv = f(True, 3), f(p.has_normals, 3), f(p.has_covariances, 9)
+        k = C.c_int64(0)
+        self._check(call(_ptr(x), _ptr(nr), _ptr(cv), max(n, 1), C.byref(k)))
+        cut = lambda a: a[:int(k.value)] if a is not None else None
+        return dict(xyz=cut(x), normals=cut(nr), covs=cut(cv))
+
+    def export_submap(self, idx):
+        """dict(xyz, normals, covs) of one submap's map cloud in its row order."""
+        return self._export(int(self.submap_info(idx).n_rows),
+                            lambda x, nr, cv, cap, k: self._lib.reg_submaps_export_submap(self._s, int(idx), 0, x, nr, cv, cap, k))
+
+    def export(self):
+        """Mapper::getAssembledMapPointCloud: every submap's rows in submap order."""
+        return self._export(int(self.info().total_points),
+                            lambda x, nr, cv, cap, k: self._lib.reg_submaps_export(self._s, 0, x, nr, cv, cap, k))
+
+    def export_device(self, capacity_rows, xyz_ptr=None, nrm_ptr=None, cov_ptr=None) -> int:
+        vp = lambda p: C.c_void_p(p) if p else None
+        k = C.c_int64(0)
+        self._check(self._lib.reg_submaps_export(self._s, 1, vp(xyz_ptr), vp(nrm_ptr), vp(cov_ptr), int(capacity_rows), C.byref(k)))
+        return int(k.value)
+
+    def transform(self, ids, dTs):
+        """SubmapCollection::transform: ids[k] receives dTs[k]; the others follow their parents (reg_host_submaps_transform_plan)."""
+        i = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        t = np.ascontiguousarray([np.asarray(T, np.float64).reshape(4, 4).T for T in dTs], np.float64).reshape(-1)
+        self._check(self._lib.reg_submaps_transform(self._s, _ptr(i) if i.size else None, _ptr(t) if i.size else None, int(i.size)))
+
+    def add_loop_closure_edges(self, pairs):
+        p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+        self._check(self._lib.reg_submaps_add_loop_closure_edges(self._s, _ptr(a), _ptr(b), int(p.shape[0])))
+
+    def adjacency(self):
+        """(adj n x n uint8, marks n int32: -1 no entry, 0, 1)."""
+        n = int(self.info().n_submaps)
+        adj, marks = np.zeros((n, n), np.uint8), np.zeros(n, np.int32)
+        self._check(self._lib.reg_submaps_get_adjacency(self._s, _ptr(adj), _ptr(marks), n))
+        return adj, marks
+
+    def _pop(self, fn, n):
+        ids, stamps, k = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), C.c_int32(0)
+        self._check(fn(self._s, _ptr(ids), _ptr(stamps), ids.shape[0], C.byref(k)))
+        return [(int(a), int(b)) for a, b in zip(ids[:k.value], stamps[:k.value])]
+
+    def pop_finished(self):
+        return self._pop(self._lib.reg_submaps_pop_finished, int(self.info().n_finished))
+
+    def pop_loop_closure_candidates(self):
+        return self._pop(self._lib.reg_submaps_pop_loop_closure_candidates, int(self.info().n_loop_closure_candidates))
+
+    def push_loop_closure_candidate(self, idx, stamp_ns):
+        self._check(self._lib.reg_submaps_push_loop_closure_candidate(self._s, int(idx), int(stamp_ns)))
+
+    def loop_closure_candidates(self, last_finished) -> list:
+        n = int(self.info().n_submaps)
+        out, k = np.zeros(n, np.int32), C.c_int32(0)
+        self._check(self._lib.reg_submaps_loop_closure_candidates(self._s, int(last_finished), _ptr(out), n, C.byref(k)))
+        return out[:k.value].tolist()
+
+    def odometry_constraint_pairs(self, candidates=None, existing=()) -> list:
+        n = int(self.info().n_submaps)
+        c = None if candidates is None else np.ascontiguousarray(candidates, np.int32).reshape(-1)
+        e = np.ascontiguousarray(existing, np.int32).reshape(-1, 2)
+        cap = max(n, 0 if c is None else c.size, 1)
+        out, k = np.zeros((cap, 2), np.int32), C.c_int32(0)
+        self._check(self._lib.reg_submaps_odometry_constraint_pairs(
+            self._s, _ptr(c) if c is not None else None, 0 if c is None else int(c.size), _ptr(e) if e.size else None,
+            int(e.shape[0]), _ptr(out), cap, C.byref(k)))
+        return [tuple(r) for r in out[:k.value].tolist()]
 
 
 class Odometry:

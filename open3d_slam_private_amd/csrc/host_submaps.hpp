@@ -1,0 +1,792 @@
+// host_submaps.hpp -- the submap collection on the device: reg_submaps (o3d_slam::SubmapCollection with its
+// AdjacencyMatrix, the candidate rule of PlaceRecognition and the pair selection of computeOdometryConstraints) over the map
+// clouds of host_mapcloud.hpp, the occupancy sets of kernels_submaps.hpp and a ring of device copies of pre-processed scans;
+// the pure host functions behind it (branch table, BFS, transform plan, the Mapper's initial guess).
+// Part of the single translation unit reg_core.hip (included there, after host_posegraph.hpp; not a standalone header).
+#pragma once
+
+struct SmScan {   // one entry of overlapScansBuffer_ (ScanTimeTransform), resident
+    DevBuf xyz, nrm, cov;
+    int64_t n = 0, stamp = 0;
+    double T[16];
+};
+struct SmSubmap {
+    reg_map_cloud* map = nullptr;
+    int32_t id = 0, parent = 0;
+    bool center_computed = false, has_features = false;
+    double origin[16], T_sensor[16], center[3] = {0, 0, 0}, feature_clock = 0.0;
+    DevBuf keys[2];   // the occupancy set: built in the spare buffer, then swapped
+    int cur = 0;
+    int64_t n_keys = 0;
+    ~SmSubmap() { reg_map_cloud_destroy(map); }
+};
+struct SmStamped {
+    int32_t id;
+    int64_t stamp;
+};
+struct reg_submaps {
+    reg_handle* h = nullptr;
+    reg_submaps_params prm;
+    std::vector<std::unique_ptr<SmSubmap>> subs;
+    int32_t active = 0, scans_in_active = 0, last_finished = 0;
+    bool force = false;
+    double T_sensor[16];
+    int64_t stamp = 0;
+    std::unique_ptr<SmScan[]> slots;   // num_scans_overlap + 1: the spare one receives the next scan
+    std::deque<int> ring;        // slot indices, oldest first
+    std::vector<SmStamped> finished, candidates;
+    std::vector<std::set<int32_t>> adj;   // AdjacencyMatrix::adjacency_
+    std::vector<int32_t> marks;           // isLoopClosureSubmap_: -1 no entry, 0 false, 1 true
+    DevBuf f_xyz64, f_xyz, f_nrm, f_fpfh; // the sparse cloud (fp64, fp32), its normals and FPFH of the last feature computation
+};
+
+static void sm_add_edge(reg_submaps* s, int32_t a, int32_t b) {   // AdjacencyMatrix::addEdge: both marks become false
+    s->adj[a].insert(b);
+    s->adj[b].insert(a);
+    s->marks[a] = s->marks[b] = 0;
+}
+static bool sm_adjacent(const reg_submaps* s, int32_t a, int32_t b) { return a == b || s->adj[a].count(b) != 0; }
+static const double* sm_center(const SmSubmap& b) { return b.center_computed ? b.center : b.origin + 12; }
+static double sm_dist(const double* a, const double* b) {   // (a - b).norm()
+    const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
+    return std::sqrt((dx * dx + dy * dy) + dz * dz);
+}
+static void sm_mul(const double* A, const double* B, double* C) { pg_mul(B, A, C); }   // column-major A B (pg_mul is row-major)
+static void sm_rigid_inverse(const double* T, double* O) {                              // column-major
+    double r[16], ri[16];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) r[4 * i + j] = T[4 * j + i];
+    pg_rigid_inverse(r, ri);
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) O[4 * j + i] = ri[4 * i + j];
+}
+static int sm_spare_slot(const reg_submaps* s) {
+    for (int k = 0; k <= s->prm.num_scans_overlap; ++k)
+        if (std::find(s->ring.begin(), s->ring.end(), k) == s->ring.end()) return k;
+    return 0;   // not reached: the ring holds at most slots - 1 entries
+}
+static SmSubmap* sm_new_submap(reg_submaps* s, int32_t id, int32_t parent, const double* origin) {
+    std::unique_ptr<SmSubmap> b(new SmSubmap());
+    if (reg_map_cloud_create(s->h, &s->prm.map, &b->map) != REG_OK) return nullptr;
+    b->id = id;
+    b->parent = parent;
+    std::memcpy(b->origin, origin, sizeof(b->origin));
+    od_identity(b->T_sensor);
+    return b.release();
+}
+
+// The occupancy set of submap b from its current map cloud, into the spare key buffer; swapped in at the end.
+static reg_status sm_build_keys(reg_submaps* s, SmSubmap& b) {
+    reg_handle* h = s->h;
+    const int64_t n = b.map->n;
+    if (n == 0) {
+        b.n_keys = 0;
+        return REG_OK;
+    }
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, h->dm.reserve((size_t)n));
+    const RunArrays a = h->dm.arrays();
+    const double inv = 1.0 / (s->prm.voxel_expansion_factor * s->prm.map.map_voxel_size);
+    k_occ_keys<<<grid_for(n), 256, 0, h->stream>>>(mc_cur(b.map).xyz, n, inv, a.keys, a.vals);
+    uint32_t tail[2];
+    uint64_t first = 0;
+    REGCHK(sort_runs(h, a, n, tail));
+    HIPCHK(h, hipMemcpyAsync(&first, a.sorted, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    const int64_t n_keys = flag_total(tail) - (first == kOccNoKey ? 1 : 0);
+    DevBuf& out = b.keys[b.cur ^ 1];
+    HIPCHK(h, dm_grow(out, (size_t)std::max<int64_t>(n_keys, 1), 8));
+    if (n_keys > 0) {
+        k_occ_unique<<<grid_for(n), 256, 0, h->stream>>>(a.sorted, n, a.heads, a.run, out.as<uint64_t>());
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+    }
+    b.cur ^= 1;
+    b.n_keys = n_keys;
+    return REG_OK;
+}
+
+// isSwitchingSubmapsConsistant's count and fitness of n device points at pose T against the set of b
+static reg_status sm_fitness(reg_submaps* s, const SmSubmap& b, const double* d_xyz, int64_t n, const double* T, int64_t* count,
+                             double* fitness) {
+    reg_handle* h = s->h;
+    uint32_t c = 0;
+    if (n > 0 && b.n_keys > 0) {
+        HIPCHK(h, hipSetDevice(h->prm.device));
+        HIPCHK(h, h->dm_misc.reserve(256));
+        uint32_t* d_c = (uint32_t*)((char*)h->dm_misc.p + 128);
+        HIPCHK(h, hipMemsetAsync(d_c, 0, 4, h->stream));
+        const double inv = 1.0 / (s->prm.voxel_expansion_factor * s->prm.map.map_voxel_size);
+        k_occ_count<<<grid_for(n), 256, 0, h->stream>>>(d_xyz, n, xform_rows(T), inv, b.keys[b.cur].as<uint64_t>(), b.n_keys, d_c);
+        HIPCHK(h, hipMemcpyAsync(&c, d_c, 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipGetLastError());
+    }
+    *count = (int64_t)c;
+    *fitness = n > 0 ? (double)c / (double)n : std::numeric_limits<double>::quiet_NaN();   // 0 / 0 of the reference
+    return REG_OK;
+}
+
+// Submap::insertScan of a resident scan (device pointers) into submap b
+static reg_status sm_insert(reg_submaps* s, SmSubmap& b, const double* d_raw, int64_t n_raw, SmScan& sc, bool carve,
+                            reg_map_cloud_insert_result* res) {
+    if (sc.n == 0) return REG_OK;   // Submap.cpp:41-43
+    const bool nrm = s->prm.map.has_normals, cov = s->prm.map.has_covariances;
+    const double *x = sc.xyz.as<double>(), *nr = nrm ? sc.nrm.as<double>() : nullptr, *cv = cov ? sc.cov.as<double>() : nullptr;
+    if (s->prm.is_use_initial_map && b.map->n == 0)   // Submap.cpp:47-52
+        return reg_map_cloud_set(b.map, x, nr, cv, sc.n, 1, s->prm.map.map_voxel_size);
+    return reg_map_cloud_insert_scan(b.map, d_raw, n_raw, x, nr, cv, sc.n, 1, sc.T, carve && s->prm.is_carving_enabled, res);
+}
+
+static bool sm_idx_ok(const reg_submaps* s, int32_t idx) { return idx >= 0 && idx < (int32_t)s->subs.size(); }
+
+extern "C" {
+
+void reg_default_submaps_params(reg_submaps_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(reg_submaps_params);
+    p->max_submaps = 64;
+    p->num_scans_overlap = 3;     // SubmapParameters, Parameters.hpp:103-110
+    p->min_num_range_data = 5;
+    p->is_carving_enabled = 0;   // MapperParameters::isCarvingEnabled_, Parameters.hpp:181
+    p->min_submaps_between_loop_closures = 2;   // PlaceRecognitionParameters, Parameters.hpp:138-139
+    p->max_num_points = 400000;
+    p->radius = 20.0;
+    p->revisit_min_fitness = 0.4;
+    p->voxel_expansion_factor = 2.5;   // magic.hpp:16
+    p->min_seconds_between_features = 5.0;
+    p->loop_closure_search_radius = 20.0;
+    reg_default_map_cloud_params(&p->map);
+}
+
+reg_status reg_check_submaps_params(const reg_submaps_params* p) {
+    if (!p || p->struct_size != (int32_t)sizeof(reg_submaps_params)) return REG_BAD_ARGUMENT;
+    const double v = p->voxel_expansion_factor * p->map.map_voxel_size;
+    if (p->max_submaps < 1 || p->max_submaps > 4096 || p->num_scans_overlap < 1 || p->max_num_points < 0 ||
+        p->radius != p->radius || p->revisit_min_fitness != p->revisit_min_fitness || !(v > 0.0) || !std::isfinite(v) ||
+        !std::isfinite(1.0 / v) || p->min_seconds_between_features != p->min_seconds_between_features ||
+        p->loop_closure_search_radius != p->loop_closure_search_radius || p->map.struct_size != (int32_t)sizeof(reg_map_cloud_params))
+        return REG_BAD_ARGUMENT;
+    return REG_OK;
+}
+
+void reg_submaps_struct_sizes(int32_t sizes[5]) {
+    if (!sizes) return;
+    sizes[0] = (int32_t)sizeof(reg_submaps_params);
+    sizes[1] = (int32_t)sizeof(reg_submaps_info);
+    sizes[2] = (int32_t)sizeof(reg_submap_info);
+    sizes[3] = (int32_t)sizeof(reg_submaps_insert_result);
+    sizes[4] = (int32_t)sizeof(reg_submap_feature_params);
+}
+
+int32_t reg_host_submaps_decide(int32_t force_flag, int32_t scans_in_active, int32_t min_num_range_data, int32_t is_use_initial_map,
+                                int64_t active_points, int64_t max_num_points, int32_t closest_is_active,
+                                double distance_to_closest, double distance_to_active, double radius, int32_t adjacent,
+                                int32_t fitness_ok) {
+    if (force_flag) return REG_SUBMAPS_CREATE | REG_SUBMAPS_FORCED;        // SubmapCollection.cpp:95-99
+    if (scans_in_active < min_num_range_data) return REG_SUBMAPS_KEEP;     // :101-103
+    if (is_use_initial_map) return REG_SUBMAPS_KEEP;                       // :105-107
+    const int32_t flag = active_points > max_num_points ? REG_SUBMAPS_SET_FORCE_FLAG : 0;   // :114-116
+    if (!(distance_to_closest < radius)) return REG_SUBMAPS_CREATE | flag;                  // :122, :144-147
+    if (closest_is_active) return REG_SUBMAPS_KEEP | flag;                                  // :127-129
+    if (adjacent) {                                                                         // :132-135
+        if (fitness_ok < 0) return REG_SUBMAPS_NEED_FITNESS | flag;
+        if (fitness_ok) return REG_SUBMAPS_SWITCH | flag;
+    }
+    return (distance_to_active > radius ? REG_SUBMAPS_CREATE : REG_SUBMAPS_KEEP) | flag;    // :138-142
+}
+
+int32_t reg_host_adjacency_distance(const uint8_t* adj, const int32_t* marks, int32_t n, int32_t id) {
+    if (!adj || !marks || n < 1 || id < 0 || id >= n) return -1;
+    bool any = false;
+    for (int32_t i = 0; i < n; ++i) any = any || marks[i] >= 0;
+    if (!any) return std::numeric_limits<int32_t>::max();   // AdjacencyMatrix.cpp:24-26
+    std::vector<int32_t> parent(n, -1), queue;
+    std::vector<char> visited(n, 0);
+    visited[id] = 1;
+    queue.push_back(id);
+    int32_t v = id;
+    for (size_t head = 0; head < queue.size(); ++head) {
+        v = queue[head];
+        if (marks[v] < 0) return -1;   // isLoopClosureSubmap_.at(v) / adjacency_.at(v) throw
+        if (marks[v] > 0) break;
+        for (int32_t a = 0; a < n; ++a)   // std::set: ascending
+            if (adj[(size_t)v * n + a] && !visited[a]) {
+                visited[a] = 1;
+                queue.push_back(a);
+                parent[a] = v;
+            }
+    }
+    int32_t distance = 0;
+    while (v != id) {
+        v = parent[v];
+        ++distance;
+    }
+    return std::max(0, distance - 1);
+}
+
+reg_status reg_host_submaps_transform_plan(const int32_t* parents, int32_t n_submaps, const int32_t* ids, int32_t n, int32_t* plan) {
+    if (!parents || !plan || n_submaps < 1 || n < 0 || (n > 0 && !ids)) return REG_BAD_ARGUMENT;
+    for (int32_t i = 0; i < n_submaps; ++i) {
+        plan[i] = -1;
+        if (parents[i] < 0 || parents[i] >= n_submaps) return REG_BAD_ARGUMENT;
+    }
+    std::vector<char> listed(n_submaps, 0);
+    for (int32_t k = 0; k < n; ++k)
+        if (ids[k] >= 0 && ids[k] < n_submaps) listed[ids[k]] = 1, plan[ids[k]] = k;   // SubmapCollection.cpp:328-338
+    if (n == 0) return REG_OK;   // `while (true && !transformIncrements.empty())`
+    for (int32_t idx = 0; idx < n_submaps; ++idx) {
+        if (listed[idx]) continue;
+        int32_t cur = idx;
+        for (;;) {   // :356-368
+            cur = parents[cur];
+            if (listed[cur]) {
+                if (cur >= n) return REG_BAD_TRANSFORM;   // transformIncrements.at(currentNode): a POSITION, reproduced
+                plan[idx] = cur;
+                break;
+            }
+            if (cur == parents[cur]) return REG_BAD_TRANSFORM;   // "Stuck in a loop, this should not happen"
+        }
+    }
+    return REG_OK;
+}
+
+reg_status reg_host_mapper_initial_guess(const double prev_map_to_sensor[16], const double odom_prev[16], const double odom_now[16],
+                                         const double calib[16], double out[16]) {
+    if (!prev_map_to_sensor || !odom_prev || !odom_now || !calib || !out) return REG_BAD_ARGUMENT;
+    double ci[16], a[16], b[16], bi[16], m[16], r[16];
+    sm_rigid_inverse(calib, ci);
+    sm_mul(odom_now, ci, a);
+    sm_mul(odom_prev, ci, b);
+    sm_rigid_inverse(b, bi);
+    sm_mul(bi, a, m);
+    sm_mul(prev_map_to_sensor, m, r);
+    std::memcpy(out, r, sizeof(r));
+    return REG_OK;
+}
+
+reg_status reg_submaps_create(reg_handle* h, const reg_submaps_params* p, reg_submaps** out) {
+    if (!h || !out) return REG_BAD_ARGUMENT;
+    *out = nullptr;
+    if (reg_check_submaps_params(p) != REG_OK) {
+        h->err = "reg_submaps_create: params missing or of the wrong struct_size (map's included), max_submaps outside [1, 4096], "
+                 "num_scans_overlap < 1, max_num_points < 0, a NaN, or voxel_expansion_factor * map.map_voxel_size not finite and > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    std::unique_ptr<reg_submaps> s(new reg_submaps());
+    s->h = h;
+    s->prm = *p;
+    od_identity(s->T_sensor);
+    SmSubmap* first = sm_new_submap(s.get(), 0, 0, s->T_sensor);   // SubmapCollection.cpp:28-32
+    if (!first) return REG_BAD_ARGUMENT;                           // the map cloud's own refusal; its text is in h->err
+    s->subs.emplace_back(first);
+    s->slots.reset(new SmScan[(size_t)p->num_scans_overlap + 1]);
+    s->adj.resize((size_t)p->max_submaps);
+    s->marks.assign((size_t)p->max_submaps, -1);
+    *out = s.release();
+    return REG_OK;
+}
+
+void reg_submaps_destroy(reg_submaps* s) {
+    if (!s) return;
+    if (s->h->device_ok && hipSetDevice(s->h->prm.device) == hipSuccess) (void)hipStreamSynchronize(s->h->stream);
+    delete s;
+}
+
+reg_status reg_submaps_get_info(const reg_submaps* s, reg_submaps_info* info) {
+    if (!s || !info || info->struct_size != (int32_t)sizeof(reg_submaps_info)) return REG_BAD_ARGUMENT;
+    info->n_submaps = (int32_t)s->subs.size();
+    info->active = s->active;
+    info->force_new_submap = s->force;
+    info->scans_in_active = s->scans_in_active;
+    info->ring_size = (int32_t)s->ring.size();
+    info->n_finished = (int32_t)s->finished.size();
+    info->n_loop_closure_candidates = (int32_t)s->candidates.size();
+    info->last_finished = s->last_finished;
+    info->reserved = 0;
+    info->total_points = 0;
+    for (const auto& b : s->subs) info->total_points += b->map->n;
+    info->stamp_ns = s->stamp;
+    std::memcpy(info->T_map_to_sensor, s->T_sensor, sizeof(s->T_sensor));
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_submap_info(const reg_submaps* s, int32_t idx, reg_submap_info* info) {
+    if (!s || !info || info->struct_size != (int32_t)sizeof(reg_submap_info) || !sm_idx_ok(s, idx)) return REG_BAD_ARGUMENT;
+    const SmSubmap& b = *s->subs[idx];
+    info->id = b.id;
+    info->parent = b.parent;
+    info->center_computed = b.center_computed;
+    info->features_computed = b.has_features;
+    info->reserved = 0;
+    info->n_rows = b.map->n;
+    info->scans_inserted = b.map->scans;
+    info->n_keys = b.n_keys;
+    std::memcpy(info->origin, b.origin, sizeof(b.origin));
+    std::memcpy(info->T_map_to_sensor, b.T_sensor, sizeof(b.T_sensor));
+    for (int k = 0; k < 3; ++k) info->center[k] = sm_center(b)[k], info->crop_center[k] = b.map->center[k];
+    info->feature_clock = b.feature_clock;
+    return REG_OK;
+}
+
+reg_status reg_submaps_set_map_to_sensor(reg_submaps* s, const double T[16]) {
+    if (!s || !T) return REG_BAD_ARGUMENT;
+    std::memcpy(s->T_sensor, T, sizeof(s->T_sensor));
+    return REG_OK;
+}
+
+reg_status reg_submaps_insert_scan(reg_submaps* s, const double* raw_xyz, int64_t n_raw, const double* scan_xyz,
+                                   const double* scan_normals, const double* scan_covs, int64_t n, int on_device,
+                                   const double T[16], int64_t stamp_ns, reg_submaps_insert_result* res) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    const int32_t prev = s->active;
+    SmSubmap& act = *s->subs[prev];
+    if (res && res->struct_size != (int32_t)sizeof(reg_submaps_insert_result)) {
+        h->err = "reg_submaps_insert_scan: result of the wrong struct_size";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!T || !mc_cloud_ok(act.map, scan_xyz, scan_normals, scan_covs, n) || !dm_cloud_args_ok(raw_xyz, n_raw)) {
+        h->err = std::string("reg_submaps_insert_scan: T missing, a bad raw scan, or a scan not") + kMcCloudMsg;
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+
+    // 1. the scan into the spare slot of the ring (SubmapCollection.cpp:206); it joins the ring when the call commits
+    const int slot = sm_spare_slot(s);
+    SmScan& sc = s->slots[slot];
+    const double* src[3] = {scan_xyz, scan_normals, scan_covs};
+    DevBuf* dst[3] = {&sc.xyz, &sc.nrm, &sc.cov};
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (int k = 0; k < 3; ++k)
+        if (n > 0 && src[k]) {
+            HIPCHK(h, dm_grow(*dst[k], (size_t)n, kSpWidth[k] * 8));
+            HIPCHK(h, hipMemcpyAsync(dst[k]->p, src[k], (size_t)n * kSpWidth[k] * 8, kind, h->stream));
+        }
+    sc.n = n;
+    sc.stamp = stamp_ns;
+    std::memcpy(sc.T, T, sizeof(sc.T));
+    // the raw scan is staged only when the carve of the receiving map is due (the rule of reg_map_cloud_insert_scan)
+    const bool carve_due = s->prm.is_carving_enabled && act.map->n > 0 && (act.map->scans % act.map->prm.carve_every_n_scans) == 1 &&
+                           !(s->prm.is_use_initial_map && act.map->n == 0);
+    const double* d_raw = nullptr;
+    if (n > 0 && n_raw > 0 && carve_due) HIPCHK(h, staged_input(h, h->mc_in[3], raw_xyz, (size_t)n_raw * 3, on_device, &d_raw));
+    if (!d_raw) n_raw = 0;
+
+    // 2. updateActiveSubmap (:94-148) on the state as it stands
+    int32_t closest = 0;
+    for (int32_t i = 1; i < (int32_t)s->subs.size(); ++i)   // findClosestSubmap: std::min_element, the first minimum
+        if (sm_dist(T + 12, sm_center(*s->subs[i])) < sm_dist(T + 12, sm_center(*s->subs[closest]))) closest = i;
+    const double d_closest = sm_dist(T + 12, sm_center(*s->subs[closest])), d_active = sm_dist(T + 12, sm_center(act));
+    const int32_t adjacent = sm_adjacent(s, s->subs[closest]->id, act.id);
+    int32_t fitness_ok = -1, dec;
+    int64_t count = 0;
+    double fitness = 0.0;
+    for (;;) {
+        dec = reg_host_submaps_decide(s->force, s->scans_in_active, s->prm.min_num_range_data, s->prm.is_use_initial_map,
+                                      act.map->n, s->prm.max_num_points, closest == prev, d_closest, d_active, s->prm.radius,
+                                      adjacent, fitness_ok);
+        if ((dec & REG_SUBMAPS_ACTION_MASK) != REG_SUBMAPS_NEED_FITNESS) break;
+        REGCHK(sm_fitness(s, *s->subs[closest], sc.xyz.as<double>(), n, T, &count, &fitness));
+        fitness_ok = fitness > s->prm.revisit_min_fitness ? 1 : 0;   // a NaN fails
+    }
+    const int action = dec & REG_SUBMAPS_ACTION_MASK;
+    std::unique_ptr<SmSubmap> created;
+    int32_t now = prev;
+    if (action == REG_SUBMAPS_SWITCH) now = closest;
+    if (action == REG_SUBMAPS_CREATE) {   // createNewSubmap (:150-162)
+        now = (int32_t)s->subs.size();
+        if (now >= s->prm.max_submaps) {
+            h->err = "reg_submaps_insert_scan: a new submap is due and max_submaps is exhausted";
+            return REG_BAD_ARGUMENT;
+        }
+        created.reset(sm_new_submap(s, now, prev, T));
+        if (!created) return REG_BAD_ARGUMENT;
+    }
+
+    // 3. the device steps
+    reg_map_cloud_insert_result ins;
+    std::memset(&ins, 0, sizeof(ins));
+    ins.struct_size = (int32_t)sizeof(ins);
+    ins.n_rows = act.map->n;
+    REGCHK(sm_insert(s, act, d_raw, n_raw, sc, true, &ins));   // :214 / :238: the previous active submap either way
+    double center[3] = {0, 0, 0};
+    int32_t drained = 0;
+    int last_filled = -1;
+    if (now != prev) {
+        REGCHK(reg_map_cloud_center(act.map, center));   // computeSubmapCenter (:217)
+        SmSubmap& target = created ? *created : *s->subs[now];
+        std::deque<int> order = s->ring;                 // the ring as the push leaves it
+        order.push_back(slot);
+        if ((int)order.size() > s->prm.num_scans_overlap) order.pop_front();
+        for (int k : order) {                            // insertBufferedScans (:87-92)
+            SmScan& b = s->slots[k];
+            REGCHK(sm_insert(s, target, b.xyz.as<double>(), b.n, b, false, nullptr));
+            if (b.n > 0) last_filled = k;
+            ++drained;
+        }
+    }
+
+    // 4. commit the host state
+    std::memcpy(s->T_sensor, T, sizeof(s->T_sensor));
+    s->stamp = stamp_ns;
+    if (n > 0) std::memcpy(act.T_sensor, T, sizeof(act.T_sensor));   // Submap.cpp:45
+    if (dec & REG_SUBMAPS_FORCED) s->force = false;
+    if (dec & REG_SUBMAPS_SET_FORCE_FLAG) s->force = true;
+    if (now != prev) {
+        for (int k = 0; k < 3; ++k) act.center[k] = center[k];
+        act.center_computed = true;
+        if (created) s->subs.emplace_back(created.release());
+        SmSubmap& target = *s->subs[now];
+        if (last_filled >= 0) std::memcpy(target.T_sensor, s->slots[last_filled].T, sizeof(target.T_sensor));
+        s->active = now;
+        s->last_finished = prev;
+        s->finished.push_back(SmStamped{prev, stamp_ns});
+        s->scans_in_active = 0;
+        sm_add_edge(s, act.id, target.id);
+        s->ring.clear();
+    } else {
+        s->ring.push_back(slot);
+        if ((int)s->ring.size() > s->prm.num_scans_overlap) s->ring.pop_front();
+    }
+    s->scans_in_active += 1;
+    if (res) {   // written only by a call that succeeds
+        std::memset(res, 0, sizeof(*res));
+        res->struct_size = (int32_t)sizeof(*res);
+        res->previous_active = prev;
+        res->decision = dec;
+        res->active = now;
+        res->fitness_computed = fitness_ok >= 0;
+        res->ring_drained = drained;
+        res->fitness_count = count;
+        res->fitness = fitness;
+        res->insert = ins;
+    }
+    return REG_OK;
+}
+
+reg_status reg_submaps_force_new_submap(reg_submaps* s, reg_submaps_insert_result* res) {
+    if (!s) return REG_BAD_ARGUMENT;
+    const bool before = s->force;
+    s->force = true;   // SubmapCollection.cpp:184-186
+    const double T[16] = {s->T_sensor[0],  s->T_sensor[1],  s->T_sensor[2],  s->T_sensor[3], s->T_sensor[4],  s->T_sensor[5],
+                          s->T_sensor[6],  s->T_sensor[7],  s->T_sensor[8],  s->T_sensor[9], s->T_sensor[10], s->T_sensor[11],
+                          s->T_sensor[12], s->T_sensor[13], s->T_sensor[14], s->T_sensor[15]};
+    const reg_status st = reg_submaps_insert_scan(s, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, T, s->stamp, res);
+    s->force = st == REG_OK ? false : before;
+    return st;
+}
+
+void reg_default_submap_feature_params(reg_submap_feature_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(*p);
+    p->normal_knn = 10;   // PlaceRecognitionParameters, Parameters.hpp:121-126
+    p->feature_knn = 100;
+    p->feature_voxel_size = 0.5;
+    p->normal_radius = 1.0;
+    p->feature_radius = 2.5;
+}
+
+// The sparse cloud and its FPFH features of submap b into the collection's feature buffers: what reg_voxel_down_sample,
+// reg_estimate_normals and reg_compute_fpfh do, called with device pointers on the collection's handle.
+static reg_status sm_features(reg_submaps* s, SmSubmap& b, const reg_submap_feature_params* fp, int64_t* n_sparse) {
+    reg_handle* h = s->h;
+    const int64_t n = b.map->n;
+    *n_sparse = 0;
+    if (n == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, dm_grow(s->f_xyz64, (size_t)n, 24));
+    int64_t m = 0;
+    REGCHK(reg_voxel_down_sample(h, mc_cur(b.map).xyz, nullptr, nullptr, n, 1, fp->feature_voxel_size, s->f_xyz64.as<double>(), nullptr,
+                                 nullptr, &m));
+    HIPCHK(h, dm_grow(s->f_xyz, (size_t)m, 12));
+    HIPCHK(h, dm_grow(s->f_nrm, (size_t)m, 12));
+    HIPCHK(h, dm_grow(s->f_fpfh, (size_t)m, 33 * 8));
+    k_cast_cloud_f64<<<grid_for(m), 256, 0, h->stream>>>(s->f_xyz64.as<double>(), nullptr, nullptr, m, s->f_xyz.as<float>(), nullptr,
+                                                         nullptr);
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    reg_normals_out no;
+    std::memset(&no, 0, sizeof(no));
+    no.normals = s->f_nrm.as<float>();
+    const float origin[3] = {0.f, 0.f, 0.f};   // OrientNormalsTowardsCameraLocation(Zero), Submap.cpp:271
+    REGCHK(reg_estimate_normals(h, s->f_xyz.as<float>(), 3, m, 1, fp->normal_knn, (float)fp->normal_radius, origin, 0, &no, nullptr));
+    REGCHK(reg_compute_fpfh(h, s->f_xyz.as<float>(), 3, s->f_nrm.as<float>(), 3, m, 1, fp->feature_knn, (float)fp->feature_radius,
+                            s->f_fpfh.as<double>(), nullptr, nullptr, nullptr));
+    *n_sparse = m;
+    return REG_OK;
+}
+
+reg_status reg_submaps_compute_features(reg_submaps* s, int32_t idx, double now_seconds, const reg_submap_feature_params* fp,
+                                        int on_device, float* sparse_xyz, float* sparse_normals, double* fpfh,
+                                        int64_t capacity_rows, int64_t* n_sparse, int32_t* computed) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (computed) *computed = 0;
+    if (n_sparse) *n_sparse = 0;
+    if (!sm_idx_ok(s, idx) || now_seconds != now_seconds ||
+        (fp && (fp->struct_size != (int32_t)sizeof(*fp) || !(fp->feature_voxel_size > 0.0) || !std::isfinite(fp->feature_voxel_size) ||
+                fp->normal_knn < 1 || fp->normal_knn > kPcaMaxK || !(fp->normal_radius > 0.0) || fp->feature_knn < 2 ||
+                fp->feature_knn > kFpfhMaxNn || !(fp->feature_radius > 0.0) || !std::isfinite(fp->feature_radius) || capacity_rows < 0))) {
+        h->err = "reg_submaps_compute_features: an unknown submap index, a NaN clock, or feature params of the wrong struct_size, "
+                 "voxel size / radii not finite and > 0, normal_knn outside [1, 32], feature_knn outside [2, 128], capacity_rows < 0";
+        return REG_BAD_ARGUMENT;
+    }
+    SmSubmap& b = *s->subs[idx];
+    if (b.has_features && now_seconds - b.feature_clock < s->prm.min_seconds_between_features) return REG_OK;   // Submap.cpp:256-258
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    int64_t m = 0;
+    if (fp) {   // sparseMapCloud_ and feature_ (Submap.cpp:266-272)
+        REGCHK(sm_features(s, b, fp, &m));
+        if (m > capacity_rows) {
+            h->err = "reg_submaps_compute_features: capacity_rows is below the rows of the sparse cloud";
+            return REG_BAD_ARGUMENT;
+        }
+    }
+    REGCHK(sm_build_keys(s, b));   // voxelMap_.clear(); voxelMap_.insertCloud(...)
+    if (m > 0) {
+        HIPCHK(h, copy_out(h, sparse_xyz, s->f_xyz.p, (size_t)m * 12, on_device));
+        HIPCHK(h, copy_out(h, sparse_normals, s->f_nrm.p, (size_t)m * 12, on_device));
+        HIPCHK(h, copy_out(h, fpfh, s->f_fpfh.p, (size_t)m * 33 * 8, on_device));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    b.has_features = true;
+    b.feature_clock = now_seconds;   // featureTimer_.reset()
+    if (n_sparse) *n_sparse = m;
+    if (computed) *computed = 1;
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_keys(reg_submaps* s, int32_t idx, uint64_t* keys, int64_t capacity_rows, int64_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (n_out) *n_out = 0;
+    if (!sm_idx_ok(s, idx) || (keys && capacity_rows < s->subs[idx]->n_keys)) {
+        s->h->err = "reg_submaps_get_keys: an unknown submap index, or capacity_rows below the number of keys";
+        return REG_BAD_ARGUMENT;
+    }
+    const SmSubmap& b = *s->subs[idx];
+    if (n_out) *n_out = b.n_keys;
+    if (!keys || b.n_keys == 0) return REG_OK;
+    reg_handle* h = s->h;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, hipMemcpyAsync(keys, b.keys[b.cur].p, (size_t)b.n_keys * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return REG_OK;
+}
+
+reg_status reg_submaps_switch_fitness(reg_submaps* s, int32_t idx, const double* scan_xyz, int64_t n, int on_device,
+                                      const double T[16], int64_t* count, double* fitness) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (!sm_idx_ok(s, idx) || !T || !dm_cloud_args_ok(scan_xyz, n)) {
+        h->err = "reg_submaps_switch_fitness: an unknown submap index, T missing, or not 0 <= n <= 2^31 - 1 with points for n > 0";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d = scan_xyz;
+    if (n > 0) HIPCHK(h, staged_input(h, h->mc_in[0], d, (size_t)n * 3, on_device, &d));
+    int64_t c = 0;
+    double f = 0.0;
+    REGCHK(sm_fitness(s, *s->subs[idx], d, n, T, &c, &f));
+    if (count) *count = c;
+    if (fitness) *fitness = f;
+    return REG_OK;
+}
+
+reg_status reg_submaps_set_target(reg_submaps* s, const reg_crop* crop, int64_t* n_kept) {
+    if (!s) return REG_BAD_ARGUMENT;
+    return reg_map_cloud_set_target(s->subs[s->active]->map, crop, n_kept);
+}
+
+reg_status reg_submaps_export_submap(reg_submaps* s, int32_t idx, int on_device, double* xyz, double* normals, double* covs,
+                                     int64_t capacity_rows, int64_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (n_out) *n_out = 0;
+    if (!sm_idx_ok(s, idx)) {
+        s->h->err = "reg_submaps_export_submap: an unknown submap index";
+        return REG_BAD_ARGUMENT;
+    }
+    return reg_map_cloud_export(s->subs[idx]->map, on_device, xyz, normals, covs, capacity_rows, n_out);
+}
+
+reg_status reg_submaps_export(reg_submaps* s, int on_device, double* xyz, double* normals, double* covs, int64_t capacity_rows,
+                              int64_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (n_out) *n_out = 0;
+    int64_t total = 0;
+    for (const auto& b : s->subs) total += b->map->n;
+    if (capacity_rows < total) {
+        s->h->err = "reg_submaps_export: capacity_rows is below the number of rows";
+        return REG_BAD_ARGUMENT;
+    }
+    int64_t off = 0;
+    for (const auto& b : s->subs) {
+        int64_t k = 0;
+        REGCHK(reg_map_cloud_export(b->map, on_device, xyz ? xyz + 3 * off : nullptr, normals ? normals + 3 * off : nullptr,
+                                    covs ? covs + 9 * off : nullptr, capacity_rows - off, &k));
+        off += k;
+    }
+    if (n_out) *n_out = off;
+    return REG_OK;
+}
+
+reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const double* dT, int32_t n) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    const int32_t ns = (int32_t)s->subs.size();
+    if (n < 0 || (n > 0 && (!ids || !dT))) {
+        h->err = "reg_submaps_transform: n < 0, or ids / dT missing";
+        return REG_BAD_ARGUMENT;
+    }
+    std::vector<int32_t> parents(ns), plan(ns);
+    for (int32_t i = 0; i < ns; ++i) parents[i] = s->subs[i]->parent;
+    const reg_status st = reg_host_submaps_transform_plan(parents.data(), ns, ids, n, plan.data());
+    if (st != REG_OK) {
+        h->err = "reg_submaps_transform: stuck in a loop (an unlisted submap whose parent chain ends at an unlisted root), or a "
+                 "parent index beyond the list of increments";
+        return st;
+    }
+    auto apply = [&](SmSubmap& b, const double* T) -> reg_status {   // Submap::transform (Submap.cpp:115-128)
+        REGCHK(reg_map_cloud_transform(b.map, T));
+        double m[16], c[3];
+        sm_mul(b.T_sensor, T, m);
+        std::memcpy(b.T_sensor, m, sizeof(m));
+        for (int r = 0; r < 3; ++r) {
+            double v = T[r] * b.center[0] + T[4 + r] * b.center[1];
+            v = v + T[8 + r] * b.center[2];
+            c[r] = v + T[12 + r];
+        }
+        for (int r = 0; r < 3; ++r) b.center[r] = c[r];
+        return REG_OK;
+    };
+    for (int32_t k = 0; k < n; ++k)   // the listed ones, in list order
+        if (ids[k] >= 0 && ids[k] < ns) REGCHK(apply(*s->subs[ids[k]], dT + 16 * (size_t)k));
+    std::vector<char> listed(ns, 0);
+    for (int32_t k = 0; k < n; ++k)
+        if (ids[k] >= 0 && ids[k] < ns) listed[ids[k]] = 1;
+    for (int32_t i = 0; i < ns; ++i)
+        if (!listed[i] && plan[i] >= 0) REGCHK(apply(*s->subs[i], dT + 16 * (size_t)plan[i]));
+    s->ring.clear();   // :372
+    return REG_OK;
+}
+
+reg_status reg_submaps_add_loop_closure_edges(reg_submaps* s, const int32_t* source, const int32_t* target, int32_t n) {
+    if (!s) return REG_BAD_ARGUMENT;
+    bool ok = n >= 0 && (n == 0 || (source && target));
+    for (int32_t k = 0; ok && k < n; ++k) ok = sm_idx_ok(s, source[k]) && sm_idx_ok(s, target[k]);
+    if (!ok) {
+        s->h->err = "reg_submaps_add_loop_closure_edges: n < 0, arrays missing, or an unknown submap id";
+        return REG_BAD_ARGUMENT;
+    }
+    for (int32_t k = 0; k < n; ++k) {   // SubmapCollection.cpp:75-81
+        sm_add_edge(s, source[k], target[k]);
+        s->marks[source[k]] = s->marks[target[k]] = 1;
+    }
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_adjacency(const reg_submaps* s, uint8_t* adj, int32_t* marks, int32_t capacity) {
+    if (!s || capacity < (int32_t)s->subs.size()) return REG_BAD_ARGUMENT;
+    if (adj) std::memset(adj, 0, (size_t)capacity * capacity);
+    for (int32_t i = 0; i < capacity; ++i) {
+        const bool known = i < (int32_t)s->subs.size();
+        if (marks) marks[i] = known ? s->marks[i] : -1;
+        if (adj && known)
+            for (int32_t j : s->adj[i]) adj[(size_t)i * capacity + j] = 1;
+    }
+    return REG_OK;
+}
+
+static reg_status sm_pop(reg_submaps* s, std::vector<SmStamped>& q, int32_t* ids, int64_t* stamps, int32_t capacity, int32_t* n_out) {
+    if (n_out) *n_out = 0;
+    if (capacity < (int32_t)q.size() || (!q.empty() && !ids)) {
+        s->h->err = "reg_submaps_pop_*: capacity below the entries of the queue, or ids missing";
+        return REG_BAD_ARGUMENT;
+    }
+    for (size_t k = 0; k < q.size(); ++k) {
+        ids[k] = q[k].id;
+        if (stamps) stamps[k] = q[k].stamp;
+    }
+    if (n_out) *n_out = (int32_t)q.size();
+    q.clear();
+    return REG_OK;
+}
+reg_status reg_submaps_pop_finished(reg_submaps* s, int32_t* ids, int64_t* stamps_ns, int32_t capacity, int32_t* n_out) {
+    return s ? sm_pop(s, s->finished, ids, stamps_ns, capacity, n_out) : REG_BAD_ARGUMENT;
+}
+reg_status reg_submaps_pop_loop_closure_candidates(reg_submaps* s, int32_t* ids, int64_t* stamps_ns, int32_t capacity,
+                                                   int32_t* n_out) {
+    return s ? sm_pop(s, s->candidates, ids, stamps_ns, capacity, n_out) : REG_BAD_ARGUMENT;
+}
+reg_status reg_submaps_push_loop_closure_candidate(reg_submaps* s, int32_t id, int64_t stamp_ns) {
+    if (!s || !sm_idx_ok(s, id)) return REG_BAD_ARGUMENT;
+    s->candidates.push_back(SmStamped{id, stamp_ns});
+    return REG_OK;
+}
+
+reg_status reg_submaps_loop_closure_candidates(const reg_submaps* s, int32_t last, int32_t* out, int32_t capacity, int32_t* n_out) {
+    if (!s || !n_out || !sm_idx_ok(s, last) || capacity < 0 || (capacity > 0 && !out)) return REG_BAD_ARGUMENT;
+    *n_out = 0;
+    const int32_t ns = (int32_t)s->subs.size();
+    std::vector<uint8_t> adj((size_t)ns * ns);
+    std::vector<int32_t> marks(ns);
+    (void)reg_submaps_get_adjacency(s, adj.data(), marks.data(), ns);
+    const double max_d = s->prm.loop_closure_search_radius;
+    const int threshold = (int)std::ceil(max_d / s->prm.radius);
+    std::vector<int32_t> found;
+    for (int32_t i = 0; i < ns; ++i) {   // PlaceRecognition.cpp:239-282
+        if (i == s->active) continue;
+        if (sm_adjacent(s, s->subs[i]->id, s->subs[s->active]->id)) continue;
+        if (std::abs(i - last) == 1 || sm_adjacent(s, i, last)) continue;
+        if (sm_dist(sm_center(*s->subs[last]), sm_center(*s->subs[i])) > max_d) continue;
+        if (std::abs(i - last) <= threshold) continue;
+        const int32_t d = reg_host_adjacency_distance(adj.data(), marks.data(), ns, last);
+        if (d < 0) return REG_BAD_ARGUMENT;   // the reference would throw: last_finished has no entry in the matrix
+        if (d < s->prm.min_submaps_between_loop_closures) continue;
+        found.push_back(i);
+    }
+    if ((int32_t)found.size() > capacity) return REG_BAD_ARGUMENT;
+    for (size_t k = 0; k < found.size(); ++k) out[k] = found[k];
+    *n_out = (int32_t)found.size();
+    return REG_OK;
+}
+
+reg_status reg_submaps_odometry_constraint_pairs(const reg_submaps* s, const int32_t* candidates, int32_t n_candidates,
+                                                 const int32_t* existing, int32_t n_existing, int32_t* out, int32_t capacity,
+                                                 int32_t* n_out) {
+    if (!s || !n_out || n_candidates < 0 || n_existing < 0 || (n_existing > 0 && !existing) || capacity < 0 || (capacity > 0 && !out))
+        return REG_BAD_ARGUMENT;
+    *n_out = 0;
+    for (int32_t k = 0; candidates && k < n_candidates; ++k)
+        if (!sm_idx_ok(s, candidates[k])) return REG_BAD_ARGUMENT;
+    std::vector<int32_t> pairs;
+    auto has = [&](int32_t a, int32_t b) {   // hasConstraint
+        for (int32_t k = 0; k < n_existing; ++k)
+            if (existing[2 * k] == a && existing[2 * k + 1] == b) return true;
+        for (size_t k = 0; k + 1 < pairs.size(); k += 2)
+            if (pairs[k] == a && pairs[k + 1] == b) return true;
+        return false;
+    };
+    const int32_t active = s->subs[s->active]->id, count = candidates ? n_candidates : (int32_t)s->subs.size() - 1;
+    for (int32_t k = 0; k < count; ++k) {
+        const int32_t tgt = candidates ? candidates[k] : k + 1;
+        if (tgt < 1) continue;   // constraint_builders.cpp:96-98
+        const int32_t src = s->subs[tgt]->parent;
+        if (has(src, tgt)) continue;
+        if (!candidates && (src == active || tgt == active)) continue;   // :113
+        pairs.push_back(src);
+        pairs.push_back(tgt);
+    }
+    if ((int32_t)(pairs.size() / 2) > capacity) return REG_BAD_ARGUMENT;
+    for (size_t k = 0; k < pairs.size(); ++k) out[k] = pairs[k];
+    *n_out = (int32_t)(pairs.size() / 2);
+    return REG_OK;
+}
+
+}  // extern "C"

@@ -18,9 +18,11 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <memory>
 #include <mutex>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -59,6 +61,7 @@ using namespace o3dreg;
 #include "kernels_scanprep.hpp"
 #include "kernels_densemap.hpp"
 #include "kernels_mapcloud.hpp"
+#include "kernels_submaps.hpp"
 #include "kernels_odometry.hpp"
 #include "kernels_posegraph.hpp"
 
@@ -83,6 +86,7 @@ using namespace o3dreg;
 #include "host_mapcloud.hpp"
 #include "host_odometry.hpp"
 #include "host_posegraph.hpp"
+#include "host_submaps.hpp"
 
 #if O3D_SEARCH_STATS
 // diagnostic builds only: read (and clear) the search counters of reg_kernels.hpp

@@ -2833,3 +2833,308 @@ def transformSubmaps(submaps, parentIds, increments):
                 break
             if current == parentIds[current]:
                 raise RuntimeError("Stuck in a loop, this should not happen")
+
+
+# ---- the mapping thread's per-scan path: SubmapCollection and Mapper (SubmapCollection.cpp, Mapper.cpp:168-484) ----
+@dataclass
+class SubmapParameters:
+    """o3d_slam::SubmapParameters (Parameters.hpp:103-110), the place-recognition gates the collection reads, the number of
+    submaps the collection may hold and magic::voxelExpansionFactorAdjacencyBasedRevisiting."""
+    radius_: float = 20.0
+    minNumRangeData_: int = 5
+    maxNumPoints_: int = 400000
+    minSecondsBetweenFeatureComputation_: float = 5.0
+    adjacencyBasedRevisitingMinFitness_: float = 0.4
+    numScansOverlap_: int = 3
+    loopClosureSearchRadius_: float = 20.0
+    minSubmapsBetweenLoopClosures_: int = 2
+    maxSubmaps_: int = 64
+    voxelExpansionFactor_: float = 2.5
+
+
+class SubmapCollection:
+    """o3d_slam::SubmapCollection on one resident capi.Submaps: every submap's map cloud, its occupancy keys and the overlap
+    buffer stay on the device; the state machine runs inside the library (reg_submaps_insert_scan).  Built from a ScanToMapIcp
+    it shares that object's handle and map builder cropper, so that processForScanMatchingAndMergingDevice -> register ->
+    insertScan -> setAsReference never passes a cloud through the host."""
+
+    def __init__(self, scanToMap: "ScanToMapIcp | None" = None, *, reg: "capi.Registration | None" = None,
+                 params: "SubmapParameters | None" = None, mapVoxelSize_=0.03, mapBuilderCropper=None,
+                 carving: "SpaceCarvingParameters | None" = None, hasNormals=True, hasCovariances=False, isUseInitialMap_=False,
+                 isCarvingEnabled_=False):
+        p = params if params is not None else SubmapParameters()
+        c = carving if carving is not None else SpaceCarvingParameters()
+        if scanToMap is not None and mapBuilderCropper is None:
+            mapBuilderCropper = scanToMap.mapBuilderCropper
+        _check_crop(mapBuilderCropper, "mapBuilderCropper")
+        self.params_ = p
+        self._own = scanToMap is None and reg is None
+        if scanToMap is not None:
+            scanToMap.icp._ensure()
+            reg = scanToMap.icp._reg
+        self._reg = reg if reg is not None else _feature_handle()
+        mp = capi.default_map_cloud_params(mapBuilderCropper if mapBuilderCropper is not None else dict(type=capi.CROP_NONE),
+                                           has_normals=bool(hasNormals), has_covariances=bool(hasCovariances),
+                                           carve_every_n_scans=c.carveSpaceEveryNscans_, map_voxel_size=float(mapVoxelSize_),
+                                           carve_voxel_size=c.voxelSize_, carve_max_ray=c.maxRaytracingLength_,
+                                           carve_truncation=c.truncationDistance_, carve_min_dot=c.minDotProductWithNormal_)
+        sp = capi.default_submaps_params(
+            mp, max_submaps=p.maxSubmaps_, num_scans_overlap=p.numScansOverlap_, min_num_range_data=p.minNumRangeData_,
+            is_use_initial_map=bool(isUseInitialMap_), is_carving_enabled=bool(isCarvingEnabled_),
+            min_submaps_between_loop_closures=p.minSubmapsBetweenLoopClosures_, max_num_points=p.maxNumPoints_, radius=p.radius_,
+            revisit_min_fitness=p.adjacencyBasedRevisitingMinFitness_, voxel_expansion_factor=p.voxelExpansionFactor_,
+            min_seconds_between_features=p.minSecondsBetweenFeatureComputation_,
+            loop_closure_search_radius=p.loopClosureSearchRadius_)
+        try:
+            self.submaps = capi.Submaps(self._reg, sp)
+        except RegError as e:
+            raise InvalidParameter(str(e)) from None      # "Num scan overlap has to be > 0" among them
+        self.lastInsert_ = None
+
+    def close(self):
+        self.submaps.close()
+        if self._own:
+            self._reg.close()
+
+    def setMapToRangeSensor(self, T):
+        self.submaps.set_map_to_sensor(_check_T(T, "T"))
+
+    def getNumSubmaps(self) -> int:
+        return int(self.submaps.info().n_submaps)
+
+    def getActiveSubmapIdx(self) -> int:
+        return int(self.submaps.info().active)
+
+    def isActiveSubmapEmpty(self) -> bool:
+        return self.submaps.submap_info(self.getActiveSubmapIdx()).n_rows == 0
+
+    def getTotalNumPoints(self) -> int:
+        return int(self.submaps.info().total_points)
+
+    def insertScan(self, rawScan, preProcessedScan, mapToRangeSensor, timestamp) -> bool:
+        """SubmapCollection::insertScan.  preProcessedScan may be a DeviceCloud (then rawScan is uploaded once)."""
+        T = _check_T(mapToRangeSensor, "mapToRangeSensor")
+        if T is None:
+            raise InvalidParameter("mapToRangeSensor is missing")
+        raw = None if rawScan is None else rawScan if isinstance(rawScan, DeviceCloud) else _cloud64(rawScan, "rawScan")
+        try:
+            if isinstance(preProcessedScan, DeviceCloud) or isinstance(raw, DeviceCloud):
+                scan = preProcessedScan if isinstance(preProcessedScan, DeviceCloud) else Submap._to_device(
+                    _cloud64(preProcessedScan, "preProcessedScan"))
+                raw = raw if raw is None or isinstance(raw, DeviceCloud) else Submap._to_device(raw)
+                x, nr, cv, n = Submap._device_args(scan)
+                rp, rn = (raw.points_.data_ptr(), int(raw.n)) if raw is not None else (None, 0)
+                self.lastInsert_ = self.submaps.insert_scan_device(rp, rn, x, n, T, int(timestamp), nr, cv)
+            else:
+                scan = _cloud64(preProcessedScan, "preProcessedScan")
+                self.lastInsert_ = self.submaps.insert_scan(raw.points_ if raw is not None else None, scan.points_, T,
+                                                            int(timestamp), scan.normals_, scan.covariances_)
+        except RegError as e:
+            raise _translate(e) from None
+        return True
+
+    def forceNewSubmapCreation(self):
+        self.lastInsert_ = self.submaps.force_new_submap()
+
+    def computeFeatures(self, finishedSubmapIds, now_seconds, params: "PlaceRecognitionParameters | None" = None):
+        """SubmapCollection::computeFeatures for [(id, stamp)]: per id Submap::computeFeatures on the device from the resident
+        map (sparse cloud, normals, FPFH, occupancy set; reg_submaps_compute_features), then the id becomes a loop-closure
+        candidate.  Returns {id: (DataPoints, Feature)} of the submaps whose gate let the computation run."""
+        prm = params if params is not None else PlaceRecognitionParameters()
+        fp = capi.default_submap_feature_params(normal_knn=prm.normalKnn_, feature_knn=prm.featureKnn_,
+                                                feature_voxel_size=prm.featureVoxelSize_, normal_radius=prm.normalEstimationRadius_,
+                                                feature_radius=prm.featureRadius_)
+        out = {}
+        for idx, stamp in finishedSubmapIds:
+            try:
+                r = self.submaps.compute_features(idx, now_seconds, fp)
+            except RegError as e:
+                raise _translate(e) from None
+            if r is not None:
+                out[idx] = (DataPoints(r["xyz"], normals=r["normals"]), Feature(np.ascontiguousarray(r["fpfh"].T)))
+            self.submaps.push_loop_closure_candidate(idx, stamp)
+        return out
+
+    def popFinishedSubmapIds(self):
+        return self.submaps.pop_finished()
+
+    def popLoopClosureCandidates(self):
+        return self.submaps.pop_loop_closure_candidates()
+
+    def updateAdjacencyMatrix(self, loopClosureConstraints):
+        self.submaps.add_loop_closure_edges([(c.sourceSubmapIdx_, c.targetSubmapIdx_) for c in loopClosureConstraints])
+
+    def getLoopClosureCandidatesIdxs(self, lastFinishedSubmapIdx):
+        return self.submaps.loop_closure_candidates(lastFinishedSubmapIdx)
+
+    def getSubmapPointCloud(self, idx) -> PointCloud:
+        e = self.submaps.export_submap(idx)
+        return PointCloud(e["xyz"], e["normals"], e["covs"])
+
+    def getAssembledMapPointCloud(self) -> PointCloud:
+        e = self.submaps.export()
+        return PointCloud(e["xyz"], e["normals"], e["covs"])
+
+    def transform(self, increments):
+        """SubmapCollection::transform of [(dT, submapId)] (OptimizationProblem.getOptimizedTransformIncrements)."""
+        increments = list(increments)
+        try:
+            self.submaps.transform([i for _, i in increments], [T for T, _ in increments])
+        except RegError as e:
+            if e.status == 4:
+                raise RuntimeError("Stuck in a loop, this should not happen") from None
+            raise _translate(e) from None
+
+    def setAsReference(self, crop=None) -> int:
+        """cropSubmap + initReference of the active submap onto the handle.  Returns the rows of the patch; 0 for an empty
+        map or an empty patch (REG_EMPTY_TARGET: initReference returns false; the previous reference is gone)."""
+        _check_crop(crop, "crop")
+        try:
+            return self.submaps.set_target(crop)
+        except RegError as e:
+            if e.status == 1:
+                return 0
+            raise _translate(e) from None
+
+
+@dataclass
+class MapperParameters:
+    """What Mapper::addRangeMeasurement reads of o3d_slam::MapperParameters (Parameters.hpp:71,166,178-182)."""
+    isUseInitialMap_: bool = False
+    isMergeScansIntoMap_: bool = True
+    mapMergeDelayInSeconds_: float = 10.0
+    minMovementBetweenMappingSteps_: float = 0.0
+    referenceCloudSettingPeriod_: float = 1.0
+
+
+_TIME_MIN = -(1 << 63)
+
+
+class Mapper:
+    """o3d_slam::Mapper::addRangeMeasurement (Mapper.cpp:168-484) over a ScanToMapIcp, a SubmapCollection on the same handle and
+    the odometry buffer: the merge cloud stays on the device between the front end, the registration and the insertion.
+    Times are integer nanoseconds.  The initial guess is capi.host_mapper_initial_guess (fp64, rigid inverses).
+    Departure: the map patch is cropped (and found empty) only when the reference is re-initialised; the reference crops it
+    for every scan and uses it only then.  As in the reference, the stamp of the last re-initialisation moves only with a
+    non-empty patch, so after an empty one every following scan tries again."""
+
+    def __init__(self, scanToMap: ScanToMapIcp, submaps: SubmapCollection, odomToRangeSensorBuffer: "TransformInterpolationBuffer | None" = None,
+                 params: "MapperParameters | None" = None):
+        self.scan2MapReg_, self.submaps_ = scanToMap, submaps
+        self.params_ = params if params is not None else MapperParameters()
+        self.odomToRangeSensorBuffer_ = odomToRangeSensorBuffer if odomToRangeSensorBuffer is not None else TransformInterpolationBuffer()
+        self.mapToRangeSensorBuffer_, self.bestGuessBuffer_ = TransformInterpolationBuffer(), TransformInterpolationBuffer()
+        self.mapToRangeSensor_, self.mapToRangeSensorPrev_ = np.eye(4), np.eye(4)
+        self.mapToRangeSensorLastScanInsertion_ = np.eye(4)
+        self.calibration_, self.isCalibrationSet_ = np.eye(4), False
+        self.isNewValueSetMapper_ = self.isIgnoreOdometryPrediction_ = False
+        self.lastMeasurementTimestamp_ = self.lastReferenceInitializationTimestamp_ = _TIME_MIN
+        self.initTime_ = 0
+        self.nReferenceInitializations_ = 0
+        self.lastBranch_ = None          # the name of the branch the last call ended in
+
+    def setExternalOdometryFrameToCloudFrameCalibration(self, T):
+        self.calibration_, self.isCalibrationSet_ = _check_T(T, "calibration"), True
+
+    def setMapToRangeSensor(self, T):
+        self.mapToRangeSensor_ = _check_T(T, "T")
+
+    def setMapToRangeSensorInitial(self, T):
+        if self.isNewValueSetMapper_:
+            return
+        self.mapToRangeSensorPrev_ = self.mapToRangeSensor_ = _check_T(T, "T")
+        self.isNewValueSetMapper_ = True
+
+    def loopClosureUpdate(self, correction):
+        c = _check_T(correction, "correction")
+        self.mapToRangeSensor_, self.mapToRangeSensorPrev_ = c @ self.mapToRangeSensor_, c @ self.mapToRangeSensorPrev_
+
+    def hasProcessedMeasurements(self) -> bool:
+        return not self.mapToRangeSensorBuffer_.empty()
+
+    def getMapToRangeSensor(self, timestamp) -> np.ndarray:
+        return getTransform(timestamp, self.mapToRangeSensorBuffer_)
+
+    def getRegistrationBestGuess(self, timestamp) -> np.ndarray:
+        return getTransform(timestamp, self.bestGuessBuffer_)
+
+    def getAssembledMapPointCloud(self) -> PointCloud:
+        return self.submaps_.getAssembledMapPointCloud()
+
+    def _odom(self, time):
+        return getTransform(time, self.odomToRangeSensorBuffer_)
+
+    def _end(self, name, value):
+        self.lastBranch_ = name
+        return value
+
+    def addRangeMeasurement(self, rawScan, timestamp) -> bool:
+        p, timestamp = self.params_, int(timestamp)
+        if not p.isUseInitialMap_ and not self.isCalibrationSet_:                 # Mapper.cpp:169-174
+            return self._end("calibration_not_set", False)
+        self.submaps_.setMapToRangeSensor(self.mapToRangeSensor_)
+        if self.submaps_.isActiveSubmapEmpty():                                   # :179-194
+            if p.isUseInitialMap_:
+                self.submaps_.insertScan(rawScan, rawScan, self.mapToRangeSensor_, timestamp)
+                return self._end("first_scan_initial_map", True)
+            self.mapToRangeSensorPrev_ = self.mapToRangeSensor_
+            merge = self.scan2MapReg_.processForScanMatchingAndMergingDevice(rawScan)
+            self.submaps_.insertScan(rawScan, merge, self.mapToRangeSensor_, timestamp)
+            self.mapToRangeSensorBuffer_.push(timestamp, self.mapToRangeSensor_)
+            self.bestGuessBuffer_.push(timestamp, self.mapToRangeSensor_)
+            return self._end("first_scan", True)
+        guess = lambda now: capi.host_mapper_initial_guess(self.mapToRangeSensorPrev_, self._odom(self.lastMeasurementTimestamp_),
+                                                           self._odom(now), self.calibration_)
+        if timestamp <= self.lastMeasurementTimestamp_:                           # :196-235: propagate by the latest odometry
+            latest = self.odomToRangeSensorBuffer_.latest_time()
+            self.mapToRangeSensor_ = guess(latest)
+            self.mapToRangeSensorBuffer_.push(latest, self.mapToRangeSensor_)
+            self.bestGuessBuffer_.push(latest, self.mapToRangeSensorPrev_)
+            self.submaps_.setMapToRangeSensor(self.mapToRangeSensor_)
+            self.mapToRangeSensorPrev_ = self.mapToRangeSensor_
+            return self._end("out_of_order", True)
+        isOdomOkay = self.odomToRangeSensorBuffer_.has(timestamp)                 # :237-241
+        estimate = self.mapToRangeSensorPrev_
+        if isOdomOkay and not self.isNewValueSetMapper_ and not self.isIgnoreOdometryPrediction_:   # :248-260
+            estimate = guess(timestamp)
+        self.isIgnoreOdometryPrediction_ = False
+        merge = self.scan2MapReg_.processForScanMatchingAndMergingDevice(rawScan)   # match_ is the reading on the handle
+        d = timestamp - self.lastReferenceInitializationTimestamp_                # :325-326: whole milliseconds, truncated
+        passed = (d // 1_000_000 if d >= 0 else -((-d) // 1_000_000)) / 1e3
+        if self.isNewValueSetMapper_ or passed >= p.referenceCloudSettingPeriod_:  # :329-347
+            cropper = self.scan2MapReg_.scanMatcherCropper
+            crop = None if cropper is None else dict(cropper, center=tuple(float(v) for v in self.mapToRangeSensor_[:3, 3]))
+            if self.submaps_.setAsReference(crop) == 0:                           # any other error is raised, not swallowed
+                return self._end("empty_map_patch", False)                        # :310-316, :343-346
+            self.lastReferenceInitializationTimestamp_ = timestamp                # :341: only with a non-empty patch
+            self.nReferenceInitializations_ += 1
+        corrected, branch = np.asarray(estimate, np.float32), "registered"
+        try:
+            corrected = self.scan2MapReg_.register(corrected)[0]                  # :372-373
+        except RuntimeError:
+            branch = "icp_exception"                                              # :400-402: the initial guess stays
+        if self.isNewValueSetMapper_:                                             # :420-435
+            self.initTime_ = timestamp
+            self.mapToRangeSensorPrev_ = self.mapToRangeSensor_
+            self.mapToRangeSensorBuffer_.push(timestamp, self.mapToRangeSensor_)
+            self.bestGuessBuffer_.push(timestamp, estimate)
+            self.isNewValueSetMapper_, self.isIgnoreOdometryPrediction_ = False, True
+            return self._end("new_value_set", True)
+        self.mapToRangeSensor_ = np.asarray(corrected, np.float64)                # :438-442
+        self.mapToRangeSensorBuffer_.push(timestamp, self.mapToRangeSensor_)
+        self.bestGuessBuffer_.push(timestamp, estimate)
+        self.submaps_.setMapToRangeSensor(self.mapToRangeSensor_)
+        sinceInit = (timestamp - self.initTime_) * 1e-9
+        if p.isUseInitialMap_ and (not p.isMergeScansIntoMap_ or sinceInit < p.mapMergeDelayInSeconds_):   # :445-459
+            self.lastMeasurementTimestamp_, self.mapToRangeSensorPrev_ = timestamp, self.mapToRangeSensor_
+            return self._end("merge_delay", True)
+        L, M = self.mapToRangeSensorLastScanInsertion_, self.mapToRangeSensor_    # :463-469: |R_L^T (t_M - t_L)|
+        d = M[:3, 3] - L[:3, 3]
+        m = [(L[0, i] * d[0] + L[1, i] * d[1]) + L[2, i] * d[2] for i in range(3)]
+        if not math.sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]) < p.minMovementBetweenMappingSteps_:
+            self.submaps_.insertScan(rawScan, merge, self.mapToRangeSensor_, timestamp)
+            self.mapToRangeSensorLastScanInsertion_ = self.mapToRangeSensor_
+        else:
+            branch += "_moved_too_little"
+        self.lastMeasurementTimestamp_, self.mapToRangeSensorPrev_ = timestamp, self.mapToRangeSensor_
+        return self._end(branch, True)
