@@ -225,6 +225,23 @@ def solve_longdouble(A, b):
     return np.array(y, np.float64)
 
 
+def first_bad_pivot(A):
+    """(row, pivots) of the unblocked long-double Cholesky of A's lower triangle: the first row whose pivot is not positive
+    and finite (-1: none) and the pivots up to and including it."""
+    n = A.shape[0]
+    L = np.tril(np.array(A, np.longdouble))
+    pivots = []
+    for j in range(n):
+        if j:
+            L[j:, j] = L[j:, j] - L[j:, :j] @ L[j, :j]
+        pivots.append(float(L[j, j]))
+        if not (L[j, j] > 0 and L[j, j] < np.inf):
+            return j, pivots
+        L[j, j] = np.sqrt(L[j, j])
+        L[j + 1:, j] = L[j + 1:, j] / L[j, j]
+    return -1, pivots
+
+
 SOLVERS = {"numpy": solve_numpy, "cho": solve_cho, "longdouble": solve_longdouble}
 
 

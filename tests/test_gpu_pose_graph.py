@@ -6,14 +6,18 @@ every element is summed in edge order; two calls give identical bytes.
 Solver (reg_debug_spd_solve_f64): the bar is the normwise backward error |A x - b| / (|A| |x| + |b|), 8 x the largest value
 scipy.linalg.cho_solve reaches on the same systems (tests/pose_graph_cases.py: CHO_BACKWARD_ERRORS, largest 2.8e-17, so the
 bar is 2.24e-16; tests/test_pose_graph_host.py repeats that measurement).  The factor 8 is the margin for another blocking
-and summation order.
+and summation order.  A second table (more_solver_systems(): one and two nodes, whole tiles without padding, a trailing region
+starting in mid-tile, condition number 1e10) is held to the same bar, its reference at most an eighth of it per system; systems
+with exact answers and a scaling by powers of four are compared bit for bit, and the pivot word is the exact row + 1.
 
 LM pass and GlobalOptimization: outer iterations, LM solves, accepted steps, stop reasons and the surviving edge set are
 EQUAL to the restatement's; residuals (relative), confidences and compensated poses (absolute) are within 16 x the largest
 spread between the restatement's own three solvers on that case (SOLVER_SPREADS in tests/pose_graph_cases.py, measured on
 the host; not the device's own spread).  Poses are compared after the reference compensation only: H has a gauge direction.
 tests/test_pose_graph_host.py checks the precondition (the same decisions under all three solvers, every decision a relative
-1e-6 away from its border) on every case used here."""
+1e-6 away from its border) on every case used here.  lm_branch_cases() brings the branches and sizes cases (a) to (f) do not
+reach: rejected steps, both iteration caps, more than 256 edges, M = Mp, more than 256 nodes.  A pass that meets a bad pivot
+fails with REG_BAD_TRANSFORM, names the row and leaves the graph and the object as they were."""
 import numpy as np
 import pytest
 
@@ -36,7 +40,7 @@ def reg():
 
 @pytest.fixture(scope="module")
 def cases():
-    return {c.name: c for c in K.lm_cases() + [K.large_case()]}
+    return {c.name: c for c in K.lm_cases() + [K.large_case()] + K.lm_branch_cases()}
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +64,7 @@ def _set(pg, g):
 
 
 # ---- edge kernel and assembly -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["b_ring", "c_ring_wrong", "e_double", "g_large"])
+@pytest.mark.parametrize("name", ["b_ring", "c_ring_wrong", "e_double", "g_large", "k_dense", "m_nodes_257"])
 def test_linearize_equals_the_restatement(reg, cases, name):
     case = cases[name]
     g = case.graph
@@ -97,10 +101,57 @@ def test_solver_reports_a_bad_pivot_and_recovers(reg):
     bad = A.copy()
     bad[50, 50] = -1.0
     x, status = capi.debug_spd_solve(reg, bad, b)
-    assert x is None and 1 <= status <= 51                # 1 + the row of the first pivot that is not positive
+    assert x is None and status == 51                     # 1 + the row of the first pivot that is not positive
     assert "pivot of row" in reg.last_error()
     x, status = capi.debug_spd_solve(reg, A, b)           # the next solve on the same handle is correct
     assert status == 0 and K.backward_error(A, x, b) <= K.SOLVER_BAR
+
+
+def test_solver_backward_error_of_the_further_systems(reg):
+    """One and two nodes, whole tiles without padding (96, 192, 288), three panels with the trailing region starting in
+    mid-tile (144), two tiles plus 6 (198), and a graded system of condition number 1e10: all held to SOLVER_BAR."""
+    worst = {}
+    for name, A, b in K.more_solver_systems():
+        x, status = capi.debug_spd_solve(reg, A, b)
+        assert status == 0 and x is not None, name
+        worst[name] = K.backward_error(A, x, b)
+        x2, _ = capi.debug_spd_solve(reg, A, b)
+        assert x.tobytes() == x2.tobytes(), name          # run-to-run bit equality
+    print("backward errors:", {k: f"{v:.3g}" for k, v in worst.items()}, f"bar {K.SOLVER_BAR:.3g}")
+    for name, v in worst.items():
+        assert v <= K.SOLVER_BAR, (name, v)
+
+
+@pytest.mark.parametrize("n", [54, 198])
+def test_solver_is_exact_where_the_arithmetic_is(reg, n):
+    """The identity, diag(4^k) and a zero right-hand side, with identity padding beside the data (Mp = 96 and 288)."""
+    for name, A, b, want in K.exact_systems(n):
+        x, status = capi.debug_spd_solve(reg, A, b)
+        assert status == 0 and np.array_equal(x, want), name
+
+
+def test_solver_commutes_with_scaling_by_powers_of_four(reg):
+    """Every operation of a Cholesky solve commutes with A -> 4^20 A, b -> 4^-10 b (L scales by 2^20, exactly); an absolute
+    threshold hidden in the solver would not."""
+    A, b = K.spd_system(102, 202)
+    x, status = capi.debug_spd_solve(reg, A, b)
+    xs, status_s = capi.debug_spd_solve(reg, 4.0 ** 20 * A, 4.0 ** -10 * b)
+    assert status == 0 and status_s == 0
+    assert np.array_equal(xs, 4.0 ** -30 * x)
+
+
+def test_solver_names_the_row_of_the_bad_pivot(reg):
+    """status == r + 1 exactly: a pivot of -1 at the first and last row of the panels at the tile borders of a 198-row
+    system, a NaN and +inf on the diagonal, a NaN below it that reaches pivot r first; each is followed by a correct solve."""
+    good, b = K.spd_system(198, 298)
+    systems = [(f"row_{r}", r, K.bad_pivot_system(r)[0]) for r in K.BAD_PIVOT_ROWS] + \
+        [(name, 100, A) for name, A, _ in K.poisoned_systems(100)]
+    for name, r, A in systems:
+        x, status = capi.debug_spd_solve(reg, A, b)
+        assert x is None and status == r + 1, (name, status)
+        assert f"pivot of row {r} " in reg.last_error(), name
+        x, status = capi.debug_spd_solve(reg, good, b)
+        assert status == 0 and K.backward_error(good, x, b) <= K.SOLVER_BAR, name
 
 
 # ---- LM pass and GlobalOptimization --------------------------------------------------------------------------------------------------
@@ -115,9 +166,15 @@ def _close_rel(a, b, bar):
 
 
 LM_NAMES = ["a_chain", "b_ring", "c_ring_wrong", "d_certain", "e_double", "f_one_node", "f_two_nodes"]
+# rejected steps (certain and uncertain closures), the two iteration caps, E = 289 > 256, M = 288 = Mp, n = 257 > 256
+BRANCH_NAMES = ["h_rough_start", "h_rough_far", "i_cap_lm", "j_cap_outer", "k_dense", "l_three_tiles", "m_nodes_257"]
 
 
-@pytest.mark.parametrize("name", LM_NAMES)
+def test_the_branch_names_are_the_branch_cases():
+    assert BRANCH_NAMES == [c.name for c in K.lm_branch_cases()]
+
+
+@pytest.mark.parametrize("name", LM_NAMES + BRANCH_NAMES)
 def test_global_optimization_equals_the_restatement(reg, cases, oracle, name):
     case = cases[name]
     want, wres = oracle[name]
@@ -141,19 +198,27 @@ def test_global_optimization_equals_the_restatement(reg, cases, oracle, name):
 
 
 def test_one_pass_equals_the_restatement(reg, cases):
-    """reg_pose_graph_optimize: one pass, no prune, no compensation; every edge stays, the wrong closure with its low confidence."""
-    case = cases["c_ring_wrong"]
-    g = case.graph.copy()
-    want = R.lm_pass(g, case.option, case.criteria, R.solve_numpy)
-    with capi.PoseGraph(reg, _params(case)) as pg:
-        _set(pg, case.graph)
-        res = pg.optimize()
-        got = pg.get()
-    assert _stats(res) == _stats(want)
-    assert got["src"].shape[0] == case.graph.E
-    low = got["confidence"] <= case.option.edge_prune_threshold
-    assert list(np.flatnonzero(low)) == list(case.wrong)
-    assert list(got["ids"]) == list(range(case.graph.E))
+    """reg_pose_graph_optimize: one pass, no prune, no compensation; every edge stays, the wrong closure with its low
+    confidence.  h_rough_far rejects steps on the way (17 solves in 13 outer iterations); the residuals (gauge-free) are held
+    to the case's bar."""
+    for name in ("c_ring_wrong", "h_rough_far"):
+        case = cases[name]
+        g = case.graph.copy()
+        want = R.lm_pass(g, case.option, case.criteria, R.solve_numpy)
+        with capi.PoseGraph(reg, _params(case)) as pg:
+            _set(pg, case.graph)
+            res = pg.optimize()
+            got = pg.get()
+        print(name, _stats(res), _stats(want), res.first_residual, want["first_residual"], res.last_residual, want["last_residual"])
+        assert _stats(res) == _stats(want), name
+        assert got["src"].shape[0] == case.graph.E
+        low = got["confidence"] <= case.option.edge_prune_threshold
+        assert list(np.flatnonzero(low)) == list(case.wrong), name
+        assert list(got["ids"]) == list(range(case.graph.E))
+        res_bar = K.LM_BAR_FACTOR * K.SOLVER_SPREADS[name][2]
+        assert _close_rel(res.first_residual, want["first_residual"], res_bar), name
+        assert _close_rel(res.last_residual, want["last_residual"], res_bar), name
+    assert want["lm_solves"] > want["outer_iterations"]
 
 
 def test_the_object_is_reusable(reg, cases):
@@ -167,12 +232,60 @@ def test_the_object_is_reusable(reg, cases):
         _set(pg, a.graph)
         r2 = pg.global_optimize()
         second = pg.get()
+        c = cases["h_rough_start"]        # rejected steps in between: discarded trials stay in the other side's buffers
+        assert bytes(_params(c)) == bytes(_params(a))     # the object was created with a's parameters
+        with capi.PoseGraph(reg, _params(c)) as fresh:
+            _set(fresh, c.graph)
+            rc = fresh.global_optimize()
+        _set(pg, c.graph)
+        rc2 = pg.global_optimize()
+        _set(pg, a.graph)
+        r3 = pg.global_optimize()
+        third = pg.get()
         info = pg.info()
-    for k in ("poses", "src", "tgt", "confidence"):
-        assert first[k].tobytes() == second[k].tobytes(), k
-    for x, y in zip(r1, r2):
+    assert rc2[0].lm_solves > rc2[0].outer_iterations
+    for x, y in zip(rc, rc2):
         assert bytes(x) == bytes(y)
+    for k in ("poses", "src", "tgt", "confidence"):
+        assert first[k].tobytes() == second[k].tobytes() == third[k].tobytes(), k
+    for x, y, z in zip(r1, r2, r3):
+        assert bytes(x) == bytes(y) == bytes(z)
     assert info.solver_rows == 192 and info.device_bytes > 0       # 180 rows padded to two trailing tiles, kept
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["n_two_negative", "n_certain_negated"])
+def test_a_bad_pivot_fails_the_pass_and_leaves_the_graph(reg, cases, which):
+    """The header's promise: REG_BAD_TRANSFORM, reg_last_error names the row, the graph stays as it was set, and the object
+    goes on working.  The row is that of the first pivot <= 0 of a long-double Cholesky of the restatement's H + lambda I
+    (tests/test_pose_graph_host.py: every pivot up to it is at least 1e-6 x max diag H in magnitude)."""
+    case = K.indefinite_cases()[which]
+    g = case.graph
+    row, _ = R.first_bad_pivot(K.first_lm_system(case)[0])
+    assert row >= 0
+    after = cases["c_ring_wrong"]
+    assert bytes(_params(case)) == bytes(_params(after))      # one object serves both graphs
+    with capi.PoseGraph(reg, _params(after)) as fresh:
+        _set(fresh, after.graph)
+        want_res = fresh.global_optimize()
+        want = fresh.get()
+    for run in ("optimize", "global_optimize"):
+        with capi.PoseGraph(reg, _params(case)) as pg:
+            _set(pg, g)
+            with pytest.raises(capi.RegError) as e:
+                getattr(pg, run)()
+            assert e.value.status == 4, run                        # REG_BAD_TRANSFORM
+            assert f"pivot of row {row} " in reg.last_error(), (run, reg.last_error())
+            got = pg.get()
+            assert got["poses"].tobytes() == g.poses.tobytes() and got["confidence"].tobytes() == g.confidence.tobytes()
+            assert np.array_equal(got["src"], g.src) and np.array_equal(got["tgt"], g.tgt)
+            assert list(got["ids"]) == list(range(g.E))
+            _set(pg, after.graph)                                  # recovery on the same object
+            res = pg.global_optimize()
+            back = pg.get()
+        for k in ("poses", "src", "tgt", "confidence"):
+            assert back[k].tobytes() == want[k].tobytes(), (run, k)
+        for x, y in zip(res, want_res):
+            assert bytes(x) == bytes(y), run
 
 
 def test_validation_runs_before_any_device_work(reg, cases):
