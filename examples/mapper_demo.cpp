@@ -5,6 +5,8 @@
 // (radius, minNumRangeData, maxNumPoints, numScansOverlap, minFitness, maxSubmaps, mapVoxel, carveEvery, carveVoxel,
 // mapCropRadius, matchCropRadius, scanVoxel, knn, knnRadius, referencePeriod, carvingEnabled, featureMask); double calib[16];
 // double start[16]; per scan: int64 stamp, int64 pushOdometry, double odom[16], int64 n, double xyz[3 n].
+// With a second argument `constraints` the odometry constraints of the finished pairs are built on the resident maps
+// (SubmapCollection::computeOdometryConstraints) and printed before the final line.
 #include "../include/o3dslam_icp.hpp"
 
 #include <cstdio>
@@ -14,7 +16,7 @@ template <class T>
 static bool rd(FILE* f, T* out, size_t n) { return std::fread(out, sizeof(T), n, f) == n; }
 
 int main(int argc, char** argv) {
-    if (argc < 2) return std::fprintf(stderr, "usage: mapper_demo WALK_FILE\n"), 2;
+    if (argc < 2) return std::fprintf(stderr, "usage: mapper_demo WALK_FILE [constraints]\n"), 2;
     FILE* f = std::fopen(argv[1], "rb");
     if (!f) return std::fprintf(stderr, "cannot open %s\n", argv[1]), 2;
     int64_t nScans = 0;
@@ -66,6 +68,16 @@ int main(int argc, char** argv) {
         }
         const auto cloud = mapper.getAssembledMapPointCloud();
         std::printf("MAP %lld %d\n", (long long)cloud.size(), (int)mapper.mapToRangeSensorBuffer().size());
+        if (argc > 2 && std::string(argv[2]) == "constraints") {   // optional last step: the odometry constraints of the finished pairs
+            const int32_t added = submaps.computeOdometryConstraints();
+            std::printf("CONSTRAINTS %d\n", added);
+            for (const auto& c : submaps.getOdometryConstraints()) {
+                std::printf("ODOMETRY %d %d %d", c.sourceSubmapIdx, c.targetSubmapIdx, c.isInformationMatrixValid ? 1 : 0);
+                for (double v : c.sourceToTarget) std::printf(" %a", v);
+                for (double v : c.informationMatrix) std::printf(" %a", v);
+                std::printf("\n");
+            }
+        }
         std::printf("OK\n");
     } catch (const std::exception& e) {
         std::fprintf(stderr, "mapper_demo: %s\n", e.what());

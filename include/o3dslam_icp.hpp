@@ -1276,6 +1276,77 @@ public:
         out.resize((size_t)n);
         return out;
     }
+    // ---- pose-graph constraints from the resident maps ----
+    struct Constraint {   // o3d_slam::Constraint
+        int32_t sourceSubmapIdx = 0, targetSubmapIdx = 0;
+        double sourceToTarget[16];      // column-major
+        double informationMatrix[36];
+        bool isInformationMatrixValid = false, isOdometryConstraint = false;
+        int64_t timestampNs = 0;
+    };
+    reg_constraint_params odometryConstraintParams(bool refine = false) const {
+        reg_constraint_params p{};
+        check(reg_default_odometry_constraint_params(s_, refine ? 1 : 0, &p));
+        return p;
+    }
+    // buildConstraint / the loop-closure refinement between two resident submaps; initial == nullptr: the identity
+    reg_constraint_result buildConstraint(int32_t source, int32_t target, const reg_constraint_params& params,
+                                          const double* initial = nullptr) {
+        reg_constraint_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_submaps_build_constraint(s_, source, target, &params, initial, &r));
+        return r;
+    }
+    Constraint buildOdometryConstraint(int32_t source, int32_t target, bool refine = false) {
+        return constraintOf(buildConstraint(source, target, odometryConstraintParams(refine)), true, 0);
+    }
+    // computeOdometryConstraints into the collection's own list: of the candidates, or (no argument) of every finished pair
+    int32_t computeOdometryConstraints(const std::vector<int32_t>& candidates, bool refine = false) {
+        if (candidates.empty()) return 0;
+        const reg_constraint_params p = odometryConstraintParams(refine);
+        int32_t added = 0;
+        check(reg_submaps_compute_odometry_constraints(s_, candidates.data(), (int32_t)candidates.size(), &p, &added));
+        return added;
+    }
+    int32_t computeOdometryConstraints(bool refine = false) {
+        const reg_constraint_params p = odometryConstraintParams(refine);
+        int32_t added = 0;
+        check(reg_submaps_compute_odometry_constraints(s_, nullptr, 0, &p, &added));
+        return added;
+    }
+    std::vector<Constraint> getOdometryConstraints() const {
+        int32_t n = 0;
+        check(reg_submaps_get_odometry_constraints(s_, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &n));
+        std::vector<int32_t> src((size_t)std::max(n, 1)), tgt(src.size()), flags(src.size());
+        std::vector<double> T(src.size() * 16), info(src.size() * 36);
+        check(reg_submaps_get_odometry_constraints(s_, (int32_t)src.size(), src.data(), tgt.data(), T.data(), info.data(), flags.data(), &n));
+        std::vector<Constraint> out((size_t)n);
+        for (int32_t k = 0; k < n; ++k) {
+            Constraint& c = out[(size_t)k];
+            c.sourceSubmapIdx = src[(size_t)k], c.targetSubmapIdx = tgt[(size_t)k];
+            std::copy(T.begin() + 16 * k, T.begin() + 16 * (k + 1), c.sourceToTarget);
+            std::copy(info.begin() + 36 * k, info.begin() + 36 * (k + 1), c.informationMatrix);
+            c.isInformationMatrixValid = (flags[(size_t)k] & 1) != 0, c.isOdometryConstraint = (flags[(size_t)k] & 2) != 0;
+        }
+        return out;
+    }
+    void clearOdometryConstraints() { check(reg_submaps_clear_odometry_constraints(s_)); }
+    // buildLoopClosureConstraints of [(id, stamp)]: the accepted constraints; every verdict goes to *verdicts when given
+    std::vector<Constraint> buildLoopClosureConstraints(const std::vector<Stamped>& candidates, const reg_loop_closure_params& params,
+                                                        std::vector<reg_loop_closure_verdict>* verdicts = nullptr) {
+        std::vector<Constraint> out;
+        for (const Stamped& c : candidates) {
+            std::vector<reg_loop_closure_verdict> v((size_t)std::max(info().n_submaps, 1));
+            v[0].struct_size = (int32_t)sizeof(reg_loop_closure_verdict);
+            int32_t n = 0;
+            check(reg_submaps_build_loop_closure_constraints(s_, c.submapId, c.stampNs, &params, v.data(), (int32_t)v.size(), &n));
+            for (int32_t k = 0; k < n; ++k) {
+                if (verdicts) verdicts->push_back(v[(size_t)k]);
+                if (v[(size_t)k].verdict == REG_LC_ACCEPTED) out.push_back(constraintOf(v[(size_t)k].constraint, false, c.stampNs));
+            }
+        }
+        return out;
+    }
     // Mapper::getAssembledMapPointCloud
     MapCloud::Cloud getAssembledMapPointCloud() {
         MapCloud::Cloud out;
@@ -1321,6 +1392,15 @@ private:
     }
     void check(reg_status s) const {
         if (s != REG_OK) raise(s, reg_last_error(h_));
+    }
+    static Constraint constraintOf(const reg_constraint_result& r, bool odometry, int64_t stampNs) {
+        Constraint c;
+        c.sourceSubmapIdx = r.source, c.targetSubmapIdx = r.target;
+        std::copy(r.T, r.T + 16, c.sourceToTarget);
+        std::copy(r.information, r.information + 36, c.informationMatrix);
+        c.isInformationMatrixValid = r.information_estimated != 0, c.isOdometryConstraint = odometry;
+        c.timestampNs = stampNs;
+        return c;
     }
     reg_handle* h_ = nullptr;
     reg_submaps_params prm_;

@@ -1865,7 +1865,7 @@ REG_API reg_status reg_host_line_process_weight(const double* info, int64_t n_ed
      is as before the call: repeating the call would insert those scans twice.  A REG_BAD_ARGUMENT of a map cloud step
      (a refused voxel key) behaves the same way.  In reg_submaps_transform the same holds per submap.
    Out of scope: each submap's dense map (a reg_dense_map per id stays with the caller, who applies reg_dense_map_transform
-     with the plan), dumpToFile, the feature thread, the mutexes, building the constraints (reg_set_pair_overlap_f64). */
+     with the plan), dumpToFile, the feature thread, the mutexes.  Building the constraints is the section after this one. */
 typedef struct reg_submaps reg_submaps;
 typedef struct {
     int32_t struct_size;                  /* = sizeof(reg_submaps_params); checked */
@@ -2026,6 +2026,153 @@ REG_API reg_status reg_host_submaps_transform_plan(const int32_t* parents, int32
    entry is ((a0 b0 + a1 b1) + a2 b2) + a3 b3; the rigid inverse is [R^T | -((R0i t0 + R1i t1) + R2i t2)]. */
 REG_API reg_status reg_host_mapper_initial_guess(const double prev_map_to_sensor[16], const double odom_prev[16],
                                                  const double odom_now[16], const double calib[16], double out[16]);
+
+/* ---- pose-graph constraints from the resident submap collection -----------------------------------------------
+   buildConstraint (constraint_builders.cpp:43-90), the refinement half of buildLoopClosureConstraints
+   (PlaceRecognition.cpp:97-149), computeOdometryConstraints (constraint_builders.cpp:92-118) with the list the reference's
+   SubmapCollection owns (odometryConstraints_), and the per-submap store of Submap::sparseMapCloud_ / feature_ -- all on
+   the map clouds where they live.  Everything here is an addition to the reg_submaps section above.
+
+   reg_submaps_build_constraint runs, in this order and with both map clouds as device pointers:
+     1. is_compute_overlap != 0: reg_set_pair_overlap_f64 with T_init as T_src_to_tgt (NULL stays NULL), overlap_voxel_size
+        and min_points_per_voxel = 1; else reg_set_target_f64 of the target without a crop, then reg_set_source_f64 of the
+        source.  The target's normals are passed only for REG_COST_O3D_P2PL, the covariances of both only for REG_COST_GICP,
+        the source's normals never -- the fields the stateless builders pass;
+     2. unless skip_refinement: reg_register from (float)T_init; T = the fp32 result widened.  Skipped: T = (float)T_init
+        widened, fitness = inlier_rmse = 0, iterations = converged = 0;
+     3. with estimate_information: reg_information_matrix at (float)T with information_max_distance; else the identity and
+        n_info_pairs = 0.
+   The steps run on a handle the collection owns, never on the collection's handle: one per cost in use, created by the
+   first call that names the cost with reg_default_params + {cost, use_trimmed = 0, gicp_stop_rule = 1 for GICP}, on the
+   collection's stream (re-read at every call, as the normals workspace does), max_dist = icp_max_correspondence_distance
+   and max_iter = max_iteration set per call, destroyed with the collection.  The reference, the reading and the chain
+   configuration of the collection's handle are not touched.  The arithmetic is that of the named operators: no kernel of
+   its own.
+   Statuses: REG_BAD_ARGUMENT for a NULL or wrongly sized params / result, a cost other than REG_COST_O3D_P2PL,
+   REG_COST_O3D_P2P or REG_COST_GICP, max_iteration < 1, icp_max_correspondence_distance not finite or <= 0,
+   information_max_distance not finite, <= 0 or > icp_max_correspondence_distance (the reach of the search structure both
+   run on), an overlap voxel not finite or <= 0 with is_compute_overlap, an unknown index or source == target -- all
+   before any device work; REG_EMPTY_TARGET for an empty submap of the pair or no shared voxel; REG_MISSING_FIELD for
+   point-to-plane without target normals or GICP without covariances; otherwise what the named operator returns.  *out is
+   written only on REG_OK; a failing call changes nothing in the collection (the text is in reg_last_error of its handle).
+   Matrices: T double[16] column-major; information[36] as reg_information_matrix writes it. */
+typedef struct {
+    int32_t struct_size;                    /* = sizeof(reg_constraint_params); checked */
+    int32_t cost;                           /* REG_COST_O3D_P2PL (buildConstraint), REG_COST_O3D_P2P or REG_COST_GICP */
+    int32_t max_iteration;                  /* magic::icpRunUntilConvergenceNumberOfIterations (100) */
+    int32_t is_compute_overlap;
+    int32_t skip_refinement;
+    int32_t estimate_information;
+    double  overlap_voxel_size;
+    double  icp_max_correspondence_distance;
+    double  information_max_distance;
+} reg_constraint_params;
+typedef struct {
+    int32_t struct_size;                    /* = sizeof(reg_constraint_result), set by the caller */
+    int32_t source, target;
+    int32_t iterations, converged;          /* of reg_result */
+    int32_t refined;                        /* reg_register ran */
+    int32_t information_estimated;          /* isInformationMatrixValid_ */
+    int32_t reserved;
+    int64_t n_source_selected, n_target_selected;   /* rows of the reading / the reference (all rows without the overlap) */
+    int64_t n_info_pairs;
+    double  fitness, inlier_rmse;           /* of reg_result */
+    double  T[16];                          /* sourceToTarget_ */
+    double  information[36];
+} reg_constraint_result;
+/* buildOdometryConstraint's arguments (constraint_builders.cpp:33-41): point-to-plane, 100 iterations, overlap at
+   20 x the map voxel size, both distances 1.5 x it (0.04 m stands in for a map voxel size of zero, which getMapVoxelSize,
+   helpers.cpp:356-358, takes to be |size| <= 1e-3), information estimated, skip_refinement = !refine. */
+REG_API reg_status reg_default_odometry_constraint_params(const reg_submaps* s, int refine, reg_constraint_params* p);
+/* The argument checks of reg_submaps_build_constraint on the params alone, without a device. */
+REG_API reg_status reg_check_constraint_params(const reg_constraint_params* p);
+/* sizeof of reg_constraint_params, reg_constraint_result */
+REG_API void reg_constraints_struct_sizes(int32_t sizes[2]);
+REG_API reg_status reg_submaps_build_constraint(reg_submaps* s, int32_t source, int32_t target,
+                                                const reg_constraint_params* params,
+                                                const double T_init[16] /* NULL: identity */, reg_constraint_result* out);
+/* computeOdometryConstraints into the list the collection owns.  The pairs are those of
+   reg_submaps_odometry_constraint_pairs against that list (candidates == NULL: the overload without candidates); each is
+   built by reg_submaps_build_constraint from the identity and appended with isOdometryConstraint_ = 1.  params == NULL:
+   reg_default_odometry_constraint_params without refinement.  All or nothing: when a pair fails, the status is that pair's
+   and the list is as before.  n_added may be NULL. */
+REG_API reg_status reg_submaps_compute_odometry_constraints(reg_submaps* s, const int32_t* candidates, int32_t n,
+                                                            const reg_constraint_params* params, int32_t* n_added);
+/* getOdometryConstraints: *n_out entries in list order; source / target (capacity int32 each), T (capacity x 16,
+   column-major), information (capacity x 36), flags (bit 0: isInformationMatrixValid_, bit 1: isOdometryConstraint_); any
+   array may be NULL (all NULL: the count).  capacity below the entries with an array given: REG_BAD_ARGUMENT. */
+REG_API reg_status reg_submaps_get_odometry_constraints(const reg_submaps* s, int32_t capacity, int32_t* source, int32_t* target,
+                                                        double* T, double* information, int32_t* flags, int32_t* n_out);
+REG_API reg_status reg_submaps_clear_odometry_constraints(reg_submaps* s);
+/* The feature store.  reg_submaps_compute_features with feature params, when it succeeds, also keeps the submap's sparse
+   cloud (fp64 and fp32), its normals and its FPFH rows in buffers of that submap (device-to-device copies; 312 bytes per
+   sparse row), so that the features of one submap outlive the computation of the next.  reg_submaps_get_features hands
+   them out (host or device pointers by on_device; any may be NULL): xyz64 n x 3 doubles, xyz n x 3 floats, normals n x 3
+   floats, fpfh n x 33 doubles.  A submap without stored features gives *n_out = 0; capacity_rows below the rows with an
+   array given is REG_BAD_ARGUMENT.  reg_submaps_transform moves the stored sparse cloud of every submap it moves, as
+   Submap::transform does (Submap.cpp:117): the fp64 point by the formula of reg_map_cloud_transform, the fp32 point is its
+   cast, the normal (nx', ny', nz') = the rotation rows applied to the fp32 normal widened, each ((R0 nx + R1 ny) + R2 nz),
+   cast back to fp32; the features stay. */
+REG_API reg_status reg_submaps_get_features(reg_submaps* s, int32_t idx, int on_device, double* sparse_xyz64, float* sparse_xyz,
+                                            float* sparse_normals, double* fpfh, int64_t capacity_rows, int64_t* n_out);
+/* PlaceRecognition::isRegistrationConsistent (PlaceRecognition.cpp:182-229), host-only: T column-major; bounds = maxDrift
+   roll, pitch, yaw [rad], x, y, z [m].  The rotation block becomes a quaternion as Eigen's Quaterniond(Matrix3d) forms it,
+   is normalised, and toRPY (math.cpp:39-46) gives roll = atan2(2 (w x + y z), 1 - 2 (x x + y y)), pitch = asin(2 (w y - x z)),
+   yaw = atan2(2 (w z + x y), 1 - 2 (y y + z z)).  *failed_mask gets bit k for every component k (roll, pitch, yaw, x, y, z) with
+   fabs(value) > bounds[k] -- strictly greater, so a value on its bound passes and a NaN never fails (reproduced).
+   Consistent == a mask of 0.  REG_BAD_ARGUMENT for a NULL argument. */
+REG_API reg_status reg_host_registration_consistent(const double T[16], const double bounds[6], int32_t* failed_mask);
+/* PlaceRecognition::buildLoopClosureConstraints (PlaceRecognition.cpp:50-176) for one finished submap, on the feature store:
+   for every index of reg_submaps_loop_closure_candidates(last_finished), in order, with source = last_finished and
+   target = the candidate:
+     1. reg_match_features of the stored FPFH rows (33 columns) with the backward search and the mutual filter; the
+        correspondences are the mutual pairs when there are at least ransac.ransac_n of them, else every (a, nn_ab[a]) -- as
+        Open3D falls back; reg_ransac_correspondences on the stored fp64 sparse clouds with `ransac` as given (the seed
+        included: the same for every candidate).  All arrays stay on the device.  n_correspondences = its n_inliers;
+     2. n_correspondences < ransac_min_correspondence_set_size: REG_LC_RANSAC_SET_TOO_SMALL;
+     3. reg_host_registration_consistent of the RANSAC transform with consistency_bounds fails: REG_LC_RANSAC_INCONSISTENT;
+     4. reg_submaps_build_constraint(source, target, &refine, T_ransac): `constraint` is written, refined = 1;
+     5. constraint.fitness < min_refinement_fitness: REG_LC_FITNESS_TOO_LOW;
+     6. reg_host_registration_consistent of constraint.T fails: REG_LC_ICP_INCONSISTENT; else REG_LC_ACCEPTED.
+   A source or a candidate without stored features takes step 2 with zero correspondences and the identity.  The feature
+   steps run on the builders' point-to-point handle, not on the collection's.  Accepted constraints are NOT stored in the
+   collection (the reference hands them to the optimisation problem; isOdometryConstraint_ = 0, timestamp_ = stamp_ns).
+   verdicts: capacity records (may be NULL with capacity 0 when there is no candidate); the caller sets struct_size in the
+   first, the call writes one whole record per candidate.  *n_candidates is set whenever the candidates could be listed.  capacity below the candidates, an unknown index, a wrong
+   struct_size or refused `refine` parameters: REG_BAD_ARGUMENT before any device work.  A step that fails ends the call
+   with its status; the verdicts are written only on REG_OK.  Nothing in the collection changes either way. */
+enum {
+    REG_LC_ACCEPTED = 0, REG_LC_RANSAC_SET_TOO_SMALL = 1, REG_LC_RANSAC_INCONSISTENT = 2, REG_LC_FITNESS_TOO_LOW = 3,
+    REG_LC_ICP_INCONSISTENT = 4
+};
+typedef struct {
+    int32_t struct_size;                    /* = sizeof(reg_loop_closure_params); checked */
+    int32_t ransac_min_correspondence_set_size;   /* placeRecognition_.ransacMinCorrespondenceSetSize_ (25) */
+    double  min_refinement_fitness;         /* placeRecognition_.minRefinementFitness_ */
+    double  consistency_bounds[6];          /* consistencyCheck_: maxDrift roll, pitch, yaw [rad], x, y, z [m] */
+    reg_ransac_params ransac;               /* struct_size checked by reg_ransac_correspondences */
+    reg_constraint_params refine;
+} reg_loop_closure_params;
+typedef struct {
+    int32_t struct_size;                    /* = sizeof(reg_loop_closure_verdict), set by the caller in the first record */
+    int32_t source, candidate;
+    int32_t verdict;                        /* REG_LC_* */
+    int32_t ransac_failed_mask, icp_failed_mask;   /* of reg_host_registration_consistent, where it ran */
+    int32_t refined;                        /* step 4 ran: `constraint` is valid */
+    int32_t reserved;
+    int64_t n_correspondences;              /* ransacResult.correspondence_set_.size() */
+    int64_t ransac_iterations;              /* the stop index */
+    int64_t stamp_ns;                       /* timestamp_ */
+    double  ransac_fitness, ransac_inlier_rmse;
+    double  T_ransac[16];                   /* column-major */
+    reg_constraint_result constraint;
+} reg_loop_closure_verdict;
+/* sizeof of reg_loop_closure_params, reg_loop_closure_verdict */
+REG_API void reg_loop_closure_struct_sizes(int32_t sizes[2]);
+REG_API reg_status reg_submaps_build_loop_closure_constraints(reg_submaps* s, int32_t last_finished, int64_t stamp_ns,
+                                                              const reg_loop_closure_params* params,
+                                                              reg_loop_closure_verdict* verdicts, int32_t capacity,
+                                                              int32_t* n_candidates);
 
 #ifdef __cplusplus
 }

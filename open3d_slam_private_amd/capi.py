@@ -3224,3 +3224,250 @@ def host_band_constants():
     lib.reg_host_predict_band(math.inf, math.inf, math.inf, 0, math.inf, math.inf, 0, None, c)
     names = ("band_cap", "wide_rel", "floor", "ratio_max", "centre_gain", "geom_rel", "guard_frac", "forced_wide")
     return {k: float(np.float32(v)) for k, v in zip(names, c)}
+
+
+# ---- pose-graph constraints from the resident submap collection (include/o3dslam_reg.h) -------------------------
+class ConstraintParams(C.Structure):
+    """reg_constraint_params (include/o3dslam_reg.h): the arguments of buildConstraint / the loop-closure refinement."""
+    _fields_ = [("struct_size", C.c_int32), ("cost", C.c_int32), ("max_iteration", C.c_int32), ("is_compute_overlap", C.c_int32),
+                ("skip_refinement", C.c_int32), ("estimate_information", C.c_int32), ("overlap_voxel_size", C.c_double),
+                ("icp_max_correspondence_distance", C.c_double), ("information_max_distance", C.c_double)]
+
+
+class ConstraintResult(C.Structure):
+    """reg_constraint_result (include/o3dslam_reg.h); T_matrix() / information_matrix() give the 4 x 4 and 6 x 6 math layout."""
+    _fields_ = [("struct_size", C.c_int32), ("source", C.c_int32), ("target", C.c_int32), ("iterations", C.c_int32),
+                ("converged", C.c_int32), ("refined", C.c_int32), ("information_estimated", C.c_int32), ("reserved", C.c_int32),
+                ("n_source_selected", C.c_int64), ("n_target_selected", C.c_int64), ("n_info_pairs", C.c_int64),
+                ("fitness", C.c_double), ("inlier_rmse", C.c_double), ("T", C.c_double * 16), ("information", C.c_double * 36)]
+
+    def T_matrix(self) -> np.ndarray:
+        return np.array(self.T, np.float64).reshape(4, 4).T.copy()
+
+    def information_matrix(self) -> np.ndarray:
+        return np.array(self.information, np.float64).reshape(6, 6)
+
+
+EXPORTS += ["reg_default_odometry_constraint_params", "reg_check_constraint_params", "reg_constraints_struct_sizes",
+            "reg_submaps_build_constraint", "reg_submaps_compute_odometry_constraints", "reg_submaps_get_odometry_constraints",
+            "reg_submaps_clear_odometry_constraints", "reg_submaps_get_features", "reg_host_registration_consistent"]
+CONSISTENCY_COMPONENTS = ("roll", "pitch", "yaw", "x", "y", "z")   # bit k of reg_host_registration_consistent's mask
+_constraints_bound = False
+
+
+def _constraints_lib():
+    """The library with the prototypes of this section set."""
+    global _constraints_bound
+    lib = load_library()
+    if not _constraints_bound:
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        pd = C.POINTER(C.c_double)
+        lib.reg_default_odometry_constraint_params.argtypes = [vp, C.c_int, C.POINTER(ConstraintParams)]
+        lib.reg_check_constraint_params.argtypes = [C.POINTER(ConstraintParams)]
+        lib.reg_constraints_struct_sizes.argtypes = [C.POINTER(i32)]
+        lib.reg_constraints_struct_sizes.restype = None
+        lib.reg_submaps_build_constraint.argtypes = [vp, i32, i32, C.POINTER(ConstraintParams), pd, C.POINTER(ConstraintResult)]
+        lib.reg_submaps_compute_odometry_constraints.argtypes = [vp, vp, i32, C.POINTER(ConstraintParams), C.POINTER(i32)]
+        lib.reg_submaps_get_odometry_constraints.argtypes = [vp, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]
+        lib.reg_submaps_clear_odometry_constraints.argtypes = [vp]
+        lib.reg_submaps_get_features.argtypes = [vp, i32, C.c_int, vp, vp, vp, vp, i64, C.POINTER(i64)]
+        lib.reg_host_registration_consistent.argtypes = [pd, pd, C.POINTER(i32)]
+        _constraints_bound = True
+    return lib
+
+
+def constraint_params(cost=COST_O3D_P2PL, max_iteration=100, is_compute_overlap=True, skip_refinement=False,
+                      estimate_information=True, overlap_voxel_size=0.0, icp_max_correspondence_distance=0.0,
+                      information_max_distance=None) -> ConstraintParams:
+    """A reg_constraint_params; information_max_distance defaults to icp_max_correspondence_distance (buildConstraint)."""
+    p = ConstraintParams()
+    p.struct_size = C.sizeof(ConstraintParams)
+    p.cost, p.max_iteration = int(cost), int(max_iteration)
+    p.is_compute_overlap, p.skip_refinement = int(bool(is_compute_overlap)), int(bool(skip_refinement))
+    p.estimate_information = int(bool(estimate_information))
+    p.overlap_voxel_size = float(overlap_voxel_size)
+    p.icp_max_correspondence_distance = float(icp_max_correspondence_distance)
+    p.information_max_distance = float(icp_max_correspondence_distance if information_max_distance is None
+                                       else information_max_distance)
+    return p
+
+
+def check_constraint_params(params: ConstraintParams) -> int:
+    """reg_check_constraint_params: the status reg_submaps_build_constraint would return for these parameters (no device)."""
+    return int(_constraints_lib().reg_check_constraint_params(C.byref(params) if params is not None else None))
+
+
+def constraints_struct_sizes() -> tuple:
+    """sizeof of reg_constraint_params, reg_constraint_result in the library."""
+    out = (C.c_int32 * 2)()
+    _constraints_lib().reg_constraints_struct_sizes(out)
+    return tuple(out)
+
+
+def host_registration_consistent(T, bounds):
+    """reg_host_registration_consistent: (consistent, failed mask) of isRegistrationConsistent for the 4 x 4 T and the bounds
+    (roll, pitch, yaw [rad], x, y, z [m]); bit k of the mask names CONSISTENCY_COMPONENTS[k]."""
+    b = (C.c_double * 6)(*[float(v) for v in bounds])
+    mask = C.c_int32(0)
+    st = _constraints_lib().reg_host_registration_consistent(_T_in_f64(T), b, C.byref(mask))
+    if st != 0:
+        raise RegError(st, "reg_host_registration_consistent")
+    return mask.value == 0, int(mask.value)
+
+
+def _submaps_default_odometry_constraint_params(self, refine=False) -> ConstraintParams:
+    """reg_default_odometry_constraint_params: buildOdometryConstraint's arguments for this collection's map voxel size."""
+    p = ConstraintParams()
+    self._check(_constraints_lib().reg_default_odometry_constraint_params(self._s, int(bool(refine)), C.byref(p)))
+    return p
+
+
+def _submaps_build_constraint(self, source, target, params: ConstraintParams, T_init=None) -> ConstraintResult:
+    """reg_submaps_build_constraint: overlap selection, registration and information matrix between two resident submaps, on
+    a handle of the collection's own (the handle of `reg` keeps its reference and reading)."""
+    res = ConstraintResult()
+    res.struct_size = C.sizeof(ConstraintResult)
+    if params is not None:
+        params.struct_size = C.sizeof(ConstraintParams)
+    self._check(_constraints_lib().reg_submaps_build_constraint(self._s, int(source), int(target),
+                                                                C.byref(params) if params is not None else None,
+                                                                _T_in_f64(T_init), C.byref(res)))
+    return res
+
+
+def _submaps_compute_odometry_constraints(self, candidates=None, params: "ConstraintParams | None" = None) -> int:
+    """reg_submaps_compute_odometry_constraints: builds the missing odometry constraints (of the candidates, or of every
+    finished pair) into the collection's list; returns how many were added.  All or nothing."""
+    c = None if candidates is None else np.ascontiguousarray(candidates, np.int32).reshape(-1)
+    if c is not None and c.size == 0:
+        return 0
+    if params is not None:
+        params.struct_size = C.sizeof(ConstraintParams)
+    added = C.c_int32(0)
+    self._check(_constraints_lib().reg_submaps_compute_odometry_constraints(
+        self._s, _ptr(c) if c is not None else None, 0 if c is None else int(c.size),
+        C.byref(params) if params is not None else None, C.byref(added)))
+    return int(added.value)
+
+
+def _submaps_odometry_constraints(self) -> list:
+    """reg_submaps_get_odometry_constraints: [dict(source, target, T 4 x 4, information 6 x 6, information_valid, is_odometry)]."""
+    lib, n = _constraints_lib(), C.c_int32(0)
+    self._check(lib.reg_submaps_get_odometry_constraints(self._s, 0, None, None, None, None, None, C.byref(n)))
+    k = max(int(n.value), 1)
+    src, tgt, flags = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    T, info = np.zeros((k, 16), np.float64), np.zeros((k, 36), np.float64)
+    self._check(lib.reg_submaps_get_odometry_constraints(self._s, k, _ptr(src), _ptr(tgt), _ptr(T), _ptr(info), _ptr(flags), C.byref(n)))
+    return [dict(source=int(src[i]), target=int(tgt[i]), T=T[i].reshape(4, 4).T.copy(), information=info[i].reshape(6, 6).copy(),
+                 information_valid=bool(flags[i] & 1), is_odometry=bool(flags[i] & 2)) for i in range(int(n.value))]
+
+
+def _submaps_clear_odometry_constraints(self):
+    self._check(_constraints_lib().reg_submaps_clear_odometry_constraints(self._s))
+
+
+def _submaps_get_features(self, idx):
+    """reg_submaps_get_features: the stored sparse cloud and features of a submap, dict(xyz64 n x 3 float64, xyz n x 3 float32,
+    normals n x 3 float32, fpfh n x 33 float64); n = 0 before its features were computed."""
+    lib, n = _constraints_lib(), C.c_int64(0)
+    self._check(lib.reg_submaps_get_features(self._s, int(idx), 0, None, None, None, None, 0, C.byref(n)))
+    k = int(n.value)
+    cap = max(k, 1)
+    x64, x, nr, f = (np.empty((cap, 3), np.float64), np.empty((cap, 3), np.float32), np.empty((cap, 3), np.float32),
+                     np.empty((cap, 33), np.float64))
+    self._check(lib.reg_submaps_get_features(self._s, int(idx), 0, _ptr(x64), _ptr(x), _ptr(nr), _ptr(f), cap, C.byref(n)))
+    return dict(xyz64=x64[:k].copy(), xyz=x[:k].copy(), normals=nr[:k].copy(), fpfh=f[:k].copy())
+
+
+def _submaps_get_features_device(self, idx, capacity_rows, xyz64_ptr=None, xyz_ptr=None, nrm_ptr=None, fpfh_ptr=None) -> int:
+    """As get_features with the outputs resident in HBM.  Returns the stored rows."""
+    vp = lambda p: C.c_void_p(p) if p else None
+    n = C.c_int64(0)
+    self._check(_constraints_lib().reg_submaps_get_features(self._s, int(idx), 1, vp(xyz64_ptr), vp(xyz_ptr), vp(nrm_ptr),
+                                                            vp(fpfh_ptr), int(capacity_rows), C.byref(n)))
+    return int(n.value)
+
+
+Submaps.default_odometry_constraint_params = _submaps_default_odometry_constraint_params
+Submaps.build_constraint = _submaps_build_constraint
+Submaps.compute_odometry_constraints = _submaps_compute_odometry_constraints
+Submaps.odometry_constraints = _submaps_odometry_constraints
+Submaps.clear_odometry_constraints = _submaps_clear_odometry_constraints
+Submaps.get_features = _submaps_get_features
+Submaps.get_features_device = _submaps_get_features_device
+
+
+class LoopClosureParams(C.Structure):
+    """reg_loop_closure_params (include/o3dslam_reg.h): the gates of buildLoopClosureConstraints, RANSAC's and the refinement's
+    parameters."""
+    _fields_ = [("struct_size", C.c_int32), ("ransac_min_correspondence_set_size", C.c_int32), ("min_refinement_fitness", C.c_double),
+                ("consistency_bounds", C.c_double * 6), ("ransac", RansacParams), ("refine", ConstraintParams)]
+
+
+class LoopClosureVerdict(C.Structure):
+    """reg_loop_closure_verdict (include/o3dslam_reg.h); T_ransac_matrix() gives the 4 x 4 math layout."""
+    _fields_ = [("struct_size", C.c_int32), ("source", C.c_int32), ("candidate", C.c_int32), ("verdict", C.c_int32),
+                ("ransac_failed_mask", C.c_int32), ("icp_failed_mask", C.c_int32), ("refined", C.c_int32), ("reserved", C.c_int32),
+                ("n_correspondences", C.c_int64), ("ransac_iterations", C.c_int64), ("stamp_ns", C.c_int64),
+                ("ransac_fitness", C.c_double), ("ransac_inlier_rmse", C.c_double), ("T_ransac", C.c_double * 16),
+                ("constraint", ConstraintResult)]
+
+    def T_ransac_matrix(self) -> np.ndarray:
+        return np.array(self.T_ransac, np.float64).reshape(4, 4).T.copy()
+
+
+EXPORTS += ["reg_loop_closure_struct_sizes", "reg_submaps_build_loop_closure_constraints"]
+LC_ACCEPTED, LC_RANSAC_SET_TOO_SMALL, LC_RANSAC_INCONSISTENT, LC_FITNESS_TOO_LOW, LC_ICP_INCONSISTENT = range(5)
+
+
+def loop_closure_struct_sizes() -> tuple:
+    """sizeof of reg_loop_closure_params, reg_loop_closure_verdict in the library."""
+    lib = load_library()
+    lib.reg_loop_closure_struct_sizes.argtypes = [C.POINTER(C.c_int32)]
+    lib.reg_loop_closure_struct_sizes.restype = None
+    out = (C.c_int32 * 2)()
+    lib.reg_loop_closure_struct_sizes(out)
+    return tuple(out)
+
+
+def loop_closure_params(refine: ConstraintParams, max_correspondence_distance=0.75, ransac_n=3, max_iteration=1000000,
+                        confidence=0.99, distance_threshold=0.75, edge_similarity=0.5, seed=0, min_correspondence_set_size=25,
+                        min_refinement_fitness=0.7, bounds=(math.pi / 2, math.pi / 2, math.pi / 2, 10.0, 10.0, 15.0)) -> LoopClosureParams:
+    """A reg_loop_closure_params with PlaceRecognitionParameters' defaults (Parameters.hpp:113-135); bounds = maxDrift roll,
+    pitch, yaw [rad], x, y, z [m]."""
+    p = LoopClosureParams()
+    p.struct_size = C.sizeof(LoopClosureParams)
+    p.ransac_min_correspondence_set_size = int(min_correspondence_set_size)
+    p.min_refinement_fitness = float(min_refinement_fitness)
+    p.consistency_bounds = (C.c_double * 6)(*[float(b) for b in bounds])
+    r = p.ransac
+    r.struct_size, r.ransac_n, r.max_iteration, r.confidence = C.sizeof(RansacParams), int(ransac_n), int(max_iteration), float(confidence)
+    r.max_correspondence_distance, r.distance_threshold = float(max_correspondence_distance), float(distance_threshold)
+    r.edge_similarity, r.seed, r.batch = float(edge_similarity), int(seed), 0
+    p.refine = refine
+    p.refine.struct_size = C.sizeof(ConstraintParams)
+    return p
+
+
+def _submaps_build_loop_closure_constraints(self, last_finished, stamp_ns, params: LoopClosureParams) -> list:
+    """reg_submaps_build_loop_closure_constraints: one LoopClosureVerdict per candidate of `last_finished`, in candidate order
+    (feature matching, RANSAC, the gates and the refinement on the stored features and the resident maps)."""
+    lib = _constraints_lib()
+    lib.reg_submaps_build_loop_closure_constraints.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(LoopClosureParams),
+                                                               C.POINTER(LoopClosureVerdict), C.c_int32, C.POINTER(C.c_int32)]
+    cap = max(int(self.info().n_submaps), 1)
+    out = (LoopClosureVerdict * cap)()
+    out[0].struct_size = C.sizeof(LoopClosureVerdict)
+    n = C.c_int32(0)
+    params.struct_size = C.sizeof(LoopClosureParams)
+    self._check(lib.reg_submaps_build_loop_closure_constraints(self._s, int(last_finished), int(stamp_ns), C.byref(params), out, cap,
+                                                               C.byref(n)))
+    res = []
+    for k in range(int(n.value)):
+        v = LoopClosureVerdict()
+        C.memmove(C.byref(v), C.byref(out[k]), C.sizeof(LoopClosureVerdict))
+        res.append(v)
+    return res
+
+
+Submaps.build_loop_closure_constraints = _submaps_build_loop_closure_constraints

@@ -18,7 +18,13 @@ struct SmSubmap {
     DevBuf keys[2];   // the occupancy set: built in the spare buffer, then swapped
     int cur = 0;
     int64_t n_keys = 0;
+    DevBuf s_xyz64, s_xyz, s_nrm, s_fpfh;   // the feature store: sparseMapCloud_ (fp64, fp32), its normals, feature_
+    int64_t n_sparse = 0;
     ~SmSubmap() { reg_map_cloud_destroy(map); }
+};
+struct SmConstraint {   // o3d_slam::Constraint
+    int32_t source, target, flags;   // flags: bit 0 isInformationMatrixValid_, bit 1 isOdometryConstraint_
+    double T[16], info[36];
 };
 struct SmStamped {
     int32_t id;
@@ -38,6 +44,12 @@ struct reg_submaps {
     std::vector<std::set<int32_t>> adj;   // AdjacencyMatrix::adjacency_
     std::vector<int32_t> marks;           // isLoopClosureSubmap_: -1 no entry, 0 false, 1 true
     DevBuf f_xyz64, f_xyz, f_nrm, f_fpfh; // the sparse cloud (fp64, fp32), its normals and FPFH of the last feature computation
+    reg_handle* ch[4] = {nullptr, nullptr, nullptr, nullptr};   // the constraint builders' handles, by cost; created on first use
+    std::vector<SmConstraint> odometry;   // odometryConstraints_
+    DevBuf lc_ab, lc_ba, lc_cor, lc_inl;  // loop closure: nn_ab, nn_ba, the correspondences, RANSAC's inlier pairs
+    ~reg_submaps() {
+        for (reg_handle* w : ch) reg_destroy(w);
+    }
 };
 
 static void sm_add_edge(reg_submaps* s, int32_t a, int32_t b) {   // AdjacencyMatrix::addEdge: both marks become false
@@ -521,6 +533,24 @@ static reg_status sm_features(reg_submaps* s, SmSubmap& b, const reg_submap_feat
     return REG_OK;
 }
 
+// The feature store of submap b: m rows of the collection's feature buffers, device to device, on the stream.
+// The rows count only once every copy is queued: a failure here leaves the submap without stored features.
+static reg_status sm_store_features(reg_submaps* s, SmSubmap& b, int64_t m) {
+    reg_handle* h = s->h;
+    b.n_sparse = 0;
+    if (m == 0) return REG_OK;
+    DevBuf* dst[4] = {&b.s_xyz64, &b.s_xyz, &b.s_nrm, &b.s_fpfh};
+    const DevBuf* src[4] = {&s->f_xyz64, &s->f_xyz, &s->f_nrm, &s->f_fpfh};
+    const size_t row[4] = {24, 12, 12, 33 * 8};
+    for (int k = 0; k < 4; ++k) {
+        HIPCHK(h, dst[k]->reserve((size_t)m * row[k]));
+        HIPCHK(h, hipMemcpyAsync(dst[k]->p, src[k]->p, (size_t)m * row[k], hipMemcpyDeviceToDevice, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    b.n_sparse = m;
+    return REG_OK;
+}
+
 reg_status reg_submaps_compute_features(reg_submaps* s, int32_t idx, double now_seconds, const reg_submap_feature_params* fp,
                                         int on_device, float* sparse_xyz, float* sparse_normals, double* fpfh,
                                         int64_t capacity_rows, int64_t* n_sparse, int32_t* computed) {
@@ -554,6 +584,7 @@ reg_status reg_submaps_compute_features(reg_submaps* s, int32_t idx, double now_
         HIPCHK(h, copy_out(h, fpfh, s->f_fpfh.p, (size_t)m * 33 * 8, on_device));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
+    if (fp) REGCHK(sm_store_features(s, b, m));
     b.has_features = true;
     b.feature_clock = now_seconds;   // featureTimer_.reset()
     if (n_sparse) *n_sparse = m;
@@ -654,6 +685,12 @@ reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const doubl
     }
     auto apply = [&](SmSubmap& b, const double* T) -> reg_status {   // Submap::transform (Submap.cpp:115-128)
         REGCHK(reg_map_cloud_transform(b.map, T));
+        if (b.n_sparse > 0) {   // sparseMapCloud_.Transform (Submap.cpp:117); feature_ stays
+            HIPCHK(h, hipSetDevice(h->prm.device));
+            k_sm_transform_sparse<<<grid_for(b.n_sparse), 256, 0, h->stream>>>(b.s_xyz64.as<double>(), b.s_xyz.as<float>(),
+                                                                              b.s_nrm.as<float>(), b.n_sparse, xform_rows(T));
+            HIPCHK(h, hipGetLastError());
+        }
         double m[16], c[3];
         sm_mul(b.T_sensor, T, m);
         std::memcpy(b.T_sensor, m, sizeof(m));
@@ -786,6 +823,376 @@ reg_status reg_submaps_odometry_constraint_pairs(const reg_submaps* s, const int
     if ((int32_t)(pairs.size() / 2) > capacity) return REG_BAD_ARGUMENT;
     for (size_t k = 0; k < pairs.size(); ++k) out[k] = pairs[k];
     *n_out = (int32_t)(pairs.size() / 2);
+    return REG_OK;
+}
+
+}  // extern "C"
+
+// ---- pose-graph constraints from the resident collection ---------------------------------------------------------
+static const char* kSmConstraintMsg =
+    ": params missing or of the wrong struct_size, a cost other than REG_COST_O3D_P2PL / REG_COST_O3D_P2P / REG_COST_GICP, "
+    "max_iteration < 1, icp_max_correspondence_distance not finite and > 0, information_max_distance not in "
+    "(0, icp_max_correspondence_distance], or an overlap voxel not finite and > 0";
+
+// The builders' handle for `cost`: created on first use with the parameters of the stateless operators (reg_default_params,
+// the cost, no trimming, Open3D's stop rule for GICP), on the collection's stream -- as normals_workspace does it.
+static reg_status sm_constraint_handle(reg_submaps* s, int32_t cost, reg_handle** out) {
+    reg_handle* h = s->h;
+    if (!s->ch[cost]) {
+        reg_params p;
+        reg_default_params(&p);
+        p.cost = cost;
+        p.use_trimmed = 0;
+        p.max_dist = 1.f;   // set per call
+        p.device = h->prm.device;
+        if (cost == REG_COST_GICP) p.gicp_stop_rule = 1;
+        reg_handle* w = nullptr;
+        const reg_status cs = reg_create(&p, &w);
+        if (cs != REG_OK) {
+            h->err = std::string("reg_submaps_build_constraint: handle: ") + reg_last_error(w);
+            reg_destroy(w);
+            return cs;
+        }
+        s->ch[cost] = w;
+    }
+    const reg_status ss = reg_set_stream(s->ch[cost], h->stream);
+    if (ss != REG_OK) {
+        h->err = s->ch[cost]->err;
+        return ss;
+    }
+    *out = s->ch[cost];
+    return REG_OK;
+}
+
+extern "C" {
+
+void reg_constraints_struct_sizes(int32_t sizes[2]) {
+    if (!sizes) return;
+    sizes[0] = (int32_t)sizeof(reg_constraint_params);
+    sizes[1] = (int32_t)sizeof(reg_constraint_result);
+}
+
+reg_status reg_check_constraint_params(const reg_constraint_params* p) {
+    if (!p || p->struct_size != (int32_t)sizeof(reg_constraint_params)) return REG_BAD_ARGUMENT;
+    if (p->cost != REG_COST_O3D_P2PL && p->cost != REG_COST_O3D_P2P && p->cost != REG_COST_GICP) return REG_BAD_ARGUMENT;
+    if (p->max_iteration < 1 || !std::isfinite(p->icp_max_correspondence_distance) || !(p->icp_max_correspondence_distance > 0.0) ||
+        !(p->information_max_distance > 0.0) || !(p->information_max_distance <= p->icp_max_correspondence_distance) ||
+        !((float)p->icp_max_correspondence_distance > 0.f) || !std::isfinite((float)p->icp_max_correspondence_distance))
+        return REG_BAD_ARGUMENT;
+    if (p->is_compute_overlap && (!std::isfinite(p->overlap_voxel_size) || !(p->overlap_voxel_size > 0.0))) return REG_BAD_ARGUMENT;
+    return REG_OK;
+}
+
+reg_status reg_default_odometry_constraint_params(const reg_submaps* s, int refine, reg_constraint_params* p) {
+    if (!s || !p) return REG_BAD_ARGUMENT;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(*p);
+    // getMapVoxelSize(mapBuilder_, magic::voxelSizeCorrespondenceSearchIfMapVoxelSizeIsZero), constraint_builders.cpp:34-38,
+    // helpers.cpp:356-358: "zero" is |voxel| <= 1e-3
+    const double voxel = std::fabs(s->prm.map.map_voxel_size) <= 1e-3 ? 0.04 : s->prm.map.map_voxel_size;
+    p->cost = REG_COST_O3D_P2PL;
+    p->max_iteration = 100;   // magic::icpRunUntilConvergenceNumberOfIterations
+    p->is_compute_overlap = 1;
+    p->skip_refinement = refine ? 0 : 1;
+    p->estimate_information = 1;
+    p->overlap_voxel_size = 20.0 * voxel;                 // magic::voxelExpansionFactorOverlapComputation
+    p->icp_max_correspondence_distance = 1.5 * voxel;     // magic::voxelExpansionFactorIcpCorrespondenceDistance
+    p->information_max_distance = p->icp_max_correspondence_distance;
+    return REG_OK;
+}
+
+reg_status reg_submaps_build_constraint(reg_submaps* s, int32_t source, int32_t target, const reg_constraint_params* p,
+                                        const double T_init[16], reg_constraint_result* out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (reg_check_constraint_params(p) != REG_OK || !out || out->struct_size != (int32_t)sizeof(reg_constraint_result)) {
+        h->err = std::string("reg_submaps_build_constraint: result missing or of the wrong struct_size, or") + (kSmConstraintMsg + 1);
+        return REG_BAD_ARGUMENT;
+    }
+    if (!sm_idx_ok(s, source) || !sm_idx_ok(s, target) || source == target) {
+        h->err = "reg_submaps_build_constraint: an unknown submap index, or source == target";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    reg_handle* w = nullptr;
+    REGCHK(sm_constraint_handle(s, p->cost, &w));
+    reg_map_cloud *ms = s->subs[source]->map, *mt = s->subs[target]->map;
+    const Cols64 cs = mc_cur(ms), ct = mc_cur(mt);
+    const bool gicp = p->cost == REG_COST_GICP;
+    const double* t_nrm = p->cost == REG_COST_O3D_P2PL ? ct.nrm : nullptr;
+    const double *s_cov = gicp ? cs.aux : nullptr, *t_cov = gicp ? ct.aux : nullptr;
+    w->prm.max_dist = (float)p->icp_max_correspondence_distance;
+    w->prm.max_iter = p->max_iteration;
+    auto fail = [&](reg_status st) {
+        h->err = std::string("reg_submaps_build_constraint: ") + w->err;
+        return st;
+    };
+    reg_constraint_result r;
+    std::memset(&r, 0, sizeof(r));
+    r.struct_size = (int32_t)sizeof(r);
+    r.source = source;
+    r.target = target;
+    reg_status st;
+    if (p->is_compute_overlap) {
+        st = reg_set_pair_overlap_f64(w, ms->n > 0 ? cs.xyz : nullptr, nullptr, s_cov, ms->n, mt->n > 0 ? ct.xyz : nullptr, t_nrm, t_cov,
+                                      mt->n, 1, T_init, p->overlap_voxel_size, 1, &r.n_source_selected, &r.n_target_selected);
+        if (st != REG_OK) return fail(st);
+    } else {
+        st = reg_set_target_f64(w, ct.xyz, t_nrm, t_cov, mt->n, 1, nullptr, &r.n_target_selected);
+        if (st != REG_OK) return fail(st);
+        st = reg_set_source_f64(w, cs.xyz, nullptr, s_cov, ms->n, 1);
+        if (st != REG_OK) return fail(st);
+        r.n_source_selected = ms->n;
+    }
+    float Ti[16], To[16];
+    for (int k = 0; k < 16; ++k) Ti[k] = T_init ? (float)T_init[k] : (k % 5 == 0 ? 1.f : 0.f);
+    std::memcpy(To, Ti, sizeof(To));
+    if (!p->skip_refinement) {
+        reg_result res;
+        std::memset(&res, 0, sizeof(res));
+        st = reg_register(w, Ti, To, &res);
+        if (st != REG_OK) return fail(st);
+        r.refined = 1;
+        r.iterations = res.iterations;
+        r.converged = res.converged;
+        r.fitness = res.fitness;
+        r.inlier_rmse = res.inlier_rmse;
+    }
+    for (int k = 0; k < 16; ++k) r.T[k] = (double)To[k];
+    for (int k = 0; k < 36; ++k) r.information[k] = k % 7 == 0 ? 1.0 : 0.0;
+    if (p->estimate_information) {
+        st = reg_information_matrix(w, To, (float)p->information_max_distance, r.information, &r.n_info_pairs);
+        if (st != REG_OK) return fail(st);
+        r.information_estimated = 1;
+    }
+    *out = r;
+    return REG_OK;
+}
+
+reg_status reg_submaps_compute_odometry_constraints(reg_submaps* s, const int32_t* candidates, int32_t n,
+                                                    const reg_constraint_params* params, int32_t* n_added) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (n_added) *n_added = 0;
+    reg_constraint_params def;
+    (void)reg_default_odometry_constraint_params(s, 0, &def);
+    const reg_constraint_params* p = params ? params : &def;
+    if (reg_check_constraint_params(p) != REG_OK || n < 0) {
+        h->err = std::string("reg_submaps_compute_odometry_constraints: n < 0, or") + (kSmConstraintMsg + 1);
+        return REG_BAD_ARGUMENT;
+    }
+    std::vector<int32_t> existing, pairs(2 * (s->subs.size() + (size_t)(candidates ? n : 0)) + 2);
+    for (const SmConstraint& c : s->odometry) existing.push_back(c.source), existing.push_back(c.target);
+    int32_t np = 0;
+    if (reg_submaps_odometry_constraint_pairs(s, candidates, candidates ? n : 0, existing.data(), (int32_t)(existing.size() / 2),
+                                              pairs.data(), (int32_t)(pairs.size() / 2), &np) != REG_OK) {
+        h->err = "reg_submaps_compute_odometry_constraints: an unknown candidate index";
+        return REG_BAD_ARGUMENT;
+    }
+    std::vector<SmConstraint> built((size_t)np);
+    for (int32_t k = 0; k < np; ++k) {
+        reg_constraint_result r;
+        r.struct_size = (int32_t)sizeof(r);
+        REGCHK(reg_submaps_build_constraint(s, pairs[2 * k], pairs[2 * k + 1], p, nullptr, &r));
+        SmConstraint& c = built[k];
+        c.source = r.source;
+        c.target = r.target;
+        c.flags = (r.information_estimated ? 1 : 0) | 2;   // c.isOdometryConstraint_ = true (constraint_builders.cpp:39)
+        std::memcpy(c.T, r.T, sizeof(c.T));
+        std::memcpy(c.info, r.information, sizeof(c.info));
+    }
+    s->odometry.insert(s->odometry.end(), built.begin(), built.end());
+    if (n_added) *n_added = np;
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_odometry_constraints(const reg_submaps* s, int32_t capacity, int32_t* source, int32_t* target, double* T,
+                                                double* information, int32_t* flags, int32_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (n_out) *n_out = 0;
+    const int32_t n = (int32_t)s->odometry.size();
+    if ((source || target || T || information || flags) && capacity < n) return REG_BAD_ARGUMENT;
+    for (int32_t k = 0; k < n; ++k) {
+        const SmConstraint& c = s->odometry[k];
+        if (source) source[k] = c.source;
+        if (target) target[k] = c.target;
+        if (flags) flags[k] = c.flags;
+        if (T) std::memcpy(T + 16 * (size_t)k, c.T, sizeof(c.T));
+        if (information) std::memcpy(information + 36 * (size_t)k, c.info, sizeof(c.info));
+    }
+    if (n_out) *n_out = n;
+    return REG_OK;
+}
+
+reg_status reg_submaps_clear_odometry_constraints(reg_submaps* s) {
+    if (!s) return REG_BAD_ARGUMENT;
+    s->odometry.clear();
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_features(reg_submaps* s, int32_t idx, int on_device, double* sparse_xyz64, float* sparse_xyz,
+                                    float* sparse_normals, double* fpfh, int64_t capacity_rows, int64_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (n_out) *n_out = 0;
+    const bool any = sparse_xyz64 || sparse_xyz || sparse_normals || fpfh;
+    if (!sm_idx_ok(s, idx) || (any && capacity_rows < s->subs[idx]->n_sparse)) {
+        h->err = "reg_submaps_get_features: an unknown submap index, or capacity_rows below the stored rows";
+        return REG_BAD_ARGUMENT;
+    }
+    const SmSubmap& b = *s->subs[idx];
+    const int64_t m = b.n_sparse;
+    if (n_out) *n_out = m;
+    if (!any || m == 0) return REG_OK;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    HIPCHK(h, copy_out(h, sparse_xyz64, b.s_xyz64.p, (size_t)m * 24, on_device));
+    HIPCHK(h, copy_out(h, sparse_xyz, b.s_xyz.p, (size_t)m * 12, on_device));
+    HIPCHK(h, copy_out(h, sparse_normals, b.s_nrm.p, (size_t)m * 12, on_device));
+    HIPCHK(h, copy_out(h, fpfh, b.s_fpfh.p, (size_t)m * 33 * 8, on_device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return REG_OK;
+}
+
+reg_status reg_host_registration_consistent(const double T[16], const double bounds[6], int32_t* failed_mask) {
+    if (!T || !bounds || !failed_mask) return REG_BAD_ARGUMENT;
+    auto R = [&](int r, int c) { return T[4 * c + r]; };
+    // Eigen's Quaterniond(Matrix3d)
+    double q[4];   // w, x, y, z
+    double t = R(0, 0) + R(1, 1) + R(2, 2);
+    if (t > 0.0) {
+        t = std::sqrt(t + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[1] = (R(2, 1) - R(1, 2)) * t;
+        q[2] = (R(0, 2) - R(2, 0)) * t;
+        q[3] = (R(1, 0) - R(0, 1)) * t;
+    } else {
+        int i = 0;
+        if (R(1, 1) > R(0, 0)) i = 1;
+        if (R(2, 2) > R(i, i)) i = 2;
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        t = std::sqrt(R(i, i) - R(j, j) - R(k, k) + 1.0);
+        q[1 + i] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (R(k, j) - R(j, k)) * t;
+        q[1 + j] = (R(j, i) + R(i, j)) * t;
+        q[1 + k] = (R(k, i) + R(i, k)) * t;
+    }
+    const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const double w = q[0] / norm, x = q[1] / norm, y = q[2] / norm, z = q[3] / norm;
+    const double v[6] = {std::atan2(2.0 * (w * x + y * z), 1.0 - 2.0 * (x * x + y * y)), std::asin(2.0 * (w * y - x * z)),
+                         std::atan2(2.0 * (w * z + x * y), 1.0 - 2.0 * (y * y + z * z)), T[12], T[13], T[14]};
+    int32_t mask = 0;
+    for (int k = 0; k < 6; ++k)
+        if (std::fabs(v[k]) > bounds[k]) mask |= 1 << k;
+    *failed_mask = mask;
+    return REG_OK;
+}
+
+void reg_loop_closure_struct_sizes(int32_t sizes[2]) {
+    if (!sizes) return;
+    sizes[0] = (int32_t)sizeof(reg_loop_closure_params);
+    sizes[1] = (int32_t)sizeof(reg_loop_closure_verdict);
+}
+
+reg_status reg_submaps_build_loop_closure_constraints(reg_submaps* s, int32_t last_finished, int64_t stamp_ns,
+                                                      const reg_loop_closure_params* p, reg_loop_closure_verdict* verdicts,
+                                                      int32_t capacity, int32_t* n_candidates) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (n_candidates) *n_candidates = 0;
+    if (!p || p->struct_size != (int32_t)sizeof(reg_loop_closure_params) || reg_check_constraint_params(&p->refine) != REG_OK ||
+        p->ransac.struct_size != (int32_t)sizeof(reg_ransac_params) || p->ransac.ransac_n < 3 || capacity < 0 ||
+        (capacity > 0 && (!verdicts || verdicts[0].struct_size != (int32_t)sizeof(reg_loop_closure_verdict)))) {
+        h->err = std::string("reg_submaps_build_loop_closure_constraints: capacity < 0, verdicts missing or of the wrong struct_size, "
+                             "ransac of the wrong struct_size or ransac_n < 3, or refine") + kSmConstraintMsg;
+        return REG_BAD_ARGUMENT;
+    }
+    std::vector<int32_t> cand(s->subs.size());
+    int32_t nc = 0;
+    if (reg_submaps_loop_closure_candidates(s, last_finished, cand.data(), (int32_t)cand.size(), &nc) != REG_OK) {
+        h->err = "reg_submaps_build_loop_closure_constraints: an unknown submap index, or one without an entry in the adjacency matrix";
+        return REG_BAD_ARGUMENT;
+    }
+    if (n_candidates) *n_candidates = nc;
+    if (nc > capacity) {
+        h->err = "reg_submaps_build_loop_closure_constraints: capacity below the number of candidates";
+        return REG_BAD_ARGUMENT;
+    }
+    if (nc == 0) return REG_OK;
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    reg_handle* w = nullptr;
+    REGCHK(sm_constraint_handle(s, REG_COST_O3D_P2P, &w));
+    const SmSubmap& src = *s->subs[last_finished];
+    std::vector<reg_loop_closure_verdict> out((size_t)nc);
+    for (int32_t c = 0; c < nc; ++c) {
+        const SmSubmap& tgt = *s->subs[cand[c]];
+        reg_loop_closure_verdict& v = out[c];
+        std::memset(&v, 0, sizeof(v));
+        v.struct_size = (int32_t)sizeof(v);
+        v.source = last_finished;
+        v.candidate = cand[c];
+        v.stamp_ns = stamp_ns;
+        od_identity(v.T_ransac);
+        const int64_t na = src.n_sparse, nb = tgt.n_sparse;
+        if (na > 0 && nb > 0) {   // RegistrationRANSACBasedOnFeatureMatching (PlaceRecognition.cpp:81-84)
+            HIPCHK(h, hipSetDevice(h->prm.device));
+            HIPCHK(h, s->lc_ab.reserve((size_t)na * 4));
+            HIPCHK(h, s->lc_ba.reserve((size_t)nb * 4));
+            HIPCHK(h, s->lc_cor.reserve((size_t)na * 8));
+            HIPCHK(h, s->lc_inl.reserve((size_t)na * 8));
+            int64_t k = 0;
+            reg_status st = reg_match_features(w, src.s_fpfh.as<double>(), na, tgt.s_fpfh.as<double>(), nb, 33, 1,
+                                               s->lc_ab.as<int32_t>(), s->lc_ba.as<int32_t>(), s->lc_cor.as<int32_t>(), &k);
+            if (st != REG_OK) {
+                h->err = std::string("reg_submaps_build_loop_closure_constraints: ") + w->err;
+                return st;
+            }
+            if (k < p->ransac.ransac_n) {   // Open3D's fall-back: every (a, nearest b)
+                std::vector<int32_t> ab((size_t)na), pairs(2 * (size_t)na);
+                HIPCHK(h, hipMemcpyAsync(ab.data(), s->lc_ab.p, (size_t)na * 4, hipMemcpyDeviceToHost, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                for (int64_t a = 0; a < na; ++a) pairs[2 * a] = (int32_t)a, pairs[2 * a + 1] = ab[a];
+                HIPCHK(h, hipMemcpyAsync(s->lc_cor.p, pairs.data(), (size_t)na * 8, hipMemcpyHostToDevice, h->stream));
+                HIPCHK(h, hipStreamSynchronize(h->stream));
+                k = na;
+            }
+            reg_ransac_result rr;
+            std::memset(&rr, 0, sizeof(rr));
+            rr.struct_size = (int32_t)sizeof(rr);
+            st = reg_ransac_correspondences(w, src.s_xyz64.as<double>(), na, tgt.s_xyz64.as<double>(), nb, s->lc_cor.as<int32_t>(), k,
+                                            1, &p->ransac, &rr, s->lc_inl.as<int32_t>(), nullptr);
+            if (st != REG_OK) {
+                h->err = std::string("reg_submaps_build_loop_closure_constraints: ") + w->err;
+                return st;
+            }
+            std::memcpy(v.T_ransac, rr.T, sizeof(rr.T));
+            v.n_correspondences = rr.n_inliers;
+            v.ransac_iterations = rr.n_iterations;
+            v.ransac_fitness = rr.fitness;
+            v.ransac_inlier_rmse = rr.inlier_rmse;
+        }
+        if (v.n_correspondences < (int64_t)p->ransac_min_correspondence_set_size) {
+            v.verdict = REG_LC_RANSAC_SET_TOO_SMALL;
+            continue;
+        }
+        (void)reg_host_registration_consistent(v.T_ransac, p->consistency_bounds, &v.ransac_failed_mask);
+        if (v.ransac_failed_mask) {
+            v.verdict = REG_LC_RANSAC_INCONSISTENT;
+            continue;
+        }
+        v.constraint.struct_size = (int32_t)sizeof(v.constraint);
+        REGCHK(reg_submaps_build_constraint(s, last_finished, cand[c], &p->refine, v.T_ransac, &v.constraint));
+        v.refined = 1;
+        if (v.constraint.fitness < p->min_refinement_fitness) {
+            v.verdict = REG_LC_FITNESS_TOO_LOW;
+            continue;
+        }
+        (void)reg_host_registration_consistent(v.constraint.T, p->consistency_bounds, &v.icp_failed_mask);
+        v.verdict = v.icp_failed_mask ? REG_LC_ICP_INCONSISTENT : REG_LC_ACCEPTED;
+    }
+    std::memcpy(verdicts, out.data(), (size_t)nc * sizeof(reg_loop_closure_verdict));
     return REG_OK;
 }
 

@@ -55,3 +55,23 @@ __global__ void __launch_bounds__(256) k_occ_count(const double* __restrict__ xy
     const uint32_t hits = (uint32_t)__popcll(__ballot(hit));
     if ((threadIdx.x & 63) == 0 && hits) atomicAdd(count, hits);
 }
+
+// Submap::transform of a stored sparse cloud (Submap.cpp:117), in place, one thread per row: the fp64 point by
+// xform_point, the fp32 point as its cast, the fp32 normal widened, turned by xform_dir and cast back.  A thread reads its
+// whole row before it writes any of it and touches no other row, so the update needs no second buffer.
+__global__ void __launch_bounds__(256) k_sm_transform_sparse(double* __restrict__ xyz64, float* __restrict__ xyz,
+                                                             float* __restrict__ nrm, int64_t n, Xform64 T) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double x = xyz64[3 * i], y = xyz64[3 * i + 1], z = xyz64[3 * i + 2];
+    const double nx = (double)nrm[3 * i], ny = (double)nrm[3 * i + 1], nz = (double)nrm[3 * i + 2];
+    double p[3], d[3];
+    xform_point(T, x, y, z, p);
+    xform_dir(T, nx, ny, nz, d);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        xyz64[3 * i + k] = p[k];
+        xyz[3 * i + k] = (float)p[k];
+        nrm[3 * i + k] = (float)d[k];
+    }
+}

@@ -3138,3 +3138,151 @@ class Mapper:
             branch += "_moved_too_little"
         self.lastMeasurementTimestamp_, self.mapToRangeSensorPrev_ = timestamp, self.mapToRangeSensor_
         return self._end(branch, True)
+
+
+# ---- pose-graph constraints from the resident collection (constraint_builders.cpp, PlaceRecognition.cpp:50-176,
+#      SlamWrapper.cpp:1018-1090) --------------------------------------------------------------------------------
+@dataclass
+class PlaceRecognitionConsistencyCheckParameters:
+    """o3d_slam::PlaceRecognitionConsistencyCheckParameters (Parameters.hpp:112-119): radians and metres."""
+    maxDriftRoll_: float = math.pi / 2
+    maxDriftPitch_: float = math.pi / 2
+    maxDriftYaw_: float = math.pi / 2
+    maxDriftX_: float = 10.0
+    maxDriftY_: float = 10.0
+    maxDriftZ_: float = 15.0
+
+
+@dataclass
+class LoopClosureParameters:
+    """What buildLoopClosureConstraints reads: placeRecognition_ (the RANSAC fields, Parameters.hpp:127-135), its consistency
+    check, the refinement operator (cloudRegistration: one of the RegistrationIcp* classes, its maxCorrespondenceDistance_ and
+    max_iteration_), the map voxel size behind the overlap voxel, and the sampler's seed."""
+    placeRecognition_: PlaceRecognitionParameters = field(default_factory=PlaceRecognitionParameters)
+    consistencyCheck_: PlaceRecognitionConsistencyCheckParameters = field(default_factory=PlaceRecognitionConsistencyCheckParameters)
+    maxIcpCorrespondenceDistance_: float = 0.3
+    minRefinementFitness_: float = 0.7
+    cloudRegistration: object = None
+    mapVoxelSize_: float = 0.03
+    seed: int = 0
+
+    def struct(self) -> "capi.LoopClosureParams":
+        op = self.cloudRegistration if self.cloudRegistration is not None else RegistrationIcpPointToPlane(
+            self.maxIcpCorrespondenceDistance_, 30)
+        voxel = 0.04 if abs(self.mapVoxelSize_) <= 1e-3 else self.mapVoxelSize_          # getMapVoxelSize
+        refine = capi.constraint_params(op.params().cost, op.max_iteration_, True, False, True, 20.0 * voxel,
+                                        op.maxCorrespondenceDistance_, self.maxIcpCorrespondenceDistance_)
+        pr, cc = self.placeRecognition_, self.consistencyCheck_
+        return capi.loop_closure_params(refine, pr.ransacMaxCorrespondenceDistance_, pr.ransacModelSize_, pr.ransacNumIter_,
+                                        pr.ransacProbability_, pr.correspondenceCheckerDistance_, pr.correspondenceCheckerEdgeLength_,
+                                        self.seed, pr.ransacMinCorrespondenceSetSize_, self.minRefinementFitness_,
+                                        (cc.maxDriftRoll_, cc.maxDriftPitch_, cc.maxDriftYaw_, cc.maxDriftX_, cc.maxDriftY_, cc.maxDriftZ_))
+
+
+def isRegistrationConsistent(T, consistencyCheck: "PlaceRecognitionConsistencyCheckParameters | None" = None) -> bool:
+    """PlaceRecognition::isRegistrationConsistent (reg_host_registration_consistent)."""
+    c = consistencyCheck if consistencyCheck is not None else PlaceRecognitionConsistencyCheckParameters()
+    return capi.host_registration_consistent(_check_T(T, "T"), (c.maxDriftRoll_, c.maxDriftPitch_, c.maxDriftYaw_, c.maxDriftX_,
+                                                                c.maxDriftY_, c.maxDriftZ_))[0]
+
+
+def _constraint_of(r: "capi.ConstraintResult", isOdometry: bool) -> Constraint:
+    return Constraint(int(r.source), int(r.target), r.T_matrix(), r.information_matrix(), bool(r.information_estimated), isOdometry)
+
+
+def _collection_call(fn, *args):
+    try:
+        return fn(*args)
+    except RegError as e:
+        raise _translate(e) from None
+
+
+def _sc_buildOdometryConstraint(self, sourceIdx, targetIdx, isRefineOdometryConstraintsBetweenSubmaps_=False) -> Constraint:
+    """o3d_slam::buildOdometryConstraint (constraint_builders.cpp:33-41) between two resident submaps."""
+    p = self.submaps.default_odometry_constraint_params(isRefineOdometryConstraintsBetweenSubmaps_)
+    return _constraint_of(_collection_call(self.submaps.build_constraint, sourceIdx, targetIdx, p), True)
+
+
+def _sc_computeOdometryConstraints(self, finishedSubmapIds=None, isRefineOdometryConstraintsBetweenSubmaps_=False) -> int:
+    """SubmapCollection::computeOdometryConstraints into the list the collection owns: of [(id, stamp)] (or ids), or -- with
+    None -- the overload without candidates.  Returns how many were added."""
+    ids = None if finishedSubmapIds is None else [i[0] if isinstance(i, (tuple, list)) else i for i in finishedSubmapIds]
+    p = self.submaps.default_odometry_constraint_params(isRefineOdometryConstraintsBetweenSubmaps_)
+    return _collection_call(self.submaps.compute_odometry_constraints, ids, p)
+
+
+def _sc_getOdometryConstraints(self) -> list:
+    return [Constraint(c["source"], c["target"], c["T"], c["information"], c["information_valid"], c["is_odometry"])
+            for c in self.submaps.odometry_constraints()]
+
+
+def _sc_buildLoopClosureConstraints(self, loopClosureCandidatesIdxs, params: "LoopClosureParameters | None" = None,
+                                    withVerdicts=False):
+    """SubmapCollection::buildLoopClosureConstraints (SubmapCollection.cpp:291-305) of [(id, stamp)]: per entry
+    PlaceRecognition::buildLoopClosureConstraints on the stored features and the resident maps.  Returns the accepted
+    Constraints, each with `timestamp_`; with `withVerdicts` also every capi.LoopClosureVerdict."""
+    p = (params if params is not None else LoopClosureParameters()).struct()
+    out, verdicts = [], []
+    for idx, stamp in loopClosureCandidatesIdxs:
+        for v in _collection_call(self.submaps.build_loop_closure_constraints, idx, stamp, p):
+            verdicts.append(v)
+            if v.verdict == capi.LC_ACCEPTED:
+                c = _constraint_of(v.constraint, False)
+                c.timestamp_ = int(v.stamp_ns)
+                out.append(c)
+    return (out, verdicts) if withVerdicts else out
+
+
+def _sc_computeFeatures(self, finishedSubmapIds, now_seconds, params: "PlaceRecognitionParameters | None" = None,
+                        computeOdometryConstraints=False):
+    """As before; with computeOdometryConstraints it ends, as the reference does (SubmapCollection.cpp:276), in
+    computeOdometryConstraints(finishedSubmapIds)."""
+    finishedSubmapIds = list(finishedSubmapIds)
+    out = _sc_computeFeatures_before(self, finishedSubmapIds, now_seconds, params)
+    if computeOdometryConstraints:
+        self.computeOdometryConstraints(finishedSubmapIds)
+    return out
+
+
+_sc_computeFeatures_before = SubmapCollection.computeFeatures
+SubmapCollection.computeFeatures = _sc_computeFeatures
+SubmapCollection.buildOdometryConstraint = _sc_buildOdometryConstraint
+SubmapCollection.computeOdometryConstraints = _sc_computeOdometryConstraints
+SubmapCollection.getOdometryConstraints = _sc_getOdometryConstraints
+SubmapCollection.buildLoopClosureConstraints = _sc_buildLoopClosureConstraints
+
+
+def closeLoops(collection: SubmapCollection, problem: OptimizationProblem, mapper, candidates, params=None):
+    """One pass of SlamWrapper::loopClosureWorker and updateSubmapsAndTrajectory (SlamWrapper.cpp:1018-1090) without threads:
+    the loop-closure constraints of `candidates` [(id, stamp)]; none accepted: returns []; else the collection's odometry
+    constraints plus the missing ones (built on a copy of the list, as there), the optimisation problem rebuilt and solved,
+    the submaps transformed, the mapper's pose corrected by the increment of the latest constraint's source, the loop-closure
+    constraints reset to the identity and the adjacency matrix updated.  `mapper` may be None.  Returns the accepted constraints."""
+    loopClosureConstraints = collection.buildLoopClosureConstraints(candidates, params)
+    if not loopClosureConstraints:
+        return []
+    odometryConstraints = collection.getOdometryConstraints()
+    have = [(c.sourceSubmapIdx_, c.targetSubmapIdx_) for c in odometryConstraints]
+    for a, b in collection.submaps.odometry_constraint_pairs(None, have):
+        odometryConstraints.append(collection.buildOdometryConstraint(a, b))
+    problem.clearOdometryConstraints()
+    problem.insertLoopClosureConstraints(loopClosureConstraints)
+    problem.insertOdometryConstraints(odometryConstraints)
+    problem.buildOptimizationProblem(collection)
+    problem.solve()
+    increments = problem.getOptimizedTransformIncrements()
+    collection.transform(increments)
+    latest = max(loopClosureConstraints, key=lambda c: c.timestamp_)
+    if not latest.sourceSubmapIdx_ > latest.targetSubmapIdx_:
+        raise InvalidParameter("update submaps and trajectory: the source of a loop closure must be greater than its target")
+    if mapper is not None:
+        mapper.loopClosureUpdate(increments[latest.sourceSubmapIdx_][0])
+    reset = []
+    for i, old in enumerate(problem.getLoopClosureConstraints()):
+        c = Constraint(old.sourceSubmapIdx_, old.targetSubmapIdx_, np.eye(4), old.informationMatrix_, old.isInformationMatrixValid_,
+                       old.isOdometryConstraint_)
+        c.timestamp_ = getattr(old, "timestamp_", 0)
+        problem.updateLoopClosureConstraint(i, c)
+        reset.append(c)
+    collection.updateAdjacencyMatrix(reset)
+    return loopClosureConstraints
