@@ -740,6 +740,16 @@ public:
         keys.resize((size_t)k * 3);
         return keys;
     }
+    // Submap::carve for the dense map (Submap.cpp:146-157) in one call: transform by T (nullptr: the scan as given, the
+    // reference's choice), removeDuplicatePointsWithinSameVoxels, getKeysOfCarvedPoints, removeKey; the erased keys
+    std::vector<int32_t> carveScan(const double* scan, int64_t n, const double sensor[3], const reg_dense_carve_params& params,
+                                   const double* T = nullptr) {
+        std::vector<int32_t> keys((size_t)info().n_voxels * 3);
+        int64_t k = 0;
+        check(reg_dense_map_carve_scan(m_, scan, n, 0, sensor, &params, T, keys.data(), &k));
+        keys.resize((size_t)k * 3);
+        return keys;
+    }
     void transform(const double T[16]) { check(reg_dense_map_transform(m_, T)); }
     std::array<double, 3> center() {
         std::array<double, 3> c{};
@@ -1274,6 +1284,36 @@ public:
         int32_t n = 0;
         check(reg_submaps_loop_closure_candidates(s_, lastFinishedSubmapIdx, out.data(), (int32_t)out.size(), &n));
         out.resize((size_t)n);
+        return out;
+    }
+    // ---- every submap's dense map ----
+    void enableDenseMaps(const reg_submaps_dense_params& params) { check(reg_submaps_enable_dense_maps(s_, &params)); }
+    // Submap::insertScanDenseMap (Submap.cpp:98-113) of one submap: croppers, transform, insert, the carve when it is due
+    reg_submaps_dense_insert_result insertScanDenseMap(int32_t submapId, const double* points, const double* normals,
+                                                       const double* colors, int64_t n, const double mapToRangeSensor[16],
+                                                       bool isPerformCarving = true, bool onDevice = false) {
+        reg_submaps_dense_insert_result r{};
+        r.struct_size = (int32_t)sizeof(r);
+        check(reg_submaps_insert_scan_dense_map(s_, submapId, points, normals, colors, n, onDevice ? 1 : 0, mapToRangeSensor,
+                                                isPerformCarving ? 1 : 0, &r));
+        return r;
+    }
+    // getDenseMapCopy().toPointCloud() of one submap, in ascending key order
+    DenseMap::Cloud exportDenseSubmap(int32_t submapId, bool wantKeys = false, bool wantCounts = false) {
+        reg_dense_map_info i{};
+        i.struct_size = (int32_t)sizeof(i);
+        check(reg_submaps_get_dense_info(s_, submapId, &i, nullptr));
+        const size_t rows = (size_t)i.n_voxels;
+        DenseMap::Cloud out;
+        out.points.resize(rows * 3);
+        if (i.has_normals) out.normals.resize(rows * 3);
+        if (i.has_colors) out.colors.resize(rows * 3);
+        if (wantKeys) out.keys.resize(rows * 3);
+        if (wantCounts) out.counts.resize(rows);
+        int64_t k = 0;
+        check(reg_submaps_export_dense_submap(s_, submapId, 0, out.points.data(), i.has_normals ? out.normals.data() : nullptr,
+                                              i.has_colors ? out.colors.data() : nullptr, wantKeys ? out.keys.data() : nullptr,
+                                              wantCounts ? out.counts.data() : nullptr, i.n_voxels, &k));
         return out;
     }
     // ---- pose-graph constraints from the resident maps ----

@@ -1366,6 +1366,23 @@ REG_API reg_status reg_dense_map_carve(reg_dense_map* m, const double* scan_xyz,
                                        const double sensor[3], const reg_dense_carve_params* params,
                                        int32_t* removed_keys /* may be NULL; n_voxels x 3: (x, y, z) per row */,
                                        int64_t* n_removed);
+/* The body of Submap::carve for the dense map (Submap.cpp:146-157) in one call, without a host round trip:
+     1. T == NULL: the scan as given (the reference's oddity: the raw sensor-frame scan against a map-frame sensor); with T
+        the scan is transformed first, with the point formula above (carveInMapFrame of icp.DenseMapBuilder);
+     2. removeDuplicatePointsWithinSameVoxels at the map's voxel size, with the contract and the refusals of
+        reg_dedup_voxels: the lowest-index point of every voxel, in ascending index order; a non-finite coordinate or an index
+        outside +-(2^20 - 1) in the (transformed) scan returns REG_BAD_ARGUMENT and leaves the map as it was;
+     3. getKeysOfCarvedPoints on the kept points with the numeric contract of reg_dense_map_carve, word for word.  The
+        lookups go through a coarse level built per call (the bricks of 8 x 8 x 8 voxels the map occupies, with a 512-bit
+        mask each), which only skips keys it has proven absent;
+     4. erase, swap, and the erased keys in ascending key order: a failing call leaves the map as it was.
+   *n_removed, removed_keys and the map afterwards are identical to reg_dedup_voxels, a gather of the kept rows and
+   reg_dense_map_carve on the same inputs.  The gate of Submap::carve (every N scans, a non-empty map) is the caller's:
+   reg_submaps_insert_scan_dense_map applies it.  on_device covers scan_xyz and removed_keys. */
+REG_API reg_status reg_dense_map_carve_scan(reg_dense_map* m, const double* scan_xyz, int64_t n_scan, int on_device,
+                                            const double sensor[3], const reg_dense_carve_params* params,
+                                            const double T[16] /* NULL: the scan as given */,
+                                            int32_t* removed_keys /* may be NULL; n_voxels x 3 */, int64_t* n_removed);
 REG_API reg_status reg_dense_map_transform(reg_dense_map* m, const double T[16]);
 REG_API reg_status reg_dense_map_center(reg_dense_map* m, double center[3]);
 REG_API reg_status reg_dense_map_get_info(const reg_dense_map* m, reg_dense_map_info* info);
@@ -1864,8 +1881,25 @@ REG_API reg_status reg_host_line_process_weight(const double* info, int64_t n_ed
      submap already holds the scan; some ring scans may already be in the target submap) while every piece of host state
      is as before the call: repeating the call would insert those scans twice.  A REG_BAD_ARGUMENT of a map cloud step
      (a refused voxel key) behaves the same way.  In reg_submaps_transform the same holds per submap.
-   Out of scope: each submap's dense map (a reg_dense_map per id stays with the caller, who applies reg_dense_map_transform
-     with the plan), dumpToFile, the feature thread, the mutexes.  Building the constraints is the section after this one. */
+   Dense maps: reg_submaps_enable_dense_maps gives every submap, existing and future (created inside
+     reg_submaps_insert_scan or reg_submaps_force_new_submap), a reg_dense_map of voxel_size with the contract of that section;
+     they are destroyed with the collection.  A second enable is REG_BAD_ARGUMENT; every dense call on a collection without
+     dense maps is REG_NOT_CONFIGURED.  A collection on which they were never enabled behaves exactly as before.
+     reg_submaps_insert_scan_dense_map is Submap::insertScanDenseMap (Submap.cpp:98-113) on submap idx, in this order:
+       1. reg_dense_map_insert_scan with the stored scan parameters (the cropper's centre as given: zero is the reference);
+       2. if perform_carving, the map is not empty and scans_inserted % carve_every_n_scans == 1: reg_dense_map_carve_scan of
+          the scan -- raw (the reference's frame oddity), or transformed by T with carve_in_map_frame -- from the sensor at
+          the translation of T;
+       3. scans_inserted goes up by one.
+     Oddities reproduced: carve_every_n_scans == 1 never carves (x % 1 is 0), and a submap's first insert never carves.
+     Failure contract of the insert: argument errors and an unknown idx are detected before any device work; if step 1 fails
+     nothing has changed; if step 2 fails after a committed step 1, the map keeps the inserted scan and scans_inserted is NOT
+     advanced (repeating the call would insert the scan twice).
+     reg_submaps_transform additionally applies reg_dense_map_transform -- the literal arithmetic of
+     VoxelizedPointCloud::transform, wrong for t != 0 as that section says -- to every submap that receives an increment,
+     right after that submap's map cloud and under the same per-submap commit rule.
+   Out of scope: dumpToFile, the dense-map worker's thread and buffer, the feature thread, the mutexes.  Building the
+     constraints is the section after this one. */
 typedef struct reg_submaps reg_submaps;
 typedef struct {
     int32_t struct_size;                  /* = sizeof(reg_submaps_params); checked */
@@ -1972,6 +2006,44 @@ REG_API reg_status reg_submaps_export(reg_submaps* s, int on_device, double* xyz
                                       int64_t capacity_rows, int64_t* n_out);
 /* ids[n] with dT[16 n] (column-major), in the order of the reference's transformIncrements. */
 REG_API reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const double* dT, int32_t n);
+/* ---- the dense maps of the collection (the comment above) ---- */
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submaps_dense_params); checked */
+    int32_t carve_every_n_scans;          /* carving_.carveSpaceEveryNscans_ (10); >= 1 */
+    int32_t carve_in_map_frame;           /* 0: the reference's frame oddity; 1: the scan is transformed before the carve */
+    int32_t reserved;
+    double  voxel_size;                   /* denseMapBuilder_.mapVoxelSize_ (0.03); finite, > 0 */
+    reg_dense_scan_params  scan;          /* denseMapCropper_ (centre as given; zero is the reference) + colour range */
+    reg_dense_carve_params carve;         /* checked against voxel_size as reg_dense_map_carve checks */
+} reg_submaps_dense_params;
+typedef struct {
+    int32_t struct_size;                  /* = sizeof(reg_submaps_dense_insert_result), set by the caller */
+    int32_t carved;                       /* the gate let the carve run */
+    int64_t n_inserted;                   /* points that passed both croppers */
+    int64_t n_voxels;                     /* of the submap's dense map after the call */
+    int64_t n_removed;                    /* voxels the carve erased */
+    int64_t scans_inserted;               /* nScansInsertedDenseMap_ after the call */
+} reg_submaps_dense_insert_result;
+/* shipped: every 10 scans, the reference's frame, voxel 0.03, no crop, colours within [0, 1], the shipped carve */
+REG_API void reg_default_submaps_dense_params(reg_submaps_dense_params* p);
+/* The validation reg_submaps_enable_dense_maps runs, without a device. */
+REG_API reg_status reg_check_submaps_dense_params(const reg_submaps_dense_params* p);
+/* sizeof of reg_submaps_dense_params, reg_submaps_dense_insert_result */
+REG_API void reg_submaps_dense_struct_sizes(int32_t sizes[2]);
+REG_API reg_status reg_submaps_enable_dense_maps(reg_submaps* s, const reg_submaps_dense_params* params);
+/* xyz / normals / colors: the raw scan in the sensor frame, n x 3 doubles each (normals, colors may be NULL), all host or all
+   device pointers; result may be NULL and is written only by a call that returns REG_OK. */
+REG_API reg_status reg_submaps_insert_scan_dense_map(reg_submaps* s, int32_t idx, const double* xyz, const double* normals,
+                                                     const double* colors, int64_t n, int on_device,
+                                                     const double T_map_to_sensor[16], int32_t perform_carving,
+                                                     reg_submaps_dense_insert_result* result);
+/* reg_dense_map_get_info of submap idx and its nScansInsertedDenseMap_ (either output may be NULL). */
+REG_API reg_status reg_submaps_get_dense_info(const reg_submaps* s, int32_t idx, reg_dense_map_info* info,
+                                              int64_t* scans_inserted);
+/* getDenseMapCopy().toPointCloud() of submap idx: reg_dense_map_export of its dense map, ascending key order. */
+REG_API reg_status reg_submaps_export_dense_submap(reg_submaps* s, int32_t idx, int on_device, double* xyz, double* normals,
+                                                   double* colors, int32_t* keys, int32_t* counts, int64_t capacity_rows,
+                                                   int64_t* n_out);
 /* updateAdjacencyMatrix (:75-81): per constraint addEdge(source, target), then both marked as loop-closure submaps. */
 REG_API reg_status reg_submaps_add_loop_closure_edges(reg_submaps* s, const int32_t* source, const int32_t* target, int32_t n);
 /* The adjacency matrix: adj (capacity x capacity bytes, row-major, 1 = an entry of adjacency_) and marks (capacity

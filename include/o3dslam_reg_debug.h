@@ -51,6 +51,13 @@ REG_API reg_status reg_debug_live_resources(int64_t out[4]);
 REG_API reg_status reg_debug_spd_solve_f64(reg_handle* h, int64_t n, const double* A, const double* b, double* x,
                                            int32_t* status);
 
+/* Measurement switches of reg_dense_map_carve_scan on the dense maps of this handle (tools/time_submaps_dense.py; results
+   never change).  lanes_per_ray: 0 the shipped choice, 8 / 16 / 64 another instance of k_dm_carve_bricks, -1 the lookups of
+   k_dm_carve without the coarse level.  collect_stats != 0: the kernel counts its samples.  last (may be NULL) receives what
+   the last reg_dense_map_carve_scan on this handle left BEFORE this call takes effect: [0] bricks of the coarse level,
+   [1] samples and [2] samples that ended at the coarse level (both 0 unless counted), [3] rays after de-duplication. */
+REG_API reg_status reg_debug_dense_carve(reg_handle* h, int32_t lanes_per_ray, int32_t collect_stats, int64_t last[4]);
+
 #ifdef __cplusplus
 }
 #endif

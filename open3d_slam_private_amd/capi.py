@@ -3471,3 +3471,186 @@ def _submaps_build_loop_closure_constraints(self, last_finished, stamp_ns, param
 
 
 Submaps.build_loop_closure_constraints = _submaps_build_loop_closure_constraints
+
+
+# ---- the dense maps of the collection and the fused carve ---------------------------------------------------------
+class SubmapsDenseParams(C.Structure):
+    """reg_submaps_dense_params (include/o3dslam_reg.h): the dense-map builder of every submap of a collection."""
+    _fields_ = [("struct_size", C.c_int32), ("carve_every_n_scans", C.c_int32), ("carve_in_map_frame", C.c_int32),
+                ("reserved", C.c_int32), ("voxel_size", C.c_double), ("scan", DenseScanParams), ("carve", DenseCarveParams)]
+
+
+class SubmapsDenseInsertResult(C.Structure):
+    """reg_submaps_dense_insert_result (include/o3dslam_reg.h)."""
+    _fields_ = [("struct_size", C.c_int32), ("carved", C.c_int32), ("n_inserted", C.c_int64), ("n_voxels", C.c_int64),
+                ("n_removed", C.c_int64), ("scans_inserted", C.c_int64)]
+
+
+EXPORTS += ["reg_dense_map_carve_scan", "reg_default_submaps_dense_params", "reg_check_submaps_dense_params",
+            "reg_submaps_dense_struct_sizes", "reg_submaps_enable_dense_maps", "reg_submaps_insert_scan_dense_map",
+            "reg_submaps_get_dense_info", "reg_submaps_export_dense_submap", "reg_debug_dense_carve"]
+_dense_bound = False
+
+
+def _dense_lib():
+    """The library with the prototypes of this section set."""
+    global _dense_bound
+    lib = load_library()
+    if not _dense_bound:
+        vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+        pd, pi64 = C.POINTER(C.c_double), C.POINTER(C.c_int64)
+        lib.reg_dense_map_carve_scan.argtypes = [vp, vp, i64, C.c_int, pd, C.POINTER(DenseCarveParams), pd, vp, pi64]
+        lib.reg_default_submaps_dense_params.argtypes = [C.POINTER(SubmapsDenseParams)]
+        lib.reg_default_submaps_dense_params.restype = None
+        lib.reg_check_submaps_dense_params.argtypes = [C.POINTER(SubmapsDenseParams)]
+        lib.reg_submaps_dense_struct_sizes.argtypes = [C.POINTER(i32)]
+        lib.reg_submaps_dense_struct_sizes.restype = None
+        lib.reg_submaps_enable_dense_maps.argtypes = [vp, C.POINTER(SubmapsDenseParams)]
+        lib.reg_submaps_insert_scan_dense_map.argtypes = [vp, i32, vp, vp, vp, i64, C.c_int, pd, i32,
+                                                          C.POINTER(SubmapsDenseInsertResult)]
+        lib.reg_submaps_get_dense_info.argtypes = [vp, i32, C.POINTER(DenseMapInfo), pi64]
+        lib.reg_submaps_export_dense_submap.argtypes = [vp, i32, C.c_int, vp, vp, vp, vp, vp, i64, pi64]
+        lib.reg_debug_dense_carve.argtypes = [vp, i32, i32, pi64]
+        _dense_bound = True
+    return lib
+
+
+def default_submaps_dense_params(crop=None, rgb_min=None, rgb_max=None, carve: "DenseCarveParams | None" = None,
+                                 **overrides) -> SubmapsDenseParams:
+    """reg_default_submaps_dense_params (every 10 scans, the reference's carve frame, voxel 0.03, no crop, colours within
+    [0, 1], the shipped carve); crop / rgb_min / rgb_max as default_dense_scan_params, carve replaces the carve parameters."""
+    p = SubmapsDenseParams()
+    _dense_lib().reg_default_submaps_dense_params(C.byref(p))
+    p.scan = default_dense_scan_params(crop, rgb_min, rgb_max)
+    if carve is not None:
+        p.carve = carve
+        p.carve.struct_size = C.sizeof(DenseCarveParams)
+    for k, v in overrides.items():
+        if k in ("carve_every_n_scans", "carve_in_map_frame"):
+            setattr(p, k, int(v))
+        elif k == "voxel_size":
+            p.voxel_size = float(v)
+        else:
+            raise TypeError(f"unknown dense-map parameter {k}")
+    return p
+
+
+def check_submaps_dense_params(params: "SubmapsDenseParams | None") -> int:
+    """reg_check_submaps_dense_params: the status reg_submaps_enable_dense_maps would return for these parameters (no device)."""
+    return int(_dense_lib().reg_check_submaps_dense_params(C.byref(params) if params is not None else None))
+
+
+def submaps_dense_struct_sizes() -> tuple:
+    """sizeof of reg_submaps_dense_params, reg_submaps_dense_insert_result in the library."""
+    out = (C.c_int32 * 2)()
+    _dense_lib().reg_submaps_dense_struct_sizes(out)
+    return tuple(out)
+
+
+def debug_dense_carve(reg: "Registration", lanes_per_ray=0, collect_stats=False) -> dict:
+    """reg_debug_dense_carve: sets the measurement switches of carve_scan on the handle of `reg` and returns what its last
+    carve_scan left: dict(bricks, samples, coarse_done, rays)."""
+    out = (C.c_int64 * 4)()
+    reg._check(_dense_lib().reg_debug_dense_carve(reg._h, int(lanes_per_ray), int(bool(collect_stats)), out))
+    return dict(bricks=int(out[0]), samples=int(out[1]), coarse_done=int(out[2]), rays=int(out[3]))
+
+
+def _dense_map_carve_scan(self, scan_xyz, sensor, params: "DenseCarveParams | None" = None, T=None, want_keys=True):
+    """reg_dense_map_carve_scan: Submap::carve for the dense map in one call -- transform by T (None: the scan as given),
+    first-wins de-duplication at the map's voxel size, getKeysOfCarvedPoints, erase.  Returns the erased keys (k x 3 int32,
+    ascending key order), or their number with want_keys=False."""
+    x = self._f64(scan_xyz)
+    keys = np.empty((max(self.info().n_voxels, 1), 3), np.int32) if want_keys else None
+    k = self._carve_scan(_ptr(x), x.shape[0], 0, sensor, params, T, _ptr(keys))
+    return keys[:k].copy() if want_keys else k
+
+
+def _dense_map_carve_scan_device(self, scan_ptr, n_scan, sensor, params: "DenseCarveParams | None" = None, T=None,
+                                 keys_ptr=None) -> int:
+    """As carve_scan with the fp64 scan and the int32 key output (n_voxels x 3, may be None) resident in HBM."""
+    vp = lambda p: C.c_void_p(p) if p else None
+    return self._carve_scan(vp(scan_ptr), n_scan, 1, sensor, params, T, vp(keys_ptr))
+
+
+def _dense_map_carve_scan_call(self, x, n, on_device, sensor, params, T, keys):
+    p = params if params is not None else default_dense_carve_params()
+    p.struct_size = C.sizeof(DenseCarveParams)
+    sen = (C.c_double * 3)(*[float(v) for v in sensor])
+    k = C.c_int64(0)
+    self._check(_dense_lib().reg_dense_map_carve_scan(self._m, x, n, on_device, sen, C.byref(p), _T_in_f64(T), keys, C.byref(k)))
+    return int(k.value)
+
+
+DenseMap.carve_scan = _dense_map_carve_scan
+DenseMap.carve_scan_device = _dense_map_carve_scan_device
+DenseMap._carve_scan = _dense_map_carve_scan_call
+
+
+def _submaps_enable_dense_maps(self, params: "SubmapsDenseParams | None" = None):
+    """reg_submaps_enable_dense_maps: every submap, existing and future, gets a dense map."""
+    p = params if params is not None else default_submaps_dense_params()
+    p.struct_size = C.sizeof(SubmapsDenseParams)
+    self._check(_dense_lib().reg_submaps_enable_dense_maps(self._s, C.byref(p)))
+    self.dense_params = p
+
+
+def _submaps_insert_scan_dense_map(self, idx, xyz, T, normals=None, colors=None, perform_carving=True) -> SubmapsDenseInsertResult:
+    """Submap::insertScanDenseMap of submap idx: croppers, transform, insert, and the carve when it is due."""
+    x, nr, cl = DenseMap._f64(xyz), DenseMap._f64(normals), DenseMap._f64(colors)
+    return self._insert_dense(idx, _ptr(x), _ptr(nr), _ptr(cl), x.shape[0], 0, T, perform_carving)
+
+
+def _submaps_insert_scan_dense_map_device(self, idx, xyz_ptr, n, T, nrm_ptr=None, col_ptr=None,
+                                          perform_carving=True) -> SubmapsDenseInsertResult:
+    """As insert_scan_dense_map with the fp64 arrays (n x 3 each) resident in HBM."""
+    vp = lambda p: C.c_void_p(p) if p else None
+    return self._insert_dense(idx, vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr), n, 1, T, perform_carving)
+
+
+def _submaps_insert_dense(self, idx, x, nr, cl, n, on_device, T, perform_carving):
+    res = SubmapsDenseInsertResult()
+    res.struct_size = C.sizeof(SubmapsDenseInsertResult)
+    self._check(_dense_lib().reg_submaps_insert_scan_dense_map(self._s, int(idx), x, nr, cl, int(n), on_device, _T_in_f64(T),
+                                                               int(bool(perform_carving)), C.byref(res)))
+    return res
+
+
+def _submaps_dense_info(self, idx):
+    """(DenseMapInfo, scans_inserted) of the dense map of submap idx."""
+    i, k = DenseMapInfo(), C.c_int64(0)
+    i.struct_size = C.sizeof(DenseMapInfo)
+    self._check(_dense_lib().reg_submaps_get_dense_info(self._s, int(idx), C.byref(i), C.byref(k)))
+    return i, int(k.value)
+
+
+def _submaps_export_dense_submap(self, idx, want_keys=True, want_counts=True):
+    """getDenseMapCopy().toPointCloud() (+ raw keys and counts) of submap idx: the dict of DenseMap.export."""
+    i = self.dense_info(idx)[0]
+    n = int(i.n_voxels)
+    f = lambda on, w, t: np.empty((max(n, 1), w), t) if on else None
+    x, nr, cl = f(True, 3, np.float64), f(i.has_normals, 3, np.float64), f(i.has_colors, 3, np.float64)
+    ky, ct = f(want_keys, 3, np.int32), f(want_counts, 1, np.int32)
+    k = C.c_int64(0)
+    self._check(_dense_lib().reg_submaps_export_dense_submap(self._s, int(idx), 0, _ptr(x), _ptr(nr), _ptr(cl), _ptr(ky), _ptr(ct),
+                                                             max(n, 1), C.byref(k)))
+    cut = lambda a: a[:int(k.value)] if a is not None else None
+    return dict(xyz=cut(x), normals=cut(nr), colors=cut(cl), keys=cut(ky), counts=cut(ct).reshape(-1) if ct is not None else None)
+
+
+def _submaps_export_dense_submap_device(self, idx, capacity_rows, xyz_ptr=None, nrm_ptr=None, col_ptr=None, keys_ptr=None,
+                                        counts_ptr=None) -> int:
+    """As export_dense_submap into arrays resident in HBM (capacity_rows rows each; any may be None).  Returns n_voxels."""
+    vp = lambda p: C.c_void_p(p) if p else None
+    k = C.c_int64(0)
+    self._check(_dense_lib().reg_submaps_export_dense_submap(self._s, int(idx), 1, vp(xyz_ptr), vp(nrm_ptr), vp(col_ptr),
+                                                             vp(keys_ptr), vp(counts_ptr), int(capacity_rows), C.byref(k)))
+    return int(k.value)
+
+
+Submaps.enable_dense_maps = _submaps_enable_dense_maps
+Submaps.insert_scan_dense_map = _submaps_insert_scan_dense_map
+Submaps.insert_scan_dense_map_device = _submaps_insert_scan_dense_map_device
+Submaps._insert_dense = _submaps_insert_dense
+Submaps.dense_info = _submaps_dense_info
+Submaps.export_dense_submap = _submaps_export_dense_submap
+Submaps.export_dense_submap_device = _submaps_export_dense_submap_device

@@ -19,6 +19,7 @@ struct reg_dense_map {
 
 constexpr int64_t kDmMaxRows = 0x7fffffffLL;
 constexpr size_t kDmMinRows = 1024;
+constexpr int kDmCarveLanes = 16;   // lanes per ray of k_dm_carve_bricks (8, 16 and 64 were measured)
 
 // grows geometrically: at least `rows` rows of `row_bytes`, at least twice what the buffer held
 static hipError_t dm_grow(DevBuf& b, size_t rows, size_t row_bytes) {
@@ -132,6 +133,144 @@ static bool dm_offsets(double r, double v, DmOffsets* o) {
     return true;
 }
 
+// the scan parameters reg_dense_map_insert_scan accepts: struct_size, a known crop type, no NaN colour bound
+static bool dm_scan_params_ok(const reg_dense_scan_params* p, CropCfg* crop) {
+    bool ok = p && p->struct_size == (int32_t)sizeof(reg_dense_scan_params) && crop_cfg(&p->crop, crop);
+    for (int k = 0; ok && k < 3; ++k) ok = !(p->rgb_min[k] != p->rgb_min[k]) && !(p->rgb_max[k] != p->rgb_max[k]);
+    return ok;
+}
+// the arguments reg_dense_map_carve refuses, without a device: the bounds of the longest loop a lane can run -- offsets per
+// axis, samples per ray (the reference loops forever at r <= 0)
+static bool dm_carve_params_ok(const reg_dense_carve_params* p, double voxel, DmOffsets* off) {
+    if (!p || p->struct_size != (int32_t)sizeof(reg_dense_carve_params)) return false;
+    const double r = p->neighborhood_radius, step = 2.0 * r;
+    return r > 0.0 && std::isfinite(r) && p->max_ray > 0.0 && std::isfinite(p->max_ray) && std::isfinite(p->truncation) &&
+           std::isfinite(step) && dm_offsets(r, voxel, off) && !(p->max_ray / step > 65536.0);
+}
+static reg_status dm_carve_args(reg_dense_map* m, const char* who, const double* scan_xyz, int64_t n_scan, const double* sensor,
+                                const reg_dense_carve_params* p, DmOffsets* off) {
+    reg_handle* h = m->h;
+    if (!p || p->struct_size != (int32_t)sizeof(reg_dense_carve_params) || !sensor || !dm_cloud_args_ok(scan_xyz, n_scan)) {
+        h->err = std::string(who) + ": params / sensor missing, a wrong struct_size, or a bad scan";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!dm_carve_params_ok(p, m->voxel, off)) {
+        h->err = std::string(who) + ": neighborhood_radius and max_ray finite and > 0, truncation finite, at most 16 offsets per "
+                                    "axis, max_ray / (2 neighborhood_radius) <= 65536";
+        return REG_BAD_ARGUMENT;
+    }
+    return REG_OK;
+}
+// the erase marks of `rows` voxels (or the de-duplication flags of `rows` scan points), the keep flags and the scans of both
+static reg_status dm_reserve_marks(reg_handle* h, size_t rows) {
+    for (DevBuf* b : {&h->dm_mark, &h->dm_off1, &h->dm_keep, &h->dm_off2}) HIPCHK(h, b->reserve(rows * 4));
+    return REG_OK;
+}
+// Erases the voxels whose mark (h->dm_mark, enqueued on the stream) is set: builds the rest in the spare side, swaps, and
+// reports the erased keys in ascending order.  A failure leaves the map as it was.
+static reg_status dm_erase_marked(reg_dense_map* m, int on_device, int32_t* removed_keys, int64_t* n_removed) {
+    reg_handle* h = m->h;
+    const int64_t n = m->n;
+    uint32_t *mark = h->dm_mark.as<uint32_t>(), *rem_off = h->dm_off1.as<uint32_t>();
+    uint32_t *keep = h->dm_keep.as<uint32_t>(), *keep_off = h->dm_off2.as<uint32_t>();
+    const DmCols in = dm_cols(m, m->cur, m->has_nrm, m->has_col);
+    int64_t removed = 0;
+    REGCHK(scan_total(h, mark, rem_off, n, &removed));
+    HIPCHK(h, hipGetLastError());
+    if (removed == 0) return REG_OK;
+    StagedOut so(h, h->dm_out, on_device);
+    const int s_keys = so.add(removed_keys, 3);
+    HIPCHK(h, so.reserve((size_t)removed));
+    HIPCHK(h, dm_reserve_spare(m, (size_t)(n - removed), m->has_nrm, m->has_col));
+    const DmCols out = dm_cols(m, m->cur ^ 1, m->has_nrm, m->has_col);
+    k_dm_keep_flags<<<grid_for(n), 256, 0, h->stream>>>(mark, n, keep);
+    REGCHK(scan_excl(h, h->rp_tmp, keep, keep_off, (size_t)n));
+    k_dm_erase<<<grid_for(n), 256, 0, h->stream>>>(in, n, mark, keep_off, rem_off, out, so.at<int32_t>(s_keys));
+    HIPCHK(h, so.copy_back((size_t)removed));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    dm_swap(m, n - removed, m->has_nrm, m->has_col);
+    if (n_removed) *n_removed = removed;
+    return REG_OK;
+}
+
+template <int kLanes>
+static void dm_launch_carve_bricks(reg_handle* h, const double* rays, int64_t n_rays, const double* sensor,
+                                   const reg_dense_carve_params* p, double voxel, const DmOffsets& off, const uint64_t* rkeys,
+                                   int64_t n_res, int64_t n_bricks, unsigned long long* stats) {
+    const double r = p->neighborhood_radius;
+    k_dm_carve_bricks<kLanes><<<grid_for(n_rays, 256 / kLanes), 256, 0, h->stream>>>(
+        rays, n_rays, sensor[0], sensor[1], sensor[2], 2.0 * r, p->max_ray, p->truncation, r, voxel, voxel * 0.5, off, rkeys, n_res,
+        h->dm_bkeys.as<uint64_t>(), h->dm_bmask.as<uint64_t>(), n_bricks, h->dm_mark.as<uint32_t>(), stats);
+}
+
+// Submap::carve for the dense map on a device scan (n > 0): transform (T given), first-wins de-duplication at the map's voxel
+// size, the carve of the kept points through the coarse level, erase.  Arguments are checked by the caller.
+static reg_status dm_carve_scan_device(reg_dense_map* m, const char* who, const double* d_scan, int64_t n_scan, const double* sensor,
+                                       const reg_dense_carve_params* p, const DmOffsets& off, const double* T, int on_device,
+                                       int32_t* removed_keys, int64_t* n_removed) {
+    reg_handle* h = m->h;
+    const int64_t n = m->n, rows = std::max(n_scan, n);
+    HIPCHK(h, h->dm.reserve((size_t)rows));   // both sorts of this call: no buffer moves while a kernel reads it
+    int64_t n_rays = 0;
+    REGCHK(dm_sorted_keys(h, who, d_scan, nullptr, n_scan, T, m->inv, &n_rays));   // the refusals of reg_dedup_voxels
+    h->dm_last[0] = h->dm_last[1] = h->dm_last[2] = 0;
+    h->dm_last[3] = n_rays;
+    if (n == 0) return REG_OK;
+    const double* px = T ? h->dm_tf[0].as<double>() : d_scan;
+    REGCHK(dm_reserve_marks(h, (size_t)rows));
+    HIPCHK(h, h->dm_crop[0].reserve((size_t)n_rays * 24));
+    const RunArrays a = h->dm.arrays();
+    uint32_t *flags = h->dm_keep.as<uint32_t>(), *offs = h->dm_off2.as<uint32_t>();
+    double* rays = h->dm_crop[0].as<double>();
+    HIPCHK(h, hipMemsetAsync(flags, 0, (size_t)n_scan * 4, h->stream));
+    k_dm_dedup_mark<<<grid_for(n_scan), 256, 0, h->stream>>>(a.heads, a.svals, n_scan, flags);
+    REGCHK(scan_excl(h, h->rp_tmp, flags, offs, (size_t)n_scan));
+    k_gather_rows<3, true><<<grid_for(n_scan), 256, 0, h->stream>>>(cols64_in(px, nullptr, nullptr), n_scan, flags, offs,
+                                                                    Cols64{rays, nullptr, nullptr}, nullptr);
+    const uint64_t* rkeys = dm_cols(m, m->cur, false, false).key;
+    HIPCHK(h, hipMemsetAsync(h->dm_mark.p, 0, (size_t)n * 4, h->stream));
+    const int lanes = h->dm_carve_lanes;
+    if (lanes < 0) {   // measurement only (reg_debug_dense_carve): the lookups of reg_dense_map_carve
+        const double r = p->neighborhood_radius;
+        k_dm_carve<<<grid_for(n_rays, 4), 256, 0, h->stream>>>(rays, n_rays, sensor[0], sensor[1], sensor[2], 2.0 * r, p->max_ray,
+                                                               p->truncation, r, m->voxel, m->voxel * 0.5, off, rkeys, n,
+                                                               h->dm_mark.as<uint32_t>());
+        return dm_erase_marked(m, on_device, removed_keys, n_removed);
+    }
+    // the coarse level of the map as it stands
+    uint32_t tail[2];
+    k_dm_brick_keys<<<grid_for(n), 256, 0, h->stream>>>(rkeys, n, a.keys, a.vals);
+    REGCHK(sort_runs(h, a, n, tail));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipGetLastError());
+    const int64_t n_bricks = flag_total(tail);
+    HIPCHK(h, dm_grow(h->dm_bkeys, (size_t)n_bricks, 8));
+    HIPCHK(h, dm_grow(h->dm_bmask, (size_t)n_bricks, 64));
+    k_dm_brick_masks<<<grid_for(n), 256, 0, h->stream>>>(a.sorted, a.svals, n, a.heads, a.run, rkeys, h->dm_bkeys.as<uint64_t>(),
+                                                         h->dm_bmask.as<uint64_t>());
+    unsigned long long* stats = nullptr;
+    if (h->dm_carve_stats) {
+        HIPCHK(h, h->dm_stats.reserve(16));
+        HIPCHK(h, hipMemsetAsync(h->dm_stats.p, 0, 16, h->stream));
+        stats = h->dm_stats.as<unsigned long long>();
+    }
+    switch (lanes ? lanes : kDmCarveLanes) {
+        case 8: dm_launch_carve_bricks<8>(h, rays, n_rays, sensor, p, m->voxel, off, rkeys, n, n_bricks, stats); break;
+        case 16: dm_launch_carve_bricks<16>(h, rays, n_rays, sensor, p, m->voxel, off, rkeys, n, n_bricks, stats); break;
+        default: dm_launch_carve_bricks<64>(h, rays, n_rays, sensor, p, m->voxel, off, rkeys, n, n_bricks, stats); break;
+    }
+    h->dm_last[0] = n_bricks;
+    if (stats) {
+        unsigned long long got[2] = {0, 0};
+        HIPCHK(h, hipMemcpyAsync(got, stats, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        h->dm_last[1] = (int64_t)got[0];
+        h->dm_last[2] = (int64_t)got[1];
+    }
+    return dm_erase_marked(m, on_device, removed_keys, n_removed);
+}
+
 extern "C" {
 
 int32_t reg_host_dense_offsets(double neighborhood_radius, double voxel_size, double* offsets) {
@@ -220,9 +359,7 @@ reg_status reg_dense_map_insert_scan(reg_dense_map* m, const double* xyz, const 
     if (n_inserted) *n_inserted = 0;
     if (n_voxels) *n_voxels = m->n;
     CropCfg crop;
-    bool ok = p && p->struct_size == (int32_t)sizeof(reg_dense_scan_params) && crop_cfg(&p->crop, &crop);
-    for (int k = 0; ok && k < 3; ++k) ok = !(p->rgb_min[k] != p->rgb_min[k]) && !(p->rgb_max[k] != p->rgb_max[k]);
-    if (!ok) {
+    if (!dm_scan_params_ok(p, &crop)) {
         h->err = "reg_dense_map_insert_scan: params missing, of the wrong struct_size, an unknown crop type or a NaN colour bound";
         return REG_BAD_ARGUMENT;
     }
@@ -278,52 +415,47 @@ reg_status reg_dense_map_carve(reg_dense_map* m, const double* scan_xyz, int64_t
     if (!m) return REG_BAD_ARGUMENT;
     reg_handle* h = m->h;
     if (n_removed) *n_removed = 0;
-    if (!p || p->struct_size != (int32_t)sizeof(reg_dense_carve_params) || !sensor || !dm_cloud_args_ok(scan_xyz, n_scan)) {
-        h->err = "reg_dense_map_carve: params / sensor missing, a wrong struct_size, or a bad scan";
-        return REG_BAD_ARGUMENT;
-    }
-    const double r = p->neighborhood_radius, step = 2.0 * r;
     DmOffsets off;
-    // the bounds of the longest loop a lane can run: offsets per axis, samples per ray (the reference loops forever at r <= 0)
-    if (!(r > 0.0) || !std::isfinite(r) || !(p->max_ray > 0.0) || !std::isfinite(p->max_ray) || !std::isfinite(p->truncation) ||
-        !std::isfinite(step) || !dm_offsets(r, m->voxel, &off) || p->max_ray / step > 65536.0) {
-        h->err = "reg_dense_map_carve: neighborhood_radius and max_ray finite and > 0, truncation finite, at most 16 offsets per "
-                 "axis, max_ray / (2 neighborhood_radius) <= 65536";
-        return REG_BAD_ARGUMENT;
-    }
+    REGCHK(dm_carve_args(m, "reg_dense_map_carve", scan_xyz, n_scan, sensor, p, &off));
     if (!h->device_ok) return REG_DEVICE_ERROR;
     if (n_scan == 0 || m->n == 0) return REG_OK;
     HIPCHK(h, hipSetDevice(h->prm.device));
     const double* d_scan = scan_xyz;
     HIPCHK(h, staged_input(h, h->dm_in[0], d_scan, (size_t)n_scan * 3, on_device, &d_scan));
     const int64_t n = m->n;
-    HIPCHK(h, h->dm_mark.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_off1.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_keep.reserve((size_t)n * 4));
-    HIPCHK(h, h->dm_off2.reserve((size_t)n * 4));
-    uint32_t *mark = h->dm_mark.as<uint32_t>(), *rem_off = h->dm_off1.as<uint32_t>();
-    uint32_t *keep = h->dm_keep.as<uint32_t>(), *keep_off = h->dm_off2.as<uint32_t>();
-    const DmCols in = dm_cols(m, m->cur, m->has_nrm, m->has_col);
-    HIPCHK(h, hipMemsetAsync(mark, 0, (size_t)n * 4, h->stream));
-    k_dm_carve<<<grid_for(n_scan, 4), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], step, p->max_ray,
-                                                           p->truncation, r, m->voxel, m->voxel * 0.5, off, in.key, n, mark);
-    int64_t removed = 0;
-    REGCHK(scan_total(h, mark, rem_off, n, &removed));
-    HIPCHK(h, hipGetLastError());
-    if (removed == 0) return REG_OK;
-    StagedOut so(h, h->dm_out, on_device);
-    const int s_keys = so.add(removed_keys, 3);
-    HIPCHK(h, so.reserve((size_t)removed));
-    HIPCHK(h, dm_reserve_spare(m, (size_t)(n - removed), m->has_nrm, m->has_col));
-    const DmCols out = dm_cols(m, m->cur ^ 1, m->has_nrm, m->has_col);
-    k_dm_keep_flags<<<grid_for(n), 256, 0, h->stream>>>(mark, n, keep);
-    REGCHK(scan_excl(h, h->rp_tmp, keep, keep_off, (size_t)n));
-    k_dm_erase<<<grid_for(n), 256, 0, h->stream>>>(in, n, mark, keep_off, rem_off, out, so.at<int32_t>(s_keys));
-    HIPCHK(h, so.copy_back((size_t)removed));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipGetLastError());
-    dm_swap(m, n - removed, m->has_nrm, m->has_col);
-    if (n_removed) *n_removed = removed;
+    REGCHK(dm_reserve_marks(h, (size_t)n));
+    const double r = p->neighborhood_radius;
+    HIPCHK(h, hipMemsetAsync(h->dm_mark.p, 0, (size_t)n * 4, h->stream));
+    k_dm_carve<<<grid_for(n_scan, 4), 256, 0, h->stream>>>(d_scan, n_scan, sensor[0], sensor[1], sensor[2], 2.0 * r, p->max_ray,
+                                                           p->truncation, r, m->voxel, m->voxel * 0.5, off,
+                                                           dm_cols(m, m->cur, false, false).key, n, h->dm_mark.as<uint32_t>());
+    return dm_erase_marked(m, on_device, removed_keys, n_removed);
+}
+
+reg_status reg_dense_map_carve_scan(reg_dense_map* m, const double* scan_xyz, int64_t n_scan, int on_device, const double sensor[3],
+                                    const reg_dense_carve_params* p, const double T[16], int32_t* removed_keys,
+                                    int64_t* n_removed) {
+    if (!m) return REG_BAD_ARGUMENT;
+    reg_handle* h = m->h;
+    if (n_removed) *n_removed = 0;
+    DmOffsets off;
+    REGCHK(dm_carve_args(m, "reg_dense_map_carve_scan", scan_xyz, n_scan, sensor, p, &off));
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    if (n_scan == 0) return REG_OK;
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    const double* d_scan = scan_xyz;
+    HIPCHK(h, staged_input(h, h->dm_in[0], d_scan, (size_t)n_scan * 3, on_device, &d_scan));
+    return dm_carve_scan_device(m, "reg_dense_map_carve_scan", d_scan, n_scan, sensor, p, off, T, on_device, removed_keys,
+                                n_removed);
+}
+
+reg_status reg_debug_dense_carve(reg_handle* h, int32_t lanes_per_ray, int32_t collect_stats, int64_t last[4]) {
+    if (!h || !(lanes_per_ray == 0 || lanes_per_ray == -1 || lanes_per_ray == 8 || lanes_per_ray == 16 || lanes_per_ray == 64))
+        return REG_BAD_ARGUMENT;
+    if (last)
+        for (int k = 0; k < 4; ++k) last[k] = h->dm_last[k];
+    h->dm_carve_lanes = lanes_per_ray;
+    h->dm_carve_stats = collect_stats != 0;
     return REG_OK;
 }
 

@@ -134,6 +134,13 @@ struct reg_handle {
     DevBuf dm_in[3], dm_crop[3], dm_tf[2], dm_rank, dm_new, dm_newoff, dm_newkeys, dm_mark, dm_keep, dm_off1, dm_off2, dm_misc,
         dm_out;
     RunBufs dm;
+    // reg_dense_map_carve_scan: the brick keys and occupancy masks of the map being carved; the measurement switches of
+    // reg_debug_dense_carve (lanes per ray: 0 the default, 8 / 16 / 64, -1 the lookups of k_dm_carve; sample counters) and
+    // what the last call left: bricks, samples, samples done at the coarse level, rays
+    DevBuf dm_bkeys, dm_bmask, dm_stats;
+    int dm_carve_lanes = 0;
+    bool dm_carve_stats = false;
+    int64_t dm_last[4] = {0, 0, 0, 0};
     // the map clouds of this handle (host_mapcloud.hpp): staged inputs (scan points, normals, covariances; raw scan), the
     // transformed raw scan, and the working cloud an insert voxelises (survivors of the carve + the transformed scan)
     DevBuf mc_in[4], mc_raw, mc_cat[3];

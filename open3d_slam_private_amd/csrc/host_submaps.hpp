@@ -20,7 +20,12 @@ struct SmSubmap {
     int64_t n_keys = 0;
     DevBuf s_xyz64, s_xyz, s_nrm, s_fpfh;   // the feature store: sparseMapCloud_ (fp64, fp32), its normals, feature_
     int64_t n_sparse = 0;
-    ~SmSubmap() { reg_map_cloud_destroy(map); }
+    reg_dense_map* dense = nullptr;   // denseMap_: null until reg_submaps_enable_dense_maps
+    int64_t dense_scans = 0;          // nScansInsertedDenseMap_
+    ~SmSubmap() {
+        reg_dense_map_destroy(dense);
+        reg_map_cloud_destroy(map);
+    }
 };
 struct SmConstraint {   // o3d_slam::Constraint
     int32_t source, target, flags;   // flags: bit 0 isInformationMatrixValid_, bit 1 isOdometryConstraint_
@@ -47,6 +52,8 @@ struct reg_submaps {
     reg_handle* ch[4] = {nullptr, nullptr, nullptr, nullptr};   // the constraint builders' handles, by cost; created on first use
     std::vector<SmConstraint> odometry;   // odometryConstraints_
     DevBuf lc_ab, lc_ba, lc_cor, lc_inl;  // loop closure: nn_ab, nn_ba, the correspondences, RANSAC's inlier pairs
+    bool dense_on = false;                // reg_submaps_enable_dense_maps has run
+    reg_submaps_dense_params dprm;
     ~reg_submaps() {
         for (reg_handle* w : ch) reg_destroy(w);
     }
@@ -80,6 +87,7 @@ static int sm_spare_slot(const reg_submaps* s) {
 static SmSubmap* sm_new_submap(reg_submaps* s, int32_t id, int32_t parent, const double* origin) {
     std::unique_ptr<SmSubmap> b(new SmSubmap());
     if (reg_map_cloud_create(s->h, &s->prm.map, &b->map) != REG_OK) return nullptr;
+    if (s->dense_on && reg_dense_map_create(s->h, s->dprm.voxel_size, &b->dense) != REG_OK) return nullptr;
     b->id = id;
     b->parent = parent;
     std::memcpy(b->origin, origin, sizeof(b->origin));
@@ -685,6 +693,7 @@ reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const doubl
     }
     auto apply = [&](SmSubmap& b, const double* T) -> reg_status {   // Submap::transform (Submap.cpp:115-128)
         REGCHK(reg_map_cloud_transform(b.map, T));
+        if (b.dense) REGCHK(reg_dense_map_transform(b.dense, T));   // denseMap_.transform (Submap.cpp:122-125)
         if (b.n_sparse > 0) {   // sparseMapCloud_.Transform (Submap.cpp:117); feature_ stays
             HIPCHK(h, hipSetDevice(h->prm.device));
             k_sm_transform_sparse<<<grid_for(b.n_sparse), 256, 0, h->stream>>>(b.s_xyz64.as<double>(), b.s_xyz.as<float>(),
@@ -711,6 +720,131 @@ reg_status reg_submaps_transform(reg_submaps* s, const int32_t* ids, const doubl
         if (!listed[i] && plan[i] >= 0) REGCHK(apply(*s->subs[i], dT + 16 * (size_t)plan[i]));
     s->ring.clear();   // :372
     return REG_OK;
+}
+
+// ---- the dense maps of the collection ----
+void reg_default_submaps_dense_params(reg_submaps_dense_params* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(reg_submaps_dense_params);
+    p->carve_every_n_scans = 10;   // SpaceCarvingParameters, Parameters.hpp:88-95
+    p->voxel_size = 0.03;          // MapBuilderParameters::mapVoxelSize_
+    reg_default_dense_scan_params(&p->scan);
+    reg_default_dense_carve_params(&p->carve);
+}
+
+reg_status reg_check_submaps_dense_params(const reg_submaps_dense_params* p) {
+    if (!p || p->struct_size != (int32_t)sizeof(reg_submaps_dense_params)) return REG_BAD_ARGUMENT;
+    CropCfg crop;
+    DmOffsets off;
+    if (p->carve_every_n_scans < 1 || (p->carve_in_map_frame != 0 && p->carve_in_map_frame != 1) || !(p->voxel_size > 0.0) ||
+        !std::isfinite(p->voxel_size) || !dm_scan_params_ok(&p->scan, &crop) || !dm_carve_params_ok(&p->carve, p->voxel_size, &off))
+        return REG_BAD_ARGUMENT;
+    return REG_OK;
+}
+
+void reg_submaps_dense_struct_sizes(int32_t sizes[2]) {
+    if (!sizes) return;
+    sizes[0] = (int32_t)sizeof(reg_submaps_dense_params);
+    sizes[1] = (int32_t)sizeof(reg_submaps_dense_insert_result);
+}
+
+reg_status reg_submaps_enable_dense_maps(reg_submaps* s, const reg_submaps_dense_params* p) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (s->dense_on) {
+        h->err = "reg_submaps_enable_dense_maps: the collection has dense maps already";
+        return REG_BAD_ARGUMENT;
+    }
+    if (reg_check_submaps_dense_params(p) != REG_OK) {
+        h->err = "reg_submaps_enable_dense_maps: params missing or of a wrong struct_size (scan's and carve's included), "
+                 "carve_every_n_scans < 1, carve_in_map_frame not 0 / 1, voxel_size not finite and > 0, an unknown crop type, a "
+                 "NaN colour bound, or carve parameters reg_dense_map_carve refuses at this voxel size";
+        return REG_BAD_ARGUMENT;
+    }
+    std::vector<reg_dense_map*> made;   // holds no device memory until the first insert: all or nothing
+    for (size_t k = 0; k < s->subs.size(); ++k) {
+        reg_dense_map* m = nullptr;
+        if (reg_dense_map_create(h, p->voxel_size, &m) != REG_OK) {
+            for (reg_dense_map* d : made) reg_dense_map_destroy(d);
+            return REG_BAD_ARGUMENT;
+        }
+        made.push_back(m);
+    }
+    for (size_t k = 0; k < s->subs.size(); ++k) s->subs[k]->dense = made[k];
+    s->dprm = *p;
+    s->dense_on = true;
+    return REG_OK;
+}
+
+reg_status reg_submaps_insert_scan_dense_map(reg_submaps* s, int32_t idx, const double* xyz, const double* normals,
+                                             const double* colors, int64_t n, int on_device, const double T[16],
+                                             int32_t perform_carving, reg_submaps_dense_insert_result* res) {
+    if (!s) return REG_BAD_ARGUMENT;
+    reg_handle* h = s->h;
+    if (!s->dense_on) {
+        h->err = "reg_submaps_insert_scan_dense_map: dense maps are not enabled (reg_submaps_enable_dense_maps)";
+        return REG_NOT_CONFIGURED;
+    }
+    if (!sm_idx_ok(s, idx) || !T || !dm_cloud_args_ok(xyz, n) || (res && res->struct_size != (int32_t)sizeof(*res))) {
+        h->err = "reg_submaps_insert_scan_dense_map: an unknown submap, T missing, a bad scan (0 <= n <= 2^31 - 1 and a cloud for "
+                 "n > 0), or a result of the wrong struct_size";
+        return REG_BAD_ARGUMENT;
+    }
+    if (!h->device_ok) return REG_DEVICE_ERROR;
+    SmSubmap& b = *s->subs[idx];
+    HIPCHK(h, hipSetDevice(h->prm.device));
+    // the scan is uploaded once: both steps read the device copy
+    const double* d[3] = {xyz, normals, colors};
+    if (n > 0)
+        for (int k = 0; k < 3; ++k) HIPCHK(h, staged_input(h, h->dm_in[k], d[k], (size_t)n * 3, on_device, &d[k]));
+    int64_t n_inserted = 0, n_voxels = b.dense->n, n_removed = 0;
+    REGCHK(reg_dense_map_insert_scan(b.dense, d[0], d[1], d[2], n, 1, &s->dprm.scan, T, &n_inserted, &n_voxels));   // Submap.cpp:99-106
+    const bool carve = perform_carving && b.dense->n > 0 && b.dense_scans % s->dprm.carve_every_n_scans == 1;   // :146-149
+    if (carve && n > 0) {
+        DmOffsets off;
+        dm_offsets(s->dprm.carve.neighborhood_radius, b.dense->voxel, &off);   // checked when the maps were enabled
+        REGCHK(dm_carve_scan_device(b.dense, "reg_submaps_insert_scan_dense_map", d[0], n, T + 12, &s->dprm.carve, off,
+                                    s->dprm.carve_in_map_frame ? T : nullptr, 1, nullptr, &n_removed));
+    }
+    b.dense_scans += 1;   // :111
+    if (res) {
+        std::memset(res, 0, sizeof(*res));
+        res->struct_size = (int32_t)sizeof(*res);
+        res->carved = carve;
+        res->n_inserted = n_inserted;
+        res->n_voxels = b.dense->n;
+        res->n_removed = n_removed;
+        res->scans_inserted = b.dense_scans;
+    }
+    return REG_OK;
+}
+
+reg_status reg_submaps_get_dense_info(const reg_submaps* s, int32_t idx, reg_dense_map_info* info, int64_t* scans_inserted) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (!s->dense_on) {
+        s->h->err = "reg_submaps_get_dense_info: dense maps are not enabled (reg_submaps_enable_dense_maps)";
+        return REG_NOT_CONFIGURED;
+    }
+    if (!sm_idx_ok(s, idx)) return REG_BAD_ARGUMENT;
+    if (info) REGCHK(reg_dense_map_get_info(s->subs[idx]->dense, info));
+    if (scans_inserted) *scans_inserted = s->subs[idx]->dense_scans;
+    return REG_OK;
+}
+
+reg_status reg_submaps_export_dense_submap(reg_submaps* s, int32_t idx, int on_device, double* xyz, double* normals, double* colors,
+                                           int32_t* keys, int32_t* counts, int64_t capacity_rows, int64_t* n_out) {
+    if (!s) return REG_BAD_ARGUMENT;
+    if (n_out) *n_out = 0;
+    if (!s->dense_on) {
+        s->h->err = "reg_submaps_export_dense_submap: dense maps are not enabled (reg_submaps_enable_dense_maps)";
+        return REG_NOT_CONFIGURED;
+    }
+    if (!sm_idx_ok(s, idx)) {
+        s->h->err = "reg_submaps_export_dense_submap: an unknown submap";
+        return REG_BAD_ARGUMENT;
+    }
+    return reg_dense_map_export(s->subs[idx]->dense, on_device, xyz, normals, colors, keys, counts, capacity_rows, n_out);
 }
 
 reg_status reg_submaps_add_loop_closure_edges(reg_submaps* s, const int32_t* source, const int32_t* target, int32_t n) {

@@ -220,6 +220,190 @@ __global__ void __launch_bounds__(256) k_dm_carve(const double* __restrict__ sca
         distance += step;
     }
 }
+
+// ---- carve by bricks (reg_dense_map_carve_scan).  The coarse level of a map, built per call from its
+// ascending keys: a brick is 8 x 8 x 8 voxels; its key is the voxel key with every 21-bit offset-binary field shifted right
+// by 3, packed as vox_pack packs.  The brick keys are sorted and run-length encoded (sort_runs); per brick a 512-bit
+// occupancy mask: word = z & 7, bit = (y & 7) << 3 | (x & 7).
+constexpr int kDmBrickShift = 3;
+constexpr int kDmBrickSlots = 64;   // bricks a sample's box may touch: 4 per axis (16 offsets span at most 17 voxels: 3)
+constexpr uint64_t kDmFieldMask = (1ull << kVoxBits) - 1;
+__device__ __forceinline__ uint64_t dm_brick_pack(uint64_t bx, uint64_t by, uint64_t bz) {
+    return (bz << (2 * kVoxBits)) | (by << kVoxBits) | bx;
+}
+__global__ void k_dm_brick_keys(const uint64_t* __restrict__ rkeys, int64_t n, uint64_t* __restrict__ keys,
+                                uint32_t* __restrict__ vals) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t k = rkeys[i];
+    keys[i] = dm_brick_pack((k & kDmFieldMask) >> kDmBrickShift, ((k >> kVoxBits) & kDmFieldMask) >> kDmBrickShift,
+                            ((k >> (2 * kVoxBits)) & kDmFieldMask) >> kDmBrickShift);
+    vals[i] = (uint32_t)i;
+}
+// one thread per run head of the sorted brick keys: the brick's key and the OR of its voxels' bits (a run holds at most 512)
+__global__ void k_dm_brick_masks(const uint64_t* __restrict__ sorted, const uint32_t* __restrict__ svals, int64_t n,
+                                 const uint32_t* __restrict__ heads, const uint32_t* __restrict__ run,
+                                 const uint64_t* __restrict__ rkeys, uint64_t* __restrict__ bkeys, uint64_t* __restrict__ bmask) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= n || !heads[i]) return;
+    const uint64_t key = sorted[i];
+    uint64_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int64_t j = i; j < n && sorted[j] == key; ++j) {
+        const uint64_t k = rkeys[svals[j]];
+        const uint64_t bit = 1ull << ((((k >> kVoxBits) & 7ull) << 3) | (k & 7ull));
+        const int z = (int)((k >> (2 * kVoxBits)) & 7ull);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) w[q] |= z == q ? bit : 0ull;   // compile-time indices: w stays in registers
+    }
+    const size_t r = run[i];
+    bkeys[r] = key;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) bmask[8 * r + q] = w[q];
+}
+
+// The carve with the coarse level in front of the lookups.  kLanes lanes per ray (a lane group never straddles a wave);
+// the sample loop is uniform in the group, so `distance` is the reference's running sum in each of its lanes.  The
+// arithmetic per sample and per test point is that of k_dm_carve, operation for operation; only the way a lookup key is
+// found in the map differs:
+//   A. the box of a sample: per axis the keys floor((p + first offset) / v) and floor((p + last offset) / v) -- the
+//      operations of a test point, and x -> floor((p + x) / v) is monotonic in fp64, so every test point's key lies between
+//      them -- widened by the sample's own key and cut to the packable range.  The lanes of the group look the box's bricks
+//      up in the brick keys (one binary search each) and leave their positions in the group's LDS slots.  No brick: the
+//      sample is done.
+//   B. a test point whose brick is absent, or whose bit in the brick's mask is clear, is not in the map; the others go on
+//      to key_lower_bound and the mark.  A box of more than kDmBrickSlots bricks (not reachable with 16 offsets) and a
+//      key outside its sample's box are looked up directly: the coarse level only ever skips keys it has proven absent.
+// stats (null in production): [0] samples, [1] samples that ended at A, added once per ray.
+template <int kLanes>
+__global__ void __launch_bounds__(256)
+    k_dm_carve_bricks(const double* __restrict__ scan, int64_t n_scan, double sx, double sy, double sz, double step, double max_ray,
+                      double trunc, double radius, double voxel, double half_voxel, DmOffsets off,
+                      const uint64_t* __restrict__ rkeys, int64_t n_res, const uint64_t* __restrict__ bkeys,
+                      const uint64_t* __restrict__ bmask, int64_t n_bricks, uint32_t* __restrict__ mark,
+                      unsigned long long* __restrict__ stats) {
+    static_assert(kLanes == 8 || kLanes == 16 || kLanes == 32 || kLanes == 64, "a lane group divides a wave");
+    constexpr int kRays = 256 / kLanes;
+    __shared__ double s_off[kDmMaxOffsets];   // lane-indexed below: LDS, not a runtime-indexed kernel argument
+    __shared__ int32_t s_slot[kRays][kDmBrickSlots];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < kDmMaxOffsets; ++k) s_off[k] = off.d[k];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x % kLanes, g = threadIdx.x / kLanes;
+    const int gbase = (threadIdx.x & 63) - lane;
+    const unsigned long long gmask = kLanes == 64 ? ~0ull : ((1ull << kLanes) - 1ull);
+    const int64_t i = blockIdx.x * (int64_t)kRays + g;
+    if (i >= n_scan) return;   // group-uniform, after the only barrier
+    const double dx = scan[3 * i] - sx, dy = scan[3 * i + 1] - sy, dz = scan[3 * i + 2] - sz;
+    const double length = sqrt(sum_sq3(dx, dy, dz));
+    if (!(length > 0.0) || !(length < INFINITY)) return;   // as k_dm_carve
+    const double ux = dx / length, uy = dy / length, uz = dz / length;
+    const double reach = fmax(step, fmin(length - trunc, max_ray));
+    const int no = off.n, cube = no * no * no;
+    const double off_lo = s_off[0], off_hi = s_off[no - 1];
+    const double kmax = (double)(kVoxOff - 1);
+    unsigned long long n_samples = 0, n_done = 0;
+    double distance = 0.0;
+    while (distance < reach) {
+        double t = distance * ux;
+        const double px = t + sx;
+        t = distance * uy;
+        const double py = t + sy;
+        t = distance * uz;
+        const double pz = t + sz;
+        ++n_samples;
+        // A. the box and its bricks
+        const double p3[3] = {px, py, pz};
+        long long b0[3];
+        int nb[3];
+        bool empty = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double t0 = p3[a] + off_lo, t1 = p3[a] + off_hi;
+            const double own = floor(p3[a] / voxel);
+            const double lo = fmax(fmin(floor(t0 / voxel), own), -kmax), hi = fmin(fmax(floor(t1 / voxel), own), kmax);
+            empty = empty || !(lo <= hi);   // no key of this axis fits (NaN included)
+            b0[a] = ((long long)lo + kVoxOff) >> kDmBrickShift;
+            nb[a] = empty ? 1 : (int)((((long long)hi + kVoxOff) >> kDmBrickShift) - b0[a]) + 1;
+        }
+        if (empty) {   // every lookup of the sample is skipped by vox_fits
+            ++n_done;
+            distance += step;
+            continue;
+        }
+        const int nbricks = nb[0] * nb[1] * nb[2];
+        const bool coarse = nbricks <= kDmBrickSlots;
+        if (coarse) {
+            group_sync();   // the slots of the previous sample have been read
+            bool any = false;
+            for (int c0 = 0; c0 < nbricks; c0 += kLanes) {
+                const int c = c0 + lane;
+                int32_t slot = -1;
+                if (c < nbricks) {
+                    const int ix = c % nb[0], iy = (c / nb[0]) % nb[1], iz = c / (nb[0] * nb[1]);
+                    const uint64_t bk = dm_brick_pack((uint64_t)(b0[0] + ix), (uint64_t)(b0[1] + iy), (uint64_t)(b0[2] + iz));
+                    const int64_t lb = key_lower_bound(bkeys, n_bricks, bk);
+                    if (lb < n_bricks && bkeys[lb] == bk) slot = (int32_t)lb;
+                    s_slot[g][c] = slot;
+                }
+                any = any || ((__ballot(slot >= 0) >> gbase) & gmask) != 0ull;
+            }
+            if (!any) {
+                ++n_done;
+                distance += step;
+                continue;
+            }
+            group_sync();   // the slots are visible to every lane of the group
+        }
+        // B. the test points
+        for (int c = lane; c <= cube; c += kLanes) {
+            double tx = px, ty = py, tz = pz;
+            if (c < cube) {
+                const int ix = c / (no * no), iy = (c / no) % no, iz = c % no;
+                tx = px + s_off[ix];
+                ty = py + s_off[iy];
+                tz = pz + s_off[iz];
+            }
+            const double kx = floor(tx / voxel), ky = floor(ty / voxel), kz = floor(tz / voxel);
+            if (!vox_fits(kx, ky, kz)) continue;   // cannot be in the map (NaN included)
+            if (c < cube) {
+                double cx = kx * voxel;
+                cx = cx + half_voxel;
+                double cy = ky * voxel;
+                cy = cy + half_voxel;
+                double cz = kz * voxel;
+                cz = cz + half_voxel;
+                const double d0 = tx - cx, d1 = ty - cy, d2 = tz - cz;
+                double u = d0 * d0;
+                double v = d1 * d1;
+                double q = u + v;
+                u = d2 * d2;
+                q = q + u;
+                if (!(sqrt(q) <= radius)) continue;
+            }
+            if (coarse) {
+                const long long fx = (long long)kx + kVoxOff, fy = (long long)ky + kVoxOff, fz = (long long)kz + kVoxOff;
+                const long long jx = (fx >> kDmBrickShift) - b0[0], jy = (fy >> kDmBrickShift) - b0[1],
+                                jz = (fz >> kDmBrickShift) - b0[2];
+                if (jx >= 0 && jx < nb[0] && jy >= 0 && jy < nb[1] && jz >= 0 && jz < nb[2]) {
+                    const int32_t slot = s_slot[g][((int)jz * nb[1] + (int)jy) * nb[0] + (int)jx];
+                    if (slot < 0) continue;
+                    const uint64_t w = bmask[8 * (size_t)slot + (size_t)(fz & 7)];
+                    if (!((w >> (((fy & 7) << 3) | (fx & 7))) & 1ull)) continue;
+                }
+            }
+            const uint64_t key = vox_pack(kx, ky, kz);
+            const int64_t lb = key_lower_bound(rkeys, n_res, key);
+            if (lb < n_res && rkeys[lb] == key) mark[lb] = 1u;
+        }
+        distance += step;
+    }
+    if (stats && lane == 0) {
+        atomicAdd(stats, n_samples);
+        atomicAdd(stats + 1, n_done);
+    }
+}
 // the marked voxels leave: keep[i] = !mark[i] and its exclusive scan give the positions of the rest; the erased keys go out
 // as int32 triples in ascending key order (rem_off = exclusive scan of mark; removed may be null)
 __global__ void k_dm_keep_flags(const uint32_t* __restrict__ mark, int64_t n, uint32_t* __restrict__ keep) {

@@ -2025,12 +2025,9 @@ class DenseMapBuilder:
         """Submap::carve for the dense map (Submap.cpp:146-157)."""
         if self.denseMap_.empty() or not (self.nScansInsertedDenseMap_ % self.carving_.carveSpaceEveryNscans_ == 1):
             return
-        reg, x = self.denseMap_._reg, scan.points_
-        try:
-            if self.carveInMapFrame:
-                x = _transform_points(mapToRangeSensor, x)
-            x = x[reg.dedup_voxels(x, self.denseMap_.voxelSize_)]
-            self.lastCarvedKeys_ = self.denseMap_.map.carve(x, mapToRangeSensor[:3, 3], self.carving_.params())
+        try:                              # transform, de-duplication, carve and erase in one call (reg_dense_map_carve_scan)
+            self.lastCarvedKeys_ = self.denseMap_.map.carve_scan(scan.points_, mapToRangeSensor[:3, 3], self.carving_.params(),
+                                                                 mapToRangeSensor if self.carveInMapFrame else None)
         except RegError as e:
             raise _translate(e) from None
 
@@ -2852,6 +2849,28 @@ class SubmapParameters:
     voxelExpansionFactor_: float = 2.5
 
 
+@dataclass
+class DenseMapBuilderParameters:
+    """What Submap::insertScanDenseMap reads of params_.denseMapBuilder_ and of the submap's croppers: the dense map's voxel
+    size, the dense-map cropper (a crop dict; its centre as given, zero is the reference), the colour range and the carving
+    parameters.  carveInMapFrame=False is the reference's oddity (icp.DenseMapBuilder)."""
+    mapVoxelSize_: float = 0.03
+    cropper: "dict | None" = None
+    colorCropper: "ColorRangeCropper | None" = None
+    carving_: "SpaceCarvingParameters | None" = None
+    carveInMapFrame: bool = False
+
+    def struct(self) -> "capi.SubmapsDenseParams":
+        _check_voxel_size(self.mapVoxelSize_)
+        carving = self.carving_ if self.carving_ is not None else SpaceCarvingParameters()
+        carving.check(self.mapVoxelSize_)
+        _check_crop(self.cropper, "cropper")
+        cc = self.colorCropper if self.colorCropper is not None else ColorRangeCropper()
+        return capi.default_submaps_dense_params(self.cropper, cc.rgbMin_, cc.rgbMax_, carving.params(),
+                                                 carve_every_n_scans=carving.carveSpaceEveryNscans_,
+                                                 carve_in_map_frame=bool(self.carveInMapFrame), voxel_size=self.mapVoxelSize_)
+
+
 class SubmapCollection:
     """o3d_slam::SubmapCollection on one resident capi.Submaps: every submap's map cloud, its occupancy keys and the overlap
     buffer stay on the device; the state machine runs inside the library (reg_submaps_insert_scan).  Built from a ScanToMapIcp
@@ -2861,8 +2880,10 @@ class SubmapCollection:
     def __init__(self, scanToMap: "ScanToMapIcp | None" = None, *, reg: "capi.Registration | None" = None,
                  params: "SubmapParameters | None" = None, mapVoxelSize_=0.03, mapBuilderCropper=None,
                  carving: "SpaceCarvingParameters | None" = None, hasNormals=True, hasCovariances=False, isUseInitialMap_=False,
-                 isCarvingEnabled_=False):
+                 isCarvingEnabled_=False, denseMapBuilder: "DenseMapBuilderParameters | None" = None):
+        """denseMapBuilder: every submap also keeps its dense map on the device (insertScanDenseMap, getDenseMapCopy)."""
         p = params if params is not None else SubmapParameters()
+        dense = denseMapBuilder.struct() if denseMapBuilder is not None else None
         c = carving if carving is not None else SpaceCarvingParameters()
         if scanToMap is not None and mapBuilderCropper is None:
             mapBuilderCropper = scanToMap.mapBuilderCropper
@@ -2889,7 +2910,9 @@ class SubmapCollection:
             self.submaps = capi.Submaps(self._reg, sp)
         except RegError as e:
             raise InvalidParameter(str(e)) from None      # "Num scan overlap has to be > 0" among them
-        self.lastInsert_ = None
+        if dense is not None:
+            self.submaps.enable_dense_maps(dense)
+        self.lastInsert_ = self.lastDenseInsert_ = None
 
     def close(self):
         self.submaps.close()
@@ -2935,6 +2958,28 @@ class SubmapCollection:
 
     def forceNewSubmapCreation(self):
         self.lastInsert_ = self.submaps.force_new_submap()
+
+    def insertScanDenseMap(self, submapId, rawScan, mapToRangeSensor, isPerformCarving=True) -> bool:
+        """Submap::insertScanDenseMap of submap submapId (one step of SlamWrapper::denseMapWorker): rawScan is a cloud with
+        optional normals and colours in the sensor frame.  Needs denseMapBuilder= at construction."""
+        T = _check_T(mapToRangeSensor, "mapToRangeSensor")
+        if T is None:
+            raise InvalidParameter("mapToRangeSensor is missing")
+        c = _cloud64(rawScan, "rawScan")
+        try:
+            self.lastDenseInsert_ = self.submaps.insert_scan_dense_map(int(submapId), c.points_, T, c.normals_, c.colors_,
+                                                                       bool(isPerformCarving))
+        except RegError as e:
+            raise _translate(e) from None
+        return True
+
+    def getDenseMapCopy(self, submapId) -> PointCloud:
+        """getSubmap(submapId).getDenseMapCopy().toPointCloud(): positions, normals and colours in ascending key order."""
+        try:
+            d = self.submaps.export_dense_submap(int(submapId), want_keys=False, want_counts=False)
+        except RegError as e:
+            raise _translate(e) from None
+        return PointCloud(d["xyz"], d["normals"], None, d["colors"])
 
     def computeFeatures(self, finishedSubmapIds, now_seconds, params: "PlaceRecognitionParameters | None" = None):
         """SubmapCollection::computeFeatures for [(id, stamp)]: per id Submap::computeFeatures on the device from the resident
@@ -3032,6 +3077,7 @@ class Mapper:
         self.initTime_ = 0
         self.nReferenceInitializations_ = 0
         self.lastBranch_ = None          # the name of the branch the last call ended in
+        self.registeredCloud_ = None     # RegisteredPointCloud of the last successful call: (submapId, rawScan, transform, time)
 
     def setExternalOdometryFrameToCloudFrameCalibration(self, T):
         self.calibration_, self.isCalibrationSet_ = _check_T(T, "calibration"), True
@@ -3069,6 +3115,17 @@ class Mapper:
         return value
 
     def addRangeMeasurement(self, rawScan, timestamp) -> bool:
+        """Mapper::addRangeMeasurement; a call that returns True also records registeredCloud_, what SlamWrapper.cpp:616-622
+        pushes for the dense-map worker: the submap that was active BEFORE the call, the raw scan, getMapToRangeSensor(time)
+        (the pose of the last measurement where the buffer has none at that time) and the time."""
+        active = self.submaps_.getActiveSubmapIdx() if hasattr(self.submaps_, "getActiveSubmapIdx") else None
+        ok = self._addRangeMeasurement(rawScan, timestamp)
+        if ok:
+            t, b = int(timestamp), self.mapToRangeSensorBuffer_
+            self.registeredCloud_ = (active, rawScan, b.lookup(t) if not b.empty() and b.has(t) else self.mapToRangeSensor_, t)
+        return ok
+
+    def _addRangeMeasurement(self, rawScan, timestamp) -> bool:
         p, timestamp = self.params_, int(timestamp)
         if not p.isUseInitialMap_ and not self.isCalibrationSet_:                 # Mapper.cpp:169-174
             return self._end("calibration_not_set", False)
